@@ -15,7 +15,13 @@ A *step* is one pass of the hot path over one synthetic batch:
            process group's stream, two steps in flight (the exchange of step k runs under the lookup of step k+1).
            Per-GPU work is fixed as N grows ("weak").
 
-``value`` = lookups of all ranks / wall time of the K timed steps, inputs resident in HBM.
+``value`` = lookups of all ranks / wall time of the K timed steps, inputs resident in HBM; ``ms_per_step`` = that wall time / K.
+
+A plain run does only what ``value`` needs: set-up, SETTLE_S of untimed headline steps and W warm-ups, the K timed steps, the
+outputs of the last step if ``--dump-outputs DIR`` is given, the JSON line.  Everything described below beside the headline (the
+uniform-index roofline run, the other output layout, backward and fwd + bwd steps, the CPU baseline, the bf16 / Criteo blocks; at
+N > 1 the lookup and the exchange alone, the exchange self-check, the other compute stream, the training step) runs with
+``--full`` only.
 
 ``roofline`` (dominant kernel = the forward lookup): ``frac`` comes from the launch whose ALGORITHMIC bytes ARE memory
 bytes -- the same kernel on the same tables under uniform indices (the roofline-defining run):
@@ -25,18 +31,19 @@ Zipf launch that ``value`` times is served partly by L2, so its algorithmic rate
 profile, labelled with the profile's file name -- counters are never collected inside this run, so ``traffic`` is null
 unless ``--traffic-from-profile`` is given, and then ``traffic_from_profile`` says where the number comes from.
 
-Also timed in the default N == 1 run (BASELINE configs[2]): the deterministic scatter-add backward (key sort + apply,
+Also timed in an N == 1 run with ``--full`` (BASELINE configs[2]): the deterministic scatter-add backward (key sort + apply,
 apply alone) and the whole fwd + bwd step, under Zipf and under uniform indices, and the forward writing the other output
 layout.  Order: the uniform block runs first (with 25 warm-up launches of its own), the timed headline steps (W warm-ups, K
-steps, as given) directly after it -- a block that runs first after the set-up phase rides a clock / power transient of
-3-4 %.  ``cpu_baseline`` times the reference's CPU engine (torch.nn.EmbeddingBag, pytorch_emb.py:37-45 protocol) in a child
-process on a bounded sample -- one table, the index sets of the request's first 8 tables in turn, 15 x 32 steps per mode -- and
+steps, as given) after it and after SETTLE_S of untimed headline steps -- a block that runs first after the set-up phase rides
+a clock / power transient of 3-4 %.  ``cpu_baseline`` times the reference's CPU engine (torch.nn.EmbeddingBag,
+pytorch_emb.py:37-45 protocol) in a child process on a bounded sample -- one table, the index sets of the request's first 8
+tables in turn, 15 x 32 steps per mode -- and
 the 1-core C oracle (rank 0, N == 1 only).  ``value`` there is the reference's own mode (all threads, autograd on) unless the
 container's cgroup CPU quota is smaller than that thread pool (16 CPUs on the round-3 GPU boxes, where torch sees 256 hardware
 threads): the reference's mode then measures the throttle and is reported beside a quota-sized pool of the same engine, which
 becomes ``value``; ``unstable`` flags a repeat spread of 25 % or more.
 
-N > 1 additionally reports the exchange alone (algBW / busBW with the reference's definitions), the lookup alone, the
+N > 1 with ``--full`` additionally reports the exchange alone (algBW / busBW with the reference's definitions), the lookup alone, the
 overlap efficiency max(lookup, exchange) / step, and a fwd + bwd training step with BOTH exchanges (pooled embeddings out,
 gradients back: dlrm.py:858-878 and :204-214) pipelined three batches deep.  ``--lookup-cus`` runs the compute stream on
 a CU-masked HIP stream so RCCL's kernels have CUs of their own (the lookup saturates the memory system with 192 of 256).
@@ -62,7 +69,9 @@ from param_amd.compute.pt.pytorch_emb import algorithmic_bytes  # noqa: E402
 from param_amd.indices import tbe_request  # noqa: E402
 
 ROOFLINE_WINDOW_S = 0.12  # device time the roofline-defining window spans at least
+SETTLE_S = 0.2  # device time of untimed headline steps before the W warm-ups (past the clock / power transient)
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6.3 TB/s is the measured copy ceiling
+DUMP_BUDGET_BYTES = 60 * 10**6  # --dump-outputs: at most this many bytes of array data
 _DT = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
 
 
@@ -71,6 +80,12 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement and check beside the headline (roofline, other layout, backward, CPU baseline, "
+                        "bf16 / Criteo blocks; N > 1: exchange alone, self-check, other compute stream, training step)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last one computed (the pooled embeddings; a fixed, seeded sample of "
+                        "the bags when larger than %d MB) to DIR/<name>.npy as float32" % (DUMP_BUDGET_BYTES // 10**6))
     p.add_argument("--workload", choices=["uniform-tables", "criteo"], default="uniform-tables",
                    help="criteo: the 26 MLPerf DLRM-v2 tables with per-table multi-hot pooling (BASELINE.json configs[4])")
     p.add_argument("--mixed-dims", action="store_true",
@@ -110,7 +125,8 @@ def parse():
     p.add_argument("--traffic-from-profile", action="store_true",
                    help="fill roofline.traffic from profiles/pmc_traffic.json (a committed rocprofv3 --pmc result, not this run)")
     p.add_argument("--only-headline", action="store_true",
-                   help="time nothing but the headline step (no uniform run, other layout, backward, CPU baseline): what the "
+                   help="N == 1 with --full: time nothing but the headline step (no uniform run, other layout, backward, CPU baseline), "
+                        "as a run without --full does: what the "
                         "rocprofv3 --kernel-trace --stats profiles under profiles/ run, so that the kernel's average there is the "
                         "average of one kind of launch")
     p.add_argument("--no-extra", action="store_true",
@@ -156,6 +172,26 @@ def time_steps_med(fn, steps, warmup, barrier, windows=3):
 
 
 SECONDARY_TIMING = "median of 3 windows (HIP events on the launch stream)"
+
+
+def dump_outputs(dirname: str, pooled: torch.Tensor, bag_axis: int) -> dict:
+    """--dump-outputs: the pooled embeddings of the last timed step -> DIR/pooled_embeddings.npy (float32).  When the whole output
+    exceeds DUMP_BUDGET_BYTES, the bags kept are a fixed sample (numpy RandomState(0), sorted): the same positions in every run
+    with the same arguments, so two builds compare output for output.  Returns the record the JSON line carries."""
+    import numpy as np
+
+    n_bags = pooled.shape[bag_axis]
+    per_bag = pooled.numel() // max(n_bags, 1) * 4
+    keep = min(n_bags, DUMP_BUDGET_BYTES // per_bag)
+    if keep < n_bags:
+        bags = np.sort(np.random.RandomState(0).choice(n_bags, keep, replace=False))
+        pooled = pooled.index_select(bag_axis, torch.from_numpy(bags).to(pooled.device))
+    arr = pooled.float().cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "pooled_embeddings.npy"), arr)
+    return {"dir": dirname, "files": {"pooled_embeddings.npy": list(arr.shape)},
+            "sample": (f"{keep} of {n_bags} bags (axis {bag_axis}), numpy RandomState(0) choice, sorted" if keep < n_bags
+                       else "all bags")}
 
 
 def masked_stream(n_cus: int, dev):
@@ -532,7 +568,8 @@ def main():
     if a.cpu_child:   # child of cpu_baseline(): prints one JSON object, nothing else of the bench runs
         print(json.dumps(cpu_child(json.loads(a.cpu_child))), flush=True)
         return
-    if a.only_headline:
+    lean = a.only_headline or not a.full      # N == 1: nothing but the headline step is timed
+    if lean:
         a.no_uniform = a.no_bwd = a.no_cpu_baseline = True
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU, rank 0 prints the one JSON
@@ -789,12 +826,33 @@ def main():
             torch.cuda.set_stream(plain_stream)
             a.lookup_cus = 0
 
+    # Untimed headline steps worth SETTLE_S of device time before the W warm-ups: right after the set-up phase the headline read 3 %
+    # low with W = 5 (21.5 against 22.2 G lookups/s with W = 100, or after the uniform block of --full) -- the clock / power transient
+    # above.  Step counts are max-over-ranks, so every rank runs the same collectives.
+    _, est = time_steps(rotating(step, zreqs), 5, 0, barrier)
+    est, = rank_max(est)
+    time_steps(rotating(step, zreqs), max(25, int(SETTLE_S / max(est, 1e-6))), 0, barrier)
+    if multi:
+        flush()
+    rot_k[0] = 0      # the last timed step's request is (W + K - 1) mod REQUESTS_ROTATED whatever ran before the window
     wall, dev_s = time_steps(rotating(step, zreqs), a.steps, a.warmup, barrier)   # the closing device sync covers exchanges still in flight
     if multi:
         flush()
+    dumped = None
+    if a.dump_outputs and rank == 0:     # before anything else of the run rewrites the output buffers
+        if not multi:
+            dumped = dump_outputs(a.dump_outputs, out, 0 if out.dim() == 2 else 1)
+        else:                             # what rank 0 received in the last step's exchange, in batch-parallel [B_local, sum D] order
+            s = (kstep[0] - 1) % 2
+            if rq is not None and rq.fwd_bits:
+                rq.dequantize(ex.q_recv[s], rq.fwd_bits, ex.recv[s])
+            blocks = [ex.recv_block(s, src) for src in range(world)]
+            if blocked:
+                blocks = [b.permute(1, 0, 2).reshape(B_local, -1) for b in blocks]
+            dumped = dump_outputs(a.dump_outputs, torch.cat(blocks, dim=1), 0)
     wall, dev_s = rank_max(wall, dev_s)
     single_s = None
-    if not multi and not a.only_headline:      # the same launch replaying request 0 only (the reference's protocol), beside the rotated value
+    if not multi and not lean:      # the same launch replaying request 0 only (the reference's protocol), beside the rotated value
         _, single_s = time_steps(step, n_sub, 2, barrier)
 
     wl = (f"batched EmbeddingBag(sum) fwd, {a.tables} tables x {R} rows x {D} dim {a.dtype}, batch {B_local}/rank, pool {L}, "
@@ -830,76 +888,81 @@ def main():
             "lookups_per_step": lookups_step_all, "requests_rotated": REQUESTS_ROTATED,
         },
     }
+    if dumped:
+        result["outputs"] = dumped
     if shared_gpu:
         result["config"]["shared_gpu_debug"] = f"{world} ranks on ONE GPU over gloo (PARAM_AMD_BENCH_SHARED_GPU=1): a flow check, not a measurement"
 
     # ---- roofline of the dominant kernel (forward lookup) ---------------------------------------------------
     if not multi:
         zipf_s = dev_s
-    else:  # time the lookups alone (no a2a) for the kernel roofline
+    elif a.full:  # time the lookups alone (no a2a) for the kernel roofline
         _, zipf_s = time_steps(lookup_only, n_sub, 2, barrier)
         zipf_s, = rank_max(zipf_s)
-    if a.alpha == 0.0:
-        ui, uo, uni_s, uni_steps = idx, off, zipf_s, (a.steps if not multi else n_sub)
-    zipf_alg = alg_bytes / zipf_s / 1e9
-    prof = {}
-    pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    key = f"T{T_loc}_R{R}_D{D}_B{B_local}_L{L}_a{a.alpha}_{a.dtype}" if a.workload != "criteo" else "criteo"
-    if world == 1 and os.path.exists(pmc_path):
-        try:
-            prof = json.load(open(pmc_path)).get(key, {})
-        except Exception:
-            prof = {}
-    roof = {"bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s", "kernel": "embbag_fwd_kernel",
-            "algorithmic_bytes_per_launch": alg_bytes, "bytes_per_lookup": alg_bytes / lookups_step_rank}
-    if uni_s is not None:
-        roof.update({
-            "achieved": alg_bytes / uni_s / 1e9, "frac": alg_bytes / uni_s / 1e9 / HBM_PEAK_GBPS,
-            "run": "uniform indices (alpha = 0): no reuse possible, algorithmic bytes == HBM bytes (the roofline-defining run); "
-                   "same kernel, tables and shape as the Zipf launch `value` times",
-            "avg_launch_s": uni_s, "launches_timed": uni_steps, "lookups_per_s_kernel": lookups_step_rank / uni_s,
-            "requests_rotated": REQUESTS_ROTATED if a.alpha != 0.0 else 1,
-            **({"single_request_frac": alg_bytes / uni_single_s / 1e9 / HBM_PEAK_GBPS, "single_request_avg_launch_s": uni_single_s,
-                "single_request_note": "the same launch replaying ONE request (the reference's protocol, pytorch_emb.py:48-69; what rounds 1-5 "
-                                       "reported): up to 256 MB of its rows can stay in the memory-side cache between launches"}
-               if uni_single_s else {})})
     else:
-        roof.update({"achieved": None, "frac": None, "run": "uniform run skipped (--no-uniform): no roofline fraction reported"})
-    roof["zipf"] = {
-        "avg_launch_s": zipf_s, "lookups_per_s_kernel": lookups_step_rank / zipf_s, "algorithmic_GBps": zipf_alg,
-        "requests_rotated": REQUESTS_ROTATED,
-        **({"single_request_avg_launch_s": single_s, "single_request_lookups_per_s": lookups_step_rank / single_s} if single_s else {}),
-        "alg_frac": zipf_alg / HBM_PEAK_GBPS,
-        "note": "hot rows are served by L2, so algorithmic bytes exceed HBM bytes: alg_frac is a cache-assisted rate, not a roofline fraction",
-        "fabric_side_frac": (prof["hbm_bytes_per_launch"] / zipf_s / 1e9 / HBM_PEAK_GBPS) if prof.get("hbm_bytes_per_launch") else None,
-        "fabric_side_frac_note": "L2 -> fabric bytes (Infinity-Cache hits included) of the committed profile / this run's launch time: an "
-                                 "UPPER bound on the HBM-side rate (what the 256 MB memory-side cache serves is in it); profile and window both rotate "
-                                 "REQUESTS_ROTATED requests since round 6",
-        "fabric_side_frac_source": ("profiles/pmc_traffic.json[%s] (rocprofv3 --pmc bytes of a committed profile) / this run's launch time" % key)
-        if prof.get("hbm_bytes_per_launch") else None}
-    # PMC counters are not collected inside a bench run (separate rocprofv3 --pmc passes: profiles/): `traffic` is the committed
-    # profile's number for this workload's uniform-index launch, labelled as such, or null when there is none
-    roof["traffic"] = None
-    if world == 1 and os.path.exists(pmc_path):
-        ukey = f"T{T_loc}_R{R}_D{D}_B{B_local}_L{L}_a0.0_{a.dtype}"
-        try:
-            uprof = json.load(open(pmc_path)).get(ukey, {})
-        except Exception:
-            uprof = {}
-        if uprof.get("hbm_bytes_per_launch"):
-            roof["traffic"] = uprof["hbm_bytes_per_launch"]
-            roof["traffic_label"] = ("L2 -> fabric bytes per launch (TCC_EA read / write requests; Infinity-Cache hits included: an upper "
-                                     "bound on HBM bytes) of a COMMITTED rocprofv3 --pmc profile of this launch, not of this run")
-            roof["traffic_from_profile"] = f"profiles/pmc_traffic.json[{ukey}] <- {uprof.get('source')}"
-            roof["traffic_over_algorithmic"] = uprof["hbm_bytes_per_launch"] / alg_bytes
-    result["roofline"] = roof
-    if uni_s is not None:   # kept for readers of round-1 lines
-        result["uniform"] = {"lookups_per_s": lookups_step_all / uni_s,
-                             "achieved_GBps": alg_bytes / uni_s / 1e9, "frac": alg_bytes / uni_s / 1e9 / HBM_PEAK_GBPS,
-                             "avg_launch_s": uni_s}
+        zipf_s = None       # N > 1 without --full: the lookup is not timed alone, no roofline
+    if zipf_s is not None:
+        if a.alpha == 0.0:
+            ui, uo, uni_s, uni_steps = idx, off, zipf_s, (a.steps if not multi else n_sub)
+        zipf_alg = alg_bytes / zipf_s / 1e9
+        prof = {}
+        pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        key = f"T{T_loc}_R{R}_D{D}_B{B_local}_L{L}_a{a.alpha}_{a.dtype}" if a.workload != "criteo" else "criteo"
+        if world == 1 and os.path.exists(pmc_path):
+            try:
+                prof = json.load(open(pmc_path)).get(key, {})
+            except Exception:
+                prof = {}
+        roof = {"bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s", "kernel": "embbag_fwd_kernel",
+                "algorithmic_bytes_per_launch": alg_bytes, "bytes_per_lookup": alg_bytes / lookups_step_rank}
+        if uni_s is not None:
+            roof.update({
+                "achieved": alg_bytes / uni_s / 1e9, "frac": alg_bytes / uni_s / 1e9 / HBM_PEAK_GBPS,
+                "run": "uniform indices (alpha = 0): no reuse possible, algorithmic bytes == HBM bytes (the roofline-defining run); "
+                       "same kernel, tables and shape as the Zipf launch `value` times",
+                "avg_launch_s": uni_s, "launches_timed": uni_steps, "lookups_per_s_kernel": lookups_step_rank / uni_s,
+                "requests_rotated": REQUESTS_ROTATED if a.alpha != 0.0 else 1,
+                **({"single_request_frac": alg_bytes / uni_single_s / 1e9 / HBM_PEAK_GBPS, "single_request_avg_launch_s": uni_single_s,
+                    "single_request_note": "the same launch replaying ONE request (the reference's protocol, pytorch_emb.py:48-69; what rounds 1-5 "
+                                           "reported): up to 256 MB of its rows can stay in the memory-side cache between launches"}
+                   if uni_single_s else {})})
+        else:
+            roof.update({"achieved": None, "frac": None, "run": "uniform run not made (no --full, or --no-uniform): no roofline fraction reported"})
+        roof["zipf"] = {
+            "avg_launch_s": zipf_s, "lookups_per_s_kernel": lookups_step_rank / zipf_s, "algorithmic_GBps": zipf_alg,
+            "requests_rotated": REQUESTS_ROTATED,
+            **({"single_request_avg_launch_s": single_s, "single_request_lookups_per_s": lookups_step_rank / single_s} if single_s else {}),
+            "alg_frac": zipf_alg / HBM_PEAK_GBPS,
+            "note": "hot rows are served by L2, so algorithmic bytes exceed HBM bytes: alg_frac is a cache-assisted rate, not a roofline fraction",
+            "fabric_side_frac": (prof["hbm_bytes_per_launch"] / zipf_s / 1e9 / HBM_PEAK_GBPS) if prof.get("hbm_bytes_per_launch") else None,
+            "fabric_side_frac_note": "L2 -> fabric bytes (Infinity-Cache hits included) of the committed profile / this run's launch time: an "
+                                     "UPPER bound on the HBM-side rate (what the 256 MB memory-side cache serves is in it); profile and window both rotate "
+                                     "REQUESTS_ROTATED requests since round 6",
+            "fabric_side_frac_source": ("profiles/pmc_traffic.json[%s] (rocprofv3 --pmc bytes of a committed profile) / this run's launch time" % key)
+            if prof.get("hbm_bytes_per_launch") else None}
+        # PMC counters are not collected inside a bench run (separate rocprofv3 --pmc passes: profiles/): `traffic` is the committed
+        # profile's number for this workload's uniform-index launch, labelled as such, or null when there is none
+        roof["traffic"] = None
+        if world == 1 and os.path.exists(pmc_path):
+            ukey = f"T{T_loc}_R{R}_D{D}_B{B_local}_L{L}_a0.0_{a.dtype}"
+            try:
+                uprof = json.load(open(pmc_path)).get(ukey, {})
+            except Exception:
+                uprof = {}
+            if uprof.get("hbm_bytes_per_launch"):
+                roof["traffic"] = uprof["hbm_bytes_per_launch"]
+                roof["traffic_label"] = ("L2 -> fabric bytes per launch (TCC_EA read / write requests; Infinity-Cache hits included: an upper "
+                                         "bound on HBM bytes) of a COMMITTED rocprofv3 --pmc profile of this launch, not of this run")
+                roof["traffic_from_profile"] = f"profiles/pmc_traffic.json[{ukey}] <- {uprof.get('source')}"
+                roof["traffic_over_algorithmic"] = uprof["hbm_bytes_per_launch"] / alg_bytes
+        result["roofline"] = roof
+        if uni_s is not None:   # kept for readers of round-1 lines
+            result["uniform"] = {"lookups_per_s": lookups_step_all / uni_s,
+                                 "achieved_GBps": alg_bytes / uni_s / 1e9, "frac": alg_bytes / uni_s / 1e9 / HBM_PEAK_GBPS,
+                                 "avg_launch_s": uni_s}
 
     # ---- N == 1: the same launches writing the other output layout ---------------------------------------------------
-    if not multi and len(set(model.dims)) == 1 and not a.only_headline:
+    if not multi and len(set(model.dims)) == 1 and not lean:
         from param_amd.embedding_bag import _TableSet, _fwd
 
         other = "bd" if a.layout == "tbd" else "tbd"
@@ -915,7 +978,7 @@ def main():
         del out_o, ts_o
 
     # ---- N > 1: the exchange alone, overlap, and the fwd + bwd training step ------------------------------------
-    if multi:
+    if multi and a.full:
         a2a_bytes = ex.bytes_per_rank()  # output tensor bytes per rank (reference memSize)
 
         def a2a_only():
@@ -1122,7 +1185,7 @@ def main():
             "value": None, "unit": "lookups/s", "cores": None, "kind": "port", "sample": "timed at N=1 only"}
 
     # ---- N == 1, default workload: the bf16 half of BASELINE configs[2] with all 64 tables, and configs[4]'s Criteo tables -----
-    if (rank == 0 and world == 1 and not multi and not a.only_headline and not a.no_extra and a.workload == "uniform-tables"
+    if (rank == 0 and world == 1 and not multi and not lean and not a.no_extra and a.workload == "uniform-tables"
             and a.dtype == "fp32" and a.tables == 64 and a.rows == 10_000_000):
         import gc
 

@@ -434,7 +434,7 @@ def test_bench_multi_rank_flow_on_one_gpu(n, extra, split, force, tmp_path):
         env["PARAM_AMD_BENCH_FORCE_CUS"] = force
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(_port()), os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "5", "--warmup", "2",
-           "--no-cpu-baseline", "--no-extra", "--batch", "2048"] + extra
+           "--full", "--no-cpu-baseline", "--no-extra", "--batch", "2048"] + extra
     r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -456,3 +456,37 @@ def test_bench_multi_rank_flow_on_one_gpu(n, extra, split, force, tmp_path):
     assert list(d)[-1] == "summary" and d["config"]["requests_rotated"] >= 4
     if "--mixed-dims" in extra:
         assert d["config"]["dim"] == {"16": 9, "32": 9, "64": 3, "128": 5}, d["config"]["dim"]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A run without --full times the headline step only and prints the headline keys; --dump-outputs writes the last timed step's
+    pooled embeddings, the same bits for the same arguments in two processes, and equal to the same tables and request looked up
+    once more (the request of step W + K - 1 is request (W + K - 1) mod 4 of the rotation)."""
+    import subprocess
+    import sys
+
+    import param_amd
+    from param_amd.indices import tbe_request
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    args = ["--steps", "6", "--warmup", "1", "--tables", "8", "--rows", "200000", "--batch", "1024"]
+    lines = []
+    for k in range(2):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args + ["--dump-outputs", str(tmp_path / f"d{k}")],
+                           cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines.append(json.loads(out[0]))
+    d = lines[0]
+    assert d["steps"] == 6 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "lookups/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32"
+    for key in ("bwd_scatter_add", "fwd_bwd_step", "other_layout", "uniform", "bf16_T64", "criteo"):
+        assert key not in d, key
+    assert d["cpu_baseline"] is None and d["outputs"]["files"] == {"pooled_embeddings.npy": [8, 1024, 128]}
+    a0, a1 = np.load(tmp_path / "d0" / "pooled_embeddings.npy"), np.load(tmp_path / "d1" / "pooled_embeddings.npy")
+    assert a0.dtype == np.float32 and a0.shape == (8, 1024, 128) and np.array_equal(a0, a1)
+    m = param_amd.BatchedEmbeddingBagMI355([200000] * 8, 128, device=DEV, layout="tbd", init="normal", seed=1000,
+                                       fused_update=False)
+    idx, off = tbe_request([200000] * 8, 1024, 20, alpha=1.05, device=DEV, seed=1 + 1000 * ((1 + 6 - 1) % 4))
+    assert np.array_equal(m.lookup(idx, off).cpu().numpy(), a0)

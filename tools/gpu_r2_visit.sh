@@ -8,12 +8,12 @@ mkdir -p $OUT
 cd $REPO
 (timeout 1500 python -m pytest tests -x -q -m gpu 2>&1 | tail -15) > $OUT/${TAG}_pytest.log
 (timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3) > $OUT/${TAG}_smoke.log
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench_line.err
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_line_run2.json 2> $OUT/${TAG}_bench_line_run2.err
-timeout 600 python bench.py --steps 20 --warmup 5 --dtype bf16 --no-cpu-baseline > $OUT/${TAG}_bench_line_bf16_T64.json 2> $OUT/${TAG}_bench_bf16.err
-timeout 600 python bench.py --steps 20 --warmup 5 --workload criteo --no-cpu-baseline > $OUT/${TAG}_bench_line_criteo.json 2> $OUT/${TAG}_bench_criteo.err
-timeout 600 python bench.py --dist-debug --tables 26 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_distdebug_26tables.json 2> $OUT/${TAG}_dd26.err
-timeout 600 python bench.py --dist-debug --workload criteo --steps 10 --warmup 3 --no-cpu-baseline --lookup-cus 224 > $OUT/${TAG}_distdebug_criteo_cu224.json 2> $OUT/${TAG}_ddc.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench_line.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench_line_run2.json 2> $OUT/${TAG}_bench_line_run2.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 --dtype bf16 --no-cpu-baseline > $OUT/${TAG}_bench_line_bf16_T64.json 2> $OUT/${TAG}_bench_bf16.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 --workload criteo --no-cpu-baseline > $OUT/${TAG}_bench_line_criteo.json 2> $OUT/${TAG}_bench_criteo.err
+timeout 600 python bench.py --full --dist-debug --tables 26 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/${TAG}_distdebug_26tables.json 2> $OUT/${TAG}_dd26.err
+timeout 600 python bench.py --full --dist-debug --workload criteo --steps 10 --warmup 3 --no-cpu-baseline --lookup-cus 224 > $OUT/${TAG}_distdebug_criteo_cu224.json 2> $OUT/${TAG}_ddc.err
 cd /tmp; export TMPDIR=/tmp
 # the dominant kernel alone: every embbag_fwd_kernel launch of these two runs is the headline launch (Zipf) / the
 # roofline-defining launch (uniform), so the kernel's average in the stats file is directly comparable with the bench line
@@ -23,7 +23,7 @@ timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_
     python $REPO/bench.py --steps 20 --warmup 5 --only-headline --alpha 0 > $OUT/${TAG}_headline_uniform_under_rocprofv3.json 2> $OUT/${TAG}_prof_uniform.err
 # the whole default command (forward both layouts and both distributions, backward, fwd+bwd): per-kernel totals
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_bench -o bench -- \
-    python $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_bench_line_under_rocprofv3.json 2> $OUT/${TAG}_prof_bench.err
+    python $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_bench_line_under_rocprofv3.json 2> $OUT/${TAG}_prof_bench.err
 i=0
 for c in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))

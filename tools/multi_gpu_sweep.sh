@@ -3,7 +3,7 @@
 # visit; the round-end driver runs bench.py --gpus N only).  One process per GPU under torch.distributed.run; the drivers open
 # their own TCP store, so --master-port given to a driver differs from the launcher's rendezvous port.
 #   DEVICE=cpu bash tools/multi_gpu_sweep.sh 2      dry run of the comms.py steps on gloo ranks (build container)
-# Steps: (1) bench.py --gpus N (the contract's line: lookups/s, exchange busBW vs the xGMI bound, overlap, self-check);
+# Steps: (1) bench.py --gpus N --full (lookups/s, exchange busBW vs the xGMI bound, overlap, self-check);
 # (2) the all-to-all sweep 8 B .. 256 MB, eager and as hipGraph replays; (3) one xGMI link: --pt2pt one2one 0 -> 1, and all links of
 # GPU pairs at once: --pt2pt pairwise; (4) configs[3]: dlrm.py 26 tables, batch 8192 per rank; (5) lookup || all-to-all overlap bench.
 N=${1:?ranks}
@@ -24,12 +24,12 @@ run() {  # run <name> <module or script> <args...>: N ranks under torch.distribu
 }
 drv="--master-ip 127.0.0.1 --device $DEVICE --backend $BACKEND"
 if [ "$DEVICE" != cpu ]; then
-  run bench bench.py --gpus "$N" --steps 50 --warmup 5
-  run bench_26 bench.py --gpus "$N" --tables 26 --steps 50 --warmup 5
-  run bench_criteo bench.py --gpus "$N" --workload criteo --steps 50 --warmup 5
-  run bench_criteo_mixed bench.py --gpus "$N" --workload criteo --mixed-dims --steps 50 --warmup 5
-  run bench_masked bench.py --gpus "$N" --lookup-cus 224 --steps 50 --warmup 5     # (the default picks the compute stream by a trial in the run:
-  run bench_unmasked bench.py --gpus "$N" --lookup-cus 0 --steps 50 --warmup 5     #  both fixed settings beside it, for the record)
+  run bench bench.py --full --gpus "$N" --steps 50 --warmup 5
+  run bench_26 bench.py --full --gpus "$N" --tables 26 --steps 50 --warmup 5
+  run bench_criteo bench.py --full --gpus "$N" --workload criteo --steps 50 --warmup 5
+  run bench_criteo_mixed bench.py --full --gpus "$N" --workload criteo --mixed-dims --steps 50 --warmup 5
+  run bench_masked bench.py --full --gpus "$N" --lookup-cus 224 --steps 50 --warmup 5     # (the default picks the compute stream by a trial in the run:
+  run bench_unmasked bench.py --full --gpus "$N" --lookup-cus 0 --steps 50 --warmup 5     #  both fixed settings beside it, for the record)
   big=256M; graphs="--graph-launches 10"
 else
   big=1M; graphs=""

@@ -2,7 +2,7 @@
 # Criteo forward: flat-walk kernel (default) vs the 8-bag tiles it replaces (PARAM_AMD_FWD_FLAT=0); tile target / cap sweep
 cd "$GRAFT_REPO_ROOT"; out=gpurun_out/r3_criteo_flat; mkdir -p $out
 run() {
-  env $1 timeout 300 python bench.py --workload criteo --no-bwd --no-cpu-baseline --steps 30 > $out/line.json 2> $out/err.txt
+  env $1 timeout 300 python bench.py --full --workload criteo --no-bwd --no-cpu-baseline --steps 30 > $out/line.json 2> $out/err.txt
   python - $out/line.json "$*" <<'PY'
 import json,sys
 try:

@@ -1,6 +1,6 @@
 cd "$GRAFT_REPO_ROOT"; out=gpurun_out/r3_shortbags; mkdir -p $out
 run() {
-  env $1 timeout 300 python bench.py --no-bwd --no-cpu-baseline --steps 30 ${@:2} > $out/line.json 2> $out/err.txt
+  env $1 timeout 300 python bench.py --full --no-bwd --no-cpu-baseline --steps 30 ${@:2} > $out/line.json 2> $out/err.txt
   python - $out/line.json "$*" <<'PY'
 import json,sys
 try:

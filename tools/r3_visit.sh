@@ -35,7 +35,7 @@ PY
       timeout 600 python tools/r3_bwd_exp.py --iters 10 --dtype bf16 --tables 64 --policies 0 > "$out/bwd_exp_bf16.jsonl" 2> "$out/bwd_exp_bf16.err"
       cat "$out/bwd_exp_bf16.jsonl"; tail -3 "$out/bwd_exp_bf16.err" ;;
     bench)
-      timeout 900 python bench.py > "$out/bench_line.json" 2> "$out/bench.err"
+      timeout 900 python bench.py --full > "$out/bench_line.json" 2> "$out/bench.err"
       python - "$out/bench_line.json" <<'PY'
 import json,sys
 r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -58,12 +58,12 @@ PY
       # RCCL group (26 tables, Criteo), rocprofv3 kernel stats of the headline launches and of the whole default command
       timeout 1500 python -m pytest tests -q -m gpu > "$out/pytest.log" 2>&1; tail -3 "$out/pytest.log"
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1; tail -1 "$out/smoke.log"
-      timeout 900 python bench.py > "$out/bench_line.json" 2> "$out/bench_line.err"
-      timeout 900 python bench.py > "$out/bench_line_run2.json" 2> "$out/bench_line_run2.err"
-      timeout 900 python bench.py --dtype bf16 --no-cpu-baseline > "$out/bench_line_bf16_T64.json" 2> "$out/bench_bf16.err"
-      timeout 900 python bench.py --workload criteo --no-cpu-baseline > "$out/bench_line_criteo.json" 2> "$out/bench_criteo.err"
-      timeout 900 python bench.py --dist-debug --tables 26 --no-cpu-baseline --steps 20 > "$out/distdebug_26tables.json" 2> "$out/dd26.err"
-      timeout 900 python bench.py --dist-debug --workload criteo --no-cpu-baseline --steps 20 > "$out/distdebug_criteo.json" 2> "$out/ddc.err"
+      timeout 900 python bench.py --full > "$out/bench_line.json" 2> "$out/bench_line.err"
+      timeout 900 python bench.py --full > "$out/bench_line_run2.json" 2> "$out/bench_line_run2.err"
+      timeout 900 python bench.py --full --dtype bf16 --no-cpu-baseline > "$out/bench_line_bf16_T64.json" 2> "$out/bench_bf16.err"
+      timeout 900 python bench.py --full --workload criteo --no-cpu-baseline > "$out/bench_line_criteo.json" 2> "$out/bench_criteo.err"
+      timeout 900 python bench.py --full --dist-debug --tables 26 --no-cpu-baseline --steps 20 > "$out/distdebug_26tables.json" 2> "$out/dd26.err"
+      timeout 900 python bench.py --full --dist-debug --workload criteo --no-cpu-baseline --steps 20 > "$out/distdebug_criteo.json" 2> "$out/ddc.err"
       for v in zipf:--only-headline uniform:--only-headline,--alpha,0 full:--no-cpu-baseline; do
         name=${v%%:*}; bargs=${v#*:}
         d=/tmp/r3off_$name; rm -rf "$d"
@@ -91,7 +91,7 @@ PY
       # fwd:<ENV=val>;<ENV=val>...   the headline forward (Zipf value, uniform roofline fraction, other layout) under an environment setting
       IFS=: read -r _ cfgs <<< "$what"
       for c in ${cfgs//;/ }; do
-        env $c timeout 300 python bench.py --no-bwd --no-cpu-baseline --steps 30 > "$out/fwd_${c}.json" 2> "$out/fwd.err"
+        env $c timeout 300 python bench.py --full --no-bwd --no-cpu-baseline --steps 30 > "$out/fwd_${c}.json" 2> "$out/fwd.err"
         python - "$out/fwd_${c}.json" "$c" <<'PY'
 import json,sys
 r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); o=r.get("other_layout",{})
@@ -103,7 +103,7 @@ PY
       IFS=: read -r _ cfgs <<< "$what"
       IFS=';' read -ra arr <<< "$cfgs"
       for c in "${arr[@]}"; do
-        timeout 300 python bench.py --workload criteo --no-bwd --no-cpu-baseline --steps 30 ${c//,/ } > "$out/criteofwd.json" 2> "$out/criteofwd.err"
+        timeout 300 python bench.py --full --workload criteo --no-bwd --no-cpu-baseline --steps 30 ${c//,/ } > "$out/criteofwd.json" 2> "$out/criteofwd.err"
         python - "$out/criteofwd.json" "$c" <<'PY'
 import json,sys
 r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -113,7 +113,7 @@ PY
     distdebug:*)
       # distdebug:<name>:<bench args with , for spaces>   the N>1 code path on a 1-rank RCCL group
       IFS=: read -r _ name bargs <<< "$what"
-      timeout 900 python bench.py --dist-debug --no-cpu-baseline ${bargs//,/ } > "$out/distdebug_${name}.json" 2> "$out/distdebug_${name}.err"
+      timeout 900 python bench.py --full --dist-debug --no-cpu-baseline ${bargs//,/ } > "$out/distdebug_${name}.json" 2> "$out/distdebug_${name}.err"
       python - "$out/distdebug_${name}.json" <<'PY'
 import json,sys
 r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -142,7 +142,7 @@ PY
       # criteo:<ENV=val>;<ENV=val>...   forward (+ backward with :bwd suffix on the step name) of the Criteo workload under an environment setting
       IFS=: read -r _ cfgs <<< "$what"
       for c in ${cfgs//;/ }; do
-        env $c timeout 300 python bench.py --workload criteo --no-cpu-baseline --steps 30 > "$out/criteo_${c}.json" 2> "$out/criteo.err"
+        env $c timeout 300 python bench.py --full --workload criteo --no-cpu-baseline --steps 30 > "$out/criteo_${c}.json" 2> "$out/criteo.err"
         python - "$out/criteo_${c}.json" "$c" <<'PY'
 import json,sys
 r=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

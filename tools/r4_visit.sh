@@ -8,10 +8,10 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 timeout 1800 python -m pytest tests -q -m gpu > "$out/pytest.log" 2>&1; grep -E "passed|failed" "$out/pytest.log" | tail -2
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1; tail -1 "$out/smoke.log"
-timeout 900 python bench.py > "$out/bench_line.json" 2> "$out/bench_line.err"
-timeout 900 python bench.py > "$out/bench_line_run2.json" 2> "$out/bench_line_run2.err"
-timeout 900 python bench.py --dist-debug --tables 26 --no-cpu-baseline --steps 20 > "$out/distdebug_26tables.json" 2> "$out/dd26.err"
-timeout 900 python bench.py --dist-debug --workload criteo --no-cpu-baseline --steps 20 > "$out/distdebug_criteo.json" 2> "$out/ddc.err"
+timeout 900 python bench.py --full > "$out/bench_line.json" 2> "$out/bench_line.err"
+timeout 900 python bench.py --full > "$out/bench_line_run2.json" 2> "$out/bench_line_run2.err"
+timeout 900 python bench.py --full --dist-debug --tables 26 --no-cpu-baseline --steps 20 > "$out/distdebug_26tables.json" 2> "$out/dd26.err"
+timeout 900 python bench.py --full --dist-debug --workload criteo --no-cpu-baseline --steps 20 > "$out/distdebug_criteo.json" 2> "$out/ddc.err"
 for v in zipf:--only-headline uniform:--only-headline,--alpha,0 full:--no-cpu-baseline,--no-extra; do
   name=${v%%:*}; bargs=${v#*:}
   d=/tmp/r4off_$name; rm -rf "$d"
