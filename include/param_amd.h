@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define PM_ABI_VERSION 7
+#define PM_ABI_VERSION 8
 
 typedef void* pm_stream_t;
 
@@ -257,6 +257,36 @@ typedef struct pm_sort_status {
 } pm_sort_status;
 int pm_embbag_sort_status(const pm_embbag_batch* op, int64_t max_rows, const void* workspace, pm_sort_status* out,
                           pm_stream_t stream);
+
+/*
+ * ABI v8.  Coalesced sparse gradient: per table t, the distinct rows its lookups hit and one fp32 gradient row per distinct row,
+ *     row_ids[t][k] ascending,   values[t][k * dims[t] .. + dims[t]) = sum_{j : indices[j] == row_ids[t][k]} psw[j] * grad(t, bag(j))
+ * (psw[j] = 1 without weights) -- what torch's EmbeddingBag(sparse=True) backward gives after .coalesce(), the gradient the reference's
+ * autograd backward (train/comms/pt/dlrm.py:1290-1296) produces for the sparse=True tables of pytorch_dist_backend.py:924, with U_t
+ * rows instead of a table-sized dense buffer.  Three stream-ordered calls on one caller-owned workspace, no allocation inside:
+ *   pm_embbag_sparse_grad_workspace  bytes of workspace (>= pm_embbag_bwd_sorted_workspace: the sort's, then a few words per
+ *                                    lookup and per tile of the relabelling), or a negative PM_ERR_* code;
+ *   pm_embbag_sort_indices           the complete one-phase key sort, on that workspace;
+ *   pm_embbag_sparse_grad_count      one pass over the sorted pairs: unique_counts[t] = U_t (device int64 [num_tables]), and every
+ *                                    sorted key is REWRITTEN IN PLACE from (t << tshift) | row to (t << tshift) | slot, slot = the
+ *                                    index of the row's run within its table (the row ids are kept in the workspace).  Until the
+ *                                    next sort, pm_embbag_sorted_pairs shows slots, not rows, and pm_embbag_bwd_sorted* refuse the
+ *                                    workspace (PM_ERR_INVALID); a second count on the same sort is refused too;
+ *   pm_embbag_sparse_grad            row_ids: device array [T] of int64[U_t]; values: device array [T] of float[U_t * dims[t]], 16-byte
+ *                                    aligned; both caller-allocated from unique_counts (a table with U_t = 0 is never touched).  Writes
+ *                                    the row ids, zeroes the value rows and runs the sorted apply of pm_embbag_bwd_sorted (alpha = 1,
+ *                                    fp32 destination) into them: values are bit-identical to that apply into a zeroed fp32 table, read
+ *                                    at row_ids[t] -- for any run length.  May be repeated (another `grad`) until the next sort.
+ * Same request rules, limits and refusals as the sorted backward (at most 1024 tables: split larger requests by tables, the calls are
+ * independent; num_indices and batch below 2^32; dims multiples of 4), checked before anything is launched.  The sort must keep rows
+ * ascending within a table: after pm_set_sort_tuning(1) the count call returns PM_ERR_UNSUPPORTED.  Gradients with respect to
+ * per_sample_weights are not computed.
+ */
+int64_t pm_embbag_sparse_grad_workspace(const pm_embbag_batch* op, int64_t max_rows);
+int pm_embbag_sparse_grad_count(const pm_embbag_batch* op, int64_t max_rows, void* workspace, int64_t workspace_bytes,
+                                int64_t* unique_counts, pm_stream_t stream);
+int pm_embbag_sparse_grad(const pm_embbag_batch* op, const float* grad, int64_t max_rows, void* workspace, int64_t workspace_bytes,
+                          int64_t* const* row_ids, float* const* values, pm_stream_t stream);
 
 /*
  * Fused backward + exact row-wise Adagrad (the optimizer the reference configures for its TBE ops,

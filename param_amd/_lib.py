@@ -13,7 +13,7 @@ import threading
 
 PM_F32, PM_BF16, PM_F16, PM_I32, PM_I64 = 0, 1, 2, 10, 11
 PM_OK, PM_ERR_INVALID, PM_ERR_UNSUPPORTED, PM_ERR_HIP, PM_ERR_INDEX = 0, -1, -2, -3, -4
-PM_ABI_VERSION = 7
+PM_ABI_VERSION = 8
 PM_WD_NONE, PM_WD_L2, PM_WD_DECOUPLE = 0, 1, 2
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -56,6 +56,9 @@ EXPORTED_SYMBOLS = (
     "pm_set_hybrid_tuning",
     "pm_set_hybrid_rest",
     "pm_set_hybrid_min_tiles",
+    "pm_embbag_sparse_grad_workspace",
+    "pm_embbag_sparse_grad_count",
+    "pm_embbag_sparse_grad",
 )
 
 
@@ -213,6 +216,12 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_set_hybrid_rest.argtypes = [i32]
     L.pm_set_hybrid_min_tiles.restype = ctypes.c_int
     L.pm_set_hybrid_min_tiles.argtypes = [i32]
+    L.pm_embbag_sparse_grad_workspace.restype = ctypes.c_int64
+    L.pm_embbag_sparse_grad_workspace.argtypes = [ctypes.POINTER(pm_embbag_batch), i64]
+    L.pm_embbag_sparse_grad_count.restype = ctypes.c_int
+    L.pm_embbag_sparse_grad_count.argtypes = [ctypes.POINTER(pm_embbag_batch), i64, vp, i64, vp, vp]
+    L.pm_embbag_sparse_grad.restype = ctypes.c_int
+    L.pm_embbag_sparse_grad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i64, vp, i64, vp, vp, vp]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]

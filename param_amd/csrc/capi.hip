@@ -570,6 +570,9 @@ int pm_embbag_bwd(const pm_embbag_batch* op, const float* grad, void* const* dst
 }
 #endif
 
+static const char* const kRelabelledMsg =
+    "the sort on this workspace was relabelled by pm_embbag_sparse_grad_count (its keys hold slots, not rows): sort the request again";
+
 static int sorted_args_ok(const pm_embbag_batch* op, int64_t max_rows) {
     if (max_rows < 1 || max_rows > (1LL << 31)) return fail(PM_ERR_INVALID, "max_rows must be in [1, 2^31]");
     if (op->num_indices >= (1LL << 32) || static_cast<int64_t>(op->batch) >= (1LL << 32))
@@ -709,7 +712,9 @@ int pm_embbag_bwd_sorted(const pm_embbag_batch* op, const float* grad, void* con
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_bwd_sorted");
     if (!workspace || workspace_bytes < static_cast<int64_t>(need))
         return fail(PM_ERR_INVALID, "workspace too small: need " + std::to_string(need) + " bytes");
-    if (pm::bwd_sorted_plan_check(p, max_rows, workspace, false) != 0)
+    const int pc = pm::bwd_sorted_plan_check(p, max_rows, workspace, false);
+    if (pc == 3) return fail(PM_ERR_INVALID, kRelabelledMsg);
+    if (pc != 0)
         return fail(PM_ERR_INVALID, "pm_embbag_sort_indices has not been called for this request on this workspace (same indices / offsets pointers, batch, bag slice and weights as the sort's)");
     p.io = const_cast<float*>(grad);
     p.tables = const_cast<const void* const*>(dst_tables);
@@ -743,6 +748,7 @@ int pm_embbag_bwd_sorted_adagrad_ex(const pm_embbag_batch* op, const float* grad
         return fail(PM_ERR_INVALID, "workspace too small: need " + std::to_string(need) + " bytes");
     {
         const int pc = pm::bwd_sorted_plan_check(p, max_rows, workspace, true);
+        if (pc == 3) return fail(PM_ERR_INVALID, kRelabelledMsg);
         if (pc == 2)
             return fail(PM_ERR_INVALID, "the request was sorted for a two-phase scatter-add apply; row-wise Adagrad needs "
                                         "pm_embbag_sort_indices (phases = 1)");
@@ -764,6 +770,94 @@ int pm_embbag_bwd_sorted_adagrad(const pm_embbag_batch* op, const float* grad, v
     pm_rowwise_adagrad opt = {lr, eps, 0.0f, PM_WD_NONE, 0, 0, 0};
     return pm_embbag_bwd_sorted_adagrad_ex(op, grad, tables, table_dtype, momentum, &opt, max_rows, workspace,
                                            workspace_bytes, stream);
+}
+
+// ---- ABI v8: coalesced sparse gradient (sparse_grad.hip) ----------------------------------------------------------------
+// The workspace is the sorted backward's followed by the relabelling's own few words per sorted position and per tile.
+static int sparse_common(const pm_embbag_batch* op, int64_t max_rows, pm::KParams& p, size_t& sorted_bytes, size_t& total_bytes) {
+    int rc = make_params(op, op ? op->weight_dtype : -1, p);
+    if (rc != PM_OK) return rc;
+    if ((rc = sorted_args_ok(op, max_rows)) != PM_OK) return rc;
+    // the apply writes fp32 rows: its row-width rule (dims multiples of 4) is the fp32 destination's
+    pm::KParams chk;
+    if ((rc = make_params(op, PM_F32, chk)) != PM_OK) return rc;
+    hipError_t h = pm::sorted_workspace_bytes(p, max_rows, op->max_dim, sorted_bytes);
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_sparse_grad_workspace");
+    sorted_bytes = (sorted_bytes + 255) / 256 * 256;
+    total_bytes = sorted_bytes + pm::sparse_grad_extra_bytes(p.N, p.T);
+    return PM_OK;
+}
+
+static int sparse_pairs_fail(int pi) {
+    switch (pi) {
+        case 1: return fail(PM_ERR_INVALID, "pm_embbag_sort_indices has not been called for this request on this workspace (same indices / "
+                                            "offsets pointers, batch, bag slice and weights as the sort's)");
+        case 2: return fail(PM_ERR_UNSUPPORTED, "the sparse gradient needs the complete one-phase segmented sort: sort with pm_embbag_sort_indices "
+                                                "(sort_impl 0)");
+        case 3: return fail(PM_ERR_UNSUPPORTED, "the sparse gradient needs rows in ascending order within a table: sort mode 1 orders them by "
+                                                "their low digit first (pm_set_sort_tuning 0, 2 or 3)");
+        case 4: return fail(PM_ERR_INVALID, "pm_embbag_sparse_grad_count has been called for this sort already: sort the request again");
+        default: return fail(PM_ERR_INVALID, "pm_embbag_sparse_grad needs pm_embbag_sparse_grad_count on this sort first");
+    }
+}
+
+int64_t pm_embbag_sparse_grad_workspace(const pm_embbag_batch* op, int64_t max_rows) {
+    pm::KParams p;
+    size_t sorted_bytes = 0, total = 0;
+    const int rc = sparse_common(op, max_rows, p, sorted_bytes, total);
+    if (rc != PM_OK) return rc;
+    return static_cast<int64_t>(total);
+}
+
+int pm_embbag_sparse_grad_count(const pm_embbag_batch* op, int64_t max_rows, void* workspace, int64_t workspace_bytes,
+                                int64_t* unique_counts, pm_stream_t stream) {
+    pm::KParams p;
+    size_t sorted_bytes = 0, total = 0;
+    int rc = sparse_common(op, max_rows, p, sorted_bytes, total);
+    if (rc != PM_OK) return rc;
+    if (!unique_counts) return fail(PM_ERR_INVALID, "unique_counts is NULL");
+    if (p.N == 0 || p.bag_count == 0) {      // nothing was sorted: every table is empty
+        const hipError_t h = hipMemsetAsync(unique_counts, 0, sizeof(int64_t) * static_cast<size_t>(p.T), static_cast<hipStream_t>(stream));
+        if (h != hipSuccess) return hip_fail(h, "pm_embbag_sparse_grad_count");
+        return PM_OK;
+    }
+    if (!workspace || workspace_bytes < static_cast<int64_t>(total))
+        return fail(PM_ERR_INVALID, "workspace too small: need " + std::to_string(total) + " bytes (pm_embbag_sparse_grad_workspace)");
+    pm::SparsePairs sp;
+    const int pi = pm::sparse_grad_pairs(p, max_rows, op->max_dim, workspace, true, sp);
+    if (pi != 0) return sparse_pairs_fail(pi);
+    const hipError_t h = pm::sparse_grad_count(sp, p.T, p.N, static_cast<char*>(workspace) + sorted_bytes, unique_counts,
+                                               static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_sparse_grad_count launch");
+    return PM_OK;
+}
+
+int pm_embbag_sparse_grad(const pm_embbag_batch* op, const float* grad, int64_t max_rows, void* workspace, int64_t workspace_bytes,
+                          int64_t* const* row_ids, float* const* values, pm_stream_t stream) {
+    pm::KParams p;
+    size_t sorted_bytes = 0, total = 0;
+    int rc = sparse_common(op, max_rows, p, sorted_bytes, total);
+    if (rc != PM_OK) return rc;
+    if (p.N == 0 || p.bag_count == 0) return PM_OK;
+    if (!grad || !row_ids || !values) return fail(PM_ERR_INVALID, "grad / row_ids / values is NULL");
+    if (!workspace || workspace_bytes < static_cast<int64_t>(total))
+        return fail(PM_ERR_INVALID, "workspace too small: need " + std::to_string(total) + " bytes (pm_embbag_sparse_grad_workspace)");
+    pm::SparsePairs sp;
+    const int pi = pm::sparse_grad_pairs(p, max_rows, op->max_dim, workspace, false, sp);
+    if (pi != 0) return sparse_pairs_fail(pi);
+    hipError_t h = pm::sparse_grad_rows(sp, p.T, p.N, static_cast<const char*>(workspace) + sorted_bytes, op->dims, row_ids, values,
+                                        static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_sparse_grad launch");
+    // the sorted apply, unchanged: fp32 destination, alpha = 1, into the zeroed compact rows (row = slot)
+    pm::KParams q;
+    if ((rc = make_params(op, PM_F32, q)) != PM_OK) return rc;
+    q.io = const_cast<float*>(grad);
+    q.tables = reinterpret_cast<const void* const*>(values);
+    q.alpha = 1.0f;
+    if (g_nt_loads.load() < 0) q.nt_loads = kDefaultRowPolicy;
+    h = pm::bwd_sorted_apply(q, max_rows, PM_F32, op->max_dim, workspace, nullptr, nullptr, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_sparse_grad apply launch");
+    return PM_OK;
 }
 
 int pm_dlrm_regroup(const int64_t* lengths, const int64_t* indices, int32_t world_size, int32_t num_tables,

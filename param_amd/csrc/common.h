@@ -354,6 +354,22 @@ void set_hybrid_tuning(int enable, uint32_t spin_cap);            // hybrid back
 void set_hybrid_min_tiles(int tiles);                             // ... offered from this many bag-major workgroups on: -1 default (1024)
 void set_hybrid_rest(int mode);                                   // ... its left-overs finished in LDS (hyb_rest_kernel): -1 default, 0 / 1
 hipError_t sort_status(const KParams& p, int64_t max_rows, int max_dim, const void* workspace, hipStream_t stream, uint32_t out[6]);
+// coalesced sparse gradient (ABI v8, sparse_grad.hip): the sorted pairs of the last sort on a workspace, relabelled in place from
+// (t << tshift) | row to (t << tshift) | slot by the count call, then applied into compact [U_t, D_t] value buffers
+struct SparsePairs {
+    void* keys;              // the sorted keys (uint32 / uint64) inside the workspace
+    int key_bytes;
+    int tshift;
+    const SegDesc* desc;     // the sort's per-table segments (out_start, count)
+};
+// embbag_bwd_sorted.hip: 0 ok; 1 no sort of this request on the workspace; 2 not a complete one-phase segmented sort; 3 the sort's
+// order is not ascending within a table (sort mode 1); 4 counting, but the sort was relabelled already; 5 applying, but it was not
+int sparse_grad_pairs(const KParams& p, int64_t max_rows, int max_dim, const void* workspace, bool counting, SparsePairs& out);
+int64_t sparse_grad_max_tiles(int64_t n, int T);
+size_t sparse_grad_extra_bytes(int64_t n, int T);   // behind the sorted backward's workspace: tile plan, tile counts, run rows
+hipError_t sparse_grad_count(const SparsePairs& sp, int T, int64_t n, void* extra, int64_t* unique_counts, hipStream_t stream);
+hipError_t sparse_grad_rows(const SparsePairs& sp, int T, int64_t n, const void* extra, const int32_t* dims, int64_t* const* row_ids,
+                            float* const* values, hipStream_t stream);
 
 // DLRM input redistribution (dlrm_regroup.hip)
 hipError_t launch_dlrm_regroup(const int64_t* lengths, const int64_t* indices, int W, int F, int64_t B,

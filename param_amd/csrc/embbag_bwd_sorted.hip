@@ -290,6 +290,7 @@ struct SortPlan {
     int hyb;             // hybrid backward: 0 not launched for this sort, else the `allow` value its kernels ran with (part B of the
                          // sort then runs inside the apply call, after the bag-major kernel)
     bool applied;        // an apply has been issued for this sort (a deferred sort's pairs exist only then)
+    bool relabelled;     // pm_embbag_sparse_grad_count rewrote the keys to (table, slot): only the sparse-gradient apply may follow
     // what the sort was issued for: the apply must follow with the same request on the same workspace
     const void* indices;
     const void* offsets;
@@ -315,6 +316,7 @@ SortPlan make_plan(const KParams& p, int64_t max_rows, int64_t fixed_pooling, in
     g.mode = sort_mode_knob();
     g.hyb = 0;
     g.applied = false;
+    g.relabelled = false;
     if (g.v2) {
         // one plan for every request: the device establishes segments, per-table pooling and (for slices) the pair count
         g.H = 1;
@@ -568,7 +570,37 @@ int bwd_sorted_plan_check(const KParams& p, int64_t max_rows, const void* worksp
         g.sliced != !(p.bag_begin == 0 && p.bag_count == p.B) || g.indices != p.indices || g.offsets != p.offsets || g.B != p.B ||
         g.bag_begin != p.bag_begin || g.bag_count != p.bag_count)
         return 1;
+    if (g.relabelled) return 3;
     if (adagrad && g.H != 1) return 2;
+    return 0;
+}
+
+int sparse_grad_pairs(const KParams& p, int64_t max_rows, int max_dim, const void* workspace, bool counting, SparsePairs& out) {
+    SortPlan g;
+    {
+        std::lock_guard<std::mutex> lock(g_plan_mutex);
+        auto it = g_plans.find(workspace);
+        if (it == g_plans.end()) return 1;
+        SortPlan& r = it->second;
+        if (r.n != p.N || r.T != p.T || r.rbits != bits_for(max_rows) || r.weighted != (p.psw != nullptr) ||
+            r.sliced != !(p.bag_begin == 0 && p.bag_count == p.B) || r.indices != p.indices || r.offsets != p.offsets || r.B != p.B ||
+            r.bag_begin != p.bag_begin || r.bag_count != p.bag_count)
+            return 1;
+        if (!r.v2 || r.hyb || r.H != 1) return 2;
+        if (r.mode == 1) return 3;
+        if (counting && r.relabelled) return 4;
+        if (!counting && !r.relabelled) return 5;
+        r.relabelled = true;
+        g = r;
+    }
+    SortWs ws;
+    if (ws_layout(const_cast<void*>(workspace), p.N, p.T, ws_key_bytes(p, max_rows), ws_kbits_sort(p, max_rows), g.weighted, max_dim, ws) !=
+        hipSuccess)
+        return 1;
+    out.keys = g.in_b ? ws.keys_b : ws.keys_a;
+    out.key_bytes = g.key_bytes;
+    out.tshift = g.tshift;
+    out.desc = seg_sort_desc(ws.temp, static_cast<size_t>(p.N), p.T);
     return 0;
 }
 

@@ -429,6 +429,76 @@ def _adagrad(ts: _TableSet, grad, indices, offsets, B, mom_ptrs_dev, lr: float, 
                                                  ws.data_ptr(), ws.numel(), _stream_ptr()))
 
 
+_SPARSE_MAX_TABLES = 1024      # kSegSortMaxTables: the sorted path's limit per call; larger requests are split by tables
+
+
+def _sparse_grad_call(ts: _TableSet, op, grad, max_rows: int, dims: Sequence[int]):
+    """sort + count + (one synchronisation) + exact allocation + relabelled apply of ONE request of at most 1024 tables"""
+    L = _lib.load()
+    need = L.pm_embbag_sparse_grad_workspace(ctypes.byref(op), max_rows)
+    if need < 0:
+        _lib.check(int(need))
+    ws = getattr(ts, "_ws", None)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(int(need), dtype=torch.uint8, device=ts.device)
+        ts._ws = ws
+    s = _stream_ptr()
+    _lib.check(L.pm_embbag_sort_indices(ctypes.byref(op), max_rows, ws.data_ptr(), ws.numel(), s))
+    counts = torch.empty(len(dims), dtype=torch.int64, device=ts.device)
+    _lib.check(L.pm_embbag_sparse_grad_count(ctypes.byref(op), max_rows, ws.data_ptr(), ws.numel(), counts.data_ptr(), s))
+    U = counts.tolist()                                   # the call's one host synchronisation
+    rows = [torch.empty(u, dtype=torch.int64, device=ts.device) for u in U]
+    vals = [torch.empty((u, d), dtype=torch.float32, device=ts.device) for u, d in zip(U, dims)]
+    r_ptrs = torch.tensor([r.data_ptr() for r in rows], dtype=torch.int64, device=ts.device)
+    v_ptrs = torch.tensor([v.data_ptr() for v in vals], dtype=torch.int64, device=ts.device)
+    _lib.check(L.pm_embbag_sparse_grad(ctypes.byref(op), grad.data_ptr(), max_rows, ws.data_ptr(), ws.numel(), r_ptrs.data_ptr(),
+                                       v_ptrs.data_ptr(), s))
+    return list(zip(rows, vals))
+
+
+def _sparse_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, bag_begin=0, bag_count=None):
+    """Coalesced sparse gradient (``pm_embbag_sparse_grad*``): a list of T ``(rows_t, values_t)`` -- rows_t the distinct rows table t's
+    lookups hit (ascending int64), values_t ``[U_t, D_t]`` fp32, ``values_t[k] = sum_{j: idx_j = rows_t[k]} w_j * grad[t, bag(j)]`` in
+    the sorted backward's order.  Synchronises once per request of at most 1024 tables (to size the outputs)."""
+    _require_device(grad, "grad")
+    _, _, shape = ts.out_desc(B)
+    if grad.dtype != torch.float32 or tuple(grad.shape) != tuple(shape):
+        raise ValueError(f"grad must be float32 of shape {shape}")
+    grad = grad.contiguous()
+    op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
+    op.fixed_pooling = 0
+    if ts.T <= _SPARSE_MAX_TABLES:
+        return _sparse_grad_call(ts, op, grad, max(ts.rows), ts.dims)
+    # more tables than one sorted call takes: independent requests of at most 1024 tables -- the lookups of tables [t0, t1) are one
+    # contiguous range of the table-major index array, their offsets rebased to it; the gradient and its addressing stay the full
+    # request's (out_offsets of those tables, the stride and any blocking of the whole layout)
+    T = ts.T
+    cuts = list(range(0, T, _SPARSE_MAX_TABLES)) + [T]
+    n = indices.numel()
+    if B == 0:
+        starts = [0] * len(cuts)
+    else:
+        starts = offsets[[c * B for c in cuts[:-1]]].tolist() + [n]
+    out_off = ts.out_desc(B)[0]
+    res = []
+    for t0, t1, n0, n1 in zip(cuts[:-1], cuts[1:], starts[:-1], starts[1:]):
+        sub = _lib.pm_embbag_batch.from_buffer_copy(op)
+        sub_off = (offsets[t0 * B:t1 * B] - n0).contiguous()
+        sub.num_tables = t1 - t0
+        sub.max_dim, sub.min_dim = max(ts.dims[t0:t1]), min(ts.dims[t0:t1])
+        sub.num_indices = n1 - n0
+        sub.tables = ts.d_ptrs[t0:t1].data_ptr()
+        sub.rows = ts.d_rows[t0:t1].data_ptr()
+        sub.dims = ts.d_dims[t0:t1].data_ptr()
+        sub.out_offsets = out_off[t0:t1].data_ptr()
+        sub.indices = indices.data_ptr() + n0 * indices.element_size()
+        sub.offsets = sub_off.data_ptr()
+        if psw is not None:
+            sub.per_sample_weights = psw.data_ptr() + n0 * psw.element_size()
+        res += _sparse_grad_call(ts, sub, grad, max(ts.rows[t0:t1]), ts.dims[t0:t1])
+    return res
+
+
 class _DenseGradFn(torch.autograd.Function):
     """forward = batched lookup; backward = scatter-add into a dense fp32 weight.grad
     (torch ``sparse=False`` semantics, aten::_embedding_bag_dense_backward)."""
@@ -454,12 +524,32 @@ class _DenseGradFn(torch.autograd.Function):
         return dW.to(m.weight.dtype), None, None, None, None
 
 
+class _SparseGradFn(_DenseGradFn):
+    """the same forward; backward = the coalesced sparse gradient (``pm_embbag_sparse_grad``): ``weight.grad`` is a coalesced
+    sparse COO tensor of the U distinct rows looked up, torch ``sparse=True`` semantics (values in the weight's dtype)."""
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        indices, offsets, psw = ctx.saved_tensors
+        m = ctx.module
+        w = m.weight
+        ((rows, vals),) = _sparse_grad(m._tables(), grad_out.contiguous(), indices, offsets, ctx.B, psw if ctx.has_psw else None)
+        g = torch.sparse_coo_tensor(rows[None], vals.to(w.dtype), tuple(w.shape), is_coalesced=True)
+        # autograd's accumulation into .grad keeps these very index / value tensors but drops the coalesced flag: the module's
+        # post-accumulate hook sets it again when .grad still holds them (an accumulated sum of two steps is torch's own result)
+        m._sparse_mark = (g._values().data_ptr(), g._indices().data_ptr())
+        return g, None, None, None, None
+
+
 class EmbeddingBagMI355(nn.Module):
     """``torch.nn.EmbeddingBag(num_embeddings, embedding_dim, mode="sum")`` on MI355X HIP kernels.
 
     Same call contract as the module the reference builds at pytorch_emb.py:179 and
     pytorch_dist_backend.py:924: ``forward(indices[N], offsets[B]) -> float32[B, D]``,
     ``include_last_offset=False``; ``.weight`` is an ``nn.Parameter`` (N(0,1) init like torch).
+    ``sparse=True``: ``weight.grad`` is a sparse COO tensor, as torch's, but coalesced -- one row per distinct index looked up
+    (``U x D`` values, not torch's ``N x D``); torch's sparse-capable optimizers (``SparseAdam``, ``SGD``, ``Adagrad``) take it.
+    The backward then synchronises once (to size the gradient), as ``coalesce()`` does.
     """
 
     def __init__(self, num_embeddings: int, embedding_dim: int, mode: str = "sum", sparse: bool = False,
@@ -478,6 +568,15 @@ class EmbeddingBagMI355(nn.Module):
             w = _weight
         self.weight = nn.Parameter(w)
         self._ts: Optional[_TableSet] = None
+        self._sparse_mark = None
+        if sparse:
+            self.weight.register_post_accumulate_grad_hook(self._mark_coalesced)
+
+    def _mark_coalesced(self, p: torch.Tensor) -> None:
+        g, mark = p.grad, self._sparse_mark
+        self._sparse_mark = None
+        if g is not None and g.is_sparse and mark == (g._values().data_ptr(), g._indices().data_ptr()):
+            g._coalesced_(True)
 
     def _tables(self) -> _TableSet:
         w = self.weight.data
@@ -493,14 +592,14 @@ class EmbeddingBagMI355(nn.Module):
         if not w.is_cuda:
             _require_device(w, "EmbeddingBagMI355.weight")
         if w.requires_grad and torch.is_grad_enabled():
-            return _DenseGradFn.apply(w, self, indices, offsets, per_sample_weights)
+            return (_SparseGradFn if self.sparse else _DenseGradFn).apply(w, self, indices, offsets, per_sample_weights)
         ts = self._ts
         if ts is None or ts.ptrs[0] != w.data_ptr():
             ts = self._tables()
         return _fwd(ts, indices, offsets, offsets.numel(), per_sample_weights)
 
     def extra_repr(self) -> str:
-        return f"{self.num_embeddings}, {self.embedding_dim}, mode=sum, dtype={self.weight.dtype}"
+        return f"{self.num_embeddings}, {self.embedding_dim}, mode=sum, dtype={self.weight.dtype}" + (", sparse=True" if self.sparse else "")
 
 
 class _FusedUpdateFn(torch.autograd.Function):
@@ -710,6 +809,18 @@ class BatchedEmbeddingBagMI355(nn.Module):
         d_ptrs = torch.tensor([o.data_ptr() for o in outs], dtype=torch.int64, device=ts.device)
         _bwd(ts, grad, indices, offsets, B, d_ptrs, torch.float32, 1.0, per_sample_weights, method=method)
         return outs
+
+    def sparse_grad(self, grad, indices, offsets, per_sample_weights=None, batch: Optional[int] = None, bag_begin=0,
+                    bag_count=None):
+        """Coalesced sparse gradients of the tables, without a dense buffer: a list of T ``(rows_t, values_t)`` pairs -- ``rows_t``
+        the distinct rows table t's lookups (of the bag slice) hit, ascending int64; ``values_t`` fp32 ``[U_t, D_t]``,
+        ``values_t[k] = sum_{j: idx_j = rows_t[k]} psw[j] * grad[t, bag(j)]`` summed in the sorted backward's order (bit-identical
+        to ``sort_indices`` + ``scatter_add_(alpha=1, presorted=True)`` into zeroed fp32 tables, read at ``rows_t``).  A table with
+        no lookups gives empty tensors.  ``grad`` has the shape ``scatter_add_`` takes for the module's layout.  The call
+        synchronises once (to read the U_t and allocate exactly), as torch's ``coalesce()`` does -- once per 1024 tables for larger
+        requests, which are split into independent calls.  Gradients with respect to ``per_sample_weights`` are not computed."""
+        B = self._batch_of(offsets, indices) if batch is None else batch
+        return _sparse_grad(self._tables(), grad, indices, offsets, B, per_sample_weights, bag_begin, bag_count)
 
     def check(self, indices, offsets, per_sample_weights=None, batch: Optional[int] = None) -> None:
         B = self._batch_of(offsets, indices) if batch is None else batch
