@@ -84,6 +84,30 @@ static inline uint16_t f32_to_bf16(float f) {
     return (uint16_t)(u >> 16);
 }
 
+/* round-to-nearest-even fp32 -> fp16: subnormal results, overflow to infinity, NaN kept quiet */
+static inline uint16_t f32_to_f16(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
+    const uint32_t a = u & 0x7fffffffu;
+    if (a > 0x7f800000u) return (uint16_t)(sign | 0x7e00u | ((a >> 13) & 0x3ffu));
+    if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u); /* >= 65520 (the midpoint above 65504, a tie to even) and Inf */
+    if (a >= 0x38800000u) {                                  /* normal in fp16: rebias, round the 13 dropped bits */
+        uint32_t h = a - (112u << 23);
+        h += 0xfffu + ((h >> 13) & 1u);
+        return (uint16_t)(sign | (h >> 13));
+    }
+    if (a < 0x33000000u) return sign;                        /* below 2^-25: zero (2^-25 itself is a tie, handled below) */
+    /* subnormal in fp16: the result counts units of 2^-24 */
+    const uint32_t e = a >> 23;                              /* 102 .. 112 */
+    const uint32_t m = (a & 0x7fffffu) | 0x800000u;          /* value = m * 2^(e - 150) */
+    const uint32_t shift = 126u - e;                         /* 14 .. 24 */
+    const uint32_t half = 1u << (shift - 1), rem = m & ((1u << shift) - 1u);
+    uint32_t q = m >> shift;
+    if (rem > half || (rem == half && (q & 1u))) ++q;        /* q == 0x400 is the smallest normal: the bits line up */
+    return (uint16_t)(sign | q);
+}
+
 static inline float load_elem(const void* W, int dtype, int64_t i) {
     switch (dtype) {
         case ORACLE_F32: return ((const float*)W)[i];
@@ -207,6 +231,18 @@ int oracle_embbag_bwd_bf16(uint16_t* dst, float* scratch, int64_t rows, int32_t 
     return ORACLE_OK;
 }
 
+/* the same for an fp16 table (rounding: f32_to_f16, nearest even, once per element) */
+int oracle_embbag_bwd_f16(uint16_t* dst, float* scratch, int64_t rows, int32_t dim, const int64_t* idx, int64_t N,
+                          const int64_t* off, int64_t B, const float* psw, const float* grad, int64_t grad_stride,
+                          float alpha) {
+    const int64_t n = rows * (int64_t)dim;
+    for (int64_t i = 0; i < n; ++i) scratch[i] = f16_to_f32(dst[i]);
+    int rc = oracle_embbag_bwd_f32(scratch, rows, dim, idx, N, off, B, psw, grad, grad_stride, alpha);
+    if (rc != ORACLE_OK) return rc;
+    for (int64_t i = 0; i < n; ++i) dst[i] = f32_to_f16(scratch[i]);
+    return ORACLE_OK;
+}
+
 /*
  * Fused backward + exact row-wise Adagrad on an fp32 table (the optimizer the reference configures
  * for its TBE ops: train/comms/pt/comms_utils.py:2014, split_table_batched_embeddings_ops.py:289
@@ -289,6 +325,30 @@ int oracle_embbag_bwd_rowwise_adagrad_f32(float* W, float* mom, float* scratch, 
                                                     grad_stride, lr, eps, 0.0f, 0);
 }
 
+/*
+ * The same optimizer on a 16-bit table (dtype ORACLE_BF16 / ORACLE_F16): the table is widened to fp32, the fp32 routine
+ * above runs on the widened copy (one arithmetic, not a second statement of it), and every element of a touched row is
+ * rounded ONCE, to nearest even.  W_pre (rows*dim floats) receives the widened table and, on touched rows, the fp32
+ * value BEFORE that rounding -- what a stochastic store is judged against.  Untouched rows of W16 keep their bits.
+ */
+int oracle_embbag_bwd_rowwise_adagrad_wd_16(uint16_t* W16, int dtype, float* mom, float* W_pre, float* scratch,
+                                            uint8_t* touched, int64_t rows, int32_t dim, const int64_t* idx, int64_t N,
+                                            const int64_t* off, int64_t B, const float* psw, const float* grad,
+                                            int64_t grad_stride, float lr, float eps, float wd, int32_t wd_mode) {
+    if (dtype != ORACLE_BF16 && dtype != ORACLE_F16) return ORACLE_ERR_DTYPE;
+    const int64_t n = rows * (int64_t)dim;
+    for (int64_t i = 0; i < n; ++i) W_pre[i] = load_elem(W16, dtype, i);
+    int rc = oracle_embbag_bwd_rowwise_adagrad_wd_f32(W_pre, mom, scratch, touched, rows, dim, idx, N, off, B, psw, grad,
+                                                      grad_stride, lr, eps, wd, wd_mode);
+    if (rc != ORACLE_OK) return rc;
+    for (int64_t r = 0; r < rows; ++r) {
+        if (!touched[r]) continue;
+        for (int64_t i = r * (int64_t)dim; i < (r + 1) * (int64_t)dim; ++i)
+            W16[i] = dtype == ORACLE_BF16 ? f32_to_bf16(W_pre[i]) : f32_to_f16(W_pre[i]);
+    }
+    return ORACLE_OK;
+}
+
 /* widen helpers exported for the tests */
 void oracle_bf16_to_f32(const uint16_t* src, float* dst, int64_t n) {
     for (int64_t i = 0; i < n; ++i) dst[i] = bf16_to_f32(src[i]);
@@ -298,4 +358,7 @@ void oracle_f16_to_f32(const uint16_t* src, float* dst, int64_t n) {
 }
 void oracle_f32_to_bf16(const float* src, uint16_t* dst, int64_t n) {
     for (int64_t i = 0; i < n; ++i) dst[i] = f32_to_bf16(src[i]);
+}
+void oracle_f32_to_f16(const float* src, uint16_t* dst, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) dst[i] = f32_to_f16(src[i]);
 }

@@ -57,6 +57,32 @@ def f32_to_bf16_bits(x: np.ndarray) -> np.ndarray:
     return ((u + 0x7FFF + lsb) >> 16).astype(np.uint16)
 
 
+def f16_bits_to_f32(bits: np.ndarray) -> np.ndarray:
+    return np.ascontiguousarray(bits, dtype=np.uint16).view(np.float16).astype(np.float32)
+
+
+def ulp16(x, dtype: int) -> np.ndarray:
+    """spacing (fp64) of the 16-bit table type ``dtype`` (BF16 / F16) at the real value x: 2^(e - mantissa bits) with e the
+    exponent of |x|, held at the smallest normal exponent below the normal range (there the grid has one fixed spacing)"""
+    man, emin = (7, -126) if dtype == BF16 else (10, -14)
+    m, ex = np.frexp(np.abs(np.asarray(x, dtype=np.float64)))          # |x| = m * 2^ex, m in [0.5, 1); frexp(0) = (0, 0)
+    return np.ldexp(1.0, np.where(m == 0, emin, np.maximum(ex - 1, emin)) - man)
+
+
+def down16(x, dtype: int) -> np.ndarray:
+    """largest value of the 16-bit grid at or below x (fp64; no overflow handling: for finite in-range values)"""
+    x = np.asarray(x, dtype=np.float64)
+    u = ulp16(x, dtype)
+    return np.floor(x / u) * u
+
+
+def up16(x, dtype: int) -> np.ndarray:
+    """smallest value of the 16-bit grid at or above x"""
+    x = np.asarray(x, dtype=np.float64)
+    u = ulp16(x, dtype)
+    return np.ceil(x / u) * u
+
+
 def embbag_fwd_np(W: np.ndarray, idx, off, psw=None) -> np.ndarray:
     """out[b,:] = sum_j W[idx[j],:], sequential fp32, W already fp32 [R,D]."""
     W = np.asarray(W, dtype=np.float32)
@@ -154,6 +180,15 @@ class COracle:
         L.oracle_embbag_bwd_bf16.restype = ctypes.c_int
         L.oracle_embbag_bwd_bf16.argtypes = [ctypes.POINTER(ctypes.c_uint16), f32p, i64, i32, i64p, i64,
                                              i64p, i64, f32p, f32p, i64, ctypes.c_float]
+        L.oracle_embbag_bwd_f16.restype = ctypes.c_int
+        L.oracle_embbag_bwd_f16.argtypes = L.oracle_embbag_bwd_bf16.argtypes
+        L.oracle_embbag_bwd_rowwise_adagrad_wd_16.restype = ctypes.c_int
+        L.oracle_embbag_bwd_rowwise_adagrad_wd_16.argtypes = [ctypes.POINTER(ctypes.c_uint16), ctypes.c_int, f32p, f32p, f32p,
+                                                              ctypes.POINTER(ctypes.c_uint8), i64, i32, i64p, i64, i64p, i64,
+                                                              f32p, f32p, i64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                                              i32]
+        L.oracle_f32_to_f16.restype = None
+        L.oracle_f32_to_f16.argtypes = [f32p, ctypes.POINTER(ctypes.c_uint16), i64]
         L.oracle_embbag_bwd_rowwise_adagrad_wd_f32.restype = ctypes.c_int
         L.oracle_embbag_bwd_rowwise_adagrad_wd_f32.argtypes = [f32p, f32p, f32p, ctypes.POINTER(ctypes.c_uint8), i64, i32,
                                                                i64p, i64, i64p, i64, f32p, f32p, i64, ctypes.c_float,
@@ -240,36 +275,58 @@ class COracle:
         return dst
 
     def bwd_rowwise_adagrad(self, W: np.ndarray, mom: np.ndarray, idx, off, grad: np.ndarray, psw=None, lr=0.01,
-                            eps=1e-8, weight_decay=0.0, weight_decay_mode=0):
-        """in place on W (fp32 [R,D]) and mom (fp32 [R]); PARITY UNPINNED (fbgemm absent), see the C header."""
-        assert W.dtype == np.float32 and W.flags.c_contiguous and mom.dtype == np.float32 and mom.shape == (W.shape[0],)
+                            eps=1e-8, weight_decay=0.0, weight_decay_mode=0, dtype=None):
+        """in place on W and mom (fp32 [R]); PARITY UNPINNED (fbgemm absent), see the C header.  fp32 tables (``dtype`` None /
+        F32): W is fp32 [R,D], returns ``(W, mom)``.  16-bit tables (``dtype`` BF16 / F16): W is the uint16 bit pattern [R,D],
+        rounded to nearest once per touched element; returns ``(W, mom, W_pre)`` with W_pre fp32 [R,D] = the value before that
+        rounding on touched rows (the widened old value elsewhere)."""
+        assert W.flags.c_contiguous and mom.dtype == np.float32 and mom.shape == (W.shape[0],)
         idx = np.ascontiguousarray(idx, dtype=np.int64)
         off = np.ascontiguousarray(off, dtype=np.int64)
         grad = np.ascontiguousarray(grad, dtype=np.float32)
         psw = None if psw is None else np.ascontiguousarray(psw, dtype=np.float32)
-        scratch = np.empty_like(W)
+        scratch = np.empty(W.shape, dtype=np.float32)
         touched = np.empty(W.shape[0], dtype=np.uint8)
-        rc = self.L.oracle_embbag_bwd_rowwise_adagrad_wd_f32(
-            _ptr(W, ctypes.c_float), _ptr(mom, ctypes.c_float), _ptr(scratch, ctypes.c_float),
-            _ptr(touched, ctypes.c_uint8), W.shape[0], W.shape[1], _ptr(idx, ctypes.c_int64), len(idx),
-            _ptr(off, ctypes.c_int64), len(off), _ptr(psw, ctypes.c_float), _ptr(grad, ctypes.c_float), grad.shape[1],
-            float(lr), float(eps), float(weight_decay), int(weight_decay_mode))
-        self._check(rc)
-        return W, mom
+        tail = (W.shape[0], W.shape[1], _ptr(idx, ctypes.c_int64), len(idx), _ptr(off, ctypes.c_int64), len(off),
+                _ptr(psw, ctypes.c_float), _ptr(grad, ctypes.c_float), grad.shape[1], float(lr), float(eps),
+                float(weight_decay), int(weight_decay_mode))
+        if dtype in (None, F32):
+            assert W.dtype == np.float32
+            self._check(self.L.oracle_embbag_bwd_rowwise_adagrad_wd_f32(
+                _ptr(W, ctypes.c_float), _ptr(mom, ctypes.c_float), _ptr(scratch, ctypes.c_float),
+                _ptr(touched, ctypes.c_uint8), *tail))
+            return W, mom
+        assert dtype in (BF16, F16) and W.dtype == np.uint16
+        W_pre = np.empty(W.shape, dtype=np.float32)
+        self._check(self.L.oracle_embbag_bwd_rowwise_adagrad_wd_16(
+            _ptr(W, ctypes.c_uint16), int(dtype), _ptr(mom, ctypes.c_float), _ptr(W_pre, ctypes.c_float),
+            _ptr(scratch, ctypes.c_float), _ptr(touched, ctypes.c_uint8), *tail))
+        return W, mom, W_pre
+
+    def f32_to_f16_bits(self, x: np.ndarray) -> np.ndarray:
+        """software round-to-nearest-even fp32 -> fp16 bit patterns (the conversion bwd_f16 and the 16-bit Adagrad use)"""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        out = np.empty(x.shape, dtype=np.uint16)
+        self.L.oracle_f32_to_f16(_ptr(x, ctypes.c_float), _ptr(out, ctypes.c_uint16), x.size)
+        return out
+
+    def bwd_f16(self, dst_bits: np.ndarray, idx, off, grad: np.ndarray, psw=None, alpha=1.0):
+        """in-place on a uint16 (fp16 bit pattern) table: widened, fp32 sequential accumulate, one nearest-even rounding."""
+        return self._bwd_16(self.L.oracle_embbag_bwd_f16, dst_bits, idx, off, grad, psw, alpha)
 
     def bwd_bf16(self, dst_bits: np.ndarray, idx, off, grad: np.ndarray, psw=None, alpha=1.0):
         """in-place on a uint16 (bf16 bit pattern) table."""
+        return self._bwd_16(self.L.oracle_embbag_bwd_bf16, dst_bits, idx, off, grad, psw, alpha)
+
+    def _bwd_16(self, fn, dst_bits, idx, off, grad, psw, alpha):
         assert dst_bits.dtype == np.uint16 and dst_bits.flags.c_contiguous
         idx = np.ascontiguousarray(idx, dtype=np.int64)
         off = np.ascontiguousarray(off, dtype=np.int64)
         grad = np.ascontiguousarray(grad, dtype=np.float32)
         psw = None if psw is None else np.ascontiguousarray(psw, dtype=np.float32)
         scratch = np.empty(dst_bits.shape, dtype=np.float32)
-        rc = self.L.oracle_embbag_bwd_bf16(_ptr(dst_bits, ctypes.c_uint16), _ptr(scratch, ctypes.c_float),
-                                           dst_bits.shape[0], dst_bits.shape[1],
-                                           _ptr(idx, ctypes.c_int64), len(idx),
-                                           _ptr(off, ctypes.c_int64), len(off),
-                                           _ptr(psw, ctypes.c_float), _ptr(grad, ctypes.c_float),
-                                           grad.shape[1], float(alpha))
+        rc = fn(_ptr(dst_bits, ctypes.c_uint16), _ptr(scratch, ctypes.c_float), dst_bits.shape[0], dst_bits.shape[1],
+                _ptr(idx, ctypes.c_int64), len(idx), _ptr(off, ctypes.c_int64), len(off), _ptr(psw, ctypes.c_float),
+                _ptr(grad, ctypes.c_float), grad.shape[1], float(alpha))
         self._check(rc)
         return dst_bits

@@ -51,7 +51,9 @@ __device__ __forceinline__ void adagrad_finish(char* wptr, float (&wrow)[DST::kV
     if (p.wd_mode == PM_WD_L2) {
 #pragma unroll
         for (int k = 0; k < DST::kVec; ++k) {
-            const float reg = p.wd * wrow[k];
+            // (a lane past the table's width loaded no row: its wrow is what an earlier, WIDER table's row left there in a
+            // mixed-dim request, and counted into this row's sum of squares it inflated the state of every narrower table's rows)
+            const float reg = any_col ? p.wd * wrow[k] : 0.0f;
             const float gx = acc[k] + reg;
             ss = ss + gx * gx;
         }

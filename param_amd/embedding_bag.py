@@ -278,9 +278,10 @@ def _fwd_quantized(ts: _TableSet, indices, offsets, B, bitwidth: int, psw=None, 
     return out
 
 
-def _workspace(ts: _TableSet, op) -> torch.Tensor:
-    """Scratch for the sort-based backward, cached on the table set (grown, never shrunk)."""
-    need = _lib.load().pm_embbag_bwd_sorted_workspace(ctypes.byref(op), max(ts.rows))
+def _workspace(ts: _TableSet, op, max_rows: Optional[int] = None) -> torch.Tensor:
+    """Scratch for the sort-based backward, cached on the table set (grown, never shrunk).  ``max_rows``: of the tables ``op``
+    names, when it is a table range of the set's request."""
+    need = _lib.load().pm_embbag_bwd_sorted_workspace(ctypes.byref(op), max(ts.rows) if max_rows is None else max_rows)
     if need < 0:
         _lib.check(int(need))
     ws = getattr(ts, "_ws", None)
@@ -298,6 +299,7 @@ def _sort_indices(ts: _TableSet, indices, offsets, B, psw=None, bag_begin=0, bag
     sort into the apply and reads the indices again there, is taken by the fused calls only (``_bwd`` / ``_adagrad`` without
     ``presorted``).  ``phases=2`` (scatter-add /
     SGD apply) lets the apply run in two bag phases where the request allows; the fused row-wise Adagrad needs ``phases=1``."""
+    _no_presorted_split(ts, True)
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
     op.fixed_pooling = ts.fixed_pooling(indices, offsets, B, pooling) if _lib.needs_pooling_hint() else 0
     ws = _workspace(ts, op)
@@ -348,6 +350,54 @@ def sort_status(ts: _TableSet, indices, offsets, B, psw=None, bag_begin=0, bag_c
             "hybrid_launched": st.hybrid_launched, "lds_pairs": st.lds_pairs, "lds_tables": st.lds_tables}
 
 
+_SORTED_MAX_TABLES = 1024      # kSegSortMaxTables: the sorted path's limit per call; larger requests are split by tables
+
+
+def _table_chunks(ts: _TableSet, op, indices, offsets, B, psw=None):
+    """The request ``op`` as sub-requests of at most 1024 tables each, in table order: ``(sub, t0, t1, max_rows)`` per range
+    [t0, t1).  The lookups of a table range are one contiguous stretch of the table-major index array: its offsets are rebased to
+    that stretch, ``tables`` / ``rows`` / ``dims`` / ``out_offsets`` are the range's slice of the request's own device arrays, the index and
+    weight pointers are advanced, ``max_dim`` / ``min_dim`` are the range's; the gradient and its addressing (stride, blocking, batch
+    slice) stay the full request's.  A caller that passes its own per-table pointer arrays (destinations, optimizer state) slices
+    them ``[t0:t1]`` the same way.  A request within the limit comes back as it is (no copy, no synchronisation); a larger one
+    costs one small device-to-host read of the offsets at the cuts."""
+    T = ts.T
+    if T <= _SORTED_MAX_TABLES:
+        yield op, 0, T, max(ts.rows)
+        return
+    cuts = list(range(0, T, _SORTED_MAX_TABLES)) + [T]
+    n = indices.numel()
+    if B == 0:
+        starts = [0] * len(cuts)
+    else:
+        starts = offsets[[c * B for c in cuts[:-1]]].tolist() + [n]
+    esz = {"tables": 8, "rows": 8, "dims": 4, "out_offsets": 8}
+    for t0, t1, n0, n1 in zip(cuts[:-1], cuts[1:], starts[:-1], starts[1:]):
+        sub = _lib.pm_embbag_batch.from_buffer_copy(op)
+        sub_off = (offsets[t0 * B:t1 * B] - n0).contiguous()
+        sub.num_tables = t1 - t0
+        sub.max_dim, sub.min_dim = max(ts.dims[t0:t1]), min(ts.dims[t0:t1])
+        sub.num_indices = n1 - n0
+        for name, e in esz.items():
+            setattr(sub, name, getattr(op, name) + t0 * e)
+        sub.indices = indices.data_ptr() + n0 * indices.element_size()
+        sub.offsets = sub_off.data_ptr()
+        if psw is not None:
+            sub.per_sample_weights = psw.data_ptr() + n0 * psw.element_size()
+        # (sub_off is referenced until the consumer has launched this range's kernels on the current stream; the caching allocator
+        # reuses its memory in stream order only)
+        yield sub, t0, t1, max(ts.rows[t0:t1])
+        del sub_off
+
+
+def _no_presorted_split(ts, presorted: bool) -> None:
+    """``sort_indices`` + ``presorted=True`` keep ONE sort in the cached workspace: refused, on the host, for requests that need several"""
+    if presorted and ts.T > _SORTED_MAX_TABLES:
+        raise ValueError(f"presorted=True takes requests of at most {_SORTED_MAX_TABLES} tables (this one has {ts.T}): a larger request "
+                         "runs as several sorted calls that share one workspace, which cannot hold several sorts at once; call "
+                         "without presorted (the sort then runs inside the call, once per 1024 tables)")
+
+
 def _bwd(ts: _TableSet, grad, indices, offsets, B, dst_ptrs_dev, dst_dtype, alpha, psw=None,
          bag_begin=0, bag_count=None, method: str = "sorted", presorted: bool = False, pooling: Optional[int] = None):
     """``method="sorted"`` (default): deterministic, bit-identical to a sequential scatter-add;
@@ -369,19 +419,24 @@ def _bwd(ts: _TableSet, grad, indices, offsets, B, dst_ptrs_dev, dst_dtype, alph
         return
     if method != "sorted":
         raise ValueError('method must be "sorted" or "atomic"')
-    ws = _workspace(ts, op)
-    if not presorted and not _lib.needs_pooling_hint():
-        # sort + apply sequenced by the library itself: the one form in which it may defer part of the sort into the apply
-        # (hybrid backward: rows looked up once skip the sort)
-        op.fixed_pooling = 0       # (the cached descriptor may carry a hint from an alternates-build run: the segmented sort takes none)
-        _lib.check(L.pm_embbag_bwd_fused(ctypes.byref(op), grad.data_ptr(), dst_ptrs_dev.data_ptr(), _WDTYPE[dst_dtype],
-                                         float(alpha), max(ts.rows), ws.data_ptr(), ws.numel(), _stream_ptr()))
-        return
-    if not presorted:      # the alternative key sorts (sort_impl 1 / 2) read a pooling hint and may lay out two bag phases
-        op.fixed_pooling = ts.fixed_pooling(indices, offsets, B, pooling)
-        _lib.check(L.pm_embbag_sort_indices_ex(ctypes.byref(op), max(ts.rows), 2, ws.data_ptr(), ws.numel(), _stream_ptr()))
-    _lib.check(L.pm_embbag_bwd_sorted(ctypes.byref(op), grad.data_ptr(), dst_ptrs_dev.data_ptr(), _WDTYPE[dst_dtype],
-                                      float(alpha), max(ts.rows), ws.data_ptr(), ws.numel(), _stream_ptr()))
+    _no_presorted_split(ts, presorted)
+    dst_dt, s = _WDTYPE[dst_dtype], _stream_ptr()
+    # (more than 1024 tables: one sorted call per table range, in table order on this stream, sharing the cached workspace)
+    for sub, t0, t1, max_rows in _table_chunks(ts, op, indices, offsets, B, psw):
+        ws = _workspace(ts, sub, max_rows)
+        dst = dst_ptrs_dev.data_ptr() + 8 * t0
+        if not presorted and not _lib.needs_pooling_hint():
+            # sort + apply sequenced by the library itself: the one form in which it may defer part of the sort into the apply
+            # (hybrid backward: rows looked up once skip the sort)
+            sub.fixed_pooling = 0  # (the cached descriptor may carry a hint from an alternates-build run: the segmented sort takes none)
+            _lib.check(L.pm_embbag_bwd_fused(ctypes.byref(sub), grad.data_ptr(), dst, dst_dt, float(alpha), max_rows, ws.data_ptr(),
+                                             ws.numel(), s))
+            continue
+        if not presorted:      # the alternative key sorts (sort_impl 1 / 2) read a pooling hint and may lay out two bag phases
+            sub.fixed_pooling = ts.fixed_pooling(indices, offsets, B, pooling) if sub is op else 0
+            _lib.check(L.pm_embbag_sort_indices_ex(ctypes.byref(sub), max_rows, 2, ws.data_ptr(), ws.numel(), s))
+        _lib.check(L.pm_embbag_bwd_sorted(ctypes.byref(sub), grad.data_ptr(), dst, dst_dt, float(alpha), max_rows, ws.data_ptr(),
+                                          ws.numel(), s))
 
 
 def check_request(ts: _TableSet, indices, offsets, B, psw=None) -> None:
@@ -410,26 +465,28 @@ def _adagrad(ts: _TableSet, grad, indices, offsets, B, mom_ptrs_dev, lr: float, 
     if grad.dtype != torch.float32 or tuple(grad.shape) != tuple(shape):
         raise ValueError(f"grad must be float32 of shape {shape}")
     grad = grad.contiguous()
+    _no_presorted_split(ts, presorted)
     op = ts.request(indices, offsets, B, psw, 0, None)
     L = _lib.load()
-    ws = _workspace(ts, op)
-    opt = _lib.pm_rowwise_adagrad(float(lr), float(eps), float(weight_decay), _WD_MODES[weight_decay_mode],
-                                  1 if stochastic_rounding else 0, 0, int(seed) & (2**64 - 1))
-    if not presorted and not _lib.needs_pooling_hint():
-        op.fixed_pooling = 0
-        _lib.check(L.pm_embbag_bwd_fused_adagrad(ctypes.byref(op), grad.data_ptr(), ts.d_ptrs.data_ptr(), _WDTYPE[ts.dtype],
-                                                 mom_ptrs_dev.data_ptr(), ctypes.byref(opt), max(ts.rows),
-                                                 ws.data_ptr(), ws.numel(), _stream_ptr()))
-        return
-    if not presorted:
-        op.fixed_pooling = ts.fixed_pooling(indices, offsets, B, pooling)
-        _lib.check(L.pm_embbag_sort_indices_ex(ctypes.byref(op), max(ts.rows), 1, ws.data_ptr(), ws.numel(), _stream_ptr()))
-    _lib.check(L.pm_embbag_bwd_sorted_adagrad_ex(ctypes.byref(op), grad.data_ptr(), ts.d_ptrs.data_ptr(), _WDTYPE[ts.dtype],
-                                                 mom_ptrs_dev.data_ptr(), ctypes.byref(opt), max(ts.rows),
-                                                 ws.data_ptr(), ws.numel(), _stream_ptr()))
-
-
-_SPARSE_MAX_TABLES = 1024      # kSegSortMaxTables: the sorted path's limit per call; larger requests are split by tables
+    wdt, s = _WDTYPE[ts.dtype], _stream_ptr()
+    # (more than 1024 tables: one call per table range, as in _bwd.  A stochastic-rounding draw is keyed by the seed, the table's
+    # number INSIDE its call, the row and the column pair: every range gets a seed of its own -- the first one the caller's -- so
+    # that table t and table t + 1024 do not share their draws)
+    for sub, t0, t1, max_rows in _table_chunks(ts, op, indices, offsets, B, psw):
+        opt = _lib.pm_rowwise_adagrad(float(lr), float(eps), float(weight_decay), _WD_MODES[weight_decay_mode],
+                                      1 if stochastic_rounding else 0, 0, (int(seed) + (t0 << 32)) & (2**64 - 1))
+        ws = _workspace(ts, sub, max_rows)
+        tabs, mom = ts.d_ptrs.data_ptr() + 8 * t0, mom_ptrs_dev.data_ptr() + 8 * t0
+        if not presorted and not _lib.needs_pooling_hint():
+            sub.fixed_pooling = 0
+            _lib.check(L.pm_embbag_bwd_fused_adagrad(ctypes.byref(sub), grad.data_ptr(), tabs, wdt, mom, ctypes.byref(opt), max_rows,
+                                                     ws.data_ptr(), ws.numel(), s))
+            continue
+        if not presorted:
+            sub.fixed_pooling = ts.fixed_pooling(indices, offsets, B, pooling) if sub is op else 0
+            _lib.check(L.pm_embbag_sort_indices_ex(ctypes.byref(sub), max_rows, 1, ws.data_ptr(), ws.numel(), s))
+        _lib.check(L.pm_embbag_bwd_sorted_adagrad_ex(ctypes.byref(sub), grad.data_ptr(), tabs, wdt, mom, ctypes.byref(opt), max_rows,
+                                                     ws.data_ptr(), ws.numel(), s))
 
 
 def _sparse_grad_call(ts: _TableSet, op, grad, max_rows: int, dims: Sequence[int]):
@@ -467,35 +524,10 @@ def _sparse_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, bag_begin=0
     grad = grad.contiguous()
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
     op.fixed_pooling = 0
-    if ts.T <= _SPARSE_MAX_TABLES:
-        return _sparse_grad_call(ts, op, grad, max(ts.rows), ts.dims)
-    # more tables than one sorted call takes: independent requests of at most 1024 tables -- the lookups of tables [t0, t1) are one
-    # contiguous range of the table-major index array, their offsets rebased to it; the gradient and its addressing stay the full
-    # request's (out_offsets of those tables, the stride and any blocking of the whole layout)
-    T = ts.T
-    cuts = list(range(0, T, _SPARSE_MAX_TABLES)) + [T]
-    n = indices.numel()
-    if B == 0:
-        starts = [0] * len(cuts)
-    else:
-        starts = offsets[[c * B for c in cuts[:-1]]].tolist() + [n]
-    out_off = ts.out_desc(B)[0]
+    # more tables than one sorted call takes: independent requests of at most 1024 tables (_table_chunks)
     res = []
-    for t0, t1, n0, n1 in zip(cuts[:-1], cuts[1:], starts[:-1], starts[1:]):
-        sub = _lib.pm_embbag_batch.from_buffer_copy(op)
-        sub_off = (offsets[t0 * B:t1 * B] - n0).contiguous()
-        sub.num_tables = t1 - t0
-        sub.max_dim, sub.min_dim = max(ts.dims[t0:t1]), min(ts.dims[t0:t1])
-        sub.num_indices = n1 - n0
-        sub.tables = ts.d_ptrs[t0:t1].data_ptr()
-        sub.rows = ts.d_rows[t0:t1].data_ptr()
-        sub.dims = ts.d_dims[t0:t1].data_ptr()
-        sub.out_offsets = out_off[t0:t1].data_ptr()
-        sub.indices = indices.data_ptr() + n0 * indices.element_size()
-        sub.offsets = sub_off.data_ptr()
-        if psw is not None:
-            sub.per_sample_weights = psw.data_ptr() + n0 * psw.element_size()
-        res += _sparse_grad_call(ts, sub, grad, max(ts.rows[t0:t1]), ts.dims[t0:t1])
+    for sub, t0, t1, max_rows in _table_chunks(ts, op, indices, offsets, B, psw):
+        res += _sparse_grad_call(ts, sub, grad, max_rows, ts.dims[t0:t1])
     return res
 
 

@@ -128,7 +128,7 @@ def test_random_request_vs_oracle(seed, coracle):
         assert (np.abs(dwa[t].cpu().numpy() - truth) <= tol_atomic).all(), ("atomic backward", t)
 
     # in-place update in the table's own dtype (16-bit: widened, fp32 accumulate, one rounding)
-    if c["wdt"] in (torch.float32, torch.bfloat16):
+    if c["wdt"] in (torch.float32, torch.bfloat16, torch.float16):
         m.scatter_add_(g_t, idx_t, off_t, alpha=-0.125, per_sample_weights=psw_t, batch=B)
         for t in range(T):
             s, e = c["off"][t * B], c["off"][(t + 1) * B]
@@ -140,10 +140,16 @@ def test_random_request_vs_oracle(seed, coracle):
             if c["wdt"] == torch.float32:
                 ref = coracle.bwd_f32(tabs_f32[t].copy(), c["idx"][s:e], loc, g, pw, alpha=-0.125)
                 assert np.array_equal(m.table(t).cpu().numpy()[cold], ref[cold]), ("in-place fp32", t)
-            else:
+            elif c["wdt"] == torch.bfloat16:
                 bits = coracle.bwd_bf16(O.f32_to_bf16_bits(tabs_f32[t]), c["idx"][s:e], loc, g, pw, alpha=-0.125)
                 got = m.table(t).view(torch.int16).cpu().numpy().view(np.uint16)
                 assert np.array_equal(got[cold], bits[cold]), ("in-place bf16", t)
+            else:
+                old = tabs_f32[t].astype(np.float16)                       # exact: the table was widened from these very values
+                assert np.array_equal(old.astype(np.float32), tabs_f32[t])
+                bits = coracle.bwd_f16(old.view(np.uint16).copy(), c["idx"][s:e], loc, g, pw, alpha=-0.125)
+                got = m.table(t).view(torch.int16).cpu().numpy().view(np.uint16)
+                assert np.array_equal(got[cold], bits[cold]), ("in-place fp16", t)
 
 
 @pytest.mark.parametrize("seed", range(max(12, _SEEDS // 5)))
@@ -153,6 +159,7 @@ def test_random_adagrad_vs_oracle(seed, coracle):
 
     rng = np.random.default_rng(5000 + seed)
     c = _case(rng)
+    dims_drawn = list(c["dims"])
     if max(c["dims"]) > 256:
         c["dims"] = [min(d, 256) for d in c["dims"]]
     T, B, dims, rows = c["T"], c["B"], c["dims"], c["rows"]
@@ -199,3 +206,46 @@ def test_random_adagrad_vs_oracle(seed, coracle):
             hot = ~cold
             assert (np.abs(gw[hot] - W64[hot]) <= bound[hot]).all(), ("weights, hot rows", t)
             assert (np.abs(gm[hot] - m64[hot]) <= dm[hot] + 3e-5 * m64[hot] + 1e-10).all(), ("momentum, hot rows", t)
+    if c["wdt"] != torch.float32:
+        _adagrad_16bit(dict(c, dims=dims_drawn), seed, psw_t, coracle)
+
+
+def _adagrad_16bit(c, seed, psw_t, coracle):
+    """the same request on tables of the 16-bit dtype the case drew, with the dims it drew (up to 512): every element of a touched row within
+    half a 16-bit spacing + b of the oracle's fp32 value before rounding, b = 2e-5 |w| + 2e-6 (tests/lowp_rules.py); rows beyond
+    the exact-run limit: the derived bound above plus half a spacing"""
+    from oracle import embbag_oracle as O
+    from param_amd import BatchedEmbeddingBagMI355
+    from tests import lowp_rules as R
+
+    T, B, dims, rows = c["T"], c["B"], c["dims"], c["rows"]
+    code = O.BF16 if c["wdt"] == torch.bfloat16 else O.F16
+    widen = O.bf16_bits_to_f32 if code == O.BF16 else O.f16_bits_to_f32
+    m = BatchedEmbeddingBagMI355(rows, dims, dtype=c["wdt"], device=DEV, layout=c["layout"], init="normal", seed=seed, learning_rate=0.03,
+                                 optimizer="rowwise_adagrad", eps=1e-5)
+    old = [m.table(t).view(torch.int16).cpu().numpy().view(np.uint16).copy() for t in range(T)]
+    grad = np.random.default_rng(7000 + seed).standard_normal((B, sum(dims)) if c["layout"] == "bd" else (T, B, dims[0])).astype(np.float32)
+    m.adagrad_step_(_t(grad), _t(c["idx"], c["it"]), _t(c["off"], c["it"]), psw_t, batch=B)
+    for t in range(T):
+        s, e = c["off"][t * B], c["off"][(t + 1) * B]
+        loc = c["off"][t * B:(t + 1) * B] - s
+        col = sum(dims[:t])
+        g = np.ascontiguousarray(grad[:, col:col + dims[t]] if c["layout"] == "bd" else grad[t])
+        pw = None if c["psw"] is None else c["psw"][s:e]
+        bits, mom = old[t].copy(), np.zeros(rows[t], np.float32)
+        _, _, w_pre = coracle.bwd_rowwise_adagrad(bits, mom, c["idx"][s:e], loc, g, pw, lr=0.03, eps=1e-5, dtype=code)
+        cnt = np.bincount(c["idx"][s:e], minlength=rows[t])
+        touched, hot = cnt > 0, cnt > EXACT_RUN
+        cold = touched & ~hot
+        got_bits = m.table(t).view(torch.int16).cpu().numpy().view(np.uint16)
+        got, gm = widen(got_bits).astype(np.float64), m.momentum_table(t).cpu().numpy()
+        assert np.array_equal(got_bits[~touched], old[t][~touched]) and not gm[~touched].any(), ("16-bit, untouched rows", t)
+        wp = w_pre.astype(np.float64)
+        ratio = R.nearest_ratio(got[cold], wp[cold], code, R.tol_b(wp[cold]))
+        assert ratio.size == 0 or ratio.max() <= 1.0, ("16-bit weights", t, float(ratio.max()))
+        assert np.allclose(gm[cold], mom[cold], rtol=2e-5, atol=1e-12), ("16-bit momentum", t)
+        if hot.any():
+            W64, m64, bound_w, dm = R.adagrad_fp64(widen(old[t]), np.zeros(rows[t]), c["idx"][s:e], loc, g, pw, 0.03, 1e-5)
+            lim = bound_w + 3e-5 * np.abs(W64) + 3e-6 + O.ulp16(W64, code) / 2
+            assert (np.abs(got[hot] - W64[hot]) <= lim[hot]).all(), ("16-bit weights, hot rows", t)
+            assert (np.abs(gm[hot] - m64[hot]) <= dm[hot] + 3e-5 * m64[hot] + 1e-10).all(), ("16-bit momentum, hot rows", t)

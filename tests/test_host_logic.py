@@ -616,3 +616,16 @@ def test_bench_refuses_a_world_size_that_is_not_gpus():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3"], env=env, capture_output=True,
                        text=True, timeout=300)
     assert r.returncode != 0 and "--gpus 2 but WORLD_SIZE=1" in r.stderr
+
+
+def test_presorted_requests_are_limited_to_one_sorted_call():
+    """the host-side rule behind ``presorted=True`` / ``sort_indices`` (its device-side use: tests/test_gpu_many_tables.py): a
+    request of more than 1024 tables runs as several sorted calls, whose sorts one workspace cannot hold side by side"""
+    from param_amd import embedding_bag as eb
+
+    assert eb._SORTED_MAX_TABLES == 1024
+    for T in (1, 1024):
+        eb._no_presorted_split(types.SimpleNamespace(T=T), True)
+    eb._no_presorted_split(types.SimpleNamespace(T=5000), False)
+    with pytest.raises(ValueError, match=r"1024 tables \(this one has 1025\).*without presorted"):
+        eb._no_presorted_split(types.SimpleNamespace(T=1025), True)

@@ -254,3 +254,121 @@ def test_c_oracle_against_live_torch_on_random_requests(coracle):
             for j in range(start[b], end[b]):
                 mag[idx[j]] += np.abs(grad[b].astype(np.float64)) * (1.0 if psw is None else abs(float(psw[j])))
         assert (np.abs(dW.astype(np.float64) - Wt.grad.numpy().astype(np.float64)) <= 1e-5 * mag + 1e-30).all(), case
+
+
+# ----------------------------------------------------------------------------- the 16-bit update routines
+def _same_f16(x32, coracle):
+    import torch
+
+    got = coracle.f32_to_f16_bits(x32)
+    exp = torch.from_numpy(np.ascontiguousarray(x32, dtype=np.float32)).to(torch.float16).view(torch.int16).numpy().view(np.uint16)
+    nan = np.isnan(np.asarray(x32, dtype=np.float32))
+    assert np.array_equal(got[~nan], exp[~nan])
+    assert np.isnan(got[nan].view(np.float16)).all() and np.isnan(exp[nan].view(np.float16)).all()
+    assert np.array_equal(got[nan] & 0x8000, exp[nan] & 0x8000)            # a NaN keeps its sign
+
+
+def test_f32_to_f16_software_rounding_equals_torch(coracle):
+    """round-to-nearest-even fp32 -> fp16 of the oracle against torch's conversion, bit for bit: every fp16 value widened
+    (exact), every midpoint between two neighbouring fp16 values (ties) and both fp32 neighbours of every midpoint, +-0, values
+    below 2^-25, above 65504, Inf, NaN"""
+    allbits = np.arange(1 << 16, dtype=np.uint16)
+    wide = O.f16_bits_to_f32(allbits)
+    _same_f16(wide, coracle)
+    fin = np.isfinite(wide)
+    assert np.array_equal(coracle.f32_to_f16_bits(wide[fin]), allbits[fin])          # widening then rounding is the identity
+    # midpoints: consecutive positive finite patterns are neighbours (subnormals included); the midpoint of two fp16 values has at
+    # most 12 significant bits, exact in fp32.  The midpoint above 65504 (65520) rounds to infinity.
+    pos = O.f16_bits_to_f32(np.arange(0, 0x7c00, dtype=np.uint16)).astype(np.float64)
+    mid = np.concatenate([(pos[:-1] + pos[1:]) / 2, [65520.0]])
+    mid32 = mid.astype(np.float32)
+    assert np.array_equal(mid32.astype(np.float64), mid)
+    for sign in (1.0, -1.0):
+        m = (sign * mid32).astype(np.float32)
+        _same_f16(m, coracle)
+        _same_f16(np.nextafter(m, np.float32(np.inf)), coracle)
+        _same_f16(np.nextafter(m, np.float32(-np.inf)), coracle)
+    tiny = np.float32(2.0 ** -25)
+    edge = np.array([0.0, -0.0, tiny, -tiny, np.nextafter(tiny, np.float32(0)), np.nextafter(tiny, np.float32(1)), 1e-9, -1e-9, 1e-30,
+                     1e-40, -1e-45, 65504.0, 65519.996, 65520.0, 65536.0, 1e6, -1e6, 3e38, np.inf, -np.inf, np.nan, -np.nan],
+                    dtype=np.float32)
+    _same_f16(edge, coracle)
+    nans = np.array([0x7fc00000, 0xffc00000, 0x7f800001, 0xff800001, 0x7fffffff, 0x7f802000], dtype=np.uint32).view(np.float32)
+    _same_f16(nans, coracle)
+    rng = np.random.default_rng(0)
+    _same_f16(rng.integers(0, 1 << 32, 2_000_000, dtype=np.uint64).astype(np.uint32).view(np.float32), coracle)
+
+
+def test_f16_backward_rounds_once(coracle):
+    """bwd_f16 accumulates a row's whole update in fp32 on the widened value and rounds once: the case is built so that rounding
+    after every add gives other bits"""
+    import torch
+
+    rng = np.random.default_rng(3)
+    W = rng.standard_normal((50, 16)).astype(np.float32)
+    f16 = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.float16)          # noqa: E731
+    bits = f16(W).view(torch.int16).numpy().view(np.uint16)
+    idx = rng.integers(0, 50, 60)
+    off = np.arange(6) * 10
+    grad = rng.standard_normal((6, 16)).astype(np.float32)
+    once = O.embbag_bwd_np(50, idx, off, grad, alpha=-0.1, dst=O.f16_bits_to_f32(bits).copy())
+    expect = f16(once).view(torch.int16).numpy().view(np.uint16)
+    got = coracle.bwd_f16(bits.copy(), idx, off, grad, alpha=-0.1)
+    assert np.array_equal(got, expect)
+    each = O.f16_bits_to_f32(bits).copy()
+    for b in range(6):
+        for j in range(off[b], off[b] + 10):
+            each[idx[j]] = f16(each[idx[j]] + (np.float32(-0.1) * grad[b]).astype(np.float32)).float().numpy()
+    assert not np.array_equal(f16(each).view(torch.int16).numpy().view(np.uint16), expect)
+
+
+@pytest.mark.parametrize("code", [O.BF16, O.F16])
+@pytest.mark.parametrize("mode", [0, 1, 2])
+def test_oracle_rowwise_adagrad_16bit_tables(coracle, code, mode):
+    """the 16-bit Adagrad routine against an fp64 numpy evaluation of the same formulas followed by torch's own conversion, under
+    the interval rule the GPU kernels are held to (tests/lowp_rules.py): duplicates, per-sample weights of both signs, two steps;
+    W_pre is the fp32 routine's own result on the widened table, the stored bits its single rounding"""
+    import torch
+
+    from tests import lowp_rules as R
+
+    tdt = torch.bfloat16 if code == O.BF16 else torch.float16
+    widen = O.bf16_bits_to_f32 if code == O.BF16 else O.f16_bits_to_f32
+    to_bits = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(tdt).view(torch.int16).numpy().view(np.uint16)   # noqa: E731
+    rng = np.random.default_rng(40 + mode)
+    Rr, D, B, L, lr, eps, wd = 300, 24, 64, 12, 0.05, 1e-6, 0.02
+    bits = to_bits(rng.standard_normal((Rr, D)))
+    mom = np.zeros(Rr, np.float32)
+    for step in range(2):
+        idx = rng.integers(0, Rr // 2, B * L).astype(np.int64)            # duplicates; the upper half is never looked up
+        off = np.arange(B, dtype=np.int64) * L
+        g = rng.standard_normal((B, D)).astype(np.float32)
+        psw = rng.standard_normal(B * L).astype(np.float32)
+        old_bits, m0 = bits.copy(), mom.copy()
+        w_old = widen(old_bits)
+        f32_W, f32_m = w_old.copy(), m0.copy()
+        coracle.bwd_rowwise_adagrad(f32_W, f32_m, idx, off, g, psw, lr=lr, eps=eps, weight_decay=wd, weight_decay_mode=mode)
+        _, _, w_pre = coracle.bwd_rowwise_adagrad(bits, mom, idx, off, g, psw, lr=lr, eps=eps, weight_decay=wd,
+                                                  weight_decay_mode=mode, dtype=code)
+        touched = np.bincount(idx, minlength=Rr) > 0
+        assert touched[:Rr // 2].sum() > 100 and not touched[Rr // 2:].any()
+        assert np.array_equal(w_pre[touched], f32_W[touched]) and np.array_equal(mom, f32_m)      # one arithmetic
+        assert np.array_equal(bits[touched], to_bits(w_pre[touched]))                             # rounded once, to nearest even
+        assert np.array_equal(bits[~touched], old_bits[~touched]) and np.array_equal(mom[~touched], m0[~touched])
+        W64, m64, _, _ = R.adagrad_fp64(w_old, m0, idx, off, g, psw, lr, eps, wd, mode)
+        ref = widen(to_bits(W64.astype(np.float32)))              # (fp64 -> fp32 -> 16 bit; the interval rule absorbs the double rounding)
+        ratio = R.nearest_ratio(widen(bits)[touched], W64[touched], code, R.tol_b(W64[touched]))
+        assert ratio.max() <= 1.0, ratio.max()
+        assert (np.abs(widen(bits)[touched] - ref[touched]) <= O.ulp16(W64[touched], code)).all()
+        assert np.allclose(mom[touched], m64[touched], rtol=2e-5, atol=1e-12)
+
+
+def test_ulp16_and_neighbours():
+    for code, tdt_bits in ((O.BF16, O.bf16_bits_to_f32), (O.F16, O.f16_bits_to_f32)):
+        top = 0x7f80 if code == O.BF16 else 0x7c00
+        vals = tdt_bits(np.arange(0, top, dtype=np.uint16)).astype(np.float64)
+        gaps = np.diff(vals)
+        assert np.array_equal(O.ulp16(vals[:-1], code), gaps)                       # the spacing above every grid value
+        mid = (vals[:-1] + vals[1:]) / 2
+        assert np.array_equal(O.down16(mid, code), vals[:-1]) and np.array_equal(O.up16(mid, code), vals[1:])
+        assert np.array_equal(O.down16(vals, code), vals) and np.array_equal(O.up16(-vals, code), -vals)
