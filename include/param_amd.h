@@ -315,6 +315,7 @@ int pm_embbag_bwd_sorted_adagrad(const pm_embbag_batch* op, const float* grad, v
  * (seed, table, row, column) -- pass a different seed every step; results are reproducible for a given seed.
  */
 enum { PM_WD_NONE = 0, PM_WD_L2 = 1, PM_WD_DECOUPLE = 2 };
+/* The options of BOTH fused Adagrad flavours: row-wise (pm_embbag_bwd_*_adagrad*) and element-wise (pm_embbag_bwd_*_adagrad_elem). */
 typedef struct pm_rowwise_adagrad {
     float lr;
     float eps;
@@ -332,6 +333,31 @@ int pm_embbag_bwd_sorted_adagrad_ex(const pm_embbag_batch* op, const float* grad
 int pm_embbag_bwd_fused_adagrad(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype,
                                 float* const* momentum, const pm_rowwise_adagrad* opt, int64_t max_rows, void* workspace,
                                 int64_t workspace_bytes, pm_stream_t stream);
+
+/*
+ * Fused backward + exact ELEMENT-wise Adagrad (fbgemm's EXACT_ADAGRAD, the optimizer the reference's TBE unit test builds
+ * its operator with; the arithmetic of torch.optim.Adagrad with initial_accumulator_value = 0, lr_decay = 0): per touched
+ * row r of table t and column d, with G as above,
+ *     gx       = G[d] + wd * W[r,d]   (L2)      |   G[d]   (NONE, DECOUPLE)
+ *     s[r,d]  += gx * gx
+ *     W[r,d]   = W[r,d] - lr * gx / (sqrt(s[r,d]) + eps)                        NONE, L2
+ *     W[r,d]   = (1 - lr * wd) * W[r,d] - lr * G[d] / (sqrt(s[r,d]) + eps)      DECOUPLE
+ * `state` is a device array [T] of fp32 buffers shaped [rows_t, dims_t]: one value per weight, always fp32.  `opt` is the
+ * row-wise calls' options struct (reserved = 0); stochastic_rounding as there.  Contract of pm_embbag_bwd_sorted_adagrad_ex /
+ * pm_embbag_bwd_fused_adagrad: same sort and workspace rules, same refusals (a two-phase sort, a relabelled workspace, more
+ * than 1024 tables, max_dim > 256 (fp32) / 512 (16-bit)), same determinism (a row's gradient is summed in lookup order for up
+ * to 256 lookups, in a fixed chunk order beyond).  NONE and L2 are pinned to torch.optim.Adagrad by the tests; DECOUPLE and
+ * stochastic rounding are restated only (no third-party implementation of them is at hand).
+ * The ABI version is unchanged (8): a client that needs these two finds out at symbol resolution.
+ */
+int pm_embbag_bwd_sorted_adagrad_elem(const pm_embbag_batch* op, const float* grad, void* const* tables,
+                                      int32_t table_dtype, float* const* state, const pm_rowwise_adagrad* opt,
+                                      int64_t max_rows, const void* workspace, int64_t workspace_bytes,
+                                      pm_stream_t stream);
+/* sort + apply in one call (may take the hybrid path) */
+int pm_embbag_bwd_fused_adagrad_elem(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype,
+                                     float* const* state, const pm_rowwise_adagrad* opt, int64_t max_rows, void* workspace,
+                                     int64_t workspace_bytes, pm_stream_t stream);
 
 /*
  * DLRM input redistribution on the device: regroup what the lengths / indices all-to-alls deliver

@@ -45,6 +45,8 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_bwd_sorted_adagrad_ex",
     "pm_embbag_bwd_fused",
     "pm_embbag_bwd_fused_adagrad",
+    "pm_embbag_bwd_sorted_adagrad_elem",
+    "pm_embbag_bwd_fused_adagrad_elem",
     "pm_dlrm_regroup",
     "pm_embbag_check",
     "pm_fill_random",
@@ -63,7 +65,7 @@ EXPORTED_SYMBOLS = (
 
 
 class pm_rowwise_adagrad(ctypes.Structure):
-    """Mirror of ``struct pm_rowwise_adagrad`` (include/param_amd.h)."""
+    """Mirror of ``struct pm_rowwise_adagrad`` (include/param_amd.h): the options of the row-wise and the element-wise calls."""
 
     _fields_ = [
         ("lr", ctypes.c_float),
@@ -191,6 +193,9 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embbag_bwd_fused_adagrad.restype = ctypes.c_int
     L.pm_embbag_bwd_fused_adagrad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, vp,
                                               ctypes.POINTER(pm_rowwise_adagrad), i64, vp, i64, vp]
+    for fn in (L.pm_embbag_bwd_sorted_adagrad_elem, L.pm_embbag_bwd_fused_adagrad_elem):      # state: [T] x fp32 [rows_t, dims_t]
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, vp, ctypes.POINTER(pm_rowwise_adagrad), i64, vp, i64, vp]
     L.pm_dlrm_regroup.restype = ctypes.c_int
     L.pm_dlrm_regroup.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp, vp]
     L.pm_embbag_check.restype = ctypes.c_int

@@ -11,10 +11,13 @@ on across tables, ``T*B+1`` entries) and the generator's alpha switch (0: ``aran
 <= 1: uniform, > 1: ``np.random.zipf(alpha) % E``).
 
 Stated differences: pooling must be SUM (PoolingMode 0, the only mode on the reference hot path); the
-optimizer fused into ``backward`` is plain SGD (``"sgd"``/``"exact_sgd"``) or exact row-wise Adagrad
-(``"exact_row_wise_adagrad"``, the reference's choice at comms_utils.py:2014) -- other optimizer names raise;
-weight decay (L2 / decoupled) and stochastic rounding of 16-bit tables apply to the row-wise Adagrad update (plain SGD
-updates round to nearest); ``device`` must be a ROCm device.
+optimizer fused into ``backward`` is plain SGD (``"sgd"``/``"exact_sgd"``), exact row-wise Adagrad
+(``"exact_row_wise_adagrad"``, the reference's choice at comms_utils.py:2014) or exact element-wise Adagrad
+(``"exact_adagrad"`` / ``"adagrad"`` / ``OptimType.EXACT_ADAGRAD``, what the reference's own unit test of this operator
+builds with: one fp32 state value per weight, ``torch.optim.Adagrad``'s arithmetic) -- other optimizer names raise
+(``optimizer_name`` below, callable without a device); weight decay (L2 / decoupled) and stochastic rounding of 16-bit
+tables apply to both Adagrad updates (plain SGD updates round to nearest); the element-wise update takes tables up to 256
+(fp32) / 512 (16-bit) columns wide, like the row-wise one; ``device`` must be a ROCm device.
 """
 from __future__ import annotations
 
@@ -74,6 +77,21 @@ def _wd_mode(mode):
     return mode
 
 
+def optimizer_name(optimizer) -> str:
+    """The module's ``optimizer=`` for a TBE optimizer given as name or fbgemm ``OptimType`` member (``"sgd"`` |
+    ``"rowwise_adagrad"`` | ``"adagrad"``); raises ``ValueError`` for every optimizer the backward does not fuse.  Needs no device."""
+    opt = optimizer.value if hasattr(optimizer, "value") else optimizer
+    opt = str(opt).lower().rsplit(".", 1)[-1]
+    if opt in ("sgd", "exact_sgd"):
+        return "sgd"
+    if opt in ("exact_row_wise_adagrad", "exact_rowwise_adagrad", "rowwise_adagrad", "row_wise_adagrad"):
+        return "rowwise_adagrad"   # fbgemm OptimType.EXACT_ROWWISE_ADAGRAD ("exact_row_wise_adagrad")
+    if opt in ("exact_adagrad", "adagrad"):
+        return "adagrad"           # fbgemm OptimType.EXACT_ADAGRAD ("exact_adagrad"): element-wise
+    raise ValueError(f"optimizer {optimizer!r}: the MI355X backward fuses plain SGD, exact row-wise Adagrad and exact "
+                     "element-wise Adagrad only")
+
+
 class SplitTableBatchedEmbeddingBagsCodegenOp(OperatorInterface):
     def __init__(self):
         super().__init__()
@@ -91,13 +109,7 @@ class SplitTableBatchedEmbeddingBagsCodegenOp(OperatorInterface):
         dims_list = dims if isinstance(dims, list) else [dims] * num_tables
         if int(pooling) != 0:
             raise ValueError("only PoolingMode.SUM (0) is implemented on the MI355X path")
-        opt = str(optimizer).lower()
-        if opt in ("sgd", "exact_sgd"):
-            opt = "sgd"
-        elif opt in ("exact_row_wise_adagrad", "exact_rowwise_adagrad", "rowwise_adagrad", "row_wise_adagrad"):
-            opt = "rowwise_adagrad"   # fbgemm OptimType.EXACT_ROWWISE_ADAGRAD ("exact_row_wise_adagrad")
-        else:
-            raise ValueError(f"optimizer {optimizer!r}: the MI355X backward fuses plain SGD and exact row-wise Adagrad only")
+        opt = optimizer_name(optimizer)
         if not str(self.device).startswith(("cuda", "rocm")):
             raise ValueError(f"Unknown compute device {self.device} (the MI355X operator needs a ROCm device)")
         dev = "cuda" + str(self.device)[4:] if str(self.device).startswith("rocm") else str(self.device)

@@ -1,7 +1,7 @@
 // param_amd/csrc/bwd_sorted_apply.h -- private to the sorted backward: the apply kernels' argument block, the destination
 // element types and the launchers.  Included by embbag_bwd_sorted.hip (host logic) and by the three per-dtype translation
 // units embbag_bwd_sorted_{f32,bf16,f16}.hip, which hold the kernel instantiations -- 3 dtypes x 2 key widths x 4 lane-group
-// sizes x weighted x optimizer x 3 tile sizes of main + fix-up kernels compile in parallel instead of in one 2.5-minute unit.
+// sizes x weighted x 3 optimizers x 3 tile sizes of main + fix-up kernels compile in parallel instead of in one 2.5-minute unit.
 #pragma once
 
 #include <type_traits>
@@ -65,6 +65,8 @@ struct SortedParams {
     int32_t unique_wgs_per_cu;   // bag-major apply: > 0 = a grid of this many workgroups per CU that loop over the tiles (0: one per tile)
     int32_t join_tiles;      // 1: a tile that lies wholly inside one run hands the fix-up ONE partial sum instead of one per chunk (set by
                              // the apply's launcher: it needs every lane group to make the same number of column passes)
+    float* const* state;     // element-wise Adagrad: device array [T] of fp32 [rows_t, dims_t] state, one value per weight (else NULL;
+                             // never together with mom).  Last, so that no earlier field moves.
 };
 
 

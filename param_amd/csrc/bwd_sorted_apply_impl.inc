@@ -201,19 +201,24 @@ hipError_t launch_apply_t(SortedParams sp, hipStream_t stream) {
     // TILE instead of one per chunk).  The groups of such a tile meet at a barrier once per column pass: every lane must make the
     // same number of passes (row-wise Adagrad: one pass, all lanes).
     static const int join_env = [] { const char* e = getenv("PARAM_AMD_JOIN_TILES"); return e ? atoi(e) : 1; }();        // once per process
-    sp.join_tiles = (join_env != 0 && sp.exact_run < TILE && !(sp.mom && sp.psw) && (sp.mom || sp.max_dim % (G * DST::kVec) == 0)) ? 1 : 0;
+    const bool adagrad = sp.mom || sp.state;       // row-wise / element-wise: one column pass either way
+    sp.join_tiles = (join_env != 0 && sp.exact_run < TILE && !(adagrad && sp.psw) && (adagrad || sp.max_dim % (G * DST::kVec) == 0)) ? 1 : 0;
 #define PM_LAUNCH_SORTED(W_, OPT_)                                                                                   \
     do {                                                                                                             \
         hipLaunchKernelGGL((bwd_sorted_main_kernel<DST, K, G, W_, OPT_, TILE>), g1, blk,                             \
-                           static_cast<size_t>(sp.T) * ((OPT_) == 1 ? 28 : 20), stream, sp);                        \
+                           static_cast<size_t>(sp.T) * ((OPT_) != 0 ? 28 : 20), stream, sp);                        \
         hipLaunchKernelGGL((bwd_sorted_fixup_kernel<DST, K, G, W_, OPT_, TILE>), g2, blk, 0, stream, sp, n_chunks); \
     } while (0)
     // one (main, fix-up) pair per bag phase, in stream order: phase 0 has updated a row before phase 1 touches it
     for (int ph = 0; ph < sp.H; ++ph) {
         sp.phase = ph;
-        if (sp.mom) {  // row-wise Adagrad: one column pass with all G lanes (cross-lane reduction)
-            if (sp.max_dim > G * DST::kVec || sp.H != 1) return hipErrorInvalidValue;
-            if (sp.psw) PM_LAUNCH_SORTED(true, 1); else PM_LAUNCH_SORTED(false, 1);
+        if (adagrad) {  // one column pass with all G lanes (row-wise: cross-lane reduction; element-wise keeps the rule)
+            if (sp.max_dim > G * DST::kVec || sp.H != 1 || (sp.mom && sp.state)) return hipErrorInvalidValue;
+            if (sp.state) {
+                if (sp.psw) PM_LAUNCH_SORTED(true, 2); else PM_LAUNCH_SORTED(false, 2);
+            } else {
+                if (sp.psw) PM_LAUNCH_SORTED(true, 1); else PM_LAUNCH_SORTED(false, 1);
+            }
         } else {
             if (sp.psw) PM_LAUNCH_SORTED(true, 0); else PM_LAUNCH_SORTED(false, 0);
         }
@@ -250,10 +255,12 @@ hipError_t launch_unique_g(const SortedParams& sp, const KParams& kp, const Uniq
     const dim3 grid(n_wg), blk(kBlock);
     const size_t lds = tile_lds_bytes(kp.bags_per_block, kp.idx_cap, false);
     const int g = group_lanes(max_dim, DST::kVec);
-    if (sp.mom && max_dim > g * DST::kVec) return hipErrorInvalidValue;
+    if ((sp.mom || sp.state) && max_dim > g * DST::kVec) return hipErrorInvalidValue;
 #define PM_LAUNCH_UNIQUE(G_)                                                                                                         \
     do {                                                                                                                             \
-        if (sp.mom) hipLaunchKernelGGL((bwd_unique_kernel<DST, G_, 1>), grid, blk, lds, stream, sp, kp, ua.hyb_tab, ua.bloom, ua.emit_keys,  \
+        if (sp.state) hipLaunchKernelGGL((bwd_unique_kernel<DST, G_, 2>), grid, blk, lds, stream, sp, kp, ua.hyb_tab, ua.bloom, ua.emit_keys, \
+                                         ua.emit_vals, ua.key_bytes, ua.tile_cnt, ua.tile_cnt_stride, ua.bloom_wbits);                \
+        else if (sp.mom) hipLaunchKernelGGL((bwd_unique_kernel<DST, G_, 1>), grid, blk, lds, stream, sp, kp, ua.hyb_tab, ua.bloom, ua.emit_keys,  \
                                        ua.emit_vals, ua.key_bytes, ua.tile_cnt, ua.tile_cnt_stride, ua.bloom_wbits);                  \
         else hipLaunchKernelGGL((bwd_unique_kernel<DST, G_, 0>), grid, blk, lds, stream, sp, kp, ua.hyb_tab, ua.bloom, ua.emit_keys,         \
                                 ua.emit_vals, ua.key_bytes, ua.tile_cnt, ua.tile_cnt_stride, ua.bloom_wbits);                         \
@@ -276,7 +283,7 @@ hipError_t launch_rest_g(const SortedParams& sp, const KParams& kp, const RestAr
     const dim3 grid(static_cast<unsigned>(ra.T_h) * static_cast<unsigned>(ra.parts)), blk(kRestThreads);
     const size_t lds = static_cast<size_t>(2 * kRestCap + kRestAux) * sizeof(uint32_t);
     const int g = group_lanes(max_dim, DST::kVec);
-    if (sp.mom && max_dim > g * DST::kVec) return hipErrorInvalidValue;
+    if ((sp.mom || sp.state) && max_dim > g * DST::kVec) return hipErrorInvalidValue;
     // (the attribute is asked for once per instantiation and process)
 #define PM_LAUNCH_REST_O(G_, OPT_)                                                                                                  \
     do {                                                                                                                            \
@@ -287,7 +294,9 @@ hipError_t launch_rest_g(const SortedParams& sp, const KParams& kp, const RestAr
     } while (0)
 #define PM_LAUNCH_REST(G_)                                                    \
     do {                                                                      \
-        if (sp.mom) PM_LAUNCH_REST_O(G_, 1); else PM_LAUNCH_REST_O(G_, 0);    \
+        if (sp.state) PM_LAUNCH_REST_O(G_, 2);                                \
+        else if (sp.mom) PM_LAUNCH_REST_O(G_, 1);                             \
+        else PM_LAUNCH_REST_O(G_, 0);                                         \
     } while (0)
     switch (g) {
         case 8: PM_LAUNCH_REST(8); break;

@@ -647,9 +647,14 @@ int pm_embbag_bwd_fused(const pm_embbag_batch* op, const float* grad, void* cons
     return pm_embbag_bwd_sorted(op, grad, dst_tables, dst_dtype, alpha, max_rows, workspace, workspace_bytes, stream);
 }
 
-int pm_embbag_bwd_fused_adagrad(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype,
-                                float* const* momentum, const pm_rowwise_adagrad* opt, int64_t max_rows, void* workspace,
-                                int64_t workspace_bytes, pm_stream_t stream) {
+// the two fused Adagrad calls: `elem` = element-wise (state [rows_t, dims_t] per table), else row-wise (one value per row)
+static int sorted_adagrad(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype, float* const* state,
+                          bool elem, const pm_rowwise_adagrad* opt, int64_t max_rows, const void* workspace, int64_t workspace_bytes,
+                          pm_stream_t stream);
+
+static int fused_adagrad(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype, float* const* momentum,
+                         bool elem, const pm_rowwise_adagrad* opt, int64_t max_rows, void* workspace, int64_t workspace_bytes,
+                         pm_stream_t stream) {
     if (op && (op->num_indices == 0 || op->bag_count == 0)) return PM_OK;
     int rc = fused_apply_args_ok(op, grad, tables, table_dtype);
     if (rc != PM_OK) return rc;
@@ -660,12 +665,24 @@ int pm_embbag_bwd_fused_adagrad(const pm_embbag_batch* op, const float* grad, vo
     if (!opt) return fail(PM_ERR_INVALID, "optimizer options are NULL");
     if (opt->weight_decay_mode != PM_WD_NONE && opt->weight_decay_mode != PM_WD_L2 && opt->weight_decay_mode != PM_WD_DECOUPLE)
         return fail(PM_ERR_INVALID, "weight_decay_mode must be PM_WD_NONE, PM_WD_L2 or PM_WD_DECOUPLE");
-    if (!momentum) return fail(PM_ERR_INVALID, "grad / tables / momentum is NULL");
+    if (!momentum) return fail(PM_ERR_INVALID, elem ? "grad / tables / state is NULL" : "grad / tables / momentum is NULL");
     if (op->max_dim > 64 * ((table_dtype == PM_F32) ? 4 : 8))
-        return fail(PM_ERR_UNSUPPORTED, "row-wise Adagrad needs max_dim <= " + std::to_string(64 * ((table_dtype == PM_F32) ? 4 : 8)) + " for this table dtype");
+        return fail(PM_ERR_UNSUPPORTED, std::string(elem ? "element-wise" : "row-wise") + " Adagrad needs max_dim <= " + std::to_string(64 * ((table_dtype == PM_F32) ? 4 : 8)) + " for this table dtype");
     rc = sort_request(op, max_rows, 1, workspace, workspace_bytes, stream, true);
     if (rc != PM_OK) return rc;
-    return pm_embbag_bwd_sorted_adagrad_ex(op, grad, tables, table_dtype, momentum, opt, max_rows, workspace, workspace_bytes, stream);
+    return sorted_adagrad(op, grad, tables, table_dtype, momentum, elem, opt, max_rows, workspace, workspace_bytes, stream);
+}
+
+int pm_embbag_bwd_fused_adagrad(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype,
+                                float* const* momentum, const pm_rowwise_adagrad* opt, int64_t max_rows, void* workspace,
+                                int64_t workspace_bytes, pm_stream_t stream) {
+    return fused_adagrad(op, grad, tables, table_dtype, momentum, false, opt, max_rows, workspace, workspace_bytes, stream);
+}
+
+int pm_embbag_bwd_fused_adagrad_elem(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype,
+                                     float* const* state, const pm_rowwise_adagrad* opt, int64_t max_rows, void* workspace,
+                                     int64_t workspace_bytes, pm_stream_t stream) {
+    return fused_adagrad(op, grad, tables, table_dtype, state, true, opt, max_rows, workspace, workspace_bytes, stream);
 }
 
 int pm_embbag_sort_plan(const pm_embbag_batch* op, int64_t max_rows, int32_t phases, char* out, int32_t out_bytes) {
@@ -726,9 +743,10 @@ int pm_embbag_bwd_sorted(const pm_embbag_batch* op, const float* grad, void* con
     return PM_OK;
 }
 
-int pm_embbag_bwd_sorted_adagrad_ex(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype,
-                                    float* const* momentum, const pm_rowwise_adagrad* opt, int64_t max_rows,
-                                    const void* workspace, int64_t workspace_bytes, pm_stream_t stream) {
+static int sorted_adagrad(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype, float* const* momentum,
+                          bool elem, const pm_rowwise_adagrad* opt, int64_t max_rows, const void* workspace, int64_t workspace_bytes,
+                          pm_stream_t stream) {
+    const std::string kind = elem ? "element-wise" : "row-wise";
     pm::KParams p;
     int rc = make_params(op, table_dtype, p);
     if (rc != PM_OK) return rc;
@@ -737,10 +755,10 @@ int pm_embbag_bwd_sorted_adagrad_ex(const pm_embbag_batch* op, const float* grad
     if (opt->weight_decay_mode != PM_WD_NONE && opt->weight_decay_mode != PM_WD_L2 && opt->weight_decay_mode != PM_WD_DECOUPLE)
         return fail(PM_ERR_INVALID, "weight_decay_mode must be PM_WD_NONE, PM_WD_L2 or PM_WD_DECOUPLE");
     if (p.N == 0 || p.bag_count == 0) return PM_OK;
-    if (!grad || !tables || !momentum) return fail(PM_ERR_INVALID, "grad / tables / momentum is NULL");
+    if (!grad || !tables || !momentum) return fail(PM_ERR_INVALID, elem ? "grad / tables / state is NULL" : "grad / tables / momentum is NULL");
     const int vec = (table_dtype == PM_F32) ? 4 : 8;
     if (op->max_dim > 64 * vec)
-        return fail(PM_ERR_UNSUPPORTED, "row-wise Adagrad needs max_dim <= " + std::to_string(64 * vec) + " for this table dtype");
+        return fail(PM_ERR_UNSUPPORTED, kind + " Adagrad needs max_dim <= " + std::to_string(64 * vec) + " for this table dtype");
     size_t need = 0;
     hipError_t h = pm::sorted_workspace_bytes(p, max_rows, op->max_dim, need);
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_bwd_sorted_adagrad");
@@ -750,7 +768,7 @@ int pm_embbag_bwd_sorted_adagrad_ex(const pm_embbag_batch* op, const float* grad
         const int pc = pm::bwd_sorted_plan_check(p, max_rows, workspace, true);
         if (pc == 3) return fail(PM_ERR_INVALID, kRelabelledMsg);
         if (pc == 2)
-            return fail(PM_ERR_INVALID, "the request was sorted for a two-phase scatter-add apply; row-wise Adagrad needs "
+            return fail(PM_ERR_INVALID, "the request was sorted for a two-phase scatter-add apply; " + kind + " Adagrad needs "
                                         "pm_embbag_sort_indices (phases = 1)");
         if (pc != 0)
             return fail(PM_ERR_INVALID, "pm_embbag_sort_indices has not been called for this request on this workspace (same indices / offsets pointers, batch, bag slice and weights as the sort's)");
@@ -759,9 +777,22 @@ int pm_embbag_bwd_sorted_adagrad_ex(const pm_embbag_batch* op, const float* grad
     p.tables = const_cast<const void* const*>(tables);
     p.alpha = 1.0f;
     if (g_nt_loads.load() < 0) p.nt_loads = kDefaultRowPolicy;
-    h = pm::bwd_sorted_apply(p, max_rows, table_dtype, op->max_dim, workspace, momentum, opt, static_cast<hipStream_t>(stream));
+    h = pm::bwd_sorted_apply(p, max_rows, table_dtype, op->max_dim, workspace, elem ? nullptr : momentum, opt, static_cast<hipStream_t>(stream),
+                             elem ? momentum : nullptr);
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_bwd_sorted_adagrad launch");
     return PM_OK;
+}
+
+int pm_embbag_bwd_sorted_adagrad_ex(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype,
+                                    float* const* momentum, const pm_rowwise_adagrad* opt, int64_t max_rows,
+                                    const void* workspace, int64_t workspace_bytes, pm_stream_t stream) {
+    return sorted_adagrad(op, grad, tables, table_dtype, momentum, false, opt, max_rows, workspace, workspace_bytes, stream);
+}
+
+int pm_embbag_bwd_sorted_adagrad_elem(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype,
+                                      float* const* state, const pm_rowwise_adagrad* opt, int64_t max_rows,
+                                      const void* workspace, int64_t workspace_bytes, pm_stream_t stream) {
+    return sorted_adagrad(op, grad, tables, table_dtype, state, true, opt, max_rows, workspace, workspace_bytes, stream);
 }
 
 int pm_embbag_bwd_sorted_adagrad(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype,

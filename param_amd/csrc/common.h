@@ -192,7 +192,8 @@ int sorted_pairs_info(const KParams& p, int64_t max_rows, int max_dim, const voi
                       const uint32_t** d_count, int* key_bytes, int* tshift);
 std::string sort_plan_describe(const KParams& p, int64_t max_rows, int64_t fixed_pooling, int phases);
 hipError_t bwd_sorted_apply(const KParams& p, int64_t max_rows, int dst_dtype, int max_dim, const void* workspace,
-                            float* const* momentum, const pm_rowwise_adagrad* opt, hipStream_t stream);
+                            float* const* momentum, const pm_rowwise_adagrad* opt, hipStream_t stream,
+                            float* const* elem_state = nullptr);      // element-wise Adagrad: [T] x [rows_t, dims_t] fp32 (momentum NULL then)
 
 #ifdef PM_ALTERNATES
 // own stable LSD radix sort of (key, uint32) pairs (radix_sort.hip); element count optionally read from device memory

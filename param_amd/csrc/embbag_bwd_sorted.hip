@@ -628,7 +628,7 @@ int sorted_pairs_info(const KParams& p, int64_t max_rows, int max_dim, const voi
 }
 
 hipError_t bwd_sorted_apply(const KParams& p, int64_t max_rows, int dst_dtype, int max_dim, const void* workspace,
-                            float* const* momentum, const pm_rowwise_adagrad* opt, hipStream_t stream) {
+                            float* const* momentum, const pm_rowwise_adagrad* opt, hipStream_t stream, float* const* elem_state) {
     SortPlan g;
     {
         std::lock_guard<std::mutex> lock(g_plan_mutex);
@@ -667,6 +667,7 @@ hipError_t bwd_sorted_apply(const KParams& p, int64_t max_rows, int dst_dtype, i
     sp.nt_rows = p.nt_loads;
     sp.alpha = p.alpha;
     sp.mom = momentum;
+    sp.state = elem_state;
     sp.lr = opt ? opt->lr : 0.0f;
     sp.eps = opt ? opt->eps : 0.0f;
     sp.wd = opt ? opt->weight_decay : 0.0f;

@@ -36,6 +36,10 @@
 //      the sum of squares is a per-lane partial reduced across the G lanes of the group with
 //      wave shuffles (xor butterfly), so every lane of the group must take part: one column pass only
 //      (max_dim <= G * VEC, checked by the launcher).
+//   2  exact element-wise Adagrad (fbgemm's EXACT_ADAGRAD, the optimizer the reference's own TBE unit test builds with;
+//      torch.optim.Adagrad's arithmetic): G as for 1, one fp32 state value per WEIGHT ([rows, D] beside the table), finished
+//      per lane (adagrad_elem_finish below).  The state's 16 (fp32 tables) / 2 x 16 (16-bit tables) bytes per lane ride with the
+//      row's load and leave with its store.  Same launch rules as 1 (one column pass, H == 1, no tile join when weighted).
 
 // (register budget: the fp32 scatter-add instance compiles to 82-86 VGPRs = 5 waves per SIMD without being told to.
 //  Forcing 6 waves -- __launch_bounds__(kBlock, 6): 80 VGPRs, 4-38 spilled -- measured Zipf apply 0.97 -> 0.94 ms but
@@ -85,6 +89,58 @@ __device__ __forceinline__ void adagrad_finish(char* wptr, float (&wrow)[DST::kV
         }
         if (p.sr) DST::store_sr(wptr, wrow, nt_rows, p.sr_seed, rowkey, c);
         else DST::store(wptr, wrow, nt_rows);
+    }
+}
+
+// finish one row under exact ELEMENT-wise Adagrad (OPT 2: torch.optim.Adagrad's arithmetic with initial_accumulator_value = 0 and
+// lr_decay = 0; fbgemm's EXACT_ADAGRAD): one fp32 state value per weight, so a lane finishes its own VEC columns and nothing
+// crosses lanes.  Called only by lanes that hold columns of the row (c < D).  `st` came in with the row's load; it leaves with
+// the row's store, under the same cache policy.
+//     gx = G + wd * w (L2) | G            s = s_old + gx * gx
+//     w  = w - (lr * gx) / (sqrt(s) + eps)                          NONE, L2  (torch: addcdiv_(grad, std, value = -lr))
+//     w  = (1 - lr * wd) * w - (lr * G) / (sqrt(s) + eps)           DECOUPLE
+// (16-byte state accesses per lane and row: 1 for fp32 tables, 2 for 16-bit tables)
+template <typename DST>
+__device__ __forceinline__ void adagrad_elem_finish(char* wptr, float (&wrow)[DST::kVec], const float (&acc)[DST::kVec],
+                                                    const float (&st)[DST::kVec], float* st_ptr, const SortedParams& p, int nt_rows,
+                                                    uint64_t rowkey, int c) {
+    const float keep = p.wd_mode == PM_WD_DECOUPLE ? 1.0f - p.lr * p.wd : 1.0f;
+    // four columns at a time, their 16 bytes of state stored as soon as they are complete (nothing of the new state stays live)
+#pragma unroll
+    for (int k4 = 0; k4 < DST::kVec; k4 += 4) {
+        float s_new[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = k4 + j;
+            const float reg = p.wd_mode == PM_WD_L2 ? p.wd * wrow[k] : 0.0f;
+            const float gx = acc[k] + reg;
+            const float sq = gx * gx;
+            s_new[j] = st[k] + sq;
+            const float denom = sqrtf(s_new[j]) + p.eps;
+            const float num = p.lr * gx;
+            const float step = num / denom;
+            const float kept = p.wd_mode == PM_WD_DECOUPLE ? keep * wrow[k] : wrow[k];
+            wrow[k] = kept - step;
+        }
+        raw16_store(reinterpret_cast<char*>(st_ptr + k4),
+                    u32x4{__float_as_uint(s_new[0]), __float_as_uint(s_new[1]), __float_as_uint(s_new[2]), __float_as_uint(s_new[3])}, nt_rows);
+    }
+    if (p.sr) DST::store_sr(wptr, wrow, nt_rows, p.sr_seed, rowkey, c);
+    else DST::store(wptr, wrow, nt_rows);
+}
+// the state values of one row's VEC columns as loaded (raw until consumed, like the row: see the main kernel's batch) ...
+template <int VEC>
+__device__ __forceinline__ void state_load_raw(const void* p, u32x4 (&raw)[VEC / 4], int nt_rows) {
+#pragma unroll
+    for (int k = 0; k < VEC / 4; ++k) raw[k] = raw16_load(reinterpret_cast<const char*>(p) + 16 * k, nt_rows);
+}
+// ... and as numbers
+template <int VEC>
+__device__ __forceinline__ void state_widen(const u32x4 (&raw)[VEC / 4], float (&st)[VEC]) {
+#pragma unroll
+    for (int k = 0; k < VEC / 4; ++k) {
+        st[4 * k] = __uint_as_float(raw[k].x); st[4 * k + 1] = __uint_as_float(raw[k].y);
+        st[4 * k + 2] = __uint_as_float(raw[k].z); st[4 * k + 3] = __uint_as_float(raw[k].w);
     }
 }
 
@@ -149,7 +205,14 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
 #ifndef PM_KBATCH_16
 #define PM_KBATCH_16 2
 #endif
-    constexpr int kBatch = DST::kES == 2 ? PM_KBATCH_16 : PM_KBATCH_F32;
+    // Element-wise Adagrad on 16-bit tables: ONE position per trip of the general path (gradient 2 x 16 B + row + state 2 x 16 B = 5
+    // loads in flight) and four per trip deep inside a run (8 loads).  At two positions per trip every fp16 instance and the bf16
+    // instances with 64-bit keys came to 129-143 VGPRs -- the open run's 8 state values and the batch's 2 x 8 sit on top of what the
+    // row-wise instance holds -- past the 128 this kernel's occupancy counts on (4 waves per SIMD); asking the compiler for 128
+    // spilled 12-36 bytes.  One position: at most 115 VGPRs over all 16-bit instances, no scratch.
+    constexpr bool kLean = OPT == 2 && DST::kES == 2;
+    constexpr int kBatch = DST::kES == 2 ? (kLean ? 1 : PM_KBATCH_16) : PM_KBATCH_F32;
+    constexpr int kDeepMul = kLean ? 4 : PM_RUN_DEEP;
     constexpr int VEC = DST::kVec;
     constexpr int NG = kBlock / G;
     constexpr int C = TILE / NG;
@@ -170,7 +233,7 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
     char** s_dst = reinterpret_cast<char**>(s_tab);
     int64_t* s_ooff = reinterpret_cast<int64_t*>(s_tab + static_cast<size_t>(p.T) * 8);
     float** s_mom = reinterpret_cast<float**>(s_tab + static_cast<size_t>(p.T) * 16);
-    int32_t* s_dim = reinterpret_cast<int32_t*>(s_tab + static_cast<size_t>(p.T) * (OPT == 1 ? 24 : 16));
+    int32_t* s_dim = reinterpret_cast<int32_t*>(s_tab + static_cast<size_t>(p.T) * (OPT != 0 ? 24 : 16));
 
     const K* keys = reinterpret_cast<const K*>(p.keys);
     const int nt_rows = p.nt_rows;
@@ -230,6 +293,7 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
         s_ooff[t] = p.out_offsets[t];
         s_dim[t] = p.dims[t];
         if (OPT == 1) s_mom[t] = p.mom[t];
+        if (OPT == 2) s_mom[t] = p.state[t];      // [rows, D] fp32, one value per weight
     }
     __syncthreads();
     PM_STAMP(blockIdx.x, 1);
@@ -238,7 +302,7 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
     // its chunks' partials added in chunk order here, instead of NG of them: the fix-up's chain of partial-sum round trips and
     // its walk over the chunk records are NG times shorter (119 us -> see HISTORY r5 at the N = 8 Zipf shape).  Uniform over
     // the workgroup (LDS keys); every group of such a tile is in mode 1 from its first position to its last.
-    constexpr bool kJoin = !(WEIGHTED && OPT == 1);    // (that instance has no registers to spare: 130 VGPRs with the join; the launcher agrees)
+    constexpr bool kJoin = !(WEIGHTED && OPT != 0);    // (that instance has no registers to spare: 130 VGPRs with the join; the launcher agrees)
     __shared__ float s_join[kJoin ? kBlock * VEC : 1];
     const bool tile_joined = kJoin && p.join_tiles && n_tile == TILE && s_key[1] == s_key[TILE] && s_key[0] == s_key[1] &&
                              s_key[TILE + 1] == s_key[1] && !(s_key[1] & pad_bit);
@@ -296,8 +360,8 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
     const int l1e = l1 + own_after;      // end of this group's walk (<= n_tile)
     PM_STAMP(blockIdx.x, 2);
 
-    // OPT 1: exactly one pass in which EVERY lane of the group takes part (cross-lane reduction inside)
-    const int c_end = OPT == 1 ? lig * VEC + 1 : p.max_dim;
+    // OPT 1: exactly one pass in which EVERY lane of the group takes part (cross-lane reduction inside); OPT 2 keeps the rule
+    const int c_end = OPT != 0 ? lig * VEC + 1 : p.max_dim;
     for (int c = lig * VEC; c < c_end; c += G * VEC) {
         // mode: 0 closed, 1 leading piece (partial from zero), 2 in-chunk run, 3 trailing piece (partial from zero)
         int mode = 0;
@@ -307,17 +371,24 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
         float acc[VEC];
         float wrow[VEC];                // OPT 1: the destination row, held until the run's gradient is complete
         float cur_mom = 0.0f;           // OPT 1: the open run's optimizer state, fetched together with its row
+        constexpr int SV = OPT == 2 ? VEC : 1;
+        float srow[SV];                 // OPT 2: the open run's state values of this lane's columns, fetched together with its row
         K cur_key = 0;                  // key of the open run: row pointer, state pointer and row length are re-derived
                                         // from it when the run closes (keeping them live across the batch cost the
                                         // kernel a fifth wave per SIMD)
 #pragma unroll
         for (int k = 0; k < VEC; ++k) { acc[k] = 0.0f; wrow[k] = 0.0f; }
+#pragma unroll
+        for (int k = 0; k < SV; ++k) srow[k] = 0.0f;
         const char* const dummy_fast = reinterpret_cast<const char*>(p.partials) + static_cast<size_t>(lig) * VEC * sizeof(float);
         auto close_run = [&](K key, float (&a)[VEC], float (&w)[VEC], bool cols, float m_prev) {
             const int t = static_cast<int>(key >> p.tshift);
             const int64_t row = static_cast<int64_t>(key & row_mask);
             const int D = s_dim[t];
             char* wptr = s_dst[t] + (row * D + c) * DST::kES;
+            if constexpr (OPT == 2) {
+                if (cols) adagrad_elem_finish<DST>(wptr, w, a, srow, s_mom[t] + row * D + c, p, nt_rows, static_cast<uint64_t>(key), c);
+            } else
             if (OPT == 1) adagrad_finish<DST, G>(wptr, w, a, cols, s_mom[t] + row, m_prev, D, p, lig, nt_rows, static_cast<uint64_t>(key), c);
             else if (cols) DST::store(wptr, a, nt_rows);
         };
@@ -340,8 +411,8 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
                     const int64_t stride = any_col ? p.out_stride : 0;
                     const int64_t bextra = any_col ? p.gblk_extra : 0;      // blocked gradient layout (0: none)
                     // deep inside a run (the next batch continues it as well): twice the gradient rows per trip
-                    constexpr int kDeep = PM_RUN_DEEP * kBatch;
-                    bool deep = PM_RUN_DEEP > 1 && pos + kDeep <= l1e;
+                    constexpr int kDeep = kDeepMul * kBatch;
+                    bool deep = kDeepMul > 1 && pos + kDeep <= l1e;
 #pragma unroll
                     for (int u = kBatch; u < kDeep; ++u) deep = deep && s_key[pos + (u < kDeep ? u : 0) + 1] == cur_key;
                     if (deep) {
@@ -404,6 +475,7 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
                                             // row is loaded (a zero there costs a register copy behind a full wait per position)
             float sc[kBatch];
             float mv[kBatch];
+            u32x4 sraw[kBatch][OPT == 2 ? VEC / 4 : 1];      // OPT 2: the state values as loaded (unset where no row is loaded)
             bool col_ok[kBatch];
             // Straight-line: every position of the batch issues its gradient load and its row load, whatever it is -- a position
             // that needs none (past the chunk's end, not the head of a run) reads a harmless, cache-resident address instead
@@ -438,6 +510,9 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
                 }
                 // in-chunk runs need the destination row; the trailing open run does not
                 wraw[u] = DST::load_raw(need_row ? s_dst[t] + (row * D + c) * DST::kES : dummy, nt_rows);
+                // element-wise Adagrad: the state of the lane's columns is issued right behind the row, from the same test
+                if constexpr (OPT == 2)
+                    state_load_raw<VEC>(need_row ? reinterpret_cast<const char*>(s_mom[t] + row * D + c) : dummy, sraw[u], nt_rows);
             }
             // consume in sorted order
 #pragma unroll
@@ -477,9 +552,10 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
                         DST::widen(wraw[u], wv);
 #pragma unroll
                         for (int k = 0; k < VEC; ++k) {
-                            if (OPT == 1) wrow[k] = wv[k];   // Adagrad: gradient accumulates from zero
+                            if (OPT != 0) wrow[k] = wv[k];   // Adagrad: gradient accumulates from zero
                             else acc[k] = wv[k];             // SGD: accumulate on top of the row, lookup order
                         }
+                        if constexpr (OPT == 2) state_widen<VEC>(sraw[u], srow);
                     }
                 }
                 if (mode != 0 && any_col) {
@@ -501,6 +577,10 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
                 for (int k = 0; k < VEC; ++k) asm volatile("" : : "v"(gv[u][k]));
                 asm volatile("" : : "v"(wraw[u]));
                 asm volatile("" : : "v"(mv[u]), "v"(sc[u]));
+                if constexpr (OPT == 2) {
+#pragma unroll
+                    for (int k = 0; k < VEC / 4; ++k) asm volatile("" : : "v"(sraw[u][k]));
+                }
             }
         }
         // close the last segment of the chunk
@@ -654,17 +734,24 @@ __device__ __forceinline__ void fixup_one_run(const SortedParams& p, int64_t h, 
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 
-    const int c_end = OPT == 1 ? lig * VEC + 1 : D;
+    const int c_end = OPT != 0 ? lig * VEC + 1 : D;
     for (int c = lig * VEC; c < c_end; c += G * VEC) {
         const bool any_col = c < D;
         char* wptr = reinterpret_cast<char*>(p.dst[t]) + (row * D + c) * DST::kES;
         float acc[VEC];
         float wrow[VEC];
+        float srow[OPT == 2 ? VEC : 1];      // OPT 2: the state of this lane's columns, loaded with the row
+        float* const st_ptr = OPT == 2 ? p.state[t] + row * D + c : nullptr;
 #pragma unroll
         for (int k = 0; k < VEC; ++k) { acc[k] = 0.0f; wrow[k] = 0.0f; }
         if (any_col) {
-            if (OPT == 1) DST::load(wptr, wrow, nt_rows);
+            if (OPT != 0) DST::load(wptr, wrow, nt_rows);
             else DST::load(wptr, acc, nt_rows);
+            if constexpr (OPT == 2) {
+                u32x4 sraw[VEC / 4];
+                state_load_raw<VEC>(st_ptr, sraw, nt_rows);
+                state_widen<VEC>(sraw, srow);
+            }
         }
         float mom_prev = 0.0f;
         if (OPT == 1) mom_prev = *as_global<float>(p.mom[t] + row);
@@ -732,6 +819,9 @@ __device__ __forceinline__ void fixup_one_run(const SortedParams& p, int64_t h, 
                 }
             }
         }
+        if constexpr (OPT == 2) {
+            if (any_col) adagrad_elem_finish<DST>(wptr, wrow, acc, srow, st_ptr, p, nt_rows, static_cast<uint64_t>(key), c);
+        } else
         if (OPT == 1) adagrad_finish<DST, G>(wptr, wrow, acc, any_col, p.mom[t] + row, mom_prev, D, p, lig, nt_rows, static_cast<uint64_t>(key), c);
         else DST::store(wptr, acc, nt_rows);
     }
@@ -799,7 +889,9 @@ __global__ void __launch_bounds__(kBlock) bwd_unique_kernel(const SortedParams p
 #ifndef PM_UNIQUE_UB_16
 #define PM_UNIQUE_UB_16 4
 #endif
-    constexpr int UB = DST::kES == 2 ? PM_UNIQUE_UB_16 : PM_UNIQUE_UB_F32;     // row loads a lane group keeps in flight
+    // row loads a lane group keeps in flight (element-wise Adagrad on 16-bit tables: half as many rows, each with 2 x 16 bytes of state
+    // behind it -- 6 loads in flight where the other 16-bit instances have 4, inside the kernel's 128 VGPRs)
+    constexpr int UB = (DST::kES == 2 ? PM_UNIQUE_UB_16 : PM_UNIQUE_UB_F32) / (OPT == 2 && DST::kES == 2 ? 2 : 1);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_next;
     // The grid may be smaller than the number of tiles (launcher: PARAM_AMD_UNIQUE_WGS_PER_CU): a workgroup then takes the tiles
@@ -888,7 +980,7 @@ __global__ void __launch_bounds__(kBlock) bwd_unique_kernel(const SortedParams p
     const int64_t row_bytes = static_cast<int64_t>(D) * DST::kES;
     char* W = reinterpret_cast<char*>(const_cast<void*>(q.tables[t]));
     const float* grad_t = p.grad + q.out_offsets[t];
-    float* mom_t = OPT == 1 ? p.mom[t] : nullptr;
+    float* mom_t = OPT == 1 ? p.mom[t] : (OPT == 2 ? p.state[t] : nullptr);      // OPT 2: [rows, D], one value per weight
     const int nt_rows = p.nt_rows;
     const char* const dummy = reinterpret_cast<const char*>(p.partials) + static_cast<size_t>(lig) * VEC * sizeof(float);
     const uint64_t tkey = static_cast<uint64_t>(t) << p.tshift;
@@ -899,7 +991,7 @@ __global__ void __launch_bounds__(kBlock) bwd_unique_kernel(const SortedParams p
         auto walk = [&](auto staged_c) {
             constexpr bool ST = decltype(staged_c)::value;
             // OPT 1: one pass in which every lane of the group takes part (cross-lane reduction inside adagrad_finish)
-            const int c_end = OPT == 1 ? lig * VEC + 1 : D;
+            const int c_end = OPT != 0 ? lig * VEC + 1 : D;
             for (int c = lig * VEC; c < c_end; c += G * VEC) {
                 const bool any_col = c < D;
                 float ga[VEC];
@@ -915,6 +1007,7 @@ __global__ void __launch_bounds__(kBlock) bwd_unique_kernel(const SortedParams p
                     uint32_t rr[UB];
                     u32x4 raw[UB];
                     float mv[UB];
+                    u32x4 sraw[UB][OPT == 2 ? VEC / 4 : 1];      // OPT 2: the rows' state values, loaded with the rows
                     char* ptr[UB];
 #pragma unroll
                     for (int u = 0; u < UB; ++u) {      // straight-line: positions past the bag read its last lookup again (dropped below)
@@ -934,6 +1027,9 @@ __global__ void __launch_bounds__(kBlock) bwd_unique_kernel(const SortedParams p
                         raw[u] = DST::load_raw((live && any_col) ? ptr[u] : dummy, nt_rows);
                         mv[u] = 0.0f;
                         if (OPT == 1) mv[u] = *as_global<float>(live ? mom_t + row : reinterpret_cast<const float*>(dummy));
+                        if constexpr (OPT == 2)
+                            state_load_raw<VEC>((live && any_col) ? reinterpret_cast<const char*>(mom_t + static_cast<uint64_t>(row) * static_cast<uint32_t>(D) + c) : dummy,
+                                                sraw[u], nt_rows);
                     }
 #pragma unroll
                     for (int u = 0; u < UB; ++u) {
@@ -941,6 +1037,17 @@ __global__ void __launch_bounds__(kBlock) bwd_unique_kernel(const SortedParams p
                         if (live) {
                             float w[VEC];
                             DST::widen(raw[u], w);
+                            if constexpr (OPT == 2) {
+                                if (any_col) {
+                                    float acc[VEC], st[VEC];
+#pragma unroll
+                                    for (int k = 0; k < VEC; ++k) acc[k] = 0.0f + ga[k];                 // the sorted apply's "from zero"
+                                    state_widen<VEC>(sraw[u], st);
+                                    const uint32_t row = rr[u] & 0x7fffffffu;
+                                    adagrad_elem_finish<DST>(ptr[u], w, acc, st, mom_t + static_cast<uint64_t>(row) * static_cast<uint32_t>(D) + c, p, nt_rows,
+                                                             tkey | row, c);
+                                }
+                            } else
                             if (OPT == 1) {
                                 float acc[VEC];
 #pragma unroll
@@ -958,6 +1065,10 @@ __global__ void __launch_bounds__(kBlock) bwd_unique_kernel(const SortedParams p
                     for (int u = 0; u < UB; ++u) {      // every loaded register counts as read (see the main kernel's batch)
                         asm volatile("" : : "v"(raw[u]));
                         asm volatile("" : : "v"(mv[u]));
+                        if constexpr (OPT == 2) {
+#pragma unroll
+                            for (int k = 0; k < VEC / 4; ++k) asm volatile("" : : "v"(sraw[u][k]));
+                        }
                     }
                 }
             }
@@ -1016,7 +1127,7 @@ __global__ void __launch_bounds__(kRestThreads) hyb_rest_kernel(const SortedPara
     constexpr int NW = kRestThreads / kWave;
     // sorted positions whose loads a lane group issues together (the Adagrad instances, whose finish keeps the row and the state
     // live, take half: at the full depth they spill)
-    constexpr int KB = (DST::kES == 2 ? PM_REST_KB_16 : PM_REST_KB_F32) / (OPT == 1 ? 2 : 1);
+    constexpr int KB = (DST::kES == 2 ? PM_REST_KB_16 : PM_REST_KB_F32) / (OPT != 0 ? 2 : 1);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint32_t* const s_key = reinterpret_cast<uint32_t*>(smem);
     uint32_t* const s_val = s_key + kRestCap;
@@ -1136,23 +1247,30 @@ __global__ void __launch_bounds__(kRestThreads) hyb_rest_kernel(const SortedPara
     const int D = q.dims[t];
     char* const W = reinterpret_cast<char*>(const_cast<void*>(q.tables[t]));
     const float* const grad_t = p.grad + q.out_offsets[t];
-    float* const mom_t = OPT == 1 ? p.mom[t] : nullptr;
+    float* const mom_t = OPT == 1 ? p.mom[t] : (OPT == 2 ? p.state[t] : nullptr);
     const int nt_rows = p.nt_rows;
     const uint64_t tkey = static_cast<uint64_t>(t) << p.tshift;
     const char* const dummy = reinterpret_cast<const char*>(p.partials) + static_cast<size_t>(lig) * VEC * sizeof(float);
     PM_STAMP_DRAINED(trace_id, 4);
     // OPT 1: one pass in which every lane of the group takes part (cross-lane reduction inside adagrad_finish)
-    const int c_end = OPT == 1 ? lig * VEC + 1 : D;
+    const int c_end = OPT != 0 ? lig * VEC + 1 : D;
     for (int c = lig * VEC; c < c_end; c += G * VEC) {
         const bool any_col = c < D;
         float acc[VEC], wrow[VEC];
+        constexpr int SV = OPT == 2 ? VEC : 1;
+        float srow[SV];                     // OPT 2: the open run's state values of this lane's columns
 #pragma unroll
         for (int k = 0; k < VEC; ++k) { acc[k] = 0.0f; wrow[k] = 0.0f; }
+#pragma unroll
+        for (int k = 0; k < SV; ++k) srow[k] = 0.0f;
         float cur_mom = 0.0f;
         uint32_t cur_row = 0;
         bool open = false;
         auto close_run = [&]() {
             char* wptr = W + (static_cast<int64_t>(cur_row) * D + c) * DST::kES;
+            if constexpr (OPT == 2) {
+                if (any_col) adagrad_elem_finish<DST>(wptr, wrow, acc, srow, mom_t + static_cast<int64_t>(cur_row) * D + c, p, nt_rows, tkey | cur_row, c);
+            } else
             if (OPT == 1) adagrad_finish<DST, G>(wptr, wrow, acc, any_col, mom_t + cur_row, cur_mom, D, p, lig, nt_rows, tkey | cur_row, c);
             else if (any_col) DST::store(wptr, acc, nt_rows);
         };
@@ -1170,6 +1288,7 @@ __global__ void __launch_bounds__(kRestThreads) hyb_rest_kernel(const SortedPara
             float gv[KB][VEC];
             u32x4 wraw[KB];
             float mv[KB];
+            u32x4 sraw[KB][OPT == 2 ? VEC / 4 : 1];
 #pragma unroll
             for (int u = 0; u < KB; ++u) {      // every load of the batch before the first add; positions that need none read a harmless address
                 const float* g = (valid[u] && any_col) ? grad_t + grad_bag_offset(static_cast<int64_t>(bg[u]), q.out_stride, q.gblk_shift, q.gblk_extra) + c
@@ -1182,6 +1301,8 @@ __global__ void __launch_bounds__(kRestThreads) hyb_rest_kernel(const SortedPara
                 wraw[u] = DST::load_raw((head[u] && any_col) ? W + (static_cast<int64_t>(rw[u]) * D + c) * DST::kES : dummy, nt_rows);
                 mv[u] = 0.0f;
                 if (OPT == 1) mv[u] = *as_global<float>(head[u] ? mom_t + rw[u] : reinterpret_cast<const float*>(dummy));
+                if constexpr (OPT == 2)
+                    state_load_raw<VEC>((head[u] && any_col) ? reinterpret_cast<const char*>(mom_t + static_cast<int64_t>(rw[u]) * D + c) : dummy, sraw[u], nt_rows);
             }
 #pragma unroll
             for (int u = 0; u < KB; ++u) {
@@ -1198,9 +1319,10 @@ __global__ void __launch_bounds__(kRestThreads) hyb_rest_kernel(const SortedPara
                             DST::widen(wraw[u], wv);
 #pragma unroll
                             for (int k = 0; k < VEC; ++k) {
-                                if (OPT == 1) wrow[k] = wv[k];   // Adagrad: the gradient accumulates from zero
+                                if (OPT != 0) wrow[k] = wv[k];   // Adagrad: the gradient accumulates from zero
                                 else acc[k] = wv[k];             // SGD: on top of the row, lookup order
                             }
+                            if constexpr (OPT == 2) state_widen<VEC>(sraw[u], srow);
                         }
                     }
                     if (any_col) {
@@ -1218,6 +1340,10 @@ __global__ void __launch_bounds__(kRestThreads) hyb_rest_kernel(const SortedPara
                 for (int k = 0; k < VEC; ++k) asm volatile("" : : "v"(gv[u][k]));
                 asm volatile("" : : "v"(wraw[u]));
                 asm volatile("" : : "v"(mv[u]));
+                if constexpr (OPT == 2) {
+#pragma unroll
+                    for (int k = 0; k < VEC / 4; ++k) asm volatile("" : : "v"(sraw[u][k]));
+                }
             }
         }
         if (open) close_run();

@@ -456,8 +456,10 @@ _WD_MODES = {None: _lib.PM_WD_NONE, "none": _lib.PM_WD_NONE, 0: _lib.PM_WD_NONE,
 
 def _adagrad(ts: _TableSet, grad, indices, offsets, B, mom_ptrs_dev, lr: float, eps: float, psw=None,
              presorted: bool = False, weight_decay: float = 0.0, weight_decay_mode=None, stochastic_rounding: bool = False,
-             seed: int = 0, pooling: Optional[int] = None):
-    """Fused backward + exact row-wise Adagrad on the tables of ``ts`` (``pm_embbag_bwd_sorted_adagrad_ex``)."""
+             seed: int = 0, pooling: Optional[int] = None, elementwise: bool = False):
+    """Fused backward + exact row-wise Adagrad on the tables of ``ts`` (``pm_embbag_bwd_sorted_adagrad_ex``), or, with
+    ``elementwise``, exact element-wise Adagrad (``pm_embbag_bwd_sorted_adagrad_elem``: ``mom_ptrs_dev`` then points at one
+    fp32 ``[rows_t, dims_t]`` state buffer per table)."""
     if weight_decay_mode not in _WD_MODES:
         raise ValueError(f"weight_decay_mode must be one of none / l2 / decouple, got {weight_decay_mode!r}")
     _require_device(grad, "grad")
@@ -469,6 +471,8 @@ def _adagrad(ts: _TableSet, grad, indices, offsets, B, mom_ptrs_dev, lr: float, 
     op = ts.request(indices, offsets, B, psw, 0, None)
     L = _lib.load()
     wdt, s = _WDTYPE[ts.dtype], _stream_ptr()
+    fused_call = L.pm_embbag_bwd_fused_adagrad_elem if elementwise else L.pm_embbag_bwd_fused_adagrad
+    sorted_call = L.pm_embbag_bwd_sorted_adagrad_elem if elementwise else L.pm_embbag_bwd_sorted_adagrad_ex
     # (more than 1024 tables: one call per table range, as in _bwd.  A stochastic-rounding draw is keyed by the seed, the table's
     # number INSIDE its call, the row and the column pair: every range gets a seed of its own -- the first one the caller's -- so
     # that table t and table t + 1024 do not share their draws)
@@ -479,14 +483,12 @@ def _adagrad(ts: _TableSet, grad, indices, offsets, B, mom_ptrs_dev, lr: float, 
         tabs, mom = ts.d_ptrs.data_ptr() + 8 * t0, mom_ptrs_dev.data_ptr() + 8 * t0
         if not presorted and not _lib.needs_pooling_hint():
             sub.fixed_pooling = 0
-            _lib.check(L.pm_embbag_bwd_fused_adagrad(ctypes.byref(sub), grad.data_ptr(), tabs, wdt, mom, ctypes.byref(opt), max_rows,
-                                                     ws.data_ptr(), ws.numel(), s))
+            _lib.check(fused_call(ctypes.byref(sub), grad.data_ptr(), tabs, wdt, mom, ctypes.byref(opt), max_rows, ws.data_ptr(), ws.numel(), s))
             continue
         if not presorted:
             sub.fixed_pooling = ts.fixed_pooling(indices, offsets, B, pooling) if sub is op else 0
             _lib.check(L.pm_embbag_sort_indices_ex(ctypes.byref(sub), max_rows, 1, ws.data_ptr(), ws.numel(), s))
-        _lib.check(L.pm_embbag_bwd_sorted_adagrad_ex(ctypes.byref(sub), grad.data_ptr(), tabs, wdt, mom, ctypes.byref(opt), max_rows,
-                                                     ws.data_ptr(), ws.numel(), s))
+        _lib.check(sorted_call(ctypes.byref(sub), grad.data_ptr(), tabs, wdt, mom, ctypes.byref(opt), max_rows, ws.data_ptr(), ws.numel(), s))
 
 
 def _sparse_grad_call(ts: _TableSet, op, grad, max_rows: int, dims: Sequence[int]):
@@ -673,12 +675,12 @@ class BatchedEmbeddingBagMI355(nn.Module):
         self.rows, self.dims, self.layout = rows, dims, layout
         self.block_bags = block_bags      # layout="blocked": [B / block_bags, T, block_bags, D] (the per-rank batch of a sharded exchange)
         self.learning_rate, self.fused_update = learning_rate, fused_update
-        if optimizer not in ("sgd", "rowwise_adagrad"):
-            raise ValueError('optimizer must be "sgd" or "rowwise_adagrad"')
+        if optimizer not in ("sgd", "rowwise_adagrad", "adagrad"):
+            raise ValueError('optimizer must be "sgd", "rowwise_adagrad" or "adagrad"')
         self.optimizer, self.eps = optimizer, eps
         if weight_decay_mode not in _WD_MODES:
             raise ValueError(f"weight_decay_mode must be one of none / l2 / decouple, got {weight_decay_mode!r}")
-        # row-wise Adagrad options of the reference's TBE operator (split_table_batched_embeddings_ops.py:289-300)
+        # Adagrad options (row-wise and element-wise) of the reference's TBE operator (split_table_batched_embeddings_ops.py:289-300)
         self.weight_decay, self.weight_decay_mode = weight_decay, weight_decay_mode
         self.stochastic_rounding = stochastic_rounding      # 16-bit tables only; fp32 tables ignore it
         self._sr_step = 0
@@ -694,7 +696,8 @@ class BatchedEmbeddingBagMI355(nn.Module):
         self.weights = nn.Parameter(torch.empty(cur, dtype=dtype, device=device), requires_grad=False)
         self._starts, self._sizes = starts, sizes
         self._anchor = nn.Parameter(torch.zeros((), device=device))  # lets autograd reach backward()
-        # row-wise Adagrad state, one fp32 per row: a buffer (follows .to() / state_dict), allocated on first use
+        # Adagrad state -- row-wise: one fp32 per row; element-wise ("adagrad"): one fp32 per weight, sum(rows_t * dims_t) values --
+        # a buffer (follows .to() / state_dict), allocated on first use
         self.register_buffer("momentum", None)
         self._ts: Optional[_TableSet] = None
         if init is not None:
@@ -777,7 +780,7 @@ class BatchedEmbeddingBagMI355(nn.Module):
         the module's optimizer is): the fused row-wise Adagrad needs a one-phase sort, the scatter-add apply may use two."""
         B = self._batch_of(offsets, indices) if batch is None else batch
         if for_adagrad is None:
-            for_adagrad = self.optimizer == "rowwise_adagrad"
+            for_adagrad = self.optimizer in ("rowwise_adagrad", "adagrad")
         _sort_indices(self._tables(), indices, offsets, B, per_sample_weights, phases=1 if for_adagrad else 2, pooling=pooling)
 
     def scatter_add_(self, grad, indices, offsets, alpha: float, per_sample_weights=None,
@@ -796,18 +799,23 @@ class BatchedEmbeddingBagMI355(nn.Module):
         return sort_status(self._tables(), indices, offsets, B, per_sample_weights, bag_begin, bag_count)
 
     def momentum_table(self, t: int) -> torch.Tensor:
-        """row-wise Adagrad state of table t (allocated zero on first use)"""
+        """Adagrad state of table t (allocated zero on first use): ``[rows_t]`` for ``optimizer="rowwise_adagrad"``,
+        ``[rows_t, dims_t]`` for the element-wise ``optimizer="adagrad"``"""
+        elem = self.optimizer == "adagrad"
+        per_row = self.dims if elem else [1] * len(self.rows)      # state values per table row
         if self.momentum is None:
-            self.momentum = torch.zeros(sum(self.rows), dtype=torch.float32, device=self.weights.device)
+            self.momentum = torch.zeros(sum(r * w for r, w in zip(self.rows, per_row)), dtype=torch.float32, device=self.weights.device)
         if self._mom_base != (self.momentum.data_ptr(), self.momentum.device):     # first use, or moved by .to()
             starts = [0]
-            for r in self.rows[:-1]:
-                starts.append(starts[-1] + r)
+            for r, w in zip(self.rows[:-1], per_row[:-1]):
+                starts.append(starts[-1] + r * w)
             self._mom_starts = starts
             self._mom_ptrs = torch.tensor([self.momentum.data_ptr() + 4 * s for s in starts], dtype=torch.int64,
                                           device=self.momentum.device)
             self._mom_base = (self.momentum.data_ptr(), self.momentum.device)
         s = self._mom_starts[t]
+        if elem:
+            return self.momentum[s:s + self.rows[t] * self.dims[t]].view(self.rows[t], self.dims[t])
         return self.momentum[s:s + self.rows[t]]
 
     def adagrad_step_(self, grad, indices, offsets, per_sample_weights=None, batch: Optional[int] = None,
@@ -815,18 +823,21 @@ class BatchedEmbeddingBagMI355(nn.Module):
         """Fused backward + exact row-wise Adagrad (TBE ``EXACT_ROWWISE_ADAGRAD``, the optimizer the reference
         configures at comms_utils.py:2014): ``m[r] += mean_d(G[r,d]^2); W[r] -= lr / (sqrt(m[r]) + eps) * G[r]``,
         with the module's ``weight_decay`` / ``weight_decay_mode`` (l2 | decouple) and, for 16-bit tables,
-        ``stochastic_rounding``."""
+        ``stochastic_rounding``.  With ``optimizer="adagrad"``: exact ELEMENT-wise Adagrad (TBE ``EXACT_ADAGRAD``,
+        ``torch.optim.Adagrad``'s arithmetic), one state value per weight: ``s[r,d] += G[r,d]^2;
+        W[r,d] -= lr * G[r,d] / (sqrt(s[r,d]) + eps)``, same options (l2 adds ``wd * W`` to ``G`` first).  (Called on a module of
+        any other optimizer, the step is the row-wise one, as before.)"""
         self.momentum_table(0)
         B = self._batch_of(offsets, indices) if batch is None else batch
         self._sr_step += 1          # a fresh stochastic-rounding stream every step, reproducible run to run
         _adagrad(self._tables(), grad, indices, offsets, B, self._mom_ptrs, self.learning_rate, self.eps,
                  per_sample_weights, presorted, self.weight_decay, self.weight_decay_mode, self.stochastic_rounding,
-                 seed=0x5EED0000 + self._sr_step, pooling=pooling)
+                 seed=0x5EED0000 + self._sr_step, pooling=pooling, elementwise=self.optimizer == "adagrad")
 
     def optimizer_step_(self, grad, indices, offsets, per_sample_weights=None, batch: Optional[int] = None,
                         presorted: bool = False):
         """what ``.backward()`` applies when ``fused_update`` is on"""
-        if self.optimizer == "rowwise_adagrad":
+        if self.optimizer in ("rowwise_adagrad", "adagrad"):
             self.adagrad_step_(grad, indices, offsets, per_sample_weights, batch, presorted)
         else:
             self.scatter_add_(grad, indices, offsets, alpha=-self.learning_rate, per_sample_weights=per_sample_weights,
