@@ -69,18 +69,46 @@ def ulp16(x, dtype: int) -> np.ndarray:
     return np.ldexp(1.0, np.where(m == 0, emin, np.maximum(ex - 1, emin)) - man)
 
 
+def max16(dtype: int) -> float:
+    """largest finite value of the 16-bit table type"""
+    return float(np.ldexp(2.0 - 2.0 ** -7, 127)) if dtype == BF16 else 65504.0
+
+
 def down16(x, dtype: int) -> np.ndarray:
-    """largest value of the 16-bit grid at or below x (fp64; no overflow handling: for finite in-range values)"""
+    """largest value of the 16-bit grid at or below x (fp64).  The grid ends at +-max16: below -max16 the answer is -Inf, above
+    max16 it is max16; Inf and NaN are their own neighbours."""
     x = np.asarray(x, dtype=np.float64)
     u = ulp16(x, dtype)
-    return np.floor(x / u) * u
+    top = max16(dtype)
+    with np.errstate(invalid="ignore", over="ignore"):
+        y = np.where(np.isfinite(x), np.floor(x / u) * u, x)
+    return np.where(y > top, np.where(np.isfinite(x), top, y), np.where(y < -top, -np.inf, y))
 
 
 def up16(x, dtype: int) -> np.ndarray:
-    """smallest value of the 16-bit grid at or above x"""
+    """smallest value of the 16-bit grid at or above x: the upper neighbour of anything above max16 is +Inf"""
     x = np.asarray(x, dtype=np.float64)
     u = ulp16(x, dtype)
-    return np.ceil(x / u) * u
+    top = max16(dtype)
+    with np.errstate(invalid="ignore", over="ignore"):
+        y = np.where(np.isfinite(x), np.ceil(x / u) * u, x)
+    return np.where(y < -top, np.where(np.isfinite(x), -top, y), np.where(y > top, np.inf, y))
+
+
+def fma_f32(a, b, c) -> np.ndarray:
+    """``fmaf(a, b, c)``: a * b + c in fp32 with ONE rounding.  The product of two fp32 values is exact in fp64; the fp64 sum is
+    rounded to odd (its error, from the two-sum, sets the last bit), so that the final rounding to fp32 cannot be a double
+    rounding (53 >= 24 + 2 bits).  Inf and NaN pass through as the hardware passes them."""
+    a, b, c = (np.asarray(v, dtype=np.float32).astype(np.float64) for v in (a, b, c))
+    with np.errstate(invalid="ignore", over="ignore"):
+        p = a * b
+        s = np.asarray(p + c)
+        bb = s - p
+        e = (p - (s - bb)) + (c - bb)                                  # two-sum: p + c = s + e exactly (finite s)
+        fix = np.isfinite(s) & (e != 0) & ((s.view(np.int64) & 1) == 0)
+        up = (e > 0) == (s > 0)                                        # towards larger magnitude: the next bit pattern
+        s = np.where(fix, (s.view(np.int64) + np.where(up, 1, -1)).view(np.float64), s)
+        return s.astype(np.float32)
 
 
 def embbag_fwd_np(W: np.ndarray, idx, off, psw=None) -> np.ndarray:
@@ -98,9 +126,7 @@ def embbag_fwd_np(W: np.ndarray, idx, off, psw=None) -> np.ndarray:
                 raise IndexError(f"index {r} out of range [0,{W.shape[0]})")
             row = W[r]
             if psw is not None:
-                # fused multiply-add (one rounding): the f32*f32 product is exact in
-                # f64, so add in f64 and round once
-                acc = (acc.astype(np.float64) + np.float64(psw[j]) * row.astype(np.float64)).astype(np.float32)
+                acc = fma_f32(np.float32(psw[j]), row, acc)          # fused multiply-add: one rounding
             else:
                 acc = (acc + row).astype(np.float32)
         out[b] = acc

@@ -31,26 +31,35 @@ def quantize_rows(x: np.ndarray, bits: int) -> np.ndarray:
     if bits == 16:
         with np.errstate(over="ignore"):                                   # beyond fp16 range: inf, as torch's cast
             return x.astype(np.float16).view(np.uint8).reshape(n, 2 * dim)
-    mn, mx = x.min(axis=1), x.max(axis=1)
+    # the extremes as std::min_element / std::max_element find them: the FIRST minimal / maximal element, so a row whose minimum (or
+    # maximum) is zero stores the sign of its first zero; numpy's min / max pick a sign by their own reduction order.  +0 and -0
+    # compare equal and argmin / argmax return the first occurrence.  (torch's vectorised prepack agrees wherever the zeros of the
+    # two signs sit in different columns modulo 8; where they share such a column its result follows its SIMD reduction and is
+    # not pinned: tests/test_special_values_host.py.)
+    at = np.arange(n)
+    mn, mx = x[at, x.argmin(axis=1)], x[at, x.argmax(axis=1)]
     if bits == 8:
-        rng = mx - mn
-        scale = rng / np.float32(255.0)
-        inv = np.float32(255.0) / (rng + np.float32(1e-8))
-        codes = np.rint((x - mn[:, None]) * inv[:, None]).astype(np.uint8)
+        with np.errstate(over="ignore", invalid="ignore"):                 # a range beyond fp32: inf, codes 0 (as torch)
+            rng = mx - mn
+            scale = rng / np.float32(255.0)
+            inv = np.float32(255.0) / (rng + np.float32(1e-8))
+            codes = np.rint((x - mn[:, None]) * inv[:, None]).astype(np.uint8)
         tail = np.stack([scale, mn], axis=1).astype(np.float32).view(np.uint8).reshape(n, 8)
         return np.concatenate([codes, tail], axis=1)
     levels = np.float32((1 << bits) - 1)
-    bias_h = mn.astype(np.float16)
+    with np.errstate(over="ignore"):
+        bias_h = mn.astype(np.float16)
     bias = bias_h.astype(np.float32)
-    rng = mx - bias
-    with np.errstate(divide="ignore", over="ignore"):
+    with np.errstate(divide="ignore", over="ignore", invalid="ignore"):
+        rng = mx - bias
         scale_h = np.where(rng == 0, np.float32(1), rng / levels).astype(np.float16)
         scale_h = np.where(scale_h == 0, np.float16(1), scale_h)
         inv = np.float32(1) / scale_h.astype(np.float32)
     bad = np.isinf(inv)
     scale_h = np.where(bad, np.float16(1), scale_h).astype(np.float16)
     inv = np.where(bad, np.float32(1), inv).astype(np.float32)
-    q = np.clip(np.rint((x - bias[:, None]) * inv[:, None]), 0, levels).astype(np.uint8)
+    with np.errstate(over="ignore", invalid="ignore"):
+        q = np.clip(np.rint((x - bias[:, None]) * inv[:, None]), 0, levels).astype(np.uint8)
     per = 8 // bits
     packed = np.zeros((n, dim // per), np.uint8)
     for k in range(per):

@@ -54,12 +54,19 @@ def grad_sum_f32(rows, idx, loc_off, g, psw=None):
     return G, count
 
 
-def step_f32(w, s, G, touched, lr, eps, wd=0.0, wd_code=WD_NONE):
-    """one step in fp32, operation by operation as stated above; returns new (w, s).  ``touched``: boolean per row."""
+def step_f32(w, s, G, touched, lr, eps, wd=0.0, wd_code=WD_NONE, torch_fused=False):
+    """one step in fp32, operation by operation as stated above; returns new (w, s).  ``touched``: boolean per row.
+    ``torch_fused``: form ``gx = fma(wd, w, G)`` and ``s = fma(gx, gx, s_old)`` with one rounding each, which is what torch's CPU
+    ``grad.add(param, alpha=wd)`` and ``state_sum.addcmul_(grad, grad)`` evaluate; the kernels (built without contraction) and this
+    restatement by default round the products first -- the TWO operations in which they depart from torch's bits, by a last place
+    (tests/test_special_values_host.py pins every other operation bit for bit through this switch)."""
     w, s, G = (np.asarray(a, dtype=np.float32) for a in (w, s, G))
     lr, eps, wd = np.float32(lr), np.float32(eps), np.float32(wd)
-    gx = (G + wd * w).astype(np.float32) if wd_code == WD_L2 else G
-    s_new = (s + gx * gx).astype(np.float32)
+    if wd_code == WD_L2:
+        gx = O.fma_f32(wd, w, G) if torch_fused else (G + wd * w).astype(np.float32)
+    else:
+        gx = G
+    s_new = O.fma_f32(gx, gx, s) if torch_fused else (s + gx * gx).astype(np.float32)
     step = ((lr * gx) / (np.sqrt(s_new) + eps)).astype(np.float32)
     kept = ((np.float32(1.0) - lr * wd) * w).astype(np.float32) if wd_code == WD_DECOUPLE else w
     w_new = (kept - step).astype(np.float32)
