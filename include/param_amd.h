@@ -279,8 +279,8 @@ int pm_embbag_sort_status(const pm_embbag_batch* op, int64_t max_rows, const voi
  *                                    at row_ids[t] -- for any run length.  May be repeated (another `grad`) until the next sort.
  * Same request rules, limits and refusals as the sorted backward (at most 1024 tables: split larger requests by tables, the calls are
  * independent; num_indices and batch below 2^32; dims multiples of 4), checked before anything is launched.  The sort must keep rows
- * ascending within a table: after pm_set_sort_tuning(1) the count call returns PM_ERR_UNSUPPORTED.  Gradients with respect to
- * per_sample_weights are not computed.
+ * ascending within a table: after pm_set_sort_tuning(1) the count call returns PM_ERR_UNSUPPORTED.  The gradient with respect to
+ * per_sample_weights is a call of its own: pm_embbag_psw_grad.
  */
 int64_t pm_embbag_sparse_grad_workspace(const pm_embbag_batch* op, int64_t max_rows);
 int pm_embbag_sparse_grad_count(const pm_embbag_batch* op, int64_t max_rows, void* workspace, int64_t workspace_bytes,
@@ -358,6 +358,32 @@ int pm_embbag_bwd_sorted_adagrad_elem(const pm_embbag_batch* op, const float* gr
 int pm_embbag_bwd_fused_adagrad_elem(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype,
                                      float* const* state, const pm_rowwise_adagrad* opt, int64_t max_rows, void* workspace,
                                      int64_t workspace_bytes, pm_stream_t stream);
+
+/*
+ * Gradient of per_sample_weights -- the one piece of mode="sum" autograd the table backwards above do not give: for every
+ * lookup j of a bag (t, b) inside [bag_begin, bag_begin + bag_count)
+ *     out[j] = sum_{c < D_t} grad(t, b)[c] * table_t[indices[j], c]
+ * `grad` is addressed as the sorted backward addresses it: out_offsets[t] + b * out_stride, plus the blocked term
+ * (b >> grad_block_shift) * grad_block_extra.  `out` is fp32 [num_indices], indexed like `indices`; lookups of bags outside the
+ * slice are not written.  The value does not depend on the weights: op->per_sample_weights is ignored and may be NULL.  Run it
+ * BEFORE an in-place update of the tables (the fused backwards): the gradient belongs to the weights the forward read.
+ * Arithmetic, fixed so that the result is deterministic and independent of the launch shape (numpy restates it exactly:
+ * tests/psw_grad_rules.py): table elements are widened to fp32 (exact); every product and every add is rounded to fp32 on its
+ * own -- no fused multiply-add, unlike the weighted forward; lane l of a lookup's lane group owns columns [l V, (l + 1) V), V = 4
+ * (fp32 tables) / 8 (16-bit tables), and adds its V products to +0 in ascending column order; the lane partials are combined by
+ * an xor butterfly with masks 1, 2, 4, .. up to half the group width, lanes past D_t / V holding +0.  Since x + 0 == x the value
+ * is the same for every power-of-two group width >= D_t / V: mixed-dim and max_dim-wide launches give the same bits.
+ * One gather over the rows the forward read (D_t * e row bytes, the index and 4 bytes out per lookup; the gradient is read once
+ * per bag): no atomics, no workspace, no allocation, stream-ordered.  Tables fp32 / bf16 / fp16, indices int32 / int64, any
+ * number of tables.  max_dim <= 256 (fp32) / 512 (16-bit): wider requests get PM_ERR_UNSUPPORTED.  Request rules as
+ * pm_embbag_fwd, blocked-gradient rules as pm_embbag_bwd_fused; a NULL grad, or a NULL out with num_indices > 0, is
+ * PM_ERR_INVALID; an empty request is PM_OK without touching the device.
+ * Replaces aten::_embedding_bag_per_sample_weights_backward (autograd of the weighted lookups at train/compute/pt/pytorch_emb.py:40,61)
+ * and the indice_weights gradient of fbgemm's TBE backward (split_table_batched_embeddings_ops.py:318-324; the reference's TBE
+ * example, run_op_split_table_batched_embeddings.py, runs weighted).
+ * The ABI version is unchanged (8): a client that needs this call finds out at symbol resolution.
+ */
+int pm_embbag_psw_grad(const pm_embbag_batch* op, const float* grad, float* out, pm_stream_t stream);
 
 /*
  * DLRM input redistribution on the device: regroup what the lengths / indices all-to-alls deliver

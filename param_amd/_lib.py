@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_sparse_grad_workspace",
     "pm_embbag_sparse_grad_count",
     "pm_embbag_sparse_grad",
+    "pm_embbag_psw_grad",
 )
 
 
@@ -227,6 +228,8 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embbag_sparse_grad_count.argtypes = [ctypes.POINTER(pm_embbag_batch), i64, vp, i64, vp, vp]
     L.pm_embbag_sparse_grad.restype = ctypes.c_int
     L.pm_embbag_sparse_grad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i64, vp, i64, vp, vp, vp]
+    L.pm_embbag_psw_grad.restype = ctypes.c_int
+    L.pm_embbag_psw_grad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]

@@ -553,6 +553,24 @@ int pm_embbag_fwd_split(const pm_embbag_batch* op, float* out, pm_stream_t strea
     return PM_OK;
 }
 
+int pm_embbag_psw_grad(const pm_embbag_batch* op, const float* grad, float* out, pm_stream_t stream) {
+    pm::KParams p;
+    int rc = make_params(op, op ? op->weight_dtype : -1, p);   // (the blocked-gradient rules are make_params' own)
+    if (rc != PM_OK) return rc;
+    if (!grad) return fail(PM_ERR_INVALID, "grad is NULL");
+    if (!out && op->num_indices > 0) return fail(PM_ERR_INVALID, "out is NULL");
+    const int vec = op->weight_dtype == PM_F32 ? 4 : 8;
+    if (op->max_dim > pm::kWave * vec)
+        return fail(PM_ERR_UNSUPPORTED, "pm_embbag_psw_grad: max_dim must be at most " + std::to_string(pm::kWave * vec) +
+                                            " for this element type (one 16-byte load per lane of a 64-lane group)");
+    if (p.bag_count == 0 || p.N == 0) return PM_OK;
+    p.io = const_cast<float*>(grad);
+    p.psw = nullptr;                                            // the value does not depend on the weights
+    const hipError_t h = pm::launch_embbag_psw_grad(p, op->weight_dtype, op->max_dim, op->min_dim, out, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_psw_grad launch");
+    return PM_OK;
+}
+
 #ifdef PM_ALTERNATES
 int pm_embbag_bwd(const pm_embbag_batch* op, const float* grad, void* const* dst_tables, int32_t dst_dtype,
                   float alpha, pm_stream_t stream) {

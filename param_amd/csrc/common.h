@@ -172,6 +172,8 @@ __host__ __device__ inline size_t tile_lds_bytes(int bags_per_block, int idx_cap
 hipError_t launch_embbag_fwd(const KParams& p, int weight_dtype, int max_dim, int unroll,
                              hipStream_t stream);
 hipError_t launch_embbag_fwd_split(const KParams& p, int weight_dtype, int max_dim, hipStream_t stream);
+// gradient of per_sample_weights (embbag_psw_grad.hip): p.io = the gradient, out[N] fp32; min_dim as in pm_embbag_batch
+hipError_t launch_embbag_psw_grad(const KParams& p, int weight_dtype, int max_dim, int min_dim, float* out, hipStream_t stream);
 #ifdef PM_ALTERNATES
 hipError_t launch_embbag_bwd(const KParams& p, int dst_dtype, int max_dim, hipStream_t stream);   // the atomic backward (embbag_bwd.hip)
 #endif

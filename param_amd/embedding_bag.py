@@ -533,9 +533,31 @@ def _sparse_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, bag_begin=0
     return res
 
 
+def _psw_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, out=None, bag_begin=0, bag_count=None):
+    """Gradient of ``per_sample_weights`` (``pm_embbag_psw_grad``): fp32 ``[N]``, ``out[j] = <grad[t, bag(j)], table_t[indices[j]]>``
+    for the lookups of the bag slice, with the arithmetic fixed in include/param_amd.h.  ``psw`` only keeps the cached request
+    descriptor of the backward that follows: the value does not depend on it."""
+    _require_device(grad, "grad")
+    _, _, shape = ts.out_desc(B)
+    if grad.dtype != torch.float32 or tuple(grad.shape) != tuple(shape):
+        raise ValueError(f"grad must be float32 of shape {shape}")
+    grad = grad.contiguous()
+    op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
+    n = indices.numel()
+    if out is None:
+        out = torch.zeros(n, dtype=torch.float32, device=ts.device)      # lookups outside the slice (or outside every bag): zero
+    elif out.dtype != torch.float32 or out.numel() != n or not out.is_contiguous() or out.device != ts.device:
+        raise ValueError(f"out must be a contiguous float32 tensor of {n} entries on {ts.device}")
+    rc = _lib.load().pm_embbag_psw_grad(ctypes.byref(op), grad.data_ptr(), out.data_ptr(), _stream_ptr())
+    if rc:
+        _lib.check(rc)
+    return out
+
+
 class _DenseGradFn(torch.autograd.Function):
     """forward = batched lookup; backward = scatter-add into a dense fp32 weight.grad
-    (torch ``sparse=False`` semantics, aten::_embedding_bag_dense_backward)."""
+    (torch ``sparse=False`` semantics, aten::_embedding_bag_dense_backward), and -- for ``per_sample_weights`` that require it --
+    their gradient (aten::_embedding_bag_per_sample_weights_backward)."""
 
     @staticmethod
     def forward(ctx, weight, module, indices, offsets, psw):
@@ -553,9 +575,11 @@ class _DenseGradFn(torch.autograd.Function):
         ts = m._tables()
         dW = torch.zeros(m.weight.shape, dtype=torch.float32, device=grad_out.device)
         d_ptr = torch.tensor([dW.data_ptr()], dtype=torch.int64, device=grad_out.device)
-        _bwd(ts, grad_out.contiguous(), indices, offsets, ctx.B, d_ptr, torch.float32, 1.0,
+        grad_out = grad_out.contiguous()
+        _bwd(ts, grad_out, indices, offsets, ctx.B, d_ptr, torch.float32, 1.0,
              psw if ctx.has_psw else None)
-        return dW.to(m.weight.dtype), None, None, None, None
+        d_psw = _psw_grad(ts, grad_out, indices, offsets, ctx.B, psw) if ctx.has_psw and ctx.needs_input_grad[4] else None
+        return dW.to(m.weight.dtype), None, None, None, d_psw
 
 
 class _SparseGradFn(_DenseGradFn):
@@ -567,12 +591,14 @@ class _SparseGradFn(_DenseGradFn):
         indices, offsets, psw = ctx.saved_tensors
         m = ctx.module
         w = m.weight
-        ((rows, vals),) = _sparse_grad(m._tables(), grad_out.contiguous(), indices, offsets, ctx.B, psw if ctx.has_psw else None)
+        grad_out = grad_out.contiguous()
+        ((rows, vals),) = _sparse_grad(m._tables(), grad_out, indices, offsets, ctx.B, psw if ctx.has_psw else None)
+        d_psw = _psw_grad(m._tables(), grad_out, indices, offsets, ctx.B, psw) if ctx.has_psw and ctx.needs_input_grad[4] else None
         g = torch.sparse_coo_tensor(rows[None], vals.to(w.dtype), tuple(w.shape), is_coalesced=True)
         # autograd's accumulation into .grad keeps these very index / value tensors but drops the coalesced flag: the module's
         # post-accumulate hook sets it again when .grad still holds them (an accumulated sum of two steps is torch's own result)
         m._sparse_mark = (g._values().data_ptr(), g._indices().data_ptr())
-        return g, None, None, None, None
+        return g, None, None, None, d_psw
 
 
 class EmbeddingBagMI355(nn.Module):
@@ -637,7 +663,8 @@ class EmbeddingBagMI355(nn.Module):
 
 
 class _FusedUpdateFn(torch.autograd.Function):
-    """TBE-style: backward applies ``W[idx] += -lr * grad`` in place (no weight.grad)."""
+    """TBE-style: backward applies ``W[idx] += -lr * grad`` in place (no weight.grad); ``per_sample_weights`` that require grad get
+    theirs (fbgemm's ``indice_weights`` gradient), computed from the tables as the forward read them."""
 
     @staticmethod
     def forward(ctx, anchor, module, indices, offsets, psw):
@@ -649,8 +676,13 @@ class _FusedUpdateFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         indices, offsets, psw = ctx.saved_tensors
-        ctx.module.optimizer_step_(grad_out, indices, offsets, per_sample_weights=psw if ctx.has_psw else None)
-        return None, None, None, None, None
+        m = ctx.module
+        d_psw = None
+        if ctx.has_psw and ctx.needs_input_grad[4]:
+            # before the in-place update, on the same stream: the gradient belongs to the weights the forward read
+            d_psw = _psw_grad(m._tables(), grad_out, indices, offsets, m._batch_of(offsets, indices), psw)
+        m.optimizer_step_(grad_out, indices, offsets, per_sample_weights=psw if ctx.has_psw else None)
+        return None, None, None, None, d_psw
 
 
 class BatchedEmbeddingBagMI355(nn.Module):
@@ -861,9 +893,22 @@ class BatchedEmbeddingBagMI355(nn.Module):
         to ``sort_indices`` + ``scatter_add_(alpha=1, presorted=True)`` into zeroed fp32 tables, read at ``rows_t``).  A table with
         no lookups gives empty tensors.  ``grad`` has the shape ``scatter_add_`` takes for the module's layout.  The call
         synchronises once (to read the U_t and allocate exactly), as torch's ``coalesce()`` does -- once per 1024 tables for larger
-        requests, which are split into independent calls.  Gradients with respect to ``per_sample_weights`` are not computed."""
+        requests, which are split into independent calls.  The gradient with respect to ``per_sample_weights`` is a call of its
+        own: ``per_sample_weights_grad``."""
         B = self._batch_of(offsets, indices) if batch is None else batch
         return _sparse_grad(self._tables(), grad, indices, offsets, B, per_sample_weights, bag_begin, bag_count)
+
+    def per_sample_weights_grad(self, grad, indices, offsets, batch: Optional[int] = None, out=None, bag_begin=0, bag_count=None):
+        """Gradient of ``per_sample_weights``: fp32 ``[N]``, ``out[j] = sum_c grad[t, bag(j)][c] * table_t[indices[j], c]`` -- what
+        ``torch.nn.functional.embedding_bag(..., mode="sum", per_sample_weights=w)`` returns as ``w.grad`` and fbgemm's TBE as the
+        ``indice_weights`` gradient.  One gather kernel over the rows the forward read (``pm_embbag_psw_grad``), deterministic:
+        products and adds rounded to fp32 one by one in a fixed order (include/param_amd.h), the same bits for every launch shape.
+        ``grad`` has the shape ``scatter_add_`` takes for the module's layout.  ``bag_begin/bag_count`` select a batch slice:
+        entries of lookups outside it are zero in a tensor the method allocates and untouched in a caller's ``out``.  Any number
+        of tables (no sort, no workspace).  Call it BEFORE an in-place update of the tables."""
+        _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
+        B = self._batch_of(offsets, indices) if batch is None else batch
+        return _psw_grad(self._tables(), grad, indices, offsets, B, None, out, bag_begin, bag_count)
 
     def check(self, indices, offsets, per_sample_weights=None, batch: Optional[int] = None) -> None:
         B = self._batch_of(offsets, indices) if batch is None else batch
