@@ -70,10 +70,56 @@ int flat_target_knob(const FwdEnv& env) { const int k = g_flat_target.load(); re
 
 bool dtype_is_weight(int d) { return d == PM_F32 || d == PM_BF16 || d == PM_F16; }
 
+const char* const kNoSortRecorded = "no sort has been recorded for this workspace";
+
+// A request's launch parameters in three parts (defined below make_params): what can be refused -- for the element type the call
+// reads or writes the tables as --, the base parameters every entry point uses, and the forward's own tiling.
+int validate_request(const pm_embbag_batch* op, int elem_dtype, int* tile_bags_out = nullptr);
+void fill_params(const pm_embbag_batch* op, int elem_dtype, int bpb, pm::KParams& p);
+void plan_forward(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p);
+
 // Validate the host-visible part of a request and derive the launch geometry.
 // forward = the call is pm_embbag_fwd / pm_embbag_fwd_quantized: only those get the staged-output geometry (smaller tiles,
 // index tile sized for the request) and work tiles; every other entry point keeps the plain bag-count tiling.
 int make_params(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p, bool forward = false) {
+    int bpb = 0;
+    const int rc = validate_request(op, elem_dtype, &bpb);
+    if (rc != PM_OK) return rc;
+    fill_params(op, elem_dtype, bpb, p);
+    if (forward) plan_forward(op, elem_dtype, p);
+    return PM_OK;
+}
+
+// bags per tile of the plain bag-count tiling
+int tile_bags(const pm_embbag_batch* op, int elem_dtype) {
+    const int vec = (elem_dtype == PM_F32) ? 4 : 8;
+    const int G = pm::group_lanes(op->max_dim, vec);
+    const int NG = pm::kBlock / G;
+    int bpb = g_bags_per_block.load();
+    if (bpb <= 0) {
+        // 4 bags per lane group amortise the LDS staging; small requests shrink the tile until the
+        // grid fills the chip (256 CUs x 8 resident workgroups) -- a 16 K-bag single-table lookup
+        // ran 2 workgroups per CU at 49 % of the roofline with the fixed tile (gpurun r1e)
+        bpb = 4 * NG;
+        // Short average bags go with one bag per lane group: requests whose tables have very different bag
+        // sizes (Criteo multi-hot 1 .. 100, average 8.2) otherwise leave a few tables' workgroups 100x longer
+        // than the rest -- measured 7.2 (32 bags/tile) vs 14.3 G lookups/s (8); with uniform L = 20 the
+        // 32-bag tile is 3.5 % faster under Zipf and 2 % slower under uniform indices (sweeps r1f/r1g).
+        {
+            const int64_t tb = static_cast<int64_t>(op->num_tables) * op->batch;
+            if (tb > 0 && op->num_indices < 12 * tb) bpb = NG;
+        }
+        const int64_t want_blocks = 256 * 8;
+        while (bpb > NG && static_cast<int64_t>(op->num_tables) * ((op->bag_count + bpb - 1) / bpb) < want_blocks) bpb /= 2;
+    }
+    if (bpb < NG) bpb = NG;
+    if (bpb > 1024) bpb = 1024;
+    return bpb;
+}
+
+// Everything a request can be refused for on the host, in the order the checks have always run: the same input gives the same first
+// error.  tile_bags_out: the tile the grid was checked with.
+int validate_request(const pm_embbag_batch* op, int elem_dtype, int* tile_bags_out) {
     if (!op) return fail(PM_ERR_INVALID, "op is NULL");
     if (op->num_tables < 1) return fail(PM_ERR_INVALID, "num_tables must be >= 1");
     if (!dtype_is_weight(elem_dtype)) return fail(PM_ERR_INVALID, "weight/dst dtype must be PM_F32, PM_BF16 or PM_F16");
@@ -96,31 +142,23 @@ int make_params(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p, bool 
     if (op->fixed_pooling < 0 ||
         (op->fixed_pooling > 0 && op->fixed_pooling * op->batch * static_cast<int64_t>(op->num_tables) != op->num_indices))
         return fail(PM_ERR_INVALID, "fixed_pooling must be 0 or num_indices / (num_tables * batch)");
+    const int bpb = tile_bags(op, elem_dtype);
+    if ((op->bag_count + bpb - 1) / bpb * op->num_tables > 0x7fffffffLL) return fail(PM_ERR_UNSUPPORTED, "grid too large");
+    if (op->grad_block_shift < 0 || op->grad_block_shift > 31 || op->grad_block_extra < 0 || op->table_group < 0)
+        return fail(PM_ERR_INVALID, "grad_block_shift must be in [0, 31], grad_block_extra and table_group >= 0");
+    // a blocked gradient needs blocks of at least two bags that tile the batch (ADVICE r5: shift 0 with a non-zero extra used to read
+    // the un-blocked layout without a word, and so did a batch that is not a whole number of blocks)
+    if (op->grad_block_shift == 0 && op->grad_block_extra != 0)
+        return fail(PM_ERR_INVALID, "grad_block_extra needs grad_block_shift >= 1 (a block of one bag is the un-blocked layout)");
+    if (op->grad_block_shift > 0 && (op->batch & ((static_cast<int64_t>(1) << op->grad_block_shift) - 1)) != 0)
+        return fail(PM_ERR_INVALID, "batch must be a multiple of 2^grad_block_shift bags");
+    if (tile_bags_out) *tile_bags_out = bpb;
+    return PM_OK;
+}
 
-    const int G = pm::group_lanes(op->max_dim, vec);
-    const int NG = pm::kBlock / G;
-    int bpb = g_bags_per_block.load();
-    if (bpb <= 0) {
-        // 4 bags per lane group amortise the LDS staging; small requests shrink the tile until the
-        // grid fills the chip (256 CUs x 8 resident workgroups) -- a 16 K-bag single-table lookup
-        // ran 2 workgroups per CU at 49 % of the roofline with the fixed tile (gpurun r1e)
-        bpb = 4 * NG;
-        // Short average bags go with one bag per lane group: requests whose tables have very different bag
-        // sizes (Criteo multi-hot 1 .. 100, average 8.2) otherwise leave a few tables' workgroups 100x longer
-        // than the rest -- measured 7.2 (32 bags/tile) vs 14.3 G lookups/s (8); with uniform L = 20 the
-        // 32-bag tile is 3.5 % faster under Zipf and 2 % slower under uniform indices (sweeps r1f/r1g).
-        {
-            const int64_t tb = static_cast<int64_t>(op->num_tables) * op->batch;
-            if (tb > 0 && op->num_indices < 12 * tb) bpb = NG;
-        }
-        const int64_t want_blocks = 256 * 8;
-        while (bpb > NG && static_cast<int64_t>(op->num_tables) * ((op->bag_count + bpb - 1) / bpb) < want_blocks) bpb /= 2;
-    }
-    if (bpb < NG) bpb = NG;
-    if (bpb > 1024) bpb = 1024;
-
+void fill_params(const pm_embbag_batch* op, int elem_dtype, int bpb, pm::KParams& p) {
+    const int NG = pm::kBlock / pm::group_lanes(op->max_dim, (elem_dtype == PM_F32) ? 4 : 8);
     const int64_t tiles = (op->bag_count + bpb - 1) / bpb;
-    if (tiles * op->num_tables > 0x7fffffffLL) return fail(PM_ERR_UNSUPPORTED, "grid too large");
 
     const int64_t total_bags = static_cast<int64_t>(op->num_tables) * op->batch;
     const int64_t avg_l = total_bags > 0 ? (op->num_indices + total_bags - 1) / total_bags : 0;
@@ -169,14 +207,6 @@ int make_params(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p, bool 
     // ... and only where the order can matter: with one bag per lane group (short-bag tiles) nothing is pulled
     p.ordered = (total_bags > 0 && op->num_indices % total_bags != 0 && bpb > NG) ? 1 : 0;
     p.alpha = 1.0f;
-    if (op->grad_block_shift < 0 || op->grad_block_shift > 31 || op->grad_block_extra < 0 || op->table_group < 0)
-        return fail(PM_ERR_INVALID, "grad_block_shift must be in [0, 31], grad_block_extra and table_group >= 0");
-    // a blocked gradient needs blocks of at least two bags that tile the batch (ADVICE r5: shift 0 with a non-zero extra used to read
-    // the un-blocked layout without a word, and so did a batch that is not a whole number of blocks)
-    if (op->grad_block_shift == 0 && op->grad_block_extra != 0)
-        return fail(PM_ERR_INVALID, "grad_block_extra needs grad_block_shift >= 1 (a block of one bag is the un-blocked layout)");
-    if (op->grad_block_shift > 0 && (op->batch & ((static_cast<int64_t>(1) << op->grad_block_shift) - 1)) != 0)
-        return fail(PM_ERR_INVALID, "batch must be a multiple of 2^grad_block_shift bags");
     p.gblk_shift = op->grad_block_shift > 0 ? op->grad_block_shift : 31;
     p.gblk_extra = op->grad_block_shift > 0 ? op->grad_block_extra : 0;
     // LDS-staged output (forward): the tile's pooled rows leave in one burst at the end of the tile (embbag_fwd.hip).
@@ -191,138 +221,144 @@ int make_params(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p, bool 
     p.flat_bags = 0;
     p.flat_target = 0;
     p.flat_compact = 0;
-    if (forward) {
-        const FwdEnv& env = fwd_env();
-        int want = g_stage_out.load();
-        if (want < 0) want = env.stage;
-        const bool even = total_bags > 0 && op->num_indices % total_bags == 0;
-        if (want && even && !p.ordered && g_bags_per_block.load() <= 0) {
-            while (bpb > NG && static_cast<int64_t>(bpb) * op->max_dim * 4 > 16384) bpb /= 2;
-            if (static_cast<int64_t>(bpb) * op->max_dim * 4 <= 16384) {
-                const int64_t tiles2 = (op->bag_count + bpb - 1) / bpb;
-                if (tiles2 * op->num_tables <= 0x7fffffffLL) {
-                    p.bags_per_block = bpb;
-                    p.tiles_per_table = static_cast<int32_t>(tiles2);
-                    p.stage_out = op->max_dim;
-                    int64_t need = (2 * static_cast<int64_t>(bpb) * avg_l + 255) / 256 * 256;
-                    if (need < 512) need = 512;
-                    if (need < p.idx_cap) p.idx_cap = static_cast<int32_t>(need);
-                }
-            }
-        } else if (want && even && !p.ordered && static_cast<int64_t>(bpb) * op->max_dim * 4 <= 16384) {
-            p.stage_out = op->max_dim;   // explicit bags_per_block (sweeps): stage if it fits, index tile sized the same way
-            int64_t need = (2 * static_cast<int64_t>(bpb) * avg_l + 255) / 256 * 256;
-            if (need < 512) need = 512;
-            if (need < p.idx_cap) p.idx_cap = static_cast<int32_t>(need);
-        } else if (want && !even && !p.ordered && g_bags_per_block.load() <= 0 &&
-                   static_cast<int64_t>(bpb) * op->max_dim * 4 <= 4096) {
-            // short-bag tiles of requests with per-table pooling (Criteo multi-hot: one bag per lane group, 8 bags per
-            // tile): the staging buffer is 4 KB, the full-size index tile stays -- 20.6 KB per workgroup
-            p.stage_out = op->max_dim;
-        }
-        p.stage_bags = p.bags_per_block;
-        // ... and those requests run the flat-walk kernel (embbag_fwd.hip): tiles sized per table on the device (~256 lookups, up
-        // to 32 bags for the pooling-1 tables), row loads in flight across bag borders.  tiles_per_table stays the count of the
-        // smallest tile (one bag per lane group): workgroups past their table's tile count leave.  Criteo tables, visit
-        // r3_criteo_flat (Zipf G lookups/s / uniform fraction; run-to-run +-1.5 %): 8-bag tiles 15.7-15.9 / 0.69-0.71; flat walk
-        // target 512 cap 64: 16.4-16.5 / 0.705-0.716; **256 / 32: 16.6 / 0.719**; 128: 16.1 / 0.695; 1024 / 128: 14.1 / 0.64.
-        // PARAM_AMD_FWD_FLAT=0 turns it off (PARAM_AMD_FLAT_TARGET / _BAGS: sweeps).
-        // (Round 6: that cap of 32 bags was chosen under round 3's grid, where a larger cap also meant more surplus workgroups.  With
-        // the compact launch a one-hot table's 32-bag tile is three round trips of set-up around 32 row loads; one process per setting,
-        // three each, us uniform / Zipf: cap 32: 192-193 / 118; 64: 182 / 114; 128: 186 / 112; **256: 181 / 111.6**
-        // -- profiles/r06_flat_bags_cap_sweep_all128.jsonl.  The cap is 256 bags on every flat-walk path now.)
-        const int flat_env = env.flat;
-        const bool flat_on = flat_env != 0;
-        // ... and so do fixed-pooling requests of one or two lookups per bag (one-hot tables): bag by bag a lane group has one or
-        // two row loads in flight.  48 x 10 M x 128 fp32, batch 65536 (tools/r3_shortbags.sh; Zipf G lookups/s / uniform fraction):
-        // pooling 1: 4.00 / 0.529 -> 5.05 / 0.624; pooling 2: 7.78 / 0.687 -> 8.75 / 0.686; pooling 4: 13.5 / 0.723 -> 13.4 / 0.679
-        // (not taken; PARAM_AMD_FWD_FLAT=2 extends the rule to 4 for that measurement).
-        const int flat_maxl = env.flat_maxl;
-        if (flat_on && even && avg_l <= (flat_maxl > 0 ? flat_maxl : flat_env == 2 ? 4 : 2) && !p.ordered && g_bags_per_block.load() <= 0 &&
-            p.stage_out > 0) {
-            const int64_t tiles_ng = (op->bag_count + NG - 1) / NG;
-            if (tiles_ng * op->num_tables <= 0x7fffffffLL) {
-                const int tgt2 = flat_target_knob(env);
-                p.flat_bags = env.flat_bags < 32 ? 32 : (env.flat_bags > 1024 ? 1024 : env.flat_bags / NG * NG);
-                p.flat_target = tgt2;
-                p.tiles_per_table = static_cast<int32_t>(tiles_ng);
-                p.stage_bags = NG;
-                p.bags_per_block = p.flat_bags;
-                if (p.idx_cap < 1024) p.idx_cap = 1024;
+}
+
+void plan_forward(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p) {
+    const int vec = (elem_dtype == PM_F32) ? 4 : 8;
+    const int G = pm::group_lanes(op->max_dim, vec);
+    const int NG = pm::kBlock / G;
+    int bpb = p.bags_per_block;
+    const int64_t total_bags = static_cast<int64_t>(op->num_tables) * op->batch;
+    const int64_t avg_l = total_bags > 0 ? (op->num_indices + total_bags - 1) / total_bags : 0;
+    const FwdEnv& env = fwd_env();
+    int want = g_stage_out.load();
+    if (want < 0) want = env.stage;
+    const bool even = total_bags > 0 && op->num_indices % total_bags == 0;
+    if (want && even && !p.ordered && g_bags_per_block.load() <= 0) {
+        while (bpb > NG && static_cast<int64_t>(bpb) * op->max_dim * 4 > 16384) bpb /= 2;
+        if (static_cast<int64_t>(bpb) * op->max_dim * 4 <= 16384) {
+            const int64_t tiles2 = (op->bag_count + bpb - 1) / bpb;
+            if (tiles2 * op->num_tables <= 0x7fffffffLL) {
+                p.bags_per_block = bpb;
+                p.tiles_per_table = static_cast<int32_t>(tiles2);
+                p.stage_out = op->max_dim;
+                int64_t need = (2 * static_cast<int64_t>(bpb) * avg_l + 255) / 256 * 256;
+                if (need < 512) need = 512;
+                if (need < p.idx_cap) p.idx_cap = static_cast<int32_t>(need);
             }
         }
-        if (flat_on && !even && !p.ordered && g_bags_per_block.load() <= 0 && bpb == NG && p.stage_out > 0) {
-            const int cap_env = env.flat_bags;
-            const int tgt_env = flat_target_knob(env);
-            p.flat_bags = cap_env < NG ? NG : (cap_env > 1024 ? 1024 : cap_env / NG * NG);
-            p.flat_target = tgt_env < 1 ? 1 : tgt_env;
-            p.bags_per_block = p.flat_bags;   // sizes the LDS offsets array; stage_bags (the burst buffer) stays at NG rows
-        }
-        // ABI v7, mixed embedding dims (min_dim given and its lane group narrower than max_dim's): the flat-walk kernel sizes the lane
-        // group PER TABLE on the device (embbag_fwd.hip), whatever the bags look like -- tiles are ~flat_target lookups of any pooling
-        // factor.  flat_bags = the bags the narrowest table's sub-groups pool at once (at least the usual 32): the LDS offsets array.
-        // Ragged requests keep the ordered kernel (longest bag first matters more there than idle lanes).
-        if (flat_on && op->min_dim > 0 && op->min_dim < op->max_dim && !p.ordered && g_bags_per_block.load() <= 0) {
-            int need = (op->min_dim + vec - 1) / vec, g_min = 4;          // sub-groups of 4 lanes at least: 64-byte pieces
-            while (g_min < need) g_min <<= 1;
-            if (g_min < G) {
-                const int ng_max = pm::kBlock / g_min;
-                const int64_t tiles_ng = (op->bag_count + NG - 1) / NG;   // the grid of the smallest tile: the widest table's NG bags
-                if (tiles_ng * op->num_tables <= 0x7fffffffLL) {
-                    if (p.flat_bags < ng_max) p.flat_bags = ng_max;
-                    // (256 bags at most per tile: a one-hot narrow table then reaches the ~flat_target lookups per tile the wide tables
-                    // have -- its 64-bag tiles were three round trips of set-up around 4 KB of rows.  Criteo tables with mixed dims, one
-                    // process per setting, two each: cap 64: 143.3-143.9 us, 128: 142.3-142.9, 256: 141.5-142.1; the narrow tables alone
-                    // 24.3 -> 21.6 us: profiles/r06_flat_bags_cap_sweep.jsonl)
-                    if (p.flat_bags < 256) p.flat_bags = 256;
-                    if (p.flat_bags < 32) p.flat_bags = 32;
-                    if (p.flat_target <= 0) p.flat_target = flat_target_knob(env) < 1 ? 1 : flat_target_knob(env);
-                    p.tiles_per_table = static_cast<int32_t>(tiles_ng);
-                    p.bags_per_block = p.flat_bags;
-                    p.stage_out = op->max_dim;
-                    p.stage_bags = NG;                                    // burst buffer: NG rows of max_dim floats (4 KB at D = 128 fp32)
-                    // index tile: twice what a tile holds on average -- ~flat_target lookups, or the narrowest table's ng_max bags
-                    int64_t cap2 = 2 * static_cast<int64_t>(ng_max) * avg_l;
-                    if (cap2 < 2 * static_cast<int64_t>(p.flat_target)) cap2 = 2 * static_cast<int64_t>(p.flat_target);
-                    cap2 = (cap2 + 255) / 256 * 256;
-                    p.idx_cap = static_cast<int32_t>(cap2 < 1024 ? 1024 : (cap2 > 4096 ? 4096 : cap2));
-                    if (p.xcd_affine == 3) p.xcd_affine = 0;             // eighths of the tile order assume equal tiles per table
-                }
-            }
-        }
-        // flat-walk launches are one resident set of workgroups walking the tile order (embbag_fwd.hip, round 6): 1 = the launcher asks
-        // the device how many that is
-        {
-            int fg = g_flat_grid.load();
-            if (fg < 0) fg = env.flat_compact;
-            if (p.flat_bags > 0 && op->num_tables <= 1024 && fg > 0) {
-                // the tiles the request will have, from its sizes (the tables' own pooling factors are on the device): ~flat_target
-                // lookups each, but at most flat_bags bags; a quarter more, because a table's tile is its average bag count rounded DOWN
-                // to whole lane-group rounds
-                const int64_t n_slice = op->batch > 0 ? (op->num_indices * op->bag_count + op->batch - 1) / op->batch : 0;
-                const int64_t by_lookups = (n_slice + p.flat_target - 1) / p.flat_target;
-                const int64_t by_bags = static_cast<int64_t>(op->num_tables) * ((op->bag_count + p.flat_bags - 1) / p.flat_bags);
-                int64_t est = (by_lookups > by_bags ? by_lookups : by_bags) * 5 / 4 + op->num_tables;
-                if (est < 1024) est = 1024;
-                if (est > (1 << 20)) est = 1 << 20;
-                p.flat_compact = fg > 1 ? fg : static_cast<int32_t>(est);
-            }
-        }
-        // Two tilings built and measured in round 3 for requests whose tables have very different pooling factors (Criteo
-        // multi-hot 1 .. 100) -- both slower than the 8-bag tiles in table-major order, which stay:
-        //  * WORK tiles (~640 lookups per tile whatever the pooling factor, tile boundaries derived on the device from the
-        //    tables' lookup counts): 186 us against 120 us under Zipf, 249 against 185 us under uniform indices (caps of
-        //    32 .. 1024 bags, targets of 320 .. 1280: all slower).  A pooling-1 bag is ONE row load; a lane group walking 16 ..
-        //    128 of them in turn has one load in flight where 1024 eight-bag workgroups have them all in flight at once -- the
-        //    small tiles ARE the memory-level parallelism.  Removed again (profiles/r03_criteo_fwd_work_tiles.txt).
-        //  * tile-major block order (t = b % T, so every table advances at the same rate and the heavy table's long workgroups
-        //    start throughout the launch): 165 against 120 us under Zipf, 220 against 186 us uniform -- a table's tiles then run
-        //    on all eight XCDs at once and on every CU next to other tables' rows.  Kept behind PARAM_AMD_FWD_TILE_MAJOR=1.
-        const int tm_env = env.tile_major;
-        const bool uneven = total_bags > 0 && op->num_indices % total_bags != 0;
-        if (p.xcd_affine != 1 && op->num_tables > 1 && tm_env > 0 && uneven) p.xcd_affine = 2;
+    } else if (want && even && !p.ordered && static_cast<int64_t>(bpb) * op->max_dim * 4 <= 16384) {
+        p.stage_out = op->max_dim;   // explicit bags_per_block (sweeps): stage if it fits, index tile sized the same way
+        int64_t need = (2 * static_cast<int64_t>(bpb) * avg_l + 255) / 256 * 256;
+        if (need < 512) need = 512;
+        if (need < p.idx_cap) p.idx_cap = static_cast<int32_t>(need);
+    } else if (want && !even && !p.ordered && g_bags_per_block.load() <= 0 &&
+               static_cast<int64_t>(bpb) * op->max_dim * 4 <= 4096) {
+        // short-bag tiles of requests with per-table pooling (Criteo multi-hot: one bag per lane group, 8 bags per
+        // tile): the staging buffer is 4 KB, the full-size index tile stays -- 20.6 KB per workgroup
+        p.stage_out = op->max_dim;
     }
-    return PM_OK;
+    p.stage_bags = p.bags_per_block;
+    // ... and those requests run the flat-walk kernel (embbag_fwd.hip): tiles sized per table on the device (~256 lookups, up
+    // to 32 bags for the pooling-1 tables), row loads in flight across bag borders.  tiles_per_table stays the count of the
+    // smallest tile (one bag per lane group): workgroups past their table's tile count leave.  Criteo tables, visit
+    // r3_criteo_flat (Zipf G lookups/s / uniform fraction; run-to-run +-1.5 %): 8-bag tiles 15.7-15.9 / 0.69-0.71; flat walk
+    // target 512 cap 64: 16.4-16.5 / 0.705-0.716; **256 / 32: 16.6 / 0.719**; 128: 16.1 / 0.695; 1024 / 128: 14.1 / 0.64.
+    // PARAM_AMD_FWD_FLAT=0 turns it off (PARAM_AMD_FLAT_TARGET / _BAGS: sweeps).
+    // (Round 6: that cap of 32 bags was chosen under round 3's grid, where a larger cap also meant more surplus workgroups.  With
+    // the compact launch a one-hot table's 32-bag tile is three round trips of set-up around 32 row loads; one process per setting,
+    // three each, us uniform / Zipf: cap 32: 192-193 / 118; 64: 182 / 114; 128: 186 / 112; **256: 181 / 111.6**
+    // -- profiles/r06_flat_bags_cap_sweep_all128.jsonl.  The cap is 256 bags on every flat-walk path now.)
+    const int flat_env = env.flat;
+    const bool flat_on = flat_env != 0;
+    // ... and so do fixed-pooling requests of one or two lookups per bag (one-hot tables): bag by bag a lane group has one or
+    // two row loads in flight.  48 x 10 M x 128 fp32, batch 65536 (tools/r3_shortbags.sh; Zipf G lookups/s / uniform fraction):
+    // pooling 1: 4.00 / 0.529 -> 5.05 / 0.624; pooling 2: 7.78 / 0.687 -> 8.75 / 0.686; pooling 4: 13.5 / 0.723 -> 13.4 / 0.679
+    // (not taken; PARAM_AMD_FWD_FLAT=2 extends the rule to 4 for that measurement).
+    const int flat_maxl = env.flat_maxl;
+    if (flat_on && even && avg_l <= (flat_maxl > 0 ? flat_maxl : flat_env == 2 ? 4 : 2) && !p.ordered && g_bags_per_block.load() <= 0 &&
+        p.stage_out > 0) {
+        const int64_t tiles_ng = (op->bag_count + NG - 1) / NG;
+        if (tiles_ng * op->num_tables <= 0x7fffffffLL) {
+            const int tgt2 = flat_target_knob(env);
+            p.flat_bags = env.flat_bags < 32 ? 32 : (env.flat_bags > 1024 ? 1024 : env.flat_bags / NG * NG);
+            p.flat_target = tgt2;
+            p.tiles_per_table = static_cast<int32_t>(tiles_ng);
+            p.stage_bags = NG;
+            p.bags_per_block = p.flat_bags;
+            if (p.idx_cap < 1024) p.idx_cap = 1024;
+        }
+    }
+    if (flat_on && !even && !p.ordered && g_bags_per_block.load() <= 0 && bpb == NG && p.stage_out > 0) {
+        const int cap_env = env.flat_bags;
+        const int tgt_env = flat_target_knob(env);
+        p.flat_bags = cap_env < NG ? NG : (cap_env > 1024 ? 1024 : cap_env / NG * NG);
+        p.flat_target = tgt_env < 1 ? 1 : tgt_env;
+        p.bags_per_block = p.flat_bags;   // sizes the LDS offsets array; stage_bags (the burst buffer) stays at NG rows
+    }
+    // ABI v7, mixed embedding dims (min_dim given and its lane group narrower than max_dim's): the flat-walk kernel sizes the lane
+    // group PER TABLE on the device (embbag_fwd.hip), whatever the bags look like -- tiles are ~flat_target lookups of any pooling
+    // factor.  flat_bags = the bags the narrowest table's sub-groups pool at once (at least the usual 32): the LDS offsets array.
+    // Ragged requests keep the ordered kernel (longest bag first matters more there than idle lanes).
+    if (flat_on && op->min_dim > 0 && op->min_dim < op->max_dim && !p.ordered && g_bags_per_block.load() <= 0) {
+        int need = (op->min_dim + vec - 1) / vec, g_min = 4;          // sub-groups of 4 lanes at least: 64-byte pieces
+        while (g_min < need) g_min <<= 1;
+        if (g_min < G) {
+            const int ng_max = pm::kBlock / g_min;
+            const int64_t tiles_ng = (op->bag_count + NG - 1) / NG;   // the grid of the smallest tile: the widest table's NG bags
+            if (tiles_ng * op->num_tables <= 0x7fffffffLL) {
+                if (p.flat_bags < ng_max) p.flat_bags = ng_max;
+                // (256 bags at most per tile: a one-hot narrow table then reaches the ~flat_target lookups per tile the wide tables
+                // have -- its 64-bag tiles were three round trips of set-up around 4 KB of rows.  Criteo tables with mixed dims, one
+                // process per setting, two each: cap 64: 143.3-143.9 us, 128: 142.3-142.9, 256: 141.5-142.1; the narrow tables alone
+                // 24.3 -> 21.6 us: profiles/r06_flat_bags_cap_sweep.jsonl)
+                if (p.flat_bags < 256) p.flat_bags = 256;
+                if (p.flat_bags < 32) p.flat_bags = 32;
+                if (p.flat_target <= 0) p.flat_target = flat_target_knob(env) < 1 ? 1 : flat_target_knob(env);
+                p.tiles_per_table = static_cast<int32_t>(tiles_ng);
+                p.bags_per_block = p.flat_bags;
+                p.stage_out = op->max_dim;
+                p.stage_bags = NG;                                    // burst buffer: NG rows of max_dim floats (4 KB at D = 128 fp32)
+                // index tile: twice what a tile holds on average -- ~flat_target lookups, or the narrowest table's ng_max bags
+                int64_t cap2 = 2 * static_cast<int64_t>(ng_max) * avg_l;
+                if (cap2 < 2 * static_cast<int64_t>(p.flat_target)) cap2 = 2 * static_cast<int64_t>(p.flat_target);
+                cap2 = (cap2 + 255) / 256 * 256;
+                p.idx_cap = static_cast<int32_t>(cap2 < 1024 ? 1024 : (cap2 > 4096 ? 4096 : cap2));
+                if (p.xcd_affine == 3) p.xcd_affine = 0;             // eighths of the tile order assume equal tiles per table
+            }
+        }
+    }
+    // flat-walk launches are one resident set of workgroups walking the tile order (embbag_fwd.hip, round 6): 1 = the launcher asks
+    // the device how many that is
+    {
+        int fg = g_flat_grid.load();
+        if (fg < 0) fg = env.flat_compact;
+        if (p.flat_bags > 0 && op->num_tables <= 1024 && fg > 0) {
+            // the tiles the request will have, from its sizes (the tables' own pooling factors are on the device): ~flat_target
+            // lookups each, but at most flat_bags bags; a quarter more, because a table's tile is its average bag count rounded DOWN
+            // to whole lane-group rounds
+            const int64_t n_slice = op->batch > 0 ? (op->num_indices * op->bag_count + op->batch - 1) / op->batch : 0;
+            const int64_t by_lookups = (n_slice + p.flat_target - 1) / p.flat_target;
+            const int64_t by_bags = static_cast<int64_t>(op->num_tables) * ((op->bag_count + p.flat_bags - 1) / p.flat_bags);
+            int64_t est = (by_lookups > by_bags ? by_lookups : by_bags) * 5 / 4 + op->num_tables;
+            if (est < 1024) est = 1024;
+            if (est > (1 << 20)) est = 1 << 20;
+            p.flat_compact = fg > 1 ? fg : static_cast<int32_t>(est);
+        }
+    }
+    // Two tilings built and measured in round 3 for requests whose tables have very different pooling factors (Criteo
+    // multi-hot 1 .. 100) -- both slower than the 8-bag tiles in table-major order, which stay:
+    //  * WORK tiles (~640 lookups per tile whatever the pooling factor, tile boundaries derived on the device from the
+    //    tables' lookup counts): 186 us against 120 us under Zipf, 249 against 185 us under uniform indices (caps of
+    //    32 .. 1024 bags, targets of 320 .. 1280: all slower).  A pooling-1 bag is ONE row load; a lane group walking 16 ..
+    //    128 of them in turn has one load in flight where 1024 eight-bag workgroups have them all in flight at once -- the
+    //    small tiles ARE the memory-level parallelism.  Removed again (profiles/r03_criteo_fwd_work_tiles.txt).
+    //  * tile-major block order (t = b % T, so every table advances at the same rate and the heavy table's long workgroups
+    //    start throughout the launch): 165 against 120 us under Zipf, 220 against 186 us uniform -- a table's tiles then run
+    //    on all eight XCDs at once and on every CU next to other tables' rows.  Kept behind PARAM_AMD_FWD_TILE_MAJOR=1.
+    const int tm_env = env.tile_major;
+    const bool uneven = total_bags > 0 && op->num_indices % total_bags != 0;
+    if (p.xcd_affine != 1 && op->num_tables > 1 && tm_env > 0 && uneven) p.xcd_affine = 2;
 }
 
 // Row loads in flight per lane group when pm_set_tuning leaves the choice to the library.  Two is the measured optimum of a launch
@@ -339,6 +375,98 @@ int small_request_unroll(const pm_embbag_batch* op, const pm::KParams& p) {
     // 128: 6.9 / 6.0 / 5.6, 256: 9.6 / 7.7 / 6.6, 512: 13.0 / 13.1 / 13.1, 1024: 22.4 / 22.6 / 23.1 -- it pays up to one workgroup per CU
     if (wgs > 384) return kDefaultUnroll;
     return avg_l >= 8 ? 8 : (avg_l >= 4 ? 4 : kDefaultUnroll);
+}
+
+// ---- the sorted backward's entry points: what they share ---------------------------------------------------------------
+// the one text of each reason the sort recorded on a workspace does not fit a call; kind: "row-wise" / "element-wise" (Adagrad)
+int plan_fail(pm::PlanStatus st, const char* kind) {
+    switch (st) {
+        case pm::PlanStatus::ok: return PM_OK;
+        case pm::PlanStatus::none:
+            return fail(PM_ERR_INVALID, "pm_embbag_sort_indices has not been called for this request on this workspace (same indices / "
+                                        "offsets pointers, batch, bag slice and weights as the sort's)");
+        case pm::PlanStatus::two_phase:
+            return fail(PM_ERR_INVALID, std::string("the request was sorted for a two-phase scatter-add apply; ") + kind + " Adagrad needs "
+                                        "pm_embbag_sort_indices (phases = 1)");
+        case pm::PlanStatus::relabelled:
+            return fail(PM_ERR_INVALID, "the sort on this workspace was relabelled by pm_embbag_sparse_grad_count (its keys hold slots, not "
+                                        "rows): sort the request again");
+        case pm::PlanStatus::not_complete_segmented:
+            return fail(PM_ERR_UNSUPPORTED, "the sparse gradient needs the complete one-phase segmented sort: sort with pm_embbag_sort_indices "
+                                            "(sort_impl 0)");
+        case pm::PlanStatus::low_digit_order:
+            return fail(PM_ERR_UNSUPPORTED, "the sparse gradient needs rows in ascending order within a table: sort mode 1 orders them by "
+                                            "their low digit first (pm_set_sort_tuning 0, 2 or 3)");
+        case pm::PlanStatus::already_counted:
+            return fail(PM_ERR_INVALID, "pm_embbag_sparse_grad_count has been called for this sort already: sort the request again");
+        default: return fail(PM_ERR_INVALID, "pm_embbag_sparse_grad needs pm_embbag_sparse_grad_count on this sort first");
+    }
+}
+
+int sorted_args_ok(const pm_embbag_batch* op, int64_t max_rows) {
+    if (max_rows < 1 || max_rows > (1LL << 31)) return fail(PM_ERR_INVALID, "max_rows must be in [1, 2^31]");
+    if (op->num_indices >= (1LL << 32) || static_cast<int64_t>(op->batch) >= (1LL << 32))
+        return fail(PM_ERR_UNSUPPORTED, "sorted backward needs num_indices and batch below 2^32");
+#ifndef PM_ALTERNATES
+    if (op->num_tables > pm::kSegSortMaxTables)
+        return fail(PM_ERR_UNSUPPORTED, "sorted backward: at most " + std::to_string(pm::kSegSortMaxTables) +
+                                            " tables per request (split the request by tables: the calls are independent)");
+#endif
+    return PM_OK;
+}
+
+// The request of a sorted call.  sparse: the coalesced sparse gradient (sparse_grad.hip), whose apply writes fp32 rows: its row-width
+// rule (dims multiples of 4) is the fp32 destination's.
+int sorted_request(const pm_embbag_batch* op, int dtype, int64_t max_rows, bool sparse, pm::KParams& p) {
+    int rc = make_params(op, dtype, p);
+    if (rc != PM_OK) return rc;
+    if ((rc = sorted_args_ok(op, max_rows)) != PM_OK) return rc;
+    return sparse ? validate_request(op, PM_F32) : PM_OK;
+}
+
+// ... and its workspace.  sparse: the sorted backward's, followed by the relabelling's own few words per sorted position and per tile.
+int sorted_bytes(const char* who, const pm_embbag_batch* op, int64_t max_rows, bool sparse, const pm::KParams& p, size_t& sorted,
+                        size_t& total) {
+    const hipError_t h = pm::sorted_workspace_bytes(p, max_rows, op->max_dim, sorted);
+    if (h != hipSuccess) return hip_fail(h, who);
+    if (sparse) sorted = (sorted + 255) / 256 * 256;
+    total = sparse ? sorted + pm::sparse_grad_extra_bytes(p.N, p.T) : sorted;
+    return PM_OK;
+}
+
+// How every sorted entry point opens, each step written once and in the order they have always run: the request, the caller's own
+// argument checks and its nothing-to-do early-out (own_checks: PM_OK to go on, kDone to return PM_OK now), the workspace, and whether
+// the sort recorded on it fits (plan: a pm::PlanStatus).  Returns PM_OK to go on, kDone, or the error.
+constexpr int kDone = 1;      // (the PM_ERR_* codes are negative)
+struct SortedCall {
+    const char* who;          // names the call in a HIP error of the workspace size query
+    int dtype;                // the element type the call reads or writes the tables as
+    bool sparse;              // a sparse-gradient call (sorted_request, sorted_bytes); it sizes the workspace BEFORE its own checks
+    const char* kind;         // Adagrad: "row-wise" / "element-wise"
+    pm::KParams p;            // out: the request
+    size_t sorted;            // out: bytes of the sorted backward's part of the workspace
+};
+template <typename Own, typename Plan>
+int sorted_call_prologue(SortedCall& c, const pm_embbag_batch* op, int64_t max_rows, const void* workspace, int64_t workspace_bytes,
+                         Own&& own_checks, Plan&& plan) {
+    int rc = sorted_request(op, c.dtype, max_rows, c.sparse, c.p);
+    if (rc != PM_OK) return rc;
+    size_t need = 0;
+    if (c.sparse && (rc = sorted_bytes(c.who, op, max_rows, true, c.p, c.sorted, need)) != PM_OK) return rc;
+    if ((rc = own_checks()) != PM_OK) return rc;
+    if (!c.sparse && (rc = sorted_bytes(c.who, op, max_rows, false, c.p, c.sorted, need)) != PM_OK) return rc;
+    if (!workspace || workspace_bytes < static_cast<int64_t>(need))
+        return fail(PM_ERR_INVALID, "workspace too small: need " + std::to_string(need) + " bytes" +
+                                        (c.sparse ? " (pm_embbag_sparse_grad_workspace)" : ""));
+    return plan_fail(plan(), c.kind);
+}
+
+// the sorted apply's view of the request: the gradient, the tables it updates, alpha and the default destination-row policy
+void apply_params(pm::KParams& p, const float* grad, const void* tables, float alpha) {
+    p.io = const_cast<float*>(grad);
+    p.tables = static_cast<const void* const*>(tables);
+    p.alpha = alpha;
+    if (g_nt_loads.load() < 0) p.nt_loads = kDefaultRowPolicy;
 }
 
 }  // namespace
@@ -420,7 +548,7 @@ int pm_embbag_sort_status(const pm_embbag_batch* op, int64_t max_rows, const voi
     if (!workspace || !out) return fail(PM_ERR_INVALID, "NULL argument");
     uint32_t v[6] = {0, 0, 0, 0, 0, 0};
     const hipError_t h = pm::sort_status(p, max_rows, op->max_dim, workspace, static_cast<hipStream_t>(stream), v);
-    if (h == hipErrorInvalidValue) return fail(PM_ERR_INVALID, "no sort has been recorded for this workspace");
+    if (h == hipErrorInvalidValue) return fail(PM_ERR_INVALID, kNoSortRecorded);
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_sort_status");
     out->lookback_fallbacks = v[0];
     out->pairs_sorted = v[1];
@@ -588,30 +716,16 @@ int pm_embbag_bwd(const pm_embbag_batch* op, const float* grad, void* const* dst
 }
 #endif
 
-static const char* const kRelabelledMsg =
-    "the sort on this workspace was relabelled by pm_embbag_sparse_grad_count (its keys hold slots, not rows): sort the request again";
-
-static int sorted_args_ok(const pm_embbag_batch* op, int64_t max_rows) {
-    if (max_rows < 1 || max_rows > (1LL << 31)) return fail(PM_ERR_INVALID, "max_rows must be in [1, 2^31]");
-    if (op->num_indices >= (1LL << 32) || static_cast<int64_t>(op->batch) >= (1LL << 32))
-        return fail(PM_ERR_UNSUPPORTED, "sorted backward needs num_indices and batch below 2^32");
-#ifndef PM_ALTERNATES
-    if (op->num_tables > pm::kSegSortMaxTables)
-        return fail(PM_ERR_UNSUPPORTED, "sorted backward: at most " + std::to_string(pm::kSegSortMaxTables) +
-                                            " tables per request (split the request by tables: the calls are independent)");
-#endif
-    return PM_OK;
+static int64_t workspace_query(const char* who, const pm_embbag_batch* op, int64_t max_rows, bool sparse) {
+    pm::KParams p;
+    size_t sorted = 0, total = 0;
+    int rc = sorted_request(op, op ? op->weight_dtype : -1, max_rows, sparse, p);
+    if (rc != PM_OK || (rc = sorted_bytes(who, op, max_rows, sparse, p, sorted, total)) != PM_OK) return rc;
+    return static_cast<int64_t>(total);
 }
 
 int64_t pm_embbag_bwd_sorted_workspace(const pm_embbag_batch* op, int64_t max_rows) {
-    pm::KParams p;
-    int rc = make_params(op, op ? op->weight_dtype : -1, p);
-    if (rc != PM_OK) return rc;
-    if ((rc = sorted_args_ok(op, max_rows)) != PM_OK) return rc;
-    size_t bytes = 0;
-    hipError_t h = pm::sorted_workspace_bytes(p, max_rows, op->max_dim, bytes);
-    if (h != hipSuccess) return hip_fail(h, "pm_embbag_bwd_sorted_workspace");
-    return static_cast<int64_t>(bytes);
+    return workspace_query("pm_embbag_bwd_sorted_workspace", op, max_rows, false);
 }
 
 int pm_embbag_sort_indices(const pm_embbag_batch* op, int64_t max_rows, void* workspace, int64_t workspace_bytes,
@@ -622,17 +736,12 @@ int pm_embbag_sort_indices(const pm_embbag_batch* op, int64_t max_rows, void* wo
 static int sort_request(const pm_embbag_batch* op, int64_t max_rows, int32_t phases, void* workspace, int64_t workspace_bytes,
                         pm_stream_t stream, bool defer_ok) {
     if (phases != 1 && phases != 2) return fail(PM_ERR_INVALID, "phases must be 1 or 2");
-    pm::KParams p;
-    int rc = make_params(op, op ? op->weight_dtype : -1, p);
-    if (rc != PM_OK) return rc;
-    if ((rc = sorted_args_ok(op, max_rows)) != PM_OK) return rc;
-    if (p.N == 0) return PM_OK;
-    size_t need = 0;
-    hipError_t h = pm::sorted_workspace_bytes(p, max_rows, op->max_dim, need);
-    if (h != hipSuccess) return hip_fail(h, "pm_embbag_sort_indices");
-    if (!workspace || workspace_bytes < static_cast<int64_t>(need))
-        return fail(PM_ERR_INVALID, "workspace too small: need " + std::to_string(need) + " bytes");
-    h = pm::sort_indices(p, max_rows, op->max_dim, op->fixed_pooling, phases, workspace, static_cast<hipStream_t>(stream), defer_ok);
+    SortedCall c{"pm_embbag_sort_indices", op ? op->weight_dtype : -1, false, ""};
+    const pm::KParams& p = c.p;
+    const int rc = sorted_call_prologue(c, op, max_rows, workspace, workspace_bytes, [&]() -> int { return p.N == 0 ? kDone : PM_OK; },
+                                        [] { return pm::PlanStatus::ok; });
+    if (rc != PM_OK) return rc == kDone ? PM_OK : rc;
+    const hipError_t h = pm::sort_indices(p, max_rows, op->max_dim, op->fixed_pooling, phases, workspace, static_cast<hipStream_t>(stream), defer_ok);
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_sort_indices");
     return PM_OK;
 }
@@ -642,74 +751,12 @@ int pm_embbag_sort_indices_ex(const pm_embbag_batch* op, int64_t max_rows, int32
     return sort_request(op, max_rows, phases, workspace, workspace_bytes, stream, false);
 }
 
-// The fused calls validate what their APPLY half needs before the sort half launches anything (ADVICE r5: a NULL gradient or a bad
-// dtype used to be found after the sort's kernels -- and, on the hybrid path, after a deferred plan -- had been issued).
-static int fused_apply_args_ok(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t dtype) {
-    if (!op) return fail(PM_ERR_INVALID, "op is NULL");
-    if (!dtype_is_weight(dtype)) return fail(PM_ERR_INVALID, "weight/dst dtype must be PM_F32, PM_BF16 or PM_F16");
-    if (!grad || !tables) return fail(PM_ERR_INVALID, "grad / dst_tables is NULL");
-    return PM_OK;
-}
-
-int pm_embbag_bwd_fused(const pm_embbag_batch* op, const float* grad, void* const* dst_tables, int32_t dst_dtype, float alpha,
-                        int64_t max_rows, void* workspace, int64_t workspace_bytes, pm_stream_t stream) {
-    if (op && (op->num_indices == 0 || op->bag_count == 0)) return PM_OK;
-    int rc = fused_apply_args_ok(op, grad, dst_tables, dst_dtype);
-    if (rc != PM_OK) return rc;
-    {
-        pm::KParams chk;                            // the apply builds its parameters for the DESTINATION dtype: its row-width rule too
-        if ((rc = make_params(op, dst_dtype, chk)) != PM_OK) return rc;
-    }
-    rc = sort_request(op, max_rows, 1, workspace, workspace_bytes, stream, true);
-    if (rc != PM_OK) return rc;
-    return pm_embbag_bwd_sorted(op, grad, dst_tables, dst_dtype, alpha, max_rows, workspace, workspace_bytes, stream);
-}
-
-// the two fused Adagrad calls: `elem` = element-wise (state [rows_t, dims_t] per table), else row-wise (one value per row)
-static int sorted_adagrad(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype, float* const* state,
-                          bool elem, const pm_rowwise_adagrad* opt, int64_t max_rows, const void* workspace, int64_t workspace_bytes,
-                          pm_stream_t stream);
-
-static int fused_adagrad(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype, float* const* momentum,
-                         bool elem, const pm_rowwise_adagrad* opt, int64_t max_rows, void* workspace, int64_t workspace_bytes,
-                         pm_stream_t stream) {
-    if (op && (op->num_indices == 0 || op->bag_count == 0)) return PM_OK;
-    int rc = fused_apply_args_ok(op, grad, tables, table_dtype);
-    if (rc != PM_OK) return rc;
-    {
-        pm::KParams chk;
-        if ((rc = make_params(op, table_dtype, chk)) != PM_OK) return rc;
-    }
-    if (!opt) return fail(PM_ERR_INVALID, "optimizer options are NULL");
-    if (opt->weight_decay_mode != PM_WD_NONE && opt->weight_decay_mode != PM_WD_L2 && opt->weight_decay_mode != PM_WD_DECOUPLE)
-        return fail(PM_ERR_INVALID, "weight_decay_mode must be PM_WD_NONE, PM_WD_L2 or PM_WD_DECOUPLE");
-    if (!momentum) return fail(PM_ERR_INVALID, elem ? "grad / tables / state is NULL" : "grad / tables / momentum is NULL");
-    if (op->max_dim > 64 * ((table_dtype == PM_F32) ? 4 : 8))
-        return fail(PM_ERR_UNSUPPORTED, std::string(elem ? "element-wise" : "row-wise") + " Adagrad needs max_dim <= " + std::to_string(64 * ((table_dtype == PM_F32) ? 4 : 8)) + " for this table dtype");
-    rc = sort_request(op, max_rows, 1, workspace, workspace_bytes, stream, true);
-    if (rc != PM_OK) return rc;
-    return sorted_adagrad(op, grad, tables, table_dtype, momentum, elem, opt, max_rows, workspace, workspace_bytes, stream);
-}
-
-int pm_embbag_bwd_fused_adagrad(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype,
-                                float* const* momentum, const pm_rowwise_adagrad* opt, int64_t max_rows, void* workspace,
-                                int64_t workspace_bytes, pm_stream_t stream) {
-    return fused_adagrad(op, grad, tables, table_dtype, momentum, false, opt, max_rows, workspace, workspace_bytes, stream);
-}
-
-int pm_embbag_bwd_fused_adagrad_elem(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype,
-                                     float* const* state, const pm_rowwise_adagrad* opt, int64_t max_rows, void* workspace,
-                                     int64_t workspace_bytes, pm_stream_t stream) {
-    return fused_adagrad(op, grad, tables, table_dtype, state, true, opt, max_rows, workspace, workspace_bytes, stream);
-}
-
 int pm_embbag_sort_plan(const pm_embbag_batch* op, int64_t max_rows, int32_t phases, char* out, int32_t out_bytes) {
     if (phases != 1 && phases != 2) return fail(PM_ERR_INVALID, "phases must be 1 or 2");
     if (!out || out_bytes < 1) return fail(PM_ERR_INVALID, "out buffer is NULL / empty");
     pm::KParams p;
-    int rc = make_params(op, op ? op->weight_dtype : -1, p);
+    int rc = sorted_request(op, op ? op->weight_dtype : -1, max_rows, false, p);
     if (rc != PM_OK) return rc;
-    if ((rc = sorted_args_ok(op, max_rows)) != PM_OK) return rc;
     const std::string d = pm::sort_plan_describe(p, max_rows, op->fixed_pooling, phases);
     snprintf(out, static_cast<size_t>(out_bytes), "%s", d.c_str());
     return PM_OK;
@@ -718,85 +765,69 @@ int pm_embbag_sort_plan(const pm_embbag_batch* op, int64_t max_rows, int32_t pha
 int pm_embbag_sorted_pairs(const pm_embbag_batch* op, int64_t max_rows, const void* workspace, const void** keys,
                            const uint32_t** vals, const uint32_t** d_count, int32_t* key_bytes, int32_t* tshift) {
     pm::KParams p;
-    int rc = make_params(op, op ? op->weight_dtype : -1, p);
+    const int rc = sorted_request(op, op ? op->weight_dtype : -1, max_rows, false, p);
     if (rc != PM_OK) return rc;
-    if ((rc = sorted_args_ok(op, max_rows)) != PM_OK) return rc;
     if (!workspace || !keys || !vals || !d_count || !key_bytes || !tshift) return fail(PM_ERR_INVALID, "NULL argument");
-    int kb = 0, ts = 0;
-    const int pi = pm::sorted_pairs_info(p, max_rows, op->max_dim, workspace, keys, vals, d_count, &kb, &ts);
-    if (pi == 2)
+    pm::SortedPairsInfo pi;
+    if (pm::sorted_pairs_info(p, max_rows, op->max_dim, workspace, pi) != pm::PlanStatus::ok) return fail(PM_ERR_INVALID, kNoSortRecorded);
+    if (pi.deferred)
         return fail(PM_ERR_INVALID, "the last sort on this workspace was deferred into its apply (pm_embbag_bwd_fused*, hybrid backward) and no "
                                     "apply has been issued yet: there are no sorted pairs to look at");
-    if (pi != 0) return fail(PM_ERR_INVALID, "no sort has been recorded for this workspace");
-    *key_bytes = kb;
-    *tshift = ts;
+    *keys = pi.keys;
+    *vals = pi.vals;
+    *d_count = pi.d_count;
+    *key_bytes = pi.key_bytes;
+    *tshift = pi.tshift;
     return PM_OK;
 }
 
 int pm_embbag_bwd_sorted(const pm_embbag_batch* op, const float* grad, void* const* dst_tables, int32_t dst_dtype,
                          float alpha, int64_t max_rows, const void* workspace, int64_t workspace_bytes,
                          pm_stream_t stream) {
-    pm::KParams p;
-    int rc = make_params(op, dst_dtype, p);
-    if (rc != PM_OK) return rc;
-    if ((rc = sorted_args_ok(op, max_rows)) != PM_OK) return rc;
-    if (p.N == 0 || p.bag_count == 0) return PM_OK;
-    if (!grad || !dst_tables) return fail(PM_ERR_INVALID, "grad / dst_tables is NULL");
-    size_t need = 0;
-    hipError_t h = pm::sorted_workspace_bytes(p, max_rows, op->max_dim, need);
-    if (h != hipSuccess) return hip_fail(h, "pm_embbag_bwd_sorted");
-    if (!workspace || workspace_bytes < static_cast<int64_t>(need))
-        return fail(PM_ERR_INVALID, "workspace too small: need " + std::to_string(need) + " bytes");
-    const int pc = pm::bwd_sorted_plan_check(p, max_rows, workspace, false);
-    if (pc == 3) return fail(PM_ERR_INVALID, kRelabelledMsg);
-    if (pc != 0)
-        return fail(PM_ERR_INVALID, "pm_embbag_sort_indices has not been called for this request on this workspace (same indices / offsets pointers, batch, bag slice and weights as the sort's)");
-    p.io = const_cast<float*>(grad);
-    p.tables = const_cast<const void* const*>(dst_tables);
-    p.alpha = alpha;
-    if (g_nt_loads.load() < 0) p.nt_loads = kDefaultRowPolicy;
-    h = pm::bwd_sorted_apply(p, max_rows, dst_dtype, op->max_dim, workspace, nullptr, nullptr,
-                             static_cast<hipStream_t>(stream));
+    SortedCall c{"pm_embbag_bwd_sorted", dst_dtype, false, ""};
+    pm::KParams& p = c.p;
+    const int rc = sorted_call_prologue(
+        c, op, max_rows, workspace, workspace_bytes,
+        [&]() -> int {
+            if (p.N == 0 || p.bag_count == 0) return kDone;
+            return (!grad || !dst_tables) ? fail(PM_ERR_INVALID, "grad / dst_tables is NULL") : PM_OK;
+        },
+        [&] { return pm::bwd_sorted_plan_check(p, max_rows, workspace, false); });
+    if (rc != PM_OK) return rc == kDone ? PM_OK : rc;
+    apply_params(p, grad, dst_tables, alpha);
+    const hipError_t h = pm::bwd_sorted_apply(p, max_rows, dst_dtype, op->max_dim, workspace, static_cast<hipStream_t>(stream));
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_bwd_sorted launch");
     return PM_OK;
 }
 
-static int sorted_adagrad(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype, float* const* momentum,
-                          bool elem, const pm_rowwise_adagrad* opt, int64_t max_rows, const void* workspace, int64_t workspace_bytes,
-                          pm_stream_t stream) {
-    const std::string kind = elem ? "element-wise" : "row-wise";
-    pm::KParams p;
-    int rc = make_params(op, table_dtype, p);
-    if (rc != PM_OK) return rc;
-    if ((rc = sorted_args_ok(op, max_rows)) != PM_OK) return rc;
+// what the Adagrad calls check of their own, in their order (after the options, an empty request is PM_OK: kDone)
+static int check_adagrad_args(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype, float* const* state,
+                              bool elem, const pm_rowwise_adagrad* opt) {
     if (!opt) return fail(PM_ERR_INVALID, "optimizer options are NULL");
     if (opt->weight_decay_mode != PM_WD_NONE && opt->weight_decay_mode != PM_WD_L2 && opt->weight_decay_mode != PM_WD_DECOUPLE)
         return fail(PM_ERR_INVALID, "weight_decay_mode must be PM_WD_NONE, PM_WD_L2 or PM_WD_DECOUPLE");
-    if (p.N == 0 || p.bag_count == 0) return PM_OK;
-    if (!grad || !tables || !momentum) return fail(PM_ERR_INVALID, elem ? "grad / tables / state is NULL" : "grad / tables / momentum is NULL");
+    if (op->num_indices == 0 || op->bag_count == 0) return kDone;
+    if (!grad || !tables || !state) return fail(PM_ERR_INVALID, elem ? "grad / tables / state is NULL" : "grad / tables / momentum is NULL");
     const int vec = (table_dtype == PM_F32) ? 4 : 8;
     if (op->max_dim > 64 * vec)
-        return fail(PM_ERR_UNSUPPORTED, kind + " Adagrad needs max_dim <= " + std::to_string(64 * vec) + " for this table dtype");
-    size_t need = 0;
-    hipError_t h = pm::sorted_workspace_bytes(p, max_rows, op->max_dim, need);
-    if (h != hipSuccess) return hip_fail(h, "pm_embbag_bwd_sorted_adagrad");
-    if (!workspace || workspace_bytes < static_cast<int64_t>(need))
-        return fail(PM_ERR_INVALID, "workspace too small: need " + std::to_string(need) + " bytes");
-    {
-        const int pc = pm::bwd_sorted_plan_check(p, max_rows, workspace, true);
-        if (pc == 3) return fail(PM_ERR_INVALID, kRelabelledMsg);
-        if (pc == 2)
-            return fail(PM_ERR_INVALID, "the request was sorted for a two-phase scatter-add apply; " + kind + " Adagrad needs "
-                                        "pm_embbag_sort_indices (phases = 1)");
-        if (pc != 0)
-            return fail(PM_ERR_INVALID, "pm_embbag_sort_indices has not been called for this request on this workspace (same indices / offsets pointers, batch, bag slice and weights as the sort's)");
-    }
-    p.io = const_cast<float*>(grad);
-    p.tables = const_cast<const void* const*>(tables);
-    p.alpha = 1.0f;
-    if (g_nt_loads.load() < 0) p.nt_loads = kDefaultRowPolicy;
-    h = pm::bwd_sorted_apply(p, max_rows, table_dtype, op->max_dim, workspace, elem ? nullptr : momentum, opt, static_cast<hipStream_t>(stream),
-                             elem ? momentum : nullptr);
+        return fail(PM_ERR_UNSUPPORTED, std::string(elem ? "element-wise" : "row-wise") + " Adagrad needs max_dim <= " + std::to_string(64 * vec) +
+                                            " for this table dtype");
+    return PM_OK;
+}
+
+// the Adagrad apply: `elem` = element-wise (state [rows_t, dims_t] per table), else row-wise (one value per row)
+static int sorted_adagrad(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype, float* const* momentum,
+                          bool elem, const pm_rowwise_adagrad* opt, int64_t max_rows, const void* workspace, int64_t workspace_bytes,
+                          pm_stream_t stream) {
+    SortedCall c{"pm_embbag_bwd_sorted_adagrad", table_dtype, false, elem ? "element-wise" : "row-wise"};
+    pm::KParams& p = c.p;
+    const int rc = sorted_call_prologue(c, op, max_rows, workspace, workspace_bytes,
+                                        [&] { return check_adagrad_args(op, grad, tables, table_dtype, momentum, elem, opt); },
+                                        [&] { return pm::bwd_sorted_plan_check(p, max_rows, workspace, true); });
+    if (rc != PM_OK) return rc == kDone ? PM_OK : rc;
+    apply_params(p, grad, tables, 1.0f);
+    const hipError_t h = pm::bwd_sorted_apply(p, max_rows, table_dtype, op->max_dim, workspace, static_cast<hipStream_t>(stream),
+                                              pm::ApplyUpdate{opt, momentum, elem});
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_bwd_sorted_adagrad launch");
     return PM_OK;
 }
@@ -821,61 +852,70 @@ int pm_embbag_bwd_sorted_adagrad(const pm_embbag_batch* op, const float* grad, v
                                            workspace_bytes, stream);
 }
 
+// The fused calls validate what their APPLY half needs before the sort half launches anything (ADVICE r5: a NULL gradient or a bad
+// dtype used to be found after the sort's kernels -- and, on the hybrid path, after a deferred plan -- had been issued).
+// (kDone: an empty request.)
+static int fused_apply_args_ok(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t dtype) {
+    if (op && (op->num_indices == 0 || op->bag_count == 0)) return kDone;
+    if (!op) return fail(PM_ERR_INVALID, "op is NULL");
+    if (!dtype_is_weight(dtype)) return fail(PM_ERR_INVALID, "weight/dst dtype must be PM_F32, PM_BF16 or PM_F16");
+    if (!grad || !tables) return fail(PM_ERR_INVALID, "grad / dst_tables is NULL");
+    return validate_request(op, dtype);      // the apply builds its parameters for the DESTINATION dtype: its row-width rule too
+}
+
+int pm_embbag_bwd_fused(const pm_embbag_batch* op, const float* grad, void* const* dst_tables, int32_t dst_dtype, float alpha,
+                        int64_t max_rows, void* workspace, int64_t workspace_bytes, pm_stream_t stream) {
+    int rc = fused_apply_args_ok(op, grad, dst_tables, dst_dtype);
+    if (rc != PM_OK) return rc == kDone ? PM_OK : rc;
+    if ((rc = sort_request(op, max_rows, 1, workspace, workspace_bytes, stream, true)) != PM_OK) return rc;
+    return pm_embbag_bwd_sorted(op, grad, dst_tables, dst_dtype, alpha, max_rows, workspace, workspace_bytes, stream);
+}
+
+static int fused_adagrad(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype, float* const* momentum,
+                         bool elem, const pm_rowwise_adagrad* opt, int64_t max_rows, void* workspace, int64_t workspace_bytes,
+                         pm_stream_t stream) {
+    int rc = fused_apply_args_ok(op, grad, tables, table_dtype);
+    if (rc != PM_OK) return rc == kDone ? PM_OK : rc;
+    if ((rc = check_adagrad_args(op, grad, tables, table_dtype, momentum, elem, opt)) != PM_OK) return rc;      // (before the sort half)
+    if ((rc = sort_request(op, max_rows, 1, workspace, workspace_bytes, stream, true)) != PM_OK) return rc;
+    return sorted_adagrad(op, grad, tables, table_dtype, momentum, elem, opt, max_rows, workspace, workspace_bytes, stream);
+}
+
+int pm_embbag_bwd_fused_adagrad(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype,
+                                float* const* momentum, const pm_rowwise_adagrad* opt, int64_t max_rows, void* workspace,
+                                int64_t workspace_bytes, pm_stream_t stream) {
+    return fused_adagrad(op, grad, tables, table_dtype, momentum, false, opt, max_rows, workspace, workspace_bytes, stream);
+}
+
+int pm_embbag_bwd_fused_adagrad_elem(const pm_embbag_batch* op, const float* grad, void* const* tables, int32_t table_dtype,
+                                     float* const* state, const pm_rowwise_adagrad* opt, int64_t max_rows, void* workspace,
+                                     int64_t workspace_bytes, pm_stream_t stream) {
+    return fused_adagrad(op, grad, tables, table_dtype, state, true, opt, max_rows, workspace, workspace_bytes, stream);
+}
+
 // ---- ABI v8: coalesced sparse gradient (sparse_grad.hip) ----------------------------------------------------------------
 // The workspace is the sorted backward's followed by the relabelling's own few words per sorted position and per tile.
-static int sparse_common(const pm_embbag_batch* op, int64_t max_rows, pm::KParams& p, size_t& sorted_bytes, size_t& total_bytes) {
-    int rc = make_params(op, op ? op->weight_dtype : -1, p);
-    if (rc != PM_OK) return rc;
-    if ((rc = sorted_args_ok(op, max_rows)) != PM_OK) return rc;
-    // the apply writes fp32 rows: its row-width rule (dims multiples of 4) is the fp32 destination's
-    pm::KParams chk;
-    if ((rc = make_params(op, PM_F32, chk)) != PM_OK) return rc;
-    hipError_t h = pm::sorted_workspace_bytes(p, max_rows, op->max_dim, sorted_bytes);
-    if (h != hipSuccess) return hip_fail(h, "pm_embbag_sparse_grad_workspace");
-    sorted_bytes = (sorted_bytes + 255) / 256 * 256;
-    total_bytes = sorted_bytes + pm::sparse_grad_extra_bytes(p.N, p.T);
-    return PM_OK;
-}
-
-static int sparse_pairs_fail(int pi) {
-    switch (pi) {
-        case 1: return fail(PM_ERR_INVALID, "pm_embbag_sort_indices has not been called for this request on this workspace (same indices / "
-                                            "offsets pointers, batch, bag slice and weights as the sort's)");
-        case 2: return fail(PM_ERR_UNSUPPORTED, "the sparse gradient needs the complete one-phase segmented sort: sort with pm_embbag_sort_indices "
-                                                "(sort_impl 0)");
-        case 3: return fail(PM_ERR_UNSUPPORTED, "the sparse gradient needs rows in ascending order within a table: sort mode 1 orders them by "
-                                                "their low digit first (pm_set_sort_tuning 0, 2 or 3)");
-        case 4: return fail(PM_ERR_INVALID, "pm_embbag_sparse_grad_count has been called for this sort already: sort the request again");
-        default: return fail(PM_ERR_INVALID, "pm_embbag_sparse_grad needs pm_embbag_sparse_grad_count on this sort first");
-    }
-}
-
 int64_t pm_embbag_sparse_grad_workspace(const pm_embbag_batch* op, int64_t max_rows) {
-    pm::KParams p;
-    size_t sorted_bytes = 0, total = 0;
-    const int rc = sparse_common(op, max_rows, p, sorted_bytes, total);
-    if (rc != PM_OK) return rc;
-    return static_cast<int64_t>(total);
+    return workspace_query("pm_embbag_sparse_grad_workspace", op, max_rows, true);
 }
 
 int pm_embbag_sparse_grad_count(const pm_embbag_batch* op, int64_t max_rows, void* workspace, int64_t workspace_bytes,
                                 int64_t* unique_counts, pm_stream_t stream) {
-    pm::KParams p;
-    size_t sorted_bytes = 0, total = 0;
-    int rc = sparse_common(op, max_rows, p, sorted_bytes, total);
-    if (rc != PM_OK) return rc;
-    if (!unique_counts) return fail(PM_ERR_INVALID, "unique_counts is NULL");
-    if (p.N == 0 || p.bag_count == 0) {      // nothing was sorted: every table is empty
-        const hipError_t h = hipMemsetAsync(unique_counts, 0, sizeof(int64_t) * static_cast<size_t>(p.T), static_cast<hipStream_t>(stream));
-        if (h != hipSuccess) return hip_fail(h, "pm_embbag_sparse_grad_count");
-        return PM_OK;
-    }
-    if (!workspace || workspace_bytes < static_cast<int64_t>(total))
-        return fail(PM_ERR_INVALID, "workspace too small: need " + std::to_string(total) + " bytes (pm_embbag_sparse_grad_workspace)");
     pm::SparsePairs sp;
-    const int pi = pm::sparse_grad_pairs(p, max_rows, op->max_dim, workspace, true, sp);
-    if (pi != 0) return sparse_pairs_fail(pi);
-    const hipError_t h = pm::sparse_grad_count(sp, p.T, p.N, static_cast<char*>(workspace) + sorted_bytes, unique_counts,
+    SortedCall c{"pm_embbag_sparse_grad_workspace", op ? op->weight_dtype : -1, true, ""};
+    const pm::KParams& p = c.p;
+    const int rc = sorted_call_prologue(
+        c, op, max_rows, workspace, workspace_bytes,
+        [&]() -> int {
+            if (!unique_counts) return fail(PM_ERR_INVALID, "unique_counts is NULL");
+            if (p.N != 0 && p.bag_count != 0) return PM_OK;
+            // nothing was sorted: every table is empty
+            const hipError_t h = hipMemsetAsync(unique_counts, 0, sizeof(int64_t) * static_cast<size_t>(p.T), static_cast<hipStream_t>(stream));
+            return h != hipSuccess ? hip_fail(h, "pm_embbag_sparse_grad_count") : kDone;
+        },
+        [&] { return pm::sparse_grad_pairs(p, max_rows, op->max_dim, workspace, true, sp); });
+    if (rc != PM_OK) return rc == kDone ? PM_OK : rc;
+    const hipError_t h = pm::sparse_grad_count(sp, p.T, p.N, static_cast<char*>(workspace) + c.sorted, unique_counts,
                                                static_cast<hipStream_t>(stream));
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_sparse_grad_count launch");
     return PM_OK;
@@ -883,28 +923,25 @@ int pm_embbag_sparse_grad_count(const pm_embbag_batch* op, int64_t max_rows, voi
 
 int pm_embbag_sparse_grad(const pm_embbag_batch* op, const float* grad, int64_t max_rows, void* workspace, int64_t workspace_bytes,
                           int64_t* const* row_ids, float* const* values, pm_stream_t stream) {
-    pm::KParams p;
-    size_t sorted_bytes = 0, total = 0;
-    int rc = sparse_common(op, max_rows, p, sorted_bytes, total);
-    if (rc != PM_OK) return rc;
-    if (p.N == 0 || p.bag_count == 0) return PM_OK;
-    if (!grad || !row_ids || !values) return fail(PM_ERR_INVALID, "grad / row_ids / values is NULL");
-    if (!workspace || workspace_bytes < static_cast<int64_t>(total))
-        return fail(PM_ERR_INVALID, "workspace too small: need " + std::to_string(total) + " bytes (pm_embbag_sparse_grad_workspace)");
     pm::SparsePairs sp;
-    const int pi = pm::sparse_grad_pairs(p, max_rows, op->max_dim, workspace, false, sp);
-    if (pi != 0) return sparse_pairs_fail(pi);
-    hipError_t h = pm::sparse_grad_rows(sp, p.T, p.N, static_cast<const char*>(workspace) + sorted_bytes, op->dims, row_ids, values,
+    SortedCall c{"pm_embbag_sparse_grad_workspace", op ? op->weight_dtype : -1, true, ""};
+    const pm::KParams& p = c.p;
+    int rc = sorted_call_prologue(
+        c, op, max_rows, workspace, workspace_bytes,
+        [&]() -> int {
+            if (p.N == 0 || p.bag_count == 0) return kDone;
+            return (!grad || !row_ids || !values) ? fail(PM_ERR_INVALID, "grad / row_ids / values is NULL") : PM_OK;
+        },
+        [&] { return pm::sparse_grad_pairs(p, max_rows, op->max_dim, workspace, false, sp); });
+    if (rc != PM_OK) return rc == kDone ? PM_OK : rc;
+    hipError_t h = pm::sparse_grad_rows(sp, p.T, p.N, static_cast<const char*>(workspace) + c.sorted, op->dims, row_ids, values,
                                         static_cast<hipStream_t>(stream));
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_sparse_grad launch");
     // the sorted apply, unchanged: fp32 destination, alpha = 1, into the zeroed compact rows (row = slot)
     pm::KParams q;
     if ((rc = make_params(op, PM_F32, q)) != PM_OK) return rc;
-    q.io = const_cast<float*>(grad);
-    q.tables = reinterpret_cast<const void* const*>(values);
-    q.alpha = 1.0f;
-    if (g_nt_loads.load() < 0) q.nt_loads = kDefaultRowPolicy;
-    h = pm::bwd_sorted_apply(q, max_rows, PM_F32, op->max_dim, workspace, nullptr, nullptr, static_cast<hipStream_t>(stream));
+    apply_params(q, grad, values, 1.0f);
+    h = pm::bwd_sorted_apply(q, max_rows, PM_F32, op->max_dim, workspace, static_cast<hipStream_t>(stream));
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_sparse_grad apply launch");
     return PM_OK;
 }

@@ -189,13 +189,36 @@ hipError_t sorted_workspace_bytes(const KParams& p, int64_t max_rows, int max_di
 // reads the request's indices again.  A sort issued on its own always consumes the request completely.
 hipError_t sort_indices(const KParams& p, int64_t max_rows, int max_dim, int64_t fixed_pooling, int phases, void* workspace,
                         hipStream_t stream, bool defer_ok = false);
-int bwd_sorted_plan_check(const KParams& p, int64_t max_rows, const void* workspace, bool adagrad);
-int sorted_pairs_info(const KParams& p, int64_t max_rows, int max_dim, const void* workspace, const void** keys, const uint32_t** vals,
-                      const uint32_t** d_count, int* key_bytes, int* tshift);
+// why the sort recorded on a workspace does not fit a call (embbag_bwd_sorted.hip: find_plan; capi.hip has the one text of each)
+enum class PlanStatus {
+    ok,
+    none,                      // no sort was recorded for this workspace / it was for another request
+    two_phase,                 // sorted in two bag phases, but the apply (Adagrad) needs every row's lookups in ONE run
+    relabelled,                // pm_embbag_sparse_grad_count rewrote the keys to slots: only the sparse-gradient apply may follow
+    not_complete_segmented,    // sparse gradient: not a complete one-phase segmented sort
+    low_digit_order,           // sparse gradient: the sort's order is not ascending within a table (sort mode 1)
+    already_counted,           // sparse gradient, counting: the sort was relabelled already
+    not_counted,               // sparse gradient, applying: it was not
+};
+PlanStatus bwd_sorted_plan_check(const KParams& p, int64_t max_rows, const void* workspace, bool adagrad);
+// where the last sort on a workspace left its pairs (device pointers into the workspace): tests and tools
+struct SortedPairsInfo {
+    const void* keys;
+    const uint32_t* vals;
+    const uint32_t* d_count;
+    int key_bytes, tshift;
+    bool deferred;             // the sort was deferred into its apply (hybrid backward) and no apply has been issued: no pairs yet
+};
+PlanStatus sorted_pairs_info(const KParams& p, int64_t max_rows, int max_dim, const void* workspace, SortedPairsInfo& out);
 std::string sort_plan_describe(const KParams& p, int64_t max_rows, int64_t fixed_pooling, int phases);
-hipError_t bwd_sorted_apply(const KParams& p, int64_t max_rows, int dst_dtype, int max_dim, const void* workspace,
-                            float* const* momentum, const pm_rowwise_adagrad* opt, hipStream_t stream,
-                            float* const* elem_state = nullptr);      // element-wise Adagrad: [T] x [rows_t, dims_t] fp32 (momentum NULL then)
+// what the sorted apply does with a row's summed gradient; the default is the plain scatter-add
+struct ApplyUpdate {
+    const pm_rowwise_adagrad* opt = nullptr;   // Adagrad options (NULL: scatter-add)
+    float* const* state = nullptr;             // device [T]: fp32 state per table, [rows_t] (row-wise) or [rows_t, dims_t] (element-wise)
+    bool elementwise = false;
+};
+hipError_t bwd_sorted_apply(const KParams& p, int64_t max_rows, int dst_dtype, int max_dim, const void* workspace, hipStream_t stream,
+                            ApplyUpdate update = {});
 
 #ifdef PM_ALTERNATES
 // own stable LSD radix sort of (key, uint32) pairs (radix_sort.hip); element count optionally read from device memory
@@ -269,7 +292,7 @@ struct HybArgs {             // hybrid part of a sort request
     int slices;              // map slices per table (hyb_slices(N, T): a power of two, kBloomK .. kBloomKMax)
 };
 // (the per-table records, the dup bitmaps [min(T, kHybMaxTables)][kBloomTableWords] and the per-tile counts of flagged lookups
-// live in the sort's scratch: seg_sort_hyb_tab / seg_sort_bloom / seg_sort_tile_cnt)
+// live in the sort's scratch: seg_sort_view)
 struct HybTiles {            // how the bag-major apply tiled the request when it listed the flagged lookups (hyb_rest_kernel reads the lists)
     int bags_per_tile;       // KParams::bags_per_block of the apply
     int tiles_per_table;
@@ -311,8 +334,19 @@ int seg_sort_radix_bits(int mode, int rbits_max);   // 8, or 9 where a 9-bit dig
 bool seg_sort_lookback(int mode, int rbits_max, int64_t n);   // mode 0 as one kernel per pass (tiles learn their prefixes from their predecessors in flight)
 int seg_sort_passes(int mode, int rbits_max);
 bool seg_sort_result_in_b(int mode, int rbits_max);
-const SegDesc* seg_sort_desc(const void* scratch, size_t n_max, int T);
-const uint32_t* seg_sort_count(const void* scratch, size_t n_max, int T);   // device uint32: pairs in the sorted arrays
+struct SegScratchView {      // what the outside needs of the sort's scratch: device pointers (seg_sort.hip: scratch_layout)
+    const SegDesc* desc;
+    const uint32_t* n_total;             // device uint32: pairs in the sorted arrays
+    const uint32_t* lookback_timeouts;   // device uint32: look-back walks that gave up
+    const uint32_t* rest_pairs;          // two device words: pairs / tables hyb_rest_kernel finished in LDS (zeroed by every sort)
+    const HybTable* hyb_tab;
+    const uint32_t* bloom;
+    uint32_t* tile_cnt;                  // [T][tile_cnt_stride]: flagged lookups per tile of the bag-major apply
+    size_t tile_cnt_stride;
+    const uint32_t* rest_stage;          // [T_h][2][kRestCap]: rows | bags of a staged table
+    const uint32_t* rest_n;              // [T_h]: staged pairs of table t (0: none / not staged)
+};
+SegScratchView seg_sort_view(const void* scratch, size_t n_max, int T);
 // The sort in two parts: part A (the tables' segments and verdicts + the hybrid tables' dup bitmaps: all the bag-major apply
 // needs) and part B (everything else).  When the hybrid kernels are launched (rq.hyb.allow) part B runs inside the APPLY call,
 // after the bag-major kernel -- which lists the flagged lookups tile by tile as a by-product of its own staging -- and
@@ -326,12 +360,6 @@ hipError_t seg_sort_part_b(const SegSortRequest& rq, int mode, K* keys_a, K* key
 template <typename K>
 hipError_t seg_sort_pairs(const SegSortRequest& rq, int mode, K* keys_a, K* keys_b, uint32_t* vals_a, uint32_t* vals_b, uint32_t* bag_of,
                           void* scratch, hipStream_t stream);
-const uint32_t* seg_sort_timeouts(const void* scratch, size_t n_max, int T);   // device uint32: look-back walks that gave up
-const HybTable* seg_sort_hyb_tab(const void* scratch, size_t n_max, int T);
-const uint32_t* seg_sort_bloom(const void* scratch, size_t n_max, int T);
-uint32_t* seg_sort_tile_cnt(const void* scratch, size_t n_max, int T);     // [T][B / 4 + 1] at most: flagged lookups per tile of the bag-major apply
-size_t seg_sort_tile_cnt_stride(size_t n_max);
-uint32_t* seg_sort_rest_stat(void* scratch, size_t n_max, int T);         // two device words: pairs / tables hyb_rest_kernel finished in LDS (zeroed by every sort)
 // Round 6: what the bag-major kernel left of a hybrid table -- the flagged lookups it listed tile by tile, ~3 % of a uniform
 // request -- is STAGED by hyb_stage_kernel (seg_hybrid.inc): a table with at most kRestCap of them gets its lists copied back to
 // back (list = request-position order) as (row, bag) into its own slot of a staging area and its sort segment emptied; a table
@@ -341,8 +369,6 @@ uint32_t* seg_sort_rest_stat(void* scratch, size_t n_max, int T);         // two
 constexpr int kRestThreads = 1024;
 constexpr int kRestItems = 8;                           // pairs per thread in the LDS sort
 constexpr int kRestCap = kRestThreads * kRestItems;     // 8192 flagged lookups per table (benchmark shape: ~4 800)
-const uint32_t* seg_sort_rest_stage(const void* scratch, size_t n_max, int T);   // [T_h][2][kRestCap]: rows | bags of a staged table
-const uint32_t* seg_sort_rest_n(const void* scratch, size_t n_max, int T);       // [T_h]: staged pairs of table t (0: none / not staged)
 template <typename K>
 hipError_t seg_sort_stage_leftovers(const SegSortRequest& rq, const K* keys_b, const uint32_t* vals_b, K* keys_a, uint32_t* vals_a,
                                     HybTiles tiles, int rest_enable, void* scratch, hipStream_t stream);
@@ -365,9 +391,7 @@ struct SparsePairs {
     int tshift;
     const SegDesc* desc;     // the sort's per-table segments (out_start, count)
 };
-// embbag_bwd_sorted.hip: 0 ok; 1 no sort of this request on the workspace; 2 not a complete one-phase segmented sort; 3 the sort's
-// order is not ascending within a table (sort mode 1); 4 counting, but the sort was relabelled already; 5 applying, but it was not
-int sparse_grad_pairs(const KParams& p, int64_t max_rows, int max_dim, const void* workspace, bool counting, SparsePairs& out);
+PlanStatus sparse_grad_pairs(const KParams& p, int64_t max_rows, int max_dim, const void* workspace, bool counting, SparsePairs& out);
 int64_t sparse_grad_max_tiles(int64_t n, int T);
 size_t sparse_grad_extra_bytes(int64_t n, int T);   // behind the sorted backward's workspace: tile plan, tile counts, run rows
 hipError_t sparse_grad_count(const SparsePairs& sp, int T, int64_t n, void* extra, int64_t* unique_counts, hipStream_t stream);

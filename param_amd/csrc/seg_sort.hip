@@ -1358,7 +1358,7 @@ struct Scratch {
 
 // hyb = the request can take the hybrid backward (unweighted): only then does the layout END with the dup maps (256 KB .. 4 MB per
 // table: up to 512 MB at 128 tables), the per-tile counts, the slice queues' lengths and the left-over stage.  Everything before them
-// sits where it sits either way, so the accessors below need not know (weighted requests used to reserve all of it).
+// sits where it sits either way, so seg_sort_view below need not know (weighted requests used to reserve all of it).
 Scratch scratch_layout(void* base, size_t n, int T, bool hyb = true) {
     Scratch s;
     char* p = reinterpret_cast<char*>(base);
@@ -1396,20 +1396,11 @@ Scratch scratch_layout(void* base, size_t n, int T, bool hyb = true) {
 
 size_t seg_sort_scratch_bytes(size_t n_max, int T, bool hybrid_possible) { return scratch_layout(nullptr, n_max, T, hybrid_possible).total; }
 
-const SegDesc* seg_sort_desc(const void* scratch, size_t n_max, int T) { return scratch_layout(const_cast<void*>(scratch), n_max, T).desc; }
-const uint32_t* seg_sort_count(const void* scratch, size_t n_max, int T) {
-    return &scratch_layout(const_cast<void*>(scratch), n_max, T).hdr->n_total;
+SegScratchView seg_sort_view(const void* scratch, size_t n_max, int T) {
+    const Scratch s = scratch_layout(const_cast<void*>(scratch), n_max, T);
+    return {s.desc, &s.hdr->n_total, &s.hdr->lookback_timeouts, &s.hdr->rest_pairs, s.hyb_tab, s.bloom, s.tile_cnt, tile_cnt_stride(n_max),
+            s.rest_stage, s.rest_n};
 }
-const uint32_t* seg_sort_timeouts(const void* scratch, size_t n_max, int T) {
-    return &scratch_layout(const_cast<void*>(scratch), n_max, T).hdr->lookback_timeouts;
-}
-const HybTable* seg_sort_hyb_tab(const void* scratch, size_t n_max, int T) { return scratch_layout(const_cast<void*>(scratch), n_max, T).hyb_tab; }
-const uint32_t* seg_sort_bloom(const void* scratch, size_t n_max, int T) { return scratch_layout(const_cast<void*>(scratch), n_max, T).bloom; }
-uint32_t* seg_sort_tile_cnt(const void* scratch, size_t n_max, int T) { return scratch_layout(const_cast<void*>(scratch), n_max, T).tile_cnt; }
-size_t seg_sort_tile_cnt_stride(size_t n_max) { return tile_cnt_stride(n_max); }
-uint32_t* seg_sort_rest_stat(void* scratch, size_t n_max, int T) { return &scratch_layout(scratch, n_max, T).hdr->rest_pairs; }
-const uint32_t* seg_sort_rest_stage(const void* scratch, size_t n_max, int T) { return scratch_layout(const_cast<void*>(scratch), n_max, T).rest_stage; }
-const uint32_t* seg_sort_rest_n(const void* scratch, size_t n_max, int T) { return scratch_layout(const_cast<void*>(scratch), n_max, T).rest_n; }
 
 // mode 0 sorts 9 bits per pass where that saves a global pass over the pairs: 25 .. 27 row bits (the 40 M-row Criteo tables:
 // 3 passes instead of 4), 17 / 18 bits (2 instead of 3), 9 bits.  Everywhere else 8: a 512-value digit costs LDS (three

@@ -278,10 +278,11 @@ def _fwd_quantized(ts: _TableSet, indices, offsets, B, bitwidth: int, psw=None, 
     return out
 
 
-def _workspace(ts: _TableSet, op, max_rows: Optional[int] = None) -> torch.Tensor:
+def _workspace(ts: _TableSet, op, max_rows: Optional[int] = None, query=None) -> torch.Tensor:
     """Scratch for the sort-based backward, cached on the table set (grown, never shrunk).  ``max_rows``: of the tables ``op``
-    names, when it is a table range of the set's request."""
-    need = _lib.load().pm_embbag_bwd_sorted_workspace(ctypes.byref(op), max(ts.rows) if max_rows is None else max_rows)
+    names, when it is a table range of the set's request.  ``query``: the size function (default
+    ``pm_embbag_bwd_sorted_workspace``; the sparse gradient has its own)."""
+    need = (query or _lib.load().pm_embbag_bwd_sorted_workspace)(ctypes.byref(op), max(ts.rows) if max_rows is None else max_rows)
     if need < 0:
         _lib.check(int(need))
     ws = getattr(ts, "_ws", None)
@@ -289,6 +290,15 @@ def _workspace(ts: _TableSet, op, max_rows: Optional[int] = None) -> torch.Tenso
         ws = torch.empty(int(need), dtype=torch.uint8, device=ts.device)
         ts._ws = ws
     return ws
+
+
+def _check_grad(ts: _TableSet, grad, B) -> torch.Tensor:
+    """the gradient of a batch of B bags in the table set's output layout, contiguous"""
+    _require_device(grad, "grad")
+    _, _, shape = ts.out_desc(B)
+    if grad.dtype != torch.float32 or tuple(grad.shape) != tuple(shape):
+        raise ValueError(f"grad must be float32 of shape {shape}")
+    return grad.contiguous()
 
 
 def _sort_indices(ts: _TableSet, indices, offsets, B, psw=None, bag_begin=0, bag_count=None, phases: int = 2,
@@ -402,11 +412,7 @@ def _bwd(ts: _TableSet, grad, indices, offsets, B, dst_ptrs_dev, dst_dtype, alph
          bag_begin=0, bag_count=None, method: str = "sorted", presorted: bool = False, pooling: Optional[int] = None):
     """``method="sorted"`` (default): deterministic, bit-identical to a sequential scatter-add;
     ``method="atomic"``: hardware float atomics (order not fixed; tests / tools: the alternates build)."""
-    _require_device(grad, "grad")
-    _, _, shape = ts.out_desc(B)
-    if grad.dtype != torch.float32 or tuple(grad.shape) != tuple(shape):
-        raise ValueError(f"grad must be float32 of shape {shape}")
-    grad = grad.contiguous()
+    grad = _check_grad(ts, grad, B)
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
     L = _lib.load()
     if method == "atomic":
@@ -420,23 +426,32 @@ def _bwd(ts: _TableSet, grad, indices, offsets, B, dst_ptrs_dev, dst_dtype, alph
     if method != "sorted":
         raise ValueError('method must be "sorted" or "atomic"')
     _no_presorted_split(ts, presorted)
-    dst_dt, s = _WDTYPE[dst_dtype], _stream_ptr()
-    # (more than 1024 tables: one sorted call per table range, in table order on this stream, sharing the cached workspace)
+    dst_dt, s, g = _WDTYPE[dst_dtype], _stream_ptr(), grad.data_ptr()
+
+    def call(fn):      # the fused and the sorted call take the same arguments
+        return lambda sub, t0, max_rows, ws: fn(ctypes.byref(sub), g, dst_ptrs_dev.data_ptr() + 8 * t0, dst_dt, float(alpha), max_rows,
+                                                ws.data_ptr(), ws.numel(), s)
+    # (the alternative key sorts may lay out two bag phases for the scatter-add apply)
+    _sorted_chunks_call(ts, op, indices, offsets, B, psw, presorted, pooling, 2, call(L.pm_embbag_bwd_fused), call(L.pm_embbag_bwd_sorted))
+
+
+def _sorted_chunks_call(ts: _TableSet, op, indices, offsets, B, psw, presorted: bool, pooling, phases: int, fused, sorted_) -> None:
+    """The sorted backward of the request ``op``, one call per range of at most 1024 tables, in table order on this stream, sharing
+    the cached workspace.  ``fused(sub, t0, max_rows, ws)`` issues the fused call (sort + apply) of a range, ``sorted_`` the apply
+    of a sorted one; both return the library's code.  ``phases``: what a sort issued here may lay out (2: scatter-add, 1: Adagrad)."""
+    L, s = _lib.load(), _stream_ptr()
     for sub, t0, t1, max_rows in _table_chunks(ts, op, indices, offsets, B, psw):
         ws = _workspace(ts, sub, max_rows)
-        dst = dst_ptrs_dev.data_ptr() + 8 * t0
         if not presorted and not _lib.needs_pooling_hint():
             # sort + apply sequenced by the library itself: the one form in which it may defer part of the sort into the apply
             # (hybrid backward: rows looked up once skip the sort)
             sub.fixed_pooling = 0  # (the cached descriptor may carry a hint from an alternates-build run: the segmented sort takes none)
-            _lib.check(L.pm_embbag_bwd_fused(ctypes.byref(sub), grad.data_ptr(), dst, dst_dt, float(alpha), max_rows, ws.data_ptr(),
-                                             ws.numel(), s))
+            _lib.check(fused(sub, t0, max_rows, ws))
             continue
         if not presorted:      # the alternative key sorts (sort_impl 1 / 2) read a pooling hint and may lay out two bag phases
             sub.fixed_pooling = ts.fixed_pooling(indices, offsets, B, pooling) if sub is op else 0
-            _lib.check(L.pm_embbag_sort_indices_ex(ctypes.byref(sub), max_rows, 2, ws.data_ptr(), ws.numel(), s))
-        _lib.check(L.pm_embbag_bwd_sorted(ctypes.byref(sub), grad.data_ptr(), dst, dst_dt, float(alpha), max_rows, ws.data_ptr(),
-                                          ws.numel(), s))
+            _lib.check(L.pm_embbag_sort_indices_ex(ctypes.byref(sub), max_rows, phases, ws.data_ptr(), ws.numel(), s))
+        _lib.check(sorted_(sub, t0, max_rows, ws))
 
 
 def check_request(ts: _TableSet, indices, offsets, B, psw=None) -> None:
@@ -462,11 +477,7 @@ def _adagrad(ts: _TableSet, grad, indices, offsets, B, mom_ptrs_dev, lr: float, 
     fp32 ``[rows_t, dims_t]`` state buffer per table)."""
     if weight_decay_mode not in _WD_MODES:
         raise ValueError(f"weight_decay_mode must be one of none / l2 / decouple, got {weight_decay_mode!r}")
-    _require_device(grad, "grad")
-    _, _, shape = ts.out_desc(B)
-    if grad.dtype != torch.float32 or tuple(grad.shape) != tuple(shape):
-        raise ValueError(f"grad must be float32 of shape {shape}")
-    grad = grad.contiguous()
+    grad = _check_grad(ts, grad, B)
     _no_presorted_split(ts, presorted)
     op = ts.request(indices, offsets, B, psw, 0, None)
     L = _lib.load()
@@ -476,31 +487,20 @@ def _adagrad(ts: _TableSet, grad, indices, offsets, B, mom_ptrs_dev, lr: float, 
     # (more than 1024 tables: one call per table range, as in _bwd.  A stochastic-rounding draw is keyed by the seed, the table's
     # number INSIDE its call, the row and the column pair: every range gets a seed of its own -- the first one the caller's -- so
     # that table t and table t + 1024 do not share their draws)
-    for sub, t0, t1, max_rows in _table_chunks(ts, op, indices, offsets, B, psw):
-        opt = _lib.pm_rowwise_adagrad(float(lr), float(eps), float(weight_decay), _WD_MODES[weight_decay_mode],
-                                      1 if stochastic_rounding else 0, 0, (int(seed) + (t0 << 32)) & (2**64 - 1))
-        ws = _workspace(ts, sub, max_rows)
-        tabs, mom = ts.d_ptrs.data_ptr() + 8 * t0, mom_ptrs_dev.data_ptr() + 8 * t0
-        if not presorted and not _lib.needs_pooling_hint():
-            sub.fixed_pooling = 0
-            _lib.check(fused_call(ctypes.byref(sub), grad.data_ptr(), tabs, wdt, mom, ctypes.byref(opt), max_rows, ws.data_ptr(), ws.numel(), s))
-            continue
-        if not presorted:
-            sub.fixed_pooling = ts.fixed_pooling(indices, offsets, B, pooling) if sub is op else 0
-            _lib.check(L.pm_embbag_sort_indices_ex(ctypes.byref(sub), max_rows, 1, ws.data_ptr(), ws.numel(), s))
-        _lib.check(sorted_call(ctypes.byref(sub), grad.data_ptr(), tabs, wdt, mom, ctypes.byref(opt), max_rows, ws.data_ptr(), ws.numel(), s))
+    def call(fn):
+        def issue(sub, t0, max_rows, ws):
+            opt = _lib.pm_rowwise_adagrad(float(lr), float(eps), float(weight_decay), _WD_MODES[weight_decay_mode],
+                                          1 if stochastic_rounding else 0, 0, (int(seed) + (t0 << 32)) & (2**64 - 1))
+            return fn(ctypes.byref(sub), grad.data_ptr(), ts.d_ptrs.data_ptr() + 8 * t0, wdt, mom_ptrs_dev.data_ptr() + 8 * t0,
+                      ctypes.byref(opt), max_rows, ws.data_ptr(), ws.numel(), s)
+        return issue
+    _sorted_chunks_call(ts, op, indices, offsets, B, psw, presorted, pooling, 1, call(fused_call), call(sorted_call))
 
 
 def _sparse_grad_call(ts: _TableSet, op, grad, max_rows: int, dims: Sequence[int]):
     """sort + count + (one synchronisation) + exact allocation + relabelled apply of ONE request of at most 1024 tables"""
     L = _lib.load()
-    need = L.pm_embbag_sparse_grad_workspace(ctypes.byref(op), max_rows)
-    if need < 0:
-        _lib.check(int(need))
-    ws = getattr(ts, "_ws", None)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(int(need), dtype=torch.uint8, device=ts.device)
-        ts._ws = ws
+    ws = _workspace(ts, op, max_rows, L.pm_embbag_sparse_grad_workspace)
     s = _stream_ptr()
     _lib.check(L.pm_embbag_sort_indices(ctypes.byref(op), max_rows, ws.data_ptr(), ws.numel(), s))
     counts = torch.empty(len(dims), dtype=torch.int64, device=ts.device)
@@ -519,11 +519,7 @@ def _sparse_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, bag_begin=0
     """Coalesced sparse gradient (``pm_embbag_sparse_grad*``): a list of T ``(rows_t, values_t)`` -- rows_t the distinct rows table t's
     lookups hit (ascending int64), values_t ``[U_t, D_t]`` fp32, ``values_t[k] = sum_{j: idx_j = rows_t[k]} w_j * grad[t, bag(j)]`` in
     the sorted backward's order.  Synchronises once per request of at most 1024 tables (to size the outputs)."""
-    _require_device(grad, "grad")
-    _, _, shape = ts.out_desc(B)
-    if grad.dtype != torch.float32 or tuple(grad.shape) != tuple(shape):
-        raise ValueError(f"grad must be float32 of shape {shape}")
-    grad = grad.contiguous()
+    grad = _check_grad(ts, grad, B)
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
     op.fixed_pooling = 0
     # more tables than one sorted call takes: independent requests of at most 1024 tables (_table_chunks)
@@ -537,11 +533,7 @@ def _psw_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, out=None, bag_
     """Gradient of ``per_sample_weights`` (``pm_embbag_psw_grad``): fp32 ``[N]``, ``out[j] = <grad[t, bag(j)], table_t[indices[j]]>``
     for the lookups of the bag slice, with the arithmetic fixed in include/param_amd.h.  ``psw`` only keeps the cached request
     descriptor of the backward that follows: the value does not depend on it."""
-    _require_device(grad, "grad")
-    _, _, shape = ts.out_desc(B)
-    if grad.dtype != torch.float32 or tuple(grad.shape) != tuple(shape):
-        raise ValueError(f"grad must be float32 of shape {shape}")
-    grad = grad.contiguous()
+    grad = _check_grad(ts, grad, B)
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
     n = indices.numel()
     if out is None:
@@ -781,6 +773,9 @@ class BatchedEmbeddingBagMI355(nn.Module):
             return n // T
         raise ValueError(f"offsets has {n} entries: neither T*B+1 nor T*B for T={T}")
 
+    def _batch(self, offsets, indices, batch: Optional[int]) -> int:
+        return self._batch_of(offsets, indices) if batch is None else batch
+
     # -- ops ---------------------------------------------------------------------------------
     def lookup(self, indices, offsets, per_sample_weights=None, out=None, bag_begin=0, bag_count=None,
                batch: Optional[int] = None, split_bags: bool = False):
@@ -810,7 +805,7 @@ class BatchedEmbeddingBagMI355(nn.Module):
                      for_adagrad: Optional[bool] = None, pooling: Optional[int] = None) -> None:
         """Pre-sort the request for the deterministic backward (can overlap the forward).  ``for_adagrad`` (default: what
         the module's optimizer is): the fused row-wise Adagrad needs a one-phase sort, the scatter-add apply may use two."""
-        B = self._batch_of(offsets, indices) if batch is None else batch
+        B = self._batch(offsets, indices, batch)
         if for_adagrad is None:
             for_adagrad = self.optimizer in ("rowwise_adagrad", "adagrad")
         _sort_indices(self._tables(), indices, offsets, B, per_sample_weights, phases=1 if for_adagrad else 2, pooling=pooling)
@@ -821,13 +816,13 @@ class BatchedEmbeddingBagMI355(nn.Module):
         """In place ``W_t[idx[j]] += alpha * psw[j] * grad(t, bag(j))`` (alpha = -lr: SGD step).  ``pooling``: the
         caller's word that every bag has exactly that many lookups (saves the one-off device check of a new request)."""
         ts = self._tables()
-        B = self._batch_of(offsets, indices) if batch is None else batch
+        B = self._batch(offsets, indices, batch)
         _bwd(ts, grad, indices, offsets, B, ts.d_ptrs, self.weights.dtype, alpha, per_sample_weights,
              bag_begin, bag_count, method, presorted, pooling)
 
     def sort_status(self, indices, offsets, per_sample_weights=None, batch: Optional[int] = None, bag_begin=0, bag_count=None) -> dict:
         """status of the last key sort on this module's workspace (synchronises)"""
-        B = self._batch_of(offsets, indices) if batch is None else batch
+        B = self._batch(offsets, indices, batch)
         return sort_status(self._tables(), indices, offsets, B, per_sample_weights, bag_begin, bag_count)
 
     def momentum_table(self, t: int) -> torch.Tensor:
@@ -860,7 +855,7 @@ class BatchedEmbeddingBagMI355(nn.Module):
         W[r,d] -= lr * G[r,d] / (sqrt(s[r,d]) + eps)``, same options (l2 adds ``wd * W`` to ``G`` first).  (Called on a module of
         any other optimizer, the step is the row-wise one, as before.)"""
         self.momentum_table(0)
-        B = self._batch_of(offsets, indices) if batch is None else batch
+        B = self._batch(offsets, indices, batch)
         self._sr_step += 1          # a fresh stochastic-rounding stream every step, reproducible run to run
         _adagrad(self._tables(), grad, indices, offsets, B, self._mom_ptrs, self.learning_rate, self.eps,
                  per_sample_weights, presorted, self.weight_decay, self.weight_decay_mode, self.stochastic_rounding,
@@ -879,7 +874,7 @@ class BatchedEmbeddingBagMI355(nn.Module):
                    method: str = "sorted"):
         """fp32 dense gradients (list, one per table) -- small tables / parity tests only."""
         ts = self._tables()
-        B = self._batch_of(offsets, indices) if batch is None else batch
+        B = self._batch(offsets, indices, batch)
         outs = [torch.zeros(r, d, dtype=torch.float32, device=ts.device) for r, d in zip(self.rows, self.dims)]
         d_ptrs = torch.tensor([o.data_ptr() for o in outs], dtype=torch.int64, device=ts.device)
         _bwd(ts, grad, indices, offsets, B, d_ptrs, torch.float32, 1.0, per_sample_weights, method=method)
@@ -895,7 +890,7 @@ class BatchedEmbeddingBagMI355(nn.Module):
         synchronises once (to read the U_t and allocate exactly), as torch's ``coalesce()`` does -- once per 1024 tables for larger
         requests, which are split into independent calls.  The gradient with respect to ``per_sample_weights`` is a call of its
         own: ``per_sample_weights_grad``."""
-        B = self._batch_of(offsets, indices) if batch is None else batch
+        B = self._batch(offsets, indices, batch)
         return _sparse_grad(self._tables(), grad, indices, offsets, B, per_sample_weights, bag_begin, bag_count)
 
     def per_sample_weights_grad(self, grad, indices, offsets, batch: Optional[int] = None, out=None, bag_begin=0, bag_count=None):
@@ -907,9 +902,9 @@ class BatchedEmbeddingBagMI355(nn.Module):
         entries of lookups outside it are zero in a tensor the method allocates and untouched in a caller's ``out``.  Any number
         of tables (no sort, no workspace).  Call it BEFORE an in-place update of the tables."""
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
-        B = self._batch_of(offsets, indices) if batch is None else batch
+        B = self._batch(offsets, indices, batch)
         return _psw_grad(self._tables(), grad, indices, offsets, B, None, out, bag_begin, bag_count)
 
     def check(self, indices, offsets, per_sample_weights=None, batch: Optional[int] = None) -> None:
-        B = self._batch_of(offsets, indices) if batch is None else batch
+        B = self._batch(offsets, indices, batch)
         check_request(self._tables(), indices, offsets, B, per_sample_weights)
