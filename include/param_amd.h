@@ -80,8 +80,8 @@ typedef struct pm_embbag_batch {
     const int32_t* dims;          /* device [T] */
     const int64_t* out_offsets;   /* device [T], element units (see above) */
     int64_t out_stride;           /* element units (see above) */
-    const void* indices;          /* device [N] */
-    const void* offsets;          /* device [T*B] or [T*B+1] */
+    const void* indices;          /* device [N]; WRITTEN by pm_embbag_bounds_check in its two repairing modes, by nothing else */
+    const void* offsets;          /* device [T*B] or [T*B+1]; WRITTEN by pm_embbag_bounds_check in its two repairing modes, by nothing else */
     const float* per_sample_weights; /* device [N] or NULL */
     int64_t fixed_pooling;        /* (ABI v4: only the sort_impl 1 / 2 alternatives read it; the default sort establishes every
                                      table's pooling on the device by reading the offsets.)
@@ -413,6 +413,49 @@ int pm_embbag_check(const pm_embbag_batch* op, int32_t* d_error_count, pm_stream
  * multiple of max_dim -- what pm_embbag_fwd_quantized assumes. */
 enum { PM_CHECK_UNIFORM_DIMS = 1 };
 int pm_embbag_check_ex(const pm_embbag_batch* op, int32_t flags, int32_t* d_error_count, pm_stream_t stream);
+
+/*
+ * Bounds check in front of the lookups: repair (or count) out-of-range indices and broken offsets ON THE DEVICE, stream-ordered, with
+ * no host synchronisation -- so that the forward / backward kernels, which do not check, can be handed the arrays of a real input
+ * pipeline.  Replaces fbgemm's bounds_check_indices kernel, which SplitTableBatchedEmbeddingBagsCodegen(bounds_check_mode=...) runs in
+ * front of every forward (BoundsCheckMode FATAL | WARNING | IGNORE | NONE; the reference builds that module at
+ * train/compute/python/workloads/pytorch/split_table_batched_embeddings_ops.py:279-300 and train/comms/pt/comms_utils.py:1994-2017).
+ * pm_embbag_check above can only count, walks a bag per thread and is read back by its callers; it stays as the independent verdict.
+ *
+ * The rule, for T tables, B bags per table, N = num_indices lookups (bag_begin / bag_count are ignored: the whole request is sanitised):
+ *   offsets   o = the first T * B entries;  o'[0] = 0,  o'[k] = max(o'[k - 1], clamp(o[k], 0, N))  -- a clamp followed by an inclusive
+ *             prefix maximum, the monotone closure.  (fbgemm repairs bag by bag with a benign race between neighbouring bags; this
+ *             rule has no race and is idempotent.)  A trailing entry offsets[T * B], present iff PM_BOUNDS_LAST_OFFSET is or'ed
+ *             into `mode`, becomes N.
+ *   table     lookup j in [0, N) belongs to the last table t with o'[t * B] <= j: every lookup to exactly one table, empty tables own none.
+ *   indices   indices[j] outside [0, rows[t]) becomes 0 (fbgemm's replacement value).  per_sample_weights are not touched.
+ *   report    d_report, device int64[4], OVERWRITTEN by every call (never accumulated), every field deterministic:
+ *             [0] bad_indices       entries replaced                    [2] first_bad_index   smallest such position, or PM_BOUNDS_NONE
+ *             [1] bad_offsets       offsets entries whose stored value  [3] first_bad_offset  smallest such position, or PM_BOUNDS_NONE
+ *                                   changes (the trailing one included)
+ *   writes    memory is written only where a value changes: a clean request stays bit-identical, its report is {0, 0, none, none}.
+ * After a repairing call the request satisfies exactly what pm_embbag_check demands.  tests/bounds_rules.py restates the rule in numpy.
+ *   mode      PM_BOUNDS_FATAL    dry run: count, write nothing to indices / offsets (the caller reads the report and raises)
+ *             PM_BOUNDS_WARNING  repair in place and report
+ *             PM_BOUNDS_IGNORE   repair in place, no report (d_report is not used and may be NULL)
+ * d_scratch: pm_embbag_bounds_check_scratch(op) bytes of caller-owned device memory, 8-byte aligned (the scan's partial maxima, one per
+ * PM_BOUNDS_OFFSETS_PER_WG offsets, and the T + 1 repaired table borders).  indices / offsets need only be aligned to their element.
+ * Any number of tables, int32 / int64 (int32: num_indices < 2^31).  Four launches, none waits for another workgroup inside a launch.
+ * Safe on arbitrary contents of both arrays: no offset is used as an address before it is clamped, indices are read inside [0, N).
+ * Refused on the host, before any HIP call: what every entry point refuses, an unknown mode, a NULL d_report outside IGNORE, a
+ * scratch that is NULL or too small.  batch == 0: PM_OK, nothing is launched and nothing written (the report neither: it would be
+ * {0, 0, none, none}); num_indices == 0: the offsets are still repaired.
+ * The ABI version is unchanged (8): a client that needs these two finds out at symbol resolution.
+ */
+#define PM_BOUNDS_FATAL   1   /* dry run: count, write nothing            */
+#define PM_BOUNDS_WARNING 2   /* repair in place and report               */
+#define PM_BOUNDS_IGNORE  3   /* repair in place, no report (may be NULL) */
+#define PM_BOUNDS_LAST_OFFSET 0x100          /* or'ed into mode: offsets has T * B + 1 entries; the last one becomes num_indices */
+#define PM_BOUNDS_NONE INT64_MAX             /* first_bad_* of a report without a finding */
+#define PM_BOUNDS_OFFSETS_PER_WG 2048        /* offsets per workgroup of the scan: sizes the scratch */
+int64_t pm_embbag_bounds_check_scratch(const pm_embbag_batch* op);            /* bytes of partials and borders */
+int     pm_embbag_bounds_check(const pm_embbag_batch* op, int32_t mode, int64_t* d_report /*[4]*/,
+                               void* d_scratch, int64_t scratch_bytes, pm_stream_t stream);
 
 /*
  * Fill a buffer with counter-based pseudo-random values at HBM write speed:

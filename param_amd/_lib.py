@@ -15,6 +15,11 @@ PM_F32, PM_BF16, PM_F16, PM_I32, PM_I64 = 0, 1, 2, 10, 11
 PM_OK, PM_ERR_INVALID, PM_ERR_UNSUPPORTED, PM_ERR_HIP, PM_ERR_INDEX = 0, -1, -2, -3, -4
 PM_ABI_VERSION = 8
 PM_WD_NONE, PM_WD_L2, PM_WD_DECOUPLE = 0, 1, 2
+# pm_embbag_bounds_check (include/param_amd.h): modes, the flag for a [T*B+1] offsets array, "no finding", offsets per scan workgroup
+PM_BOUNDS_FATAL, PM_BOUNDS_WARNING, PM_BOUNDS_IGNORE = 1, 2, 3
+PM_BOUNDS_LAST_OFFSET = 0x100
+PM_BOUNDS_NONE = 2**63 - 1
+PM_BOUNDS_OFFSETS_PER_WG = 2048
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PARAM_AMD_LIB") or os.path.join(_HERE, "libparam_amd.so")   # PARAM_AMD_LIB: kernel experiments only
@@ -62,6 +67,8 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_sparse_grad_count",
     "pm_embbag_sparse_grad",
     "pm_embbag_psw_grad",
+    "pm_embbag_bounds_check_scratch",
+    "pm_embbag_bounds_check",
 )
 
 
@@ -230,6 +237,10 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embbag_sparse_grad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i64, vp, i64, vp, vp, vp]
     L.pm_embbag_psw_grad.restype = ctypes.c_int
     L.pm_embbag_psw_grad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp]
+    L.pm_embbag_bounds_check_scratch.restype = ctypes.c_int64
+    L.pm_embbag_bounds_check_scratch.argtypes = [ctypes.POINTER(pm_embbag_batch)]
+    L.pm_embbag_bounds_check.restype = ctypes.c_int
+    L.pm_embbag_bounds_check.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, vp, vp, i64, vp]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]

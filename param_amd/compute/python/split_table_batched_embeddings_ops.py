@@ -102,7 +102,10 @@ class SplitTableBatchedEmbeddingBagsCodegenOp(OperatorInterface):
 
     def build(self, num_tables: int, rows, dims, pooling: int, weighted: bool, weights_precision: str,
               optimizer: str, lr: float = 0.01, eps: float = 1.0e-8, weight_decay: float = 0.0,
-              weight_decay_mode=None):
+              weight_decay_mode=None, bounds_check_mode=None):
+        """(``bounds_check_mode``, trailing and optional -- the reference's positional config stops before it: fbgemm TBE's
+        constructor argument, a name / ``BoundsCheckMode`` member / its int; default ``none``.  The forward then repairs or
+        refuses a bad request on the device first, and the backward sees the repaired tensors.)"""
         from ... import BatchedEmbeddingBagMI355
 
         rows_list = rows if isinstance(rows, list) else [rows] * num_tables
@@ -118,7 +121,8 @@ class SplitTableBatchedEmbeddingBagsCodegenOp(OperatorInterface):
                                            device=dev, init="uniform_dlrm", learning_rate=lr, fused_update=True,
                                            optimizer=opt, eps=eps, weight_decay=weight_decay,
                                            weight_decay_mode=_wd_mode(weight_decay_mode),
-                                           stochastic_rounding=True)   # the reference's fixed choice (:291)
+                                           stochastic_rounding=True,   # the reference's fixed choice (:291)
+                                           bounds_check_mode=bounds_check_mode)
 
     def cleanup(self):
         self.op = None

@@ -973,6 +973,50 @@ int pm_embbag_check(const pm_embbag_batch* op, int32_t* d_error_count, pm_stream
     return pm_embbag_check_ex(op, 0, d_error_count, stream);
 }
 
+// what both bounds-check calls refuse beyond make_params: sizes the index type cannot hold, pointers off their element
+static int bounds_request(const pm_embbag_batch* op, pm::KParams& p) {
+    const int rc = make_params(op, op ? op->weight_dtype : -1, p);
+    if (rc != PM_OK) return rc;
+    if (op->index_dtype == PM_I32 && op->num_indices > 0x7fffffffLL)
+        return fail(PM_ERR_INVALID, "pm_embbag_bounds_check: int32 offsets cannot hold num_indices >= 2^31");
+    if (op->batch > 0 && !op->offsets) return fail(PM_ERR_INVALID, "offsets is NULL");
+    const uintptr_t es = op->index_dtype == PM_I64 ? 8 : 4;
+    if (reinterpret_cast<uintptr_t>(op->indices) % es != 0 || reinterpret_cast<uintptr_t>(op->offsets) % es != 0)
+        return fail(PM_ERR_INVALID, "pm_embbag_bounds_check: indices / offsets must be aligned to their element type");
+    return PM_OK;
+}
+
+int64_t pm_embbag_bounds_check_scratch(const pm_embbag_batch* op) {
+    pm::KParams p;
+    const int rc = bounds_request(op, p);
+    if (rc != PM_OK) return rc;
+    return pm::bounds_check_scratch_bytes(static_cast<int64_t>(p.T) * p.B, p.T);
+}
+
+int pm_embbag_bounds_check(const pm_embbag_batch* op, int32_t mode, int64_t* d_report, void* d_scratch, int64_t scratch_bytes,
+                           pm_stream_t stream) {
+    pm::KParams p;
+    const int rc = bounds_request(op, p);
+    if (rc != PM_OK) return rc;
+    const int32_t what = mode & ~PM_BOUNDS_LAST_OFFSET;
+    if (what != PM_BOUNDS_FATAL && what != PM_BOUNDS_WARNING && what != PM_BOUNDS_IGNORE)
+        return fail(PM_ERR_INVALID, "pm_embbag_bounds_check: unknown mode " + std::to_string(mode) +
+                                        " (PM_BOUNDS_FATAL, PM_BOUNDS_WARNING or PM_BOUNDS_IGNORE, optionally | PM_BOUNDS_LAST_OFFSET)");
+    if (what == PM_BOUNDS_IGNORE) d_report = nullptr;
+    else if (!d_report) return fail(PM_ERR_INVALID, "pm_embbag_bounds_check: d_report is NULL (only PM_BOUNDS_IGNORE goes without a report)");
+    if (reinterpret_cast<uintptr_t>(d_report) % 8 != 0) return fail(PM_ERR_INVALID, "pm_embbag_bounds_check: d_report must be 8-byte aligned");
+    const int64_t need = pm::bounds_check_scratch_bytes(static_cast<int64_t>(p.T) * p.B, p.T);
+    if (need == 0) return PM_OK;                                 // no bags: nothing is repaired, nothing is launched
+    if (!d_scratch || scratch_bytes < need)
+        return fail(PM_ERR_INVALID, "pm_embbag_bounds_check: scratch is NULL or too small: " + std::to_string(need) +
+                                        " bytes needed (pm_embbag_bounds_check_scratch)");
+    if (reinterpret_cast<uintptr_t>(d_scratch) % 8 != 0) return fail(PM_ERR_INVALID, "pm_embbag_bounds_check: scratch must be 8-byte aligned");
+    const hipError_t h = pm::launch_bounds_check(p, what != PM_BOUNDS_FATAL, (mode & PM_BOUNDS_LAST_OFFSET) != 0, d_report, d_scratch,
+                                                 static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_bounds_check launch");
+    return PM_OK;
+}
+
 int pm_fill_random(void* dst, int64_t count, int32_t dtype, int32_t dist, float lo, float hi, uint64_t seed,
                    pm_stream_t stream) {
     if (count < 0) return fail(PM_ERR_INVALID, "negative count");

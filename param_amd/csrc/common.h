@@ -179,6 +179,9 @@ hipError_t launch_embbag_bwd(const KParams& p, int dst_dtype, int max_dim, hipSt
 #endif
 hipError_t launch_embbag_check(const KParams& p, int32_t* d_err, int vec, int max_dim, int64_t fixed_pooling,
                                int uniform_dims, hipStream_t stream);
+// bounds check / repair of a request (bounds_check.hip): scratch = partial maxima + T + 1 table borders; report: device int64[4] or NULL
+int64_t bounds_check_scratch_bytes(int64_t TB, int T);
+hipError_t launch_bounds_check(const KParams& p, bool write, bool has_last, int64_t* report, void* scratch, hipStream_t stream);
 hipError_t launch_fill_random(void* dst, int64_t count, int dtype, int dist, float lo, float hi,
                               uint64_t seed, hipStream_t stream);
 

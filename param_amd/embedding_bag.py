@@ -465,6 +465,110 @@ def check_request(ts: _TableSet, indices, offsets, B, psw=None) -> None:
         raise IndexError(f"param_amd: {n} out-of-range indices / invalid offsets in EmbeddingBag request")
 
 
+_BOUNDS_MODES = {"fatal": _lib.PM_BOUNDS_FATAL, "warning": _lib.PM_BOUNDS_WARNING, "ignore": _lib.PM_BOUNDS_IGNORE, "none": 0}
+_FBGEMM_BOUNDS_INTS = {0: "fatal", 1: "warning", 2: "ignore", 3: "none"}      # fbgemm_gpu's BoundsCheckMode values
+
+
+def bounds_check_mode_name(mode) -> str:
+    """``"fatal" | "warning" | "ignore" | "none"`` from what a caller of fbgemm's TBE module passes as ``bounds_check_mode``: one of
+    those names in any case, a ``BoundsCheckMode`` member (read by its name) or its int (FATAL 0, WARNING 1, IGNORE 2, NONE 3);
+    ``None`` is ``"none"``.  Anything else raises ValueError."""
+    if mode is None:
+        return "none"
+    name = getattr(mode, "name", None)
+    if isinstance(name, str):
+        key = name.lower()
+    elif isinstance(mode, str):
+        key = mode.lower()
+    elif isinstance(mode, int) and not isinstance(mode, bool):
+        key = _FBGEMM_BOUNDS_INTS.get(mode)
+    else:
+        key = None
+    if key not in _BOUNDS_MODES:
+        raise ValueError(f"bounds_check_mode must be one of fatal / warning / ignore / none (any case, fbgemm's BoundsCheckMode "
+                         f"members or their ints 0 .. 3), got {mode!r}")
+    return key
+
+
+def _bounds_report_dict(report: torch.Tensor) -> dict:
+    """the device report of ``pm_embbag_bounds_check`` as a dict (synchronises); PM_BOUNDS_NONE -> None"""
+    bi, bo, fi, fo = report.tolist()
+    none = _lib.PM_BOUNDS_NONE
+    return {"bad_indices": bi, "bad_offsets": bo, "first_bad_index": None if fi == none else fi,
+            "first_bad_offset": None if fo == none else fo}
+
+
+def _bounds_check(ts: _TableSet, indices, offsets, B, mode: str, report: Optional[torch.Tensor], psw=None, bag_begin=0,
+                  bag_count=None) -> None:
+    """``pm_embbag_bounds_check`` on the whole request (the plain descriptor: T tables, batch B -- also for ``layout="blocked"``),
+    stream-ordered, no synchronisation.  ``psw`` / ``bag_begin`` / ``bag_count`` only keep the cached descriptor of the lookup that
+    follows; the call reads none of them.  ``report``: int64[4] on the device (``"ignore"``: not used).  Memory the call repairs is
+    written behind torch's back: the table set's verdict about the offsets' contents is dropped."""
+    op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
+    L = _lib.load()
+    need = L.pm_embbag_bounds_check_scratch(ctypes.byref(op))
+    if need < 0:
+        _lib.check(int(need))
+    scratch = getattr(ts, "_bounds_scratch", None)
+    if scratch is None or scratch.numel() * 8 < need:
+        scratch = torch.empty((int(need) + 7) // 8, dtype=torch.int64, device=ts.device)
+        ts._bounds_scratch = scratch
+    flags = _BOUNDS_MODES[mode] | (_lib.PM_BOUNDS_LAST_OFFSET if offsets.numel() == ts.T * B + 1 else 0)
+    if report is not None and ts.T * B == 0:
+        report.copy_(torch.tensor([0, 0, _lib.PM_BOUNDS_NONE, _lib.PM_BOUNDS_NONE], dtype=torch.int64))     # nothing is launched for no bags
+    rc = L.pm_embbag_bounds_check(ctypes.byref(op), flags, None if report is None or mode == "ignore" else report.data_ptr(),
+                                  scratch.data_ptr(), scratch.numel() * 8, _stream_ptr())
+    if rc:
+        _lib.check(rc)
+    if mode != "fatal":
+        ts._pool_key = None
+
+
+class _BoundsChecked:
+    """``bounds_check_mode`` of the two modules (fbgemm TBE's constructor argument): with a mode other than ``"none"`` every
+    ``forward`` / ``lookup`` first runs the device-side sanitiser (``pm_embbag_bounds_check``; rule in include/param_amd.h) on the
+    caller's ``indices`` / ``offsets``, so that the lookup and -- through the tensors autograd saved -- the backward see the repaired
+    request.  The other standalone entry points (``scatter_add_``, ``adagrad_step_``, ``dense_grad``, ``sparse_grad``,
+    ``per_sample_weights_grad``, ``sort_indices``, ``lookup_quantized``) do NOT call it: run ``sanitize_`` in front of them.
+
+    * ``"none"`` (default): no launch, no byte touched.
+    * ``"ignore"``: repair in place.
+    * ``"warning"``: repair in place and keep the report on the device; ``bounds_report()`` synchronises and returns the last call's.
+    * ``"fatal"``: dry run, ONE synchronisation, then ``IndexError`` naming counts and first positions; the caller's tensors are
+      untouched and no lookup kernel is issued.
+    """
+
+    def _init_bounds(self, bounds_check_mode) -> None:
+        self.bounds_check_mode = bounds_check_mode_name(bounds_check_mode)
+        self._bounds_report: Optional[torch.Tensor] = None
+        self._bounds_reported = False
+
+    def _sanitize(self, ts: _TableSet, indices, offsets, B, mode: str, psw=None, bag_begin=0, bag_count=None) -> None:
+        rep = None
+        if mode != "ignore":
+            rep = self._bounds_report
+            if rep is None or rep.device != ts.device:
+                rep = self._bounds_report = torch.empty(4, dtype=torch.int64, device=ts.device)
+        _bounds_check(ts, indices, offsets, B, mode, rep, psw, bag_begin, bag_count)
+        self._bounds_reported = rep is not None
+        if mode != "fatal":
+            self._b1_key = None              # (BatchedEmbeddingBagMI355: the T == 1 memo of what offsets[-1] said)
+            return
+        r = _bounds_report_dict(rep)
+        if r["bad_indices"] or r["bad_offsets"]:
+            raise IndexError(f"param_amd: bounds_check_mode=fatal: {r['bad_indices']} out-of-range indices (first at position "
+                             f"{r['first_bad_index']}), {r['bad_offsets']} invalid offsets (first at position {r['first_bad_offset']}) "
+                             "in EmbeddingBag request")
+
+    def bounds_report(self) -> Optional[dict]:
+        """What the last sanitiser call of this module found (``"warning"`` and ``"fatal"`` calls; synchronises):
+        ``{"bad_indices", "bad_offsets", "first_bad_index", "first_bad_offset"}``, the positions ``None`` without a finding.
+        ``None`` when the last call kept no report (``"ignore"``) or none has run."""
+        if not self._bounds_reported or self._bounds_report is None:
+            return None
+        return _bounds_report_dict(self._bounds_report)
+
+
 _WD_MODES = {None: _lib.PM_WD_NONE, "none": _lib.PM_WD_NONE, 0: _lib.PM_WD_NONE, "l2": _lib.PM_WD_L2, 1: _lib.PM_WD_L2,
              "decouple": _lib.PM_WD_DECOUPLE, "decoupled": _lib.PM_WD_DECOUPLE, 2: _lib.PM_WD_DECOUPLE}
 
@@ -593,7 +697,7 @@ class _SparseGradFn(_DenseGradFn):
         return g, None, None, None, d_psw
 
 
-class EmbeddingBagMI355(nn.Module):
+class EmbeddingBagMI355(nn.Module, _BoundsChecked):
     """``torch.nn.EmbeddingBag(num_embeddings, embedding_dim, mode="sum")`` on MI355X HIP kernels.
 
     Same call contract as the module the reference builds at pytorch_emb.py:179 and
@@ -602,13 +706,16 @@ class EmbeddingBagMI355(nn.Module):
     ``sparse=True``: ``weight.grad`` is a sparse COO tensor, as torch's, but coalesced -- one row per distinct index looked up
     (``U x D`` values, not torch's ``N x D``); torch's sparse-capable optimizers (``SparseAdam``, ``SGD``, ``Adagrad``) take it.
     The backward then synchronises once (to size the gradient), as ``coalesce()`` does.
+    ``bounds_check_mode`` (default ``"none"``): see :class:`_BoundsChecked` -- ``forward`` repairs / refuses a bad request first.
     """
 
     def __init__(self, num_embeddings: int, embedding_dim: int, mode: str = "sum", sparse: bool = False,
-                 dtype: torch.dtype = torch.float32, device=None, _weight: Optional[torch.Tensor] = None):
+                 dtype: torch.dtype = torch.float32, device=None, _weight: Optional[torch.Tensor] = None,
+                 bounds_check_mode="none"):
         super().__init__()
         if mode != "sum":
             raise NotImplementedError('only mode="sum" is on the reference hot path (pytorch_emb.py:179)')
+        self._init_bounds(bounds_check_mode)      # (validated before anything is allocated)
         self.num_embeddings, self.embedding_dim, self.mode, self.sparse = num_embeddings, embedding_dim, mode, sparse
         if _weight is None:
             w = torch.empty(num_embeddings, embedding_dim, dtype=dtype, device=device)
@@ -643,12 +750,21 @@ class EmbeddingBagMI355(nn.Module):
         w = self._parameters["weight"]
         if not w.is_cuda:
             _require_device(w, "EmbeddingBagMI355.weight")
+        if self.bounds_check_mode != "none":
+            self._sanitize(self._tables(), indices, offsets, offsets.numel(), self.bounds_check_mode, per_sample_weights)
         if w.requires_grad and torch.is_grad_enabled():
             return (_SparseGradFn if self.sparse else _DenseGradFn).apply(w, self, indices, offsets, per_sample_weights)
         ts = self._ts
         if ts is None or ts.ptrs[0] != w.data_ptr():
             ts = self._tables()
         return _fwd(ts, indices, offsets, offsets.numel(), per_sample_weights)
+
+    def sanitize_(self, indices, offsets, mode=None) -> None:
+        """The sanitiser on its own (``offsets`` is ``[B]``, as ``forward`` takes it): in place, stream-ordered.  ``mode``: default
+        the module's ``bounds_check_mode``, ``"warning"`` where that is ``"none"``."""
+        _require_device(self.weight, "EmbeddingBagMI355.weight")
+        mode = bounds_check_mode_name(mode) if mode is not None else self.bounds_check_mode
+        self._sanitize(self._tables(), indices, offsets, offsets.numel(), "warning" if mode == "none" else mode)
 
     def extra_repr(self) -> str:
         return f"{self.num_embeddings}, {self.embedding_dim}, mode=sum, dtype={self.weight.dtype}" + (", sparse=True" if self.sparse else "")
@@ -677,7 +793,7 @@ class _FusedUpdateFn(torch.autograd.Function):
         return None, None, None, None, d_psw
 
 
-class BatchedEmbeddingBagMI355(nn.Module):
+class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     """T embedding tables in one HBM slab, looked up by ONE kernel launch.
 
     ``forward(indices, offsets, per_sample_weights=None)`` uses the TBE request layout
@@ -685,14 +801,20 @@ class BatchedEmbeddingBagMI355(nn.Module):
     (``layout="bd"``) or ``[T, B, D]`` (``layout="tbd"``, dlrm.py's ``torch.stack`` shape) or ``[B / block_bags, T, block_bags, D]``
     (``layout="blocked"``: the send layout of a table-wise sharded exchange -- every peer's chunk contiguous, made of ``[block_bags, D]``
     runs per table; forward whole-batch requests only).
+
+    ``bounds_check_mode`` (default ``"none"``; fbgemm TBE's argument of that name): see :class:`_BoundsChecked` -- ``forward`` and
+    ``lookup`` repair / refuse a bad request first, ``sanitize_`` is the call on its own.  With ONE table and a mode other than
+    ``"none"`` pass ``batch=``: whether a ``[B + 1]`` or a ``[B]`` offsets tensor was meant is otherwise guessed from ``offsets[-1]``,
+    which may be the corrupt entry.
     """
 
     def __init__(self, rows: Sequence[int], dims, dtype: torch.dtype = torch.float32, device="cuda",
                  layout: str = "bd", init: Optional[str] = "uniform_dlrm", seed: int = 0,
                  learning_rate: float = 0.01, fused_update: bool = True, optimizer: str = "sgd", eps: float = 1.0e-8,
                  weight_decay: float = 0.0, weight_decay_mode=None, stochastic_rounding: bool = False,
-                 block_bags: Optional[int] = None):
+                 block_bags: Optional[int] = None, bounds_check_mode="none"):
         super().__init__()
+        self._init_bounds(bounds_check_mode)      # (validated, like the optimizer below, before anything is allocated)
         rows = [int(r) for r in rows]
         dims = [int(dims)] * len(rows) if isinstance(dims, int) else [int(d) for d in dims]
         assert len(rows) == len(dims) and len(rows) >= 1
@@ -783,7 +905,19 @@ class BatchedEmbeddingBagMI355(nn.Module):
         one-workgroup-per-bag kernel for few, long bags (deterministic, fp32-rounding-close to the default, not bit-equal)."""
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
         B = self._batch_of(offsets, indices) if batch is None else batch
+        if self.bounds_check_mode != "none":
+            self._sanitize(self._tables(), indices, offsets, B, self.bounds_check_mode, per_sample_weights, bag_begin, bag_count)
         return _fwd(self._tables(), indices, offsets, B, per_sample_weights, out, bag_begin, bag_count, split_bags)
+
+    def sanitize_(self, indices, offsets, batch: Optional[int] = None, mode=None) -> None:
+        """The sanitiser on its own, in front of any entry point that does not run it (everything but ``forward`` / ``lookup``):
+        repairs ``indices`` / ``offsets`` in place on the current stream, without a synchronisation (``"fatal"``: one, and nothing
+        is written).  ``mode``: default the module's ``bounds_check_mode``, ``"warning"`` where that is ``"none"``;
+        ``bounds_report()`` reads what it found.  One table: pass ``batch=`` (see the class)."""
+        _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
+        B = self._batch(offsets, indices, batch)
+        mode = bounds_check_mode_name(mode) if mode is not None else self.bounds_check_mode
+        self._sanitize(self._tables(), indices, offsets, B, "warning" if mode == "none" else mode)
 
     def lookup_quantized(self, indices, offsets, bitwidth: int, per_sample_weights=None, out=None, bag_begin=0,
                          bag_count=None, batch: Optional[int] = None):
