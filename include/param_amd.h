@@ -386,6 +386,51 @@ int pm_embbag_bwd_fused_adagrad_elem(const pm_embbag_batch* op, const float* gra
 int pm_embbag_psw_grad(const pm_embbag_batch* op, const float* grad, float* out, pm_stream_t stream);
 
 /*
+ * PADDING -- torch's nn.EmbeddingBag(mode="sum", padding_idx=...) rule, per table: padding_idx is a device array int64 [num_tables],
+ * padding_idx[t] in [0, rows[t]) names table t's padding row, -1 says the table has none (a value outside [-1, rows[t]) is the
+ * caller's error: the Python modules check it at construction).  A lookup j of table t with indices[j] == padding_idx[t] is PADDED:
+ * it contributes nothing to the forward, its row receives no gradient and no optimizer update, and its per_sample_weights gradient
+ * is +0.0.  The request struct is unchanged (sizeof 144): the array is an extra argument of the four functions below, and a client
+ * that needs them finds out at symbol resolution -- the ABI version stays 8.  tests/padding_rules.py restates the rule in numpy.
+ *
+ * pm_embbag_fwd_padded   out(t, b)[:] = sum over the lookups j of bag (t, b) with indices[j] != padding_idx[t], in index order from +0.0,
+ *                        of psw[j] * table_t[indices[j], :] -- plain fp32 adds unweighted, one fused multiply-add per kept lookup
+ *                        weighted: the arithmetic of pm_embbag_fwd, and bit-identical to pm_embbag_fwd on the request with the padded
+ *                        lookups removed.  A bag of padding only gives +0.0 everywhere, like an empty bag.  The padding row is never
+ *                        read into a sum: a NaN or Inf stored there reaches no output.  Same request, layouts, dtypes, bag slices and
+ *                        refusals as pm_embbag_fwd; a NULL padding_idx is PM_ERR_INVALID.  A kernel family of its own
+ *                        (csrc/embbag_fwd_pad.hip): a tile's indices are compacted while they are staged into LDS, so a padded lookup
+ *                        costs no row load; bags longer than the LDS index tile predicate the load off.
+ * pm_embbag_pad_mask     values: fp32 [num_indices], indexed like `indices` (the output of pm_embbag_psw_grad): writes +0.0 at every
+ *                        padded lookup of the bags inside [bag_begin, bag_begin + bag_count) and touches nothing else.  Run it behind
+ *                        pm_embbag_psw_grad on the same stream.
+ * pm_pad_rows_guard      keeps the padding rows out of a backward WITHOUT changing it: called with PM_PAD_SAVE before, and with
+ *                        PM_PAD_RESTORE after, any of pm_embbag_bwd_sorted* / pm_embbag_bwd_fused* (one call or several: the table
+ *                        ranges of a request of more than 1024 tables), it copies row padding_idx[t] of every table t that has one --
+ *                        dims[t] elements of table_dtype at tables[t] -- into slot t of the caller-owned `stash` and back, and with it
+ *                        the row's optimizer state: state_kind PM_PAD_STATE_ROW one fp32 at state[t][padding_idx[t]] (row-wise
+ *                        Adagrad), PM_PAD_STATE_ELEM dims[t] fp32 at state[t] + padding_idx[t] * dims[t] (element-wise Adagrad),
+ *                        PM_PAD_STATE_NONE nothing (state may be NULL).  After the restore the padding rows and their state hold their
+ *                        earlier bits whatever the optimizer, decay mode or rounding did to them; every other row is what the backward
+ *                        made it.  `tables` may be the weight tables or the fp32 destination buffers of a dense gradient.  One wave per
+ *                        table, 16-byte copies, stream-ordered, no synchronisation.  stash: pm_pad_rows_guard_bytes(num_tables, max_dim,
+ *                        table_dtype, state_kind) bytes, 16-byte aligned; max_dim >= every dims[t].  The padded lookups are still
+ *                        sorted and accumulated by the backward in between -- into a row that is then put back.
+ * Null pointers, an unknown dtype, state kind or direction, and a stash that is too small are PM_ERR_INVALID, before any HIP call.
+ * Replaces the padding_idx handling inside aten::_embedding_bag / _embedding_bag_dense_backward /
+ * _embedding_bag_per_sample_weights_backward (the kernels behind train/compute/pt/pytorch_emb.py:40,61,179).
+ */
+#define PM_PAD_SAVE    0
+#define PM_PAD_RESTORE 1
+enum { PM_PAD_STATE_NONE = 0, PM_PAD_STATE_ROW = 1, PM_PAD_STATE_ELEM = 2 };
+int pm_embbag_fwd_padded(const pm_embbag_batch* op, const int64_t* padding_idx, float* out, pm_stream_t stream);
+int pm_embbag_pad_mask(const pm_embbag_batch* op, const int64_t* padding_idx, float* values, pm_stream_t stream);
+int64_t pm_pad_rows_guard_bytes(int32_t num_tables, int32_t max_dim, int32_t table_dtype, int32_t state_kind);
+int pm_pad_rows_guard(int32_t num_tables, int32_t max_dim, void* const* tables, const int32_t* dims, int32_t table_dtype,
+                      const int64_t* padding_idx, float* const* state, int32_t state_kind, void* stash, int64_t stash_bytes,
+                      int32_t direction, pm_stream_t stream);
+
+/*
  * DLRM input redistribution on the device: regroup what the lengths / indices all-to-alls deliver
  * (train/comms/pt/dlrm.py:744-855) -- lengths [world][num_tables][batch] int64 and the indices
  * concatenated block by block in that (rank, table) order -- into the TBE request of the batched

@@ -20,6 +20,9 @@ PM_BOUNDS_FATAL, PM_BOUNDS_WARNING, PM_BOUNDS_IGNORE = 1, 2, 3
 PM_BOUNDS_LAST_OFFSET = 0x100
 PM_BOUNDS_NONE = 2**63 - 1
 PM_BOUNDS_OFFSETS_PER_WG = 2048
+# pm_pad_rows_guard: direction, and which optimizer state travels with a padding row
+PM_PAD_SAVE, PM_PAD_RESTORE = 0, 1
+PM_PAD_STATE_NONE, PM_PAD_STATE_ROW, PM_PAD_STATE_ELEM = 0, 1, 2
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PARAM_AMD_LIB") or os.path.join(_HERE, "libparam_amd.so")   # PARAM_AMD_LIB: kernel experiments only
@@ -69,6 +72,10 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_psw_grad",
     "pm_embbag_bounds_check_scratch",
     "pm_embbag_bounds_check",
+    "pm_embbag_fwd_padded",
+    "pm_embbag_pad_mask",
+    "pm_pad_rows_guard_bytes",
+    "pm_pad_rows_guard",
 )
 
 
@@ -241,6 +248,15 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embbag_bounds_check_scratch.argtypes = [ctypes.POINTER(pm_embbag_batch)]
     L.pm_embbag_bounds_check.restype = ctypes.c_int
     L.pm_embbag_bounds_check.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, vp, vp, i64, vp]
+    # padding: the pad array (device int64 [T], -1 = none) is an extra argument, the request struct is unchanged
+    L.pm_embbag_fwd_padded.restype = ctypes.c_int
+    L.pm_embbag_fwd_padded.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp]
+    L.pm_embbag_pad_mask.restype = ctypes.c_int
+    L.pm_embbag_pad_mask.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp]
+    L.pm_pad_rows_guard_bytes.restype = ctypes.c_int64
+    L.pm_pad_rows_guard_bytes.argtypes = [i32, i32, i32, i32]
+    L.pm_pad_rows_guard.restype = ctypes.c_int
+    L.pm_pad_rows_guard.argtypes = [i32, i32, vp, vp, i32, vp, vp, i32, vp, i64, i32, vp]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]

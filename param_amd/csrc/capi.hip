@@ -644,6 +644,94 @@ int pm_embbag_fwd(const pm_embbag_batch* op, float* out, pm_stream_t stream) {
     return PM_OK;
 }
 
+// ---- padding (embbag_fwd_pad.hip, pad_rows.hip) --------------------------------------------------------------------------
+// The padded forward keeps the plain bag-count tiling of make_params and adds the product forward's output burst where the
+// tile's rows fit 16 KB (the tile is halved until they do); requests whose lookups divide evenly over the bags get an index
+// tile sized for what a tile holds, as the product forward's do (a longer tile reads its indices from the request).
+static void plan_padded_forward(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p) {
+    const int NG = pm::kBlock / pm::group_lanes(op->max_dim, (elem_dtype == PM_F32) ? 4 : 8);
+    int bpb = p.bags_per_block;
+    if (g_bags_per_block.load() <= 0)
+        while (bpb > NG && static_cast<int64_t>(bpb) * op->max_dim * 4 > 16384) bpb /= 2;
+    p.bags_per_block = bpb;
+    p.tiles_per_table = static_cast<int32_t>((op->bag_count + bpb - 1) / bpb);      // (bpb only shrank: the grid check of validate_request holds)
+    const int64_t total_bags = static_cast<int64_t>(op->num_tables) * op->batch;
+    const bool even = total_bags > 0 && op->num_indices % total_bags == 0;
+    int want = g_stage_out.load();
+    if (want < 0) want = fwd_env().stage;
+    p.stage_out = (want && static_cast<int64_t>(bpb) * op->max_dim * 4 <= 16384) ? op->max_dim : 0;
+    p.stage_bags = bpb;
+    if (even) {
+        int64_t need = (2 * static_cast<int64_t>(bpb) * (op->num_indices / total_bags) + 255) / 256 * 256;
+        if (need < 512) need = 512;
+        if (need < p.idx_cap) p.idx_cap = static_cast<int32_t>(need);
+    }
+    p.ordered = 0;
+}
+
+int pm_embbag_fwd_padded(const pm_embbag_batch* op, const int64_t* padding_idx, float* out, pm_stream_t stream) {
+    pm::KParams p;
+    int rc = make_params(op, op ? op->weight_dtype : -1, p);
+    if (rc != PM_OK) return rc;
+    if (!padding_idx) return fail(PM_ERR_INVALID, "padding_idx is NULL (device int64 [num_tables], -1 = no padding row: pm_embbag_fwd takes requests without one)");
+    if (p.bag_count == 0) return PM_OK;
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    plan_padded_forward(op, op->weight_dtype, p);
+    p.io = out;
+    const hipError_t h = pm::launch_embbag_fwd_padded(p, op->weight_dtype, op->max_dim, padding_idx, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_fwd_padded launch");
+    return PM_OK;
+}
+
+int pm_embbag_pad_mask(const pm_embbag_batch* op, const int64_t* padding_idx, float* values, pm_stream_t stream) {
+    pm::KParams p;
+    int rc = make_params(op, op ? op->weight_dtype : -1, p);
+    if (rc != PM_OK) return rc;
+    if (!padding_idx) return fail(PM_ERR_INVALID, "padding_idx is NULL");
+    if (!values && op->num_indices > 0) return fail(PM_ERR_INVALID, "values is NULL");
+    if (p.bag_count == 0 || p.N == 0) return PM_OK;
+    const hipError_t h = pm::launch_pad_mask(p, padding_idx, values, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_pad_mask launch");
+    return PM_OK;
+}
+
+static int pad_guard_layout(int32_t num_tables, int32_t max_dim, int32_t table_dtype, int32_t state_kind, int64_t& row_slot, int64_t& slot) {
+    if (num_tables < 1) return fail(PM_ERR_INVALID, "num_tables must be >= 1");
+    if (!dtype_is_weight(table_dtype)) return fail(PM_ERR_INVALID, "weight/dst dtype must be PM_F32, PM_BF16 or PM_F16");
+    const int vec = (table_dtype == PM_F32) ? 4 : 8;
+    if (max_dim < 1 || max_dim % vec != 0)
+        return fail(PM_ERR_UNSUPPORTED, "every dims[t] (and max_dim) must be a multiple of " + std::to_string(vec) + " for this element type");
+    if (state_kind != PM_PAD_STATE_NONE && state_kind != PM_PAD_STATE_ROW && state_kind != PM_PAD_STATE_ELEM)
+        return fail(PM_ERR_INVALID, "state_kind must be PM_PAD_STATE_NONE, PM_PAD_STATE_ROW or PM_PAD_STATE_ELEM");
+    row_slot = static_cast<int64_t>(max_dim) * (16 / vec);                      // a multiple of 16 bytes
+    slot = row_slot + (state_kind == PM_PAD_STATE_ROW ? 16 : state_kind == PM_PAD_STATE_ELEM ? static_cast<int64_t>(max_dim) * 4 : 0);
+    return PM_OK;
+}
+
+int64_t pm_pad_rows_guard_bytes(int32_t num_tables, int32_t max_dim, int32_t table_dtype, int32_t state_kind) {
+    int64_t row_slot = 0, slot = 0;
+    const int rc = pad_guard_layout(num_tables, max_dim, table_dtype, state_kind, row_slot, slot);
+    return rc != PM_OK ? rc : slot * num_tables;
+}
+
+int pm_pad_rows_guard(int32_t num_tables, int32_t max_dim, void* const* tables, const int32_t* dims, int32_t table_dtype,
+                      const int64_t* padding_idx, float* const* state, int32_t state_kind, void* stash, int64_t stash_bytes,
+                      int32_t direction, pm_stream_t stream) {
+    int64_t row_slot = 0, slot = 0;
+    const int rc = pad_guard_layout(num_tables, max_dim, table_dtype, state_kind, row_slot, slot);
+    if (rc != PM_OK) return rc;
+    if (direction != PM_PAD_SAVE && direction != PM_PAD_RESTORE) return fail(PM_ERR_INVALID, "direction must be PM_PAD_SAVE or PM_PAD_RESTORE");
+    if (!tables || !dims || !padding_idx) return fail(PM_ERR_INVALID, "tables / dims / padding_idx is NULL");
+    if (state_kind != PM_PAD_STATE_NONE && !state) return fail(PM_ERR_INVALID, "state is NULL");
+    if (!stash || stash_bytes < slot * num_tables)
+        return fail(PM_ERR_INVALID, "stash is NULL or too small: " + std::to_string(slot * num_tables) + " bytes needed (pm_pad_rows_guard_bytes)");
+    if (reinterpret_cast<uintptr_t>(stash) % 16 != 0) return fail(PM_ERR_INVALID, "stash must be 16-byte aligned");
+    const hipError_t h = pm::launch_pad_guard(num_tables, tables, dims, table_dtype == PM_F32 ? 4 : 2, padding_idx, state, state_kind, stash,
+                                              slot, row_slot, direction == PM_PAD_RESTORE, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_pad_rows_guard launch");
+    return PM_OK;
+}
+
 int pm_embbag_fwd_quantized(const pm_embbag_batch* op, void* out, int32_t bitwidth, pm_stream_t stream) {
     pm::KParams p;
     int rc = make_params(op, op ? op->weight_dtype : -1, p, true);

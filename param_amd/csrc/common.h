@@ -184,6 +184,12 @@ int64_t bounds_check_scratch_bytes(int64_t TB, int T);
 hipError_t launch_bounds_check(const KParams& p, bool write, bool has_last, int64_t* report, void* scratch, hipStream_t stream);
 hipError_t launch_fill_random(void* dst, int64_t count, int dtype, int dist, float lo, float hi,
                               uint64_t seed, hipStream_t stream);
+// padding (embbag_fwd_pad.hip, pad_rows.hip): pad_idx = device int64 [T], -1 = the table has no padding row
+hipError_t launch_embbag_fwd_padded(const KParams& p, int weight_dtype, int max_dim, const int64_t* pad_idx, hipStream_t stream);
+hipError_t launch_pad_guard(int T, void* const* tables, const int32_t* dims, int elem_bytes, const int64_t* pad_idx,
+                            float* const* state, int state_kind, void* stash, int64_t slot_bytes, int64_t row_slot_bytes,
+                            bool restore, hipStream_t stream);
+hipError_t launch_pad_mask(const KParams& p, const int64_t* pad_idx, float* values, hipStream_t stream);
 
 // sort-based deterministic backward (embbag_bwd_sorted.hip)
 hipError_t sorted_workspace_bytes(const KParams& p, int64_t max_rows, int max_dim, size_t& bytes);

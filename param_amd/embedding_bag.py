@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import operator
 from typing import Optional, Sequence
 
 import torch
@@ -57,6 +58,57 @@ def fill_random_(t: torch.Tensor, dist: str = "normal", a: float = 0.0, b: float
                                           1 if dist == "normal" else 0, float(a), float(b),
                                           int(seed) & (2**64 - 1), _stream_ptr()))
     return t
+
+
+def _normalize_padding_idx(padding_idx, num_embeddings: int) -> Optional[int]:
+    """torch's rule for ``padding_idx`` (``nn.EmbeddingBag.__init__``): ``None``, or an int in ``[-n, n)``; negative values count
+    from the end.  Out of range raises with torch's text."""
+    if padding_idx is None:
+        return None
+    if isinstance(padding_idx, bool):
+        raise TypeError("padding_idx must be an int or None")
+    k = operator.index(padding_idx)
+    if not -num_embeddings <= k < num_embeddings:
+        raise ValueError(f"padding_idx must be within num_embeddings (got {k} for {num_embeddings} rows)")
+    return k + num_embeddings if k < 0 else k
+
+
+def _pad_tensor(pads: Sequence[Optional[int]], device) -> torch.Tensor:
+    """the device form of per-table padding indices: int64 ``[T]``, -1 = the table has none (include/param_amd.h)"""
+    return torch.tensor([-1 if k is None else k for k in pads], dtype=torch.int64, device=device)
+
+
+class _PadGuard:
+    """``pm_pad_rows_guard`` around a backward call that is left as it is: ``save()`` copies every table's padding row (and its
+    optimizer state) into a stash cached on the table set, ``restore()`` puts them back -- two small stream-ordered launches, no
+    synchronisation.  ``tables_dev`` / ``state_dev``: device pointer arrays ``[T]`` (the weight tables or a dense gradient's
+    buffers; the Adagrad state).  With ``pad=None`` both calls do nothing."""
+
+    def __init__(self, ts: "_TableSet", pad: Optional[torch.Tensor], tables_dev: torch.Tensor, dtype: torch.dtype,
+                 state_dev: Optional[torch.Tensor] = None, state_kind: int = _lib.PM_PAD_STATE_NONE):
+        self.pad = pad
+        if pad is None:
+            return
+        L = _lib.load()
+        self.args = (ts.T, ts.max_dim, tables_dev.data_ptr(), ts.d_dims.data_ptr(), _WDTYPE[dtype], pad.data_ptr(),
+                     None if state_dev is None else state_dev.data_ptr(), state_kind)
+        need = L.pm_pad_rows_guard_bytes(ts.T, ts.max_dim, _WDTYPE[dtype], state_kind)
+        if need < 0:
+            _lib.check(int(need))
+        stash = getattr(ts, "_pad_stash", None)
+        if stash is None or stash.numel() < need:
+            stash = ts._pad_stash = torch.empty(int(need), dtype=torch.uint8, device=ts.device)
+        self.stash = stash
+
+    def _call(self, direction: int) -> None:
+        if self.pad is not None:
+            _lib.check(_lib.load().pm_pad_rows_guard(*self.args, self.stash.data_ptr(), self.stash.numel(), direction, _stream_ptr()))
+
+    def save(self) -> None:
+        self._call(_lib.PM_PAD_SAVE)
+
+    def restore(self) -> None:
+        self._call(_lib.PM_PAD_RESTORE)
 
 
 class _TableSet:
@@ -233,9 +285,13 @@ class _TableSet:
         return op
 
 
-def _fwd(ts: _TableSet, indices, offsets, B, psw=None, out=None, bag_begin=0, bag_count=None, split_bags: bool = False):
+def _fwd(ts: _TableSet, indices, offsets, B, psw=None, out=None, bag_begin=0, bag_count=None, split_bags: bool = False,
+         pad: Optional[torch.Tensor] = None):
     """``split_bags``: one workgroup per bag with wave-shuffle / LDS partial reductions (``pm_embbag_fwd_split``) -- for
-    few, long bags; agrees with the default kernel to fp32 rounding, not bit for bit."""
+    few, long bags; agrees with the default kernel to fp32 rounding, not bit for bit.  ``pad``: per-table padding indices
+    (device int64 ``[T]``, -1 = none): the padded forward (``pm_embbag_fwd_padded``); ``None``: the call is what it always was."""
+    if pad is not None and (split_bags or ts.layout == "blocked"):
+        raise ValueError('padding_idx is not supported with split_bags=True or layout="blocked"')
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count, forward=True)
     _, _, shape = ts.out_desc(B)
     if out is None:
@@ -243,7 +299,10 @@ def _fwd(ts: _TableSet, indices, offsets, B, psw=None, out=None, bag_begin=0, ba
     elif out.dtype != torch.float32 or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
         raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
     L = _lib.load()
-    rc = (L.pm_embbag_fwd_split if split_bags else L.pm_embbag_fwd)(ctypes.byref(op), out.data_ptr(), _stream_ptr())
+    if pad is not None:
+        rc = L.pm_embbag_fwd_padded(ctypes.byref(op), pad.data_ptr(), out.data_ptr(), _stream_ptr())
+    else:
+        rc = (L.pm_embbag_fwd_split if split_bags else L.pm_embbag_fwd)(ctypes.byref(op), out.data_ptr(), _stream_ptr())
     if rc:
         _lib.check(rc)
     return out
@@ -409,9 +468,18 @@ def _no_presorted_split(ts, presorted: bool) -> None:
 
 
 def _bwd(ts: _TableSet, grad, indices, offsets, B, dst_ptrs_dev, dst_dtype, alpha, psw=None,
-         bag_begin=0, bag_count=None, method: str = "sorted", presorted: bool = False, pooling: Optional[int] = None):
+         bag_begin=0, bag_count=None, method: str = "sorted", presorted: bool = False, pooling: Optional[int] = None,
+         pad: Optional[torch.Tensor] = None):
     """``method="sorted"`` (default): deterministic, bit-identical to a sequential scatter-add;
-    ``method="atomic"``: hardware float atomics (order not fixed; tests / tools: the alternates build)."""
+    ``method="atomic"``: hardware float atomics (order not fixed; tests / tools: the alternates build).
+    ``pad``: per-table padding indices (device int64 ``[T]``): those rows of the destinations are saved before and restored
+    after the call (``_PadGuard``) -- once, around all table ranges of a large request."""
+    if pad is not None:
+        guard = _PadGuard(ts, pad, dst_ptrs_dev, dst_dtype)
+        guard.save()
+        _bwd(ts, grad, indices, offsets, B, dst_ptrs_dev, dst_dtype, alpha, psw, bag_begin, bag_count, method, presorted, pooling)
+        guard.restore()
+        return
     grad = _check_grad(ts, grad, B)
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
     L = _lib.load()
@@ -575,10 +643,18 @@ _WD_MODES = {None: _lib.PM_WD_NONE, "none": _lib.PM_WD_NONE, 0: _lib.PM_WD_NONE,
 
 def _adagrad(ts: _TableSet, grad, indices, offsets, B, mom_ptrs_dev, lr: float, eps: float, psw=None,
              presorted: bool = False, weight_decay: float = 0.0, weight_decay_mode=None, stochastic_rounding: bool = False,
-             seed: int = 0, pooling: Optional[int] = None, elementwise: bool = False):
+             seed: int = 0, pooling: Optional[int] = None, elementwise: bool = False, pad: Optional[torch.Tensor] = None):
     """Fused backward + exact row-wise Adagrad on the tables of ``ts`` (``pm_embbag_bwd_sorted_adagrad_ex``), or, with
     ``elementwise``, exact element-wise Adagrad (``pm_embbag_bwd_sorted_adagrad_elem``: ``mom_ptrs_dev`` then points at one
-    fp32 ``[rows_t, dims_t]`` state buffer per table)."""
+    fp32 ``[rows_t, dims_t]`` state buffer per table).  ``pad``: per-table padding indices (device int64 ``[T]``): those rows
+    and their state are saved before and restored after the step (``_PadGuard``)."""
+    if pad is not None:
+        guard = _PadGuard(ts, pad, ts.d_ptrs, ts.dtype, mom_ptrs_dev, _lib.PM_PAD_STATE_ELEM if elementwise else _lib.PM_PAD_STATE_ROW)
+        guard.save()
+        _adagrad(ts, grad, indices, offsets, B, mom_ptrs_dev, lr, eps, psw, presorted, weight_decay, weight_decay_mode,
+                 stochastic_rounding, seed, pooling, elementwise)
+        guard.restore()
+        return
     if weight_decay_mode not in _WD_MODES:
         raise ValueError(f"weight_decay_mode must be one of none / l2 / decouple, got {weight_decay_mode!r}")
     grad = _check_grad(ts, grad, B)
@@ -601,8 +677,9 @@ def _adagrad(ts: _TableSet, grad, indices, offsets, B, mom_ptrs_dev, lr: float, 
     _sorted_chunks_call(ts, op, indices, offsets, B, psw, presorted, pooling, 1, call(fused_call), call(sorted_call))
 
 
-def _sparse_grad_call(ts: _TableSet, op, grad, max_rows: int, dims: Sequence[int]):
-    """sort + count + (one synchronisation) + exact allocation + relabelled apply of ONE request of at most 1024 tables"""
+def _sparse_grad_call(ts: _TableSet, op, grad, max_rows: int, dims: Sequence[int], pads=None):
+    """sort + count + (one synchronisation) + exact allocation + relabelled apply of ONE request of at most 1024 tables.
+    ``pads``: the tables' padding indices (host ints / None): those rows are taken out of the result (one more synchronisation)."""
     L = _lib.load()
     ws = _workspace(ts, op, max_rows, L.pm_embbag_sparse_grad_workspace)
     s = _stream_ptr()
@@ -616,10 +693,31 @@ def _sparse_grad_call(ts: _TableSet, op, grad, max_rows: int, dims: Sequence[int
     v_ptrs = torch.tensor([v.data_ptr() for v in vals], dtype=torch.int64, device=ts.device)
     _lib.check(L.pm_embbag_sparse_grad(ctypes.byref(op), grad.data_ptr(), max_rows, ws.data_ptr(), ws.numel(), r_ptrs.data_ptr(),
                                        v_ptrs.data_ptr(), s))
+    if pads is not None:
+        rows, vals = _drop_padding_rows(rows, vals, pads)
     return list(zip(rows, vals))
 
 
-def _sparse_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, bag_begin=0, bag_count=None):
+def _drop_padding_rows(rows, vals, pads):
+    """the padding row out of every table's coalesced ``(rows_t, values_t)``: rows_t is ascending, so the row's slot is one
+    ``searchsorted``; the slots of all padded tables come back in ONE device-to-host read (-1: the row was not looked up)"""
+    at = [(t, k) for t, k in enumerate(pads) if k is not None and rows[t].numel()]
+    if not at:
+        return rows, vals
+    found = []
+    for t, k in at:
+        key = torch.tensor([k], dtype=torch.int64, device=rows[t].device)
+        pos = torch.searchsorted(rows[t], key).clamp_(max=rows[t].numel() - 1)
+        found.append(torch.where(rows[t][pos] == key, pos, torch.full_like(pos, -1)))
+    rows, vals = list(rows), list(vals)
+    for (t, _), pos in zip(at, torch.cat(found).tolist()):
+        if pos >= 0:
+            rows[t] = torch.cat((rows[t][:pos], rows[t][pos + 1:]))
+            vals[t] = torch.cat((vals[t][:pos], vals[t][pos + 1:]))
+    return rows, vals
+
+
+def _sparse_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, bag_begin=0, bag_count=None, pads=None):
     """Coalesced sparse gradient (``pm_embbag_sparse_grad*``): a list of T ``(rows_t, values_t)`` -- rows_t the distinct rows table t's
     lookups hit (ascending int64), values_t ``[U_t, D_t]`` fp32, ``values_t[k] = sum_{j: idx_j = rows_t[k]} w_j * grad[t, bag(j)]`` in
     the sorted backward's order.  Synchronises once per request of at most 1024 tables (to size the outputs)."""
@@ -629,14 +727,16 @@ def _sparse_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, bag_begin=0
     # more tables than one sorted call takes: independent requests of at most 1024 tables (_table_chunks)
     res = []
     for sub, t0, t1, max_rows in _table_chunks(ts, op, indices, offsets, B, psw):
-        res += _sparse_grad_call(ts, sub, grad, max_rows, ts.dims[t0:t1])
+        res += _sparse_grad_call(ts, sub, grad, max_rows, ts.dims[t0:t1], None if pads is None else pads[t0:t1])
     return res
 
 
-def _psw_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, out=None, bag_begin=0, bag_count=None):
+def _psw_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, out=None, bag_begin=0, bag_count=None,
+              pad: Optional[torch.Tensor] = None):
     """Gradient of ``per_sample_weights`` (``pm_embbag_psw_grad``): fp32 ``[N]``, ``out[j] = <grad[t, bag(j)], table_t[indices[j]]>``
     for the lookups of the bag slice, with the arithmetic fixed in include/param_amd.h.  ``psw`` only keeps the cached request
-    descriptor of the backward that follows: the value does not depend on it."""
+    descriptor of the backward that follows: the value does not depend on it.  ``pad``: per-table padding indices (device int64
+    ``[T]``): the entries of padded lookups are then overwritten with +0.0 (``pm_embbag_pad_mask``, one more launch)."""
     grad = _check_grad(ts, grad, B)
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
     n = indices.numel()
@@ -647,6 +747,8 @@ def _psw_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, out=None, bag_
     rc = _lib.load().pm_embbag_psw_grad(ctypes.byref(op), grad.data_ptr(), out.data_ptr(), _stream_ptr())
     if rc:
         _lib.check(rc)
+    if pad is not None:
+        _lib.check(_lib.load().pm_embbag_pad_mask(ctypes.byref(op), pad.data_ptr(), out.data_ptr(), _stream_ptr()))
     return out
 
 
@@ -662,7 +764,7 @@ class _DenseGradFn(torch.autograd.Function):
         ctx.module, ctx.B = module, B
         ctx.save_for_backward(indices, offsets, psw if psw is not None else torch.empty(0))
         ctx.has_psw = psw is not None
-        return _fwd(ts, indices, offsets, B, psw)
+        return _fwd(ts, indices, offsets, B, psw, pad=module._pad_dev())
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -672,9 +774,10 @@ class _DenseGradFn(torch.autograd.Function):
         dW = torch.zeros(m.weight.shape, dtype=torch.float32, device=grad_out.device)
         d_ptr = torch.tensor([dW.data_ptr()], dtype=torch.int64, device=grad_out.device)
         grad_out = grad_out.contiguous()
+        pad = m._pad_dev()
         _bwd(ts, grad_out, indices, offsets, ctx.B, d_ptr, torch.float32, 1.0,
-             psw if ctx.has_psw else None)
-        d_psw = _psw_grad(ts, grad_out, indices, offsets, ctx.B, psw) if ctx.has_psw and ctx.needs_input_grad[4] else None
+             psw if ctx.has_psw else None, pad=pad)
+        d_psw = _psw_grad(ts, grad_out, indices, offsets, ctx.B, psw, pad=pad) if ctx.has_psw and ctx.needs_input_grad[4] else None
         return dW.to(m.weight.dtype), None, None, None, d_psw
 
 
@@ -688,8 +791,10 @@ class _SparseGradFn(_DenseGradFn):
         m = ctx.module
         w = m.weight
         grad_out = grad_out.contiguous()
-        ((rows, vals),) = _sparse_grad(m._tables(), grad_out, indices, offsets, ctx.B, psw if ctx.has_psw else None)
-        d_psw = _psw_grad(m._tables(), grad_out, indices, offsets, ctx.B, psw) if ctx.has_psw and ctx.needs_input_grad[4] else None
+        ((rows, vals),) = _sparse_grad(m._tables(), grad_out, indices, offsets, ctx.B, psw if ctx.has_psw else None,
+                                       pads=None if m.padding_idx is None else [m.padding_idx])
+        d_psw = (_psw_grad(m._tables(), grad_out, indices, offsets, ctx.B, psw, pad=m._pad_dev())
+                 if ctx.has_psw and ctx.needs_input_grad[4] else None)
         g = torch.sparse_coo_tensor(rows[None], vals.to(w.dtype), tuple(w.shape), is_coalesced=True)
         # autograd's accumulation into .grad keeps these very index / value tensors but drops the coalesced flag: the module's
         # post-accumulate hook sets it again when .grad still holds them (an accumulated sum of two steps is torch's own result)
@@ -707,15 +812,25 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
     (``U x D`` values, not torch's ``N x D``); torch's sparse-capable optimizers (``SparseAdam``, ``SGD``, ``Adagrad``) take it.
     The backward then synchronises once (to size the gradient), as ``coalesce()`` does.
     ``bounds_check_mode`` (default ``"none"``): see :class:`_BoundsChecked` -- ``forward`` repairs / refuses a bad request first.
+    ``padding_idx`` (default ``None``; torch's argument): an int in ``[-n, n)``, negative values count from the end.  Lookups of that
+    row contribute nothing to the output, the row gets no gradient (dense: its gradient row is zero; ``sparse=True``: it is absent
+    from the COO rows) and their ``per_sample_weights`` gradient is +0.0; the row is never read into a sum, so what it holds (NaN)
+    reaches no output.  A module that creates its own weights zero-fills the row; a caller's ``_weight`` is left alone.  ``None``
+    adds no launch.  The sanitiser runs first: a bad index it repairs to 0 is padding when ``padding_idx == 0``.
+    2-D input: ``forward(input[B, L])`` (``offsets`` must be ``None``) treats every row as one bag of L lookups, as torch does;
+    ``per_sample_weights`` then has the input's shape, and so has its gradient.
     """
 
     def __init__(self, num_embeddings: int, embedding_dim: int, mode: str = "sum", sparse: bool = False,
                  dtype: torch.dtype = torch.float32, device=None, _weight: Optional[torch.Tensor] = None,
-                 bounds_check_mode="none"):
+                 bounds_check_mode="none", padding_idx: Optional[int] = None):
         super().__init__()
         if mode != "sum":
             raise NotImplementedError('only mode="sum" is on the reference hot path (pytorch_emb.py:179)')
         self._init_bounds(bounds_check_mode)      # (validated before anything is allocated)
+        self.padding_idx = _normalize_padding_idx(padding_idx, num_embeddings if _weight is None else int(_weight.shape[0]))
+        self._pad_t: Optional[torch.Tensor] = None
+        self._off2d: dict = {}
         self.num_embeddings, self.embedding_dim, self.mode, self.sparse = num_embeddings, embedding_dim, mode, sparse
         if _weight is None:
             w = torch.empty(num_embeddings, embedding_dim, dtype=dtype, device=device)
@@ -723,6 +838,8 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
                 fill_random_(w, "normal", 0.0, 1.0, seed=torch.initial_seed())
             else:
                 nn.init.normal_(w)  # host staging only; forward refuses non-ROCm tensors
+            if self.padding_idx is not None:
+                w[self.padding_idx].zero_()      # torch: the padding row of module-made weights starts as zeros
         else:
             w = _weight
         self.weight = nn.Parameter(w)
@@ -743,10 +860,43 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
             self._ts = _TableSet([w], "bd")
         return self._ts
 
-    def forward(self, indices, offsets, per_sample_weights=None):
+    def _pad_dev(self) -> Optional[torch.Tensor]:
+        """the padding index as the kernels take it (device int64 ``[1]``), or None"""
+        if self.padding_idx is None:
+            return None
+        dev = self._parameters["weight"].device
+        if self._pad_t is None or self._pad_t.device != dev:
+            self._pad_t = _pad_tensor([self.padding_idx], dev)
+        return self._pad_t
+
+    def _bags_2d(self, input, offsets, per_sample_weights):
+        """a ``[B, L]`` input as the 1-D request of B bags of L lookups: ``offsets = arange(B) * L`` is built on the device once
+        per (B, L, dtype) and reused"""
+        if offsets is not None:
+            raise ValueError(f"if input is 2D, then offsets has to be None, as input is treated is a mini-batch of fixed length "
+                             f"sequences. However, found offsets of type {type(offsets)}")
+        B, L = int(input.shape[0]), int(input.shape[1])
+        if per_sample_weights is not None:
+            if tuple(per_sample_weights.shape) != tuple(input.shape):
+                raise ValueError(f"embedding_bag: If per_sample_weights ({tuple(per_sample_weights.shape)}) is not None, then it must "
+                                 f"have the same shape as the input ({tuple(input.shape)})")
+            per_sample_weights = per_sample_weights.reshape(-1)
+        key = (B, L, input.dtype, input.device)
+        off = self._off2d.get(key)
+        if off is None:
+            if len(self._off2d) >= 8:
+                self._off2d.clear()
+            off = self._off2d[key] = torch.arange(B, dtype=input.dtype, device=input.device) * L
+        return input.reshape(-1), off, per_sample_weights
+
+    def forward(self, indices, offsets=None, per_sample_weights=None):
         # (the reference's benchmark loop calls this once per step, pytorch_emb.py:56-66: below batch ~2048 the step IS the host
         # time of this call, so the parameter is fetched once -- nn.Module.__getattr__ per access otherwise -- and the table set
         # is revalidated by pointer only)
+        if indices.dim() == 2:
+            indices, offsets, per_sample_weights = self._bags_2d(indices, offsets, per_sample_weights)
+        elif offsets is None:
+            raise ValueError("offsets has to be a 1D Tensor but got None")
         w = self._parameters["weight"]
         if not w.is_cuda:
             _require_device(w, "EmbeddingBagMI355.weight")
@@ -757,6 +907,8 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
         ts = self._ts
         if ts is None or ts.ptrs[0] != w.data_ptr():
             ts = self._tables()
+        if self.padding_idx is not None:
+            return _fwd(ts, indices, offsets, offsets.numel(), per_sample_weights, pad=self._pad_dev())
         return _fwd(ts, indices, offsets, offsets.numel(), per_sample_weights)
 
     def sanitize_(self, indices, offsets, mode=None) -> None:
@@ -767,7 +919,8 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
         self._sanitize(self._tables(), indices, offsets, offsets.numel(), "warning" if mode == "none" else mode)
 
     def extra_repr(self) -> str:
-        return f"{self.num_embeddings}, {self.embedding_dim}, mode=sum, dtype={self.weight.dtype}" + (", sparse=True" if self.sparse else "")
+        return (f"{self.num_embeddings}, {self.embedding_dim}, mode=sum, dtype={self.weight.dtype}" + (", sparse=True" if self.sparse else "") +
+                (f", padding_idx={self.padding_idx}" if self.padding_idx is not None else ""))
 
 
 class _FusedUpdateFn(torch.autograd.Function):
@@ -788,7 +941,7 @@ class _FusedUpdateFn(torch.autograd.Function):
         d_psw = None
         if ctx.has_psw and ctx.needs_input_grad[4]:
             # before the in-place update, on the same stream: the gradient belongs to the weights the forward read
-            d_psw = _psw_grad(m._tables(), grad_out, indices, offsets, m._batch_of(offsets, indices), psw)
+            d_psw = _psw_grad(m._tables(), grad_out, indices, offsets, m._batch_of(offsets, indices), psw, pad=m._pad_dev())
         m.optimizer_step_(grad_out, indices, offsets, per_sample_weights=psw if ctx.has_psw else None)
         return None, None, None, None, d_psw
 
@@ -806,18 +959,38 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     ``lookup`` repair / refuse a bad request first, ``sanitize_`` is the call on its own.  With ONE table and a mode other than
     ``"none"`` pass ``batch=``: whether a ``[B + 1]`` or a ``[B]`` offsets tensor was meant is otherwise guessed from ``offsets[-1]``,
     which may be the corrupt entry.
+
+    ``padding_idx`` (default ``None``): ``None``, one int applied to every table, or a sequence of ``int | None`` per table; each
+    int in ``[-rows_t, rows_t)``, negative values count from the end.  The attribute ``padding_idx`` holds the normalised per-table
+    list (``None`` when no table has a padding row).  A lookup of its table's padding row contributes nothing to ``forward`` /
+    ``lookup`` (the row is never read into a sum); ``scatter_add_``, ``adagrad_step_``, ``optimizer_step_``, ``dense_grad`` and the
+    fused ``backward`` leave the row -- and its optimizer state -- bit for bit as it was; ``sparse_grad`` leaves it out;
+    ``per_sample_weights_grad`` gives +0.0 there.  ``reset_parameters`` zero-fills the padding rows.  ``lookup_quantized``,
+    ``lookup(split_bags=True)`` and ``layout="blocked"`` do not take padding (ValueError).  The sanitiser runs first: a bad index
+    it repairs to 0 is padding in a table whose ``padding_idx`` is 0.
     """
 
     def __init__(self, rows: Sequence[int], dims, dtype: torch.dtype = torch.float32, device="cuda",
                  layout: str = "bd", init: Optional[str] = "uniform_dlrm", seed: int = 0,
                  learning_rate: float = 0.01, fused_update: bool = True, optimizer: str = "sgd", eps: float = 1.0e-8,
                  weight_decay: float = 0.0, weight_decay_mode=None, stochastic_rounding: bool = False,
-                 block_bags: Optional[int] = None, bounds_check_mode="none"):
+                 block_bags: Optional[int] = None, bounds_check_mode="none", padding_idx=None):
         super().__init__()
         self._init_bounds(bounds_check_mode)      # (validated, like the optimizer below, before anything is allocated)
         rows = [int(r) for r in rows]
         dims = [int(dims)] * len(rows) if isinstance(dims, int) else [int(d) for d in dims]
         assert len(rows) == len(dims) and len(rows) >= 1
+        try:
+            pads = [padding_idx if padding_idx is None or isinstance(padding_idx, bool) else operator.index(padding_idx)] * len(rows)
+        except TypeError:      # not one integer (of any integer type) for every table: one entry per table
+            pads = list(padding_idx)
+            if len(pads) != len(rows):
+                raise ValueError(f"padding_idx has {len(pads)} entries for {len(rows)} tables (None, one int, or one int | None per table)")
+        pads = [_normalize_padding_idx(k, r) for k, r in zip(pads, rows)]
+        self.padding_idx = pads if any(k is not None for k in pads) else None
+        if self.padding_idx is not None and layout == "blocked":
+            raise ValueError('padding_idx is not supported with layout="blocked"')
+        self._pad_t: Optional[torch.Tensor] = None
         self.rows, self.dims, self.layout = rows, dims, layout
         self.block_bags = block_bags      # layout="blocked": [B / block_bags, T, block_bags, D] (the per-rank batch of a sharded exchange)
         self.learning_rate, self.fused_update = learning_rate, fused_update
@@ -869,11 +1042,22 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             else:  # U(-1/sqrt(n), 1/sqrt(n)): pytorch_dist_backend.py:923-934
                 lim = math.sqrt(1.0 / self.rows[t])
                 fill_random_(w, "uniform", -lim, lim, seed=seed * 1000003 + t)
+            if self.padding_idx is not None and self.padding_idx[t] is not None:
+                w[self.padding_idx[t]].zero_()      # torch: a padding row starts as zeros
 
     def _tables(self) -> _TableSet:
         if self._ts is None or self._ts.ptrs[0] != self.table(0).data_ptr():
             self._ts = _TableSet([self.table(t) for t in range(len(self.rows))], self.layout, self.block_bags)
         return self._ts
+
+    def _pad_dev(self) -> Optional[torch.Tensor]:
+        """the per-table padding indices as the kernels take them (device int64 ``[T]``, -1 = none), or None"""
+        if self.padding_idx is None:
+            return None
+        dev = self.weights.device
+        if self._pad_t is None or self._pad_t.device != dev:
+            self._pad_t = _pad_tensor(self.padding_idx, dev)
+        return self._pad_t
 
     def _batch_of(self, offsets, indices=None) -> int:
         # TBE convention first: offsets has T*B+1 entries (split_table_batched_embeddings_ops.py:
@@ -903,10 +1087,14 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
                batch: Optional[int] = None, split_bags: bool = False):
         """Forward without autograd glue; ``bag_begin/bag_count`` select a batch slice.  ``split_bags=True`` selects the
         one-workgroup-per-bag kernel for few, long bags (deterministic, fp32-rounding-close to the default, not bit-equal)."""
+        if split_bags and self.padding_idx is not None:
+            raise ValueError("lookup(split_bags=True) does not take padding_idx")
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
         B = self._batch_of(offsets, indices) if batch is None else batch
         if self.bounds_check_mode != "none":
             self._sanitize(self._tables(), indices, offsets, B, self.bounds_check_mode, per_sample_weights, bag_begin, bag_count)
+        if self.padding_idx is not None:
+            return _fwd(self._tables(), indices, offsets, B, per_sample_weights, out, bag_begin, bag_count, pad=self._pad_dev())
         return _fwd(self._tables(), indices, offsets, B, per_sample_weights, out, bag_begin, bag_count, split_bags)
 
     def sanitize_(self, indices, offsets, batch: Optional[int] = None, mode=None) -> None:
@@ -926,6 +1114,8 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         all-to-all (the reference's ``--bitwidth``), written by the lookup kernel itself.  ``param_amd.quant.
         dequantize_rows`` restores fp32; the bytes equal ``quantize_rows(lookup(...))``.  Whole-batch requests the staged
         kernel does not take (ragged bags) run as lookup + quantiser; a batch SLICE of such a request raises (PM_ERR_UNSUPPORTED)."""
+        if self.padding_idx is not None:
+            raise ValueError("lookup_quantized does not take padding_idx")
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
         B = self._batch_of(offsets, indices) if batch is None else batch
         return _fwd_quantized(self._tables(), indices, offsets, B, bitwidth, per_sample_weights, out, bag_begin, bag_count)
@@ -952,7 +1142,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         ts = self._tables()
         B = self._batch(offsets, indices, batch)
         _bwd(ts, grad, indices, offsets, B, ts.d_ptrs, self.weights.dtype, alpha, per_sample_weights,
-             bag_begin, bag_count, method, presorted, pooling)
+             bag_begin, bag_count, method, presorted, pooling, pad=self._pad_dev())
 
     def sort_status(self, indices, offsets, per_sample_weights=None, batch: Optional[int] = None, bag_begin=0, bag_count=None) -> dict:
         """status of the last key sort on this module's workspace (synchronises)"""
@@ -993,7 +1183,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         self._sr_step += 1          # a fresh stochastic-rounding stream every step, reproducible run to run
         _adagrad(self._tables(), grad, indices, offsets, B, self._mom_ptrs, self.learning_rate, self.eps,
                  per_sample_weights, presorted, self.weight_decay, self.weight_decay_mode, self.stochastic_rounding,
-                 seed=0x5EED0000 + self._sr_step, pooling=pooling, elementwise=self.optimizer == "adagrad")
+                 seed=0x5EED0000 + self._sr_step, pooling=pooling, elementwise=self.optimizer == "adagrad", pad=self._pad_dev())
 
     def optimizer_step_(self, grad, indices, offsets, per_sample_weights=None, batch: Optional[int] = None,
                         presorted: bool = False):
@@ -1005,13 +1195,21 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
                               batch=batch, presorted=presorted)
 
     def dense_grad(self, grad, indices, offsets, per_sample_weights=None, batch: Optional[int] = None,
-                   method: str = "sorted"):
-        """fp32 dense gradients (list, one per table) -- small tables / parity tests only."""
+                   method: str = "sorted", out: Optional[Sequence[torch.Tensor]] = None):
+        """fp32 dense gradients (list, one per table) -- small tables / parity tests only.  ``out``: one contiguous fp32
+        ``[rows_t, dims_t]`` buffer per table to ADD the gradient to (default: fresh zeros); a padding row of such a buffer is
+        exactly what it was before the call."""
         ts = self._tables()
         B = self._batch(offsets, indices, batch)
-        outs = [torch.zeros(r, d, dtype=torch.float32, device=ts.device) for r, d in zip(self.rows, self.dims)]
+        if out is None:
+            outs = [torch.zeros(r, d, dtype=torch.float32, device=ts.device) for r, d in zip(self.rows, self.dims)]
+        else:
+            outs = list(out)
+            if len(outs) != len(self.rows) or any(o.dtype != torch.float32 or tuple(o.shape) != (r, d) or not o.is_contiguous() or
+                                                  o.device != ts.device for o, r, d in zip(outs, self.rows, self.dims)):
+                raise ValueError("out must hold one contiguous float32 [rows_t, dims_t] tensor per table on the module's device")
         d_ptrs = torch.tensor([o.data_ptr() for o in outs], dtype=torch.int64, device=ts.device)
-        _bwd(ts, grad, indices, offsets, B, d_ptrs, torch.float32, 1.0, per_sample_weights, method=method)
+        _bwd(ts, grad, indices, offsets, B, d_ptrs, torch.float32, 1.0, per_sample_weights, method=method, pad=self._pad_dev())
         return outs
 
     def sparse_grad(self, grad, indices, offsets, per_sample_weights=None, batch: Optional[int] = None, bag_begin=0,
@@ -1025,7 +1223,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         requests, which are split into independent calls.  The gradient with respect to ``per_sample_weights`` is a call of its
         own: ``per_sample_weights_grad``."""
         B = self._batch(offsets, indices, batch)
-        return _sparse_grad(self._tables(), grad, indices, offsets, B, per_sample_weights, bag_begin, bag_count)
+        return _sparse_grad(self._tables(), grad, indices, offsets, B, per_sample_weights, bag_begin, bag_count, pads=self.padding_idx)
 
     def per_sample_weights_grad(self, grad, indices, offsets, batch: Optional[int] = None, out=None, bag_begin=0, bag_count=None):
         """Gradient of ``per_sample_weights``: fp32 ``[N]``, ``out[j] = sum_c grad[t, bag(j)][c] * table_t[indices[j], c]`` -- what
@@ -1037,7 +1235,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         of tables (no sort, no workspace).  Call it BEFORE an in-place update of the tables."""
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
         B = self._batch(offsets, indices, batch)
-        return _psw_grad(self._tables(), grad, indices, offsets, B, None, out, bag_begin, bag_count)
+        return _psw_grad(self._tables(), grad, indices, offsets, B, None, out, bag_begin, bag_count, pad=self._pad_dev())
 
     def check(self, indices, offsets, per_sample_weights=None, batch: Optional[int] = None) -> None:
         B = self._batch(offsets, indices, batch)
