@@ -431,6 +431,35 @@ int pm_pad_rows_guard(int32_t num_tables, int32_t max_dim, void* const* tables, 
                       int32_t direction, pm_stream_t stream);
 
 /*
+ * MEAN POOLING -- torch's nn.EmbeddingBag(mode="mean") rule (fbgemm TBE: PoolingMode.MEAN, unweighted).  count(t, b) = the lookups of
+ * bag (t, b) whose index is not table t's padding index.  padding_idx is the device array of PADDING above, or NULL when no table has a
+ * padding row.  The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs the two calls finds out
+ * at symbol resolution.  tests/mean_rules.py restates the rule in numpy.
+ *
+ * pm_embbag_fwd_mean     out(t, b)[:] = sum(t, b)[:] / (float)count(t, b) for count >= 1: sum is exactly what pm_embbag_fwd_padded gives
+ *                        (additions in index order from +0.0, fp32; 16-bit rows widened first), followed by ONE correctly rounded IEEE
+ *                        fp32 division per element -- not a multiplication by a reciprocal.  An empty bag or a bag of padding only
+ *                        gives +0.0 with no division.  The padded forward's kernel with the division fused in front of its stores
+ *                        (csrc/embbag_fwd_pad.hip): same tiling, layouts, dtypes, bag slices and refusals as pm_embbag_fwd_padded.
+ *                        Mean is unweighted: per_sample_weights != NULL is PM_ERR_UNSUPPORTED.
+ * pm_embbag_mean_grad    scaled(t, b)[:] = grad(t, b)[:] * r with r = 1.0f / (float)count(t, b): r is rounded to fp32 first, then one fp32
+ *                        multiplication per element -- not a division of the gradient.  count == 0: +0.0 everywhere.  grad and scaled
+ *                        are addressed like out (out_offsets[t] + b * out_stride); only the bags inside [bag_begin, bag_begin +
+ *                        bag_count) are written; scaled may be grad itself.  Any number of tables.  The mean backward IS the sum
+ *                        backward on `scaled`: pass it as the gradient of any of pm_embbag_bwd_sorted* / pm_embbag_bwd_fused* /
+ *                        pm_embbag_sparse_grad (once, in front of the table ranges of a request of more than 1024 tables), with
+ *                        pm_pad_rows_guard around it as before.  One launch: a lane group per bag, 16 bytes per lane.
+ * Both refuse, before any HIP call: what pm_embbag_fwd refuses; blocked layouts (grad_block_shift != 0 or table_group != 0:
+ * PM_ERR_UNSUPPORTED); a NULL out / grad / scaled or a grad / scaled that is not 16-byte aligned (PM_ERR_INVALID).  bag_count == 0 is
+ * PM_OK without a launch.
+ * Replaces the mode="mean" branches of aten::_embedding_bag and _embedding_bag_dense_backward / _embedding_bag_sparse_backward (the
+ * kernels behind nn.EmbeddingBag at train/compute/pt/pytorch_emb.py:179) and PoolingMode.MEAN of fbgemm's TBE forward and backward
+ * (split_table_batched_embeddings_ops.py:290), for unweighted requests.
+ */
+int pm_embbag_fwd_mean(const pm_embbag_batch* op, const int64_t* padding_idx, float* out, pm_stream_t stream);
+int pm_embbag_mean_grad(const pm_embbag_batch* op, const int64_t* padding_idx, const float* grad, float* scaled, pm_stream_t stream);
+
+/*
  * DLRM input redistribution on the device: regroup what the lengths / indices all-to-alls deliver
  * (train/comms/pt/dlrm.py:744-855) -- lengths [world][num_tables][batch] int64 and the indices
  * concatenated block by block in that (rank, table) order -- into the TBE request of the batched

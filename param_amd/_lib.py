@@ -76,6 +76,8 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_pad_mask",
     "pm_pad_rows_guard_bytes",
     "pm_pad_rows_guard",
+    "pm_embbag_fwd_mean",
+    "pm_embbag_mean_grad",
 )
 
 
@@ -257,6 +259,11 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_pad_rows_guard_bytes.argtypes = [i32, i32, i32, i32]
     L.pm_pad_rows_guard.restype = ctypes.c_int
     L.pm_pad_rows_guard.argtypes = [i32, i32, vp, vp, i32, vp, vp, i32, vp, i64, i32, vp]
+    # mean pooling: the pad array may be NULL (no table has a padding row)
+    L.pm_embbag_fwd_mean.restype = ctypes.c_int
+    L.pm_embbag_fwd_mean.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp]
+    L.pm_embbag_mean_grad.restype = ctypes.c_int
+    L.pm_embbag_mean_grad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp, vp]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]

@@ -695,6 +695,44 @@ int pm_embbag_pad_mask(const pm_embbag_batch* op, const int64_t* padding_idx, fl
     return PM_OK;
 }
 
+// ---- mean pooling (embbag_fwd_pad.hip with MEAN = true, mean_pool.hip) --------------------------------------------------
+// what both calls refuse on the host, behind make_params: blocked layouts (the padded family's tiling and the scaling kernel address
+// bag b at out_offsets[t] + b * out_stride)
+static int mean_args_ok(const pm_embbag_batch* op) {
+    if (op->grad_block_shift != 0 || op->table_group != 0)
+        return fail(PM_ERR_UNSUPPORTED, "mean pooling does not take blocked layouts (grad_block_shift / table_group must be 0)");
+    return PM_OK;
+}
+
+int pm_embbag_fwd_mean(const pm_embbag_batch* op, const int64_t* padding_idx, float* out, pm_stream_t stream) {
+    pm::KParams p;
+    int rc = make_params(op, op ? op->weight_dtype : -1, p);
+    if (rc != PM_OK) return rc;
+    if ((rc = mean_args_ok(op)) != PM_OK) return rc;
+    if (op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "mean pooling is unweighted: per_sample_weights must be NULL");
+    if (p.bag_count == 0) return PM_OK;
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    plan_padded_forward(op, op->weight_dtype, p);
+    p.io = out;
+    const hipError_t h = pm::launch_embbag_fwd_mean(p, op->weight_dtype, op->max_dim, padding_idx, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_fwd_mean launch");
+    return PM_OK;
+}
+
+int pm_embbag_mean_grad(const pm_embbag_batch* op, const int64_t* padding_idx, const float* grad, float* scaled, pm_stream_t stream) {
+    pm::KParams p;
+    int rc = make_params(op, op ? op->weight_dtype : -1, p);
+    if (rc != PM_OK) return rc;
+    if ((rc = mean_args_ok(op)) != PM_OK) return rc;
+    if (p.bag_count == 0) return PM_OK;
+    if (!grad || !scaled) return fail(PM_ERR_INVALID, "grad / scaled is NULL");
+    if (reinterpret_cast<uintptr_t>(grad) % 16 != 0 || reinterpret_cast<uintptr_t>(scaled) % 16 != 0)
+        return fail(PM_ERR_INVALID, "grad and scaled must be 16-byte aligned");
+    const hipError_t h = pm::launch_mean_grad(p, op->max_dim, padding_idx, grad, scaled, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_mean_grad launch");
+    return PM_OK;
+}
+
 static int pad_guard_layout(int32_t num_tables, int32_t max_dim, int32_t table_dtype, int32_t state_kind, int64_t& row_slot, int64_t& slot) {
     if (num_tables < 1) return fail(PM_ERR_INVALID, "num_tables must be >= 1");
     if (!dtype_is_weight(table_dtype)) return fail(PM_ERR_INVALID, "weight/dst dtype must be PM_F32, PM_BF16 or PM_F16");

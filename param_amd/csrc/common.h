@@ -190,6 +190,9 @@ hipError_t launch_pad_guard(int T, void* const* tables, const int32_t* dims, int
                             float* const* state, int state_kind, void* stash, int64_t slot_bytes, int64_t row_slot_bytes,
                             bool restore, hipStream_t stream);
 hipError_t launch_pad_mask(const KParams& p, const int64_t* pad_idx, float* values, hipStream_t stream);
+// mean pooling (embbag_fwd_pad.hip with MEAN = true, mean_pool.hip): pad_idx may be NULL (no table has a padding row)
+hipError_t launch_embbag_fwd_mean(const KParams& p, int weight_dtype, int max_dim, const int64_t* pad_idx, hipStream_t stream);
+hipError_t launch_mean_grad(const KParams& p, int max_dim, const int64_t* pad_idx, const float* grad, float* scaled, hipStream_t stream);
 
 // sort-based deterministic backward (embbag_bwd_sorted.hip)
 hipError_t sorted_workspace_bytes(const KParams& p, int64_t max_rows, int max_dim, size_t& bytes);

@@ -18,6 +18,13 @@
 // gives +0.0, like an empty bag.
 // Kept small on purpose: two row loads in flight (the product default), bags taken in tile order, lane groups sized for
 // max_dim (a narrow table of a mixed request wastes lanes).  3 dtypes x 4 group widths x weighted / not = 24 instantiations.
+//
+// MEAN pooling (pm_embbag_fwd_mean) is the same kernel with MEAN = true: the pooled sum -- the very
+// additions above -- is divided by (float)count before it leaves the registers, count = the bag's kept lookups: e - s of a
+// staged tile (the bounds are compacted positions), counted along the walk of an unstaged one.  ONE correctly rounded fp32
+// division per element (the compiler's default: no reciprocal, no fast-math); count == 0 skips it, the bag stays +0.0.  A NULL
+// pad array is "no table has a padding row" (pad = -1).  Mean is unweighted: 3 dtypes x 4 group widths = 12 more instantiations;
+// every MEAN line sits under `if constexpr`, so the 24 above keep their code.
 #include <type_traits>
 
 #include "common.h"
@@ -39,7 +46,7 @@ __host__ __device__ inline size_t pad_out_offset(int bags_per_block, int idx_cap
     return (pad_pre_offset(bags_per_block, idx_cap, weighted) + static_cast<size_t>(idx_cap) * 2 + 15) / 16 * 16;
 }
 
-template <typename WT, int G, bool WEIGHTED>
+template <typename WT, int G, bool WEIGHTED, bool MEAN = false>
 __global__ void __launch_bounds__(kBlock) pad_fwd_kernel(const KParams p, const int64_t* __restrict__ pad_idx) {
     constexpr int VEC = Elem<WT>::kVec;
     constexpr int NG = kBlock / G;
@@ -54,7 +61,9 @@ __global__ void __launch_bounds__(kBlock) pad_fwd_kernel(const KParams p, const 
     const int64_t left_bags = p.bag_begin + p.bag_count - bag0;
     if (left_bags <= 0) return;
     const int nb = left_bags < p.bags_per_block ? static_cast<int>(left_bags) : p.bags_per_block;
-    const int64_t pad = pad_idx[t];            // -1: the table has no padding row (no index equals it)
+    int64_t pad;                               // -1: the table has no padding row (no index equals it)
+    if constexpr (MEAN) pad = pad_idx ? pad_idx[t] : -1;
+    else pad = pad_idx[t];
 
     int64_t* s_off = reinterpret_cast<int64_t*>(smem);
     int32_t* s_idx = reinterpret_cast<int32_t*>(smem + (static_cast<size_t>(p.bags_per_block + 2) / 2 * 2) * sizeof(int64_t));
@@ -139,6 +148,7 @@ __global__ void __launch_bounds__(kBlock) pad_fwd_kernel(const KParams p, const 
             float acc[VEC];
 #pragma unroll
             for (int k = 0; k < VEC; ++k) acc[k] = 0.0f;
+            int64_t kept = 0;                  // MEAN: the bag's kept lookups (staged: e - s, set below)
             auto add = [&](const u32x4& raw, float w) {
                 float f[VEC];
                 Elem<WT>::widen(raw, f);
@@ -183,7 +193,16 @@ __global__ void __launch_bounds__(kBlock) pad_fwd_kernel(const KParams p, const 
 #pragma unroll
                     for (int u = 0; u < kPadUnroll; ++u) {
                         if (keep[u]) add(raw[u], w[u]);
+                        if constexpr (MEAN) kept += keep[u] ? 1 : 0;
                     }
+                }
+            }
+            if constexpr (MEAN) {
+                if (staged) kept = e - s;
+                if (kept > 0) {                // an empty or all-padding bag stays +0.0: no division
+                    const float n = static_cast<float>(kept);
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) acc[k] = acc[k] / n;
                 }
             }
             if (burst) {
@@ -227,6 +246,31 @@ hipError_t launch_pad_w(const KParams& p0, const int64_t* pad_idx, hipStream_t s
     return hipGetLastError();
 }
 
+// mean pooling: unweighted, pad_idx may be NULL
+template <typename WT, int G>
+hipError_t launch_mean_w(const KParams& p0, const int64_t* pad_idx, hipStream_t stream) {
+    KParams p = p0;
+    p.psw = nullptr;
+    const size_t tile_lds = pad_out_offset(p.bags_per_block, p.idx_cap, false);
+    size_t lds = tile_lds + (p.stage_out > 0 ? static_cast<size_t>(p.bags_per_block) * p.stage_out * sizeof(float) : 0);
+    if (lds > 65536) {
+        p.stage_out = 0;
+        lds = tile_lds;
+    }
+    hipLaunchKernelGGL((pad_fwd_kernel<WT, G, false, true>), dim3(p.T * p.tiles_per_table), dim3(kBlock), lds, stream, p, pad_idx);
+    return hipGetLastError();
+}
+
+template <typename WT>
+hipError_t launch_mean_g(const KParams& p, int max_dim, const int64_t* pad_idx, hipStream_t stream) {
+    switch (group_lanes(max_dim, Elem<WT>::kVec)) {
+        case 8: return launch_mean_w<WT, 8>(p, pad_idx, stream);
+        case 16: return launch_mean_w<WT, 16>(p, pad_idx, stream);
+        case 32: return launch_mean_w<WT, 32>(p, pad_idx, stream);
+        default: return launch_mean_w<WT, 64>(p, pad_idx, stream);
+    }
+}
+
 template <typename WT>
 hipError_t launch_pad_g(const KParams& p, int max_dim, const int64_t* pad_idx, hipStream_t stream) {
     switch (group_lanes(max_dim, Elem<WT>::kVec)) {
@@ -245,6 +289,15 @@ hipError_t launch_embbag_fwd_padded(const KParams& p, int weight_dtype, int max_
         case PM_F32: return launch_pad_g<float>(p, max_dim, pad_idx, stream);
         case PM_BF16: return launch_pad_g<bf16_t>(p, max_dim, pad_idx, stream);
         default: return launch_pad_g<f16_t>(p, max_dim, pad_idx, stream);
+    }
+}
+
+// the same tiling; pad_idx NULL = no table has a padding row
+hipError_t launch_embbag_fwd_mean(const KParams& p, int weight_dtype, int max_dim, const int64_t* pad_idx, hipStream_t stream) {
+    switch (weight_dtype) {
+        case PM_F32: return launch_mean_g<float>(p, max_dim, pad_idx, stream);
+        case PM_BF16: return launch_mean_g<bf16_t>(p, max_dim, pad_idx, stream);
+        default: return launch_mean_g<f16_t>(p, max_dim, pad_idx, stream);
     }
 }
 

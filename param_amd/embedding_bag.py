@@ -286,12 +286,15 @@ class _TableSet:
 
 
 def _fwd(ts: _TableSet, indices, offsets, B, psw=None, out=None, bag_begin=0, bag_count=None, split_bags: bool = False,
-         pad: Optional[torch.Tensor] = None):
+         pad: Optional[torch.Tensor] = None, mean: bool = False):
     """``split_bags``: one workgroup per bag with wave-shuffle / LDS partial reductions (``pm_embbag_fwd_split``) -- for
     few, long bags; agrees with the default kernel to fp32 rounding, not bit for bit.  ``pad``: per-table padding indices
-    (device int64 ``[T]``, -1 = none): the padded forward (``pm_embbag_fwd_padded``); ``None``: the call is what it always was."""
+    (device int64 ``[T]``, -1 = none): the padded forward (``pm_embbag_fwd_padded``); ``None``: the call is what it always was.
+    ``mean``: mean pooling (``pm_embbag_fwd_mean``: the padded forward's kernel with the division fused; ``pad`` may be ``None``)."""
     if pad is not None and (split_bags or ts.layout == "blocked"):
         raise ValueError('padding_idx is not supported with split_bags=True or layout="blocked"')
+    if mean and (split_bags or ts.layout == "blocked" or psw is not None):
+        raise ValueError('mean pooling is not supported with split_bags=True, layout="blocked" or per_sample_weights')
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count, forward=True)
     _, _, shape = ts.out_desc(B)
     if out is None:
@@ -299,7 +302,9 @@ def _fwd(ts: _TableSet, indices, offsets, B, psw=None, out=None, bag_begin=0, ba
     elif out.dtype != torch.float32 or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
         raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
     L = _lib.load()
-    if pad is not None:
+    if mean:
+        rc = L.pm_embbag_fwd_mean(ctypes.byref(op), None if pad is None else pad.data_ptr(), out.data_ptr(), _stream_ptr())
+    elif pad is not None:
         rc = L.pm_embbag_fwd_padded(ctypes.byref(op), pad.data_ptr(), out.data_ptr(), _stream_ptr())
     else:
         rc = (L.pm_embbag_fwd_split if split_bags else L.pm_embbag_fwd)(ctypes.byref(op), out.data_ptr(), _stream_ptr())
@@ -358,6 +363,26 @@ def _check_grad(ts: _TableSet, grad, B) -> torch.Tensor:
     if grad.dtype != torch.float32 or tuple(grad.shape) != tuple(shape):
         raise ValueError(f"grad must be float32 of shape {shape}")
     return grad.contiguous()
+
+
+_MEAN_WEIGHTED = "mean pooling is unweighted: per_sample_weights must be None (fbgemm's weighted mean is not implemented)"
+
+
+def _mean_scale(ts: _TableSet, grad, indices, offsets, B, pad: Optional[torch.Tensor] = None, bag_begin=0, bag_count=None) -> torch.Tensor:
+    """The gradient of a MEAN-pooled forward as the gradient of its sum (``pm_embbag_mean_grad``): a scratch of ``grad``'s shape from
+    torch's allocator holding ``grad(t, b) * (1.0f / count(t, b))`` for the bags of the slice (+0.0 for a bag without kept lookups;
+    bags outside the slice are not written -- no backward reads them).  ``grad`` itself is never modified.  One launch for any
+    number of tables; every backward route then runs unchanged on the result."""
+    if ts.layout == "blocked":
+        raise ValueError('mean pooling is not supported with layout="blocked"')
+    grad = _check_grad(ts, grad, B)
+    op = ts.request(indices, offsets, B, None, bag_begin, bag_count)
+    scaled = torch.empty_like(grad)
+    rc = _lib.load().pm_embbag_mean_grad(ctypes.byref(op), None if pad is None else pad.data_ptr(), grad.data_ptr(), scaled.data_ptr(),
+                                         _stream_ptr())
+    if rc:
+        _lib.check(rc)
+    return scaled
 
 
 def _sort_indices(ts: _TableSet, indices, offsets, B, psw=None, bag_begin=0, bag_count=None, phases: int = 2,
@@ -469,11 +494,16 @@ def _no_presorted_split(ts, presorted: bool) -> None:
 
 def _bwd(ts: _TableSet, grad, indices, offsets, B, dst_ptrs_dev, dst_dtype, alpha, psw=None,
          bag_begin=0, bag_count=None, method: str = "sorted", presorted: bool = False, pooling: Optional[int] = None,
-         pad: Optional[torch.Tensor] = None):
+         pad: Optional[torch.Tensor] = None, mean: bool = False):
     """``method="sorted"`` (default): deterministic, bit-identical to a sequential scatter-add;
     ``method="atomic"``: hardware float atomics (order not fixed; tests / tools: the alternates build).
     ``pad``: per-table padding indices (device int64 ``[T]``): those rows of the destinations are saved before and restored
-    after the call (``_PadGuard``) -- once, around all table ranges of a large request."""
+    after the call (``_PadGuard``) -- once, around all table ranges of a large request.
+    ``mean``: ``grad`` is the gradient of a mean-pooled forward: scaled once (``_mean_scale``), then everything below as it is."""
+    if mean:
+        if psw is not None:
+            raise ValueError(_MEAN_WEIGHTED)
+        grad = _mean_scale(ts, grad, indices, offsets, B, pad, bag_begin, bag_count)
     if pad is not None:
         guard = _PadGuard(ts, pad, dst_ptrs_dev, dst_dtype)
         guard.save()
@@ -555,6 +585,28 @@ def bounds_check_mode_name(mode) -> str:
     if key not in _BOUNDS_MODES:
         raise ValueError(f"bounds_check_mode must be one of fatal / warning / ignore / none (any case, fbgemm's BoundsCheckMode "
                          f"members or their ints 0 .. 3), got {mode!r}")
+    return key
+
+
+_FBGEMM_POOLING_INTS = {0: "sum", 1: "mean", 2: "none"}      # fbgemm_gpu's PoolingMode values
+
+
+def pooling_mode_name(mode) -> str:
+    """``"sum" | "mean"`` from what a caller of fbgemm's TBE module passes as ``pooling_mode``: one of those names in any case, a
+    ``PoolingMode`` member (read by its name) or its int (SUM 0, MEAN 1).  ``NONE`` / 2 (no pooling: one output row per lookup) and
+    anything else raise ValueError.  Needs no device."""
+    name = getattr(mode, "name", None)
+    if isinstance(name, str):
+        key = name.lower()
+    elif isinstance(mode, str):
+        key = mode.lower()
+    elif isinstance(mode, int) and not isinstance(mode, bool):
+        key = _FBGEMM_POOLING_INTS.get(mode)
+    else:
+        key = None
+    if key not in ("sum", "mean"):
+        raise ValueError(f"pooling_mode must be sum or mean (any case, fbgemm's PoolingMode.SUM / MEAN or their ints 0 / 1; "
+                         f"PoolingMode.NONE is not implemented), got {mode!r}")
     return key
 
 
@@ -643,11 +695,17 @@ _WD_MODES = {None: _lib.PM_WD_NONE, "none": _lib.PM_WD_NONE, 0: _lib.PM_WD_NONE,
 
 def _adagrad(ts: _TableSet, grad, indices, offsets, B, mom_ptrs_dev, lr: float, eps: float, psw=None,
              presorted: bool = False, weight_decay: float = 0.0, weight_decay_mode=None, stochastic_rounding: bool = False,
-             seed: int = 0, pooling: Optional[int] = None, elementwise: bool = False, pad: Optional[torch.Tensor] = None):
+             seed: int = 0, pooling: Optional[int] = None, elementwise: bool = False, pad: Optional[torch.Tensor] = None,
+             mean: bool = False):
     """Fused backward + exact row-wise Adagrad on the tables of ``ts`` (``pm_embbag_bwd_sorted_adagrad_ex``), or, with
     ``elementwise``, exact element-wise Adagrad (``pm_embbag_bwd_sorted_adagrad_elem``: ``mom_ptrs_dev`` then points at one
     fp32 ``[rows_t, dims_t]`` state buffer per table).  ``pad``: per-table padding indices (device int64 ``[T]``): those rows
-    and their state are saved before and restored after the step (``_PadGuard``)."""
+    and their state are saved before and restored after the step (``_PadGuard``).  ``mean``: ``grad`` is the gradient of a
+    mean-pooled forward: scaled once (``_mean_scale``), then everything below as it is."""
+    if mean:
+        if psw is not None:
+            raise ValueError(_MEAN_WEIGHTED)
+        grad = _mean_scale(ts, grad, indices, offsets, B, pad)
     if pad is not None:
         guard = _PadGuard(ts, pad, ts.d_ptrs, ts.dtype, mom_ptrs_dev, _lib.PM_PAD_STATE_ELEM if elementwise else _lib.PM_PAD_STATE_ROW)
         guard.save()
@@ -717,10 +775,16 @@ def _drop_padding_rows(rows, vals, pads):
     return rows, vals
 
 
-def _sparse_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, bag_begin=0, bag_count=None, pads=None):
+def _sparse_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, bag_begin=0, bag_count=None, pads=None,
+                 mean: bool = False, pad: Optional[torch.Tensor] = None):
     """Coalesced sparse gradient (``pm_embbag_sparse_grad*``): a list of T ``(rows_t, values_t)`` -- rows_t the distinct rows table t's
     lookups hit (ascending int64), values_t ``[U_t, D_t]`` fp32, ``values_t[k] = sum_{j: idx_j = rows_t[k]} w_j * grad[t, bag(j)]`` in
-    the sorted backward's order.  Synchronises once per request of at most 1024 tables (to size the outputs)."""
+    the sorted backward's order.  Synchronises once per request of at most 1024 tables (to size the outputs).  ``mean``: ``grad`` is
+    the gradient of a mean-pooled forward: scaled once (``_mean_scale``; ``pad`` = the device form of ``pads``)."""
+    if mean:
+        if psw is not None:
+            raise ValueError(_MEAN_WEIGHTED)
+        grad = _mean_scale(ts, grad, indices, offsets, B, pad, bag_begin, bag_count)
     grad = _check_grad(ts, grad, B)
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
     op.fixed_pooling = 0
@@ -764,6 +828,8 @@ class _DenseGradFn(torch.autograd.Function):
         ctx.module, ctx.B = module, B
         ctx.save_for_backward(indices, offsets, psw if psw is not None else torch.empty(0))
         ctx.has_psw = psw is not None
+        if module.mode == "mean":
+            return _fwd(ts, indices, offsets, B, None, pad=module._pad_dev(), mean=True)
         return _fwd(ts, indices, offsets, B, psw, pad=module._pad_dev())
 
     @staticmethod
@@ -775,6 +841,9 @@ class _DenseGradFn(torch.autograd.Function):
         d_ptr = torch.tensor([dW.data_ptr()], dtype=torch.int64, device=grad_out.device)
         grad_out = grad_out.contiguous()
         pad = m._pad_dev()
+        if m.mode == "mean":      # (grad_out is left as it is: the scaled copy is a scratch of _bwd's)
+            _bwd(ts, grad_out, indices, offsets, ctx.B, d_ptr, torch.float32, 1.0, None, pad=pad, mean=True)
+            return dW.to(m.weight.dtype), None, None, None, None
         _bwd(ts, grad_out, indices, offsets, ctx.B, d_ptr, torch.float32, 1.0,
              psw if ctx.has_psw else None, pad=pad)
         d_psw = _psw_grad(ts, grad_out, indices, offsets, ctx.B, psw, pad=pad) if ctx.has_psw and ctx.needs_input_grad[4] else None
@@ -791,8 +860,12 @@ class _SparseGradFn(_DenseGradFn):
         m = ctx.module
         w = m.weight
         grad_out = grad_out.contiguous()
-        ((rows, vals),) = _sparse_grad(m._tables(), grad_out, indices, offsets, ctx.B, psw if ctx.has_psw else None,
-                                       pads=None if m.padding_idx is None else [m.padding_idx])
+        if m.mode == "mean":
+            ((rows, vals),) = _sparse_grad(m._tables(), grad_out, indices, offsets, ctx.B, None,
+                                           pads=None if m.padding_idx is None else [m.padding_idx], mean=True, pad=m._pad_dev())
+        else:
+            ((rows, vals),) = _sparse_grad(m._tables(), grad_out, indices, offsets, ctx.B, psw if ctx.has_psw else None,
+                                           pads=None if m.padding_idx is None else [m.padding_idx])
         d_psw = (_psw_grad(m._tables(), grad_out, indices, offsets, ctx.B, psw, pad=m._pad_dev())
                  if ctx.has_psw and ctx.needs_input_grad[4] else None)
         g = torch.sparse_coo_tensor(rows[None], vals.to(w.dtype), tuple(w.shape), is_coalesced=True)
@@ -803,7 +876,7 @@ class _SparseGradFn(_DenseGradFn):
 
 
 class EmbeddingBagMI355(nn.Module, _BoundsChecked):
-    """``torch.nn.EmbeddingBag(num_embeddings, embedding_dim, mode="sum")`` on MI355X HIP kernels.
+    """``torch.nn.EmbeddingBag(num_embeddings, embedding_dim, mode="sum" | "mean")`` on MI355X HIP kernels.
 
     Same call contract as the module the reference builds at pytorch_emb.py:179 and
     pytorch_dist_backend.py:924: ``forward(indices[N], offsets[B]) -> float32[B, D]``,
@@ -819,14 +892,21 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
     adds no launch.  The sanitiser runs first: a bad index it repairs to 0 is padding when ``padding_idx == 0``.
     2-D input: ``forward(input[B, L])`` (``offsets`` must be ``None``) treats every row as one bag of L lookups, as torch does;
     ``per_sample_weights`` then has the input's shape, and so has its gradient.
+    ``mode="mean"``: ``out = sum / (float)count``, ``count`` = the bag's lookups that are not ``padding_idx`` (after the sanitiser's
+    repairs): the sum forward's additions, then one correctly rounded fp32 division per element; an empty or all-padding bag gives
+    +0.0.  Every lookup receives ``grad * (1.0f / (float)count)`` -- the reciprocal rounded to fp32 first, then one multiplication --
+    summed as the sum backward sums, dense and ``sparse=True``.  On fp32 tables that is torch's CPU module bit for bit (forward always;
+    gradients where no row is looked up twice, otherwise up to the order of the additions).  16-bit tables keep this package's
+    convention (rows widened, fp32 sums and output); torch's own 16-bit module rounds the sum to 16 bits before it divides.
+    ``per_sample_weights`` with ``mode="mean"`` raises ``NotImplementedError``, as torch does; ``mode="max"`` is not implemented.
     """
 
     def __init__(self, num_embeddings: int, embedding_dim: int, mode: str = "sum", sparse: bool = False,
                  dtype: torch.dtype = torch.float32, device=None, _weight: Optional[torch.Tensor] = None,
                  bounds_check_mode="none", padding_idx: Optional[int] = None):
         super().__init__()
-        if mode != "sum":
-            raise NotImplementedError('only mode="sum" is on the reference hot path (pytorch_emb.py:179)')
+        if mode not in ("sum", "mean"):
+            raise NotImplementedError('only mode="sum" (the reference hot path, pytorch_emb.py:179) and mode="mean" are implemented')
         self._init_bounds(bounds_check_mode)      # (validated before anything is allocated)
         self.padding_idx = _normalize_padding_idx(padding_idx, num_embeddings if _weight is None else int(_weight.shape[0]))
         self._pad_t: Optional[torch.Tensor] = None
@@ -897,6 +977,9 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
             indices, offsets, per_sample_weights = self._bags_2d(indices, offsets, per_sample_weights)
         elif offsets is None:
             raise ValueError("offsets has to be a 1D Tensor but got None")
+        if per_sample_weights is not None and self.mode != "sum":
+            raise NotImplementedError("embedding_bag: per_sample_weights was not None. per_sample_weights is only supported for "
+                                      f"mode='sum' (got mode='{self.mode}'). Please open a feature request on GitHub.")
         w = self._parameters["weight"]
         if not w.is_cuda:
             _require_device(w, "EmbeddingBagMI355.weight")
@@ -907,6 +990,8 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
         ts = self._ts
         if ts is None or ts.ptrs[0] != w.data_ptr():
             ts = self._tables()
+        if self.mode == "mean":
+            return _fwd(ts, indices, offsets, offsets.numel(), None, pad=self._pad_dev(), mean=True)
         if self.padding_idx is not None:
             return _fwd(ts, indices, offsets, offsets.numel(), per_sample_weights, pad=self._pad_dev())
         return _fwd(ts, indices, offsets, offsets.numel(), per_sample_weights)
@@ -919,7 +1004,7 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
         self._sanitize(self._tables(), indices, offsets, offsets.numel(), "warning" if mode == "none" else mode)
 
     def extra_repr(self) -> str:
-        return (f"{self.num_embeddings}, {self.embedding_dim}, mode=sum, dtype={self.weight.dtype}" + (", sparse=True" if self.sparse else "") +
+        return (f"{self.num_embeddings}, {self.embedding_dim}, mode={self.mode}, dtype={self.weight.dtype}" + (", sparse=True" if self.sparse else "") +
                 (f", padding_idx={self.padding_idx}" if self.padding_idx is not None else ""))
 
 
@@ -968,15 +1053,29 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     ``per_sample_weights_grad`` gives +0.0 there.  ``reset_parameters`` zero-fills the padding rows.  ``lookup_quantized``,
     ``lookup(split_bags=True)`` and ``layout="blocked"`` do not take padding (ValueError).  The sanitiser runs first: a bad index
     it repairs to 0 is padding in a table whose ``padding_idx`` is 0.
+
+    ``pooling_mode`` (default ``"sum"``; fbgemm TBE's argument of that name): ``"sum"`` / ``"mean"`` in any case, a ``PoolingMode``
+    member or its int (0 / 1); ``NONE`` / 2 raises ValueError.  With ``"mean"``, ``forward`` / ``lookup`` (``out=`` and batch slices
+    included) give ``sum / (float)count`` -- ``count`` = the bag's lookups that are not its table's padding index, after the
+    sanitiser's repairs; the sum forward's additions, then one correctly rounded fp32 division; +0.0 for a bag without kept lookups
+    -- and ``scatter_add_``, ``adagrad_step_``, ``optimizer_step_``, ``dense_grad``, ``sparse_grad`` and the fused ``backward`` take
+    ``grad`` as the gradient of THAT forward: every lookup receives ``grad * (1.0f / (float)count)`` (one more launch and a scratch
+    of ``grad``'s shape; ``grad`` is not modified), then each is exactly what it is for a sum module.  A stated difference to
+    fbgemm, which allows weighted mean: ``per_sample_weights`` with ``"mean"`` raises ValueError, and so do
+    ``per_sample_weights_grad``, ``lookup(split_bags=True)``, ``lookup_quantized`` and ``layout="blocked"``.  ``"sum"`` adds no launch.
     """
 
     def __init__(self, rows: Sequence[int], dims, dtype: torch.dtype = torch.float32, device="cuda",
                  layout: str = "bd", init: Optional[str] = "uniform_dlrm", seed: int = 0,
                  learning_rate: float = 0.01, fused_update: bool = True, optimizer: str = "sgd", eps: float = 1.0e-8,
                  weight_decay: float = 0.0, weight_decay_mode=None, stochastic_rounding: bool = False,
-                 block_bags: Optional[int] = None, bounds_check_mode="none", padding_idx=None):
+                 block_bags: Optional[int] = None, bounds_check_mode="none", padding_idx=None, pooling_mode="sum"):
         super().__init__()
         self._init_bounds(bounds_check_mode)      # (validated, like the optimizer below, before anything is allocated)
+        self.pooling_mode = pooling_mode_name(pooling_mode)
+        self._mean = self.pooling_mode == "mean"
+        if self._mean and layout == "blocked":
+            raise ValueError('pooling_mode="mean" is not supported with layout="blocked"')
         rows = [int(r) for r in rows]
         dims = [int(dims)] * len(rows) if isinstance(dims, int) else [int(d) for d in dims]
         assert len(rows) == len(dims) and len(rows) >= 1
@@ -1089,10 +1188,14 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         one-workgroup-per-bag kernel for few, long bags (deterministic, fp32-rounding-close to the default, not bit-equal)."""
         if split_bags and self.padding_idx is not None:
             raise ValueError("lookup(split_bags=True) does not take padding_idx")
+        if self._mean and (split_bags or per_sample_weights is not None):
+            raise ValueError('pooling_mode="mean" does not take split_bags=True' if split_bags else _MEAN_WEIGHTED)
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
         B = self._batch_of(offsets, indices) if batch is None else batch
         if self.bounds_check_mode != "none":
             self._sanitize(self._tables(), indices, offsets, B, self.bounds_check_mode, per_sample_weights, bag_begin, bag_count)
+        if self._mean:
+            return _fwd(self._tables(), indices, offsets, B, None, out, bag_begin, bag_count, pad=self._pad_dev(), mean=True)
         if self.padding_idx is not None:
             return _fwd(self._tables(), indices, offsets, B, per_sample_weights, out, bag_begin, bag_count, pad=self._pad_dev())
         return _fwd(self._tables(), indices, offsets, B, per_sample_weights, out, bag_begin, bag_count, split_bags)
@@ -1116,6 +1219,8 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         kernel does not take (ragged bags) run as lookup + quantiser; a batch SLICE of such a request raises (PM_ERR_UNSUPPORTED)."""
         if self.padding_idx is not None:
             raise ValueError("lookup_quantized does not take padding_idx")
+        if self._mean:
+            raise ValueError('lookup_quantized does not take pooling_mode="mean"')
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
         B = self._batch_of(offsets, indices) if batch is None else batch
         return _fwd_quantized(self._tables(), indices, offsets, B, bitwidth, per_sample_weights, out, bag_begin, bag_count)
@@ -1141,6 +1246,10 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         caller's word that every bag has exactly that many lookups (saves the one-off device check of a new request)."""
         ts = self._tables()
         B = self._batch(offsets, indices, batch)
+        if self._mean:
+            _bwd(ts, grad, indices, offsets, B, ts.d_ptrs, self.weights.dtype, alpha, per_sample_weights,
+                 bag_begin, bag_count, method, presorted, pooling, pad=self._pad_dev(), mean=True)
+            return
         _bwd(ts, grad, indices, offsets, B, ts.d_ptrs, self.weights.dtype, alpha, per_sample_weights,
              bag_begin, bag_count, method, presorted, pooling, pad=self._pad_dev())
 
@@ -1183,7 +1292,8 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         self._sr_step += 1          # a fresh stochastic-rounding stream every step, reproducible run to run
         _adagrad(self._tables(), grad, indices, offsets, B, self._mom_ptrs, self.learning_rate, self.eps,
                  per_sample_weights, presorted, self.weight_decay, self.weight_decay_mode, self.stochastic_rounding,
-                 seed=0x5EED0000 + self._sr_step, pooling=pooling, elementwise=self.optimizer == "adagrad", pad=self._pad_dev())
+                 seed=0x5EED0000 + self._sr_step, pooling=pooling, elementwise=self.optimizer == "adagrad", pad=self._pad_dev(),
+                 mean=self._mean)
 
     def optimizer_step_(self, grad, indices, offsets, per_sample_weights=None, batch: Optional[int] = None,
                         presorted: bool = False):
@@ -1209,7 +1319,8 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
                                                   o.device != ts.device for o, r, d in zip(outs, self.rows, self.dims)):
                 raise ValueError("out must hold one contiguous float32 [rows_t, dims_t] tensor per table on the module's device")
         d_ptrs = torch.tensor([o.data_ptr() for o in outs], dtype=torch.int64, device=ts.device)
-        _bwd(ts, grad, indices, offsets, B, d_ptrs, torch.float32, 1.0, per_sample_weights, method=method, pad=self._pad_dev())
+        _bwd(ts, grad, indices, offsets, B, d_ptrs, torch.float32, 1.0, per_sample_weights, method=method, pad=self._pad_dev(),
+             mean=self._mean)
         return outs
 
     def sparse_grad(self, grad, indices, offsets, per_sample_weights=None, batch: Optional[int] = None, bag_begin=0,
@@ -1223,6 +1334,9 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         requests, which are split into independent calls.  The gradient with respect to ``per_sample_weights`` is a call of its
         own: ``per_sample_weights_grad``."""
         B = self._batch(offsets, indices, batch)
+        if self._mean:
+            return _sparse_grad(self._tables(), grad, indices, offsets, B, per_sample_weights, bag_begin, bag_count,
+                                pads=self.padding_idx, mean=True, pad=self._pad_dev())
         return _sparse_grad(self._tables(), grad, indices, offsets, B, per_sample_weights, bag_begin, bag_count, pads=self.padding_idx)
 
     def per_sample_weights_grad(self, grad, indices, offsets, batch: Optional[int] = None, out=None, bag_begin=0, bag_count=None):
@@ -1233,6 +1347,8 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         ``grad`` has the shape ``scatter_add_`` takes for the module's layout.  ``bag_begin/bag_count`` select a batch slice:
         entries of lookups outside it are zero in a tensor the method allocates and untouched in a caller's ``out``.  Any number
         of tables (no sort, no workspace).  Call it BEFORE an in-place update of the tables."""
+        if self._mean:
+            raise ValueError('per_sample_weights_grad: pooling_mode="mean" is unweighted')
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
         B = self._batch(offsets, indices, batch)
         return _psw_grad(self._tables(), grad, indices, offsets, B, None, out, bag_begin, bag_count, pad=self._pad_dev())
