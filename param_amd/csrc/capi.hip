@@ -669,18 +669,24 @@ static void plan_padded_forward(const pm_embbag_batch* op, int elem_dtype, pm::K
     p.ordered = 0;
 }
 
+// what pm_embbag_fwd_padded and pm_embbag_fwd_mean do behind their own argument rules (`launch`, `label`: the entry point's own)
+static int padded_forward(const pm_embbag_batch* op, pm::KParams& p, const int64_t* padding_idx, float* out, pm_stream_t stream,
+                          decltype(&pm::launch_embbag_fwd_padded) launch, const char* label) {
+    if (p.bag_count == 0) return PM_OK;
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    plan_padded_forward(op, op->weight_dtype, p);
+    p.io = out;
+    const hipError_t h = launch(p, op->weight_dtype, op->max_dim, padding_idx, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, label);
+    return PM_OK;
+}
+
 int pm_embbag_fwd_padded(const pm_embbag_batch* op, const int64_t* padding_idx, float* out, pm_stream_t stream) {
     pm::KParams p;
     int rc = make_params(op, op ? op->weight_dtype : -1, p);
     if (rc != PM_OK) return rc;
     if (!padding_idx) return fail(PM_ERR_INVALID, "padding_idx is NULL (device int64 [num_tables], -1 = no padding row: pm_embbag_fwd takes requests without one)");
-    if (p.bag_count == 0) return PM_OK;
-    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
-    plan_padded_forward(op, op->weight_dtype, p);
-    p.io = out;
-    const hipError_t h = pm::launch_embbag_fwd_padded(p, op->weight_dtype, op->max_dim, padding_idx, static_cast<hipStream_t>(stream));
-    if (h != hipSuccess) return hip_fail(h, "pm_embbag_fwd_padded launch");
-    return PM_OK;
+    return padded_forward(op, p, padding_idx, out, stream, pm::launch_embbag_fwd_padded, "pm_embbag_fwd_padded launch");
 }
 
 int pm_embbag_pad_mask(const pm_embbag_batch* op, const int64_t* padding_idx, float* values, pm_stream_t stream) {
@@ -710,13 +716,7 @@ int pm_embbag_fwd_mean(const pm_embbag_batch* op, const int64_t* padding_idx, fl
     if (rc != PM_OK) return rc;
     if ((rc = mean_args_ok(op)) != PM_OK) return rc;
     if (op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "mean pooling is unweighted: per_sample_weights must be NULL");
-    if (p.bag_count == 0) return PM_OK;
-    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
-    plan_padded_forward(op, op->weight_dtype, p);
-    p.io = out;
-    const hipError_t h = pm::launch_embbag_fwd_mean(p, op->weight_dtype, op->max_dim, padding_idx, static_cast<hipStream_t>(stream));
-    if (h != hipSuccess) return hip_fail(h, "pm_embbag_fwd_mean launch");
-    return PM_OK;
+    return padded_forward(op, p, padding_idx, out, stream, pm::launch_embbag_fwd_mean, "pm_embbag_fwd_mean launch");
 }
 
 int pm_embbag_mean_grad(const pm_embbag_batch* op, const int64_t* padding_idx, const float* grad, float* scaled, pm_stream_t stream) {

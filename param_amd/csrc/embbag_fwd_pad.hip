@@ -230,9 +230,11 @@ __global__ void __launch_bounds__(kBlock) pad_fwd_kernel(const KParams p, const 
     }
 }
 
-template <typename WT, int G>
+// the launcher ladder, once for both poolings: MEAN is unweighted (psw is dropped) and takes a NULL pad_idx
+template <typename WT, int G, bool MEAN>
 hipError_t launch_pad_w(const KParams& p0, const int64_t* pad_idx, hipStream_t stream) {
     KParams p = p0;
+    if (MEAN) p.psw = nullptr;
     const bool weighted = p.psw != nullptr;
     const int grid = p.T * p.tiles_per_table;
     const size_t tile_lds = pad_out_offset(p.bags_per_block, p.idx_cap, weighted);
@@ -241,43 +243,28 @@ hipError_t launch_pad_w(const KParams& p0, const int64_t* pad_idx, hipStream_t s
         p.stage_out = 0;
         lds = tile_lds;
     }
-    if (weighted) hipLaunchKernelGGL((pad_fwd_kernel<WT, G, true>), dim3(grid), dim3(kBlock), lds, stream, p, pad_idx);
+    if constexpr (MEAN) hipLaunchKernelGGL((pad_fwd_kernel<WT, G, false, true>), dim3(grid), dim3(kBlock), lds, stream, p, pad_idx);
+    else if (weighted) hipLaunchKernelGGL((pad_fwd_kernel<WT, G, true>), dim3(grid), dim3(kBlock), lds, stream, p, pad_idx);
     else hipLaunchKernelGGL((pad_fwd_kernel<WT, G, false>), dim3(grid), dim3(kBlock), lds, stream, p, pad_idx);
     return hipGetLastError();
 }
 
-// mean pooling: unweighted, pad_idx may be NULL
-template <typename WT, int G>
-hipError_t launch_mean_w(const KParams& p0, const int64_t* pad_idx, hipStream_t stream) {
-    KParams p = p0;
-    p.psw = nullptr;
-    const size_t tile_lds = pad_out_offset(p.bags_per_block, p.idx_cap, false);
-    size_t lds = tile_lds + (p.stage_out > 0 ? static_cast<size_t>(p.bags_per_block) * p.stage_out * sizeof(float) : 0);
-    if (lds > 65536) {
-        p.stage_out = 0;
-        lds = tile_lds;
-    }
-    hipLaunchKernelGGL((pad_fwd_kernel<WT, G, false, true>), dim3(p.T * p.tiles_per_table), dim3(kBlock), lds, stream, p, pad_idx);
-    return hipGetLastError();
-}
-
-template <typename WT>
-hipError_t launch_mean_g(const KParams& p, int max_dim, const int64_t* pad_idx, hipStream_t stream) {
-    switch (group_lanes(max_dim, Elem<WT>::kVec)) {
-        case 8: return launch_mean_w<WT, 8>(p, pad_idx, stream);
-        case 16: return launch_mean_w<WT, 16>(p, pad_idx, stream);
-        case 32: return launch_mean_w<WT, 32>(p, pad_idx, stream);
-        default: return launch_mean_w<WT, 64>(p, pad_idx, stream);
-    }
-}
-
-template <typename WT>
+template <typename WT, bool MEAN>
 hipError_t launch_pad_g(const KParams& p, int max_dim, const int64_t* pad_idx, hipStream_t stream) {
     switch (group_lanes(max_dim, Elem<WT>::kVec)) {
-        case 8: return launch_pad_w<WT, 8>(p, pad_idx, stream);
-        case 16: return launch_pad_w<WT, 16>(p, pad_idx, stream);
-        case 32: return launch_pad_w<WT, 32>(p, pad_idx, stream);
-        default: return launch_pad_w<WT, 64>(p, pad_idx, stream);
+        case 8: return launch_pad_w<WT, 8, MEAN>(p, pad_idx, stream);
+        case 16: return launch_pad_w<WT, 16, MEAN>(p, pad_idx, stream);
+        case 32: return launch_pad_w<WT, 32, MEAN>(p, pad_idx, stream);
+        default: return launch_pad_w<WT, 64, MEAN>(p, pad_idx, stream);
+    }
+}
+
+template <bool MEAN>
+hipError_t launch_pad_t(const KParams& p, int weight_dtype, int max_dim, const int64_t* pad_idx, hipStream_t stream) {
+    switch (weight_dtype) {
+        case PM_F32: return launch_pad_g<float, MEAN>(p, max_dim, pad_idx, stream);
+        case PM_BF16: return launch_pad_g<bf16_t, MEAN>(p, max_dim, pad_idx, stream);
+        default: return launch_pad_g<f16_t, MEAN>(p, max_dim, pad_idx, stream);
     }
 }
 
@@ -285,20 +272,12 @@ hipError_t launch_pad_g(const KParams& p, int max_dim, const int64_t* pad_idx, h
 
 // p: plain bag-count tiling (bags_per_block <= 1024, idx_cap <= 4096); stage_out > 0: bags_per_block * stage_out floats of burst buffer
 hipError_t launch_embbag_fwd_padded(const KParams& p, int weight_dtype, int max_dim, const int64_t* pad_idx, hipStream_t stream) {
-    switch (weight_dtype) {
-        case PM_F32: return launch_pad_g<float>(p, max_dim, pad_idx, stream);
-        case PM_BF16: return launch_pad_g<bf16_t>(p, max_dim, pad_idx, stream);
-        default: return launch_pad_g<f16_t>(p, max_dim, pad_idx, stream);
-    }
+    return launch_pad_t<false>(p, weight_dtype, max_dim, pad_idx, stream);
 }
 
 // the same tiling; pad_idx NULL = no table has a padding row
 hipError_t launch_embbag_fwd_mean(const KParams& p, int weight_dtype, int max_dim, const int64_t* pad_idx, hipStream_t stream) {
-    switch (weight_dtype) {
-        case PM_F32: return launch_mean_g<float>(p, max_dim, pad_idx, stream);
-        case PM_BF16: return launch_mean_g<bf16_t>(p, max_dim, pad_idx, stream);
-        default: return launch_mean_g<f16_t>(p, max_dim, pad_idx, stream);
-    }
+    return launch_pad_t<true>(p, weight_dtype, max_dim, pad_idx, stream);
 }
 
 }  // namespace pm

@@ -89,16 +89,9 @@ class _PadGuard:
         self.pad = pad
         if pad is None:
             return
-        L = _lib.load()
         self.args = (ts.T, ts.max_dim, tables_dev.data_ptr(), ts.d_dims.data_ptr(), _WDTYPE[dtype], pad.data_ptr(),
                      None if state_dev is None else state_dev.data_ptr(), state_kind)
-        need = L.pm_pad_rows_guard_bytes(ts.T, ts.max_dim, _WDTYPE[dtype], state_kind)
-        if need < 0:
-            _lib.check(int(need))
-        stash = getattr(ts, "_pad_stash", None)
-        if stash is None or stash.numel() < need:
-            stash = ts._pad_stash = torch.empty(int(need), dtype=torch.uint8, device=ts.device)
-        self.stash = stash
+        self.stash = ts.scratch("_pad_stash", _lib.load().pm_pad_rows_guard_bytes(ts.T, ts.max_dim, _WDTYPE[dtype], state_kind))
 
     def _call(self, direction: int) -> None:
         if self.pad is not None:
@@ -160,6 +153,18 @@ class _TableSet:
         self._tbd_cache: dict[int, torch.Tensor] = {}
         self._req: dict = {}         # one cached descriptor per kind of request (forward of a blocked layout / everything else)
         self._pool_key, self._pool_val = None, 0
+
+    def scratch(self, slot: str, need: int, dtype: torch.dtype = torch.uint8) -> torch.Tensor:
+        """The scratch tensor kept as attribute ``slot`` of this table set (``_ws``: the sorted backward's workspace, ``_pad_stash``,
+        ``_bounds_scratch``), of at least ``need`` bytes in whole elements of ``dtype``: grown, never shrunk.  ``need`` is what a size
+        query of the library returned: a negative value is its error code and raises."""
+        if need < 0:
+            _lib.check(int(need))
+        t = self.__dict__.get(slot)
+        if t is None or t.nbytes < need:
+            t = torch.empty((int(need) + dtype.itemsize - 1) // dtype.itemsize, dtype=dtype, device=self.device)
+            setattr(self, slot, t)
+        return t
 
     def out_desc(self, B: int):
         """(out_offsets device tensor, out_stride, output shape) for a batch of B bags."""
@@ -346,14 +351,8 @@ def _workspace(ts: _TableSet, op, max_rows: Optional[int] = None, query=None) ->
     """Scratch for the sort-based backward, cached on the table set (grown, never shrunk).  ``max_rows``: of the tables ``op``
     names, when it is a table range of the set's request.  ``query``: the size function (default
     ``pm_embbag_bwd_sorted_workspace``; the sparse gradient has its own)."""
-    need = (query or _lib.load().pm_embbag_bwd_sorted_workspace)(ctypes.byref(op), max(ts.rows) if max_rows is None else max_rows)
-    if need < 0:
-        _lib.check(int(need))
-    ws = getattr(ts, "_ws", None)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(int(need), dtype=torch.uint8, device=ts.device)
-        ts._ws = ws
-    return ws
+    query = query or _lib.load().pm_embbag_bwd_sorted_workspace
+    return ts.scratch("_ws", query(ctypes.byref(op), max(ts.rows) if max_rows is None else max_rows))
 
 
 def _check_grad(ts: _TableSet, grad, B) -> torch.Tensor:
@@ -383,6 +382,16 @@ def _mean_scale(ts: _TableSet, grad, indices, offsets, B, pad: Optional[torch.Te
     if rc:
         _lib.check(rc)
     return scaled
+
+
+def _grad_as_sum(ts: _TableSet, grad, indices, offsets, B, psw, pad, mean: bool, bag_begin=0, bag_count=None) -> torch.Tensor:
+    """The gradient of the module's forward as the gradient of a SUM forward of the same request, which is what every backward
+    route below takes: ``grad`` itself for sum pooling, its scaled copy (``_mean_scale``) for mean pooling -- which is unweighted."""
+    if not mean:
+        return grad
+    if psw is not None:
+        raise ValueError(_MEAN_WEIGHTED)
+    return _mean_scale(ts, grad, indices, offsets, B, pad, bag_begin, bag_count)
 
 
 def _sort_indices(ts: _TableSet, indices, offsets, B, psw=None, bag_begin=0, bag_count=None, phases: int = 2,
@@ -498,39 +507,33 @@ def _bwd(ts: _TableSet, grad, indices, offsets, B, dst_ptrs_dev, dst_dtype, alph
     """``method="sorted"`` (default): deterministic, bit-identical to a sequential scatter-add;
     ``method="atomic"``: hardware float atomics (order not fixed; tests / tools: the alternates build).
     ``pad``: per-table padding indices (device int64 ``[T]``): those rows of the destinations are saved before and restored
-    after the call (``_PadGuard``) -- once, around all table ranges of a large request.
-    ``mean``: ``grad`` is the gradient of a mean-pooled forward: scaled once (``_mean_scale``), then everything below as it is."""
-    if mean:
-        if psw is not None:
-            raise ValueError(_MEAN_WEIGHTED)
-        grad = _mean_scale(ts, grad, indices, offsets, B, pad, bag_begin, bag_count)
-    if pad is not None:
-        guard = _PadGuard(ts, pad, dst_ptrs_dev, dst_dtype)
-        guard.save()
-        _bwd(ts, grad, indices, offsets, B, dst_ptrs_dev, dst_dtype, alpha, psw, bag_begin, bag_count, method, presorted, pooling)
-        guard.restore()
-        return
-    grad = _check_grad(ts, grad, B)
+    after the call (``_PadGuard``) -- once, around all table ranges of a large request; a call refused on the host launches neither.
+    ``mean``: ``grad`` is the gradient of a mean-pooled forward: scaled once (``_grad_as_sum``), then everything below as it is."""
+    grad = _check_grad(ts, _grad_as_sum(ts, grad, indices, offsets, B, psw, pad, mean, bag_begin, bag_count), B)
+    if method not in ("sorted", "atomic"):
+        raise ValueError('method must be "sorted" or "atomic"')
+    if method == "sorted":
+        _no_presorted_split(ts, presorted)
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
-    L = _lib.load()
+    dst_dt, s, g = _WDTYPE[dst_dtype], _stream_ptr(), grad.data_ptr()
+    guard = _PadGuard(ts, pad, dst_ptrs_dev, dst_dtype)
+    guard.save()
     if method == "atomic":
         # the atomic kernel is a measured baseline and a cross-check (25 x slower): it lives in the ALTERNATES build only
         # (libparam_amd_alt.so, `make -C param_amd/csrc alt`; ImportError if that is not built)
         A = _lib.load_alternates()
-        rc = A.pm_embbag_bwd(ctypes.byref(op), grad.data_ptr(), dst_ptrs_dev.data_ptr(), _WDTYPE[dst_dtype], float(alpha), _stream_ptr())
+        rc = A.pm_embbag_bwd(ctypes.byref(op), g, dst_ptrs_dev.data_ptr(), dst_dt, float(alpha), s)
         if rc != _lib.PM_OK:
             raise _lib.ParamAmdError(rc, A.pm_last_error().decode())
-        return
-    if method != "sorted":
-        raise ValueError('method must be "sorted" or "atomic"')
-    _no_presorted_split(ts, presorted)
-    dst_dt, s, g = _WDTYPE[dst_dtype], _stream_ptr(), grad.data_ptr()
+    else:
+        L = _lib.load()
 
-    def call(fn):      # the fused and the sorted call take the same arguments
-        return lambda sub, t0, max_rows, ws: fn(ctypes.byref(sub), g, dst_ptrs_dev.data_ptr() + 8 * t0, dst_dt, float(alpha), max_rows,
-                                                ws.data_ptr(), ws.numel(), s)
-    # (the alternative key sorts may lay out two bag phases for the scatter-add apply)
-    _sorted_chunks_call(ts, op, indices, offsets, B, psw, presorted, pooling, 2, call(L.pm_embbag_bwd_fused), call(L.pm_embbag_bwd_sorted))
+        def call(fn):      # the fused and the sorted call take the same arguments
+            return lambda sub, t0, max_rows, ws: fn(ctypes.byref(sub), g, dst_ptrs_dev.data_ptr() + 8 * t0, dst_dt, float(alpha), max_rows,
+                                                    ws.data_ptr(), ws.numel(), s)
+        # (the alternative key sorts may lay out two bag phases for the scatter-add apply)
+        _sorted_chunks_call(ts, op, indices, offsets, B, psw, presorted, pooling, 2, call(L.pm_embbag_bwd_fused), call(L.pm_embbag_bwd_sorted))
+    guard.restore()
 
 
 def _sorted_chunks_call(ts: _TableSet, op, indices, offsets, B, psw, presorted: bool, pooling, phases: int, fused, sorted_) -> None:
@@ -567,25 +570,31 @@ _BOUNDS_MODES = {"fatal": _lib.PM_BOUNDS_FATAL, "warning": _lib.PM_BOUNDS_WARNIN
 _FBGEMM_BOUNDS_INTS = {0: "fatal", 1: "warning", 2: "ignore", 3: "none"}      # fbgemm_gpu's BoundsCheckMode values
 
 
-def bounds_check_mode_name(mode) -> str:
-    """``"fatal" | "warning" | "ignore" | "none"`` from what a caller of fbgemm's TBE module passes as ``bounds_check_mode``: one of
-    those names in any case, a ``BoundsCheckMode`` member (read by its name) or its int (FATAL 0, WARNING 1, IGNORE 2, NONE 3);
-    ``None`` is ``"none"``.  Anything else raises ValueError."""
-    if mode is None:
-        return "none"
+def _mode_name(mode, ints: dict, names, what: str) -> str:
+    """an fbgemm-style enum argument as one of ``names``: such a name in any case, an enum member (read by its ``name``) or its int
+    (``ints``: int -> name); anything else raises ValueError(``what``, got ...)"""
     name = getattr(mode, "name", None)
     if isinstance(name, str):
         key = name.lower()
     elif isinstance(mode, str):
         key = mode.lower()
     elif isinstance(mode, int) and not isinstance(mode, bool):
-        key = _FBGEMM_BOUNDS_INTS.get(mode)
+        key = ints.get(mode)
     else:
         key = None
-    if key not in _BOUNDS_MODES:
-        raise ValueError(f"bounds_check_mode must be one of fatal / warning / ignore / none (any case, fbgemm's BoundsCheckMode "
-                         f"members or their ints 0 .. 3), got {mode!r}")
+    if key not in names:
+        raise ValueError(f"{what}, got {mode!r}")
     return key
+
+
+def bounds_check_mode_name(mode) -> str:
+    """``"fatal" | "warning" | "ignore" | "none"`` from what a caller of fbgemm's TBE module passes as ``bounds_check_mode``: one of
+    those names in any case, a ``BoundsCheckMode`` member (read by its name) or its int (FATAL 0, WARNING 1, IGNORE 2, NONE 3);
+    ``None`` is ``"none"``.  Anything else raises ValueError."""
+    if mode is None:
+        return "none"
+    return _mode_name(mode, _FBGEMM_BOUNDS_INTS, _BOUNDS_MODES, "bounds_check_mode must be one of fatal / warning / ignore / none "
+                      "(any case, fbgemm's BoundsCheckMode members or their ints 0 .. 3)")
 
 
 _FBGEMM_POOLING_INTS = {0: "sum", 1: "mean", 2: "none"}      # fbgemm_gpu's PoolingMode values
@@ -595,19 +604,8 @@ def pooling_mode_name(mode) -> str:
     """``"sum" | "mean"`` from what a caller of fbgemm's TBE module passes as ``pooling_mode``: one of those names in any case, a
     ``PoolingMode`` member (read by its name) or its int (SUM 0, MEAN 1).  ``NONE`` / 2 (no pooling: one output row per lookup) and
     anything else raise ValueError.  Needs no device."""
-    name = getattr(mode, "name", None)
-    if isinstance(name, str):
-        key = name.lower()
-    elif isinstance(mode, str):
-        key = mode.lower()
-    elif isinstance(mode, int) and not isinstance(mode, bool):
-        key = _FBGEMM_POOLING_INTS.get(mode)
-    else:
-        key = None
-    if key not in ("sum", "mean"):
-        raise ValueError(f"pooling_mode must be sum or mean (any case, fbgemm's PoolingMode.SUM / MEAN or their ints 0 / 1; "
-                         f"PoolingMode.NONE is not implemented), got {mode!r}")
-    return key
+    return _mode_name(mode, _FBGEMM_POOLING_INTS, ("sum", "mean"), "pooling_mode must be sum or mean (any case, fbgemm's "
+                      "PoolingMode.SUM / MEAN or their ints 0 / 1; PoolingMode.NONE is not implemented)")
 
 
 def _bounds_report_dict(report: torch.Tensor) -> dict:
@@ -623,16 +621,10 @@ def _bounds_check(ts: _TableSet, indices, offsets, B, mode: str, report: Optiona
     """``pm_embbag_bounds_check`` on the whole request (the plain descriptor: T tables, batch B -- also for ``layout="blocked"``),
     stream-ordered, no synchronisation.  ``psw`` / ``bag_begin`` / ``bag_count`` only keep the cached descriptor of the lookup that
     follows; the call reads none of them.  ``report``: int64[4] on the device (``"ignore"``: not used).  Memory the call repairs is
-    written behind torch's back: the table set's verdict about the offsets' contents is dropped."""
+    written behind torch's back: the caller drops what it remembers about the request's contents (``_contents_changed``)."""
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
     L = _lib.load()
-    need = L.pm_embbag_bounds_check_scratch(ctypes.byref(op))
-    if need < 0:
-        _lib.check(int(need))
-    scratch = getattr(ts, "_bounds_scratch", None)
-    if scratch is None or scratch.numel() * 8 < need:
-        scratch = torch.empty((int(need) + 7) // 8, dtype=torch.int64, device=ts.device)
-        ts._bounds_scratch = scratch
+    scratch = ts.scratch("_bounds_scratch", L.pm_embbag_bounds_check_scratch(ctypes.byref(op)), torch.int64)
     flags = _BOUNDS_MODES[mode] | (_lib.PM_BOUNDS_LAST_OFFSET if offsets.numel() == ts.T * B + 1 else 0)
     if report is not None and ts.T * B == 0:
         report.copy_(torch.tensor([0, 0, _lib.PM_BOUNDS_NONE, _lib.PM_BOUNDS_NONE], dtype=torch.int64))     # nothing is launched for no bags
@@ -640,12 +632,12 @@ def _bounds_check(ts: _TableSet, indices, offsets, B, mode: str, report: Optiona
                                   scratch.data_ptr(), scratch.numel() * 8, _stream_ptr())
     if rc:
         _lib.check(rc)
-    if mode != "fatal":
-        ts._pool_key = None
 
 
 class _BoundsChecked:
-    """``bounds_check_mode`` of the two modules (fbgemm TBE's constructor argument): with a mode other than ``"none"`` every
+    """What the two modules share: ``bounds_check_mode``, described below, and the plumbing of ``padding_idx`` (``_pad_dev``).
+
+    ``bounds_check_mode`` of the two modules (fbgemm TBE's constructor argument): with a mode other than ``"none"`` every
     ``forward`` / ``lookup`` first runs the device-side sanitiser (``pm_embbag_bounds_check``; rule in include/param_amd.h) on the
     caller's ``indices`` / ``offsets``, so that the lookup and -- through the tensors autograd saved -- the backward see the repaired
     request.  The other standalone entry points (``scatter_add_``, ``adagrad_step_``, ``dense_grad``, ``sparse_grad``,
@@ -658,10 +650,30 @@ class _BoundsChecked:
       untouched and no lookup kernel is issued.
     """
 
-    def _init_bounds(self, bounds_check_mode) -> None:
+    _TABLES = "weight"      # the nn.Parameter that holds the tables: where they live is where the pad array goes
+
+    def _init_shared(self, bounds_check_mode) -> None:
         self.bounds_check_mode = bounds_check_mode_name(bounds_check_mode)
         self._bounds_report: Optional[torch.Tensor] = None
         self._bounds_reported = False
+        self._seen: dict = {}      # what the module remembers about the CONTENTS of request tensors (dropped by _contents_changed)
+        self._pad_t: Optional[torch.Tensor] = None
+
+    def _pad_dev(self) -> Optional[torch.Tensor]:
+        """``padding_idx`` as the kernels take it (device int64 ``[T]``, -1 = the table has none), or None"""
+        pads = self.padding_idx
+        if pads is None:
+            return None
+        dev = self._parameters[self._TABLES].device
+        if self._pad_t is None or self._pad_t.device != dev:
+            self._pad_t = _pad_tensor(pads if isinstance(pads, list) else [pads], dev)
+        return self._pad_t
+
+    def _contents_changed(self, ts: _TableSet) -> None:
+        """the request's bytes were rewritten behind torch's back (no version counter moved): every memo about them goes -- the
+        table set's fixed-pooling verdict and whatever the module keeps in ``_seen``"""
+        ts._pool_key = None
+        self._seen.clear()
 
     def _sanitize(self, ts: _TableSet, indices, offsets, B, mode: str, psw=None, bag_begin=0, bag_count=None) -> None:
         rep = None
@@ -672,7 +684,7 @@ class _BoundsChecked:
         _bounds_check(ts, indices, offsets, B, mode, rep, psw, bag_begin, bag_count)
         self._bounds_reported = rep is not None
         if mode != "fatal":
-            self._b1_key = None              # (BatchedEmbeddingBagMI355: the T == 1 memo of what offsets[-1] said)
+            self._contents_changed(ts)
             return
         r = _bounds_report_dict(rep)
         if r["bad_indices"] or r["bad_offsets"]:
@@ -700,19 +712,9 @@ def _adagrad(ts: _TableSet, grad, indices, offsets, B, mom_ptrs_dev, lr: float, 
     """Fused backward + exact row-wise Adagrad on the tables of ``ts`` (``pm_embbag_bwd_sorted_adagrad_ex``), or, with
     ``elementwise``, exact element-wise Adagrad (``pm_embbag_bwd_sorted_adagrad_elem``: ``mom_ptrs_dev`` then points at one
     fp32 ``[rows_t, dims_t]`` state buffer per table).  ``pad``: per-table padding indices (device int64 ``[T]``): those rows
-    and their state are saved before and restored after the step (``_PadGuard``).  ``mean``: ``grad`` is the gradient of a
-    mean-pooled forward: scaled once (``_mean_scale``), then everything below as it is."""
-    if mean:
-        if psw is not None:
-            raise ValueError(_MEAN_WEIGHTED)
-        grad = _mean_scale(ts, grad, indices, offsets, B, pad)
-    if pad is not None:
-        guard = _PadGuard(ts, pad, ts.d_ptrs, ts.dtype, mom_ptrs_dev, _lib.PM_PAD_STATE_ELEM if elementwise else _lib.PM_PAD_STATE_ROW)
-        guard.save()
-        _adagrad(ts, grad, indices, offsets, B, mom_ptrs_dev, lr, eps, psw, presorted, weight_decay, weight_decay_mode,
-                 stochastic_rounding, seed, pooling, elementwise)
-        guard.restore()
-        return
+    and their state are saved before and restored after the step (``_PadGuard``); a step refused on the host launches neither.
+    ``mean``: ``grad`` is the gradient of a mean-pooled forward: scaled once (``_grad_as_sum``), then everything below as it is."""
+    grad = _grad_as_sum(ts, grad, indices, offsets, B, psw, pad, mean)
     if weight_decay_mode not in _WD_MODES:
         raise ValueError(f"weight_decay_mode must be one of none / l2 / decouple, got {weight_decay_mode!r}")
     grad = _check_grad(ts, grad, B)
@@ -732,7 +734,10 @@ def _adagrad(ts: _TableSet, grad, indices, offsets, B, mom_ptrs_dev, lr: float, 
             return fn(ctypes.byref(sub), grad.data_ptr(), ts.d_ptrs.data_ptr() + 8 * t0, wdt, mom_ptrs_dev.data_ptr() + 8 * t0,
                       ctypes.byref(opt), max_rows, ws.data_ptr(), ws.numel(), s)
         return issue
+    guard = _PadGuard(ts, pad, ts.d_ptrs, ts.dtype, mom_ptrs_dev, _lib.PM_PAD_STATE_ELEM if elementwise else _lib.PM_PAD_STATE_ROW)
+    guard.save()
     _sorted_chunks_call(ts, op, indices, offsets, B, psw, presorted, pooling, 1, call(fused_call), call(sorted_call))
+    guard.restore()
 
 
 def _sparse_grad_call(ts: _TableSet, op, grad, max_rows: int, dims: Sequence[int], pads=None):
@@ -780,12 +785,8 @@ def _sparse_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, bag_begin=0
     """Coalesced sparse gradient (``pm_embbag_sparse_grad*``): a list of T ``(rows_t, values_t)`` -- rows_t the distinct rows table t's
     lookups hit (ascending int64), values_t ``[U_t, D_t]`` fp32, ``values_t[k] = sum_{j: idx_j = rows_t[k]} w_j * grad[t, bag(j)]`` in
     the sorted backward's order.  Synchronises once per request of at most 1024 tables (to size the outputs).  ``mean``: ``grad`` is
-    the gradient of a mean-pooled forward: scaled once (``_mean_scale``; ``pad`` = the device form of ``pads``)."""
-    if mean:
-        if psw is not None:
-            raise ValueError(_MEAN_WEIGHTED)
-        grad = _mean_scale(ts, grad, indices, offsets, B, pad, bag_begin, bag_count)
-    grad = _check_grad(ts, grad, B)
+    the gradient of a mean-pooled forward: scaled once (``_grad_as_sum``; ``pad`` = the device form of ``pads``)."""
+    grad = _check_grad(ts, _grad_as_sum(ts, grad, indices, offsets, B, psw, pad, mean, bag_begin, bag_count), B)
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
     op.fixed_pooling = 0
     # more tables than one sorted call takes: independent requests of at most 1024 tables (_table_chunks)
@@ -828,9 +829,7 @@ class _DenseGradFn(torch.autograd.Function):
         ctx.module, ctx.B = module, B
         ctx.save_for_backward(indices, offsets, psw if psw is not None else torch.empty(0))
         ctx.has_psw = psw is not None
-        if module.mode == "mean":
-            return _fwd(ts, indices, offsets, B, None, pad=module._pad_dev(), mean=True)
-        return _fwd(ts, indices, offsets, B, psw, pad=module._pad_dev())
+        return _fwd(ts, indices, offsets, B, psw, pad=module._pad_dev(), mean=module.mode == "mean")
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -841,11 +840,8 @@ class _DenseGradFn(torch.autograd.Function):
         d_ptr = torch.tensor([dW.data_ptr()], dtype=torch.int64, device=grad_out.device)
         grad_out = grad_out.contiguous()
         pad = m._pad_dev()
-        if m.mode == "mean":      # (grad_out is left as it is: the scaled copy is a scratch of _bwd's)
-            _bwd(ts, grad_out, indices, offsets, ctx.B, d_ptr, torch.float32, 1.0, None, pad=pad, mean=True)
-            return dW.to(m.weight.dtype), None, None, None, None
-        _bwd(ts, grad_out, indices, offsets, ctx.B, d_ptr, torch.float32, 1.0,
-             psw if ctx.has_psw else None, pad=pad)
+        # (mean: grad_out is left as it is -- the scaled copy is a scratch of _bwd's)
+        _bwd(ts, grad_out, indices, offsets, ctx.B, d_ptr, torch.float32, 1.0, psw if ctx.has_psw else None, pad=pad, mean=m.mode == "mean")
         d_psw = _psw_grad(ts, grad_out, indices, offsets, ctx.B, psw, pad=pad) if ctx.has_psw and ctx.needs_input_grad[4] else None
         return dW.to(m.weight.dtype), None, None, None, d_psw
 
@@ -860,12 +856,8 @@ class _SparseGradFn(_DenseGradFn):
         m = ctx.module
         w = m.weight
         grad_out = grad_out.contiguous()
-        if m.mode == "mean":
-            ((rows, vals),) = _sparse_grad(m._tables(), grad_out, indices, offsets, ctx.B, None,
-                                           pads=None if m.padding_idx is None else [m.padding_idx], mean=True, pad=m._pad_dev())
-        else:
-            ((rows, vals),) = _sparse_grad(m._tables(), grad_out, indices, offsets, ctx.B, psw if ctx.has_psw else None,
-                                           pads=None if m.padding_idx is None else [m.padding_idx])
+        ((rows, vals),) = _sparse_grad(m._tables(), grad_out, indices, offsets, ctx.B, psw if ctx.has_psw else None,
+                                       pads=None if m.padding_idx is None else [m.padding_idx], mean=m.mode == "mean", pad=m._pad_dev())
         d_psw = (_psw_grad(m._tables(), grad_out, indices, offsets, ctx.B, psw, pad=m._pad_dev())
                  if ctx.has_psw and ctx.needs_input_grad[4] else None)
         g = torch.sparse_coo_tensor(rows[None], vals.to(w.dtype), tuple(w.shape), is_coalesced=True)
@@ -907,9 +899,8 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
         super().__init__()
         if mode not in ("sum", "mean"):
             raise NotImplementedError('only mode="sum" (the reference hot path, pytorch_emb.py:179) and mode="mean" are implemented')
-        self._init_bounds(bounds_check_mode)      # (validated before anything is allocated)
+        self._init_shared(bounds_check_mode)      # (validated before anything is allocated)
         self.padding_idx = _normalize_padding_idx(padding_idx, num_embeddings if _weight is None else int(_weight.shape[0]))
-        self._pad_t: Optional[torch.Tensor] = None
         self._off2d: dict = {}
         self.num_embeddings, self.embedding_dim, self.mode, self.sparse = num_embeddings, embedding_dim, mode, sparse
         if _weight is None:
@@ -939,15 +930,6 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
         if self._ts is None or self._ts.ptrs[0] != w.data_ptr():
             self._ts = _TableSet([w], "bd")
         return self._ts
-
-    def _pad_dev(self) -> Optional[torch.Tensor]:
-        """the padding index as the kernels take it (device int64 ``[1]``), or None"""
-        if self.padding_idx is None:
-            return None
-        dev = self._parameters["weight"].device
-        if self._pad_t is None or self._pad_t.device != dev:
-            self._pad_t = _pad_tensor([self.padding_idx], dev)
-        return self._pad_t
 
     def _bags_2d(self, input, offsets, per_sample_weights):
         """a ``[B, L]`` input as the 1-D request of B bags of L lookups: ``offsets = arange(B) * L`` is built on the device once
@@ -990,11 +972,7 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
         ts = self._ts
         if ts is None or ts.ptrs[0] != w.data_ptr():
             ts = self._tables()
-        if self.mode == "mean":
-            return _fwd(ts, indices, offsets, offsets.numel(), None, pad=self._pad_dev(), mean=True)
-        if self.padding_idx is not None:
-            return _fwd(ts, indices, offsets, offsets.numel(), per_sample_weights, pad=self._pad_dev())
-        return _fwd(ts, indices, offsets, offsets.numel(), per_sample_weights)
+        return _fwd(ts, indices, offsets, offsets.numel(), per_sample_weights, pad=self._pad_dev(), mean=self.mode == "mean")
 
     def sanitize_(self, indices, offsets, mode=None) -> None:
         """The sanitiser on its own (``offsets`` is ``[B]``, as ``forward`` takes it): in place, stream-ordered.  ``mode``: default
@@ -1071,7 +1049,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
                  weight_decay: float = 0.0, weight_decay_mode=None, stochastic_rounding: bool = False,
                  block_bags: Optional[int] = None, bounds_check_mode="none", padding_idx=None, pooling_mode="sum"):
         super().__init__()
-        self._init_bounds(bounds_check_mode)      # (validated, like the optimizer below, before anything is allocated)
+        self._init_shared(bounds_check_mode)      # (validated, like the optimizer below, before anything is allocated)
         self.pooling_mode = pooling_mode_name(pooling_mode)
         self._mean = self.pooling_mode == "mean"
         if self._mean and layout == "blocked":
@@ -1089,7 +1067,6 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         self.padding_idx = pads if any(k is not None for k in pads) else None
         if self.padding_idx is not None and layout == "blocked":
             raise ValueError('padding_idx is not supported with layout="blocked"')
-        self._pad_t: Optional[torch.Tensor] = None
         self.rows, self.dims, self.layout = rows, dims, layout
         self.block_bags = block_bags      # layout="blocked": [B / block_bags, T, block_bags, D] (the per-rank batch of a sharded exchange)
         self.learning_rate, self.fused_update = learning_rate, fused_update
@@ -1149,14 +1126,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             self._ts = _TableSet([self.table(t) for t in range(len(self.rows))], self.layout, self.block_bags)
         return self._ts
 
-    def _pad_dev(self) -> Optional[torch.Tensor]:
-        """the per-table padding indices as the kernels take them (device int64 ``[T]``, -1 = none), or None"""
-        if self.padding_idx is None:
-            return None
-        dev = self.weights.device
-        if self._pad_t is None or self._pad_t.device != dev:
-            self._pad_t = _pad_tensor(self.padding_idx, dev)
-        return self._pad_t
+    _TABLES = "weights"
 
     def _batch_of(self, offsets, indices=None) -> int:
         # TBE convention first: offsets has T*B+1 entries (split_table_batched_embeddings_ops.py:
@@ -1168,10 +1138,10 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             # [B] tensor does not (its last bag would silently be dropped): look once per request (one small D2H read,
             # remembered for the tensors of a benchmark loop); pass batch= to skip the question altogether.
             key = (offsets.data_ptr(), offsets._version, n, None if indices is None else indices.numel())
-            if getattr(self, "_b1_key", None) != key:
+            if self._seen.get("b1_key") != key:
                 closed = indices is not None and int(offsets[-1]) == indices.numel()
-                self._b1_key, self._b1_val = key, (n - 1 if closed else n)
-            return self._b1_val
+                self._seen.update(b1_key=key, b1_val=n - 1 if closed else n)
+            return self._seen["b1_val"]
         if n >= 1 and (n - 1) % T == 0:
             return (n - 1) // T
         if n % T == 0:
@@ -1194,11 +1164,8 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         B = self._batch_of(offsets, indices) if batch is None else batch
         if self.bounds_check_mode != "none":
             self._sanitize(self._tables(), indices, offsets, B, self.bounds_check_mode, per_sample_weights, bag_begin, bag_count)
-        if self._mean:
-            return _fwd(self._tables(), indices, offsets, B, None, out, bag_begin, bag_count, pad=self._pad_dev(), mean=True)
-        if self.padding_idx is not None:
-            return _fwd(self._tables(), indices, offsets, B, per_sample_weights, out, bag_begin, bag_count, pad=self._pad_dev())
-        return _fwd(self._tables(), indices, offsets, B, per_sample_weights, out, bag_begin, bag_count, split_bags)
+        return _fwd(self._tables(), indices, offsets, B, per_sample_weights, out, bag_begin, bag_count, split_bags,
+                    pad=self._pad_dev(), mean=self._mean)
 
     def sanitize_(self, indices, offsets, batch: Optional[int] = None, mode=None) -> None:
         """The sanitiser on its own, in front of any entry point that does not run it (everything but ``forward`` / ``lookup``):
@@ -1246,12 +1213,8 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         caller's word that every bag has exactly that many lookups (saves the one-off device check of a new request)."""
         ts = self._tables()
         B = self._batch(offsets, indices, batch)
-        if self._mean:
-            _bwd(ts, grad, indices, offsets, B, ts.d_ptrs, self.weights.dtype, alpha, per_sample_weights,
-                 bag_begin, bag_count, method, presorted, pooling, pad=self._pad_dev(), mean=True)
-            return
         _bwd(ts, grad, indices, offsets, B, ts.d_ptrs, self.weights.dtype, alpha, per_sample_weights,
-             bag_begin, bag_count, method, presorted, pooling, pad=self._pad_dev())
+             bag_begin, bag_count, method, presorted, pooling, pad=self._pad_dev(), mean=self._mean)
 
     def sort_status(self, indices, offsets, per_sample_weights=None, batch: Optional[int] = None, bag_begin=0, bag_count=None) -> dict:
         """status of the last key sort on this module's workspace (synchronises)"""
@@ -1334,10 +1297,8 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         requests, which are split into independent calls.  The gradient with respect to ``per_sample_weights`` is a call of its
         own: ``per_sample_weights_grad``."""
         B = self._batch(offsets, indices, batch)
-        if self._mean:
-            return _sparse_grad(self._tables(), grad, indices, offsets, B, per_sample_weights, bag_begin, bag_count,
-                                pads=self.padding_idx, mean=True, pad=self._pad_dev())
-        return _sparse_grad(self._tables(), grad, indices, offsets, B, per_sample_weights, bag_begin, bag_count, pads=self.padding_idx)
+        return _sparse_grad(self._tables(), grad, indices, offsets, B, per_sample_weights, bag_begin, bag_count,
+                            pads=self.padding_idx, mean=self._mean, pad=self._pad_dev())
 
     def per_sample_weights_grad(self, grad, indices, offsets, batch: Optional[int] = None, out=None, bag_begin=0, bag_count=None):
         """Gradient of ``per_sample_weights``: fp32 ``[N]``, ``out[j] = sum_c grad[t, bag(j)][c] * table_t[indices[j], c]`` -- what
