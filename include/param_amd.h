@@ -460,6 +460,45 @@ int pm_embbag_fwd_mean(const pm_embbag_batch* op, const int64_t* padding_idx, fl
 int pm_embbag_mean_grad(const pm_embbag_batch* op, const int64_t* padding_idx, const float* grad, float* scaled, pm_stream_t stream);
 
 /*
+ * OUTPUT DTYPE -- a bf16 / fp16 pooled output and 16-bit gradients (fbgemm TBE: output_dtype = SparseType.BF16 | FP16; torch's
+ * nn.EmbeddingBag over a 16-bit table returns 16 bits).  The request struct is unchanged (sizeof 144) and the ABI version stays 8: a
+ * client that needs the two calls finds out at symbol resolution.  tests/out16_rules.py restates the rule in numpy.
+ *
+ * FORWARD   out16 = round16(out32), out32 = exactly what the fp32 forward of the same request gives: the sum (pm_embbag_fwd /
+ *           pm_embbag_fwd_padded), the weighted sum or the mean (pm_embbag_fwd_mean), over fp32, bf16 or fp16 tables -- the same fp32
+ *           additions in index order from +0.0, mean with the same single division.  ONE rounding follows, per element, in registers,
+ *           to nearest even; nothing is rounded before it (no 16-bit partial sums).  fp16 overflow gives +-Inf; fp16 and bf16
+ *           subnormals are produced, not flushed; signed zeros are kept.  A NaN becomes a quiet NaN of the same sign: bf16
+ *           (u >> 16) | 0x40 of the fp32 bits u, fp16 what the hardware conversion gives (the payload is not part of the rule).
+ * BACKWARD  a 16-bit gradient is widened exactly; every backward entry point then does what it does for that fp32 gradient.  With
+ *           mean pooling the 1.0f / (float)count scaling happens in the launch that widens, and the result equals
+ *           pm_embbag_mean_grad on the widened gradient bit for bit.  The caller's gradient is only read.
+ *
+ * pm_embbag_fwd_out16    the padded forward's kernel family (csrc/embbag_fwd_pad_kernel.inc) with a 16-bit output element: out is
+ *                        out_dtype (PM_BF16 | PM_F16) and addressed like the fp32 out, out_offsets[t] + b * out_stride counted in
+ *                        OUTPUT elements (the same numbers as for the fp32 request); only the bags inside [bag_begin, bag_begin +
+ *                        bag_count) are written.  padding_idx: the device array of PADDING, or NULL (no table has a padding row).
+ *                        mean: 0 = sum (weighted where per_sample_weights is given), 1 = mean.  The value is converted before it
+ *                        goes to the LDS burst buffer or to the direct store, and leaves in pieces of 4 outputs (8 bytes: what the
+ *                        alignment rules of a request guarantee).  Refused before any HIP call: what pm_embbag_fwd refuses; out_dtype
+ *                        PM_F32 or unknown (PM_ERR_INVALID: fp32 output is pm_embbag_fwd / pm_embbag_fwd_padded / pm_embbag_fwd_mean);
+ *                        mean not 0 / 1; blocked layouts (PM_ERR_UNSUPPORTED); mean with per_sample_weights (PM_ERR_UNSUPPORTED); a
+ *                        NULL out or one that is not 8-byte aligned (PM_ERR_INVALID).  bag_count == 0 is PM_OK without a launch.
+ * pm_embbag_grad_widen   grad32(t, b)[:] = (float)grad16(t, b)[:] (mean == 0), times r = 1.0f / (float)count(t, b) with +0.0 everywhere
+ *                        for count == 0 (mean == 1: pm_embbag_mean_grad's arithmetic).  grad16 (grad_dtype PM_BF16 | PM_F16) and grad32
+ *                        are addressed like out, each in its own elements; only the bags of the slice are written; any number of
+ *                        tables, one launch (csrc/grad_widen.hip).  Pass grad32 to any of pm_embbag_bwd_sorted* / pm_embbag_bwd_fused*
+ *                        / pm_embbag_sparse_grad / pm_embbag_psw_grad (once, in front of the table ranges of a request of more than
+ *                        1024 tables).  Refusals as pm_embbag_mean_grad, plus grad_dtype PM_F32 or unknown, mean not 0 / 1, mean with
+ *                        per_sample_weights; grad16 must be 8-byte and grad32 16-byte aligned, and the two must differ.
+ * Replaces the output cast behind fbgemm's TBE forward (output_dtype) and the .to(torch.float32) pass in front of its backward.
+ */
+int pm_embbag_fwd_out16(const pm_embbag_batch* op, const int64_t* padding_idx, int32_t mean, int32_t out_dtype, void* out,
+                        pm_stream_t stream);
+int pm_embbag_grad_widen(const pm_embbag_batch* op, const int64_t* padding_idx, int32_t mean, int32_t grad_dtype, const void* grad16,
+                         float* grad32, pm_stream_t stream);
+
+/*
  * DLRM input redistribution on the device: regroup what the lengths / indices all-to-alls deliver
  * (train/comms/pt/dlrm.py:744-855) -- lengths [world][num_tables][batch] int64 and the indices
  * concatenated block by block in that (rank, table) order -- into the TBE request of the batched

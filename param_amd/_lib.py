@@ -78,6 +78,8 @@ EXPORTED_SYMBOLS = (
     "pm_pad_rows_guard",
     "pm_embbag_fwd_mean",
     "pm_embbag_mean_grad",
+    "pm_embbag_fwd_out16",
+    "pm_embbag_grad_widen",
 )
 
 
@@ -264,6 +266,11 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embbag_fwd_mean.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp]
     L.pm_embbag_mean_grad.restype = ctypes.c_int
     L.pm_embbag_mean_grad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp, vp]
+    # 16-bit output and gradients: (op, pad array or NULL, mean 0 / 1, PM_BF16 | PM_F16, ...)
+    L.pm_embbag_fwd_out16.restype = ctypes.c_int
+    L.pm_embbag_fwd_out16.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, i32, vp, vp]
+    L.pm_embbag_grad_widen.restype = ctypes.c_int
+    L.pm_embbag_grad_widen.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, i32, vp, vp, vp]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]

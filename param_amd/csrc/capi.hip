@@ -648,18 +648,19 @@ int pm_embbag_fwd(const pm_embbag_batch* op, float* out, pm_stream_t stream) {
 // The padded forward keeps the plain bag-count tiling of make_params and adds the product forward's output burst where the
 // tile's rows fit 16 KB (the tile is halved until they do); requests whose lookups divide evenly over the bags get an index
 // tile sized for what a tile holds, as the product forward's do (a longer tile reads its indices from the request).
-static void plan_padded_forward(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p) {
+// out_bytes: of an output element (pm_embbag_fwd_out16: 2 -- its burst buffer holds 2-byte elements).
+static void plan_padded_forward(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p, int out_bytes = 4) {
     const int NG = pm::kBlock / pm::group_lanes(op->max_dim, (elem_dtype == PM_F32) ? 4 : 8);
     int bpb = p.bags_per_block;
     if (g_bags_per_block.load() <= 0)
-        while (bpb > NG && static_cast<int64_t>(bpb) * op->max_dim * 4 > 16384) bpb /= 2;
+        while (bpb > NG && static_cast<int64_t>(bpb) * op->max_dim * out_bytes > 16384) bpb /= 2;
     p.bags_per_block = bpb;
     p.tiles_per_table = static_cast<int32_t>((op->bag_count + bpb - 1) / bpb);      // (bpb only shrank: the grid check of validate_request holds)
     const int64_t total_bags = static_cast<int64_t>(op->num_tables) * op->batch;
     const bool even = total_bags > 0 && op->num_indices % total_bags == 0;
     int want = g_stage_out.load();
     if (want < 0) want = fwd_env().stage;
-    p.stage_out = (want && static_cast<int64_t>(bpb) * op->max_dim * 4 <= 16384) ? op->max_dim : 0;
+    p.stage_out = (want && static_cast<int64_t>(bpb) * op->max_dim * out_bytes <= 16384) ? op->max_dim : 0;
     p.stage_bags = bpb;
     if (even) {
         int64_t need = (2 * static_cast<int64_t>(bpb) * (op->num_indices / total_bags) + 255) / 256 * 256;
@@ -730,6 +731,54 @@ int pm_embbag_mean_grad(const pm_embbag_batch* op, const int64_t* padding_idx, c
         return fail(PM_ERR_INVALID, "grad and scaled must be 16-byte aligned");
     const hipError_t h = pm::launch_mean_grad(p, op->max_dim, padding_idx, grad, scaled, static_cast<hipStream_t>(stream));
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_mean_grad launch");
+    return PM_OK;
+}
+
+// ---- 16-bit output and gradients (embbag_fwd_out16_*.hip, grad_widen.hip) -------------------------------------------------------
+static int out16_dtype_ok(int32_t dtype, const char* what, const char* fp32_hint) {
+    if (dtype == PM_BF16 || dtype == PM_F16) return PM_OK;
+    return fail(PM_ERR_INVALID, std::string(what) + " must be PM_BF16 or PM_F16 (" + fp32_hint + ")");
+}
+
+int pm_embbag_fwd_out16(const pm_embbag_batch* op, const int64_t* padding_idx, int32_t mean, int32_t out_dtype, void* out, pm_stream_t stream) {
+    pm::KParams p;
+    int rc = make_params(op, op ? op->weight_dtype : -1, p);
+    if (rc != PM_OK) return rc;
+    if ((rc = out16_dtype_ok(out_dtype, "out_dtype", "fp32 output is written by pm_embbag_fwd, pm_embbag_fwd_padded and pm_embbag_fwd_mean")) != PM_OK) return rc;
+    if (mean != 0 && mean != 1) return fail(PM_ERR_INVALID, "mean must be 0 or 1");
+    if (op->grad_block_shift != 0 || op->table_group != 0)
+        return fail(PM_ERR_UNSUPPORTED, "16-bit output does not take blocked layouts (grad_block_shift / table_group must be 0)");
+    if (mean && op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "mean pooling is unweighted: per_sample_weights must be NULL");
+    if (p.bag_count == 0) return PM_OK;
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    if (reinterpret_cast<uintptr_t>(out) % 8 != 0) return fail(PM_ERR_INVALID, "out must be 8-byte aligned");
+    plan_padded_forward(op, op->weight_dtype, p, 2);
+    p.io = static_cast<float*>(out);           // (the kernel addresses it as 2-byte elements)
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const hipError_t h = op->weight_dtype == PM_F32    ? pm::launch_embbag_fwd_out16_f32(p, op->max_dim, padding_idx, mean != 0, out_dtype, s)
+                         : op->weight_dtype == PM_BF16 ? pm::launch_embbag_fwd_out16_bf16(p, op->max_dim, padding_idx, mean != 0, out_dtype, s)
+                                                       : pm::launch_embbag_fwd_out16_f16(p, op->max_dim, padding_idx, mean != 0, out_dtype, s);
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_fwd_out16 launch");
+    return PM_OK;
+}
+
+int pm_embbag_grad_widen(const pm_embbag_batch* op, const int64_t* padding_idx, int32_t mean, int32_t grad_dtype, const void* grad16,
+                         float* grad32, pm_stream_t stream) {
+    pm::KParams p;
+    int rc = make_params(op, op ? op->weight_dtype : -1, p);
+    if (rc != PM_OK) return rc;
+    if ((rc = out16_dtype_ok(grad_dtype, "grad_dtype", "an fp32 gradient goes to the backward entry points as it is, or through pm_embbag_mean_grad")) != PM_OK) return rc;
+    if (mean != 0 && mean != 1) return fail(PM_ERR_INVALID, "mean must be 0 or 1");
+    if (op->grad_block_shift != 0 || op->table_group != 0)
+        return fail(PM_ERR_UNSUPPORTED, "16-bit gradients do not take blocked layouts (grad_block_shift / table_group must be 0)");
+    if (mean && op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "mean pooling is unweighted: per_sample_weights must be NULL");
+    if (p.bag_count == 0) return PM_OK;
+    if (!grad16 || !grad32) return fail(PM_ERR_INVALID, "grad16 / grad32 is NULL");
+    if (reinterpret_cast<uintptr_t>(grad16) % 8 != 0 || reinterpret_cast<uintptr_t>(grad32) % 16 != 0)
+        return fail(PM_ERR_INVALID, "grad16 must be 8-byte aligned and grad32 16-byte aligned");
+    if (grad16 == static_cast<const void*>(grad32)) return fail(PM_ERR_INVALID, "grad32 must not be grad16 (the widening is not in place)");
+    const hipError_t h = pm::launch_grad_widen(p, op->max_dim, padding_idx, mean != 0, grad_dtype, grad16, grad32, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_grad_widen launch");
     return PM_OK;
 }
 

@@ -193,6 +193,13 @@ hipError_t launch_pad_mask(const KParams& p, const int64_t* pad_idx, float* valu
 // mean pooling (embbag_fwd_pad.hip with MEAN = true, mean_pool.hip): pad_idx may be NULL (no table has a padding row)
 hipError_t launch_embbag_fwd_mean(const KParams& p, int weight_dtype, int max_dim, const int64_t* pad_idx, hipStream_t stream);
 hipError_t launch_mean_grad(const KParams& p, int max_dim, const int64_t* pad_idx, const float* grad, float* scaled, hipStream_t stream);
+// 16-bit output and gradients (embbag_fwd_out16_*.hip: one translation unit per table dtype; grad_widen.hip): p.io = the bf16 / fp16
+// output, out_dtype / grad_dtype PM_BF16 | PM_F16, pad_idx may be NULL; the burst buffer holds bags_per_block * stage_out 2-byte elements
+hipError_t launch_embbag_fwd_out16_f32(const KParams& p, int max_dim, const int64_t* pad_idx, bool mean, int out_dtype, hipStream_t stream);
+hipError_t launch_embbag_fwd_out16_bf16(const KParams& p, int max_dim, const int64_t* pad_idx, bool mean, int out_dtype, hipStream_t stream);
+hipError_t launch_embbag_fwd_out16_f16(const KParams& p, int max_dim, const int64_t* pad_idx, bool mean, int out_dtype, hipStream_t stream);
+hipError_t launch_grad_widen(const KParams& p, int max_dim, const int64_t* pad_idx, bool mean, int grad_dtype, const void* grad16,
+                             float* grad32, hipStream_t stream);
 
 // sort-based deterministic backward (embbag_bwd_sorted.hip)
 hipError_t sorted_workspace_bytes(const KParams& p, int64_t max_rows, int max_dim, size_t& bytes);

@@ -6,9 +6,9 @@
 // backward fed with the scaled gradient".
 //
 // A lane group per bag, 16 bytes per lane (a wider row takes several rounds), plain loads and stores (the backward reads the buffer
-// at once: it should stay in L2).  Without a pad array the count is two offset reads; with one, the group's lanes stride over the
-// bag's indices and every round's kept lookups are a ballot, masked to the group's lanes, and a population count.
+// at once: it should stay in L2).  The count is mean_count.h's (shared with grad_widen.hip).
 #include "common.h"
+#include "mean_count.h"
 
 namespace pm {
 namespace {
@@ -23,22 +23,7 @@ __global__ void __launch_bounds__(kBlock) mean_grad_kernel(const KParams p, cons
     const int t = static_cast<int>(bag / p.bag_count);
     const int64_t b = p.bag_begin + bag % p.bag_count;
     const int64_t g = static_cast<int64_t>(t) * p.B + b;
-    int64_t s = bag_start_or_end(p, g), e = bag_start_or_end(p, g + 1);
-    s = s < 0 ? 0 : s;                         // (an unrepaired request: nothing outside the index array is read)
-    e = e > p.N ? p.N : e;
-    int64_t count = e > s ? e - s : 0;
-    const int64_t pad = pad_idx ? pad_idx[t] : -1;
-    if (pad >= 0 && count > 0) {
-        const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
-        const int shift = lane & ~(G - 1);     // the group's first lane in its wave
-        const uint64_t mask = G == kWave ? ~0ull : ((1ull << G) - 1ull);
-        count = 0;
-        for (int64_t j0 = s; j0 < e; j0 += G) {                  // the trip count is the group's: its lanes stay together
-            const int64_t j = j0 + lig;
-            const bool keep = j < e && load_index(p.indices, j, p.idx64) != pad;
-            count += __popcll((__ballot(keep) >> shift) & mask);
-        }
-    }
+    const int64_t count = bag_kept_count(p, pad_idx, t, g, G, lig);      // mean_count.h
     const int D = p.dims[t];
     const int64_t row = p.out_offsets[t] + b * p.out_stride;
     const f32x4* src = reinterpret_cast<const f32x4*>(grad + row);

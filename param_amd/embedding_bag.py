@@ -291,23 +291,31 @@ class _TableSet:
 
 
 def _fwd(ts: _TableSet, indices, offsets, B, psw=None, out=None, bag_begin=0, bag_count=None, split_bags: bool = False,
-         pad: Optional[torch.Tensor] = None, mean: bool = False):
+         pad: Optional[torch.Tensor] = None, mean: bool = False, out16: Optional[torch.dtype] = None):
     """``split_bags``: one workgroup per bag with wave-shuffle / LDS partial reductions (``pm_embbag_fwd_split``) -- for
     few, long bags; agrees with the default kernel to fp32 rounding, not bit for bit.  ``pad``: per-table padding indices
     (device int64 ``[T]``, -1 = none): the padded forward (``pm_embbag_fwd_padded``); ``None``: the call is what it always was.
-    ``mean``: mean pooling (``pm_embbag_fwd_mean``: the padded forward's kernel with the division fused; ``pad`` may be ``None``)."""
+    ``mean``: mean pooling (``pm_embbag_fwd_mean``: the padded forward's kernel with the division fused; ``pad`` may be ``None``).
+    ``out16``: ``torch.bfloat16`` / ``torch.float16``: the output is that dtype (``pm_embbag_fwd_out16``: the padded forward's kernel with
+    one rounding fused in front of its stores -- sum, weighted sum or mean, ``pad`` may be ``None``); ``None``: fp32, the calls above."""
+    if out16 is not None and (split_bags or ts.layout == "blocked"):
+        raise ValueError('a 16-bit output_dtype is not supported with split_bags=True or layout="blocked"')
     if pad is not None and (split_bags or ts.layout == "blocked"):
         raise ValueError('padding_idx is not supported with split_bags=True or layout="blocked"')
     if mean and (split_bags or ts.layout == "blocked" or psw is not None):
         raise ValueError('mean pooling is not supported with split_bags=True, layout="blocked" or per_sample_weights')
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count, forward=True)
     _, _, shape = ts.out_desc(B)
+    odt = torch.float32 if out16 is None else out16
     if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=ts.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
+        out = torch.empty(shape, dtype=odt, device=ts.device)
+    elif out.dtype != odt or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {str(odt).replace('torch.', '')} tensor of shape {shape}")
     L = _lib.load()
-    if mean:
+    if out16 is not None:
+        rc = L.pm_embbag_fwd_out16(ctypes.byref(op), None if pad is None else pad.data_ptr(), 1 if mean else 0, _WDTYPE[out16],
+                                   out.data_ptr(), _stream_ptr())
+    elif mean:
         rc = L.pm_embbag_fwd_mean(ctypes.byref(op), None if pad is None else pad.data_ptr(), out.data_ptr(), _stream_ptr())
     elif pad is not None:
         rc = L.pm_embbag_fwd_padded(ctypes.byref(op), pad.data_ptr(), out.data_ptr(), _stream_ptr())
@@ -355,13 +363,48 @@ def _workspace(ts: _TableSet, op, max_rows: Optional[int] = None, query=None) ->
     return ts.scratch("_ws", query(ctypes.byref(op), max(ts.rows) if max_rows is None else max_rows))
 
 
-def _check_grad(ts: _TableSet, grad, B) -> torch.Tensor:
-    """the gradient of a batch of B bags in the table set's output layout, contiguous"""
+def _check_grad(ts: _TableSet, grad, B, out16: Optional[torch.dtype] = None) -> torch.Tensor:
+    """the gradient of a batch of B bags in the table set's output layout, contiguous: fp32 (always), or the module's 16-bit output
+    dtype ``out16``"""
     _require_device(grad, "grad")
     _, _, shape = ts.out_desc(B)
-    if grad.dtype != torch.float32 or tuple(grad.shape) != tuple(shape):
-        raise ValueError(f"grad must be float32 of shape {shape}")
+    if (grad.dtype != torch.float32 and (out16 is None or grad.dtype != out16)) or tuple(grad.shape) != tuple(shape):
+        also = "" if out16 is None else f" or {str(out16).replace('torch.', '')} (the module's output_dtype)"
+        raise ValueError(f"grad must be float32{also} of shape {shape}")
     return grad.contiguous()
+
+
+def _output_dtype(spec) -> torch.dtype:
+    """``output_dtype`` of the two modules as a torch dtype: ``None`` / ``torch.float32`` (fp32, the default), ``torch.bfloat16``,
+    ``torch.float16``, the strings ``"fp32"`` / ``"bf16"`` / ``"fp16"`` in any case, or an enum member whose ``value`` or ``name`` is one
+    of those (fbgemm's ``SparseType``, read by shape).  Anything else raises ValueError.  Needs no device."""
+    names = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+    if spec is None:
+        return torch.float32
+    if isinstance(spec, torch.dtype) and spec in names.values():
+        return spec
+    for key in (spec, getattr(spec, "value", None), getattr(spec, "name", None)):
+        if isinstance(key, str) and key.lower() in names:
+            return names[key.lower()]
+    raise ValueError(f"output_dtype must be None, torch.float32, torch.bfloat16, torch.float16, one of fp32 / bf16 / fp16 (any case) or "
+                     f"an enum member of that value or name (fbgemm's SparseType), got {spec!r}")
+
+
+def _widen(ts: _TableSet, grad, indices, offsets, B, psw, pad: Optional[torch.Tensor], mean: bool, bag_begin=0, bag_count=None) -> torch.Tensor:
+    """A bf16 / fp16 gradient as the fp32 gradient of a SUM forward (``pm_embbag_grad_widen``): a scratch of ``grad``'s shape from torch's
+    allocator holding ``float(grad(t, b))`` for the bags of the slice -- with ``mean`` times ``1.0f / count(t, b)`` in the same launch,
+    which is ``_mean_scale`` of the widened gradient bit for bit.  Bags outside the slice are not written (no backward reads them);
+    ``grad`` itself is never modified.  One launch for any number of tables.  ``psw`` only keeps the cached request descriptor of the
+    backward that follows: the call reads no weights."""
+    if ts.layout == "blocked":
+        raise ValueError('a 16-bit gradient is not supported with layout="blocked"')
+    op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
+    wide = torch.empty(grad.shape, dtype=torch.float32, device=grad.device)
+    rc = _lib.load().pm_embbag_grad_widen(ctypes.byref(op), None if pad is None else pad.data_ptr(), 1 if mean else 0, _WDTYPE[grad.dtype],
+                                          grad.data_ptr(), wide.data_ptr(), _stream_ptr())
+    if rc:
+        _lib.check(rc)
+    return wide
 
 
 _MEAN_WEIGHTED = "mean pooling is unweighted: per_sample_weights must be None (fbgemm's weighted mean is not implemented)"
@@ -384,9 +427,17 @@ def _mean_scale(ts: _TableSet, grad, indices, offsets, B, pad: Optional[torch.Te
     return scaled
 
 
-def _grad_as_sum(ts: _TableSet, grad, indices, offsets, B, psw, pad, mean: bool, bag_begin=0, bag_count=None) -> torch.Tensor:
-    """The gradient of the module's forward as the gradient of a SUM forward of the same request, which is what every backward
-    route below takes: ``grad`` itself for sum pooling, its scaled copy (``_mean_scale``) for mean pooling -- which is unweighted."""
+def _grad_as_sum(ts: _TableSet, grad, indices, offsets, B, psw, pad, mean: bool, bag_begin=0, bag_count=None,
+                 out16: Optional[torch.dtype] = None) -> torch.Tensor:
+    """The gradient of the module's forward as the fp32 gradient of a SUM forward of the same request, which is what every backward
+    route below takes: ``grad`` itself for sum pooling, its scaled copy (``_mean_scale``) for mean pooling -- which is unweighted.  A
+    gradient in the module's 16-bit output dtype ``out16`` is widened once (``_widen``), the mean scaling fused into that launch."""
+    if out16 is not None:
+        grad = _check_grad(ts, grad, B, out16)      # (fp32 or out16: any other dtype is refused here, by the module's own rule)
+        if grad.dtype == out16:
+            if mean and psw is not None:
+                raise ValueError(_MEAN_WEIGHTED)
+            return _widen(ts, grad, indices, offsets, B, psw, pad, mean, bag_begin, bag_count)
     if not mean:
         return grad
     if psw is not None:
@@ -503,13 +554,14 @@ def _no_presorted_split(ts, presorted: bool) -> None:
 
 def _bwd(ts: _TableSet, grad, indices, offsets, B, dst_ptrs_dev, dst_dtype, alpha, psw=None,
          bag_begin=0, bag_count=None, method: str = "sorted", presorted: bool = False, pooling: Optional[int] = None,
-         pad: Optional[torch.Tensor] = None, mean: bool = False):
+         pad: Optional[torch.Tensor] = None, mean: bool = False, out16: Optional[torch.dtype] = None):
     """``method="sorted"`` (default): deterministic, bit-identical to a sequential scatter-add;
     ``method="atomic"``: hardware float atomics (order not fixed; tests / tools: the alternates build).
     ``pad``: per-table padding indices (device int64 ``[T]``): those rows of the destinations are saved before and restored
     after the call (``_PadGuard``) -- once, around all table ranges of a large request; a call refused on the host launches neither.
-    ``mean``: ``grad`` is the gradient of a mean-pooled forward: scaled once (``_grad_as_sum``), then everything below as it is."""
-    grad = _check_grad(ts, _grad_as_sum(ts, grad, indices, offsets, B, psw, pad, mean, bag_begin, bag_count), B)
+    ``mean``: ``grad`` is the gradient of a mean-pooled forward: scaled once (``_grad_as_sum``), then everything below as it is.
+    ``out16``: the module's 16-bit output dtype: a gradient of that dtype is widened once (``_grad_as_sum``)."""
+    grad = _check_grad(ts, _grad_as_sum(ts, grad, indices, offsets, B, psw, pad, mean, bag_begin, bag_count, out16), B)
     if method not in ("sorted", "atomic"):
         raise ValueError('method must be "sorted" or "atomic"')
     if method == "sorted":
@@ -652,8 +704,10 @@ class _BoundsChecked:
 
     _TABLES = "weight"      # the nn.Parameter that holds the tables: where they live is where the pad array goes
 
-    def _init_shared(self, bounds_check_mode) -> None:
+    def _init_shared(self, bounds_check_mode, output_dtype=None) -> None:
         self.bounds_check_mode = bounds_check_mode_name(bounds_check_mode)
+        self.output_dtype = _output_dtype(output_dtype)
+        self._out16 = None if self.output_dtype == torch.float32 else self.output_dtype      # what the host layer is handed
         self._bounds_report: Optional[torch.Tensor] = None
         self._bounds_reported = False
         self._seen: dict = {}      # what the module remembers about the CONTENTS of request tensors (dropped by _contents_changed)
@@ -708,13 +762,14 @@ _WD_MODES = {None: _lib.PM_WD_NONE, "none": _lib.PM_WD_NONE, 0: _lib.PM_WD_NONE,
 def _adagrad(ts: _TableSet, grad, indices, offsets, B, mom_ptrs_dev, lr: float, eps: float, psw=None,
              presorted: bool = False, weight_decay: float = 0.0, weight_decay_mode=None, stochastic_rounding: bool = False,
              seed: int = 0, pooling: Optional[int] = None, elementwise: bool = False, pad: Optional[torch.Tensor] = None,
-             mean: bool = False):
+             mean: bool = False, out16: Optional[torch.dtype] = None):
     """Fused backward + exact row-wise Adagrad on the tables of ``ts`` (``pm_embbag_bwd_sorted_adagrad_ex``), or, with
     ``elementwise``, exact element-wise Adagrad (``pm_embbag_bwd_sorted_adagrad_elem``: ``mom_ptrs_dev`` then points at one
     fp32 ``[rows_t, dims_t]`` state buffer per table).  ``pad``: per-table padding indices (device int64 ``[T]``): those rows
     and their state are saved before and restored after the step (``_PadGuard``); a step refused on the host launches neither.
-    ``mean``: ``grad`` is the gradient of a mean-pooled forward: scaled once (``_grad_as_sum``), then everything below as it is."""
-    grad = _grad_as_sum(ts, grad, indices, offsets, B, psw, pad, mean)
+    ``mean``: ``grad`` is the gradient of a mean-pooled forward: scaled once (``_grad_as_sum``), then everything below as it is.
+    ``out16``: the module's 16-bit output dtype: a gradient of that dtype is widened once (``_grad_as_sum``)."""
+    grad = _grad_as_sum(ts, grad, indices, offsets, B, psw, pad, mean, out16=out16)
     if weight_decay_mode not in _WD_MODES:
         raise ValueError(f"weight_decay_mode must be one of none / l2 / decouple, got {weight_decay_mode!r}")
     grad = _check_grad(ts, grad, B)
@@ -781,12 +836,13 @@ def _drop_padding_rows(rows, vals, pads):
 
 
 def _sparse_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, bag_begin=0, bag_count=None, pads=None,
-                 mean: bool = False, pad: Optional[torch.Tensor] = None):
+                 mean: bool = False, pad: Optional[torch.Tensor] = None, out16: Optional[torch.dtype] = None):
     """Coalesced sparse gradient (``pm_embbag_sparse_grad*``): a list of T ``(rows_t, values_t)`` -- rows_t the distinct rows table t's
     lookups hit (ascending int64), values_t ``[U_t, D_t]`` fp32, ``values_t[k] = sum_{j: idx_j = rows_t[k]} w_j * grad[t, bag(j)]`` in
     the sorted backward's order.  Synchronises once per request of at most 1024 tables (to size the outputs).  ``mean``: ``grad`` is
-    the gradient of a mean-pooled forward: scaled once (``_grad_as_sum``; ``pad`` = the device form of ``pads``)."""
-    grad = _check_grad(ts, _grad_as_sum(ts, grad, indices, offsets, B, psw, pad, mean, bag_begin, bag_count), B)
+    the gradient of a mean-pooled forward: scaled once (``_grad_as_sum``; ``pad`` = the device form of ``pads``).  ``out16``: the module's
+    16-bit output dtype: a gradient of that dtype is widened once (``_grad_as_sum``)."""
+    grad = _check_grad(ts, _grad_as_sum(ts, grad, indices, offsets, B, psw, pad, mean, bag_begin, bag_count, out16), B)
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
     op.fixed_pooling = 0
     # more tables than one sorted call takes: independent requests of at most 1024 tables (_table_chunks)
@@ -797,12 +853,13 @@ def _sparse_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, bag_begin=0
 
 
 def _psw_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, out=None, bag_begin=0, bag_count=None,
-              pad: Optional[torch.Tensor] = None):
+              pad: Optional[torch.Tensor] = None, out16: Optional[torch.dtype] = None):
     """Gradient of ``per_sample_weights`` (``pm_embbag_psw_grad``): fp32 ``[N]``, ``out[j] = <grad[t, bag(j)], table_t[indices[j]]>``
     for the lookups of the bag slice, with the arithmetic fixed in include/param_amd.h.  ``psw`` only keeps the cached request
     descriptor of the backward that follows: the value does not depend on it.  ``pad``: per-table padding indices (device int64
-    ``[T]``): the entries of padded lookups are then overwritten with +0.0 (``pm_embbag_pad_mask``, one more launch)."""
-    grad = _check_grad(ts, grad, B)
+    ``[T]``): the entries of padded lookups are then overwritten with +0.0 (``pm_embbag_pad_mask``, one more launch).  ``out16``: the
+    module's 16-bit output dtype: a gradient of that dtype is widened first (``_grad_as_sum``)."""
+    grad = _check_grad(ts, _grad_as_sum(ts, grad, indices, offsets, B, psw, None, False, bag_begin, bag_count, out16), B)
     op = ts.request(indices, offsets, B, psw, bag_begin, bag_count)
     n = indices.numel()
     if out is None:
@@ -817,6 +874,15 @@ def _psw_grad(ts: _TableSet, grad, indices, offsets, B, psw=None, out=None, bag_
     return out
 
 
+def _psw_shared_grad(ctx, ts: _TableSet, grad_out, indices, offsets, psw, B=None) -> torch.Tensor:
+    """``grad_out`` of an autograd backward that also owes the ``per_sample_weights`` gradient: a 16-bit one is widened here, once, for
+    both consumers (weighted requests are sum-pooled: no scaling); every other gradient comes back as it is"""
+    out16 = ctx.module._out16
+    if out16 is None or grad_out.dtype != out16 or not (ctx.has_psw and ctx.needs_input_grad[4]):
+        return grad_out
+    return _grad_as_sum(ts, grad_out, indices, offsets, ctx.B if B is None else B, psw, None, False, out16=out16)
+
+
 class _DenseGradFn(torch.autograd.Function):
     """forward = batched lookup; backward = scatter-add into a dense fp32 weight.grad
     (torch ``sparse=False`` semantics, aten::_embedding_bag_dense_backward), and -- for ``per_sample_weights`` that require it --
@@ -829,7 +895,7 @@ class _DenseGradFn(torch.autograd.Function):
         ctx.module, ctx.B = module, B
         ctx.save_for_backward(indices, offsets, psw if psw is not None else torch.empty(0))
         ctx.has_psw = psw is not None
-        return _fwd(ts, indices, offsets, B, psw, pad=module._pad_dev(), mean=module.mode == "mean")
+        return _fwd(ts, indices, offsets, B, psw, pad=module._pad_dev(), mean=module.mode == "mean", out16=module._out16)
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -838,10 +904,11 @@ class _DenseGradFn(torch.autograd.Function):
         ts = m._tables()
         dW = torch.zeros(m.weight.shape, dtype=torch.float32, device=grad_out.device)
         d_ptr = torch.tensor([dW.data_ptr()], dtype=torch.int64, device=grad_out.device)
-        grad_out = grad_out.contiguous()
+        grad_out = _psw_shared_grad(ctx, ts, grad_out.contiguous(), indices, offsets, psw)
         pad = m._pad_dev()
         # (mean: grad_out is left as it is -- the scaled copy is a scratch of _bwd's)
-        _bwd(ts, grad_out, indices, offsets, ctx.B, d_ptr, torch.float32, 1.0, psw if ctx.has_psw else None, pad=pad, mean=m.mode == "mean")
+        _bwd(ts, grad_out, indices, offsets, ctx.B, d_ptr, torch.float32, 1.0, psw if ctx.has_psw else None, pad=pad, mean=m.mode == "mean",
+             out16=m._out16)
         d_psw = _psw_grad(ts, grad_out, indices, offsets, ctx.B, psw, pad=pad) if ctx.has_psw and ctx.needs_input_grad[4] else None
         return dW.to(m.weight.dtype), None, None, None, d_psw
 
@@ -855,9 +922,10 @@ class _SparseGradFn(_DenseGradFn):
         indices, offsets, psw = ctx.saved_tensors
         m = ctx.module
         w = m.weight
-        grad_out = grad_out.contiguous()
+        grad_out = _psw_shared_grad(ctx, m._tables(), grad_out.contiguous(), indices, offsets, psw)
         ((rows, vals),) = _sparse_grad(m._tables(), grad_out, indices, offsets, ctx.B, psw if ctx.has_psw else None,
-                                       pads=None if m.padding_idx is None else [m.padding_idx], mean=m.mode == "mean", pad=m._pad_dev())
+                                       pads=None if m.padding_idx is None else [m.padding_idx], mean=m.mode == "mean", pad=m._pad_dev(),
+                                       out16=m._out16)
         d_psw = (_psw_grad(m._tables(), grad_out, indices, offsets, ctx.B, psw, pad=m._pad_dev())
                  if ctx.has_psw and ctx.needs_input_grad[4] else None)
         g = torch.sparse_coo_tensor(rows[None], vals.to(w.dtype), tuple(w.shape), is_coalesced=True)
@@ -891,15 +959,19 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
     gradients where no row is looked up twice, otherwise up to the order of the additions).  16-bit tables keep this package's
     convention (rows widened, fp32 sums and output); torch's own 16-bit module rounds the sum to 16 bits before it divides.
     ``per_sample_weights`` with ``mode="mean"`` raises ``NotImplementedError``, as torch does; ``mode="max"`` is not implemented.
+    ``output_dtype`` (default ``None`` = fp32; fbgemm TBE's argument): ``torch.bfloat16`` / ``torch.float16``, ``"bf16"`` / ``"fp16"`` in
+    any case or an enum member of that value or name (``SparseType``): ``forward`` returns that dtype -- the fp32 result of the same
+    request rounded once, to nearest even, in the lookup kernel (``pm_embbag_fwd_out16``) -- and the backward receives it: the gradient
+    is widened exactly (``pm_embbag_grad_widen``, the mean scaling fused) and then treated as the fp32 gradient it stands for.
     """
 
     def __init__(self, num_embeddings: int, embedding_dim: int, mode: str = "sum", sparse: bool = False,
                  dtype: torch.dtype = torch.float32, device=None, _weight: Optional[torch.Tensor] = None,
-                 bounds_check_mode="none", padding_idx: Optional[int] = None):
+                 bounds_check_mode="none", padding_idx: Optional[int] = None, output_dtype=None):
         super().__init__()
         if mode not in ("sum", "mean"):
             raise NotImplementedError('only mode="sum" (the reference hot path, pytorch_emb.py:179) and mode="mean" are implemented')
-        self._init_shared(bounds_check_mode)      # (validated before anything is allocated)
+        self._init_shared(bounds_check_mode, output_dtype)      # (validated before anything is allocated)
         self.padding_idx = _normalize_padding_idx(padding_idx, num_embeddings if _weight is None else int(_weight.shape[0]))
         self._off2d: dict = {}
         self.num_embeddings, self.embedding_dim, self.mode, self.sparse = num_embeddings, embedding_dim, mode, sparse
@@ -972,7 +1044,8 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
         ts = self._ts
         if ts is None or ts.ptrs[0] != w.data_ptr():
             ts = self._tables()
-        return _fwd(ts, indices, offsets, offsets.numel(), per_sample_weights, pad=self._pad_dev(), mean=self.mode == "mean")
+        return _fwd(ts, indices, offsets, offsets.numel(), per_sample_weights, pad=self._pad_dev(), mean=self.mode == "mean",
+                    out16=self._out16)
 
     def sanitize_(self, indices, offsets, mode=None) -> None:
         """The sanitiser on its own (``offsets`` is ``[B]``, as ``forward`` takes it): in place, stream-ordered.  ``mode``: default
@@ -983,7 +1056,8 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
 
     def extra_repr(self) -> str:
         return (f"{self.num_embeddings}, {self.embedding_dim}, mode={self.mode}, dtype={self.weight.dtype}" + (", sparse=True" if self.sparse else "") +
-                (f", padding_idx={self.padding_idx}" if self.padding_idx is not None else ""))
+                (f", padding_idx={self.padding_idx}" if self.padding_idx is not None else "") +
+                (f", output_dtype={self.output_dtype}" if self._out16 is not None else ""))
 
 
 class _FusedUpdateFn(torch.autograd.Function):
@@ -1004,7 +1078,9 @@ class _FusedUpdateFn(torch.autograd.Function):
         d_psw = None
         if ctx.has_psw and ctx.needs_input_grad[4]:
             # before the in-place update, on the same stream: the gradient belongs to the weights the forward read
-            d_psw = _psw_grad(m._tables(), grad_out, indices, offsets, m._batch_of(offsets, indices), psw, pad=m._pad_dev())
+            B = m._batch_of(offsets, indices)
+            grad_out = _psw_shared_grad(ctx, m._tables(), grad_out.contiguous(), indices, offsets, psw, B)
+            d_psw = _psw_grad(m._tables(), grad_out, indices, offsets, B, psw, pad=m._pad_dev())
         m.optimizer_step_(grad_out, indices, offsets, per_sample_weights=psw if ctx.has_psw else None)
         return None, None, None, None, d_psw
 
@@ -1041,15 +1117,27 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     of ``grad``'s shape; ``grad`` is not modified), then each is exactly what it is for a sum module.  A stated difference to
     fbgemm, which allows weighted mean: ``per_sample_weights`` with ``"mean"`` raises ValueError, and so do
     ``per_sample_weights_grad``, ``lookup(split_bags=True)``, ``lookup_quantized`` and ``layout="blocked"``.  ``"sum"`` adds no launch.
+
+    ``output_dtype`` (default ``None`` = fp32; fbgemm TBE's argument of that name): ``torch.float32`` / ``torch.bfloat16`` /
+    ``torch.float16``, ``"fp32"`` / ``"bf16"`` / ``"fp16"`` in any case, or an enum member whose value or name is one of those
+    (``SparseType``); anything else raises ValueError.  With a 16-bit dtype ``forward`` / ``lookup`` (``out=`` and batch slices
+    included) return it: the fp32 result of the same request -- sum, weighted sum or mean, with or without padding -- rounded once per
+    element, to nearest even, in the lookup kernel (``pm_embbag_fwd_out16``).  ``scatter_add_``, ``adagrad_step_``, ``optimizer_step_``,
+    ``dense_grad``, ``sparse_grad``, ``per_sample_weights_grad`` and the fused ``backward`` then take ``grad`` in fp32 (always) or in
+    that dtype: a 16-bit gradient is widened exactly into an fp32 scratch (one more launch, ``pm_embbag_grad_widen``, which also does
+    the mean scaling; ``grad`` is not modified) and each is exactly what it is for that fp32 gradient.  ``layout="blocked"``,
+    ``lookup(split_bags=True)`` and ``lookup_quantized`` do not take a 16-bit ``output_dtype`` (ValueError).  The default adds no launch.
     """
 
     def __init__(self, rows: Sequence[int], dims, dtype: torch.dtype = torch.float32, device="cuda",
                  layout: str = "bd", init: Optional[str] = "uniform_dlrm", seed: int = 0,
                  learning_rate: float = 0.01, fused_update: bool = True, optimizer: str = "sgd", eps: float = 1.0e-8,
                  weight_decay: float = 0.0, weight_decay_mode=None, stochastic_rounding: bool = False,
-                 block_bags: Optional[int] = None, bounds_check_mode="none", padding_idx=None, pooling_mode="sum"):
+                 block_bags: Optional[int] = None, bounds_check_mode="none", padding_idx=None, pooling_mode="sum", output_dtype=None):
         super().__init__()
-        self._init_shared(bounds_check_mode)      # (validated, like the optimizer below, before anything is allocated)
+        self._init_shared(bounds_check_mode, output_dtype)      # (validated, like the optimizer below, before anything is allocated)
+        if self._out16 is not None and layout == "blocked":
+            raise ValueError('a 16-bit output_dtype is not supported with layout="blocked"')
         self.pooling_mode = pooling_mode_name(pooling_mode)
         self._mean = self.pooling_mode == "mean"
         if self._mean and layout == "blocked":
@@ -1160,12 +1248,14 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             raise ValueError("lookup(split_bags=True) does not take padding_idx")
         if self._mean and (split_bags or per_sample_weights is not None):
             raise ValueError('pooling_mode="mean" does not take split_bags=True' if split_bags else _MEAN_WEIGHTED)
+        if split_bags and self._out16 is not None:
+            raise ValueError("lookup(split_bags=True) does not take a 16-bit output_dtype")
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
         B = self._batch_of(offsets, indices) if batch is None else batch
         if self.bounds_check_mode != "none":
             self._sanitize(self._tables(), indices, offsets, B, self.bounds_check_mode, per_sample_weights, bag_begin, bag_count)
         return _fwd(self._tables(), indices, offsets, B, per_sample_weights, out, bag_begin, bag_count, split_bags,
-                    pad=self._pad_dev(), mean=self._mean)
+                    pad=self._pad_dev(), mean=self._mean, out16=self._out16)
 
     def sanitize_(self, indices, offsets, batch: Optional[int] = None, mode=None) -> None:
         """The sanitiser on its own, in front of any entry point that does not run it (everything but ``forward`` / ``lookup``):
@@ -1188,6 +1278,8 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             raise ValueError("lookup_quantized does not take padding_idx")
         if self._mean:
             raise ValueError('lookup_quantized does not take pooling_mode="mean"')
+        if self._out16 is not None:
+            raise ValueError("lookup_quantized does not take a 16-bit output_dtype (its fp16 rows are a payload format of its own)")
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
         B = self._batch_of(offsets, indices) if batch is None else batch
         return _fwd_quantized(self._tables(), indices, offsets, B, bitwidth, per_sample_weights, out, bag_begin, bag_count)
@@ -1214,7 +1306,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         ts = self._tables()
         B = self._batch(offsets, indices, batch)
         _bwd(ts, grad, indices, offsets, B, ts.d_ptrs, self.weights.dtype, alpha, per_sample_weights,
-             bag_begin, bag_count, method, presorted, pooling, pad=self._pad_dev(), mean=self._mean)
+             bag_begin, bag_count, method, presorted, pooling, pad=self._pad_dev(), mean=self._mean, out16=self._out16)
 
     def sort_status(self, indices, offsets, per_sample_weights=None, batch: Optional[int] = None, bag_begin=0, bag_count=None) -> dict:
         """status of the last key sort on this module's workspace (synchronises)"""
@@ -1256,7 +1348,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         _adagrad(self._tables(), grad, indices, offsets, B, self._mom_ptrs, self.learning_rate, self.eps,
                  per_sample_weights, presorted, self.weight_decay, self.weight_decay_mode, self.stochastic_rounding,
                  seed=0x5EED0000 + self._sr_step, pooling=pooling, elementwise=self.optimizer == "adagrad", pad=self._pad_dev(),
-                 mean=self._mean)
+                 mean=self._mean, out16=self._out16)
 
     def optimizer_step_(self, grad, indices, offsets, per_sample_weights=None, batch: Optional[int] = None,
                         presorted: bool = False):
@@ -1283,7 +1375,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
                 raise ValueError("out must hold one contiguous float32 [rows_t, dims_t] tensor per table on the module's device")
         d_ptrs = torch.tensor([o.data_ptr() for o in outs], dtype=torch.int64, device=ts.device)
         _bwd(ts, grad, indices, offsets, B, d_ptrs, torch.float32, 1.0, per_sample_weights, method=method, pad=self._pad_dev(),
-             mean=self._mean)
+             mean=self._mean, out16=self._out16)
         return outs
 
     def sparse_grad(self, grad, indices, offsets, per_sample_weights=None, batch: Optional[int] = None, bag_begin=0,
@@ -1298,7 +1390,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         own: ``per_sample_weights_grad``."""
         B = self._batch(offsets, indices, batch)
         return _sparse_grad(self._tables(), grad, indices, offsets, B, per_sample_weights, bag_begin, bag_count,
-                            pads=self.padding_idx, mean=self._mean, pad=self._pad_dev())
+                            pads=self.padding_idx, mean=self._mean, pad=self._pad_dev(), out16=self._out16)
 
     def per_sample_weights_grad(self, grad, indices, offsets, batch: Optional[int] = None, out=None, bag_begin=0, bag_count=None):
         """Gradient of ``per_sample_weights``: fp32 ``[N]``, ``out[j] = sum_c grad[t, bag(j)][c] * table_t[indices[j], c]`` -- what
@@ -1312,7 +1404,10 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             raise ValueError('per_sample_weights_grad: pooling_mode="mean" is unweighted')
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
         B = self._batch(offsets, indices, batch)
-        return _psw_grad(self._tables(), grad, indices, offsets, B, None, out, bag_begin, bag_count, pad=self._pad_dev())
+        return _psw_grad(self._tables(), grad, indices, offsets, B, None, out, bag_begin, bag_count, pad=self._pad_dev(), out16=self._out16)
+
+    def extra_repr(self) -> str:
+        return f"output_dtype={self.output_dtype}" if self._out16 is not None else ""
 
     def check(self, indices, offsets, per_sample_weights=None, batch: Optional[int] = None) -> None:
         B = self._batch(offsets, indices, batch)
