@@ -10,11 +10,6 @@ namespace {
 
 thread_local std::string g_last_error;
 
-// Row loads a lane group keeps in flight in the forward.  Round 3 found that rounds 1-2 had measured this knob with ONE load
-// in flight whatever its value (a wait at the merge of the staged / unstaged index paths, embbag_fwd.hip); with the batch
-// real: 1 -> 19.3 G lookups/s Zipf / 0.727 of the HBM peak uniform, 2 -> 22.2 / 0.734, 3 -> 21.5 / 0.712, 4 -> 21.7 / 0.732,
-// 6 -> 21.3 / 0.712, 8 -> 21.4 / 0.732 (48 x 10 M x 128 fp32, profiles/r03_fwd_unroll_sweep.txt); Criteo 14.1 / 15.6 / 15.1 at 1 / 2 / 4.
-constexpr int kDefaultUnroll = 2;
 std::atomic<int> g_unroll{0};
 std::atomic<int> g_bags_per_block{0};
 std::atomic<int> g_xcd_affine{-1};
@@ -37,89 +32,73 @@ int hip_fail(hipError_t rc, const char* what) {
     return fail(PM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(rc));
 }
 
-// The forward's environment switches (kernel sweeps; every one has a pm_set_* or a default that the product uses): read ONCE
-// per process, on the first forward -- not on the launch path (getenv is not thread-safe against setenv, and a value that
-// changes between two calls of one request's sequence is a hazard, not a feature).
-struct FwdEnv {
-    int stage;        // PARAM_AMD_FWD_STAGE=0: no LDS-staged output burst
-    int flat;         // PARAM_AMD_FWD_FLAT=0: no flat-walk kernel; 2: also for pooling factors up to 4
-    int flat_maxl;    // PARAM_AMD_FLAT_MAXL
-    int flat_target;  // PARAM_AMD_FLAT_TARGET (lookups per flat-walk tile)
-    int flat_bags;    // PARAM_AMD_FLAT_BAGS (bags per flat-walk tile at most)
-    int tile_major;   // PARAM_AMD_FWD_TILE_MAJOR=1
-    int flat_compact; // PARAM_AMD_FLAT_COMPACT=0: the flat-walk kernel's old grid (T x smallest-tile count); N > 1: exactly N workgroups
-};
-const FwdEnv& fwd_env() {
-    static const FwdEnv e = [] {
+// The forward's environment switches (pm::FwdEnv, launch_plan.h): read ONCE per process, on the first request -- not on the launch
+// path (getenv is not thread-safe against setenv, and a value that changes between two calls of one request's sequence is a hazard,
+// not a feature).
+const pm::FwdEnv& fwd_env() {
+    static const pm::FwdEnv e = [] {
         auto num = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
-        FwdEnv r;
+        pm::FwdEnv r;
         const char* st = getenv("PARAM_AMD_FWD_STAGE");
         r.stage = (st && st[0] == '0') ? 0 : 1;
-        r.flat = num("PARAM_AMD_FWD_FLAT", 1);
-        r.flat_maxl = num("PARAM_AMD_FLAT_MAXL", 0);
-        r.flat_target = num("PARAM_AMD_FLAT_TARGET", 256);
-        r.flat_bags = num("PARAM_AMD_FLAT_BAGS", 256);
-        r.tile_major = num("PARAM_AMD_FWD_TILE_MAJOR", -1);
-        r.flat_compact = num("PARAM_AMD_FLAT_COMPACT", 1);
+        r.flat = num("PARAM_AMD_FWD_FLAT", r.flat);
+        r.flat_maxl = num("PARAM_AMD_FLAT_MAXL", r.flat_maxl);
+        r.flat_target = num("PARAM_AMD_FLAT_TARGET", r.flat_target);
+        r.flat_bags = num("PARAM_AMD_FLAT_BAGS", r.flat_bags);
+        r.tile_major = num("PARAM_AMD_FWD_TILE_MAJOR", r.tile_major);
+        r.flat_compact = num("PARAM_AMD_FLAT_COMPACT", r.flat_compact);
         return r;
     }();
     return e;
 }
 
-int flat_target_knob(const FwdEnv& env) { const int k = g_flat_target.load(); return k > 0 ? k : env.flat_target; }
+// Every knob a plan reads, loaded once per call (apply_params alone reads one more, the sorted apply's row policy): a pm_set_* from another thread lands before or after a request's plan, never inside it.
+pm::PlanKnobs current_knobs() {
+    constexpr auto relaxed = std::memory_order_relaxed;
+    pm::TuningSetters s;
+    s.unroll = g_unroll.load(relaxed);
+    s.bags_per_block = g_bags_per_block.load(relaxed);
+    s.xcd_affine = g_xcd_affine.load(relaxed);
+    s.nt_loads = g_nt_loads.load(relaxed);
+    s.stage_out = g_stage_out.load(relaxed);
+    s.flat_grid = g_flat_grid.load(relaxed);
+    s.flat_target = g_flat_target.load(relaxed);
+    return pm::resolve_knobs(s, fwd_env());
+}
 
 bool dtype_is_weight(int d) { return d == PM_F32 || d == PM_BF16 || d == PM_F16; }
 
 const char* const kNoSortRecorded = "no sort has been recorded for this workspace";
 
-// A request's launch parameters in three parts (defined below make_params): what can be refused -- for the element type the call
-// reads or writes the tables as --, the base parameters every entry point uses, and the forward's own tiling.
-int validate_request(const pm_embbag_batch* op, int elem_dtype, int* tile_bags_out = nullptr);
-void fill_params(const pm_embbag_batch* op, int elem_dtype, int bpb, pm::KParams& p);
-void plan_forward(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p);
+// which of launch_plan.h's plans an entry point launches with
+enum class PlanKind { base, forward, quantized, padded, padded16 };
 
-// Validate the host-visible part of a request and derive the launch geometry.
-// forward = the call is pm_embbag_fwd / pm_embbag_fwd_quantized: only those get the staged-output geometry (smaller tiles,
-// index tile sized for the request) and work tiles; every other entry point keeps the plain bag-count tiling.
-int make_params(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p, bool forward = false) {
-    int bpb = 0;
-    const int rc = validate_request(op, elem_dtype, &bpb);
+// A request's launch parameters in two parts (defined below make_params): what can be refused -- for the element type the call
+// reads or writes the tables as; shape: the request's shape, which the grid check derives and a plan starts from --, and the request
+// with a plan's geometry as kernel arguments.
+int validate_request(const pm_embbag_batch* op, int elem_dtype, const pm::PlanKnobs& knobs, pm::PlanShape* shape = nullptr);
+void fill_params(const pm_embbag_batch* op, const pm::LaunchPlan& plan, pm::KParams& p);
+
+// Validate the host-visible part of a request and derive the launch geometry: the plain bag-count tiling (base) for every entry point
+// but the forwards, which name their own plan.  unroll: the plan's (forward, quantized).
+int make_params(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p, PlanKind kind = PlanKind::base, int* unroll = nullptr) {
+    const pm::PlanKnobs knobs = current_knobs();
+    pm::PlanShape shape;
+    const int rc = validate_request(op, elem_dtype, knobs, &shape);
     if (rc != PM_OK) return rc;
-    fill_params(op, elem_dtype, bpb, p);
-    if (forward) plan_forward(op, elem_dtype, p);
+    const pm::LaunchPlan plan = kind == PlanKind::forward     ? pm::plan_forward(*op, shape, knobs)
+                                : kind == PlanKind::quantized ? pm::plan_quantized(*op, shape, knobs)
+                                : kind == PlanKind::padded    ? pm::plan_padded(*op, shape, knobs, 4)
+                                : kind == PlanKind::padded16  ? pm::plan_padded(*op, shape, knobs, 2)
+                                                              : pm::plan_base(*op, shape, knobs);
+    fill_params(op, plan, p);
+    if (unroll) *unroll = plan.unroll;
     return PM_OK;
 }
 
-// bags per tile of the plain bag-count tiling
-int tile_bags(const pm_embbag_batch* op, int elem_dtype) {
-    const int vec = (elem_dtype == PM_F32) ? 4 : 8;
-    const int G = pm::group_lanes(op->max_dim, vec);
-    const int NG = pm::kBlock / G;
-    int bpb = g_bags_per_block.load();
-    if (bpb <= 0) {
-        // 4 bags per lane group amortise the LDS staging; small requests shrink the tile until the
-        // grid fills the chip (256 CUs x 8 resident workgroups) -- a 16 K-bag single-table lookup
-        // ran 2 workgroups per CU at 49 % of the roofline with the fixed tile (gpurun r1e)
-        bpb = 4 * NG;
-        // Short average bags go with one bag per lane group: requests whose tables have very different bag
-        // sizes (Criteo multi-hot 1 .. 100, average 8.2) otherwise leave a few tables' workgroups 100x longer
-        // than the rest -- measured 7.2 (32 bags/tile) vs 14.3 G lookups/s (8); with uniform L = 20 the
-        // 32-bag tile is 3.5 % faster under Zipf and 2 % slower under uniform indices (sweeps r1f/r1g).
-        {
-            const int64_t tb = static_cast<int64_t>(op->num_tables) * op->batch;
-            if (tb > 0 && op->num_indices < 12 * tb) bpb = NG;
-        }
-        const int64_t want_blocks = 256 * 8;
-        while (bpb > NG && static_cast<int64_t>(op->num_tables) * ((op->bag_count + bpb - 1) / bpb) < want_blocks) bpb /= 2;
-    }
-    if (bpb < NG) bpb = NG;
-    if (bpb > 1024) bpb = 1024;
-    return bpb;
-}
-
 // Everything a request can be refused for on the host, in the order the checks have always run: the same input gives the same first
-// error.  tile_bags_out: the tile the grid was checked with.
-int validate_request(const pm_embbag_batch* op, int elem_dtype, int* tile_bags_out) {
+// error.
+int validate_request(const pm_embbag_batch* op, int elem_dtype, const pm::PlanKnobs& knobs, pm::PlanShape* shape) {
     if (!op) return fail(PM_ERR_INVALID, "op is NULL");
     if (op->num_tables < 1) return fail(PM_ERR_INVALID, "num_tables must be >= 1");
     if (!dtype_is_weight(elem_dtype)) return fail(PM_ERR_INVALID, "weight/dst dtype must be PM_F32, PM_BF16 or PM_F16");
@@ -142,8 +121,10 @@ int validate_request(const pm_embbag_batch* op, int elem_dtype, int* tile_bags_o
     if (op->fixed_pooling < 0 ||
         (op->fixed_pooling > 0 && op->fixed_pooling * op->batch * static_cast<int64_t>(op->num_tables) != op->num_indices))
         return fail(PM_ERR_INVALID, "fixed_pooling must be 0 or num_indices / (num_tables * batch)");
-    const int bpb = tile_bags(op, elem_dtype);
-    if ((op->bag_count + bpb - 1) / bpb * op->num_tables > 0x7fffffffLL) return fail(PM_ERR_UNSUPPORTED, "grid too large");
+    // the grid of the base plan's tile (the forward plans check their own smaller tiles and keep this one where those do not fit)
+    const pm::PlanShape s = pm::plan_shape(*op, elem_dtype, knobs);
+    if (shape) *shape = s;
+    if ((op->bag_count + s.base_tile - 1) / s.base_tile * op->num_tables > pm::kMaxGrid) return fail(PM_ERR_UNSUPPORTED, "grid too large");
     if (op->grad_block_shift < 0 || op->grad_block_shift > 31 || op->grad_block_extra < 0 || op->table_group < 0)
         return fail(PM_ERR_INVALID, "grad_block_shift must be in [0, 31], grad_block_extra and table_group >= 0");
     // a blocked gradient needs blocks of at least two bags that tile the batch (shift 0 with a non-zero extra used to read
@@ -152,23 +133,10 @@ int validate_request(const pm_embbag_batch* op, int elem_dtype, int* tile_bags_o
         return fail(PM_ERR_INVALID, "grad_block_extra needs grad_block_shift >= 1 (a block of one bag is the un-blocked layout)");
     if (op->grad_block_shift > 0 && (op->batch & ((static_cast<int64_t>(1) << op->grad_block_shift) - 1)) != 0)
         return fail(PM_ERR_INVALID, "batch must be a multiple of 2^grad_block_shift bags");
-    if (tile_bags_out) *tile_bags_out = bpb;
     return PM_OK;
 }
 
-void fill_params(const pm_embbag_batch* op, int elem_dtype, int bpb, pm::KParams& p) {
-    const int NG = pm::kBlock / pm::group_lanes(op->max_dim, (elem_dtype == PM_F32) ? 4 : 8);
-    const int64_t tiles = (op->bag_count + bpb - 1) / bpb;
-
-    const int64_t total_bags = static_cast<int64_t>(op->num_tables) * op->batch;
-    const int64_t avg_l = total_bags > 0 ? (op->num_indices + total_bags - 1) / total_bags : 0;
-    int64_t cap = 2 * bpb * avg_l;
-    cap = (cap + 255) / 256 * 256;
-    // tables of one request can have very different bag sizes (Criteo multi-hot 1 .. 100 at an average of 8):
-    // size the tile for 4x the average, at least 2048 entries (4096 unweighted: 16 KiB of LDS per workgroup)
-    if (cap < (op->per_sample_weights ? 2048 : 4096)) cap = op->per_sample_weights ? 2048 : 4096;
-    if (cap > 4096) cap = 4096;
-
+void fill_params(const pm_embbag_batch* op, const pm::LaunchPlan& plan, pm::KParams& p) {
     p.tables = op->tables;
     p.rows = op->rows;
     p.dims = op->dims;
@@ -183,198 +151,22 @@ void fill_params(const pm_embbag_batch* op, int elem_dtype, int bpb, pm::KParams
     p.bag_begin = op->bag_begin;
     p.bag_count = op->bag_count;
     p.T = op->num_tables;
-    p.tiles_per_table = static_cast<int32_t>(tiles);
-    p.bags_per_block = bpb;
-    p.idx_cap = static_cast<int32_t>(cap);
     p.idx64 = op->index_dtype == PM_I64 ? 1 : 0;
-    const int xa = g_xcd_affine.load();
-    // T % 8 == 0: table t on XCD t % 8.  Any other table count (26 tables: BASELINE configs[3]): contiguous eighths of the
-    // table-major tile order (common.h) -- 26 x 10 M x 128, [B, sum D] output: 0.692 -> 0.700 of the HBM peak under uniform indices,
-    // 19.6 -> 21.15 G lookups/s under Zipf (tools/r4_fwd_xcd.py) -- but only where every table has the same lookups per tile: with
-    // the Criteo tables' pooling factors of 1 .. 100 the XCD that gets the 100-hot table does a third of the launch (0.70 -> 0.27)
-    {
-        const int64_t tb = static_cast<int64_t>(op->num_tables) * op->batch;
-        const bool even_req = tb > 0 && op->num_indices % tb == 0;
-        p.xcd_affine = xa == 0 ? 0 : (op->num_tables % pm::kXcds == 0 ? 1 : ((op->num_tables > 1 && even_req) ? 3 : 0));
-        // blocked requests (table_group = W consecutive request tables read ONE weight table): contiguous eighths of the
-        // table-major tile order keep a weight table's blocks on one XCD; t % 8 would spread them over all eight
-        if (xa != 0 && op->table_group > 1 && op->num_tables > 1 && even_req) p.xcd_affine = 3;
-    }
-    const int nt = g_nt_loads.load();
-    p.nt_loads = nt > 0 ? nt : 0;   // forward: any non-zero = non-temporal row loads; sorted backward: 1 nt, 2 system scope
-    // lookups that do not divide evenly over the bags: certainly ragged (fixed-size requests -- every benchmark shape --
-    // always divide; a ragged request that happens to divide merely runs the unordered kernel)
-    // ... and only where the order can matter: with one bag per lane group (short-bag tiles) nothing is pulled
-    p.ordered = (total_bags > 0 && op->num_indices % total_bags != 0 && bpb > NG) ? 1 : 0;
     p.alpha = 1.0f;
     p.gblk_shift = op->grad_block_shift > 0 ? op->grad_block_shift : 31;
     p.gblk_extra = op->grad_block_shift > 0 ? op->grad_block_extra : 0;
-    // LDS-staged output (forward): the tile's pooled rows leave in one burst at the end of the tile (embbag_fwd.hip).
-    // Measured at benchmark size: uniform indices 0.69 -> 0.72-0.74 of the HBM peak in both output layouts, Zipf within
-    // +-2 % -- provided the workgroup's LDS stays small (at 6 workgroups per CU the latency-bound Zipf launch lost 12 %):
-    // so only for requests whose lookups divide evenly over the bags (fixed pooling: every benchmark shape), whose index
-    // tile can then be sized for what a tile really holds instead of the 4096-entry default, and only where the staging
-    // buffer fits 16 KB (the tile is halved until it does).  pm_set_forward_tuning(0) / PARAM_AMD_FWD_STAGE=0 turn it off.
     p.out_bits = 0;
-    p.stage_out = 0;
-    p.stage_bags = 0;
-    p.flat_bags = 0;
-    p.flat_target = 0;
-    p.flat_compact = 0;
-}
-
-void plan_forward(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p) {
-    const int vec = (elem_dtype == PM_F32) ? 4 : 8;
-    const int G = pm::group_lanes(op->max_dim, vec);
-    const int NG = pm::kBlock / G;
-    int bpb = p.bags_per_block;
-    const int64_t total_bags = static_cast<int64_t>(op->num_tables) * op->batch;
-    const int64_t avg_l = total_bags > 0 ? (op->num_indices + total_bags - 1) / total_bags : 0;
-    const FwdEnv& env = fwd_env();
-    int want = g_stage_out.load();
-    if (want < 0) want = env.stage;
-    const bool even = total_bags > 0 && op->num_indices % total_bags == 0;
-    if (want && even && !p.ordered && g_bags_per_block.load() <= 0) {
-        while (bpb > NG && static_cast<int64_t>(bpb) * op->max_dim * 4 > 16384) bpb /= 2;
-        if (static_cast<int64_t>(bpb) * op->max_dim * 4 <= 16384) {
-            const int64_t tiles2 = (op->bag_count + bpb - 1) / bpb;
-            if (tiles2 * op->num_tables <= 0x7fffffffLL) {
-                p.bags_per_block = bpb;
-                p.tiles_per_table = static_cast<int32_t>(tiles2);
-                p.stage_out = op->max_dim;
-                int64_t need = (2 * static_cast<int64_t>(bpb) * avg_l + 255) / 256 * 256;
-                if (need < 512) need = 512;
-                if (need < p.idx_cap) p.idx_cap = static_cast<int32_t>(need);
-            }
-        }
-    } else if (want && even && !p.ordered && static_cast<int64_t>(bpb) * op->max_dim * 4 <= 16384) {
-        p.stage_out = op->max_dim;   // explicit bags_per_block (sweeps): stage if it fits, index tile sized the same way
-        int64_t need = (2 * static_cast<int64_t>(bpb) * avg_l + 255) / 256 * 256;
-        if (need < 512) need = 512;
-        if (need < p.idx_cap) p.idx_cap = static_cast<int32_t>(need);
-    } else if (want && !even && !p.ordered && g_bags_per_block.load() <= 0 &&
-               static_cast<int64_t>(bpb) * op->max_dim * 4 <= 4096) {
-        // short-bag tiles of requests with per-table pooling (Criteo multi-hot: one bag per lane group, 8 bags per
-        // tile): the staging buffer is 4 KB, the full-size index tile stays -- 20.6 KB per workgroup
-        p.stage_out = op->max_dim;
-    }
-    p.stage_bags = p.bags_per_block;
-    // ... and those requests run the flat-walk kernel (embbag_fwd.hip): tiles sized per table on the device (~256 lookups, up
-    // to 32 bags for the pooling-1 tables), row loads in flight across bag borders.  tiles_per_table stays the count of the
-    // smallest tile (one bag per lane group): workgroups past their table's tile count leave.  Criteo tables, visit
-    // r3_criteo_flat (Zipf G lookups/s / uniform fraction; run-to-run +-1.5 %): 8-bag tiles 15.7-15.9 / 0.69-0.71; flat walk
-    // target 512 cap 64: 16.4-16.5 / 0.705-0.716; **256 / 32: 16.6 / 0.719**; 128: 16.1 / 0.695; 1024 / 128: 14.1 / 0.64.
-    // PARAM_AMD_FWD_FLAT=0 turns it off (PARAM_AMD_FLAT_TARGET / _BAGS: sweeps).
-    // (Round 6: that cap of 32 bags was chosen under round 3's grid, where a larger cap also meant more surplus workgroups.  With
-    // the compact launch a one-hot table's 32-bag tile is three round trips of set-up around 32 row loads; one process per setting,
-    // three each, us uniform / Zipf: cap 32: 192-193 / 118; 64: 182 / 114; 128: 186 / 112; **256: 181 / 111.6**
-    // -- profiles/r06_flat_bags_cap_sweep_all128.jsonl.  The cap is 256 bags on every flat-walk path now.)
-    const int flat_env = env.flat;
-    const bool flat_on = flat_env != 0;
-    // ... and so do fixed-pooling requests of one or two lookups per bag (one-hot tables): bag by bag a lane group has one or
-    // two row loads in flight.  48 x 10 M x 128 fp32, batch 65536 (tools/r3_shortbags.sh; Zipf G lookups/s / uniform fraction):
-    // pooling 1: 4.00 / 0.529 -> 5.05 / 0.624; pooling 2: 7.78 / 0.687 -> 8.75 / 0.686; pooling 4: 13.5 / 0.723 -> 13.4 / 0.679
-    // (not taken; PARAM_AMD_FWD_FLAT=2 extends the rule to 4 for that measurement).
-    const int flat_maxl = env.flat_maxl;
-    if (flat_on && even && avg_l <= (flat_maxl > 0 ? flat_maxl : flat_env == 2 ? 4 : 2) && !p.ordered && g_bags_per_block.load() <= 0 &&
-        p.stage_out > 0) {
-        const int64_t tiles_ng = (op->bag_count + NG - 1) / NG;
-        if (tiles_ng * op->num_tables <= 0x7fffffffLL) {
-            const int tgt2 = flat_target_knob(env);
-            p.flat_bags = env.flat_bags < 32 ? 32 : (env.flat_bags > 1024 ? 1024 : env.flat_bags / NG * NG);
-            p.flat_target = tgt2;
-            p.tiles_per_table = static_cast<int32_t>(tiles_ng);
-            p.stage_bags = NG;
-            p.bags_per_block = p.flat_bags;
-            if (p.idx_cap < 1024) p.idx_cap = 1024;
-        }
-    }
-    if (flat_on && !even && !p.ordered && g_bags_per_block.load() <= 0 && bpb == NG && p.stage_out > 0) {
-        const int cap_env = env.flat_bags;
-        const int tgt_env = flat_target_knob(env);
-        p.flat_bags = cap_env < NG ? NG : (cap_env > 1024 ? 1024 : cap_env / NG * NG);
-        p.flat_target = tgt_env < 1 ? 1 : tgt_env;
-        p.bags_per_block = p.flat_bags;   // sizes the LDS offsets array; stage_bags (the burst buffer) stays at NG rows
-    }
-    // ABI v7, mixed embedding dims (min_dim given and its lane group narrower than max_dim's): the flat-walk kernel sizes the lane
-    // group PER TABLE on the device (embbag_fwd.hip), whatever the bags look like -- tiles are ~flat_target lookups of any pooling
-    // factor.  flat_bags = the bags the narrowest table's sub-groups pool at once (at least the usual 32): the LDS offsets array.
-    // Ragged requests keep the ordered kernel (longest bag first matters more there than idle lanes).
-    if (flat_on && op->min_dim > 0 && op->min_dim < op->max_dim && !p.ordered && g_bags_per_block.load() <= 0) {
-        int need = (op->min_dim + vec - 1) / vec, g_min = 4;          // sub-groups of 4 lanes at least: 64-byte pieces
-        while (g_min < need) g_min <<= 1;
-        if (g_min < G) {
-            const int ng_max = pm::kBlock / g_min;
-            const int64_t tiles_ng = (op->bag_count + NG - 1) / NG;   // the grid of the smallest tile: the widest table's NG bags
-            if (tiles_ng * op->num_tables <= 0x7fffffffLL) {
-                if (p.flat_bags < ng_max) p.flat_bags = ng_max;
-                // (256 bags at most per tile: a one-hot narrow table then reaches the ~flat_target lookups per tile the wide tables
-                // have -- its 64-bag tiles were three round trips of set-up around 4 KB of rows.  Criteo tables with mixed dims, one
-                // process per setting, two each: cap 64: 143.3-143.9 us, 128: 142.3-142.9, 256: 141.5-142.1; the narrow tables alone
-                // 24.3 -> 21.6 us: profiles/r06_flat_bags_cap_sweep.jsonl)
-                if (p.flat_bags < 256) p.flat_bags = 256;
-                if (p.flat_bags < 32) p.flat_bags = 32;
-                if (p.flat_target <= 0) p.flat_target = flat_target_knob(env) < 1 ? 1 : flat_target_knob(env);
-                p.tiles_per_table = static_cast<int32_t>(tiles_ng);
-                p.bags_per_block = p.flat_bags;
-                p.stage_out = op->max_dim;
-                p.stage_bags = NG;                                    // burst buffer: NG rows of max_dim floats (4 KB at D = 128 fp32)
-                // index tile: twice what a tile holds on average -- ~flat_target lookups, or the narrowest table's ng_max bags
-                int64_t cap2 = 2 * static_cast<int64_t>(ng_max) * avg_l;
-                if (cap2 < 2 * static_cast<int64_t>(p.flat_target)) cap2 = 2 * static_cast<int64_t>(p.flat_target);
-                cap2 = (cap2 + 255) / 256 * 256;
-                p.idx_cap = static_cast<int32_t>(cap2 < 1024 ? 1024 : (cap2 > 4096 ? 4096 : cap2));
-                if (p.xcd_affine == 3) p.xcd_affine = 0;             // eighths of the tile order assume equal tiles per table
-            }
-        }
-    }
-    // flat-walk launches are one resident set of workgroups walking the tile order (embbag_fwd.hip, round 6): 1 = the launcher asks
-    // the device how many that is
-    {
-        int fg = g_flat_grid.load();
-        if (fg < 0) fg = env.flat_compact;
-        if (p.flat_bags > 0 && op->num_tables <= 1024 && fg > 0) {
-            // the tiles the request will have, from its sizes (the tables' own pooling factors are on the device): ~flat_target
-            // lookups each, but at most flat_bags bags; a quarter more, because a table's tile is its average bag count rounded DOWN
-            // to whole lane-group rounds
-            const int64_t n_slice = op->batch > 0 ? (op->num_indices * op->bag_count + op->batch - 1) / op->batch : 0;
-            const int64_t by_lookups = (n_slice + p.flat_target - 1) / p.flat_target;
-            const int64_t by_bags = static_cast<int64_t>(op->num_tables) * ((op->bag_count + p.flat_bags - 1) / p.flat_bags);
-            int64_t est = (by_lookups > by_bags ? by_lookups : by_bags) * 5 / 4 + op->num_tables;
-            if (est < 1024) est = 1024;
-            if (est > (1 << 20)) est = 1 << 20;
-            p.flat_compact = fg > 1 ? fg : static_cast<int32_t>(est);
-        }
-    }
-    // Two tilings built and measured in round 3 for requests whose tables have very different pooling factors (Criteo
-    // multi-hot 1 .. 100) -- both slower than the 8-bag tiles in table-major order, which stay:
-    //  * WORK tiles (~640 lookups per tile whatever the pooling factor, tile boundaries derived on the device from the
-    //    tables' lookup counts): 186 us against 120 us under Zipf, 249 against 185 us under uniform indices (caps of
-    //    32 .. 1024 bags, targets of 320 .. 1280: all slower).  A pooling-1 bag is ONE row load; a lane group walking 16 ..
-    //    128 of them in turn has one load in flight where 1024 eight-bag workgroups have them all in flight at once -- the
-    //    small tiles ARE the memory-level parallelism.  Removed again (profiles/r03_criteo_fwd_work_tiles.txt).
-    //  * tile-major block order (t = b % T, so every table advances at the same rate and the heavy table's long workgroups
-    //    start throughout the launch): 165 against 120 us under Zipf, 220 against 186 us uniform -- a table's tiles then run
-    //    on all eight XCDs at once and on every CU next to other tables' rows.  Kept behind PARAM_AMD_FWD_TILE_MAJOR=1.
-    const int tm_env = env.tile_major;
-    const bool uneven = total_bags > 0 && op->num_indices % total_bags != 0;
-    if (p.xcd_affine != 1 && op->num_tables > 1 && tm_env > 0 && uneven) p.xcd_affine = 2;
-}
-
-// Row loads in flight per lane group when pm_set_tuning leaves the choice to the library.  Two is the measured optimum of a launch
-// that fills the chip (eight workgroups per CU: occupancy provides the memory-level parallelism).  A SMALL request -- the reference
-// driver's batch 512 .. 4096 rows of one 14 M x 128 table, train/compute/pt/dataset.py:56-82 -- has one or two workgroups per CU,
-// each lane group a chain of pooling / 2 dependent round trips: there a deeper batch IS the parallelism.  Additions stay in index
-// order: same bits for every value.
-int small_request_unroll(const pm_embbag_batch* op, const pm::KParams& p) {
-    if (p.flat_bags > 0 || p.ordered) return kDefaultUnroll;
-    const int64_t wgs = static_cast<int64_t>(p.T) * p.tiles_per_table;
-    const int64_t bags = static_cast<int64_t>(op->num_tables) * op->batch;
-    const int64_t avg_l = bags > 0 ? op->num_indices / bags : 0;
-    // kernel us under rocprofv3 --kernel-trace (profiles/r06_small_batch_kernel_us.txt; batch 2 / 4 / 8): 64 workgroups 6.6 / 5.6 / 5.5,
-    // 128: 6.9 / 6.0 / 5.6, 256: 9.6 / 7.7 / 6.6, 512: 13.0 / 13.1 / 13.1, 1024: 22.4 / 22.6 / 23.1 -- it pays up to one workgroup per CU
-    if (wgs > 384) return kDefaultUnroll;
-    return avg_l >= 8 ? 8 : (avg_l >= 4 ? 4 : kDefaultUnroll);
+    p.tiles_per_table = plan.tiles_per_table;
+    p.bags_per_block = plan.bags_per_block;
+    p.idx_cap = plan.idx_cap;
+    p.xcd_affine = plan.xcd_affine;
+    p.nt_loads = plan.nt_loads;
+    p.ordered = plan.ordered;
+    p.stage_out = plan.stage_out;
+    p.stage_bags = plan.stage_bags;
+    p.flat_bags = plan.flat_bags;
+    p.flat_target = plan.flat_target;
+    p.flat_compact = plan.flat_compact;
 }
 
 // ---- the sorted backward's entry points: what they share ---------------------------------------------------------------
@@ -421,7 +213,7 @@ int sorted_request(const pm_embbag_batch* op, int dtype, int64_t max_rows, bool 
     int rc = make_params(op, dtype, p);
     if (rc != PM_OK) return rc;
     if ((rc = sorted_args_ok(op, max_rows)) != PM_OK) return rc;
-    return sparse ? validate_request(op, PM_F32) : PM_OK;
+    return sparse ? validate_request(op, PM_F32, current_knobs()) : PM_OK;
 }
 
 // ... and its workspace.  sparse: the sorted backward's, followed by the relabelling's own few words per sorted position and per tile.
@@ -462,11 +254,26 @@ int sorted_call_prologue(SortedCall& c, const pm_embbag_batch* op, int64_t max_r
 }
 
 // the sorted apply's view of the request: the gradient, the tables it updates, alpha and the default destination-row policy
+// (a cache policy, no geometry: the one knob read outside current_knobs -- "not set" is not a value a plan carries)
 void apply_params(pm::KParams& p, const float* grad, const void* tables, float alpha) {
     p.io = const_cast<float*>(grad);
     p.tables = static_cast<const void* const*>(tables);
     p.alpha = alpha;
     if (g_nt_loads.load() < 0) p.nt_loads = kDefaultRowPolicy;
+}
+
+// what pm_embbag_fwd_padded, pm_embbag_fwd_mean and pm_embbag_fwd_out16 do behind their own argument rules, on a padded plan
+// (launch_plan.h).  out_align: bytes `out` must be aligned to, 0 for no rule beyond its element's; `launch`, `label`: the entry point's own.
+template <typename Launch>
+int padded_forward(pm::KParams& p, void* out, uintptr_t out_align, pm_stream_t stream, Launch&& launch, const char* label) {
+    if (p.bag_count == 0) return PM_OK;
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    if (out_align && reinterpret_cast<uintptr_t>(out) % out_align != 0)
+        return fail(PM_ERR_INVALID, "out must be " + std::to_string(out_align) + "-byte aligned");
+    p.io = static_cast<float*>(out);           // (the 16-bit kernels address it as 2-byte elements)
+    const hipError_t h = launch(p, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, label);
+    return PM_OK;
 }
 
 }  // namespace
@@ -632,62 +439,26 @@ int pm_rows_dequantize(const void* src, int64_t n_rows, int32_t dim, int32_t bit
 
 int pm_embbag_fwd(const pm_embbag_batch* op, float* out, pm_stream_t stream) {
     pm::KParams p;
-    int rc = make_params(op, op ? op->weight_dtype : -1, p, true);
+    int unroll = 0;
+    int rc = make_params(op, op ? op->weight_dtype : -1, p, PlanKind::forward, &unroll);
     if (rc != PM_OK) return rc;
     if (p.bag_count == 0) return PM_OK;
     if (!out) return fail(PM_ERR_INVALID, "out is NULL");
     p.io = out;
-    int unroll = g_unroll.load();
-    if (unroll == 0) unroll = small_request_unroll(op, p);
     const hipError_t h = pm::launch_embbag_fwd(p, op->weight_dtype, op->max_dim, unroll, static_cast<hipStream_t>(stream));
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_fwd launch");
     return PM_OK;
 }
 
 // ---- padding (embbag_fwd_pad.hip, pad_rows.hip) --------------------------------------------------------------------------
-// The padded forward keeps the plain bag-count tiling of make_params and adds the product forward's output burst where the
-// tile's rows fit 16 KB (the tile is halved until they do); requests whose lookups divide evenly over the bags get an index
-// tile sized for what a tile holds, as the product forward's do (a longer tile reads its indices from the request).
-// out_bytes: of an output element (pm_embbag_fwd_out16: 2 -- its burst buffer holds 2-byte elements).
-static void plan_padded_forward(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p, int out_bytes = 4) {
-    const int NG = pm::kBlock / pm::group_lanes(op->max_dim, (elem_dtype == PM_F32) ? 4 : 8);
-    int bpb = p.bags_per_block;
-    if (g_bags_per_block.load() <= 0)
-        while (bpb > NG && static_cast<int64_t>(bpb) * op->max_dim * out_bytes > 16384) bpb /= 2;
-    p.bags_per_block = bpb;
-    p.tiles_per_table = static_cast<int32_t>((op->bag_count + bpb - 1) / bpb);      // (bpb only shrank: the grid check of validate_request holds)
-    const int64_t total_bags = static_cast<int64_t>(op->num_tables) * op->batch;
-    const bool even = total_bags > 0 && op->num_indices % total_bags == 0;
-    int want = g_stage_out.load();
-    if (want < 0) want = fwd_env().stage;
-    p.stage_out = (want && static_cast<int64_t>(bpb) * op->max_dim * out_bytes <= 16384) ? op->max_dim : 0;
-    p.stage_bags = bpb;
-    if (even) {
-        int64_t need = (2 * static_cast<int64_t>(bpb) * (op->num_indices / total_bags) + 255) / 256 * 256;
-        if (need < 512) need = 512;
-        if (need < p.idx_cap) p.idx_cap = static_cast<int32_t>(need);
-    }
-    p.ordered = 0;
-}
-
-// what pm_embbag_fwd_padded and pm_embbag_fwd_mean do behind their own argument rules (`launch`, `label`: the entry point's own)
-static int padded_forward(const pm_embbag_batch* op, pm::KParams& p, const int64_t* padding_idx, float* out, pm_stream_t stream,
-                          decltype(&pm::launch_embbag_fwd_padded) launch, const char* label) {
-    if (p.bag_count == 0) return PM_OK;
-    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
-    plan_padded_forward(op, op->weight_dtype, p);
-    p.io = out;
-    const hipError_t h = launch(p, op->weight_dtype, op->max_dim, padding_idx, static_cast<hipStream_t>(stream));
-    if (h != hipSuccess) return hip_fail(h, label);
-    return PM_OK;
-}
-
 int pm_embbag_fwd_padded(const pm_embbag_batch* op, const int64_t* padding_idx, float* out, pm_stream_t stream) {
     pm::KParams p;
-    int rc = make_params(op, op ? op->weight_dtype : -1, p);
+    int rc = make_params(op, op ? op->weight_dtype : -1, p, PlanKind::padded);
     if (rc != PM_OK) return rc;
     if (!padding_idx) return fail(PM_ERR_INVALID, "padding_idx is NULL (device int64 [num_tables], -1 = no padding row: pm_embbag_fwd takes requests without one)");
-    return padded_forward(op, p, padding_idx, out, stream, pm::launch_embbag_fwd_padded, "pm_embbag_fwd_padded launch");
+    return padded_forward(p, out, 0, stream, [&](const pm::KParams& q, hipStream_t s) {
+        return pm::launch_embbag_fwd_padded(q, op->weight_dtype, op->max_dim, padding_idx, s);
+    }, "pm_embbag_fwd_padded launch");
 }
 
 int pm_embbag_pad_mask(const pm_embbag_batch* op, const int64_t* padding_idx, float* values, pm_stream_t stream) {
@@ -703,28 +474,35 @@ int pm_embbag_pad_mask(const pm_embbag_batch* op, const int64_t* padding_idx, fl
 }
 
 // ---- mean pooling (embbag_fwd_pad.hip with MEAN = true, mean_pool.hip) --------------------------------------------------
-// what both calls refuse on the host, behind make_params: blocked layouts (the padded family's tiling and the scaling kernel address
-// bag b at out_offsets[t] + b * out_stride)
-static int mean_args_ok(const pm_embbag_batch* op) {
+// What the mean, 16-bit output and 16-bit gradient calls refuse on the host, behind make_params.  Blocked layouts: the padded family's
+// tiling and the scaling / widening kernels address bag b at out_offsets[t] + b * out_stride.
+struct Subject { const char* noun; const char* verb; };   // who refuses, in the error text: "<noun> <verb> not take ..."
+constexpr Subject kMeanPooling{"mean pooling", "does"}, kOutput16{"16-bit output", "does"}, kGradients16{"16-bit gradients", "do"};
+static int blocked_refused(const pm_embbag_batch* op, const Subject& who) {
     if (op->grad_block_shift != 0 || op->table_group != 0)
-        return fail(PM_ERR_UNSUPPORTED, "mean pooling does not take blocked layouts (grad_block_shift / table_group must be 0)");
+        return fail(PM_ERR_UNSUPPORTED, std::string(who.noun) + " " + who.verb + " not take blocked layouts (grad_block_shift / table_group must be 0)");
+    return PM_OK;
+}
+static int weighted_mean_refused(const pm_embbag_batch* op) {
+    if (op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "mean pooling is unweighted: per_sample_weights must be NULL");
     return PM_OK;
 }
 
 int pm_embbag_fwd_mean(const pm_embbag_batch* op, const int64_t* padding_idx, float* out, pm_stream_t stream) {
     pm::KParams p;
-    int rc = make_params(op, op ? op->weight_dtype : -1, p);
+    int rc = make_params(op, op ? op->weight_dtype : -1, p, PlanKind::padded);
     if (rc != PM_OK) return rc;
-    if ((rc = mean_args_ok(op)) != PM_OK) return rc;
-    if (op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "mean pooling is unweighted: per_sample_weights must be NULL");
-    return padded_forward(op, p, padding_idx, out, stream, pm::launch_embbag_fwd_mean, "pm_embbag_fwd_mean launch");
+    if ((rc = blocked_refused(op, kMeanPooling)) != PM_OK || (rc = weighted_mean_refused(op)) != PM_OK) return rc;
+    return padded_forward(p, out, 0, stream, [&](const pm::KParams& q, hipStream_t s) {
+        return pm::launch_embbag_fwd_mean(q, op->weight_dtype, op->max_dim, padding_idx, s);
+    }, "pm_embbag_fwd_mean launch");
 }
 
 int pm_embbag_mean_grad(const pm_embbag_batch* op, const int64_t* padding_idx, const float* grad, float* scaled, pm_stream_t stream) {
     pm::KParams p;
     int rc = make_params(op, op ? op->weight_dtype : -1, p);
     if (rc != PM_OK) return rc;
-    if ((rc = mean_args_ok(op)) != PM_OK) return rc;
+    if ((rc = blocked_refused(op, kMeanPooling)) != PM_OK) return rc;
     if (p.bag_count == 0) return PM_OK;
     if (!grad || !scaled) return fail(PM_ERR_INVALID, "grad / scaled is NULL");
     if (reinterpret_cast<uintptr_t>(grad) % 16 != 0 || reinterpret_cast<uintptr_t>(scaled) % 16 != 0)
@@ -735,31 +513,26 @@ int pm_embbag_mean_grad(const pm_embbag_batch* op, const int64_t* padding_idx, c
 }
 
 // ---- 16-bit output and gradients (embbag_fwd_out16_*.hip, grad_widen.hip) -------------------------------------------------------
-static int out16_dtype_ok(int32_t dtype, const char* what, const char* fp32_hint) {
-    if (dtype == PM_BF16 || dtype == PM_F16) return PM_OK;
-    return fail(PM_ERR_INVALID, std::string(what) + " must be PM_BF16 or PM_F16 (" + fp32_hint + ")");
+// what pm_embbag_fwd_out16 and pm_embbag_grad_widen refuse of their own; what: the dtype argument's name, who: as blocked_refused's
+static int out16_args_ok(const pm_embbag_batch* op, int32_t dtype, const char* what, const char* fp32_hint, int32_t mean, const Subject& who) {
+    if (dtype != PM_BF16 && dtype != PM_F16) return fail(PM_ERR_INVALID, std::string(what) + " must be PM_BF16 or PM_F16 (" + fp32_hint + ")");
+    if (mean != 0 && mean != 1) return fail(PM_ERR_INVALID, "mean must be 0 or 1");
+    const int rc = blocked_refused(op, who);
+    return rc != PM_OK || !mean ? rc : weighted_mean_refused(op);
 }
 
 int pm_embbag_fwd_out16(const pm_embbag_batch* op, const int64_t* padding_idx, int32_t mean, int32_t out_dtype, void* out, pm_stream_t stream) {
     pm::KParams p;
-    int rc = make_params(op, op ? op->weight_dtype : -1, p);
+    int rc = make_params(op, op ? op->weight_dtype : -1, p, PlanKind::padded16);
     if (rc != PM_OK) return rc;
-    if ((rc = out16_dtype_ok(out_dtype, "out_dtype", "fp32 output is written by pm_embbag_fwd, pm_embbag_fwd_padded and pm_embbag_fwd_mean")) != PM_OK) return rc;
-    if (mean != 0 && mean != 1) return fail(PM_ERR_INVALID, "mean must be 0 or 1");
-    if (op->grad_block_shift != 0 || op->table_group != 0)
-        return fail(PM_ERR_UNSUPPORTED, "16-bit output does not take blocked layouts (grad_block_shift / table_group must be 0)");
-    if (mean && op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "mean pooling is unweighted: per_sample_weights must be NULL");
-    if (p.bag_count == 0) return PM_OK;
-    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
-    if (reinterpret_cast<uintptr_t>(out) % 8 != 0) return fail(PM_ERR_INVALID, "out must be 8-byte aligned");
-    plan_padded_forward(op, op->weight_dtype, p, 2);
-    p.io = static_cast<float*>(out);           // (the kernel addresses it as 2-byte elements)
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    const hipError_t h = op->weight_dtype == PM_F32    ? pm::launch_embbag_fwd_out16_f32(p, op->max_dim, padding_idx, mean != 0, out_dtype, s)
-                         : op->weight_dtype == PM_BF16 ? pm::launch_embbag_fwd_out16_bf16(p, op->max_dim, padding_idx, mean != 0, out_dtype, s)
-                                                       : pm::launch_embbag_fwd_out16_f16(p, op->max_dim, padding_idx, mean != 0, out_dtype, s);
-    if (h != hipSuccess) return hip_fail(h, "pm_embbag_fwd_out16 launch");
-    return PM_OK;
+    if ((rc = out16_args_ok(op, out_dtype, "out_dtype", "fp32 output is written by pm_embbag_fwd, pm_embbag_fwd_padded and pm_embbag_fwd_mean", mean,
+                            kOutput16)) != PM_OK)
+        return rc;
+    const auto launch = op->weight_dtype == PM_F32 ? pm::launch_embbag_fwd_out16_f32
+                        : op->weight_dtype == PM_BF16 ? pm::launch_embbag_fwd_out16_bf16 : pm::launch_embbag_fwd_out16_f16;
+    return padded_forward(p, out, 8, stream, [&](const pm::KParams& q, hipStream_t s) {
+        return launch(q, op->max_dim, padding_idx, mean != 0, out_dtype, s);
+    }, "pm_embbag_fwd_out16 launch");
 }
 
 int pm_embbag_grad_widen(const pm_embbag_batch* op, const int64_t* padding_idx, int32_t mean, int32_t grad_dtype, const void* grad16,
@@ -767,11 +540,9 @@ int pm_embbag_grad_widen(const pm_embbag_batch* op, const int64_t* padding_idx, 
     pm::KParams p;
     int rc = make_params(op, op ? op->weight_dtype : -1, p);
     if (rc != PM_OK) return rc;
-    if ((rc = out16_dtype_ok(grad_dtype, "grad_dtype", "an fp32 gradient goes to the backward entry points as it is, or through pm_embbag_mean_grad")) != PM_OK) return rc;
-    if (mean != 0 && mean != 1) return fail(PM_ERR_INVALID, "mean must be 0 or 1");
-    if (op->grad_block_shift != 0 || op->table_group != 0)
-        return fail(PM_ERR_UNSUPPORTED, "16-bit gradients do not take blocked layouts (grad_block_shift / table_group must be 0)");
-    if (mean && op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "mean pooling is unweighted: per_sample_weights must be NULL");
+    if ((rc = out16_args_ok(op, grad_dtype, "grad_dtype", "an fp32 gradient goes to the backward entry points as it is, or through pm_embbag_mean_grad",
+                            mean, kGradients16)) != PM_OK)
+        return rc;
     if (p.bag_count == 0) return PM_OK;
     if (!grad16 || !grad32) return fail(PM_ERR_INVALID, "grad16 / grad32 is NULL");
     if (reinterpret_cast<uintptr_t>(grad16) % 8 != 0 || reinterpret_cast<uintptr_t>(grad32) % 16 != 0)
@@ -821,24 +592,19 @@ int pm_pad_rows_guard(int32_t num_tables, int32_t max_dim, void* const* tables, 
 
 int pm_embbag_fwd_quantized(const pm_embbag_batch* op, void* out, int32_t bitwidth, pm_stream_t stream) {
     pm::KParams p;
-    int rc = make_params(op, op ? op->weight_dtype : -1, p, true);
+    int unroll = 0;
+    int rc = make_params(op, op ? op->weight_dtype : -1, p, PlanKind::quantized, &unroll);
     if (rc != PM_OK) return rc;
     if ((rc = rowquant_args_ok(0, op->max_dim, bitwidth)) != PM_OK) return rc;
     if (op->out_stride % op->max_dim != 0) return fail(PM_ERR_INVALID, "out_stride must be a whole number of max_dim-element rows");
     if (p.bag_count == 0) return PM_OK;
     if (!out) return fail(PM_ERR_INVALID, "out is NULL");
     if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return fail(PM_ERR_INVALID, "out must be 16-byte aligned");
-    if (p.flat_bags > 0) {   // the quantised burst lives in the bag-per-group kernel: back to its 8-bag tiles
-        p.bags_per_block = p.stage_bags;
-        p.flat_bags = 0;
-    }
     if (!p.stage_out)
         return fail(PM_ERR_UNSUPPORTED, "quantised output needs the staged forward (fixed-pooling requests whose tile fits the staging "
                                         "buffer, staging not disabled): run pm_embbag_fwd and pm_rows_quantize instead");
     p.io = static_cast<float*>(out);
     p.out_bits = bitwidth;
-    int unroll = g_unroll.load();
-    if (unroll == 0) unroll = kDefaultUnroll;
     hipError_t h = pm::launch_embbag_fwd(p, op->weight_dtype, op->max_dim, unroll, static_cast<hipStream_t>(stream));
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_fwd_quantized launch");
     return PM_OK;
@@ -1035,7 +801,7 @@ static int fused_apply_args_ok(const pm_embbag_batch* op, const float* grad, voi
     if (!op) return fail(PM_ERR_INVALID, "op is NULL");
     if (!dtype_is_weight(dtype)) return fail(PM_ERR_INVALID, "weight/dst dtype must be PM_F32, PM_BF16 or PM_F16");
     if (!grad || !tables) return fail(PM_ERR_INVALID, "grad / dst_tables is NULL");
-    return validate_request(op, dtype);      // the apply builds its parameters for the DESTINATION dtype: its row-width rule too
+    return validate_request(op, dtype, current_knobs());      // the apply builds its parameters for the DESTINATION dtype: its row-width rule too
 }
 
 int pm_embbag_bwd_fused(const pm_embbag_batch* op, const float* grad, void* const* dst_tables, int32_t dst_dtype, float alpha,

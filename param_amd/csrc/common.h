@@ -7,12 +7,11 @@
 #include <string>
 
 #include "param_amd.h"
+#include "launch_plan.h"   // kBlock, kXcds, group_lanes: shared with the host's launch plans
 
 namespace pm {
 
-constexpr int kBlock = 256;  // 4 wave64 per workgroup
 constexpr int kWave = 64;
-constexpr int kXcds = 8;     // MI355X: 8 XCDs, block b is dispatched to XCD b % 8 (speed only)
 
 // native clang vector types (the nontemporal builtins reject HIP_vector_type wrappers)
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -448,14 +447,6 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// lanes per bag for a given widest row: next power of two >= max_dim / vec, clamped to [8, 64]
-inline int group_lanes(int max_dim, int vec) {
-    int need = (max_dim + vec - 1) / vec;
-    int g = 8;
-    while (g < need && g < 64) g <<= 1;
-    return g;
 }
 
 }  // namespace pm

@@ -1,0 +1,375 @@
+// param_amd/csrc/launch_plan.h -- a request's launch geometry as pure host functions of (request, element type, knobs).
+// No HIP, no atomics, no environment: capi.hip snapshots the knobs once per call (current_knobs) and copies a plan into KParams;
+// tests/launch_plan_dump.cpp compiles this header with a plain C++ compiler and tests/test_launch_plan_host.py pins what it plans.
+// (The functions are static: the libraries export nothing of them.)
+#pragma once
+
+#include <stdint.h>
+
+#include "param_amd.h"
+
+namespace pm {
+
+constexpr int kBlock = 256;  // 4 wave64 per workgroup
+constexpr int kXcds = 8;     // MI355X: 8 XCDs, block b is dispatched to XCD b % 8 (speed only)
+
+// lanes per bag for a given widest row: next power of two >= max_dim / vec, clamped to [8, 64]
+inline int group_lanes(int max_dim, int vec) {
+    int need = (max_dim + vec - 1) / vec;
+    int g = 8;
+    while (g < need && g < 64) g <<= 1;
+    return g;
+}
+
+// Row loads a lane group keeps in flight in the forward.  Round 3 found that rounds 1-2 had measured this knob with ONE load
+// in flight whatever its value (a wait at the merge of the staged / unstaged index paths, embbag_fwd.hip); with the batch
+// real: 1 -> 19.3 G lookups/s Zipf / 0.727 of the HBM peak uniform, 2 -> 22.2 / 0.734, 3 -> 21.5 / 0.712, 4 -> 21.7 / 0.732,
+// 6 -> 21.3 / 0.712, 8 -> 21.4 / 0.732 (48 x 10 M x 128 fp32, profiles/r03_fwd_unroll_sweep.txt); Criteo 14.1 / 15.6 / 15.1 at 1 / 2 / 4.
+constexpr int kDefaultUnroll = 2;
+constexpr int kBurstBytes = 16384;     // the LDS-staged output burst: a tile's pooled rows must fit this
+constexpr int64_t kMaxGrid = 0x7fffffffLL;
+
+// ---- knobs --------------------------------------------------------------------------------------------------------------------
+// The forward's environment switches (kernel sweeps; every one has a pm_set_* or a default that the product uses); the values
+// here are the defaults.
+struct FwdEnv {
+    int stage = 1;         // PARAM_AMD_FWD_STAGE=0: no LDS-staged output burst
+    int flat = 1;          // PARAM_AMD_FWD_FLAT=0: no flat-walk kernel; 2: also for pooling factors up to 4
+    int flat_maxl = 0;     // PARAM_AMD_FLAT_MAXL
+    int flat_target = 256; // PARAM_AMD_FLAT_TARGET (lookups per flat-walk tile)
+    int flat_bags = 256;   // PARAM_AMD_FLAT_BAGS (bags per flat-walk tile at most)
+    int tile_major = -1;   // PARAM_AMD_FWD_TILE_MAJOR=1
+    int flat_compact = 1;  // PARAM_AMD_FLAT_COMPACT=0: the flat-walk kernel's old grid (T x smallest-tile count); N > 1: exactly N workgroups
+};
+// what pm_set_tuning and pm_set_forward_tuning were last given; the values here are "not set"
+struct TuningSetters {
+    int unroll = 0, bags_per_block = 0, xcd_affine = -1, nt_loads = -1;   // pm_set_tuning
+    int stage_out = -1, flat_grid = -1, flat_target = -1;                 // pm_set_forward_tuning
+};
+// One call's view of every knob, resolved: a setter value >= 0 (flat_target: > 0) wins, otherwise the environment's, otherwise the
+// default.  A plan is a function of this snapshot, so every plan is one that some knob setting describes.
+struct PlanKnobs {
+    int unroll;          // 0: the library chooses
+    int bags_per_block;  // <= 0: the library chooses
+    int xcd_affine;      // 0: plain table-major block order
+    int nt_loads;        // > 0: non-temporal row loads (< 0: not set -- the sorted backward then has its own default)
+    int stage;           // 0: no output burst
+    int flat;            // FwdEnv::flat
+    int flat_maxl;
+    int flat_target;     // >= 1
+    int flat_bags;
+    int flat_grid;       // 0: grid of T x smallest-tile count; 1: as many resident workgroups as the request has tiles; N > 1: exactly N
+    int tile_major;
+};
+static inline PlanKnobs resolve_knobs(const TuningSetters& s, const FwdEnv& e) {
+    PlanKnobs k;
+    k.unroll = s.unroll;
+    k.bags_per_block = s.bags_per_block;
+    k.xcd_affine = s.xcd_affine;
+    k.nt_loads = s.nt_loads;
+    k.stage = s.stage_out >= 0 ? s.stage_out : e.stage;
+    k.flat = e.flat;
+    k.flat_maxl = e.flat_maxl;
+    k.flat_target = s.flat_target > 0 ? s.flat_target : e.flat_target;
+    if (k.flat_target < 1) k.flat_target = 1;   // (an environment value of 0 or text: the grid estimate divides by it)
+    k.flat_bags = e.flat_bags;
+    k.flat_grid = s.flat_grid >= 0 ? s.flat_grid : e.flat_compact;
+    k.tile_major = e.tile_major;
+    return k;
+}
+
+// ---- the plan -----------------------------------------------------------------------------------------------------------------
+// The geometry members of KParams (common.h describes each) and the forward's unroll (0 where the launch has none).
+struct LaunchPlan {
+    int32_t tiles_per_table, bags_per_block, idx_cap, xcd_affine, nt_loads, ordered;
+    int32_t stage_out, stage_bags, flat_bags, flat_target, flat_compact;
+    int32_t unroll;
+};
+
+// what the rules below read of a request, derived once
+struct PlanShape {
+    int vec;             // elements per 16-byte load
+    int G, NG;           // lanes per lane group (sized for max_dim), lane groups per workgroup
+    int64_t total_bags;  // T * B
+    int64_t avg_l;       // lookups per bag, rounded up
+    bool even;           // the lookups divide evenly over the bags (fixed pooling: every benchmark shape)
+    bool uneven;         // ... they certainly do not: the request is ragged (a request without bags is neither)
+    int base_tile;       // bags per tile of the plain bag-count tiling (tile_bags): the host's grid check and every plan start from it
+};
+
+static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline int64_t round256(int64_t n) { return (n + 255) / 256 * 256; }
+// LDS index tile (entries): twice what `bags` bags hold on average, in steps of 256, at least `floor`
+static inline int64_t index_tile(int64_t bags, int64_t avg_l, int64_t floor) {
+    const int64_t cap = round256(2 * bags * avg_l);
+    return cap < floor ? floor : cap;
+}
+// bags per flat-walk tile at most: the knob in whole lane-group rounds, within [floor, 1024]
+// (whole rounds, not a power of two: PARAM_AMD_FLAT_BAGS=48 plans 48-bag tiles)
+static inline int flat_bag_cap(int knob, int floor, int NG) { return knob < floor ? floor : (knob > 1024 ? 1024 : knob / NG * NG); }
+// the largest tile from `bpb` down (halving, not below one bag per lane group) whose rows of max_dim elem_bytes-elements fit the burst
+static inline int burst_tile(int bpb, int NG, int max_dim, int elem_bytes) {
+    while (bpb > NG && static_cast<int64_t>(bpb) * max_dim * elem_bytes > kBurstBytes) bpb /= 2;
+    return bpb;
+}
+
+// bags per tile of the plain bag-count tiling (s: everything of the shape but base_tile)
+static inline int tile_bags(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k) {
+    const int NG = s.NG;
+    int bpb = k.bags_per_block;
+    if (bpb <= 0) {
+        // 4 bags per lane group amortise the LDS staging; small requests shrink the tile until the
+        // grid fills the chip (256 CUs x 8 resident workgroups) -- a 16 K-bag single-table lookup
+        // ran 2 workgroups per CU at 49 % of the roofline with the fixed tile (sweep r1e)
+        bpb = 4 * NG;
+        // Short average bags go with one bag per lane group: requests whose tables have very different bag
+        // sizes (Criteo multi-hot 1 .. 100, average 8.2) otherwise leave a few tables' workgroups 100x longer
+        // than the rest -- measured 7.2 (32 bags/tile) vs 14.3 G lookups/s (8); with uniform L = 20 the
+        // 32-bag tile is 3.5 % faster under Zipf and 2 % slower under uniform indices (sweeps r1f/r1g).
+        if (s.total_bags > 0 && op.num_indices < 12 * s.total_bags) bpb = NG;
+        const int64_t want_blocks = 256 * 8;
+        while (bpb > NG && op.num_tables * ceil_div(op.bag_count, bpb) < want_blocks) bpb /= 2;
+    }
+    if (bpb < NG) bpb = NG;
+    if (bpb > 1024) bpb = 1024;
+    return bpb;
+}
+
+// A request's shape, derived once per call: capi.hip's validate_request checks the base tile's grid and hands the shape to the plan.
+static inline PlanShape plan_shape(const pm_embbag_batch& op, int elem_dtype, const PlanKnobs& k) {
+    PlanShape s;
+    s.vec = (elem_dtype == PM_F32) ? 4 : 8;
+    s.G = group_lanes(op.max_dim, s.vec);
+    s.NG = kBlock / s.G;
+    s.total_bags = static_cast<int64_t>(op.num_tables) * op.batch;
+    s.avg_l = s.total_bags > 0 ? (op.num_indices + s.total_bags - 1) / s.total_bags : 0;
+    s.even = s.total_bags > 0 && op.num_indices % s.total_bags == 0;
+    s.uneven = s.total_bags > 0 && !s.even;
+    s.base_tile = tile_bags(op, s, k);
+    return s;
+}
+
+// Each kind of plan below comes twice: for a shape the caller has derived already (capi.hip), and for (request, element type, knobs).
+
+// ---- base: the plain bag-count tiling of every backward, check, bounds, psw-grad, split, mean-grad and widen entry ----------------
+static inline LaunchPlan plan_base(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k) {
+    LaunchPlan p = {};
+    p.bags_per_block = s.base_tile;
+    p.tiles_per_table = static_cast<int32_t>(ceil_div(op.bag_count, p.bags_per_block));
+    // tables of one request can have very different bag sizes (Criteo multi-hot 1 .. 100 at an average of 8): the full 4096 entries
+    // (16 KiB of LDS per workgroup) unless the request is weighted -- then twice the tile's average, at least 2048
+    const int64_t cap = index_tile(p.bags_per_block, s.avg_l, op.per_sample_weights ? 2048 : 4096);
+    p.idx_cap = static_cast<int32_t>(cap > 4096 ? 4096 : cap);
+    // T % 8 == 0: table t on XCD t % 8.  Any other table count (26 tables: BASELINE configs[3]): contiguous eighths of the
+    // table-major tile order (common.h) -- 26 x 10 M x 128, [B, sum D] output: 0.692 -> 0.700 of the HBM peak under uniform indices,
+    // 19.6 -> 21.15 G lookups/s under Zipf (tools/r4_fwd_xcd.py) -- but only where every table has the same lookups per tile: with
+    // the Criteo tables' pooling factors of 1 .. 100 the XCD that gets the 100-hot table does a third of the launch (0.70 -> 0.27)
+    const bool eighths = op.num_tables > 1 && s.even;
+    if (k.xcd_affine == 0) p.xcd_affine = 0;
+    // blocked requests (table_group = W consecutive request tables read ONE weight table): contiguous eighths of the
+    // table-major tile order keep a weight table's blocks on one XCD; t % 8 would spread them over all eight
+    else if (op.table_group > 1 && eighths) p.xcd_affine = 3;
+    else p.xcd_affine = op.num_tables % kXcds == 0 ? 1 : (eighths ? 3 : 0);
+    p.nt_loads = k.nt_loads > 0 ? k.nt_loads : 0;   // forward: any non-zero = non-temporal row loads; sorted backward: 1 nt, 2 system scope
+    // lookups that do not divide evenly over the bags: certainly ragged (fixed-size requests -- every benchmark shape --
+    // always divide; a ragged request that happens to divide merely runs the unordered kernel)
+    // ... and only where the order can matter: with one bag per lane group (short-bag tiles) nothing is pulled
+    p.ordered = (s.uneven && p.bags_per_block > s.NG) ? 1 : 0;
+    return p;
+}
+static inline LaunchPlan plan_base(const pm_embbag_batch& op, int elem_dtype, const PlanKnobs& k) {
+    return plan_base(op, plan_shape(op, elem_dtype, k), k);
+}
+
+// ---- forward: the steps pm_embbag_fwd's plan takes from the base plan, in this order -------------------------------------------------
+// LDS-staged output: the tile's pooled rows leave in one burst at the end of the tile (embbag_fwd.hip).
+// Measured at benchmark size: uniform indices 0.69 -> 0.72-0.74 of the HBM peak in both output layouts, Zipf within
+// +-2 % -- provided the workgroup's LDS stays small (at 6 workgroups per CU the latency-bound Zipf launch lost 12 %):
+// so only for requests whose lookups divide evenly over the bags (fixed pooling: every benchmark shape), whose index
+// tile can then be sized for what a tile really holds instead of the 4096-entry default, and only where the staging
+// buffer fits 16 KB (the tile is halved until it does; an explicit bags_per_block -- sweeps -- is staged if it fits as it is).
+// pm_set_forward_tuning(0) / PARAM_AMD_FWD_STAGE=0 turn it off.
+static inline LaunchPlan with_burst_buffer(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k, LaunchPlan p) {
+    const bool auto_tile = k.bags_per_block <= 0;
+    if (k.stage && !p.ordered && s.even) {
+        const int bpb = auto_tile ? burst_tile(p.bags_per_block, s.NG, op.max_dim, 4) : p.bags_per_block;
+        const int64_t tiles = ceil_div(op.bag_count, bpb);
+        if (static_cast<int64_t>(bpb) * op.max_dim * 4 <= kBurstBytes && tiles * op.num_tables <= kMaxGrid) {
+            p.bags_per_block = bpb;
+            p.tiles_per_table = static_cast<int32_t>(tiles);
+            p.stage_out = op.max_dim;
+            const int64_t need = index_tile(bpb, s.avg_l, 512);
+            if (need < p.idx_cap) p.idx_cap = static_cast<int32_t>(need);
+        }
+    } else if (k.stage && !p.ordered && auto_tile && static_cast<int64_t>(p.bags_per_block) * op.max_dim * 4 <= 4096) {
+        // short-bag tiles of requests with per-table pooling (Criteo multi-hot: one bag per lane group, 8 bags per
+        // tile): the staging buffer is 4 KB, the full-size index tile stays -- 20.6 KB per workgroup
+        p.stage_out = op.max_dim;
+    }
+    p.stage_bags = p.bags_per_block;
+    return p;
+}
+
+// Short-bag requests run the flat-walk kernel (embbag_fwd.hip): tiles sized per table on the device (~256 lookups, up
+// to 32 bags for the pooling-1 tables), row loads in flight across bag borders.  tiles_per_table stays the count of the
+// smallest tile (one bag per lane group): workgroups past their table's tile count leave.  Criteo tables, visit
+// r3_criteo_flat (Zipf G lookups/s / uniform fraction; run-to-run +-1.5 %): 8-bag tiles 15.7-15.9 / 0.69-0.71; flat walk
+// target 512 cap 64: 16.4-16.5 / 0.705-0.716; **256 / 32: 16.6 / 0.719**; 128: 16.1 / 0.695; 1024 / 128: 14.1 / 0.64.
+// PARAM_AMD_FWD_FLAT=0 turns it off (PARAM_AMD_FLAT_TARGET / _BAGS: sweeps).
+// (Round 6: that cap of 32 bags was chosen under round 3's grid, where a larger cap also meant more surplus workgroups.  With
+// the compact launch a one-hot table's 32-bag tile is three round trips of set-up around 32 row loads; one process per setting,
+// three each, us uniform / Zipf: cap 32: 192-193 / 118; 64: 182 / 114; 128: 186 / 112; **256: 181 / 111.6**
+// -- profiles/r06_flat_bags_cap_sweep_all128.jsonl.  The cap is 256 bags on every flat-walk path now.)
+// Two kinds of request take it: ragged ones already on one bag per lane group with a staged tile (Criteo multi-hot), and
+// fixed-pooling requests of one or two lookups per bag (one-hot tables): bag by bag a lane group has one or
+// two row loads in flight.  48 x 10 M x 128 fp32, batch 65536 (tools/r3_shortbags.sh; Zipf G lookups/s / uniform fraction):
+// pooling 1: 4.00 / 0.529 -> 5.05 / 0.624; pooling 2: 7.78 / 0.687 -> 8.75 / 0.686; pooling 4: 13.5 / 0.723 -> 13.4 / 0.679
+// (not taken; PARAM_AMD_FWD_FLAT=2 extends the rule to 4 for that measurement).
+static inline LaunchPlan with_short_bag_flat_walk(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k, LaunchPlan p) {
+    if (!k.flat || p.ordered || k.bags_per_block > 0 || p.stage_out <= 0) return p;
+    const int64_t tiles_ng = ceil_div(op.bag_count, s.NG);
+    if (s.even && s.avg_l <= (k.flat_maxl > 0 ? k.flat_maxl : k.flat == 2 ? 4 : 2) && tiles_ng * op.num_tables <= kMaxGrid) {
+        p.flat_bags = flat_bag_cap(k.flat_bags, 32, s.NG);
+        p.flat_target = k.flat_target;
+        p.tiles_per_table = static_cast<int32_t>(tiles_ng);
+        p.stage_bags = s.NG;
+        p.bags_per_block = p.flat_bags;
+        if (p.idx_cap < 1024) p.idx_cap = 1024;
+    } else if (!s.even && p.bags_per_block == s.NG) {
+        p.flat_bags = flat_bag_cap(k.flat_bags, s.NG, s.NG);
+        p.flat_target = k.flat_target;
+        p.bags_per_block = p.flat_bags;   // sizes the LDS offsets array; stage_bags (the burst buffer) stays at NG rows
+    }
+    return p;
+}
+
+// ABI v7, mixed embedding dims (min_dim given and its lane group narrower than max_dim's): the flat-walk kernel sizes the lane
+// group PER TABLE on the device (embbag_fwd.hip), whatever the bags look like -- tiles are ~flat_target lookups of any pooling
+// factor.  Ragged requests keep the ordered kernel (longest bag first matters more there than idle lanes).
+static inline LaunchPlan with_mixed_dims(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k, LaunchPlan p) {
+    if (!k.flat || op.min_dim <= 0 || op.min_dim >= op.max_dim || p.ordered || k.bags_per_block > 0) return p;
+    int need = (op.min_dim + s.vec - 1) / s.vec, g_min = 4;          // sub-groups of 4 lanes at least: 64-byte pieces
+    while (g_min < need) g_min <<= 1;
+    const int64_t tiles_ng = ceil_div(op.bag_count, s.NG);             // the grid of the smallest tile: the widest table's NG bags
+    if (g_min >= s.G || tiles_ng * op.num_tables > kMaxGrid) return p;
+    const int ng_max = kBlock / g_min;                                 // bags the narrowest table's sub-groups pool at once (64 at most)
+    // 256 bags at most per tile (the LDS offsets array): a one-hot narrow table then reaches the ~flat_target lookups per tile the wide
+    // tables have -- its 64-bag tiles were three round trips of set-up around 4 KB of rows.  Criteo tables with mixed dims, one
+    // process per setting, two each: cap 64: 143.3-143.9 us, 128: 142.3-142.9, 256: 141.5-142.1; the narrow tables alone
+    // 24.3 -> 21.6 us: profiles/r06_flat_bags_cap_sweep.jsonl
+    if (p.flat_bags < 256) p.flat_bags = 256;
+    if (p.flat_target <= 0) p.flat_target = k.flat_target;
+    p.tiles_per_table = static_cast<int32_t>(tiles_ng);
+    p.bags_per_block = p.flat_bags;
+    p.stage_out = op.max_dim;                                          // (staged even with stage_out 0: the flat walk has no unstaged path)
+    p.stage_bags = s.NG;                                               // burst buffer: NG rows of max_dim floats (4 KB at D = 128 fp32)
+    // index tile: twice what a tile holds on average -- ~flat_target lookups, or the narrowest table's ng_max bags -- within [1024, 4096]
+    int64_t cap = index_tile(ng_max, s.avg_l, 1024);
+    if (cap < round256(2 * static_cast<int64_t>(p.flat_target))) cap = round256(2 * static_cast<int64_t>(p.flat_target));
+    p.idx_cap = static_cast<int32_t>(cap > 4096 ? 4096 : cap);
+    if (p.xcd_affine == 3) p.xcd_affine = 0;                           // eighths of the tile order assume equal tiles per table
+    return p;
+}
+
+// flat-walk launches are one resident set of workgroups walking the tile order (embbag_fwd.hip, round 6)
+static inline LaunchPlan with_compact_grid(const pm_embbag_batch& op, const PlanKnobs& k, LaunchPlan p) {
+    if (p.flat_bags <= 0 || op.num_tables > 1024 || k.flat_grid <= 0) return p;
+    // the tiles the request will have, from its sizes (the tables' own pooling factors are on the device): ~flat_target
+    // lookups each, but at most flat_bags bags; a quarter more, because a table's tile is its average bag count rounded DOWN
+    // to whole lane-group rounds
+    const int64_t n_slice = op.batch > 0 ? ceil_div(op.num_indices * op.bag_count, op.batch) : 0;
+    const int64_t by_lookups = ceil_div(n_slice, p.flat_target);
+    const int64_t by_bags = op.num_tables * ceil_div(op.bag_count, p.flat_bags);
+    int64_t est = (by_lookups > by_bags ? by_lookups : by_bags) * 5 / 4 + op.num_tables;
+    if (est < 1024) est = 1024;
+    if (est > (1 << 20)) est = 1 << 20;
+    p.flat_compact = k.flat_grid > 1 ? k.flat_grid : static_cast<int32_t>(est);
+    return p;
+}
+
+// Two tilings built and measured in round 3 for requests whose tables have very different pooling factors (Criteo
+// multi-hot 1 .. 100) -- both slower than the 8-bag tiles in table-major order, which stay:
+//  * WORK tiles (~640 lookups per tile whatever the pooling factor, tile boundaries derived on the device from the
+//    tables' lookup counts): 186 us against 120 us under Zipf, 249 against 185 us under uniform indices (caps of
+//    32 .. 1024 bags, targets of 320 .. 1280: all slower).  A pooling-1 bag is ONE row load; a lane group walking 16 ..
+//    128 of them in turn has one load in flight where 1024 eight-bag workgroups have them all in flight at once -- the
+//    small tiles ARE the memory-level parallelism.  Removed again (profiles/r03_criteo_fwd_work_tiles.txt).
+//  * tile-major block order (t = b % T, so every table advances at the same rate and the heavy table's long workgroups
+//    start throughout the launch): 165 against 120 us under Zipf, 220 against 186 us uniform -- a table's tiles then run
+//    on all eight XCDs at once and on every CU next to other tables' rows.  Kept behind PARAM_AMD_FWD_TILE_MAJOR=1.
+static inline LaunchPlan with_tile_major(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k, LaunchPlan p) {
+    if (p.xcd_affine != 1 && op.num_tables > 1 && k.tile_major > 0 && s.uneven) p.xcd_affine = 2;
+    return p;
+}
+
+// Row loads in flight per lane group when pm_set_tuning leaves the choice to the library.  Two is the measured optimum of a launch
+// that fills the chip (eight workgroups per CU: occupancy provides the memory-level parallelism).  A SMALL request -- the reference
+// driver's batch 512 .. 4096 rows of one 14 M x 128 table, train/compute/pt/dataset.py:56-82 -- has one or two workgroups per CU,
+// each lane group a chain of pooling / 2 dependent round trips: there a deeper batch IS the parallelism.  Additions stay in index
+// order: same bits for every value.
+static inline int small_request_unroll(const pm_embbag_batch& op, const PlanShape& s, const LaunchPlan& p) {
+    if (p.flat_bags > 0 || p.ordered) return kDefaultUnroll;
+    const int64_t wgs = static_cast<int64_t>(op.num_tables) * p.tiles_per_table;
+    const int64_t avg_l = s.total_bags > 0 ? op.num_indices / s.total_bags : 0;   // (rounded down)
+    // kernel us under rocprofv3 --kernel-trace (profiles/r06_small_batch_kernel_us.txt; batch 2 / 4 / 8): 64 workgroups 6.6 / 5.6 / 5.5,
+    // 128: 6.9 / 6.0 / 5.6, 256: 9.6 / 7.7 / 6.6, 512: 13.0 / 13.1 / 13.1, 1024: 22.4 / 22.6 / 23.1 -- it pays up to one workgroup per CU
+    if (wgs > 384) return kDefaultUnroll;
+    return avg_l >= 8 ? 8 : (avg_l >= 4 ? 4 : kDefaultUnroll);
+}
+
+static inline LaunchPlan forward_geometry(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k) {
+    LaunchPlan p = plan_base(op, s, k);
+    p = with_burst_buffer(op, s, k, p);
+    p = with_short_bag_flat_walk(op, s, k, p);
+    p = with_mixed_dims(op, s, k, p);
+    p = with_compact_grid(op, k, p);
+    return with_tile_major(op, s, k, p);
+}
+
+// ---- forward: pm_embbag_fwd -------------------------------------------------------------------------------------------------------
+static inline LaunchPlan plan_forward(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k) {
+    LaunchPlan p = forward_geometry(op, s, k);
+    p.unroll = k.unroll != 0 ? k.unroll : small_request_unroll(op, s, p);
+    return p;
+}
+static inline LaunchPlan plan_forward(const pm_embbag_batch& op, int elem_dtype, const PlanKnobs& k) {
+    return plan_forward(op, plan_shape(op, elem_dtype, k), k);
+}
+
+// ---- quantized: pm_embbag_fwd_quantized (it refuses a plan that is not staged) -----------------------------------------------------
+static inline LaunchPlan plan_quantized(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k) {
+    LaunchPlan p = forward_geometry(op, s, k);
+    if (p.flat_bags > 0) {   // the quantised burst lives in the bag-per-group kernel: back to its tiles of one bag per lane group
+        p.bags_per_block = p.stage_bags;
+        p.flat_bags = 0;
+    }
+    p.unroll = k.unroll != 0 ? k.unroll : kDefaultUnroll;
+    return p;
+}
+static inline LaunchPlan plan_quantized(const pm_embbag_batch& op, int elem_dtype, const PlanKnobs& k) {
+    return plan_quantized(op, plan_shape(op, elem_dtype, k), k);
+}
+
+// ---- padded: pm_embbag_fwd_padded, pm_embbag_fwd_mean (out_bytes 4) and pm_embbag_fwd_out16 (2) -------------------------------------
+// The padded forward keeps the plain bag-count tiling and adds the product forward's output burst where the tile's rows of
+// out_bytes-elements fit 16 KB (the tile is halved until they do; it only shrinks, so the base plan's grid check holds); requests whose
+// lookups divide evenly over the bags get an index tile sized for what a tile holds, as the product forward's do (a longer tile reads
+// its indices from the request).  The kernel has no ordered variant.
+static inline LaunchPlan plan_padded(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k, int out_bytes) {
+    LaunchPlan p = plan_base(op, s, k);
+    if (k.bags_per_block <= 0) p.bags_per_block = burst_tile(p.bags_per_block, s.NG, op.max_dim, out_bytes);
+    p.tiles_per_table = static_cast<int32_t>(ceil_div(op.bag_count, p.bags_per_block));
+    p.stage_out = (k.stage && static_cast<int64_t>(p.bags_per_block) * op.max_dim * out_bytes <= kBurstBytes) ? op.max_dim : 0;
+    p.stage_bags = p.bags_per_block;
+    if (s.even) {
+        const int64_t need = index_tile(p.bags_per_block, s.avg_l, 512);
+        if (need < p.idx_cap) p.idx_cap = static_cast<int32_t>(need);
+    }
+    p.ordered = 0;
+    return p;
+}
+static inline LaunchPlan plan_padded(const pm_embbag_batch& op, int elem_dtype, const PlanKnobs& k, int out_bytes) {
+    return plan_padded(op, plan_shape(op, elem_dtype, k), k, out_bytes);
+}
+
+}  // namespace pm
