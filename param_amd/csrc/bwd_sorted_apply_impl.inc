@@ -238,12 +238,8 @@ hipError_t launch_apply_w(const SortedParams& sp, hipStream_t stream) {
 
 template <typename DST, typename K>
 hipError_t launch_apply_g(const SortedParams& sp, int max_dim, hipStream_t stream) {
-    switch (group_lanes(max_dim, DST::kVec)) {
-        case 8: return launch_apply_w<DST, K, 8>(sp, stream);
-        case 16: return launch_apply_w<DST, K, 16>(sp, stream);
-        case 32: return launch_apply_w<DST, K, 32>(sp, stream);
-        default: return launch_apply_w<DST, K, 64>(sp, stream);
-    }
+    return dispatch_group_lanes(group_lanes(max_dim, DST::kVec),
+                                [&](auto g) { return launch_apply_w<DST, K, decltype(g)::value>(sp, stream); });
 }
 
 

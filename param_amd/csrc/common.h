@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
 
 #include "param_amd.h"
 #include "launch_plan.h"   // kBlock, kXcds, group_lanes: shared with the host's launch plans
@@ -119,32 +120,27 @@ __device__ __forceinline__ void block_to_tile(const KParams& p, int& t, int& til
     }
 }
 
-// Stage the tile's offsets (absolute, int64) and -- when the tile's index range fits --
+// LDS layout of a tile: int64 s_off[bags_per_block + 1] | int32 s_idx[idx_cap] | float s_w[idx_cap]
+// (the ONE definition of where the index tile starts: every kernel that stages a tile and every launcher that sizes its LDS
+// goes through these two)
+__host__ __device__ inline size_t tile_idx_offset(int bags_per_block) {
+    return (static_cast<size_t>(bags_per_block + 2) / 2 * 2) * sizeof(int64_t);
+}
+__host__ __device__ inline size_t tile_lds_bytes(int bags_per_block, int idx_cap, bool weighted) {
+    return tile_idx_offset(bags_per_block) + static_cast<size_t>(idx_cap) * 4 * (weighted ? 2 : 1);
+}
+
+// Stage the offsets of a tile given by its first bag and bag count and -- when the tile's index range fits --
 // its indices (narrowed to int32: rows[t] < 2^31 is the caller's contract, verified by pm_embbag_check and
 // by the Python modules) and per-sample
 // weights into LDS with coalesced loads.  Returns true if indices were staged.
-// LDS layout: int64 s_off[bags_per_block + 1] | int32 s_idx[idx_cap] | float s_w[idx_cap]
-template <bool WEIGHTED>
-__device__ __forceinline__ bool stage_tile_at(const KParams& p, int t, int64_t bag0, int nb, char* smem,
-                                              int64_t*& s_off, int32_t*& s_idx, float*& s_w);
-
-template <bool WEIGHTED>
-__device__ __forceinline__ bool stage_tile(const KParams& p, int t, int tile, char* smem, int& nb,
-                                           int64_t*& s_off, int32_t*& s_idx, float*& s_w) {
-    const int64_t bag0 = p.bag_begin + static_cast<int64_t>(tile) * p.bags_per_block;
-    const int64_t left = p.bag_begin + p.bag_count - bag0;
-    nb = left < p.bags_per_block ? static_cast<int>(left) : p.bags_per_block;
-    return stage_tile_at<WEIGHTED>(p, t, bag0, nb, smem, s_off, s_idx, s_w);
-}
-
-// the same for a tile given by its first bag and bag count (work tiles)
 template <bool WEIGHTED>
 __device__ __forceinline__ bool stage_tile_at(const KParams& p, int t, int64_t bag0, int nb, char* smem,
                                               int64_t*& s_off, int32_t*& s_idx, float*& s_w) {
     const int64_t g0 = static_cast<int64_t>(t) * p.B + bag0;
 
     s_off = reinterpret_cast<int64_t*>(smem);
-    s_idx = reinterpret_cast<int32_t*>(smem + (static_cast<size_t>(p.bags_per_block + 2) / 2 * 2) * sizeof(int64_t));
+    s_idx = reinterpret_cast<int32_t*>(smem + tile_idx_offset(p.bags_per_block));
     s_w = reinterpret_cast<float*>(s_idx + p.idx_cap);
 
     for (int i = threadIdx.x; i <= nb; i += kBlock) s_off[i] = bag_start_or_end(p, g0 + i);
@@ -162,9 +158,31 @@ __device__ __forceinline__ bool stage_tile_at(const KParams& p, int t, int64_t b
     return staged;
 }
 
-__host__ __device__ inline size_t tile_lds_bytes(int bags_per_block, int idx_cap, bool weighted) {
-    return (static_cast<size_t>(bags_per_block + 2) / 2 * 2) * sizeof(int64_t) +
-           static_cast<size_t>(idx_cap) * 4 * (weighted ? 2 : 1);
+// the same for tile `tile` of the plain bag-count tiling (the alternates' atomic backward)
+template <bool WEIGHTED>
+__device__ __forceinline__ bool stage_tile(const KParams& p, int t, int tile, char* smem, int& nb,
+                                           int64_t*& s_off, int32_t*& s_idx, float*& s_w) {
+    const int64_t bag0 = p.bag_begin + static_cast<int64_t>(tile) * p.bags_per_block;
+    const int64_t left = p.bag_begin + p.bag_count - bag0;
+    nb = left < p.bags_per_block ? static_cast<int>(left) : p.bags_per_block;
+    return stage_tile_at<WEIGHTED>(p, t, bag0, nb, smem, s_off, s_idx, s_w);
+}
+
+// ---- launcher ladders: a run-time lane-group width / flag becomes a template argument -------------------------------------
+// f(std::integral_constant<int, G>{}) for the group width `lanes` (group_lanes: 8 / 16 / 32 / 64)
+template <typename F>
+inline auto dispatch_group_lanes(int lanes, F&& f) {
+    switch (lanes) {
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        default: return f(std::integral_constant<int, 64>{});
+    }
+}
+// f(std::true_type{}) or f(std::false_type{})
+template <typename F>
+inline auto dispatch_bool(bool flag, F&& f) {
+    return flag ? f(std::true_type{}) : f(std::false_type{});
 }
 
 // ---- host-side launchers implemented in the kernel files ----------------------------------

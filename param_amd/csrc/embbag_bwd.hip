@@ -129,21 +129,16 @@ hipError_t launch_w(const KParams& p, hipStream_t stream) {
     const bool weighted = p.psw != nullptr;
     const int grid = p.T * p.tiles_per_table;
     const size_t lds = tile_lds_bytes(p.bags_per_block, p.idx_cap, weighted);
-    if (weighted)
-        hipLaunchKernelGGL((embbag_bwd_kernel<DST, G, true>), dim3(grid), dim3(kBlock), lds, stream, p);
-    else
-        hipLaunchKernelGGL((embbag_bwd_kernel<DST, G, false>), dim3(grid), dim3(kBlock), lds, stream, p);
+    dispatch_bool(weighted, [&](auto w) {
+        hipLaunchKernelGGL((embbag_bwd_kernel<DST, G, decltype(w)::value>), dim3(grid), dim3(kBlock), lds, stream, p);
+    });
     return hipGetLastError();
 }
 
 template <typename DST>
 hipError_t launch_g(const KParams& p, int max_dim, hipStream_t stream) {
-    switch (group_lanes(max_dim, DST::kVec)) {
-        case 8: return launch_w<DST, 8>(p, stream);
-        case 16: return launch_w<DST, 16>(p, stream);
-        case 32: return launch_w<DST, 32>(p, stream);
-        default: return launch_w<DST, 64>(p, stream);
-    }
+    return dispatch_group_lanes(group_lanes(max_dim, DST::kVec),
+                                [&](auto g) { return launch_w<DST, decltype(g)::value>(p, stream); });
 }
 
 }  // namespace

@@ -909,7 +909,7 @@ __global__ void __launch_bounds__(kBlock) bwd_unique_kernel(const SortedParams p
     const int nb = left_bags < q.bags_per_block ? static_cast<int>(left_bags) : q.bags_per_block;
     if (threadIdx.x == 0) s_next = NG;
     int64_t* s_off = reinterpret_cast<int64_t*>(smem);
-    uint32_t* s_idx = reinterpret_cast<uint32_t*>(smem + (static_cast<size_t>(q.bags_per_block + 2) / 2 * 2) * sizeof(int64_t));
+    uint32_t* s_idx = reinterpret_cast<uint32_t*>(smem + tile_idx_offset(q.bags_per_block));
     const int64_t g0 = static_cast<int64_t>(t) * q.B + bag0;
     for (int i = threadIdx.x; i <= nb; i += kBlock) s_off[i] = bag_start_or_end(q, g0 + i);
     __syncthreads();

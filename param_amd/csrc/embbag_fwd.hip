@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(kBlock) embbag_fwd_kernel(const KParams p) {
     const int64_t bag0 = p.bag_begin + static_cast<int64_t>(tile) * p.bags_per_block;
     const int64_t left_bags = p.bag_begin + p.bag_count - bag0;
     const int nb = left_bags < p.bags_per_block ? static_cast<int>(left_bags) : p.bags_per_block;
-    if (threadIdx.x == 0) s_next = NG;  // bags 0 .. NG-1 are taken statically; visible after stage_tile's barrier
+    if (threadIdx.x == 0) s_next = NG;  // bags 0 .. NG-1 are taken statically; visible after stage_tile_at's barrier
 
     int64_t* s_off;
     int32_t* s_idx;
@@ -198,6 +198,8 @@ __global__ void __launch_bounds__(kBlock) embbag_fwd_kernel(const KParams p) {
 #pragma unroll
                     for (int u = 0; u < UNROLL; ++u) raw[u] = load16(Wc + row_offset<ST>(r[u], row_bytes), nt);
 #pragma unroll
+                    // (fwd::accumulate, written out here and in the tail: called from either place it costs the weighted ordered
+                    // bf16 UNROLL = 4 instances a wave per SIMD, 72 -> 74 VGPRs -- profiles/fwd_refactor_isa.md)
                     for (int u = 0; u < UNROLL; ++u) {
                         float f[VEC];
                         Elem<WT>::widen(raw[u], f);
@@ -221,7 +223,7 @@ __global__ void __launch_bounds__(kBlock) embbag_fwd_kernel(const KParams p) {
                     for (int u = 0; u < UNROLL - 1; ++u) raw[u] = load16(Wc + row_offset<ST>(r[u], row_bytes), nt);
 #pragma unroll
                     for (int u = 0; u < UNROLL - 1; ++u) {
-                        if (j + u < e) {
+                        if (j + u < e) {                     // (fwd::accumulate again: see the batch loop)
                             float f[VEC];
                             Elem<WT>::widen(raw[u], f);
 #pragma unroll
@@ -255,17 +257,10 @@ __global__ void __launch_bounds__(kBlock) embbag_fwd_kernel(const KParams p) {
     if (STAGE && stage) {
         __syncthreads();
         if (p.out_bits == 0) {
-            const int q = D / 4;                       // 16-byte pieces per row
-            auto piece = [&](int bg, int c4) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(s_out + static_cast<size_t>(bg) * D + c4 * 4);
-                __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out_t + (bag0 + bg) * p.out_stride + c4 * 4));
-            };
-            if ((q & (q - 1)) == 0) {                  // piece i is (i >> lg, i & (q - 1)): no integer division per 16 bytes
-                const int lg = 31 - __builtin_clz(static_cast<unsigned>(q));
-                for (int i = threadIdx.x; i < nb * q; i += kBlock) piece(i >> lg, i & (q - 1));
-            } else {
-                for (int i = threadIdx.x; i < nb * q; i += kBlock) piece(i / q, i % q);
-            }
+            const int q = D / 4;
+            // (the division loop named first: in the other order the compiler inverts the benchmark instance's branch)
+            if ((q & (q - 1)) != 0) burst_rows<false>(s_out, out_t, bag0, p.out_stride, nb, D);
+            else burst_rows<true>(s_out, out_t, bag0, p.out_stride, nb, D);
         } else {
             quantized_burst(p, s_out, nb, D, bag0, p.out_offsets[t]);
         }
@@ -336,6 +331,8 @@ __global__ void __launch_bounds__(kBlock) embbag_fwd_flat_kernel(const KParams p
 
     auto do_tile = [&](int t, int tile, int D, int g, int bags) {
         const int NG = kBlock / g;                   // bags pooled concurrently by this workgroup
+        // (the tile extent, like fwd::accumulate and the sub-group width below, stays written out here: lifted into shared
+        // helpers they move the benchmark's flat instances off the measured code -- profiles/fwd_refactor_isa.md)
         const int64_t bag0 = p.bag_begin + static_cast<int64_t>(tile) * bags;
         const int64_t left_bags = p.bag_begin + p.bag_count - bag0;
         if (left_bags <= 0) return;
@@ -422,12 +419,7 @@ __global__ void __launch_bounds__(kBlock) embbag_fwd_flat_kernel(const KParams p
         }
         if (stage) {
             __syncthreads();
-            const int q = D / 4;
-            for (int i = threadIdx.x; i < nb * q; i += kBlock) {
-                const int bg = i / q, c4 = i % q;
-                const f32x4 v = *reinterpret_cast<const f32x4*>(s_out + static_cast<size_t>(bg) * D + c4 * 4);
-                __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out_t + (bag0 + bg) * p.out_stride + c4 * 4));
-            }
+            burst_rows(s_out, out_t, bag0, p.out_stride, nb, D);
         }
     };
 
@@ -490,7 +482,7 @@ __global__ void __launch_bounds__(kBlock) embbag_fwd_flat_kernel(const KParams p
 template <typename WT, int G, int UNROLL>
 hipError_t launch_w(const KParams& p, hipStream_t stream) {
     const bool weighted = p.psw != nullptr;
-    const int grid = p.T * p.tiles_per_table;
+    int grid = p.T * p.tiles_per_table;
     size_t lds = tile_lds_bytes(p.bags_per_block, p.idx_cap, weighted);
     if (p.flat_bags > 0) {   // short-bag requests with per-table pooling (capi.hip decides)
         lds += static_cast<size_t>(p.stage_bags) * p.stage_out * sizeof(float);
@@ -500,15 +492,14 @@ hipError_t launch_w(const KParams& p, hipStream_t stream) {
             // tiles' true count is on the device), so nearly every workgroup pools ONE tile and the dispatcher balances the load; where
             // the estimate falls short workgroups walk on (b + grid, ...), where it overshoots the surplus leaves after the prologue --
             // at the END of the dispatch order, behind no one
-            const int g2 = p.flat_compact < grid ? p.flat_compact : grid;
-            if (weighted) hipLaunchKernelGGL((embbag_fwd_flat_kernel<WT, G, UNROLL, true>), dim3(g2), dim3(kBlock), lds, stream, p);
-            else hipLaunchKernelGGL((embbag_fwd_flat_kernel<WT, G, UNROLL, false>), dim3(g2), dim3(kBlock), lds, stream, p);
-            return hipGetLastError();
+            if (p.flat_compact < grid) grid = p.flat_compact;
         }
-        if (weighted) hipLaunchKernelGGL((embbag_fwd_flat_kernel<WT, G, UNROLL, true>), dim3(grid), dim3(kBlock), lds, stream, p);
-        else hipLaunchKernelGGL((embbag_fwd_flat_kernel<WT, G, UNROLL, false>), dim3(grid), dim3(kBlock), lds, stream, p);
+        dispatch_bool(weighted, [&](auto w) {
+            hipLaunchKernelGGL((embbag_fwd_flat_kernel<WT, G, UNROLL, decltype(w)::value>), dim3(grid), dim3(kBlock), lds, stream, p);
+        });
         return hipGetLastError();
     }
+    // (spelled out in this order on purpose: the order of instantiation is the order of the kernels in the code object)
 #define PM_FWD(W_, O_, S_) hipLaunchKernelGGL((embbag_fwd_kernel<WT, G, UNROLL, W_, O_, S_>), dim3(grid), dim3(kBlock), lds, stream, p)
     if (p.stage_out && !p.ordered) {   // fixed-pooling requests (capi.hip decides)
         lds += static_cast<size_t>(p.bags_per_block) * p.stage_out * sizeof(float);   // stage_out = widest row (elements)
@@ -533,12 +524,8 @@ hipError_t launch_u(const KParams& p, int unroll, hipStream_t stream) {
 
 template <typename WT>
 hipError_t launch_g(const KParams& p, int max_dim, int unroll, hipStream_t stream) {
-    switch (group_lanes(max_dim, Elem<WT>::kVec)) {
-        case 8: return launch_u<WT, 8>(p, unroll, stream);
-        case 16: return launch_u<WT, 16>(p, unroll, stream);
-        case 32: return launch_u<WT, 32>(p, unroll, stream);
-        default: return launch_u<WT, 64>(p, unroll, stream);
-    }
+    return dispatch_group_lanes(group_lanes(max_dim, Elem<WT>::kVec),
+                                [&](auto g) { return launch_u<WT, decltype(g)::value>(p, unroll, stream); });
 }
 
 }  // namespace

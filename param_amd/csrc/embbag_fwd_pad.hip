@@ -1,7 +1,9 @@
 // param_amd/csrc/embbag_fwd_pad.hip -- batched EmbeddingBag(sum) forward with PADDING: a lookup whose index equals its table's
 // padding index contributes nothing (torch's nn.EmbeddingBag(padding_idx=...) rule; pm_embbag_fwd_padded, include/param_amd.h).
 //
-// A kernel family of its own: the product forward (embbag_fwd.hip) is not touched.  Same tiling -- one
+// A kernel family of its own next to the product forward (embbag_fwd.hip), built from the same device
+// pieces: element types, row loads, the accumulate step and the burst of a tile's rows come from fwd_elem.h, the LDS tile layout
+// from common.h.  Same tiling -- one
 // 256-thread workgroup owns `bags_per_block` consecutive bags of one table, a group of G lanes owns a bag, a lane keeps a
 // 16-byte column slice of the fp32 accumulator -- and the same arithmetic: additions in index order from +0.0, one fmaf per
 // kept lookup when weighted.  The result is therefore bit-identical to pm_embbag_fwd on the request with the padded lookups

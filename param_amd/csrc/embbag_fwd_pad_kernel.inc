@@ -60,7 +60,7 @@ __global__ void __launch_bounds__(kBlock) pad_fwd_kernel(const KParams p, const 
     else pad = pad_idx[t];
 
     int64_t* s_off = reinterpret_cast<int64_t*>(smem);
-    int32_t* s_idx = reinterpret_cast<int32_t*>(smem + (static_cast<size_t>(p.bags_per_block + 2) / 2 * 2) * sizeof(int64_t));
+    int32_t* s_idx = reinterpret_cast<int32_t*>(smem + tile_idx_offset(p.bags_per_block));
     float* s_w = reinterpret_cast<float*>(s_idx + p.idx_cap);
     uint16_t* s_pre = reinterpret_cast<uint16_t*>(smem + pad_pre_offset(p.bags_per_block, p.idx_cap, WEIGHTED));
     float* s_out = reinterpret_cast<float*>(smem + pad_out_offset(p.bags_per_block, p.idx_cap, WEIGHTED));
@@ -146,12 +146,7 @@ __global__ void __launch_bounds__(kBlock) pad_fwd_kernel(const KParams p, const 
 #pragma unroll
             for (int k = 0; k < VEC; ++k) acc[k] = 0.0f;
             int64_t kept = 0;                  // MEAN: the bag's kept lookups (staged: e - s, set below)
-            auto add = [&](const u32x4& raw, float w) {
-                float f[VEC];
-                Elem<WT>::widen(raw, f);
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) acc[k] = WEIGHTED ? fmaf(w, f[k], acc[k]) : acc[k] + f[k];
-            };
+            auto add = [&](const u32x4& raw, float w) { accumulate<WT, WEIGHTED>(acc, raw, w); };
             if (staged) {
                 // dense list in LDS: the product forward's loop
                 int j = static_cast<int>(s);
@@ -233,16 +228,15 @@ __global__ void __launch_bounds__(kBlock) pad_fwd_kernel(const KParams p, const 
     }
     if (burst) {
         __syncthreads();
-        const int q = D / 4;                   // pieces of 4 outputs per row: 16 bytes (fp32 output), 8 bytes (16-bit output)
-        for (int i = threadIdx.x; i < nb * q; i += kBlock) {
-            const int bg = i / q, c4 = i % q;
-            if constexpr (OUT16) {
+        if constexpr (OUT16) {
+            const int q = D / 4;               // 8-byte pieces of 4 outputs per row
+            for (int i = threadIdx.x; i < nb * q; i += kBlock) {
+                const int bg = i / q, c4 = i % q;
                 const u32x2 v = *reinterpret_cast<const u32x2*>(s_out16 + static_cast<size_t>(bg) * D + c4 * 4);
                 __builtin_nontemporal_store(v, reinterpret_cast<u32x2*>(out16_t + (bag0 + bg) * p.out_stride + c4 * 4));
-            } else {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(s_out + static_cast<size_t>(bg) * D + c4 * 4);
-                __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out_t + (bag0 + bg) * p.out_stride + c4 * 4));
             }
+        } else {
+            burst_rows(s_out, out_t, bag0, p.out_stride, nb, D);
         }
     }
 }
@@ -260,20 +254,18 @@ hipError_t launch_pad_w(const KParams& p0, const int64_t* pad_idx, hipStream_t s
         p.stage_out = 0;
         lds = tile_lds;
     }
-    if constexpr (MEAN) hipLaunchKernelGGL((pad_fwd_kernel<WT, G, false, true, OT>), dim3(grid), dim3(kBlock), lds, stream, p, pad_idx);
-    else if (weighted) hipLaunchKernelGGL((pad_fwd_kernel<WT, G, true, false, OT>), dim3(grid), dim3(kBlock), lds, stream, p, pad_idx);
-    else hipLaunchKernelGGL((pad_fwd_kernel<WT, G, false, false, OT>), dim3(grid), dim3(kBlock), lds, stream, p, pad_idx);
+    auto launch = [&](auto w) {
+        hipLaunchKernelGGL((pad_fwd_kernel<WT, G, decltype(w)::value, MEAN, OT>), dim3(grid), dim3(kBlock), lds, stream, p, pad_idx);
+    };
+    if constexpr (MEAN) launch(std::false_type{});   // (mean is unweighted: no WEIGHTED + MEAN instance)
+    else dispatch_bool(weighted, launch);
     return hipGetLastError();
 }
 
 template <typename WT, bool MEAN, typename OT>
 hipError_t launch_pad_g(const KParams& p, int max_dim, const int64_t* pad_idx, hipStream_t stream) {
-    switch (group_lanes(max_dim, Elem<WT>::kVec)) {
-        case 8: return launch_pad_w<WT, 8, MEAN, OT>(p, pad_idx, stream);
-        case 16: return launch_pad_w<WT, 16, MEAN, OT>(p, pad_idx, stream);
-        case 32: return launch_pad_w<WT, 32, MEAN, OT>(p, pad_idx, stream);
-        default: return launch_pad_w<WT, 64, MEAN, OT>(p, pad_idx, stream);
-    }
+    return dispatch_group_lanes(group_lanes(max_dim, Elem<WT>::kVec),
+                                [&](auto g) { return launch_pad_w<WT, decltype(g)::value, MEAN, OT>(p, pad_idx, stream); });
 }
 
 // the 16-bit-output variants of one table dtype (one translation unit each): 4 group widths x {plain, weighted, mean} x {bf16, fp16}

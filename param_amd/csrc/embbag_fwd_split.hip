@@ -12,45 +12,20 @@
 // The order of the additions is fixed (deterministic) but it is not the sequential order: results agree with the
 // sequential sum to fp32 rounding (tests: 1e-5 relative to sum |row|), not bit for bit -- which is why this is a separate,
 // explicitly requested entry point (pm_embbag_fwd_split) and the default stays the bit-exact kernel.
+// Element types and the accumulate step are the forward family's (fwd_elem.h).
 #include "common.h"
+#include "fwd_elem.h"
 
 namespace pm {
 namespace {
 
-constexpr int kIdxChunk = 2048;  // indices of the bag staged in LDS per round
+using namespace fwd;
 
-struct sbf16_t { uint16_t v; };
-struct sf16_t { uint16_t v; };
-template <typename WT> struct SElem;
-template <> struct SElem<float> {
-    static constexpr int kVec = 4;
-    __device__ static __forceinline__ void widen(const u32x4& raw, float (&f)[4]) {
-        f[0] = __uint_as_float(raw.x); f[1] = __uint_as_float(raw.y); f[2] = __uint_as_float(raw.z); f[3] = __uint_as_float(raw.w);
-    }
-};
-template <> struct SElem<sbf16_t> {
-    static constexpr int kVec = 8;
-    __device__ static __forceinline__ void widen(const u32x4& raw, float (&f)[8]) {
-        const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(w[i] << 16); f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-    }
-};
-template <> struct SElem<sf16_t> {
-    static constexpr int kVec = 8;
-    __device__ static __forceinline__ void widen(const u32x4& raw, float (&f)[8]) {
-        const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            f[2 * i] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(w[i] & 0xffffu)));
-            f[2 * i + 1] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(w[i] >> 16)));
-        }
-    }
-};
+constexpr int kIdxChunk = 2048;  // indices of the bag staged in LDS per round
 
 template <typename WT, int G, bool WEIGHTED>
 __global__ void __launch_bounds__(kBlock) embbag_fwd_split_kernel(const KParams p) {
-    constexpr int VEC = SElem<WT>::kVec;
+    constexpr int VEC = Elem<WT>::kVec;
     constexpr int NG = kBlock / G;
     constexpr int UNROLL = 4;
     constexpr int ES = 16 / VEC;
@@ -100,12 +75,7 @@ __global__ void __launch_bounds__(kBlock) embbag_fwd_split_kernel(const KParams 
                     }
 #pragma unroll
                     for (int u = 0; u < UNROLL; ++u) {
-                        if (j + u * NG < n) {
-                            float f[VEC];
-                            SElem<WT>::widen(raw[u], f);
-#pragma unroll
-                            for (int k = 0; k < VEC; ++k) acc[k] = WEIGHTED ? fmaf(w[u], f[k], acc[k]) : acc[k] + f[k];
-                        }
+                        if (j + u * NG < n) accumulate<WT, WEIGHTED>(acc, raw[u], WEIGHTED ? w[u] : 1.0f);
                     }
                 }
             }
@@ -145,21 +115,16 @@ template <typename WT, int G>
 hipError_t launch_w(const KParams& p, hipStream_t stream) {
     const int64_t grid = static_cast<int64_t>(p.T) * p.bag_count;
     if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (p.psw)
-        hipLaunchKernelGGL((embbag_fwd_split_kernel<WT, G, true>), dim3(static_cast<unsigned>(grid)), dim3(kBlock), 0, stream, p);
-    else
-        hipLaunchKernelGGL((embbag_fwd_split_kernel<WT, G, false>), dim3(static_cast<unsigned>(grid)), dim3(kBlock), 0, stream, p);
+    dispatch_bool(p.psw != nullptr, [&](auto w) {
+        hipLaunchKernelGGL((embbag_fwd_split_kernel<WT, G, decltype(w)::value>), dim3(static_cast<unsigned>(grid)), dim3(kBlock), 0, stream, p);
+    });
     return hipGetLastError();
 }
 
 template <typename WT>
 hipError_t launch_g(const KParams& p, int max_dim, hipStream_t stream) {
-    switch (group_lanes(max_dim, SElem<WT>::kVec)) {
-        case 8: return launch_w<WT, 8>(p, stream);
-        case 16: return launch_w<WT, 16>(p, stream);
-        case 32: return launch_w<WT, 32>(p, stream);
-        default: return launch_w<WT, 64>(p, stream);
-    }
+    return dispatch_group_lanes(group_lanes(max_dim, Elem<WT>::kVec),
+                                [&](auto g) { return launch_w<WT, decltype(g)::value>(p, stream); });
 }
 
 }  // namespace
@@ -167,8 +132,8 @@ hipError_t launch_g(const KParams& p, int max_dim, hipStream_t stream) {
 hipError_t launch_embbag_fwd_split(const KParams& p, int weight_dtype, int max_dim, hipStream_t stream) {
     switch (weight_dtype) {
         case PM_F32: return launch_g<float>(p, max_dim, stream);
-        case PM_BF16: return launch_g<sbf16_t>(p, max_dim, stream);
-        default: return launch_g<sf16_t>(p, max_dim, stream);
+        case PM_BF16: return launch_g<bf16_t>(p, max_dim, stream);
+        default: return launch_g<f16_t>(p, max_dim, stream);
     }
 }
 

@@ -92,7 +92,7 @@ __global__ void __launch_bounds__(kBlock) embbag_psw_grad_kernel(const KParams p
     constexpr int ES = 16 / VEC;   // bytes per table element
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int64_t* const s_off = reinterpret_cast<int64_t*>(smem);
-    int32_t* const s_idx = reinterpret_cast<int32_t*>(smem + (static_cast<size_t>(p.bags_per_block + 2) / 2 * 2) * sizeof(int64_t));
+    int32_t* const s_idx = reinterpret_cast<int32_t*>(smem + tile_idx_offset(p.bags_per_block));
     float* const s_val = reinterpret_cast<float*>(s_idx + p.idx_cap);
     int* const s_pref = reinterpret_cast<int*>(smem + (tile_lds_bytes(p.bags_per_block, p.idx_cap, true) + 15) / 16 * 16);
     uint16_t* const s_bags = reinterpret_cast<uint16_t*>(s_pref + p.T + 1);

@@ -1,4 +1,8 @@
-// param_amd/csrc/fwd_elem.h -- element types and row-load helpers of the forward kernels (embbag_fwd.hip).  gfx950 only.
+// param_amd/csrc/fwd_elem.h -- the device building blocks of the forward kernel families (embbag_fwd.hip, embbag_fwd_split.hip,
+// embbag_fwd_pad_kernel.inc) and of the per_sample_weights gradient (embbag_psw_grad.hip): element types, row loads, the
+// accumulate step and the burst of a tile's rows.  embbag_fwd.hip still spells the accumulate step out and says why at the
+// spot: the compiler's output for these kernels moves with WHERE an expression is written, and a call that took a measured
+// kernel off its code, or an instance to another waves-per-SIMD step, was not made (profiles/fwd_refactor_isa.md).  gfx950 only.
 #pragma once
 
 #include "common.h"
@@ -51,6 +55,34 @@ template <bool ST>
 __device__ __forceinline__ int64_t row_offset(int64_t r, int64_t row_bytes) {
     if (ST) return static_cast<int64_t>(static_cast<uint64_t>(static_cast<uint32_t>(r)) * static_cast<uint32_t>(row_bytes));
     return r * row_bytes;
+}
+
+// one lookup joins the sum: the row's 16 bytes widened to fp32, then one add -- or one fmaf when weighted -- per element
+template <typename WT, bool WEIGHTED>
+__device__ __forceinline__ void accumulate(float (&acc)[Elem<WT>::kVec], const u32x4& raw, float w) {
+    constexpr int VEC = Elem<WT>::kVec;
+    float f[VEC];
+    Elem<WT>::widen(raw, f);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) acc[k] = WEIGHTED ? fmaf(w, f[k], acc[k]) : acc[k] + f[k];
+}
+
+// The tile's nb pooled fp32 rows of D floats leave the burst buffer together, 16 bytes per lane and step (call after a barrier).
+// POW2: the caller has found a row to be a power-of-two number of pieces, and piece i is (i >> lg, i & (q - 1)) -- no integer
+// division per 16 bytes; a compile-time choice that only embbag_fwd_kernel makes.
+template <bool POW2 = false>
+__device__ __forceinline__ void burst_rows(const float* s_out, float* out_t, int64_t bag0, int64_t out_stride, int nb, int D) {
+    const int q = D / 4;                       // 16-byte pieces per row
+    auto piece = [&](int bg, int c4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(s_out + static_cast<size_t>(bg) * D + c4 * 4);
+        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(out_t + (bag0 + bg) * out_stride + c4 * 4));
+    };
+    if (POW2) {
+        const int lg = 31 - __builtin_clz(static_cast<unsigned>(q));
+        for (int i = threadIdx.x; i < nb * q; i += kBlock) piece(i >> lg, i & (q - 1));
+    } else {
+        for (int i = threadIdx.x; i < nb * q; i += kBlock) piece(i / q, i % q);
+    }
 }
 
 }  // namespace fwd
