@@ -499,6 +499,34 @@ int pm_embbag_grad_widen(const pm_embbag_batch* op, const int64_t* padding_idx, 
                          float* grad32, pm_stream_t stream);
 
 /*
+ * UN-POOLED LOOKUPS -- torch's nn.Embedding rule (fbgemm TBE: PoolingMode.NONE, sequence embeddings): one output row per lookup.  For
+ * every lookup position j in [0, num_indices) that belongs to a bag inside [bag_begin, bag_begin + bag_count) of its table t
+ *     out[j * out_row_stride + c] = conv(table_t[indices[j], c])      for c < dims[t]
+ * and nothing else of `out` is touched: not the columns from dims[t] to out_row_stride, not the rows of positions outside the slice.
+ * Table t owns the positions [offsets[t * batch], offsets[(t + 1) * batch]), the last table ends at num_indices (the borders the
+ * pooled entry points use); the bags inside a table matter for the slice only.  out_offsets and out_stride of the request are not
+ * read: `out` is addressed by position, with its own row stride, in elements of out_dtype.  tests/embedding_rules.py restates the rule.
+ *   conv   same element type in and out (PM_F32 -> PM_F32, PM_BF16 -> PM_BF16, PM_F16 -> PM_F16): a bit copy -- -0.0, subnormals, Inf
+ *          and NaN payloads leave exactly as stored, no arithmetic touches the value (the bag-of-one route through pm_embbag_fwd adds
+ *          the row to +0.0, which turns -0.0 into +0.0, and always widens to fp32);
+ *          a 16-bit table with out_dtype PM_F32: the exact widening of every pooled forward;
+ *          an fp32 table with a 16-bit out_dtype, and bf16 <-> fp16: widened exactly, then rounded ONCE as pm_embbag_fwd_out16 rounds
+ *          (OUTPUT DTYPE above; tests/out16_rules.py).
+ * One launch for any number of tables (csrc/embedding_gather.hip): a tile is 256 consecutive positions, whatever tables they belong
+ * to; a lane group moves one row with 16-byte loads and non-temporal stores, several rows in flight.  Tables fp32 / bf16 / fp16,
+ * indices int32 / int64, dims[t] may differ per table.  No atomics, no workspace, no allocation, stream-ordered.
+ * Refused on the host, before any HIP call: what pm_embbag_fwd refuses; an unknown out_dtype, a NULL out with num_indices > 0, an out
+ * that is not 16-byte (PM_F32) / 8-byte (16-bit) aligned, out_row_stride < max_dim or not a multiple of 4 (PM_ERR_INVALID);
+ * per_sample_weights != NULL, a non-zero table_group / grad_block_shift / grad_block_extra (PM_ERR_UNSUPPORTED).  num_indices == 0 or
+ * bag_count == 0 is PM_OK without a launch.  The gradient needs no call of its own: it is the sum backward of the request "one bag per
+ * lookup" (offsets = 0, 1, 2, ..; batch = num_indices) on the gradient rows.
+ * Replaces aten::embedding behind nn.Embedding (the un-pooled sibling of the module at train/compute/pt/pytorch_emb.py:179) and
+ * PoolingMode.NONE of fbgemm's TBE forward (split_table_batched_embeddings_ops.py:290 names the pooling mode).
+ * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs this call finds out at symbol resolution.
+ */
+int pm_embedding_gather(const pm_embbag_batch* op, int32_t out_dtype, void* out, int64_t out_row_stride, pm_stream_t stream);
+
+/*
  * DLRM input redistribution on the device: regroup what the lengths / indices all-to-alls deliver
  * (train/comms/pt/dlrm.py:744-855) -- lengths [world][num_tables][batch] int64 and the indices
  * concatenated block by block in that (rank, table) order -- into the TBE request of the batched

@@ -80,6 +80,7 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_mean_grad",
     "pm_embbag_fwd_out16",
     "pm_embbag_grad_widen",
+    "pm_embedding_gather",
 )
 
 
@@ -271,6 +272,9 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embbag_fwd_out16.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, i32, vp, vp]
     L.pm_embbag_grad_widen.restype = ctypes.c_int
     L.pm_embbag_grad_widen.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, i32, vp, vp, vp]
+    # un-pooled rows: (op, PM_F32 | PM_BF16 | PM_F16, out, out_row_stride, stream)
+    L.pm_embedding_gather.restype = ctypes.c_int
+    L.pm_embedding_gather.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, vp, i64, vp]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]

@@ -553,6 +553,30 @@ int pm_embbag_grad_widen(const pm_embbag_batch* op, const int64_t* padding_idx, 
     return PM_OK;
 }
 
+// ---- un-pooled rows (embedding_gather.hip) ---------------------------------------------------------------------------------------------
+int pm_embedding_gather(const pm_embbag_batch* op, int32_t out_dtype, void* out, int64_t out_row_stride, pm_stream_t stream) {
+    pm::KParams p;
+    int rc = make_params(op, op ? op->weight_dtype : -1, p);      // (what pm_embbag_fwd refuses; the base plan's geometry is not used)
+    if (rc != PM_OK) return rc;
+    if (!dtype_is_weight(out_dtype)) return fail(PM_ERR_INVALID, "out_dtype must be PM_F32, PM_BF16 or PM_F16");
+    if (op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "un-pooled rows are unweighted: per_sample_weights must be NULL");
+    if (op->table_group != 0 || op->grad_block_shift != 0 || op->grad_block_extra != 0)
+        return fail(PM_ERR_UNSUPPORTED, "un-pooled rows do not take blocked layouts (table_group / grad_block_shift / grad_block_extra must be 0)");
+    if (out_row_stride < op->max_dim || out_row_stride % 4 != 0)
+        return fail(PM_ERR_INVALID, "out_row_stride must be a multiple of 4 elements and at least max_dim");
+    if (!out && op->num_indices > 0) return fail(PM_ERR_INVALID, "out is NULL");
+    const uintptr_t align = out_dtype == PM_F32 ? 16 : 8;
+    if (reinterpret_cast<uintptr_t>(out) % align != 0) return fail(PM_ERR_INVALID, "out must be " + std::to_string(align) + "-byte aligned");
+    if (op->num_indices == 0 || op->bag_count == 0) return PM_OK;
+    const pm::GatherPlan g = pm::plan_gather(*op, op->weight_dtype, current_knobs());
+    if (g.grid > pm::kMaxGrid) return fail(PM_ERR_UNSUPPORTED, "grid too large");
+    p.io = static_cast<float*>(out);           // (addressed in out_dtype's elements)
+    p.out_stride = out_row_stride;
+    const hipError_t h = pm::launch_embedding_gather(p, op->weight_dtype, out_dtype, g, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embedding_gather launch");
+    return PM_OK;
+}
+
 static int pad_guard_layout(int32_t num_tables, int32_t max_dim, int32_t table_dtype, int32_t state_kind, int64_t& row_slot, int64_t& slot) {
     if (num_tables < 1) return fail(PM_ERR_INVALID, "num_tables must be >= 1");
     if (!dtype_is_weight(table_dtype)) return fail(PM_ERR_INVALID, "weight/dst dtype must be PM_F32, PM_BF16 or PM_F16");

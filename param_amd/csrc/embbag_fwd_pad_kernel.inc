@@ -12,21 +12,7 @@
 
 using namespace fwd;
 
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-// fp32 -> 16 bits, round to nearest even; overflow to +-Inf, subnormals produced, signed zeros kept, NaN -> a quiet NaN of its sign
-struct OutBF16 {
-    __device__ static __forceinline__ uint32_t round(float f) {
-        const uint32_t u = __float_as_uint(f);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;      // (the convention of the sorted apply's f32_to_bf16_rne)
-        return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-    }
-};
-struct OutF16 {
-    __device__ static __forceinline__ uint32_t round(float f) {
-        return __builtin_bit_cast(uint16_t, static_cast<_Float16>(f));      // v_cvt_f16_f32: the hardware conversion
-    }
-};
+// (OutBF16 / OutF16 -- the one rounding -- and u32x2, the 8-byte piece of 4 outputs, live in fwd_elem.h: the row gather shares them)
 
 constexpr int kPadUnroll = 2;              // row loads in flight per lane group
 constexpr int kPadWaves = kBlock / kWave;

@@ -1,6 +1,6 @@
 // param_amd/csrc/fwd_elem.h -- the device building blocks of the forward kernel families (embbag_fwd.hip, embbag_fwd_split.hip,
-// embbag_fwd_pad_kernel.inc) and of the per_sample_weights gradient (embbag_psw_grad.hip): element types, row loads, the
-// accumulate step and the burst of a tile's rows.  embbag_fwd.hip still spells the accumulate step out and says why at the
+// embbag_fwd_pad_kernel.inc), of the per_sample_weights gradient (embbag_psw_grad.hip) and of the un-pooled row gather
+// (embedding_gather.hip): element types, the 16-bit output elements, row loads, the accumulate step and the burst of a tile's rows.  embbag_fwd.hip still spells the accumulate step out and says why at the
 // spot: the compiler's output for these kernels moves with WHERE an expression is written, and a call that took a measured
 // kernel off its code, or an instance to another waves-per-SIMD step, was not made (profiles/fwd_refactor_isa.md).  gfx950 only.
 #pragma once
@@ -41,6 +41,23 @@ template <> struct Elem<f16_t> {
             f[2 * i] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(w[i] & 0xffffu)));
             f[2 * i + 1] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(w[i] >> 16)));
         }
+    }
+};
+
+// A 16-bit OUTPUT element (the padded forward's OT, embbag_fwd_pad_kernel.inc; the row gather's, embedding_gather.hip):
+// fp32 -> 16 bits, round to nearest even; overflow to +-Inf, subnormals produced, signed zeros kept, NaN -> a quiet NaN of its sign.
+// Four outputs leave as one 8-byte piece (u32x2): what the alignment rules of a request guarantee.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+struct OutBF16 {
+    __device__ static __forceinline__ uint32_t round(float f) {
+        const uint32_t u = __float_as_uint(f);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;      // (the convention of the sorted apply's f32_to_bf16_rne)
+        return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    }
+};
+struct OutF16 {
+    __device__ static __forceinline__ uint32_t round(float f) {
+        return __builtin_bit_cast(uint16_t, static_cast<_Float16>(f));      // v_cvt_f16_f32: the hardware conversion
     }
 };
 

@@ -372,4 +372,46 @@ static inline LaunchPlan plan_padded(const pm_embbag_batch& op, int elem_dtype, 
     return plan_padded(op, plan_shape(op, elem_dtype, k), k, out_bytes);
 }
 
+// ---- gather: pm_embedding_gather (embedding_gather.hip) -- un-pooled rows, one output row per lookup POSITION ---------------------------
+// A tile is kBlock consecutive positions of the index array, whatever tables they belong to: the output is addressed by position, so
+// nothing about a tile depends on bags.  A lane group moves one row at a time and owns kBlock / NG = G of the tile's positions.
+// Rows a lane group keeps in flight (two batches of that many ping-pong, embedding_gather.hip).  Nothing depends on a loaded row but its
+// own store, so the forward's optimum (kDefaultUnroll = 2) does not carry over: the deepest batch wins although it runs on 230
+// registers and two waves per SIMD.  tools/gather_probe.py, 16 x 10 M x 128, 2.6 M lookups, us per call, medians of 5 windows of one
+// process, spread <= 1 % (profiles/gather_probe.json); unroll 1 / 2 / 4 / 8:
+//   fp32 -> fp32, uniform indices 517.9 / 505.3 / 493.6 / 486.9      Zipf 366.8 / 356.9 / 346.2 / 338.9
+//   bf16 -> bf16, uniform indices 252.2 / 245.1 / 241.1 / 239.8      Zipf 181.3 / 175.4 / 171.9 / 160.5
+// (the pooled forward of the same rows as bags of one: 557.6 / 394.6 / 402.2 / 408.5 us; an earlier visit, with 4 as the default, ordered
+// the four values the same way in every case)
+constexpr int kGatherUnroll = 8;
+constexpr int kGatherLdsBorders = kBlock;   // T + 1 table borders are staged in LDS up to this many (one load per thread), searched in global memory beyond
+struct GatherPlan {
+    int32_t vec;             // table elements per 16-byte load
+    int32_t group_lanes;     // G: lanes that move one row
+    int32_t tile;            // positions per workgroup (= kBlock: the tile's indices are one coalesced load, one per lane)
+    int32_t col_passes;      // passes of G * vec columns over the widest row (fp32 D > 256: more than one)
+    int32_t unroll;          // rows in flight per lane group: 1, 2, 4 or 8 (divides G)
+    int32_t lds_borders;     // 1: the T + 1 table borders are staged in LDS; 0: every position searches them in global memory
+    int32_t xcd_contiguous;  // 1: XCD x serves the x-th eighth of the tile order (a table's rows meet in one or two L2s)
+    int64_t grid;            // workgroups: ceil(num_indices / tile), every position in exactly one
+};
+// block -> tile, host and device (constexpr): the identity, or common.h's xcd_contiguous_tile -- a bijection of [0, total) for any total
+constexpr int64_t gather_block_tile(int64_t bid, int64_t total, bool xcd_contiguous) {
+    return !xcd_contiguous ? bid : (bid % kXcds) * (total / kXcds) + ((bid % kXcds) < (total % kXcds) ? (bid % kXcds) : (total % kXcds)) + bid / kXcds;
+}
+static inline GatherPlan plan_gather(const pm_embbag_batch& op, int elem_dtype, const PlanKnobs& k) {
+    GatherPlan g = {};
+    g.vec = (elem_dtype == PM_F32) ? 4 : 8;
+    g.group_lanes = group_lanes(op.max_dim, g.vec);
+    g.tile = kBlock;
+    g.col_passes = static_cast<int32_t>(ceil_div(op.max_dim, static_cast<int64_t>(g.group_lanes) * g.vec));
+    // pm_set_tuning's unroll (1, 2, 3, 4, 6, 8) rounded down to a divisor of every group width
+    const int u = k.unroll != 0 ? k.unroll : kGatherUnroll;
+    g.unroll = u >= 8 ? 8 : (u >= 4 ? 4 : (u >= 2 ? 2 : 1));
+    g.lds_borders = op.num_tables + 1 <= kGatherLdsBorders ? 1 : 0;
+    g.xcd_contiguous = (op.num_tables > 1 && k.xcd_affine != 0) ? 1 : 0;
+    g.grid = ceil_div(op.num_indices, g.tile);
+    return g;
+}
+
 }  // namespace pm

@@ -8,7 +8,9 @@
   ``fbgemm_gpu.SplitTableBatchedEmbeddingBagsCodegen`` (``comms_utils.py:1994-2017``,
   ``pytorch_dist_backend.py:221,845-857``, ``split_table_batched_embeddings_ops.py:279-324``):
   ``forward(indices, offsets, per_sample_weights)`` -> ``[B, sum D]``; ``backward`` applies the
-  fused in-place scatter-add update (plain SGD form).
+  fused in-place scatter-add update (plain SGD form); ``lookup_sequence`` -> ``[N, D]``, fbgemm's un-pooled (sequence) forward.
+* :class:`EmbeddingMI355`         -- drop-in for ``torch.nn.Embedding(n, m)``, the un-pooled sibling: ``forward(input)`` ->
+  ``[*input.shape, m]``.
 
 PyTorch is plumbing here (device memory, streams, autograd glue); all arithmetic runs in the
 hand-written HIP kernels behind the C ABI (include/param_amd.h).  There is no CPU path: a
@@ -352,6 +354,31 @@ def _fwd_quantized(ts: _TableSet, indices, offsets, B, bitwidth: int, psw=None, 
         quant.quantize_rows(full, D, bitwidth, out=out)
         return out
     _lib.check(rc)
+    return out
+
+
+def _check_rows_out(out: torch.Tensor, n: int, D: int, odt: torch.dtype, device) -> None:
+    """a caller's ``out`` of the un-pooled lookup: contiguous ``[n, D]`` of ``odt`` on ``device`` (checked before anything runs)"""
+    if out.dtype != odt or tuple(out.shape) != (n, D) or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"out must be a contiguous {str(odt).replace('torch.', '')} tensor of shape {(n, D)} on {device}")
+
+
+def _gather(ts: _TableSet, indices, offsets, B, odt: torch.dtype, out=None, bag_begin=0, bag_count=None) -> torch.Tensor:
+    """Un-pooled rows (``pm_embedding_gather``): ``[N, D]`` of ``odt``, row ``j`` = row ``indices[j]`` of the table that owns position
+    ``j`` -- the stored bits when ``odt`` is the tables' dtype, widened exactly or rounded once otherwise.  Needs one common embedding
+    dim.  With a batch slice only the rows of positions inside it are written: a caller's ``out`` keeps the others, a tensor
+    allocated here holds zeros there.  No launch for an empty request."""
+    D, n = ts.dims[0], indices.numel()
+    op = ts.request(indices, offsets, B, None, bag_begin, bag_count)
+    if out is None:
+        whole = bag_begin == 0 and bag_count in (None, B)
+        out = (torch.empty if whole else torch.zeros)((n, D), dtype=odt, device=ts.device)
+    else:
+        _check_rows_out(out, n, D, odt, ts.device)
+    if n:
+        rc = _lib.load().pm_embedding_gather(ctypes.byref(op), _WDTYPE[odt], out.data_ptr(), D, _stream_ptr())
+        if rc:
+            _lib.check(rc)
     return out
 
 
@@ -1060,6 +1087,158 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
                 (f", output_dtype={self.output_dtype}" if self._out16 is not None else ""))
 
 
+class _EmbeddingGradFn(torch.autograd.Function):
+    """forward = the un-pooled lookup (``pm_embedding_gather``); backward = the SUM backward of the derived request "one bag per
+    lookup" -- ``offsets' = arange(N)``, ``B' = N``, gradient ``grad_out.reshape(N, D)`` -- dense (``_bwd`` into a zeroed fp32 buffer,
+    aten::embedding_dense_backward) or, with ``sparse=True``, coalesced COO (``_sparse_grad``).  No backward kernel of its own."""
+
+    @staticmethod
+    def forward(ctx, weight, module, indices, shape):
+        ctx.module = module
+        ctx.save_for_backward(indices)
+        ts = module._tables()
+        return _gather(ts, indices, module._offsets0(indices), 1, module.output_dtype).view(*shape, module.embedding_dim)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (indices,) = ctx.saved_tensors
+        m = ctx.module
+        w = m.weight
+        ts = m._tables()
+        n = indices.numel()
+        grad = grad_out.reshape(n, m.embedding_dim).contiguous()
+        offsets = m._offsets_arange(indices)
+        if not m.sparse:
+            dW = torch.zeros(w.shape, dtype=torch.float32, device=grad.device)
+            if n:
+                d_ptr = torch.tensor([dW.data_ptr()], dtype=torch.int64, device=grad.device)
+                _bwd(ts, grad, indices, offsets, n, d_ptr, torch.float32, 1.0, pad=m._pad_dev(), out16=m._out16)
+            return dW.to(w.dtype), None, None, None
+        if n:
+            ((rows, vals),) = _sparse_grad(ts, grad, indices, offsets, n, pads=None if m.padding_idx is None else [m.padding_idx],
+                                           pad=m._pad_dev(), out16=m._out16)
+        else:
+            rows = torch.empty(0, dtype=torch.int64, device=grad.device)
+            vals = torch.empty((0, m.embedding_dim), dtype=torch.float32, device=grad.device)
+        g = torch.sparse_coo_tensor(rows[None], vals.to(w.dtype), tuple(w.shape), is_coalesced=True)
+        m._sparse_mark = (g._values().data_ptr(), g._indices().data_ptr())      # (see _SparseGradFn)
+        return g, None, None, None
+
+
+class EmbeddingMI355(nn.Module, _BoundsChecked):
+    """``torch.nn.Embedding(num_embeddings, embedding_dim)`` on an MI355X HIP kernel: the un-pooled sibling of
+    :class:`EmbeddingBagMI355` (fbgemm TBE's sequence embeddings, ``PoolingMode.NONE``, for one table).
+
+    ``forward(input)`` takes an int32 / int64 tensor of any shape and returns ``[*input.shape, D]``: row ``input[...]`` of ``.weight``
+    per lookup, moved by ONE launch (``pm_embedding_gather``: the request is one table, one bag, ``offsets = [0]``).  An empty input
+    returns an empty output without a launch.  A floating-point input raises ``TypeError``.
+    ``output_dtype`` (default ``None`` = fp32, this package's convention: 16-bit rows are widened exactly): ``torch.float32`` /
+    ``torch.bfloat16`` / ``torch.float16`` or the spellings the bag modules take.  With the table's own dtype the stored bits come
+    back as they are -- ``-0.0``, NaN payloads and subnormals included, which is what torch's module returns; an fp32 table with a
+    16-bit ``output_dtype``, and bf16 <-> fp16, are rounded once to nearest even (the rule of the bag modules' ``output_dtype``).
+    ``padding_idx`` (default ``None``) follows ``nn.Embedding``: an int in ``[-n, n)``, negative values count from the end; the forward
+    still returns the row as stored (a NaN kept there comes out); the row receives no gradient (dense: its gradient row is zero;
+    ``sparse=True``: it is absent from the COO rows); a module that creates its own weights zero-fills it.
+    Autograd: the sum backward of the request "one bag per lookup" (``offsets = arange(N)``), so ``weight.grad`` is what
+    :class:`EmbeddingBagMI355` gives for bags of one -- dense fp32 accumulation in lookup order, or with ``sparse=True`` a coalesced
+    sparse COO tensor of the distinct rows looked up (one synchronisation, as there).  A gradient in a 16-bit ``output_dtype`` is
+    widened exactly first.  ``N >= 2^32`` lookups raise ``ValueError``.
+    ``bounds_check_mode`` (default ``"none"``): see :class:`_BoundsChecked` -- ``forward`` repairs / refuses bad indices first;
+    ``sanitize_`` is the call on its own.  ``max_norm`` and ``scale_grad_by_freq`` are not implemented (no such parameters).
+    """
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, padding_idx: Optional[int] = None, sparse: bool = False,
+                 dtype: torch.dtype = torch.float32, device=None, _weight: Optional[torch.Tensor] = None,
+                 bounds_check_mode="none", output_dtype=None):
+        super().__init__()
+        self._init_shared(bounds_check_mode, output_dtype)      # (validated before anything is allocated)
+        self.padding_idx = _normalize_padding_idx(padding_idx, num_embeddings if _weight is None else int(_weight.shape[0]))
+        self.num_embeddings, self.embedding_dim, self.sparse = num_embeddings, embedding_dim, sparse
+        if _weight is None:
+            w = torch.empty(num_embeddings, embedding_dim, dtype=dtype, device=device)
+            if w.is_cuda:
+                fill_random_(w, "normal", 0.0, 1.0, seed=torch.initial_seed())
+            else:
+                nn.init.normal_(w)  # host staging only; forward refuses non-ROCm tensors
+            if self.padding_idx is not None:
+                w[self.padding_idx].zero_()      # torch: the padding row of module-made weights starts as zeros
+        else:
+            w = _weight
+        self.weight = nn.Parameter(w)
+        self._ts: Optional[_TableSet] = None
+        self._off0: dict = {}        # the forward's offsets [0], one per (dtype, device)
+        self._offn: dict = {}        # the backward's offsets arange(N), per (N, dtype, device)
+        self._sparse_mark = None
+        if sparse:
+            self.weight.register_post_accumulate_grad_hook(self._mark_coalesced)
+
+    @classmethod
+    def from_pretrained(cls, embeddings: torch.Tensor, freeze: bool = True, padding_idx: Optional[int] = None, sparse: bool = False, **kw):
+        """``nn.Embedding.from_pretrained``: the module around a caller's 2-D ``embeddings`` (left as they are, the padding row
+        included); ``freeze=True`` (default) turns the weight's gradient off.  ``kw``: ``bounds_check_mode``, ``output_dtype``."""
+        if embeddings.dim() != 2:
+            raise ValueError("Embeddings parameter is expected to be 2-dimensional")
+        m = cls(int(embeddings.shape[0]), int(embeddings.shape[1]), padding_idx=padding_idx, sparse=sparse, _weight=embeddings, **kw)
+        m.weight.requires_grad = not freeze
+        return m
+
+    _mark_coalesced = EmbeddingBagMI355._mark_coalesced
+    _tables = EmbeddingBagMI355._tables
+
+    def _offsets0(self, indices) -> torch.Tensor:
+        key = (indices.dtype, indices.device)
+        off = self._off0.get(key)
+        if off is None:
+            off = self._off0[key] = torch.zeros(1, dtype=indices.dtype, device=indices.device)
+        return off
+
+    def _offsets_arange(self, indices) -> torch.Tensor:
+        """``arange(N)`` in the indices' dtype, built on the device once per (N, dtype, device) and reused (like ``_off2d``)"""
+        key = (indices.numel(), indices.dtype, indices.device)
+        off = self._offn.get(key)
+        if off is None:
+            if len(self._offn) >= 8:
+                self._offn.clear()
+            off = self._offn[key] = torch.arange(key[0], dtype=indices.dtype, device=indices.device)
+        return off
+
+    def _flat(self, input) -> torch.Tensor:
+        if not isinstance(input, torch.Tensor) or input.dtype not in _IDTYPE:
+            raise TypeError(f"EmbeddingMI355: input must be an int32 or int64 tensor, got {getattr(input, 'dtype', type(input))}")
+        if input.numel() >= 2**32:
+            raise ValueError("EmbeddingMI355: the backward carries lookup positions in 32 bits: fewer than 2^32 lookups per call")
+        w = self._parameters["weight"]
+        if not w.is_cuda:
+            _require_device(w, "EmbeddingMI355.weight")
+        _require_device(input, "input")
+        return input.reshape(-1).contiguous()
+
+    def forward(self, input):
+        indices = self._flat(input)
+        w = self._parameters["weight"]
+        if self.bounds_check_mode != "none" and indices.numel():
+            self._sanitize(self._tables(), indices, self._offsets0(indices), 1, self.bounds_check_mode)
+        if w.requires_grad and torch.is_grad_enabled():
+            return _EmbeddingGradFn.apply(w, self, indices, tuple(input.shape))
+        out = _gather(self._tables(), indices, self._offsets0(indices), 1, self.output_dtype)
+        return out.view(*input.shape, self.embedding_dim)
+
+    def sanitize_(self, input, mode=None) -> None:
+        """The sanitiser on its own: repairs ``input`` in place (it must be contiguous: a copy would be repaired instead),
+        stream-ordered.  ``mode``: default the module's ``bounds_check_mode``, ``"warning"`` where that is ``"none"``."""
+        if not input.is_contiguous():
+            raise ValueError("sanitize_ needs a contiguous input (it is repaired in place)")
+        indices = self._flat(input)
+        mode = bounds_check_mode_name(mode) if mode is not None else self.bounds_check_mode
+        if indices.numel():
+            self._sanitize(self._tables(), indices, self._offsets0(indices), 1, "warning" if mode == "none" else mode)
+
+    def extra_repr(self) -> str:
+        return (f"{self.num_embeddings}, {self.embedding_dim}, dtype={self.weight.dtype}" + (", sparse=True" if self.sparse else "") +
+                (f", padding_idx={self.padding_idx}" if self.padding_idx is not None else "") +
+                (f", output_dtype={self.output_dtype}" if self._out16 is not None else ""))
+
+
 class _FusedUpdateFn(torch.autograd.Function):
     """TBE-style: backward applies ``W[idx] += -lr * grad`` in place (no weight.grad); ``per_sample_weights`` that require grad get
     theirs (fbgemm's ``indice_weights`` gradient), computed from the tables as the forward read them."""
@@ -1256,6 +1435,31 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             self._sanitize(self._tables(), indices, offsets, B, self.bounds_check_mode, per_sample_weights, bag_begin, bag_count)
         return _fwd(self._tables(), indices, offsets, B, per_sample_weights, out, bag_begin, bag_count, split_bags,
                     pad=self._pad_dev(), mean=self._mean, out16=self._out16)
+
+    def lookup_sequence(self, indices, offsets, batch: Optional[int] = None, out=None, bag_begin=0, bag_count=None):
+        """The UN-POOLED forward over the module's T tables (fbgemm TBE's sequence embeddings, ``PoolingMode.NONE``): ``[N, D]`` in the
+        module's ``output_dtype``, ``N = indices.numel()``, row ``j`` = row ``indices[j]`` of the table that owns lookup position ``j``
+        (table ``t`` owns ``[offsets[t * B], offsets[(t + 1) * B])``) -- one launch, ``pm_embedding_gather``.  With the tables' own dtype
+        as ``output_dtype`` the stored bits come back; fp32 (the default) widens 16-bit rows exactly; anything else is rounded once.
+        Runs after ``bounds_check_mode``, like ``lookup``.  ``bag_begin/bag_count`` select a batch slice: only the rows of lookups
+        inside it are written -- a caller's ``out`` keeps every other row, a tensor allocated here holds zeros there.
+        ``padding_idx`` does not affect it (``nn.Embedding``'s forward rule: the padding row comes back as stored).  Needs one common
+        embedding dim; ``layout="blocked"``, mixed dims, ``pooling_mode="mean"`` (a mean module has no un-pooled form) and an ``out``
+        that is not a contiguous ``[N, D]`` tensor of ``output_dtype`` on the module's device raise ValueError.  The gradient of
+        sequence rows has no batched backward here (see README, "Un-pooled lookups")."""
+        if self.layout == "blocked":
+            raise ValueError('lookup_sequence does not take layout="blocked"')
+        if len(set(self.dims)) != 1:
+            raise ValueError("lookup_sequence needs one common embedding dim")
+        if self._mean:
+            raise ValueError('lookup_sequence does not take pooling_mode="mean": a mean module has no un-pooled form')
+        if out is not None:
+            _check_rows_out(out, indices.numel(), self.dims[0], self.output_dtype, self.weights.device)
+        _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
+        B = self._batch_of(offsets, indices) if batch is None else batch
+        if self.bounds_check_mode != "none":
+            self._sanitize(self._tables(), indices, offsets, B, self.bounds_check_mode, None, bag_begin, bag_count)
+        return _gather(self._tables(), indices, offsets, B, self.output_dtype, out, bag_begin, bag_count)
 
     def sanitize_(self, indices, offsets, batch: Optional[int] = None, mode=None) -> None:
         """The sanitiser on its own, in front of any entry point that does not run it (everything but ``forward`` / ``lookup``):
