@@ -226,6 +226,8 @@ int pm_embbag_bwd_fused(const pm_embbag_batch* op, const float* grad, void* cons
  * *keys / *vals: device pointers into the workspace (keys of *key_bytes bytes: table << *tshift | row; values: bag within
  * the table, or the lookup position for weighted requests); *d_count: device uint32 holding the number of pairs (batch
  * slices sort only their own lookups), or NULL when it is num_indices.  Valid until the next sort on the workspace.
+ * After a sequence sort (pm_embseq_sort_indices, below) the values are lookup positions in the request's index array; this call and
+ * pm_embbag_sort_status work there as after any other sort.
  */
 int pm_embbag_sorted_pairs(const pm_embbag_batch* op, int64_t max_rows, const void* workspace, const void** keys,
                            const uint32_t** vals, const uint32_t** d_count, int32_t* key_bytes, int32_t* tshift);
@@ -525,6 +527,61 @@ int pm_embbag_grad_widen(const pm_embbag_batch* op, const int64_t* padding_idx, 
  * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs this call finds out at symbol resolution.
  */
 int pm_embedding_gather(const pm_embbag_batch* op, int32_t out_dtype, void* out, int64_t out_row_stride, pm_stream_t stream);
+
+/*
+ * SEQUENCE GRADIENTS -- the batched backward of the un-pooled lookup above: the gradient of pm_embedding_gather's rows applied to all
+ * num_tables tables by one sort and one apply.  The request is the one pm_embedding_gather takes: table t owns the lookup positions
+ * [offsets[t * batch], offsets[(t + 1) * batch]), the last table ends at num_indices; the bags inside a table matter only for the
+ * slice [bag_begin, bag_begin + bag_count), whose lookups are the contiguous stretch [offsets[t * batch + bag_begin],
+ * offsets[t * batch + bag_begin + bag_count)) of every table.  out_offsets and out_stride of the request are not read.  The gradient
+ * is fp32 and addressed by lookup POSITION: row j starts at grad + j * grad_row_stride (elements); columns from dims[t] to the stride
+ * and rows of positions outside the slice are never read.
+ * The rule: for table t and row r let J(t, r) be the positions j owned by t, inside the slice, with indices[j] == r, ascending.
+ *   scatter-add / SGD   dst_t[r] accumulates alpha * grad[j] over J(t, r) in that order: what pm_embbag_bwd_sorted does for a row whose
+ *                       bags are those positions;
+ *   Adagrad             G = sum of grad[j] over J(t, r) from zero in that order, then the row-wise (elementwise = 0) or element-wise
+ *                       (elementwise = 1) finish exactly as documented for pm_embbag_bwd_sorted_adagrad_ex / _adagrad_elem: weight
+ *                       decay modes, stochastic rounding (keyed by seed, table, row, column pair), one rounding per 16-bit row.
+ * Rows with at most 256 lookups are bit-identical to that sequential loop; hotter rows are summed as ordered chunk partials, as
+ * everywhere in the sorted backward.  Deterministic, no atomics; every gradient row is read once.  By construction this is the sum
+ * backward of the one-table request "one bag per lookup" (offsets = 0, 1, 2, ..; batch = its lookups) applied per table, without the
+ * T sorts, applies and workspaces that route costs, and without a host read of the table borders; tests/sequence_grad_rules.py
+ * restates it in numpy.
+ * The sort forms every table's keys from the index array in its first radix pass (the path of a pooling-1 table) with the lookup
+ * position as the value: no key-building pass, no bag-of array, never the hybrid route -- a sequence sort is always complete, and
+ * the fused calls are simply sort then apply.  The apply is the sorted apply of pm_embbag_bwd_sorted*: same kernels, the position
+ * in the place of the bag, no per-table gradient offset.
+ *   pm_embseq_sort_indices        the key sort (needs the request only; may run on a side stream under the forward);
+ *   pm_embseq_bwd_sorted          the scatter-add apply of a sorted request;   pm_embseq_bwd_fused          sort + apply;
+ *   pm_embseq_bwd_sorted_adagrad  the Adagrad apply (state: device [T] of fp32 [rows_t] row-wise / [rows_t, dims_t] element-wise);
+ *   pm_embseq_bwd_fused_adagrad   sort + apply.
+ * Workspace: pm_embbag_bwd_sorted_workspace of the same request with per_sample_weights == NULL (no query of its own).  The workspace
+ * remembers which kind of sort it holds: a pooled apply (pm_embbag_bwd_sorted*, pm_embbag_sparse_grad*) after a sequence sort, and a
+ * sequence apply after a pooled sort, are PM_ERR_INVALID.  pm_embbag_sorted_pairs / pm_embbag_sort_status work after a sequence sort;
+ * the values are then lookup positions.
+ * Refused on the host, before any HIP call: everything pm_embbag_bwd_sorted refuses (more than 1024 tables, 2^32 or more lookups, bad
+ * dtypes, a workspace that is NULL or too small, a missing or mismatching sort); per_sample_weights != NULL, a non-zero table_group /
+ * grad_block_shift / grad_block_extra (PM_ERR_UNSUPPORTED); a NULL grad with num_indices > 0, a grad that is not 16-byte aligned,
+ * grad_row_stride < max_dim or not a multiple of 4 (PM_ERR_INVALID); the Adagrad width limits of the pooled calls (max_dim > 256 fp32
+ * / 512 16-bit: PM_ERR_UNSUPPORTED); elementwise not 0 or 1 (PM_ERR_INVALID).  num_indices == 0 or bag_count == 0 is PM_OK without a
+ * launch.  Padding rows: pm_pad_rows_guard around the call, as for the pooled backwards.
+ * Replaces aten::embedding_dense_backward per table (the backward of nn.Embedding, the un-pooled sibling of the module at
+ * train/compute/pt/pytorch_emb.py:179) and the sequence (PoolingMode.NONE) backward of fbgemm's TBE with its fused optimizers
+ * (split_table_batched_embeddings_ops.py:289-300,318-324).
+ * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these calls finds out at symbol resolution.
+ */
+int pm_embseq_sort_indices(const pm_embbag_batch* op, int64_t max_rows, void* workspace, int64_t workspace_bytes, pm_stream_t stream);
+int pm_embseq_bwd_sorted(const pm_embbag_batch* op, const float* grad, int64_t grad_row_stride, void* const* dst_tables,
+                         int32_t dst_dtype, float alpha, int64_t max_rows, const void* workspace, int64_t workspace_bytes,
+                         pm_stream_t stream);
+int pm_embseq_bwd_fused(const pm_embbag_batch* op, const float* grad, int64_t grad_row_stride, void* const* dst_tables,
+                        int32_t dst_dtype, float alpha, int64_t max_rows, void* workspace, int64_t workspace_bytes, pm_stream_t stream);
+int pm_embseq_bwd_sorted_adagrad(const pm_embbag_batch* op, const float* grad, int64_t grad_row_stride, void* const* tables,
+                                 int32_t table_dtype, float* const* state, const pm_rowwise_adagrad* opt, int32_t elementwise,
+                                 int64_t max_rows, const void* workspace, int64_t workspace_bytes, pm_stream_t stream);
+int pm_embseq_bwd_fused_adagrad(const pm_embbag_batch* op, const float* grad, int64_t grad_row_stride, void* const* tables,
+                                int32_t table_dtype, float* const* state, const pm_rowwise_adagrad* opt, int32_t elementwise,
+                                int64_t max_rows, void* workspace, int64_t workspace_bytes, pm_stream_t stream);
 
 /*
  * DLRM input redistribution on the device: regroup what the lengths / indices all-to-alls deliver

@@ -81,6 +81,11 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_fwd_out16",
     "pm_embbag_grad_widen",
     "pm_embedding_gather",
+    "pm_embseq_sort_indices",
+    "pm_embseq_bwd_sorted",
+    "pm_embseq_bwd_fused",
+    "pm_embseq_bwd_sorted_adagrad",
+    "pm_embseq_bwd_fused_adagrad",
 )
 
 
@@ -275,6 +280,15 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     # un-pooled rows: (op, PM_F32 | PM_BF16 | PM_F16, out, out_row_stride, stream)
     L.pm_embedding_gather.restype = ctypes.c_int
     L.pm_embedding_gather.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, vp, i64, vp]
+    # sequence gradients: (op, [grad, grad_row_stride, tables, dtype, ...], max_rows, workspace, workspace_bytes, stream)
+    L.pm_embseq_sort_indices.restype = ctypes.c_int
+    L.pm_embseq_sort_indices.argtypes = [ctypes.POINTER(pm_embbag_batch), i64, vp, i64, vp]
+    for fn in (L.pm_embseq_bwd_sorted, L.pm_embseq_bwd_fused):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i64, vp, i32, ctypes.c_float, i64, vp, i64, vp]
+    for fn in (L.pm_embseq_bwd_sorted_adagrad, L.pm_embseq_bwd_fused_adagrad):      # (.., state, opt, elementwise 0 / 1, ..)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i64, vp, i32, vp, ctypes.POINTER(pm_rowwise_adagrad), i32, i64, vp, i64, vp]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]

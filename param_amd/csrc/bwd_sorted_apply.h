@@ -31,11 +31,12 @@ struct SortedParams {
     float* partials;         // per chunk: lead / trail fp32 partial sums, 2 * max_dim floats
     int32_t T;
     const void* keys;        // sorted keys (uint32 / uint64)
-    const uint32_t* vals;    // sorted values: bag within table (unweighted) or lookup position j (weighted)
+    const uint32_t* vals;    // sorted values: bag within table (unweighted) or lookup position j (weighted); a sequence apply: the
+                             // lookup position j IS the "bag" -- gradient row j, out_offsets NULL, out_stride the gradient's row stride
     const uint32_t* bag_of;  // weighted only: bag within table of lookup position j
     void* const* dst;        // destination tables
     const int32_t* dims;
-    const int64_t* out_offsets;
+    const int64_t* out_offsets;   // per-table gradient offset, device [T]; NULL (a uniform test): zero for every table (sequence apply)
     const float* grad;
     const float* psw;
     int64_t out_stride;

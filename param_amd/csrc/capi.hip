@@ -171,10 +171,13 @@ void fill_params(const pm_embbag_batch* op, const pm::LaunchPlan& plan, pm::KPar
 
 // ---- the sorted backward's entry points: what they share ---------------------------------------------------------------
 // the one text of each reason the sort recorded on a workspace does not fit a call; kind: "row-wise" / "element-wise" (Adagrad)
-int plan_fail(pm::PlanStatus st, const char* kind) {
+int plan_fail(pm::PlanStatus st, const char* kind, bool sequence = false) {
     switch (st) {
         case pm::PlanStatus::ok: return PM_OK;
         case pm::PlanStatus::none:
+            if (sequence)
+                return fail(PM_ERR_INVALID, "pm_embseq_sort_indices has not been called for this request on this workspace (same indices / "
+                                            "offsets pointers, batch and bag slice as the sort's)");
             return fail(PM_ERR_INVALID, "pm_embbag_sort_indices has not been called for this request on this workspace (same indices / "
                                         "offsets pointers, batch, bag slice and weights as the sort's)");
         case pm::PlanStatus::two_phase:
@@ -189,6 +192,12 @@ int plan_fail(pm::PlanStatus st, const char* kind) {
         case pm::PlanStatus::low_digit_order:
             return fail(PM_ERR_UNSUPPORTED, "the sparse gradient needs rows in ascending order within a table: sort mode 1 orders them by "
                                             "their low digit first (pm_set_sort_tuning 0, 2 or 3)");
+        case pm::PlanStatus::sequence_sort:
+            return fail(PM_ERR_INVALID, "the sort on this workspace is a sequence sort (pm_embseq_sort_indices: its values are lookup positions, "
+                                        "not bags): only pm_embseq_bwd_sorted* may follow it; sort the request with pm_embbag_sort_indices");
+        case pm::PlanStatus::pooled_sort:
+            return fail(PM_ERR_INVALID, "the sort on this workspace is a pooled sort (pm_embbag_sort_indices: its values are bags, not lookup "
+                                        "positions): a sequence apply needs pm_embseq_sort_indices");
         case pm::PlanStatus::already_counted:
             return fail(PM_ERR_INVALID, "pm_embbag_sparse_grad_count has been called for this sort already: sort the request again");
         default: return fail(PM_ERR_INVALID, "pm_embbag_sparse_grad needs pm_embbag_sparse_grad_count on this sort first");
@@ -237,6 +246,7 @@ struct SortedCall {
     const char* kind;         // Adagrad: "row-wise" / "element-wise"
     pm::KParams p;            // out: the request
     size_t sorted;            // out: bytes of the sorted backward's part of the workspace
+    bool sequence = false;    // a pm_embseq_* call: names the sequence sort where no sort fits
 };
 template <typename Own, typename Plan>
 int sorted_call_prologue(SortedCall& c, const pm_embbag_batch* op, int64_t max_rows, const void* workspace, int64_t workspace_bytes,
@@ -250,7 +260,7 @@ int sorted_call_prologue(SortedCall& c, const pm_embbag_batch* op, int64_t max_r
     if (!workspace || workspace_bytes < static_cast<int64_t>(need))
         return fail(PM_ERR_INVALID, "workspace too small: need " + std::to_string(need) + " bytes" +
                                         (c.sparse ? " (pm_embbag_sparse_grad_workspace)" : ""));
-    return plan_fail(plan(), c.kind);
+    return plan_fail(plan(), c.kind, c.sequence);
 }
 
 // the sorted apply's view of the request: the gradient, the tables it updates, alpha and the default destination-row policy
@@ -856,6 +866,120 @@ int pm_embbag_bwd_fused_adagrad_elem(const pm_embbag_batch* op, const float* gra
                                      float* const* state, const pm_rowwise_adagrad* opt, int64_t max_rows, void* workspace,
                                      int64_t workspace_bytes, pm_stream_t stream) {
     return fused_adagrad(op, grad, tables, table_dtype, state, true, opt, max_rows, workspace, workspace_bytes, stream);
+}
+
+// ---- sequence (un-pooled) backward: the sorted backward on a sort whose values are lookup positions ------------------------------------
+// what the pm_embseq_* calls refuse beyond the pooled calls' rules, before their nothing-to-do early-out; has_grad: the call reads one
+static int seq_request_ok(const pm_embbag_batch* op, bool has_grad, const float* grad, int64_t grad_row_stride) {
+    if (op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "sequence gradients are unweighted: per_sample_weights must be NULL");
+    if (op->table_group != 0 || op->grad_block_shift != 0 || op->grad_block_extra != 0)
+        return fail(PM_ERR_UNSUPPORTED, "sequence gradients do not take blocked layouts (table_group / grad_block_shift / grad_block_extra must be 0)");
+    if (!has_grad) return PM_OK;
+    if (grad_row_stride < op->max_dim || grad_row_stride % 4 != 0)
+        return fail(PM_ERR_INVALID, "grad_row_stride must be a multiple of 4 elements and at least max_dim");
+    if (reinterpret_cast<uintptr_t>(grad) % 16 != 0) return fail(PM_ERR_INVALID, "grad must be 16-byte aligned");
+    if (!grad && op->num_indices > 0) return fail(PM_ERR_INVALID, "grad is NULL");
+    return PM_OK;
+}
+
+// the sequence apply's view of the request: gradient row j at grad + j * grad_row_stride, no per-table offset, no blocking, no weights
+static void seq_apply_params(pm::KParams& p, const float* grad, int64_t grad_row_stride, const void* tables, float alpha) {
+    apply_params(p, grad, tables, alpha);
+    p.out_offsets = nullptr;
+    p.out_stride = grad_row_stride;
+    p.gblk_extra = 0;
+}
+
+int pm_embseq_sort_indices(const pm_embbag_batch* op, int64_t max_rows, void* workspace, int64_t workspace_bytes, pm_stream_t stream) {
+    SortedCall c{"pm_embseq_sort_indices", op ? op->weight_dtype : -1, false, ""};
+    c.sequence = true;
+    const pm::KParams& p = c.p;
+    const int rc = sorted_call_prologue(
+        c, op, max_rows, workspace, workspace_bytes,
+        [&]() -> int {
+            const int r = seq_request_ok(op, false, nullptr, 0);
+            return r != PM_OK ? r : (p.N == 0 || p.bag_count == 0) ? kDone : PM_OK;
+        },
+        [] { return pm::PlanStatus::ok; });
+    if (rc != PM_OK) return rc == kDone ? PM_OK : rc;
+    const hipError_t h = pm::sort_indices(p, max_rows, op->max_dim, 0, 1, workspace, static_cast<hipStream_t>(stream), false, true);
+    if (h != hipSuccess) return hip_fail(h, "pm_embseq_sort_indices");
+    return PM_OK;
+}
+
+int pm_embseq_bwd_sorted(const pm_embbag_batch* op, const float* grad, int64_t grad_row_stride, void* const* dst_tables, int32_t dst_dtype,
+                         float alpha, int64_t max_rows, const void* workspace, int64_t workspace_bytes, pm_stream_t stream) {
+    SortedCall c{"pm_embseq_bwd_sorted", dst_dtype, false, ""};
+    c.sequence = true;
+    pm::KParams& p = c.p;
+    const int rc = sorted_call_prologue(
+        c, op, max_rows, workspace, workspace_bytes,
+        [&]() -> int {
+            const int r = seq_request_ok(op, true, grad, grad_row_stride);
+            if (r != PM_OK) return r;
+            if (p.N == 0 || p.bag_count == 0) return kDone;
+            return !dst_tables ? fail(PM_ERR_INVALID, "dst_tables is NULL") : PM_OK;
+        },
+        [&] { return pm::bwd_sorted_plan_check(p, max_rows, workspace, false, true); });
+    if (rc != PM_OK) return rc == kDone ? PM_OK : rc;
+    seq_apply_params(p, grad, grad_row_stride, dst_tables, alpha);
+    const hipError_t h = pm::bwd_sorted_apply(p, max_rows, dst_dtype, op->max_dim, workspace, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embseq_bwd_sorted launch");
+    return PM_OK;
+}
+
+// what the sequence Adagrad calls check of their own, in order (kDone: an empty request, after the options)
+static int seq_adagrad_args(const pm_embbag_batch* op, const float* grad, int64_t grad_row_stride, void* const* tables, int32_t table_dtype,
+                            float* const* state, int32_t elementwise, const pm_rowwise_adagrad* opt) {
+    if (elementwise != 0 && elementwise != 1) return fail(PM_ERR_INVALID, "elementwise must be 0 (row-wise) or 1 (element-wise)");
+    const int r = seq_request_ok(op, true, grad, grad_row_stride);
+    return r != PM_OK ? r : check_adagrad_args(op, grad, tables, table_dtype, state, elementwise != 0, opt);
+}
+
+int pm_embseq_bwd_sorted_adagrad(const pm_embbag_batch* op, const float* grad, int64_t grad_row_stride, void* const* tables,
+                                 int32_t table_dtype, float* const* state, const pm_rowwise_adagrad* opt, int32_t elementwise,
+                                 int64_t max_rows, const void* workspace, int64_t workspace_bytes, pm_stream_t stream) {
+    SortedCall c{"pm_embseq_bwd_sorted_adagrad", table_dtype, false, elementwise == 1 ? "element-wise" : "row-wise"};
+    c.sequence = true;
+    pm::KParams& p = c.p;
+    const int rc = sorted_call_prologue(c, op, max_rows, workspace, workspace_bytes,
+                                        [&] { return seq_adagrad_args(op, grad, grad_row_stride, tables, table_dtype, state, elementwise, opt); },
+                                        [&] { return pm::bwd_sorted_plan_check(p, max_rows, workspace, true, true); });
+    if (rc != PM_OK) return rc == kDone ? PM_OK : rc;
+    seq_apply_params(p, grad, grad_row_stride, tables, 1.0f);
+    const hipError_t h = pm::bwd_sorted_apply(p, max_rows, table_dtype, op->max_dim, workspace, static_cast<hipStream_t>(stream),
+                                              pm::ApplyUpdate{opt, state, elementwise == 1});
+    if (h != hipSuccess) return hip_fail(h, "pm_embseq_bwd_sorted_adagrad launch");
+    return PM_OK;
+}
+
+// The fused sequence calls, like the pooled ones, validate what their APPLY half needs before the sort half launches anything.
+static int seq_fused_args_ok(const pm_embbag_batch* op, const float* grad, int64_t grad_row_stride, void* const* tables, int32_t dtype) {
+    if (!op) return fail(PM_ERR_INVALID, "op is NULL");
+    int rc = validate_request(op, dtype, current_knobs());      // (the destination dtype's row-width rule)
+    if (rc != PM_OK || (rc = seq_request_ok(op, true, grad, grad_row_stride)) != PM_OK) return rc;
+    if (op->num_indices == 0 || op->bag_count == 0) return kDone;
+    return !tables ? fail(PM_ERR_INVALID, "dst_tables / tables is NULL") : PM_OK;
+}
+
+int pm_embseq_bwd_fused(const pm_embbag_batch* op, const float* grad, int64_t grad_row_stride, void* const* dst_tables, int32_t dst_dtype,
+                        float alpha, int64_t max_rows, void* workspace, int64_t workspace_bytes, pm_stream_t stream) {
+    int rc = seq_fused_args_ok(op, grad, grad_row_stride, dst_tables, dst_dtype);
+    if (rc != PM_OK) return rc == kDone ? PM_OK : rc;
+    if ((rc = pm_embseq_sort_indices(op, max_rows, workspace, workspace_bytes, stream)) != PM_OK) return rc;
+    return pm_embseq_bwd_sorted(op, grad, grad_row_stride, dst_tables, dst_dtype, alpha, max_rows, workspace, workspace_bytes, stream);
+}
+
+int pm_embseq_bwd_fused_adagrad(const pm_embbag_batch* op, const float* grad, int64_t grad_row_stride, void* const* tables,
+                                int32_t table_dtype, float* const* state, const pm_rowwise_adagrad* opt, int32_t elementwise,
+                                int64_t max_rows, void* workspace, int64_t workspace_bytes, pm_stream_t stream) {
+    if (!op) return fail(PM_ERR_INVALID, "op is NULL");
+    int rc = validate_request(op, table_dtype, current_knobs());
+    if (rc != PM_OK) return rc;
+    if ((rc = seq_adagrad_args(op, grad, grad_row_stride, tables, table_dtype, state, elementwise, opt)) != PM_OK) return rc == kDone ? PM_OK : rc;
+    if ((rc = pm_embseq_sort_indices(op, max_rows, workspace, workspace_bytes, stream)) != PM_OK) return rc;
+    return pm_embseq_bwd_sorted_adagrad(op, grad, grad_row_stride, tables, table_dtype, state, opt, elementwise, max_rows, workspace,
+                                        workspace_bytes, stream);
 }
 
 // ---- ABI v8: coalesced sparse gradient (sparse_grad.hip) ----------------------------------------------------------------

@@ -226,7 +226,7 @@ hipError_t sorted_workspace_bytes(const KParams& p, int64_t max_rows, int max_di
 // sort stop after its first part (segments, verdicts, dup maps) and leave the rest to the apply call (hybrid backward), which
 // reads the request's indices again.  A sort issued on its own always consumes the request completely.
 hipError_t sort_indices(const KParams& p, int64_t max_rows, int max_dim, int64_t fixed_pooling, int phases, void* workspace,
-                        hipStream_t stream, bool defer_ok = false);
+                        hipStream_t stream, bool defer_ok = false, bool sequence = false);
 // why the sort recorded on a workspace does not fit a call (embbag_bwd_sorted.hip: find_plan; capi.hip has the one text of each)
 enum class PlanStatus {
     ok,
@@ -237,8 +237,11 @@ enum class PlanStatus {
     low_digit_order,           // sparse gradient: the sort's order is not ascending within a table (sort mode 1)
     already_counted,           // sparse gradient, counting: the sort was relabelled already
     not_counted,               // sparse gradient, applying: it was not
+    sequence_sort,             // a pooled apply (or the sparse gradient) after a sequence sort (pm_embseq_sort_indices): its values are positions
+    pooled_sort,               // a sequence apply after a pooled sort: its values are bags
 };
-PlanStatus bwd_sorted_plan_check(const KParams& p, int64_t max_rows, const void* workspace, bool adagrad);
+// sequence: the call is a sequence apply (pm_embseq_*); the sort on the workspace must be of the same kind
+PlanStatus bwd_sorted_plan_check(const KParams& p, int64_t max_rows, const void* workspace, bool adagrad, bool sequence = false);
 // where the last sort on a workspace left its pairs (device pointers into the workspace): tests and tools
 struct SortedPairsInfo {
     const void* keys;
@@ -361,6 +364,10 @@ struct SegSortRequest {
     int tshift;              // key = table << tshift | row
     int rbits_max;           // bits_for(max_rows): the number of global passes of mode 0
     bool weighted;           // values = lookup positions (+ bag_of), every table through the key-building kernel
+    bool sequence = false;   // a sequence (un-pooled) request: every table is sorted as a table of pooling factor 1 whatever its bags look
+                             // like -- keys formed from the index array in the first pass -- and the value is the lookup's POSITION in the
+                             // request's index array (in_start + i), not its bag.  No key-building pass, no bag_of, no weights, never
+                             // hybrid.  Set by the pm_embseq_* entry points only (sort_indices' `sequence` argument).
     uint32_t* zero4;         // not NULL: four words the sort's first kernel sets to zero (the apply's work-list control words)
     HybArgs hyb;
     uint32_t* queue_a;       // hybrid: two idle arrays of N words each for the mark kernel's per-slice row queues (the sort's value

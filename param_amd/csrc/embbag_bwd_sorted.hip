@@ -170,6 +170,8 @@ struct SortPlan {
                          // sort then runs inside the apply call, after the bag-major kernel)
     bool applied;        // an apply has been issued for this sort (a deferred sort's pairs exist only then)
     bool relabelled;     // pm_embbag_sparse_grad_count rewrote the keys to (table, slot): only the sparse-gradient apply may follow
+    bool sequence;       // a sequence sort (pm_embseq_*): the values are lookup positions; only a sequence apply may follow, and a
+                         // sequence apply follows nothing else
     // what the sort was issued for: the apply must follow with the same request on the same workspace
     const void* indices;
     const void* offsets;
@@ -244,8 +246,9 @@ SortWs ws_layout(const KParams& p, int64_t max_rows, int max_dim, bool weighted,
     return ws;
 }
 
-SortPlan make_plan(const KParams& p, int64_t max_rows, int64_t fixed_pooling, int phases) {
+SortPlan make_plan(const KParams& p, int64_t max_rows, int64_t fixed_pooling, int phases, bool sequence = false) {
     SortPlan g;
+    g.sequence = sequence;
     g.T = p.T;
     g.n = p.N;
     g.rbits = bits_for(max_rows);
@@ -278,7 +281,7 @@ SortPlan make_plan(const KParams& p, int64_t max_rows, int64_t fixed_pooling, in
     g.xcd = g.v2 && want_xcd();
     g.sort_end_bit = g.v2 ? g.rbits : g.kbits;
     g.in_b = g.v2 && seg_sort_result_in_b(g.mode, g.rbits);
-    g.fused_keys = g.v2 && !g.weighted;
+    g.fused_keys = g.v2 && !g.weighted;      // (a sequence sort: every table, always -- seg_sort.hip forms no other keys for it)
     if (!g.v2) legacy_plan(p, fixed_pooling, phases, g);
     return g;
 }
@@ -301,6 +304,7 @@ SegSortRequest seg_request(const KParams& p, const SortPlan& g, SortWs& ws) {
     rq.tshift = g.tshift;
     rq.rbits_max = g.rbits;
     rq.weighted = g.weighted;
+    rq.sequence = g.sequence;
     rq.zero4 = ws.fix_ctl;
     rq.hyb.allow = g.hyb;
     rq.hyb.slices = hyb_slices(p.N, p.T);
@@ -367,8 +371,9 @@ hipError_t sorted_workspace_bytes(const KParams& p, int64_t max_rows, int max_di
 }
 
 hipError_t sort_indices(const KParams& p, int64_t max_rows, int max_dim, int64_t fixed_pooling, int phases, void* workspace,
-                        hipStream_t stream, bool defer_ok) {
-    SortPlan g = make_plan(p, max_rows, fixed_pooling, phases);
+                        hipStream_t stream, bool defer_ok, bool sequence) {
+    SortPlan g = make_plan(p, max_rows, fixed_pooling, phases, sequence);
+    if (sequence && (!g.v2 || g.weighted)) return hipErrorInvalidValue;      // the segmented sort only; capi.hip refuses weights first
     SortWs ws = ws_layout(p, max_rows, max_dim, g.weighted, workspace);
     if (ws.rc != hipSuccess) return ws.rc;
     {
@@ -399,7 +404,9 @@ hipError_t sort_indices(const KParams& p, int64_t max_rows, int max_dim, int64_t
         constexpr int64_t kHybMinTiles = 1024;
         const int min_tiles_knob = g_hyb_min_tiles.load();
         const bool fills = uniq_tiles * p.T >= (min_tiles_knob < 0 ? kHybMinTiles : static_cast<int64_t>(min_tiles_knob));
-        if (defer_ok && g.v2 && en > 0 && !g.weighted && p.N >= static_cast<int64_t>(kHybMinCount) && uniq_tiles >= 1 &&
+        // ... and never to a sequence sort (its values are positions; almost every row of a uniform request is looked up once there,
+        // so a bag-major route is the obvious follow-up -- not built)
+        if (defer_ok && !sequence && g.v2 && en > 0 && !g.weighted && p.N >= static_cast<int64_t>(kHybMinCount) && uniq_tiles >= 1 &&
             uniq_tiles <= kCompactMaxTiles && ((even_req && fills) || en >= 2) && seg_sort_hybrid_available())
             g.hyb = en >= 2 ? 2 : 1;
         std::lock_guard<std::mutex> lock(g_plan_mutex);
@@ -434,9 +441,10 @@ std::string sort_plan_describe(const KParams& p, int64_t max_rows, int64_t fixed
     return buf;
 }
 
-PlanStatus bwd_sorted_plan_check(const KParams& p, int64_t max_rows, const void* workspace, bool adagrad) {
+PlanStatus bwd_sorted_plan_check(const KParams& p, int64_t max_rows, const void* workspace, bool adagrad, bool sequence) {
     SortPlan g;
     return find_plan(workspace, p, max_rows, true, g, [&](SortPlan& r) {
+        if (r.sequence != sequence) return r.sequence ? PlanStatus::sequence_sort : PlanStatus::pooled_sort;
         if (r.relabelled) return PlanStatus::relabelled;
         if (adagrad && r.H != 1) return PlanStatus::two_phase;
         return PlanStatus::ok;
@@ -446,6 +454,7 @@ PlanStatus bwd_sorted_plan_check(const KParams& p, int64_t max_rows, const void*
 PlanStatus sparse_grad_pairs(const KParams& p, int64_t max_rows, int max_dim, const void* workspace, bool counting, SparsePairs& out) {
     SortPlan g;
     const PlanStatus st = find_plan(workspace, p, max_rows, true, g, [&](SortPlan& r) {
+        if (r.sequence) return PlanStatus::sequence_sort;
         if (!r.v2 || r.hyb || r.H != 1) return PlanStatus::not_complete_segmented;
         if (r.mode == 1) return PlanStatus::low_digit_order;
         if (counting && r.relabelled) return PlanStatus::already_counted;
@@ -499,7 +508,7 @@ hipError_t bwd_sorted_apply(const KParams& p, int64_t max_rows, int dst_dtype, i
     sp.bag_of = ws.bag_of;
     sp.dst = const_cast<void* const*>(p.tables);
     sp.dims = p.dims;
-    sp.out_offsets = p.out_offsets;
+    sp.out_offsets = g.sequence ? nullptr : p.out_offsets;      // sequence: gradient rows are addressed by lookup position (no per-table offset)
     sp.grad = p.io;
     sp.psw = p.psw;
     sp.out_stride = p.out_stride;
@@ -534,6 +543,7 @@ hipError_t bwd_sorted_apply(const KParams& p, int64_t max_rows, int dst_dtype, i
     // a looping grid of 4096 workgroups changed nothing for the small launch and cost the full-size one its XCD-contiguous tile
     // order (Zipf apply +13 %).  So: the request-sized tile, one workgroup per possible tile, as for every other sort.)
     const ApplyLaunchers& launch = kApplyLaunchers[dst_dtype == PM_F32 ? 0 : dst_dtype == PM_BF16 ? 1 : 2];
+    if (g.sequence && (g.hyb || sp.psw || sp.gblk_extra != 0)) return hipErrorInvalidValue;      // (never recorded / refused in capi.hip)
     if (!g.hyb) return launch.sorted(sp, g.key_bytes, max_dim, stream);
     // Hybrid: the bag-major kernel applies the rows looked up once and lists the other lookups; then the rest of the sort
     // (compaction of the lists, prep 2, the passes) and the sorted apply of what is left -- a few per cent of the request

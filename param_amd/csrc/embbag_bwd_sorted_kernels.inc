@@ -290,7 +290,7 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
     }
     for (int t = threadIdx.x; t < p.T; t += kBlock) {
         s_dst[t] = reinterpret_cast<char*>(p.dst[t]);
-        s_ooff[t] = p.out_offsets[t];
+        s_ooff[t] = p.out_offsets ? p.out_offsets[t] : 0;      // NULL (uniform): a sequence apply, gradient rows addressed by position
         s_dim[t] = p.dims[t];
         if (OPT == 1) s_mom[t] = p.mom[t];
         if (OPT == 2) s_mom[t] = p.state[t];      // [rows, D] fp32, one value per weight
@@ -757,7 +757,7 @@ __device__ __forceinline__ void fixup_one_run(const SortedParams& p, int64_t h, 
         if (OPT == 1) mom_prev = *as_global<float>(p.mom[t] + row);
         if (exact) {
             // exact: re-walk the run in lookup order
-            const float* gbase = p.grad + p.out_offsets[t] + c;
+            const float* gbase = p.grad + (p.out_offsets ? p.out_offsets[t] : 0) + c;
             for (int q = 0; q < static_cast<int>(len); q += kFixBatch) {
                 float gv[kFixBatch][VEC];
                 float sc[kFixBatch];

@@ -1,6 +1,7 @@
 // param_amd/csrc/seg_sort.hip -- the key sort of the sorted EmbeddingBag backward, round 3: per-TABLE segments whose
 // bounds, pooling factors and key widths are established ON THE DEVICE from the request itself, so that every request --
-// fixed pooling, per-table multi-hot pooling (Criteo), ragged bags, batch slices, per-sample weights -- gets
+// fixed pooling, per-table multi-hot pooling (Criteo), ragged bags, batch slices, per-sample weights, sequence (un-pooled) requests
+// whose value is the lookup's position -- gets
 //   * the table bits out of the sort (a table's lookups are a contiguous range of the table-major request),
 //   * the first pass formed straight from the index array wherever a table's bags all have the same length (verified by
 //     reading the offsets, not taken on the caller's word), and
@@ -139,7 +140,7 @@ __device__ __forceinline__ uint32_t block_excl_scan256(uint32_t v, uint32_t* s_t
 // ---------------------------------------------------------------------------------------------------------------------
 // prep 1: one workgroup (1024 threads) per table
 __global__ void __launch_bounds__(1024) seg_prep_tables_kernel(const void* indices, const void* offsets, int idx64, const int64_t* rows, int T,
-                                                               int64_t B, int64_t N, int64_t bag_begin, int64_t bag_count, int force_ragged,
+                                                               int64_t B, int64_t N, int64_t bag_begin, int64_t bag_count, int kind,
                                                                SegDesc* desc, uint32_t* zero4, const HybArgs hyb, HybTable* hyb_tab, uint32_t* qtail,
                                                                uint32_t* rest_stat) {
     __shared__ uint32_t s_sample[2048];      // classification: 2^16 hashed bits
@@ -154,8 +155,12 @@ __global__ void __launch_bounds__(1024) seg_prep_tables_kernel(const void* indic
     const int64_t s = off_at(g0);
     const int64_t e = off_at(g0 + bag_count);
     const int64_t cnt = e > s ? e - s : 0;
-    const int64_t L = (bag_count > 0 && cnt > 0 && cnt % bag_count == 0) ? cnt / bag_count : 0;
-    int bad = (L == 0 || force_ragged) ? 1 : 0;
+    // kind: 0 the pooling factor is established below; 1 every table is ragged whatever its offsets say (weighted requests: keys are
+    // built for all of them); 2 a SEQUENCE request (SegSortRequest::sequence) -- the bags inside a table only bound the slice, every
+    // table is sorted like a table of pooling factor 1 whatever its bags look like (nothing to verify: no offset between s and e is read)
+    const bool sequence = kind == 2;
+    const int64_t L = sequence ? 1 : (bag_count > 0 && cnt > 0 && cnt % bag_count == 0) ? cnt / bag_count : 0;
+    int bad = (!sequence && (L == 0 || kind == 1)) ? 1 : 0;
     // Classification for the hybrid backward (common.h), first half: is the table structurally eligible -- a size the dup map
     // separates, a row count that makes repeats rare under uniform indices -- and if so, request a sample of 2048 lookups spread
     // over the table's slice now, so that their latency passes under the check of the offsets below.
@@ -173,7 +178,7 @@ __global__ void __launch_bounds__(1024) seg_prep_tables_kernel(const void* indic
         for (int i = threadIdx.x; i < 2048; i += 1024) s_sample[i] = 0u;
         if (threadIdx.x == 0) s_rep = 0u;
     }
-    if (!bad) {
+    if (!bad && !sequence) {
         // every bag of the (sliced) table must start where a pooling factor of L puts it; 8 independent loads per round trip
         for (int64_t i0 = threadIdx.x; i0 < bag_count; i0 += 8 * 1024) {
             int64_t v[8];
@@ -348,6 +353,7 @@ struct PassSrc {
     int first;              // 1: level 1, pass 0
     int tshift;
     uint32_t bag_begin;
+    uint32_t sequence;      // 1: a sequence request -- every table has pooling 1 and the value is the lookup's POSITION in the index array
 };
 
 // one digit histogram update of a wave (the per-pass histogram kernel of mode 3): a wave whose keys all share the digit adds
@@ -657,12 +663,15 @@ __device__ __forceinline__ void load_tile_pairs(const TileDesc& td, const PassSr
             for (int r = 0; r < kTileItems; ++r) key[r] = static_cast<K>(static_cast<uint32_t>(raw[r]));
         }
         const K tkey = static_cast<K>(td.seg) << src.tshift;
+        // the value of the segment's first element: its bag -- or, for a sequence request (pooling 1), its request position
+        // in_base - first = the table's in_start; uniform over the tile
+        const uint32_t val0 = src.sequence ? td.in_base - td.first : src.bag_begin;
 #pragma unroll
         for (int r = 0; r < kTileItems; ++r) {
             const uint32_t pos = p0 + r * kWave;
             const bool valid = pos < cnt;
             key[r] = valid ? (tkey | key[r]) : static_cast<K>(0);
-            val[r] = valid ? src.bag_begin + fast_div(td.first + pos, td.pooling, td.magic) : 0u;
+            val[r] = valid ? val0 + fast_div(td.first + pos, td.pooling, td.magic) : 0u;
         }
     } else {
 #pragma unroll
@@ -1466,10 +1475,11 @@ hipError_t seg_sort_part_a(const SegSortRequest& rq, void* scratch, hipStream_t 
     if (rq.T < 1 || rq.T > kSegSortMaxTables || rq.N > 0xffffffffLL) return hipErrorInvalidValue;
     const size_t n = static_cast<size_t>(rq.N);
     const Scratch s = scratch_layout(scratch, n, rq.T);
+    if (rq.sequence && rq.weighted) return hipErrorInvalidValue;      // (a sequence request has no weights: capi.hip refuses them)
     HybArgs hyb = rq.hyb;
-    if (rq.weighted) hyb.allow = 0;
+    if (rq.weighted || rq.sequence) hyb.allow = 0;      // a sequence sort is never hybrid: it is always complete
     hipLaunchKernelGGL(seg_prep_tables_kernel, dim3(rq.T), dim3(1024), 0, stream, rq.indices, rq.offsets, rq.idx64, rq.rows, rq.T, rq.B, rq.N,
-                       rq.bag_begin, rq.bag_count, rq.weighted ? 1 : 0, s.desc, rq.zero4, hyb, s.hyb_tab, hyb.allow ? s.qtail : nullptr,
+                       rq.bag_begin, rq.bag_count, rq.sequence ? 2 : rq.weighted ? 1 : 0, s.desc, rq.zero4, hyb, s.hyb_tab, hyb.allow ? s.qtail : nullptr,
                        &s.hdr->rest_pairs);
     if (hyb.allow) {
         if (!seg_sort_hybrid_available()) return hipErrorInvalidValue;      // (sort_indices asks first and does not offer the path then)
@@ -1526,8 +1536,10 @@ hipError_t seg_sort_part_b(const SegSortRequest& rq, int mode, K* keys_a, K* key
     // a hybrid sort's part B follows the bag-major kernel and hyb_stage_kernel (seg_sort_stage_leftovers), which has turned every
     // hybrid table's segment into "no pairs" (staged for hyb_rest_kernel's LDS sort) or "n built pairs" (compacted into the a buffers)
     if (rq.hyb.allow && !rq.weighted && !hybrid_done) return hipErrorInvalidValue;
+    if (rq.sequence && (rq.weighted || rq.hyb.allow)) return hipErrorInvalidValue;
     {
-        const int chunks = rq.bag_count > 0 ? static_cast<int>((rq.bag_count + kBuildBags - 1) / kBuildBags) : 0;
+        // (a sequence request builds no keys: every table has pooling 1 -- workgroup 0, the scans and the tile descriptors, is the launch)
+        const int chunks = (rq.bag_count > 0 && !rq.sequence) ? static_cast<int>((rq.bag_count + kBuildBags - 1) / kBuildBags) : 0;
         const dim3 gp(1u + static_cast<unsigned>(chunks) * static_cast<unsigned>(rq.T));
         if (rq.weighted)
             hipLaunchKernelGGL((seg_prep_scan_kernel<K, true>), gp, dim3(1024), 0, stream, s.desc, rq.T, s.hdr, s.tiles, tm, rq.indices,
@@ -1547,6 +1559,7 @@ hipError_t seg_sort_part_b(const SegSortRequest& rq, int mode, K* keys_a, K* key
     src.idx64 = rq.idx64;
     src.tshift = rq.tshift;
     src.bag_begin = static_cast<uint32_t>(rq.bag_begin);
+    src.sequence = rq.sequence ? 1u : 0u;
     if (lookback) {
         const uint32_t cap = rq.spin_cap ? rq.spin_cap : kLbSpinCap;
         if (rb == 9) launch_lookback<K, 9>(s, tm, rq.T, src, total, keys_a, keys_b, vals_a, vals_b, cap, stream);

@@ -634,6 +634,39 @@ def _sorted_chunks_call(ts: _TableSet, op, indices, offsets, B, psw, presorted: 
         _lib.check(sorted_(sub, t0, max_rows, ws))
 
 
+def _seq_sort_indices(ts: _TableSet, indices, offsets, B, bag_begin=0, bag_count=None) -> None:
+    """The key sort of a SEQUENCE request (``pm_embseq_sort_indices``): every table's keys from the index array, the value the lookup's
+    position.  Needs only the request; ``_seq_bwd(..., presorted=True)`` consumes it.  One sort per cached workspace: at most 1024
+    tables."""
+    _no_presorted_split(ts, True)
+    if not indices.numel():
+        return
+    op = ts.request(indices, offsets, B, None, bag_begin, bag_count)
+    op.fixed_pooling = 0
+    ws = _workspace(ts, op)
+    _lib.check(_lib.load().pm_embseq_sort_indices(ctypes.byref(op), max(ts.rows), ws.data_ptr(), ws.numel(), _stream_ptr()))
+
+
+def _seq_bwd(ts: _TableSet, grad, indices, offsets, B, bag_begin, bag_count, presorted: bool, fused, sorted_, guard: _PadGuard) -> None:
+    """The sequence backward of the request, one call per range of at most 1024 tables, in table order on this stream, sharing the
+    cached workspace.  ``grad``: contiguous fp32 ``[N, D]``, row ``j`` the gradient of lookup position ``j``; a table range's positions
+    start at its first lookup ``n0`` (``_table_chunks`` rebases its offsets and advances its index pointer), so its gradient pointer is
+    advanced by ``n0 * D`` elements.  ``fused(sub, g, t0, max_rows, ws)`` issues sort + apply of a range with the gradient at ``g``,
+    ``sorted_`` the apply of a sorted one; both return the library's code.  ``guard`` goes around all ranges."""
+    _no_presorted_split(ts, presorted)
+    if not indices.numel():
+        return
+    op = ts.request(indices, offsets, B, None, bag_begin, bag_count)
+    op.fixed_pooling = 0
+    D, base, esz = ts.dims[0], indices.data_ptr(), indices.element_size()
+    guard.save()
+    for sub, t0, _, max_rows in _table_chunks(ts, op, indices, offsets, B):
+        ws = _workspace(ts, sub, max_rows)
+        n0 = ((sub.indices or 0) - base) // esz
+        _lib.check((sorted_ if presorted else fused)(sub, grad.data_ptr() + n0 * D * 4, t0, max_rows, ws))
+    guard.restore()
+
+
 def check_request(ts: _TableSet, indices, offsets, B, psw=None) -> None:
     """Raise IndexError / ValueError like torch does on the CPU path for out-of-range
     indices or non-monotone offsets (synchronises: not for timed loops)."""
@@ -1264,6 +1297,23 @@ class _FusedUpdateFn(torch.autograd.Function):
         return None, None, None, None, d_psw
 
 
+class _FusedSequenceFn(torch.autograd.Function):
+    """the sequence sibling of ``_FusedUpdateFn``: forward = ``lookup_sequence``; backward applies the module's optimizer to the ``[N, D]``
+    gradient rows in place (``sequence_optimizer_step_``; no weight.grad)"""
+
+    @staticmethod
+    def forward(ctx, anchor, module, indices, offsets, batch):
+        ctx.module, ctx.batch = module, batch
+        ctx.save_for_backward(indices, offsets)
+        return module.lookup_sequence(indices, offsets, batch)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        indices, offsets = ctx.saved_tensors
+        ctx.module.sequence_optimizer_step_(grad_out, indices, offsets, batch=ctx.batch)
+        return None, None, None, None, None
+
+
 class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     """T embedding tables in one HBM slab, looked up by ONE kernel launch.
 
@@ -1446,7 +1496,8 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         ``padding_idx`` does not affect it (``nn.Embedding``'s forward rule: the padding row comes back as stored).  Needs one common
         embedding dim; ``layout="blocked"``, mixed dims, ``pooling_mode="mean"`` (a mean module has no un-pooled form) and an ``out``
         that is not a contiguous ``[N, D]`` tensor of ``output_dtype`` on the module's device raise ValueError.  The gradient of
-        sequence rows has no batched backward here (see README, "Un-pooled lookups")."""
+        sequence rows: ``sequence_scatter_add_`` / ``sequence_optimizer_step_`` / ``sequence_dense_grad``, or ``forward_sequence`` for
+        autograd (see README, "Un-pooled lookups")."""
         if self.layout == "blocked":
             raise ValueError('lookup_sequence does not take layout="blocked"')
         if len(set(self.dims)) != 1:
@@ -1563,13 +1614,8 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             self.scatter_add_(grad, indices, offsets, alpha=-self.learning_rate, per_sample_weights=per_sample_weights,
                               batch=batch, presorted=presorted)
 
-    def dense_grad(self, grad, indices, offsets, per_sample_weights=None, batch: Optional[int] = None,
-                   method: str = "sorted", out: Optional[Sequence[torch.Tensor]] = None):
-        """fp32 dense gradients (list, one per table) -- small tables / parity tests only.  ``out``: one contiguous fp32
-        ``[rows_t, dims_t]`` buffer per table to ADD the gradient to (default: fresh zeros); a padding row of such a buffer is
-        exactly what it was before the call."""
-        ts = self._tables()
-        B = self._batch(offsets, indices, batch)
+    def _dense_grad_buffers(self, ts: _TableSet, out):
+        """the destinations of a dense gradient -- fresh zeros, or a caller's ``out`` checked -- and their device pointer array"""
         if out is None:
             outs = [torch.zeros(r, d, dtype=torch.float32, device=ts.device) for r, d in zip(self.rows, self.dims)]
         else:
@@ -1577,7 +1623,16 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             if len(outs) != len(self.rows) or any(o.dtype != torch.float32 or tuple(o.shape) != (r, d) or not o.is_contiguous() or
                                                   o.device != ts.device for o, r, d in zip(outs, self.rows, self.dims)):
                 raise ValueError("out must hold one contiguous float32 [rows_t, dims_t] tensor per table on the module's device")
-        d_ptrs = torch.tensor([o.data_ptr() for o in outs], dtype=torch.int64, device=ts.device)
+        return outs, torch.tensor([o.data_ptr() for o in outs], dtype=torch.int64, device=ts.device)
+
+    def dense_grad(self, grad, indices, offsets, per_sample_weights=None, batch: Optional[int] = None,
+                   method: str = "sorted", out: Optional[Sequence[torch.Tensor]] = None):
+        """fp32 dense gradients (list, one per table) -- small tables / parity tests only.  ``out``: one contiguous fp32
+        ``[rows_t, dims_t]`` buffer per table to ADD the gradient to (default: fresh zeros); a padding row of such a buffer is
+        exactly what it was before the call."""
+        ts = self._tables()
+        B = self._batch(offsets, indices, batch)
+        outs, d_ptrs = self._dense_grad_buffers(ts, out)
         _bwd(ts, grad, indices, offsets, B, d_ptrs, torch.float32, 1.0, per_sample_weights, method=method, pad=self._pad_dev(),
              mean=self._mean, out16=self._out16)
         return outs
@@ -1609,6 +1664,98 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
         B = self._batch(offsets, indices, batch)
         return _psw_grad(self._tables(), grad, indices, offsets, B, None, out, bag_begin, bag_count, pad=self._pad_dev(), out16=self._out16)
+
+    # -- sequence (un-pooled) gradients ----------------------------------------------------------
+    def _seq_request(self, what: str, indices, offsets, batch, grad=None):
+        """What the sequence calls share, refusals first and on the host: ``(table set, B, fp32 gradient or None)``.  ``grad`` is ``[N, D]``
+        in fp32 or the module's 16-bit ``output_dtype``; a 16-bit one is widened exactly, once, into an fp32 scratch (a torch cast:
+        exact, and ``[N, D]`` has no bag structure for ``pm_embbag_grad_widen``); the caller's tensor is never modified."""
+        if self.layout == "blocked":
+            raise ValueError(f'{what} does not take layout="blocked"')
+        if len(set(self.dims)) != 1:
+            raise ValueError(f"{what} needs one common embedding dim")
+        if self._mean:
+            raise ValueError(f'{what} does not take pooling_mode="mean": a mean module has no un-pooled form')
+        if grad is not None:
+            shape = (indices.numel(), self.dims[0])
+            if (grad.dtype != torch.float32 and grad.dtype != self._out16) or tuple(grad.shape) != shape:
+                also = "" if self._out16 is None else f" or {str(self._out16).replace('torch.', '')} (the module's output_dtype)"
+                raise ValueError(f"{what}: grad must be float32{also} of shape {shape}, one row per lookup position")
+            _require_device(grad, "grad")
+            grad = grad.contiguous()
+            if grad.dtype != torch.float32:
+                grad = grad.float()
+        _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
+        return self._tables(), self._batch(offsets, indices, batch), grad
+
+    def sequence_sort_indices(self, indices, offsets, batch: Optional[int] = None, bag_begin=0, bag_count=None) -> None:
+        """Pre-sort a sequence request (``pm_embseq_sort_indices``; can overlap the forward): keys ``(table, row)``, values the lookup
+        positions.  ``sequence_scatter_add_`` / ``sequence_optimizer_step_`` with ``presorted=True`` consume it; the pooled calls refuse
+        a workspace that holds a sequence sort, and the other way round.  At most 1024 tables."""
+        ts, B, _ = self._seq_request("sequence_sort_indices", indices, offsets, batch)
+        _seq_sort_indices(ts, indices, offsets, B, bag_begin, bag_count)
+
+    def sequence_scatter_add_(self, grad, indices, offsets, alpha: float, batch: Optional[int] = None, bag_begin=0, bag_count=None,
+                              presorted: bool = False) -> None:
+        """The batched backward of ``lookup_sequence``: in place ``W_t[indices[j]] += alpha * grad[j]`` for every lookup position ``j`` of
+        the bag slice, ``t`` the table that owns ``j`` -- per row in ascending position order, deterministic, no atomics; one sort and one
+        apply for all T tables (``pm_embseq_bwd_fused``; 1024 tables per call).  ``grad``: ``[N, D]`` fp32 or the module's 16-bit
+        ``output_dtype``; rows of positions outside the slice are never read.  Padding rows keep their bits.  Does not run
+        ``bounds_check_mode`` (``sanitize_`` is the call on its own)."""
+        ts, B, g = self._seq_request("sequence_scatter_add_", indices, offsets, batch, grad)
+        self._seq_scatter(ts, g, indices, offsets, B, ts.d_ptrs, self.weights.dtype, alpha, bag_begin, bag_count, presorted)
+
+    def _seq_scatter(self, ts, g, indices, offsets, B, dst_ptrs_dev, dst_dtype, alpha, bag_begin=0, bag_count=None, presorted=False) -> None:
+        L, s, dt, D = _lib.load(), _stream_ptr(), _WDTYPE[dst_dtype], ts.dims[0]
+
+        def call(fn):
+            return lambda sub, gp, t0, max_rows, ws: fn(ctypes.byref(sub), gp, D, dst_ptrs_dev.data_ptr() + 8 * t0, dt, float(alpha), max_rows,
+                                                        ws.data_ptr(), ws.numel(), s)
+        _seq_bwd(ts, g, indices, offsets, B, bag_begin, bag_count, presorted, call(L.pm_embseq_bwd_fused), call(L.pm_embseq_bwd_sorted),
+                 _PadGuard(ts, self._pad_dev(), dst_ptrs_dev, dst_dtype))
+
+    def sequence_optimizer_step_(self, grad, indices, offsets, batch: Optional[int] = None, presorted: bool = False) -> None:
+        """The module's optimizer on sequence gradient rows (what ``forward_sequence(...).backward()`` applies with ``fused_update``): SGD
+        (``sequence_scatter_add_`` with ``alpha = -learning_rate``), exact row-wise Adagrad or exact element-wise Adagrad, with the
+        module's weight decay and stochastic rounding -- the arithmetic of ``optimizer_step_`` on the one-table request "one bag per
+        lookup", for all T tables in one sort and one apply (``pm_embseq_bwd_fused_adagrad``).  Stochastic rounding draws from the same
+        ``_sr_step`` seed stream as ``adagrad_step_``."""
+        ts, B, g = self._seq_request("sequence_optimizer_step_", indices, offsets, batch, grad)
+        if self.optimizer not in ("rowwise_adagrad", "adagrad"):
+            self._seq_scatter(ts, g, indices, offsets, B, ts.d_ptrs, self.weights.dtype, -self.learning_rate, presorted=presorted)
+            return
+        self.momentum_table(0)
+        self._sr_step += 1          # a fresh stochastic-rounding stream every step, reproducible run to run
+        L, s, wdt, D, elem = _lib.load(), _stream_ptr(), _WDTYPE[ts.dtype], ts.dims[0], self.optimizer == "adagrad"
+        seed, mom = 0x5EED0000 + self._sr_step, self._mom_ptrs
+
+        def call(fn):      # (every table range gets a seed of its own, as in _adagrad)
+            def issue(sub, gp, t0, max_rows, ws):
+                opt = _lib.pm_rowwise_adagrad(float(self.learning_rate), float(self.eps), float(self.weight_decay),
+                                              _WD_MODES[self.weight_decay_mode], 1 if self.stochastic_rounding else 0, 0,
+                                              (seed + (t0 << 32)) & (2**64 - 1))
+                return fn(ctypes.byref(sub), gp, D, ts.d_ptrs.data_ptr() + 8 * t0, wdt, mom.data_ptr() + 8 * t0, ctypes.byref(opt),
+                          1 if elem else 0, max_rows, ws.data_ptr(), ws.numel(), s)
+            return issue
+        guard = _PadGuard(ts, self._pad_dev(), ts.d_ptrs, ts.dtype, mom, _lib.PM_PAD_STATE_ELEM if elem else _lib.PM_PAD_STATE_ROW)
+        _seq_bwd(ts, g, indices, offsets, B, 0, None, presorted, call(L.pm_embseq_bwd_fused_adagrad), call(L.pm_embseq_bwd_sorted_adagrad),
+                 guard)
+
+    def sequence_dense_grad(self, grad, indices, offsets, batch: Optional[int] = None, out: Optional[Sequence[torch.Tensor]] = None):
+        """fp32 dense gradients of sequence rows (list, one ``[rows_t, D]`` per table): ``out_t[r] += sum of grad[j]`` over table t's
+        lookups of row r in position order -- ``aten::embedding_dense_backward`` per table, in one sort and one apply.  ``out``: as for
+        ``dense_grad`` (buffers to ADD to; default fresh zeros; a padding row is exactly what it was before the call)."""
+        ts, B, g = self._seq_request("sequence_dense_grad", indices, offsets, batch, grad)
+        outs, d_ptrs = self._dense_grad_buffers(ts, out)
+        self._seq_scatter(ts, g, indices, offsets, B, d_ptrs, torch.float32, 1.0)
+        return outs
+
+    def forward_sequence(self, indices, offsets, batch: Optional[int] = None):
+        """``lookup_sequence`` with autograd glue: with ``fused_update`` and grad enabled, ``.backward(g)`` on the ``[N, D]`` result applies
+        ``sequence_optimizer_step_(g, ...)`` in place (no weight.grad), as ``forward`` does for pooled lookups."""
+        if self.fused_update and torch.is_grad_enabled():
+            return _FusedSequenceFn.apply(self._anchor, self, indices, offsets, batch)
+        return self.lookup_sequence(indices, offsets, batch)
 
     def extra_repr(self) -> str:
         return f"output_dtype={self.output_dtype}" if self._out16 is not None else ""
