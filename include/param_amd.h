@@ -693,6 +693,35 @@ int pm_set_tuning(int32_t unroll, int32_t bags_per_block, int32_t xcd_affine, in
 int pm_set_forward_tuning(int32_t stage_out, int32_t flat_grid, int32_t flat_target);
 
 /*
+ * Which launch geometry a forward entry point WOULD use for a request under the knobs as they stand now (pm_set_tuning,
+ * pm_set_forward_tuning and the environment switches, which are read once per process): the status word of the forward.  Host only:
+ * nothing is launched, no device memory is touched and no pointer of the request is dereferenced (they are only tested for NULL, as
+ * the launching call tests them).  The request is validated exactly as the launching entry point validates it (the same error codes
+ * and pm_last_error texts for what every entry point refuses; an entry point's OWN argument rules -- a NULL out, mean with weights --
+ * are not part of the plan), and the plan is made by the very functions that call uses (param_amd/csrc/launch_plan.h).
+ *   kind  PM_PLAN_BASE       the plain bag-count tiling of every backward, check, bounds, psw-grad, split, mean-grad and widen entry
+ *         PM_PLAN_FORWARD    pm_embbag_fwd
+ *         PM_PLAN_QUANTIZED  pm_embbag_fwd_quantized
+ *         PM_PLAN_PADDED     pm_embbag_fwd_padded, pm_embbag_fwd_mean (4-byte output elements)
+ *         PM_PLAN_PADDED16   pm_embbag_fwd_out16 (2-byte output elements)
+ *   out   the twelve members of the plan in this order: tiles_per_table, bags_per_block, idx_cap, xcd_affine, nt_loads, ordered,
+ *         stage_out, stage_bags, flat_bags, flat_target, flat_compact, unroll (0 where the launch has none).  flat_bags > 0: the
+ *         flat-walk kernel; otherwise the tile kernel -- ordered, else staged where stage_out > 0, else plain.
+ * pm_embedding_gather_plan is the same for pm_embedding_gather: vec, group_lanes, tile, col_passes, unroll, lds_borders,
+ * xcd_contiguous, grid -- in this order.
+ * For tests and tools (tests/test_gpu_plan_sweep.py asserts the plan of every launch it compares).  Thread-safe like every call; a
+ * pm_set_* from another thread lands before or after the query.  Unknown kind / NULL out: PM_ERR_INVALID.
+ * The ABI version is unchanged (8): a client that needs these two finds out at symbol resolution.
+ */
+#define PM_PLAN_BASE      0
+#define PM_PLAN_FORWARD   1
+#define PM_PLAN_QUANTIZED 2
+#define PM_PLAN_PADDED    3
+#define PM_PLAN_PADDED16  4
+int pm_embbag_plan(const pm_embbag_batch* op, int32_t kind, int32_t out[12]);
+int pm_embedding_gather_plan(const pm_embbag_batch* op, int64_t out[8]);
+
+/*
  * Tuning knobs of the sorted backward (process-wide; -1 = default, which the environment can change:
  * PARAM_AMD_SORT=rocprim, PARAM_AMD_SORT_ORDER=row, PARAM_AMD_BWD_XCD=0, PARAM_AMD_BWD_PHASES=2):
  *   sort_impl   0 (default): the segmented sort of round 3 -- per-table segments, per-table pooling factors and (for batch

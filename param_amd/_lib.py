@@ -86,7 +86,15 @@ EXPORTED_SYMBOLS = (
     "pm_embseq_bwd_fused",
     "pm_embseq_bwd_sorted_adagrad",
     "pm_embseq_bwd_fused_adagrad",
+    "pm_embbag_plan",
+    "pm_embedding_gather_plan",
 )
+
+# pm_embbag_plan (include/param_amd.h): the kinds, and the members of the two plans in the order the queries fill them
+PM_PLAN_BASE, PM_PLAN_FORWARD, PM_PLAN_QUANTIZED, PM_PLAN_PADDED, PM_PLAN_PADDED16 = 0, 1, 2, 3, 4
+PLAN_FIELDS = ("tiles_per_table", "bags_per_block", "idx_cap", "xcd_affine", "nt_loads", "ordered", "stage_out", "stage_bags",
+               "flat_bags", "flat_target", "flat_compact", "unroll")
+GATHER_PLAN_FIELDS = ("vec", "group_lanes", "tile", "col_passes", "unroll", "lds_borders", "xcd_contiguous", "grid")
 
 
 class pm_rowwise_adagrad(ctypes.Structure):
@@ -289,6 +297,11 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     for fn in (L.pm_embseq_bwd_sorted_adagrad, L.pm_embseq_bwd_fused_adagrad):      # (.., state, opt, elementwise 0 / 1, ..)
         fn.restype = ctypes.c_int
         fn.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i64, vp, i32, vp, ctypes.POINTER(pm_rowwise_adagrad), i32, i64, vp, i64, vp]
+    # the plan queries (host only): (op, PM_PLAN_*, int32 out[12]) and (op, int64 out[8])
+    L.pm_embbag_plan.restype = ctypes.c_int
+    L.pm_embbag_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, ctypes.POINTER(i32)]
+    L.pm_embedding_gather_plan.restype = ctypes.c_int
+    L.pm_embedding_gather_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), ctypes.POINTER(i64)]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]
@@ -355,6 +368,21 @@ def set_forward_tuning(stage_out: int = -1, flat_grid: int = -1, flat_target: in
     flat_grid (flat-walk forward: short-bag / mixed-dim requests) 1 (default) = workgroups walking the tile order, 0 = one workgroup
     per (table, smallest tile), N > 1 = exactly N workgroups; flat_target = lookups per flat-walk tile (default 256)"""
     check(load().pm_set_forward_tuning(stage_out, flat_grid, flat_target))
+
+
+def embbag_plan(op: pm_embbag_batch, kind: int) -> dict:
+    """``pm_embbag_plan``: the launch geometry the forward entry point of ``kind`` (``PM_PLAN_*``) would use for ``op`` under the
+    knobs as they stand -- ``PLAN_FIELDS`` by name.  Host only: nothing is launched."""
+    out = (ctypes.c_int32 * len(PLAN_FIELDS))()
+    check(load().pm_embbag_plan(ctypes.byref(op), kind, out))
+    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
+
+
+def embedding_gather_plan(op: pm_embbag_batch) -> dict:
+    """``pm_embedding_gather_plan``: the geometry ``pm_embedding_gather`` would use for ``op`` -- ``GATHER_PLAN_FIELDS`` by name"""
+    out = (ctypes.c_int64 * len(GATHER_PLAN_FIELDS))()
+    check(load().pm_embedding_gather_plan(ctypes.byref(op), out))
+    return dict(zip(GATHER_PLAN_FIELDS, (int(v) for v in out)))
 
 
 def set_backward_tuning(sort_impl: int = -1, order: int = -1, xcd_affine: int = -1, max_phases: int = -1) -> None:

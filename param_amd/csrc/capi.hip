@@ -79,6 +79,15 @@ enum class PlanKind { base, forward, quantized, padded, padded16 };
 int validate_request(const pm_embbag_batch* op, int elem_dtype, const pm::PlanKnobs& knobs, pm::PlanShape* shape = nullptr);
 void fill_params(const pm_embbag_batch* op, const pm::LaunchPlan& plan, pm::KParams& p);
 
+// the plan of one kind (make_params for the launching entry points, pm_embbag_plan for the query: one choice, made here)
+pm::LaunchPlan plan_of(const pm_embbag_batch& op, const pm::PlanShape& shape, const pm::PlanKnobs& knobs, PlanKind kind) {
+    return kind == PlanKind::forward     ? pm::plan_forward(op, shape, knobs)
+           : kind == PlanKind::quantized ? pm::plan_quantized(op, shape, knobs)
+           : kind == PlanKind::padded    ? pm::plan_padded(op, shape, knobs, 4)
+           : kind == PlanKind::padded16  ? pm::plan_padded(op, shape, knobs, 2)
+                                         : pm::plan_base(op, shape, knobs);
+}
+
 // Validate the host-visible part of a request and derive the launch geometry: the plain bag-count tiling (base) for every entry point
 // but the forwards, which name their own plan.  unroll: the plan's (forward, quantized).
 int make_params(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p, PlanKind kind = PlanKind::base, int* unroll = nullptr) {
@@ -86,11 +95,7 @@ int make_params(const pm_embbag_batch* op, int elem_dtype, pm::KParams& p, PlanK
     pm::PlanShape shape;
     const int rc = validate_request(op, elem_dtype, knobs, &shape);
     if (rc != PM_OK) return rc;
-    const pm::LaunchPlan plan = kind == PlanKind::forward     ? pm::plan_forward(*op, shape, knobs)
-                                : kind == PlanKind::quantized ? pm::plan_quantized(*op, shape, knobs)
-                                : kind == PlanKind::padded    ? pm::plan_padded(*op, shape, knobs, 4)
-                                : kind == PlanKind::padded16  ? pm::plan_padded(*op, shape, knobs, 2)
-                                                              : pm::plan_base(*op, shape, knobs);
+    const pm::LaunchPlan plan = plan_of(*op, shape, knobs, kind);
     fill_params(op, plan, p);
     if (unroll) *unroll = plan.unroll;
     return PM_OK;
@@ -316,6 +321,34 @@ int pm_set_forward_tuning(int32_t stage_out, int32_t flat_grid, int32_t flat_tar
     g_stage_out.store(stage_out);
     g_flat_grid.store(flat_grid);
     g_flat_target.store(flat_target);
+    return PM_OK;
+}
+
+// ---- the plan queries: what a forward entry point would launch with, from the same validate_request / plan_* calls it makes ------------
+int pm_embbag_plan(const pm_embbag_batch* op, int32_t kind, int32_t out[12]) {
+    if (kind < PM_PLAN_BASE || kind > PM_PLAN_PADDED16) return fail(PM_ERR_INVALID, "kind must be PM_PLAN_BASE .. PM_PLAN_PADDED16");
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    static_assert(sizeof(pm::LaunchPlan) == 12 * sizeof(int32_t), "the query copies the twelve members in their order");
+    const pm::PlanKnobs knobs = current_knobs();
+    pm::PlanShape shape;
+    const int rc = validate_request(op, op ? op->weight_dtype : -1, knobs, &shape);
+    if (rc != PM_OK) return rc;
+    constexpr PlanKind kinds[] = {PlanKind::base, PlanKind::forward, PlanKind::quantized, PlanKind::padded, PlanKind::padded16};
+    const pm::LaunchPlan p = plan_of(*op, shape, knobs, kinds[kind]);
+    const int32_t v[12] = {p.tiles_per_table, p.bags_per_block, p.idx_cap, p.xcd_affine, p.nt_loads, p.ordered,
+                           p.stage_out, p.stage_bags, p.flat_bags, p.flat_target, p.flat_compact, p.unroll};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return PM_OK;
+}
+
+int pm_embedding_gather_plan(const pm_embbag_batch* op, int64_t out[8]) {
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const pm::PlanKnobs knobs = current_knobs();
+    const int rc = validate_request(op, op ? op->weight_dtype : -1, knobs);
+    if (rc != PM_OK) return rc;
+    const pm::GatherPlan g = pm::plan_gather(*op, op->weight_dtype, knobs);
+    const int64_t v[8] = {g.vec, g.group_lanes, g.tile, g.col_passes, g.unroll, g.lds_borders, g.xcd_contiguous, g.grid};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
     return PM_OK;
 }
 

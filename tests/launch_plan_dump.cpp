@@ -1,6 +1,7 @@
 // tests/launch_plan_dump.cpp -- prints what param_amd/csrc/launch_plan.h plans (tests/test_launch_plan_host.py builds and runs it).
 // stdin: one case per line, 27 integers --
-//   kind (0 base, 1 forward, 2 quantized, 3 padded with 4-byte output elements, 4 padded with 2-byte ones)
+//   kind (0 base, 1 forward, 2 quantized, 3 padded with 4-byte output elements, 4 padded with 2-byte ones; 5 the row gather,
+//         which prints the eight members of pm::GatherPlan instead)
 //   the request: num_tables batch num_indices bag_begin bag_count max_dim min_dim dtype weighted table_group grad_block_shift grad_block_extra
 //   what the setters were given: unroll bags_per_block xcd_affine nt_loads | stage_out flat_grid flat_target
 //   the environment's values: stage flat flat_maxl flat_target flat_bags tile_major flat_compact
@@ -54,6 +55,12 @@ int main() {
             case 2: p = pm::plan_quantized(op, op.weight_dtype, k); break;
             case 3: p = pm::plan_padded(op, op.weight_dtype, k, 4); break;
             case 4: p = pm::plan_padded(op, op.weight_dtype, k, 2); break;
+            case 5: {
+                const pm::GatherPlan g = pm::plan_gather(op, op.weight_dtype, k);
+                printf("%d %d %d %d %d %d %d %lld\n", g.vec, g.group_lanes, g.tile, g.col_passes, g.unroll, g.lds_borders, g.xcd_contiguous,
+                       static_cast<long long>(g.grid));
+                continue;
+            }
             default: return 2;
         }
         printf("%d %d %d %d %d %d %d %d %d %d %d %d\n", p.tiles_per_table, p.bags_per_block, p.idx_cap, p.xcd_affine, p.nt_loads, p.ordered,

@@ -174,15 +174,18 @@ def test_staged_output_forward_bit_identical(coracle, wdt, D):
 def test_staged_forward_when_lookups_divide_evenly_but_bags_are_ragged(coracle):
     """the output burst is chosen from a host-visible fact (lookups divide evenly over the bags) and sizes the index tile
     for the AVERAGE bag: a ragged request that happens to divide evenly -- a quarter of the bags 80 lookups long, the rest
-    empty -- overflows that tile and must take the direct-index path, with the same bits"""
+    empty -- overflows that tile and must take the direct-index path, with the same bits.
+    What this request plans (``pm_embbag_plan``: 32 8 512 3 0 0 128 8 0 0 0 8): a request this small ends at ONE bag per lane group --
+    staged tiles of 8 bags, an index tile of 512 entries, unroll 8 -- not at the product's 32-bag tile.  The staged 32-bag tile with a
+    tile that overflows its index tile is run by tests/test_gpu_plan_sweep.py."""
     from param_amd import BatchedEmbeddingBagMI355
 
     rng = np.random.default_rng(77)
     T, R, D, B = 3, 4000, 128, 256
     lens = np.zeros(T * B, dtype=np.int64)
-    lens[::4] = 80                                   # average 20; tiles of 32 bags hold 640 lookups on average ...
+    lens[::4] = 80                                   # average 20; tiles of 8 bags hold 160 lookups on average ...
     lens[:64] = 0
-    lens[64:96] = 160                                # ... but this one 5120
+    lens[64:96] = 160                                # ... but these four 1280 each: more than the 512-entry index tile
     lens[96:128] = 0
     # make the total divide evenly: pad the last bag
     short = (-int(lens.sum())) % (T * B)

@@ -13,8 +13,8 @@ mix specials with ordinary values inside one 16-byte lane load, and the rest are
 
 The alternates-only atomic backward (``method="atomic"``) is left out: it is built on unsafe floating-point atomics and is a
 baseline, not the product.  ``scatter_add_`` has no stochastic store: the stochastic-rounding tests cover both Adagrad flavours.
-Every backward and Adagrad test asserts the route it took (``sort_status``); the forward kernel is the library's choice and is not
-reported, so the forward tests name their requests.  Every test asserts the number of special elements it compared.
+Every backward and Adagrad test asserts the route it took (``sort_status``); the forward kernel is the library's choice
+(``pm_embbag_plan`` reports it; tests/test_gpu_plan_sweep.py runs every choice), so the forward tests name their requests.  Every test asserts the number of special elements it compared.
 """
 import numpy as np
 import pytest
@@ -106,8 +106,12 @@ def _forward_case(kind, dims, L, seed):
 def test_forward_every_kernel_same_bits_as_the_oracle(coracle, kind, route, dims, L):
     """The requests that make the library choose its forward kernels -- fixed pooling (tile kernel, staged output), ragged bags (tile
     kernel, or the flat-walk kernel where the request is staged: short bags at small D), mixed dims (flat-walk kernel, lane group per
-    table).  The choice is the library's (capi.hip) and no status word reports it: the ids name the REQUEST, not the kernel, and
-    the tile kernel's bag-ordered instance (more bags than one block's share) is not reached at B = 257.  T = 3; int32 and int64
+    table).  The choice is the library's (launch_plan.h); ``pm_embbag_plan`` reports it, and at B = 257 it is the small-request corner
+    of the plan: staged tiles of ONE bag per lane group (32 / 8 / 4 bags at D = 16 / 128 / 512, unroll 4 / 2 / 4) for fixed pooling, the
+    flat walk for the ragged requests at D = 16 and 128, plain 4-bag tiles at unroll 8 at D = 512 -- never a tile of more bags than
+    lane groups, so never the longest-bag-first instance.  The ids name the REQUEST, not the kernel.  The variants the product takes
+    at benchmark size (32-bag staged and ordered tiles, every unroll) are run by tests/test_gpu_plan_sweep.py, on ordinary values.
+    T = 3; int32 and int64
     indices, weighted (weights 0, -0, +-Inf, NaN, 1e-30, 1e-40 among ordinary ones) and unweighted, layouts ``bd`` and ``tbd``.
     fp16 tables: their subnormals must widen exactly (the oracle's widening is torch's).  The named bags are asserted one by one."""
     T, B = 3, 257

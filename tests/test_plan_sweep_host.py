@@ -1,0 +1,234 @@
+"""The plan sweep on the CPU: what every case of tests/plan_sweep.py plans, pinned in tests/plan_sweep_host.json, and the conditions that
+keep the case list from quietly shrinking.
+
+launch_plan_dump.cpp is built as tests/test_launch_plan_host.py builds it and plans every case from its sizes and knobs; the JSON holds
+one row per case -- the plan's members (twelve; the gather's eight) and the variant label ``plan_sweep.label`` derives from them.
+tests/test_gpu_plan_sweep.py then requires ``pm_embbag_plan`` to report exactly these rows next to every launch it compares.
+
+``PARAM_AMD_REWRITE_PLAN_SWEEP=1 pytest tests/test_plan_sweep_host.py`` writes the JSON anew from what launch_plan.h plans (read the
+diff: a changed row is a changed kernel choice)."""
+import json
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from tests import plan_sweep as S
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+PINNED = os.path.join(HERE, "plan_sweep_host.json")
+REWRITE = os.environ.get("PARAM_AMD_REWRITE_PLAN_SWEEP") == "1"
+
+
+@pytest.fixture(scope="module")
+def planned(tmp_path_factory):
+    """{case name: plan members} from launch_plan_dump"""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = str(tmp_path_factory.mktemp("plan_sweep") / "launch_plan_dump")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-O1", "-I", os.path.join(ROOT, "include"),
+                    "-I", os.path.join(ROOT, "param_amd", "csrc"), os.path.join(HERE, "launch_plan_dump.cpp"), "-o", exe], check=True)
+    text = "".join(c.dump_line() + "\n" for c in S.CASES)
+    out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(S.CASES)
+    return {c.name: [int(x) for x in line.split()] for c, line in zip(S.CASES, out)}
+
+
+def _rows(planned):
+    return {c.name: {"plan": planned[c.name], "label": " ".join(sorted(S.label(c, planned[c.name])))} for c in S.CASES}
+
+
+def _pinned():
+    return json.load(open(PINNED))["rows"]
+
+
+def test_every_case_plans_its_pinned_row(planned):
+    rows = _rows(planned)
+    if REWRITE:
+        with open(PINNED, "w") as f:
+            f.write('{\n "plan_fields": %s,\n "gather_fields": %s,\n "rows": {\n' % (json.dumps(list(S.PLAN_FIELDS)), json.dumps(list(S.GATHER_FIELDS))))
+            f.write(",\n".join("  %s: %s" % (json.dumps(name), json.dumps(row)) for name, row in rows.items()))
+            f.write("\n }\n}\n")
+    pinned = _pinned()
+    assert list(pinned) == [c.name for c in S.CASES], "the case list and the pinned rows name different cases"
+    bad = [(name, pinned[name], row) for name, row in rows.items() if row != pinned[name]]
+    assert not bad, f"{len(bad)} of {len(rows)} rows differ; the first (case, pinned, planned): {bad[0]}"
+
+
+def test_the_pinned_rows_are_not_being_rewritten():
+    assert not REWRITE, "PARAM_AMD_REWRITE_PLAN_SWEEP=1 rewrote tests/plan_sweep_host.json: read its diff, then run without the flag"
+
+
+def test_the_plan_query_reports_the_pinned_rows_without_a_gpu():
+    """``pm_embbag_plan`` / ``pm_embedding_gather_plan`` launch nothing and read no device memory: on a CPU-only machine, with dummy
+    pointers, they report the pinned row of every case under its knobs -- the library's ``current_knobs`` and the dump tool's
+    ``resolve_knobs`` agree.  The groups with an environment setting are asked in one child process each."""
+    import sys
+
+    from tests import plan_sweep_worker as W
+
+    rows = _pinned()
+    got = {}
+    for group in S.GROUPS:
+        if group not in S.ENV_GROUPS:
+            got.update(W.host_plans(group))
+            continue
+        env = {k: v for k, v in os.environ.items() if k not in S.ENV}
+        env.update({k: str(v) for k, v in next(c.env for c in S.CASES if c.group == group).items()})
+        env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
+        r = subprocess.run([sys.executable, "-m", "tests.plan_sweep_worker", "--plans", group], env=env, cwd=ROOT, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        got.update(json.loads(r.stdout.splitlines()[-1]))
+    bad = [(name, rows[name]["plan"], plan) for name, plan in got.items() if plan != rows[name]["plan"]]
+    assert len(got) == len(S.CASES) and not bad, f"{len(bad)} differ; the first (case, pinned, reported): {bad[0]}"
+
+
+def test_the_plan_query_refuses_what_the_launching_call_refuses():
+    import ctypes
+
+    from param_amd import _lib
+
+    L = _lib.load()
+    out = (ctypes.c_int32 * 12)()
+    op = _lib.pm_embbag_batch()
+    assert L.pm_embbag_plan(ctypes.byref(op), _lib.PM_PLAN_FORWARD, out) == _lib.PM_ERR_INVALID and b"num_tables" in L.pm_last_error()
+    assert L.pm_embbag_plan(None, _lib.PM_PLAN_FORWARD, out) == _lib.PM_ERR_INVALID
+    op.num_tables, op.weight_dtype, op.index_dtype, op.max_dim = 1, _lib.PM_F32, _lib.PM_I64, 8
+    op.tables = op.rows = op.dims = op.out_offsets = 8
+    assert L.pm_embbag_plan(ctypes.byref(op), 5, out) == _lib.PM_ERR_INVALID and b"kind" in L.pm_last_error()
+    assert L.pm_embbag_plan(ctypes.byref(op), _lib.PM_PLAN_BASE, None) == _lib.PM_ERR_INVALID
+    assert L.pm_embedding_gather_plan(ctypes.byref(op), None) == _lib.PM_ERR_INVALID
+    assert L.pm_embbag_plan(ctypes.byref(op), _lib.PM_PLAN_FORWARD, out) == _lib.PM_OK                # an empty request has a plan
+    op.max_dim = 6
+    assert L.pm_embbag_plan(ctypes.byref(op), _lib.PM_PLAN_FORWARD, out) == _lib.PM_ERR_UNSUPPORTED and b"multiple of 4" in L.pm_last_error()
+
+
+def test_the_plans_the_issue_checked():
+    """the plans quoted where the sweep was asked for, member for member"""
+    rows = _pinned()
+    p = lambda name: " ".join(map(str, rows[name]["plan"]))                                  # noqa: E731
+    assert p("tile_staged_u2_plain") == "3 32 1280 3 0 0 128 32 0 0 0 2"
+    assert p("tile_ordered_u2_plain").startswith("4 32 4096 0 0 1 0 32 ")
+    assert p("tile_rank128_weighted").startswith("3 128 4096 0 0 1 0 128 ")
+    assert p("env_tile_major_ordered").startswith("4 32 4096 2 0 1 ")
+    assert p("auto_bench_fp32") == "43 32 1280 1 0 0 128 32 0 0 0 2"
+    assert p("auto_t26") == "80 32 1280 3 0 0 128 32 0 0 0 2"
+    assert p("auto_ragged_long") == "129 32 4096 1 0 1 0 32 0 0 0 2"
+
+
+def test_auto_cases_plan_what_the_benchmark_shapes_plan():
+    """no knob set: the three product-scale cases take the kernel variant of rows bench_fp32, t26 and ragged_long of
+    tests/launch_plan_host.json -- every member but tiles_per_table, which counts the bags"""
+    spec = json.load(open(os.path.join(HERE, "launch_plan_host.json")))
+    rows = _pinned()
+    for case, fixture in (("auto_bench_fp32", "bench_fp32"), ("auto_t26", "t26"), ("auto_ragged_long", "ragged_long")):
+        c = next(c for c in S.CASES if c.name == case)
+        assert not c.tuning and not c.forward and not c.env and c.entry == "fwd" and 1_200_000 < c.req.N < 1_400_000
+        want = [r[3] for r in spec["rows"] if r[:3] == [fixture, "default", "forward"]]
+        assert len(want) == 1 and rows[case]["plan"][1:] == want[0][1:], (case, rows[case]["plan"], want)
+        assert rows[case]["plan"][0] == -(-c.req.B // want[0][1])
+
+
+def test_the_sweep_reaches_every_variant():
+    """conditions on the case list -- on the labels derived from the PLANS -- so that it cannot quietly stop covering a variant"""
+    rows = _pinned()
+    cases = [(c, set(rows[c.name]["label"].split()), dict(zip(S.PLAN_FIELDS, rows[c.name]["plan"]))) for c in S.CASES]
+    missing = []
+
+    def need(what, cond, at_least=1):
+        if sum(1 for c, w, p in cases if cond(c, w, p)) < at_least:
+            missing.append(what)
+
+    fwd = lambda c: c.entry == "fwd" and not c.env                                            # noqa: E731
+    wt = {False: "unweighted", True: "weighted"}
+    # tile kernel: unroll x weighted x {ordered, staged, plain}, fp32, G = 32, more than one bag per lane group
+    for u in S.UNROLLS:
+        for wgt in (False, True):
+            for variant in ("ordered-bitonic", "staged", "plain"):
+                need(f"tile {variant} u{u} {wt[wgt]}",
+                     lambda c, w, p: fwd(c) and {"tile", "f32", "G32", f"u{u}", wt[wgt], variant, "tile>NG"} <= w)
+    for kind in S.DTYPE:
+        for G in (8, 16, 32, 64):
+            for variant in ("ordered-bitonic", "staged"):
+                need(f"tile {variant} {kind} G{G}", lambda c, w, p: fwd(c) and {"tile", kind, f"G{G}", "u2", variant, "tile>NG"} <= w)
+    need("bitonic, partial last tile, direct-index tile", lambda c, w, p: {"tile", "ordered-bitonic", "partial", "direct"} <= w)
+    need("rank at 128 bags, weighted, direct", lambda c, w, p: {"tile", "ordered-rank", "bpb128", "weighted", "direct"} <= w)
+    need("rank at 1024 bags, direct", lambda c, w, p: {"tile", "ordered-rank", "bpb1024", "direct"} <= w)
+    need("staged, power-of-two row", lambda c, w, p: {"tile", "staged", "burst-pow2", "partial"} <= w)
+    need("staged 32-bag tile that overflows its index tile", lambda c, w, p: {"tile", "staged", "bpb32", "direct"} <= w and p["idx_cap"] == 1280, 2)
+    need("staged, D = 56", lambda c, w, p: {"tile", "staged", "burst-div"} <= w and c.dims[0] == 56)
+    for x in (0, 1, 3):
+        need(f"tile staged xcd_affine {x}", lambda c, w, p: fwd(c) and {"tile", "staged", f"xcd{x}"} <= w)
+    need("xcd_affine 1 on 8 tables", lambda c, w, p: {"tile", "xcd1"} <= w and c.req.T == 8)
+    need("xcd_affine 3, tile count not divisible by 8", lambda c, w, p: {"tile", "xcd3"} <= w and c.req.T * p["tiles_per_table"] % 8 != 0)
+    need("tile nt_loads staged", lambda c, w, p: {"tile", "staged", "nt1"} <= w)
+    need("tile nt_loads ordered", lambda c, w, p: {"tile", "ordered-bitonic", "nt1"} <= w)
+    need("tile slice staged", lambda c, w, p: {"tile", "staged", "slice", "partial"} <= w and c.bag_slice[0] > 0)
+    need("tile slice ordered", lambda c, w, p: {"tile", "ordered-bitonic", "slice", "partial"} <= w and c.bag_slice[0] > 0)
+    # flat kernel
+    for u in S.UNROLLS:
+        for wgt in (False, True):
+            for rq in ("short1", "short2", "ragged", "mixed_even", "mixed_ragged"):
+                need(f"flat {rq} u{u} {wt[wgt]}", lambda c, w, p: fwd(c) and c.request == rq and {"flat", f"u{u}", wt[wgt], "compact"} <= w)
+    need("flat, ragged route, direct-index tile", lambda c, w, p: {"flat", "direct"} <= w and c.request == "ragged")
+    need("flat_grid 0", lambda c, w, p: fwd(c) and {"flat", "old-grid"} <= w, 3)
+    need("flat_grid 1", lambda c, w, p: fwd(c) and "flat" in w and c.forward.get("flat_grid") == 1 and p["flat_compact"] >= 1024, 3)
+    need("3 workgroups, 16 lookups a tile", lambda c, w, p: {"flat", "grid3", "target16"} <= w, 3)
+    need("flat slice", lambda c, w, p: {"flat", "slice"} <= w and c.bag_slice[0] > 0)
+    for kind in ("bf16", "f16"):
+        need(f"flat {kind}", lambda c, w, p: {"flat", kind} <= w, 2)
+    # padded family
+    fams = {"padded": lambda c: c.entry == "padded", "mean": lambda c: c.entry == "mean",
+            "out16 bf16": lambda c: c.entry == "out16" and c.out16 == "bf16" and not c.mean,
+            "out16 fp16": lambda c: c.entry == "out16" and c.out16 == "fp16", "out16 mean": lambda c: c.entry == "out16" and c.mean}
+    for fam, is_fam in fams.items():
+        pad = lambda c: is_fam(c) and not c.env and c.req.pads is not None                     # noqa: E731
+        need(f"{fam}: 32 bags staged", lambda c, w, p: pad(c) and {"pad", "bpb32", "staged", "partial"} <= w)
+        need(f"{fam}: 32 bags, stage_out 0", lambda c, w, p: pad(c) and {"pad", "bpb32", "plain"} <= w)
+        need(f"{fam}: 1024 bags unweighted, staged", lambda c, w, p: pad(c) and {"pad", "bpb1024", "staged", "unweighted"} <= w
+             and S.pad_lds_bytes(c, rows[c.name]["plan"]) <= 65536 and c.req.B > 1024)
+        if fam != "mean" and fam != "out16 mean":                  # (mean pooling is unweighted)
+            need(f"{fam}: 1024 bags weighted, the launcher's 64 KB fallback",
+                 lambda c, w, p: pad(c) and {"pad", "bpb1024", "staged", "weighted"} <= w and S.pad_lds_bytes(c, rows[c.name]["plan"]) > 65536)
+            need(f"{fam}: weighted", lambda c, w, p: pad(c) and {"pad", "bpb32", "weighted", "staged"} <= w)
+        for x in (0, 1, 3):
+            need(f"{fam}: xcd_affine {x}", lambda c, w, p: pad(c) and {"pad", f"xcd{x}"} <= w)
+        need(f"{fam}: nt_loads", lambda c, w, p: pad(c) and {"pad", "nt1"} <= w)
+        need(f"{fam}: slice", lambda c, w, p: pad(c) and {"pad", "slice", "partial"} <= w and c.bag_slice[0] > 0)
+        for G in (8, 16, 32, 64):
+            need(f"{fam}: G{G}", lambda c, w, p: pad(c) and {"pad", f"G{G}", "tile>NG"} <= w)
+    need("D = 512 bf16 tables, 4-byte outputs: not staged", lambda c, w, p: c.entry == "padded" and {"pad", "bf16", "plain"} <= w and c.dims[0] == 512)
+    need("D = 512 bf16 tables, 2-byte outputs: staged", lambda c, w, p: c.entry == "out16" and {"pad", "bf16", "staged"} <= w and c.dims[0] == 512)
+    # quantized, gather, base
+    for u in (1, 3, 6):
+        need(f"quantized u{u}", lambda c, w, p: c.entry == "quantized" and {"tile", "staged", "bpb32", f"u{u}"} <= w)
+    for u in (1, 2, 4, 8):
+        for x in (0, 1):
+            need(f"gather u{u} xcd{x}", lambda c, w, p: {"gather", f"u{u}", f"xcd{x}"} <= w)
+    need("gather two passes", lambda c, w, p: {"gather", "f32", "passes2"} <= w and c.dims[0] == 512)
+    need("gather slice", lambda c, w, p: {"gather", "slice"} <= w)
+    for entry in ("psw_grad", "mean_grad", "widen", "atomic"):
+        need(f"base {entry}", lambda c, w, p: c.entry == entry and {"base", "bpb32", "xcd0"} <= w)
+    # environment groups
+    env = lambda c, name, value: c.env.get(name) == value                                       # noqa: E731
+    need("TILE_MAJOR: xcd_affine 2, ordered", lambda c, w, p: env(c, "PARAM_AMD_FWD_TILE_MAJOR", 1) and {"tile", "xcd2", "ordered-bitonic"} <= w)
+    need("TILE_MAJOR: xcd_affine 2, rank", lambda c, w, p: env(c, "PARAM_AMD_FWD_TILE_MAJOR", 1) and {"tile", "xcd2", "ordered-rank"} <= w)
+    need("TILE_MAJOR: xcd_affine 2, flat", lambda c, w, p: env(c, "PARAM_AMD_FWD_TILE_MAJOR", 1) and {"flat", "xcd2"} <= w)
+    need("FWD_FLAT=0: short bags on the tile kernel", lambda c, w, p: env(c, "PARAM_AMD_FWD_FLAT", 0) and "tile" in w, 4)
+    need("FWD_FLAT=2: pooling 3 on the flat walk", lambda c, w, p: env(c, "PARAM_AMD_FWD_FLAT", 2) and "flat" in w and c.req.N == 3 * c.req.T * c.req.B, 2)
+    need("FLAT_COMPACT=0", lambda c, w, p: env(c, "PARAM_AMD_FLAT_COMPACT", 0) and {"flat", "old-grid"} <= w, 4)
+    need("FLAT_BAGS=48", lambda c, w, p: env(c, "PARAM_AMD_FLAT_BAGS", 48) and {"flat", "bpb48", "target64"} <= w, 2)
+    need("FWD_STAGE=0: forward", lambda c, w, p: env(c, "PARAM_AMD_FWD_STAGE", 0) and {"tile", "plain"} <= w, 2)
+    need("FWD_STAGE=0: padded family", lambda c, w, p: env(c, "PARAM_AMD_FWD_STAGE", 0) and {"pad", "plain"} <= w, 2)
+    assert not missing, missing
+    assert len(S.ENV_GROUPS) == 6 and len({tuple(sorted(c.env.items())) for c in S.CASES if c.env}) == 6
+    assert all(max(c.req.rows) <= 1000 for c in S.CASES)
+    # both index types and, where the dims are equal, both layouts: every case runs them (tests/plan_sweep_worker.py: variants)
+    from tests import plan_sweep_worker as W
+
+    for c in S.CASES:
+        v = W.variants(c)
+        assert {i for i, _ in v} == {"i64", "i32"} and (len(set(c.dims)) > 1 or c.entry == "gather" or {lay for _, lay in v} == {"bd", "tbd"}), c.name
