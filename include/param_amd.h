@@ -529,6 +529,47 @@ int pm_embbag_grad_widen(const pm_embbag_batch* op, const int64_t* padding_idx, 
 int pm_embedding_gather(const pm_embbag_batch* op, int32_t out_dtype, void* out, int64_t out_row_stride, pm_stream_t stream);
 
 /*
+ * ROW-QUANTISED TABLES -- sum pooling (weighted where per_sample_weights is given) straight from tables stored in the 8- or 4-bit
+ * row-wise format: no fp32 copy of a table exists at any point.  op->tables[t] points at uint8 [rows[t], row_bytes(dims[t], bits)],
+ * contiguous, 4-byte aligned: the bytes pm_rows_quantize writes and torch's quantized::embedding_bag_{byte,4bit}_prepack produce --
+ *   the codes of the dims[t] columns first (a 4-bit code of column c in byte c / 2 at bit 4 * (c % 2)), then the row's tail:
+ *   bits 8: fp32 scale, fp32 bias (row_bytes = D + 8); bits 4: fp16 scale, fp16 bias, widened exactly (row_bytes = D / 2 + 4).
+ * op->dims[t] is the LOGICAL column count D_t; op->weight_dtype is not read.  Everything else of the request is pm_embbag_fwd's: T
+ * tables, out_offsets / out_stride, bag_begin / bag_count, int32 / int64 indices, per_sample_weights.
+ * THE RULE, for bag (t, b) and column c, over the bag's lookups j in index order from acc = +0.0:
+ *     sc  = fl32(scale_r * w_j)      bi = fl32(bias_r * w_j)       (without per_sample_weights: sc = scale_r, bi = bias_r)
+ *     acc = fmaf(sc, (float)code[r, c], fl32(acc + bi))            r = indices[j]
+ * one fp32 addition, then one fused multiply-add, per element and lookup; an empty bag gives +0.0.  That is, bit for bit, what torch's
+ * CPU operators quantized::embedding_bag_byte_rowwise_offsets and quantized::embedding_bag_4bit_rowwise_offsets compute
+ * (tests/qrows_rules.py restates it with exact arithmetic; tests/test_qrows_host.py pins the restatement to the operators).  Two
+ * consequences: the result is NOT bit-identical to pm_embbag_fwd over pm_rows_dequantize of the table (that dequantises each element
+ * with its own rounding, then adds) -- the two agree within summation rounding, |diff| <= (2L + 2) 2^-24 sum_j |w_j| (|bias_j| + code
+ * scale_j) for a bag of L lookups; and a bag of exactly one unweighted lookup equals pm_rows_dequantize of that row as a value
+ * (0 + bias is exact).  out_dtype PM_F32, or PM_BF16 / PM_F16: the fp32 value rounded ONCE, in registers, as pm_embbag_fwd_out16
+ * rounds (OUTPUT DTYPE above); out is addressed in OUTPUT elements, only the bags of the slice and only the columns below dims[t] are
+ * written.
+ * One launch for any number of tables (csrc/embbag_fwd_qrows.hip): the padded forward's tile structure, two dwords of codes per lane
+ * and row (lane groups sized for max_dim: no per-table sub-groups), loads at dword-aligned addresses -- rows start on 4-byte boundaries
+ * and no better.
+ * Column rules: dims[t] % 4 == 0 (bits 8), dims[t] % 8 == 0 (bits 4), dims[t] <= 4096.
+ * Refused on the host, before any HIP call: what pm_embbag_fwd refuses about the request (the column rules as its "multiple of the
+ * vector width" rule: PM_ERR_UNSUPPORTED); bits not 8 or 4 (PM_ERR_INVALID; 2 and 16 -- payload formats of pm_rows_quantize -- are
+ * PM_ERR_UNSUPPORTED); an unknown out_dtype (PM_ERR_INVALID); max_dim > 4096, a non-zero table_group / grad_block_shift /
+ * grad_block_extra (PM_ERR_UNSUPPORTED); a NULL out or one that is not 16-byte (PM_F32) / 8-byte (16-bit) aligned (PM_ERR_INVALID).
+ * bag_count == 0 is PM_OK without a launch.  No gradient: the tables are not trainable.
+ * pm_embbag_qrows_plan: the geometry that call WOULD use (plan_qrows, csrc/launch_plan.h) -- the twelve members of pm_embbag_plan in its
+ * order; the tile kernel, staged where stage_out > 0; unroll 2 or 4 (pm_set_tuning's unroll: below 4 -> 2, from 4 on -> 4; pm_set_tuning's
+ * bags_per_block and pm_set_forward_tuning's stage_out are honoured, nothing else of the knobs is read).  Host only, launches nothing;
+ * validates as the launching call does, except for `out` of that call.
+ * Replaces torch's two CPU operators named above (behind torch.ao.nn.quantized.EmbeddingBag) and the forward of fbgemm's
+ * IntNBitTableBatchedEmbeddingBagsCodegen for INT8 / INT4 tables.  Left out: 2-bit tables, un-pooled lookups, mean, padding_idx, pruned
+ * rows / index remapping, a padded row stride.
+ * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these two finds out at symbol resolution.
+ */
+int pm_embbag_fwd_qrows(const pm_embbag_batch* op, int32_t bits, int32_t out_dtype, void* out, pm_stream_t stream);
+int pm_embbag_qrows_plan(const pm_embbag_batch* op, int32_t bits, int32_t out_dtype, int32_t out[12]);
+
+/*
  * SEQUENCE GRADIENTS -- the batched backward of the un-pooled lookup above: the gradient of pm_embedding_gather's rows applied to all
  * num_tables tables by one sort and one apply.  The request is the one pm_embedding_gather takes: table t owns the lookup positions
  * [offsets[t * batch], offsets[(t + 1) * batch]), the last table ends at num_indices; the bags inside a table matter only for the

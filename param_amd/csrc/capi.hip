@@ -6,6 +6,11 @@
 
 #include "common.h"
 
+namespace pm {
+// row-quantised tables (embbag_fwd_qrows.hip): p.io = out of out_dtype, addressed in its elements; bits 8 | 4; unroll: plan_qrows'
+hipError_t launch_embbag_fwd_qrows(const KParams& p, int bits, int out_dtype, int max_dim, int unroll, hipStream_t stream);
+}  // namespace pm
+
 namespace {
 
 thread_local std::string g_last_error;
@@ -593,6 +598,55 @@ int pm_embbag_grad_widen(const pm_embbag_batch* op, const int64_t* padding_idx, 
     if (grad16 == static_cast<const void*>(grad32)) return fail(PM_ERR_INVALID, "grad32 must not be grad16 (the widening is not in place)");
     const hipError_t h = pm::launch_grad_widen(p, op->max_dim, padding_idx, mean != 0, grad_dtype, grad16, grad32, static_cast<hipStream_t>(stream));
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_grad_widen launch");
+    return PM_OK;
+}
+
+// ---- row-quantised tables (embbag_fwd_qrows.hip) ---------------------------------------------------------------------------------------
+// what the lookup and its plan query refuse on the host, in one order: the request for the element type whose columns per lane the
+// format has (qrows_elem_dtype: the column rules D % 4 / D % 8), then the call's own arguments.  out_bytes: of one output element.
+static int qrows_request(const pm_embbag_batch* op, int32_t bits, int32_t out_dtype, const pm::PlanKnobs& knobs, pm::PlanShape& shape, int& out_bytes) {
+    if (!op) return fail(PM_ERR_INVALID, "op is NULL");
+    if (bits == 2 || bits == 16)
+        return fail(PM_ERR_UNSUPPORTED, "bits must be 8 or 4: " + std::to_string(bits) + "-bit rows are a payload format of pm_rows_quantize / "
+                                        "pm_embbag_fwd_quantized only, no table can be pooled from them");
+    if (bits != 8 && bits != 4) return fail(PM_ERR_INVALID, "bits must be 8 or 4");
+    const int rc = validate_request(op, pm::qrows_elem_dtype(bits), knobs);
+    if (rc != PM_OK) return rc;
+    shape = pm::qrows_shape(*op, bits, knobs);      // (lane groups at least as wide in columns as that element type's: no more tiles than validated)
+    if (!dtype_is_weight(out_dtype)) return fail(PM_ERR_INVALID, "out_dtype must be PM_F32, PM_BF16 or PM_F16");
+    if (op->table_group != 0 || op->grad_block_shift != 0 || op->grad_block_extra != 0)
+        return fail(PM_ERR_UNSUPPORTED, "row-quantised tables do not take blocked layouts (table_group / grad_block_shift / grad_block_extra must be 0)");
+    if (op->max_dim > pm::kQrowsMaxDim)
+        return fail(PM_ERR_UNSUPPORTED, "row-quantised tables: dims[t] (and max_dim) must be at most " + std::to_string(pm::kQrowsMaxDim));
+    out_bytes = out_dtype == PM_F32 ? 4 : 2;
+    return PM_OK;
+}
+
+int pm_embbag_fwd_qrows(const pm_embbag_batch* op, int32_t bits, int32_t out_dtype, void* out, pm_stream_t stream) {
+    const pm::PlanKnobs knobs = current_knobs();
+    pm::PlanShape shape;
+    int out_bytes = 0;
+    const int rc = qrows_request(op, bits, out_dtype, knobs, shape, out_bytes);
+    if (rc != PM_OK) return rc;
+    const pm::LaunchPlan plan = pm::plan_qrows(*op, shape, knobs, out_bytes);
+    pm::KParams p;
+    fill_params(op, plan, p);
+    return padded_forward(p, out, out_dtype == PM_F32 ? 16 : 8, stream, [&](const pm::KParams& q, hipStream_t s) {
+        return pm::launch_embbag_fwd_qrows(q, bits, out_dtype, op->max_dim, plan.unroll, s);
+    }, "pm_embbag_fwd_qrows launch");
+}
+
+int pm_embbag_qrows_plan(const pm_embbag_batch* op, int32_t bits, int32_t out_dtype, int32_t out[12]) {
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const pm::PlanKnobs knobs = current_knobs();
+    pm::PlanShape shape;
+    int out_bytes = 0;
+    const int rc = qrows_request(op, bits, out_dtype, knobs, shape, out_bytes);
+    if (rc != PM_OK) return rc;
+    const pm::LaunchPlan p = pm::plan_qrows(*op, shape, knobs, out_bytes);
+    const int32_t v[12] = {p.tiles_per_table, p.bags_per_block, p.idx_cap, p.xcd_affine, p.nt_loads, p.ordered,
+                           p.stage_out, p.stage_bags, p.flat_bags, p.flat_target, p.flat_compact, p.unroll};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
     return PM_OK;
 }
 

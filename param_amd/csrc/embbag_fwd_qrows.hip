@@ -1,0 +1,285 @@
+// param_amd/csrc/embbag_fwd_qrows.hip -- pooled lookup over 8- and 4-bit ROW-QUANTISED tables: pm_embbag_fwd_qrows (include/param_amd.h,
+// DESIGN.md section 3.12).  Table t is uint8 [rows_t, rq::row_bytes(D_t, BITS)]: the bytes pm_rows_quantize writes and torch's
+// quantized::embedding_bag_{byte,4bit}_prepack produce -- the codes of the D_t columns (a 4-bit code of column c in byte c / 2 at bit
+// 4 * (c % 2)), then the row's scale and bias (8 bits: two fp32; 4 bits: two fp16, widened exactly).
+//
+// THE RULE (bit for bit torch's CPU operators quantized::embedding_bag_{byte,4bit}_rowwise_offsets; tests/qrows_rules.py restates it):
+// the lookups j of a bag in index order, from acc = +0.0, per column
+//     sc = scale_r * w_j     bi = bias_r * w_j        (unweighted: sc = scale_r, bi = bias_r; no multiplication happens)
+//     acc = fmaf(sc, (float)code[r, c], acc + bi)     r = indices[j]
+// one fp32 addition, then one fused multiply-add.  The build has -ffp-contract=off: the addition below is a statement of its own and
+// the fmaf is written out.  A 16-bit output is ONE rounding of that fp32 value (OutBF16 / OutF16, fwd_elem.h), in registers.
+//
+// HOW: the tile and bag structure of the padded forward (embbag_fwd_pad_kernel.inc) without its padding compaction: a workgroup serves
+// bags_per_block bags of one table; their offsets, and the tile's indices (and weights) when they fit idx_cap, are staged in LDS
+// (stage_tile_at, common.h), a longer tile reads its indices from the request.  A lane group of G lanes pools one bag; lane l holds
+// TWO DWORDS of codes per row -- 8 columns of an 8-bit row, 16 of a 4-bit row -- so G is sized for max_dim / 8 (/ 16), clamped
+// to [8, 64], for every table of the request (no per-table sub-groups: a narrow table of a mixed request idles lanes); rows wider
+// than G such pieces take further column passes.  U rows are in flight per lane group.  Every row of the two formats starts on a 4-byte
+// boundary and no better (a D = 128 8-bit row is 136 bytes): the loads are global_load_dwordx2 (codes; the 8-bit tail) and
+// global_load_dword (the 4-bit tail) at dword-aligned addresses, which gfx950 executes correctly (tests/test_gpu_qrows.py runs rows
+// of 12, 28, 8 and 16 bytes, whose pieces straddle every 8-byte phase) -- measured against one dword per lane, launch_plan.h.  Every
+// lane of the group reads the tail's address itself, which the memory pipeline serves as one request per row and column pass.  Codes are unpacked in registers: v_cvt_f32_ubyte0..3 (8 bits), v_bfe_u32 +
+// v_cvt_f32_u32 (4 bits).  The pooled rows leave through the LDS burst buffer (burst_rows) where the plan has one, else row by row.
+// The geometry -- tile, index tile, burst, unroll -- is plan_qrows' alone (launch_plan.h).  No atomics, no scratch memory, no workspace.
+#include "common.h"
+#include "fwd_elem.h"
+#include "rowquant.inc"
+
+namespace pm {
+namespace {
+
+using namespace fwd;
+
+template <int BITS> struct QRow;
+template <> struct QRow<8> {
+    static constexpr int kVec = 4;                       // columns per dword of codes
+    struct Tail { float scale, bias; };
+    __device__ static __forceinline__ Tail tail(const char* row, int code_bytes) {
+        const PM_GLOBAL uint32_t* q = as_global<uint32_t>(row + code_bytes);
+        return Tail{__uint_as_float(q[0]), __uint_as_float(q[1])};
+    }
+    __device__ static __forceinline__ void unpack(uint32_t raw, float (&f)[4]) {
+        f[0] = static_cast<float>(raw & 0xffu);
+        f[1] = static_cast<float>((raw >> 8) & 0xffu);
+        f[2] = static_cast<float>((raw >> 16) & 0xffu);
+        f[3] = static_cast<float>(raw >> 24);
+    }
+};
+template <> struct QRow<4> {
+    static constexpr int kVec = 8;
+    struct Tail { float scale, bias; };
+    __device__ static __forceinline__ Tail tail(const char* row, int code_bytes) {
+        const uint32_t sb = *as_global<uint32_t>(row + code_bytes);
+        return Tail{rq::half_value(static_cast<uint16_t>(sb & 0xffffu)), rq::half_value(static_cast<uint16_t>(sb >> 16))};
+    }
+    __device__ static __forceinline__ void unpack(uint32_t raw, float (&f)[8]) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) f[k] = static_cast<float>((raw >> (4 * k)) & 0xfu);
+    }
+};
+
+// kQrowsLaneDwords (launch_plan.h) dwords of codes per lane and row, loaded as ONE instruction at a 4-byte-aligned address: two in the
+// product (global_load_dwordx2), 1 and 4 in experiment builds.  The dwords of a row's last lane that lie behind the codes are the
+// row's own tail with two dwords per lane (read, never used: 8 tail bytes behind 8-bit codes, 4 behind 4-bit codes, and a lane's
+// first dword is always codes); with four they may lie behind the row, which is why four is not a product setting.
+constexpr int kLaneDwords = kQrowsLaneDwords;
+static_assert(kLaneDwords == 1 || kLaneDwords == 2 || kLaneDwords == 4, "PM_QROWS_LANE_DWORDS must be 1, 2 or 4");
+typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+
+// one row's codes of this lane and its tail, as loaded
+template <int BITS> struct QLoad {
+    uint32_t raw[kLaneDwords];
+    typename QRow<BITS>::Tail tail;
+};
+template <int BITS>
+__device__ __forceinline__ QLoad<BITS> load_row(const char* row, int code_off, int code_bytes) {
+    QLoad<BITS> q;
+    if constexpr (kLaneDwords == 4) {
+        const u32x4_a4 v = *as_global<u32x4_a4>(row + code_off);
+#pragma unroll
+        for (int h = 0; h < kLaneDwords; ++h) q.raw[h] = v[h];
+    } else if constexpr (kLaneDwords == 2) {
+        const u32x2_a4 v = *as_global<u32x2_a4>(row + code_off);
+#pragma unroll
+        for (int h = 0; h < kLaneDwords; ++h) q.raw[h] = v[h];
+    } else {
+        q.raw[0] = *as_global<uint32_t>(row + code_off);
+    }
+    q.tail = QRow<BITS>::tail(row, code_bytes);
+    return q;
+}
+
+// one lookup joins the sum: THE RULE, per column
+template <int BITS, bool WEIGHTED>
+__device__ __forceinline__ void accumulate_q(float (&acc)[QRow<BITS>::kVec * kLaneDwords], const QLoad<BITS>& q, float w) {
+    constexpr int VEC = QRow<BITS>::kVec;
+    float sc = q.tail.scale, bi = q.tail.bias;
+    if (WEIGHTED) {
+        sc = sc * w;
+        bi = bi * w;
+    }
+#pragma unroll
+    for (int h = 0; h < kLaneDwords; ++h) {
+        float f[VEC];
+        QRow<BITS>::unpack(q.raw[h], f);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const float t = acc[h * VEC + k] + bi;
+            acc[h * VEC + k] = fmaf(sc, f[k], t);
+        }
+    }
+}
+
+template <int BITS, int G, bool WEIGHTED, typename OT, int U>
+__global__ void __launch_bounds__(kBlock) qrows_fwd_kernel(const KParams p) {
+    constexpr bool OUT16 = !std::is_same<OT, float>::value;
+    constexpr int VEC = QRow<BITS>::kVec;
+    constexpr int CV = VEC * kLaneDwords;      // columns per lane and column pass
+    constexpr int NG = kBlock / G;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+
+    int t, tile;
+    block_to_tile(p, t, tile);
+    if (t >= p.T) return;
+    const int64_t bag0 = p.bag_begin + static_cast<int64_t>(tile) * p.bags_per_block;
+    const int64_t left_bags = p.bag_begin + p.bag_count - bag0;
+    if (left_bags <= 0) return;
+    const int nb = left_bags < p.bags_per_block ? static_cast<int>(left_bags) : p.bags_per_block;
+
+    int64_t* s_off;
+    int32_t* s_idx;
+    float* s_w;
+    const bool staged = stage_tile_at<WEIGHTED>(p, t, bag0, nb, smem, s_off, s_idx, s_w);
+    const int64_t base = s_off[0];
+    float* s_out = reinterpret_cast<float*>(smem + (tile_lds_bytes(p.bags_per_block, p.idx_cap, WEIGHTED) + 15) / 16 * 16);
+    uint16_t* s_out16 = reinterpret_cast<uint16_t*>(s_out);
+
+    const int gid = threadIdx.x / G;
+    const int lig = threadIdx.x % G;
+    const int D = p.dims[t];
+    const int code_bytes = D * BITS / 8;
+    const int64_t row_bytes = rq::row_bytes(D, BITS);
+    const char* W = reinterpret_cast<const char*>(p.tables[t]);
+    float* out_t = p.io + p.out_offsets[t];
+    // OUT16: io is the 16-bit output; offsets and strides count its 2-byte elements
+    uint16_t* out16_t = reinterpret_cast<uint16_t*>(p.io) + p.out_offsets[t];
+    const bool burst = p.stage_out > 0;
+
+    for (int bg = gid; bg < nb; bg += NG) {
+        const int64_t s = s_off[bg];
+        const int64_t e = s_off[bg + 1];
+        for (int c = lig * CV; c < D; c += G * CV) {
+            const int code_off = c / VEC * 4;              // this lane's dword(s) of the row
+            float acc[CV];
+#pragma unroll
+            for (int k = 0; k < CV; ++k) acc[k] = 0.0f;
+            // pieces of 4 outputs: a lane's dwords behind the row's codes give none (one dword per lane: D is a whole number of them)
+            auto inside = [&](int k) { return kLaneDwords == 1 || c + k < D; };
+            if (staged) {
+                int j = static_cast<int>(s - base);
+                const int je = static_cast<int>(e - base);
+                for (; j + U <= je; j += U) {
+                    QLoad<BITS> q[U];
+                    float w[U];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        q[u] = load_row<BITS>(W + row_offset<true>(static_cast<int64_t>(s_idx[j + u]), row_bytes), code_off, code_bytes);
+                        w[u] = WEIGHTED ? s_w[j + u] : 1.0f;
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) accumulate_q<BITS, WEIGHTED>(acc, q[u], w[u]);
+                }
+                for (; j < je; ++j)
+                    accumulate_q<BITS, WEIGHTED>(acc, load_row<BITS>(W + row_offset<true>(static_cast<int64_t>(s_idx[j]), row_bytes), code_off, code_bytes),
+                                                 WEIGHTED ? s_w[j] : 1.0f);
+            } else {
+                // the tile's lookups exceed the index tile: indices (and weights) come from the request
+                int64_t j = s;
+                for (; j + U <= e; j += U) {
+                    QLoad<BITS> q[U];
+                    float w[U];
+                    int64_t r[U];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        r[u] = load_index(p.indices, j + u, p.idx64);
+                        w[u] = WEIGHTED ? as_global<float>(p.psw)[j + u] : 1.0f;
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) q[u] = load_row<BITS>(W + row_offset<false>(r[u], row_bytes), code_off, code_bytes);
+#pragma unroll
+                    for (int u = 0; u < U; ++u) accumulate_q<BITS, WEIGHTED>(acc, q[u], w[u]);
+                }
+                for (; j < e; ++j)
+                    accumulate_q<BITS, WEIGHTED>(acc, load_row<BITS>(W + row_offset<false>(load_index(p.indices, j, p.idx64), row_bytes), code_off, code_bytes),
+                                                 WEIGHTED ? as_global<float>(p.psw)[j] : 1.0f);
+            }
+            if constexpr (OUT16) {
+                // the one rounding, in registers; 4 outputs = 8 bytes per piece
+                u32x2 piece[CV / 4];
+#pragma unroll
+                for (int k = 0; k < CV; k += 4)
+                    piece[k / 4] = u32x2{OT::round(acc[k]) | (OT::round(acc[k + 1]) << 16), OT::round(acc[k + 2]) | (OT::round(acc[k + 3]) << 16)};
+                if (burst) {
+                    u32x2* o2 = reinterpret_cast<u32x2*>(s_out16 + static_cast<size_t>(bg) * D + c);
+#pragma unroll
+                    for (int k = 0; k < CV / 4; ++k)
+                        if (inside(4 * k)) o2[k] = piece[k];
+                } else {
+                    u32x2* o2 = reinterpret_cast<u32x2*>(out16_t + (bag0 + bg) * p.out_stride + c);
+#pragma unroll
+                    for (int k = 0; k < CV / 4; ++k)
+                        if (inside(4 * k)) __builtin_nontemporal_store(piece[k], o2 + k);
+                }
+            } else if (burst) {
+                f32x4* o4 = reinterpret_cast<f32x4*>(s_out + static_cast<size_t>(bg) * D + c);
+#pragma unroll
+                for (int k = 0; k < CV; k += 4)
+                    if (inside(k)) o4[k / 4] = f32x4{acc[k], acc[k + 1], acc[k + 2], acc[k + 3]};
+            } else {
+                f32x4* o4 = reinterpret_cast<f32x4*>(out_t + (bag0 + bg) * p.out_stride + c);
+#pragma unroll
+                for (int k = 0; k < CV; k += 4) {
+                    f32x4 v = {acc[k], acc[k + 1], acc[k + 2], acc[k + 3]};
+                    if (inside(k)) __builtin_nontemporal_store(v, o4 + k / 4);
+                }
+            }
+        }
+    }
+    if (burst) {
+        __syncthreads();
+        if constexpr (OUT16) {
+            const int q = D / 4;               // 8-byte pieces of 4 outputs per row
+            for (int i = threadIdx.x; i < nb * q; i += kBlock) {
+                const int bg = i / q, c4 = i % q;
+                const u32x2 v = *reinterpret_cast<const u32x2*>(s_out16 + static_cast<size_t>(bg) * D + c4 * 4);
+                __builtin_nontemporal_store(v, reinterpret_cast<u32x2*>(out16_t + (bag0 + bg) * p.out_stride + c4 * 4));
+            }
+        } else {
+            burst_rows(s_out, out_t, bag0, p.out_stride, nb, D);
+        }
+    }
+}
+
+// the launcher ladder: bits, group width, weighted, output element, rows in flight
+template <int BITS, int G, typename OT>
+hipError_t launch_q_w(const KParams& p0, int unroll, hipStream_t stream) {
+    KParams p = p0;
+    const bool weighted = p.psw != nullptr;
+    const int grid = p.T * p.tiles_per_table;
+    const size_t tile_lds = (tile_lds_bytes(p.bags_per_block, p.idx_cap, weighted) + 15) / 16 * 16;
+    size_t lds = tile_lds + (p.stage_out > 0 ? static_cast<size_t>(p.bags_per_block) * p.stage_out * sizeof(typename std::conditional<std::is_same<OT, float>::value, float, uint16_t>::type) : 0);
+    if (lds > 65536) {                         // (explicit 1024-bag tiles of a weighted request: rows leave one by one)
+        p.stage_out = 0;
+        lds = tile_lds;
+    }
+    dispatch_bool(weighted, [&](auto w) {
+        dispatch_bool(unroll >= 4, [&](auto deep) {
+            constexpr int U = decltype(deep)::value ? 4 : 2;
+            hipLaunchKernelGGL((qrows_fwd_kernel<BITS, G, decltype(w)::value, OT, U>), dim3(grid), dim3(kBlock), lds, stream, p);
+        });
+    });
+    return hipGetLastError();
+}
+
+template <int BITS, typename OT>
+hipError_t launch_q_g(const KParams& p, int max_dim, int unroll, hipStream_t stream) {
+    return dispatch_group_lanes(group_lanes(max_dim, QRow<BITS>::kVec * kLaneDwords), [&](auto g) { return launch_q_w<BITS, decltype(g)::value, OT>(p, unroll, stream); });
+}
+
+template <int BITS>
+hipError_t launch_q_o(const KParams& p, int out_dtype, int max_dim, int unroll, hipStream_t stream) {
+    if (out_dtype == PM_BF16) return launch_q_g<BITS, OutBF16>(p, max_dim, unroll, stream);
+    if (out_dtype == PM_F16) return launch_q_g<BITS, OutF16>(p, max_dim, unroll, stream);
+    return launch_q_g<BITS, float>(p, max_dim, unroll, stream);
+}
+
+}  // namespace
+
+// p.io = out of out_dtype (PM_F32 | PM_BF16 | PM_F16), addressed in its elements; bits 8 | 4; unroll: plan_qrows' (2 | 4)
+hipError_t launch_embbag_fwd_qrows(const KParams& p, int bits, int out_dtype, int max_dim, int unroll, hipStream_t stream) {
+    return bits == 8 ? launch_q_o<8>(p, out_dtype, max_dim, unroll, stream) : launch_q_o<4>(p, out_dtype, max_dim, unroll, stream);
+}
+
+}  // namespace pm

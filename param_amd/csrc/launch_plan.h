@@ -372,6 +372,66 @@ static inline LaunchPlan plan_padded(const pm_embbag_batch& op, int elem_dtype, 
     return plan_padded(op, plan_shape(op, elem_dtype, k), k, out_bytes);
 }
 
+// ---- qrows: pm_embbag_fwd_qrows (embbag_fwd_qrows.hip) -- pooled lookup over 8- / 4-bit row-quantised tables ---------------------------
+// A lane holds kQrowsLaneDwords DWORDS of a row's codes -- with two: 8 columns of an 8-bit row, 16 of a 4-bit row -- and the lane group
+// is sized for max_dim in those units (group_lanes), for every table of the request: a narrower table of a mixed request idles lanes
+// (no per-table sub-groups).  Measured, tools/qrows_probe.py (16 x 10 M x 128, batch 8192, pooling 20; us, 8-bit / 4-bit tables, fp32
+// output, uniform | Zipf; one process per build, the bf16-table lookup 134.7-136.5 | 71.9-73.5 in all three):
+//   1 dword per lane  (global_load_dword)      139.8 / 105.6 | 89.3 / 64.1      profiles/qrows_probe_lane_dwords1.json
+//   2 (global_load_dwordx2, dword-aligned)     132.0 / 103.7 | 77.3 / 60.5      profiles/qrows_probe.json -- the product
+//   4 (global_load_dwordx4, dword-aligned)     133.1 / 184.2 | 67.4 / 162.9     profiles/qrows_probe_lane_dwords4.json
+// Four would be the 8-bit format's optimum (Zipf: 13 % over two) and is the 4-bit format's worst (4 of 8 lanes hold a D = 128 row, on 32
+// accumulators); and a lane's 16 bytes reach past the row's END for 8-bit rows of D % 16 == 4 and 4-bit rows of D % 32 == 8 / 16 --
+// past the table for its last row.  With two, the dwords behind a row's codes are always the row's own tail.  -DPM_QROWS_LANE_DWORDS=1
+// / =4 are experiment builds (4: for widths that are a multiple of 16 / 32 columns only).  A width per format: left as the follow-up.
+// The plan is the padded forward's, from the same blocks: the plain bag-count tiling (tile_bags), halved until the tile's rows of
+// out_bytes-elements fit the burst buffer (burst_tile; an explicit bags_per_block is kept and bursts only if it fits), and an index tile
+// sized for what a tile holds where the lookups divide evenly over the bags (index_tile; a longer tile reads its indices from the
+// request).  No ordered variant, no flat walk, plain row loads.
+// Rows in flight per lane group: 2 or 4 (pm_set_tuning's unroll: below 4 -> 2, from 4 on -> 4).  Same probe, two dwords per lane, 2 / 4
+// rows in flight: 8-bit 134.7 / 132.0 uniform, 79.0 / 77.2 Zipf; 4-bit 104.3 / 103.7, 62.3 / 60.5 -- four is never slower, and the fp32
+// forward's optimum of 2 does not carry over: kQrowsUnroll is this kernel's own default.
+#ifndef PM_QROWS_LANE_DWORDS
+#define PM_QROWS_LANE_DWORDS 2
+#endif
+constexpr int kQrowsLaneDwords = PM_QROWS_LANE_DWORDS;
+constexpr int kQrowsUnroll = 4;
+constexpr int kQrowsMaxDim = 4096;     // columns per row at most (8 column passes of the widest lane group over an 8-bit row)
+static inline int qrows_elem_dtype(int bits) { return bits == 8 ? PM_F32 : PM_BF16; }   // the element type with the format's column rule (D % 4, D % 8)
+static inline int qrows_lane_columns(int bits) { return kQrowsLaneDwords * (bits == 8 ? 4 : 8); }
+// the request's shape for this kernel's lane group (plan_shape's, with the columns a lane holds in place of an element type's)
+static inline PlanShape qrows_shape(const pm_embbag_batch& op, int bits, const PlanKnobs& k) {
+    PlanShape s;
+    s.vec = qrows_lane_columns(bits);
+    s.G = group_lanes(op.max_dim, s.vec);
+    s.NG = kBlock / s.G;
+    s.total_bags = static_cast<int64_t>(op.num_tables) * op.batch;
+    s.avg_l = s.total_bags > 0 ? (op.num_indices + s.total_bags - 1) / s.total_bags : 0;
+    s.even = s.total_bags > 0 && op.num_indices % s.total_bags == 0;
+    s.uneven = s.total_bags > 0 && !s.even;
+    s.base_tile = tile_bags(op, s, k);
+    return s;
+}
+static inline LaunchPlan plan_qrows(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k, int out_bytes) {
+    LaunchPlan p = plan_base(op, s, k);
+    if (k.bags_per_block <= 0) p.bags_per_block = burst_tile(p.bags_per_block, s.NG, op.max_dim, out_bytes);
+    p.tiles_per_table = static_cast<int32_t>(ceil_div(op.bag_count, p.bags_per_block));
+    p.stage_out = (k.stage && static_cast<int64_t>(p.bags_per_block) * op.max_dim * out_bytes <= kBurstBytes) ? op.max_dim : 0;
+    p.stage_bags = p.bags_per_block;
+    if (s.even) {
+        const int64_t need = index_tile(p.bags_per_block, s.avg_l, 512);
+        if (need < p.idx_cap) p.idx_cap = static_cast<int32_t>(need);
+    }
+    p.ordered = 0;
+    p.nt_loads = 0;
+    const int u = k.unroll != 0 ? k.unroll : kQrowsUnroll;
+    p.unroll = u >= 4 ? 4 : 2;
+    return p;
+}
+static inline LaunchPlan plan_qrows(const pm_embbag_batch& op, int bits, const PlanKnobs& k, int out_bytes) {
+    return plan_qrows(op, qrows_shape(op, bits, k), k, out_bytes);
+}
+
 // ---- gather: pm_embedding_gather (embedding_gather.hip) -- un-pooled rows, one output row per lookup POSITION ---------------------------
 // A tile is kBlock consecutive positions of the index array, whatever tables they belong to: the output is addressed by position, so
 // nothing about a tile depends on bags.  A lane group moves one row at a time and owns kBlock / NG = G of the tile's positions.

@@ -1,0 +1,277 @@
+"""Pooled lookup over 8- and 4-bit ROW-QUANTISED embedding tables (``csrc/embbag_fwd_qrows.hip`` through ``pm_embbag_fwd_qrows``).
+
+* :class:`QuantizedBatchedEmbeddingBagMI355` -- T tables stored as the bytes ``quantize_rows`` writes (torch's
+  ``quantized::embedding_bag_{byte,4bit}_prepack`` layout), pooled by ONE launch that reads those bytes: no fp32 copy of a table exists.
+  The serving-side sibling of :class:`BatchedEmbeddingBagMI355`; what fbgemm's ``IntNBitTableBatchedEmbeddingBagsCodegen`` is for.
+* :class:`QuantizedEmbeddingBagMI355` -- the single-table module with ``nn.EmbeddingBag``'s call; what
+  ``torch.ao.nn.quantized.EmbeddingBag`` is for.
+
+The arithmetic is fixed (include/param_amd.h, "ROW-QUANTISED TABLES") and equals torch's CPU operators
+``quantized::embedding_bag_{byte,4bit}_rowwise_offsets`` bit for bit: per element and lookup, in index order from +0.0,
+``acc = fmaf(scale * w, code, acc + bias * w)``.  It is NOT bit-identical to the fp32 forward over ``dequantized_table(t)`` (which rounds
+every dequantised element first); the two agree within summation rounding.  A bag of exactly one unweighted lookup equals
+``dequantize_rows`` of that row as a value.
+
+Forward only: the tables are buffers, nothing requires grad.  There is no CPU path.  Left out, on purpose: 2-bit tables, an un-pooled
+(sequence) lookup, mean pooling, ``padding_idx``, pruned rows / index remapping, a padded row stride, per-table lane sub-groups for mixed
+dims, the operator plug-in, any backward.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional, Sequence
+
+import torch
+import torch.nn as nn
+
+from . import _lib, quant
+from .embedding_bag import (_WDTYPE, BatchedEmbeddingBagMI355, EmbeddingBagMI355, _BoundsChecked, _TableSet, _require_device, _stream_ptr,
+                            bounds_check_mode_name)
+
+BITWIDTHS = (8, 4)
+MAX_DIM = 4096      # kQrowsMaxDim (csrc/launch_plan.h)
+
+
+def _check_spec(bitwidth, dims: Sequence[int], layout: str) -> None:
+    """what the constructors refuse, before anything is allocated"""
+    if bitwidth not in BITWIDTHS or isinstance(bitwidth, bool):
+        raise ValueError(f"bitwidth must be 8 or 4, got {bitwidth!r} (2-bit tables are not implemented; 16 bits is a table dtype of "
+                         "BatchedEmbeddingBagMI355)")
+    if layout == "blocked":
+        raise ValueError('row-quantised tables do not take layout="blocked"')
+    if layout not in ("bd", "tbd"):
+        raise ValueError(f'layout must be "bd" or "tbd", got {layout!r}')
+    mult = 4 if bitwidth == 8 else 8
+    for d in dims:
+        if d < mult or d % mult or d > MAX_DIM:
+            raise ValueError(f"embedding dim {d}: a {bitwidth}-bit table needs a multiple of {mult} in [{mult}, {MAX_DIM}]")
+    if layout == "tbd" and len(set(dims)) != 1:
+        raise ValueError('layout "tbd" needs one common embedding dim')
+
+
+def _sum_only(mode, padding_idx, who: str) -> None:
+    if str(getattr(mode, "name", mode)).lower() not in ("sum", "0"):
+        raise ValueError(f"{who}: only sum pooling is implemented for row-quantised tables (got {mode!r})")
+    if padding_idx is not None and not (isinstance(padding_idx, (list, tuple)) and all(k is None for k in padding_idx)):
+        raise ValueError(f"{who}: padding_idx is not implemented for row-quantised tables")
+
+
+class _QTableSet(_TableSet):
+    """:class:`_TableSet` over uint8 tables of quantised rows: ``dims`` are the LOGICAL column counts, ``dtype`` (what the request's
+    ``weight_dtype`` says) is fp32 -- ``pm_embbag_fwd_qrows`` does not read it, the sanitiser reads rows, indices and offsets only."""
+
+    def __init__(self, tables: Sequence[torch.Tensor], dims: Sequence[int], layout: str):
+        t0 = tables[0]
+        for t in tables:
+            _require_device(t, "quantised table")
+            if t.dtype != torch.uint8 or t.dim() != 2 or not t.is_contiguous() or t.data_ptr() % 4:
+                raise ValueError("quantised tables must be contiguous, 4-byte aligned 2-D uint8 tensors")
+            if t.shape[0] >= 2**31:
+                raise ValueError("tables with >= 2^31 rows are not supported")
+        self.device, self.dtype, self.layout = t0.device, torch.float32, layout
+        self.rows = [int(t.shape[0]) for t in tables]
+        self.dims = [int(d) for d in dims]
+        self.block_bags = None
+        self._blk_cache: dict = {}
+        self.T = len(tables)
+        self.max_dim, self.min_dim, self.total_dim = max(self.dims), min(self.dims), sum(self.dims)
+        self.ptrs = [t.data_ptr() for t in tables]
+        self.d_ptrs = torch.tensor(self.ptrs, dtype=torch.int64, device=self.device)
+        self.d_rows = torch.tensor(self.rows, dtype=torch.int64, device=self.device)
+        self.d_dims = torch.tensor(self.dims, dtype=torch.int32, device=self.device)
+        col0 = [0]
+        for d in self.dims[:-1]:
+            col0.append(col0[-1] + d)
+        self.col0 = col0
+        self.d_col0 = torch.tensor(col0, dtype=torch.int64, device=self.device)
+        self._tbd_cache: dict = {}
+        self._req: dict = {}
+        self._pool_key, self._pool_val = None, 0
+
+
+class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
+    """T row-quantised embedding tables in one HBM slab, pooled (sum, optionally weighted) by ONE kernel launch that reads the quantised
+    bytes.
+
+    ``QuantizedBatchedEmbeddingBagMI355(rows, dims, bitwidth, device="cuda", layout="bd", output_dtype=None, bounds_check_mode="none")``:
+    ``bitwidth`` 8 (``row_bytes = D + 8``) or 4 (``D / 2 + 4``); ``dims`` multiples of 4 (8-bit) / 8 (4-bit), at most 4096, and may differ
+    per table with ``layout="bd"`` (lane groups are sized for the widest table).  The tables start as zero bytes: every row dequantises
+    to zeros.  ``table(t)`` is the uint8 ``[rows_t, row_bytes]`` tensor -- copy prepacked bytes into it, or fill it with
+    ``quantize_from_(t, fp32)`` (the ``quantize_rows`` kernel: fp32 sources, dims a multiple of 8 up to 512).  ``dequantized_table(t)`` is
+    ``dequantize_rows`` of it.
+
+    ``lookup(indices, offsets, per_sample_weights=None, out=None, bag_begin=0, bag_count=None, batch=None)`` -- and ``forward``, the same
+    call -- takes the TBE request of :class:`BatchedEmbeddingBagMI355` and returns ``[B, sum D]`` (``"bd"``) or ``[T, B, D]`` (``"tbd"``) in
+    ``output_dtype`` (fp32, or bf16 / fp16: the fp32 value rounded once in the kernel).  The rule is the module docstring's.
+    ``plan(...)`` returns the launch geometry of the same request as a dict (``pm_embbag_qrows_plan``; nothing is launched).
+    ``bounds_check_mode``: see :class:`_BoundsChecked` -- the sanitiser reads rows, indices and offsets, never the tables.
+
+    No gradients: the tables are a buffer (``state_dict`` round-trips the bytes), the output never requires grad.  ValueError before
+    anything is allocated: ``bitwidth`` not 8 or 4, dims breaking the column rules, ``layout="blocked"``, mean pooling, ``padding_idx``.
+    At call time: tensors that are not on a ROCm device raise RuntimeError (no CPU fallback), a floating-point index tensor TypeError.
+    """
+
+    def __init__(self, rows: Sequence[int], dims, bitwidth: int, device="cuda", layout: str = "bd", output_dtype=None,
+                 bounds_check_mode="none", pooling_mode="sum", padding_idx=None):
+        super().__init__()
+        self._init_shared(bounds_check_mode, output_dtype)
+        rows = [int(r) for r in rows]
+        dims = [int(dims)] * len(rows) if isinstance(dims, int) else [int(d) for d in dims]
+        if len(rows) != len(dims) or not rows:
+            raise ValueError("rows and dims must name the same tables, at least one")
+        _check_spec(bitwidth, dims, layout)
+        _sum_only(pooling_mode, padding_idx, type(self).__name__)
+        if any(r < 0 or r >= 2**31 for r in rows):
+            raise ValueError("every table needs 0 <= rows < 2^31")
+        self.padding_idx = None
+        self.rows, self.dims, self.bitwidth, self.layout = rows, dims, int(bitwidth), layout
+        self._row_bytes = [quant.host_row_bytes(d, self.bitwidth) for d in dims]
+        # table starts padded to 256 B (rows themselves are 4-byte aligned and no better)
+        starts, cur = [], 0
+        for r, rb in zip(rows, self._row_bytes):
+            starts.append(cur)
+            cur += (r * rb + 255) // 256 * 256
+        self._starts = starts
+        self.register_buffer("weights", torch.zeros(cur, dtype=torch.uint8, device=device))
+        self._ts: Optional[_QTableSet] = None
+
+    _TABLES = "weights"
+
+    # -- tables ------------------------------------------------------------------------------
+    def table(self, t: int) -> torch.Tensor:
+        s, n = self._starts[t], self.rows[t] * self._row_bytes[t]
+        return self.weights[s:s + n].view(self.rows[t], self._row_bytes[t])
+
+    def quantize_from_(self, t: int, source: torch.Tensor) -> None:
+        """fill table ``t`` from the fp32 tensor ``source`` ``[rows_t, D_t]`` on the GPU with the ``quantize_rows`` kernel (its limits: fp32
+        only, D a multiple of 8 up to 512; other widths: copy prepacked bytes into ``table(t)``)"""
+        if source.dtype != torch.float32:
+            raise TypeError(f"quantize_from_: float32 expected, got {source.dtype} (widen 16-bit tables first)")
+        if tuple(source.shape) != (self.rows[t], self.dims[t]):
+            raise ValueError(f"quantize_from_: table {t} is {(self.rows[t], self.dims[t])}, got {tuple(source.shape)}")
+        _require_device(self.weights, f"{type(self).__name__}.weights")
+        if self.rows[t]:
+            quant.quantize_rows(source.detach().contiguous(), self.dims[t], self.bitwidth, out=self.table(t))
+
+    def dequantized_table(self, t: int) -> torch.Tensor:
+        """fp32 ``[rows_t, D_t]``: ``dequantize_rows`` of table ``t``"""
+        _require_device(self.weights, f"{type(self).__name__}.weights")
+        return quant.dequantize_rows(self.table(t), self.dims[t], self.bitwidth)
+
+    @classmethod
+    def from_float(cls, source, bitwidth: int, **kw):
+        """quantise a :class:`BatchedEmbeddingBagMI355` sum module (16-bit tables are widened first) or a sequence of fp32 ``[rows, D]``
+        tensors; keywords go to the constructor (``device``, ``layout`` default to the source's)"""
+        if isinstance(source, BatchedEmbeddingBagMI355):
+            _sum_only(source.pooling_mode, source.padding_idx, "from_float")
+            tables = [source.table(t).float() for t in range(len(source.rows))]
+            kw.setdefault("layout", source.layout)
+        else:
+            tables = list(source)
+            if not tables or any(not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32 for x in tables):
+                raise TypeError("from_float takes a BatchedEmbeddingBagMI355 or a sequence of 2-D float32 tensors")
+        kw.setdefault("device", tables[0].device)
+        m = cls([int(x.shape[0]) for x in tables], [int(x.shape[1]) for x in tables], bitwidth, **kw)
+        for t, x in enumerate(tables):
+            m.quantize_from_(t, x.to(m.weights.device))
+        return m
+
+    def _tables(self) -> _QTableSet:
+        if self._ts is None or self._ts.ptrs[0] != self.table(0).data_ptr():
+            self._ts = _QTableSet([self.table(t) for t in range(len(self.rows))], self.dims, self.layout)
+        return self._ts
+
+    _batch_of = BatchedEmbeddingBagMI355._batch_of
+
+    # -- ops ---------------------------------------------------------------------------------
+    def _request(self, indices, offsets, per_sample_weights, bag_begin, bag_count, batch, sanitize: bool):
+        if indices.dtype.is_floating_point or offsets.dtype.is_floating_point:
+            raise TypeError(f"indices and offsets must both be int64 or both int32, got {indices.dtype} / {offsets.dtype}")
+        _require_device(self.weights, f"{type(self).__name__}.weights")
+        B = self._batch_of(offsets, indices) if batch is None else batch
+        ts = self._tables()
+        if sanitize and self.bounds_check_mode != "none":
+            self._sanitize(ts, indices, offsets, B, self.bounds_check_mode, per_sample_weights, bag_begin, bag_count)
+        return ts, B, ts.request(indices, offsets, B, per_sample_weights, bag_begin, bag_count, forward=True)
+
+    def lookup(self, indices, offsets, per_sample_weights=None, out=None, bag_begin=0, bag_count=None, batch: Optional[int] = None):
+        """The pooled forward; ``bag_begin/bag_count`` select a batch slice (bags outside it keep what ``out`` held)."""
+        ts, B, op = self._request(indices, offsets, per_sample_weights, bag_begin, bag_count, batch, True)
+        _, _, shape = ts.out_desc(B)
+        odt = self.output_dtype
+        if out is None:
+            out = torch.empty(shape, dtype=odt, device=ts.device)
+        elif out.dtype != odt or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != ts.device:
+            raise ValueError(f"out must be a contiguous {str(odt).replace('torch.', '')} tensor of shape {shape} on {ts.device}")
+        rc = _lib.load().pm_embbag_fwd_qrows(ctypes.byref(op), self.bitwidth, _WDTYPE[odt], out.data_ptr(), _stream_ptr())
+        if rc:
+            _lib.check(rc)
+        return out
+
+    def forward(self, indices, offsets, per_sample_weights=None, out=None, bag_begin=0, bag_count=None, batch: Optional[int] = None):
+        return self.lookup(indices, offsets, per_sample_weights, out, bag_begin, bag_count, batch)
+
+    def plan(self, indices, offsets, per_sample_weights=None, bag_begin=0, bag_count=None, batch: Optional[int] = None) -> dict:
+        """the launch geometry ``lookup`` would use for this request under the knobs as they stand (``_lib.PLAN_FIELDS`` by name)"""
+        _, _, op = self._request(indices, offsets, per_sample_weights, bag_begin, bag_count, batch, False)
+        return _lib.embbag_qrows_plan(op, self.bitwidth, _WDTYPE[self.output_dtype])
+
+    def sanitize_(self, indices, offsets, batch: Optional[int] = None, mode=None) -> None:
+        """The sanitiser on its own (see :class:`BatchedEmbeddingBagMI355`)."""
+        _require_device(self.weights, f"{type(self).__name__}.weights")
+        B = self._batch_of(offsets, indices) if batch is None else batch
+        mode = bounds_check_mode_name(mode) if mode is not None else self.bounds_check_mode
+        self._sanitize(self._tables(), indices, offsets, B, "warning" if mode == "none" else mode)
+
+    def extra_repr(self) -> str:
+        return (f"rows={self.rows}, dims={self.dims}, bitwidth={self.bitwidth}, layout={self.layout}" +
+                (f", output_dtype={self.output_dtype}" if self._out16 is not None else ""))
+
+
+class QuantizedEmbeddingBagMI355(QuantizedBatchedEmbeddingBagMI355):
+    """``torch.ao.nn.quantized.EmbeddingBag`` / ``nn.EmbeddingBag(mode="sum")`` over ONE row-quantised table, on the HIP kernel.
+
+    ``QuantizedEmbeddingBagMI355(num_embeddings, embedding_dim, bitwidth=8, device="cuda", output_dtype=None, bounds_check_mode="none",
+    weight=None)``; ``forward(input, offsets=None, per_sample_weights=None)`` -> ``[B, D]``: ``input`` 1-D with ``offsets`` ``[B]``
+    (``include_last_offset=False``), or 2-D ``[B, L]`` with ``offsets=None`` (every row one bag of L lookups; ``per_sample_weights`` then has
+    the input's shape).  ``weight``: the packed uint8 ``[num_embeddings, row_bytes]`` bytes of ``quantized::embedding_bag_{byte,4bit}_prepack``
+    (what ``torch.ao.nn.quantized.EmbeddingBag`` holds): the same layout, copied as they are.  ``from_float(m)`` quantises an
+    :class:`EmbeddingBagMI355` or a ``torch.nn.EmbeddingBag`` of ``mode="sum"`` without ``padding_idx`` on the GPU.  Refusals as the
+    batched module's; ``mode`` other than ``"sum"`` and ``padding_idx`` raise ValueError."""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, bitwidth: int = 8, device="cuda", output_dtype=None,
+                 bounds_check_mode="none", mode="sum", padding_idx=None, weight: Optional[torch.Tensor] = None):
+        if weight is not None:
+            _check_spec(bitwidth, [int(embedding_dim)], "bd")
+            want = (int(num_embeddings), quant.host_row_bytes(int(embedding_dim), bitwidth))
+            if weight.dtype != torch.uint8 or tuple(weight.shape) != want:
+                raise ValueError(f"weight must be the packed uint8 rows {want}, got {weight.dtype} {tuple(weight.shape)}")
+        super().__init__([num_embeddings], [embedding_dim], bitwidth, device=device, layout="bd", output_dtype=output_dtype,
+                         bounds_check_mode=bounds_check_mode, pooling_mode=mode, padding_idx=padding_idx)
+        self.num_embeddings, self.embedding_dim = int(num_embeddings), int(embedding_dim)
+        self._off2d: dict = {}
+        if weight is not None:
+            self.table(0).copy_(weight)
+
+    _bags_2d = EmbeddingBagMI355._bags_2d
+
+    @classmethod
+    def from_float(cls, module, bitwidth: int = 8, **kw):
+        if not isinstance(module, (EmbeddingBagMI355, nn.EmbeddingBag)):
+            raise TypeError("from_float takes an EmbeddingBagMI355 or a torch.nn.EmbeddingBag")
+        _sum_only(module.mode, module.padding_idx, "from_float")
+        w = module.weight.detach()
+        kw.setdefault("device", w.device if w.is_cuda else "cuda")
+        m = cls(int(w.shape[0]), int(w.shape[1]), bitwidth, **kw)
+        m.quantize_from_(0, w.to(device=m.weights.device, dtype=torch.float32))
+        return m
+
+    def forward(self, input, offsets=None, per_sample_weights=None):
+        if input.dim() == 2:
+            input, offsets, per_sample_weights = self._bags_2d(input, offsets, per_sample_weights)
+        elif offsets is None:
+            raise ValueError("offsets has to be a 1D Tensor but got None")
+        return self.lookup(input, offsets, per_sample_weights, batch=offsets.numel())
+
+    def extra_repr(self) -> str:
+        return f"{self.num_embeddings}, {self.embedding_dim}, bitwidth={self.bitwidth}" + (f", output_dtype={self.output_dtype}" if self._out16 is not None else "")
