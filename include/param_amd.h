@@ -562,12 +562,48 @@ int pm_embedding_gather(const pm_embbag_batch* op, int32_t out_dtype, void* out,
  * bags_per_block and pm_set_forward_tuning's stage_out are honoured, nothing else of the knobs is read).  Host only, launches nothing;
  * validates as the launching call does, except for `out` of that call.
  * Replaces torch's two CPU operators named above (behind torch.ao.nn.quantized.EmbeddingBag) and the forward of fbgemm's
- * IntNBitTableBatchedEmbeddingBagsCodegen for INT8 / INT4 tables.  Left out: 2-bit tables, un-pooled lookups, mean, padding_idx, pruned
- * rows / index remapping, a padded row stride.
+ * IntNBitTableBatchedEmbeddingBagsCodegen for INT8 / INT4 tables.  Left out: 2-bit tables, mean, padding_idx, pruned rows / index
+ * remapping, a padded row stride (the un-pooled lookup: below).
  * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these two finds out at symbol resolution.
  */
 int pm_embbag_fwd_qrows(const pm_embbag_batch* op, int32_t bits, int32_t out_dtype, void* out, pm_stream_t stream);
 int pm_embbag_qrows_plan(const pm_embbag_batch* op, int32_t bits, int32_t out_dtype, int32_t out[12]);
+
+/*
+ * ROW-QUANTISED TABLES, UN-POOLED -- one output row per lookup from the same tables: the request and the addressing of UN-POOLED
+ * LOOKUPS above (table t owns the positions [offsets[t * batch], offsets[(t + 1) * batch]); `out` is addressed by position with its own
+ * row stride, in elements of out_dtype; out_offsets / out_stride of the request are not read), the tables and bits of ROW-QUANTISED
+ * TABLES.  op->weight_dtype is not read.
+ * THE RULE: for every lookup position j that belongs to a bag inside [bag_begin, bag_begin + bag_count) of its table t, r = indices[j],
+ * per column c < dims[t]
+ *     out[j * out_row_stride + c] = conv( fmaf(scale_r, (float)code[r, c], fl32(+0.0f + bias_r)) )
+ * and nothing else of `out` is touched.  conv: the identity for PM_F32; for PM_BF16 / PM_F16 ONE rounding of that fp32 value, in
+ * registers, as pm_embbag_fwd_out16 rounds.  It is the pooled rule above for one unweighted bag of one lookup, bit for bit -- and with
+ * it what torch's quantized::embedding_bag_{byte,4bit}_rowwise_offsets give for bags of one and quantized::embedding_byte gives
+ * (tests/qgather_rules.py restates it, tests/test_qgather_host.py pins it to the operators).  The addition is part of the rule: it is
+ * NOT fmaf(scale, code, bias) -- a bias of -0.0 enters the fused multiply-add as +0.0, so a finite row gives no -0.0 (a negative scale,
+ * a code of 0 and a bias of -0.0 would give one).  Consequence: the result equals pm_rows_dequantize of the row as a value, not on the sign of zeros.
+ * One launch for any number of tables (csrc/embedding_gather_qrows.hip): pm_embedding_gather's tiles of 256 consecutive positions; a
+ * lane group serves one row with two dwords of codes per lane (dword-aligned loads that stay inside the row), unpacks and applies the
+ * rule in registers and stores non-temporally, several rows in flight.  dims[t] may differ per table: only the columns below dims[t]
+ * of a position's row are written.  No atomics, no workspace, no allocation, stream-ordered.
+ * Refused on the host, before any HIP call: what pm_embbag_fwd_qrows refuses about the request, bits and out_dtype (bits 2 / 16
+ * PM_ERR_UNSUPPORTED, other values PM_ERR_INVALID; the column rules dims[t] % 4 / % 8 and max_dim > 4096 PM_ERR_UNSUPPORTED; a non-zero
+ * table_group / grad_block_shift / grad_block_extra PM_ERR_UNSUPPORTED; an unknown out_dtype PM_ERR_INVALID); per_sample_weights !=
+ * NULL (PM_ERR_UNSUPPORTED); out_row_stride < max_dim or not a multiple of 4 (PM_ERR_INVALID).  num_indices == 0 or bag_count == 0
+ * is then PM_OK without a launch; otherwise a NULL out, or one that is not 16-byte (PM_F32) / 8-byte (16-bit) aligned, is PM_ERR_INVALID.
+ * pm_embedding_gather_qrows_plan: the geometry that call WOULD use (plan_gather_qrows, csrc/launch_plan.h) -- the eight members of
+ * pm_embedding_gather_plan in its order: vec (columns a lane holds per pass: 8 / 16), group_lanes, tile, col_passes, unroll (pm_set_tuning's
+ * unroll rounded down to 1 / 2 / 4 / 8), lds_borders, xcd_contiguous, grid.  Host only, launches nothing; validates the request as the
+ * launching call does (`out` and out_row_stride of that call, and an out_dtype, are not part of it).
+ * Replaces quantized::embedding_byte / embedding_4bit (behind torch.ao.nn.quantized.Embedding) and PoolingMode.NONE of fbgemm's
+ * IntNBitTableBatchedEmbeddingBagsCodegen for INT8 / INT4 tables.  Left out: 2-bit tables, a padded row stride, pruned rows / index
+ * remapping, padding_idx, per-position weights, a lane width per format, any backward (the tables are not trainable).
+ * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these two finds out at symbol resolution.
+ */
+int pm_embedding_gather_qrows(const pm_embbag_batch* op, int32_t bits, int32_t out_dtype, void* out, int64_t out_row_stride,
+                              pm_stream_t stream);
+int pm_embedding_gather_qrows_plan(const pm_embbag_batch* op, int32_t bits, int64_t out[8]);
 
 /*
  * SEQUENCE GRADIENTS -- the batched backward of the un-pooled lookup above: the gradient of pm_embedding_gather's rows applied to all

@@ -4,7 +4,8 @@ Layout (only what the hot path needs):
   csrc/              hand-written HIP kernels + the C ABI (include/param_amd.h) -> libparam_amd.so
   _lib.py            ctypes binding (no fallback: raises if the library is missing)
   embedding_bag.py   EmbeddingBagMI355 / BatchedEmbeddingBagMI355 (nn.EmbeddingBag / TBE surface), EmbeddingMI355 (nn.Embedding)
-  quantized_bag.py   QuantizedBatchedEmbeddingBagMI355 / QuantizedEmbeddingBagMI355: pooled lookup over 8- / 4-bit row-quantised tables
+  quantized_bag.py   QuantizedBatchedEmbeddingBagMI355 / QuantizedEmbeddingBagMI355 / QuantizedEmbeddingMI355: pooled and un-pooled
+                     lookups over 8- / 4-bit row-quantised tables
   indices.py         uniform / Zipf index generation (reference init_indices + a scalable form)
   compute/pt/        mirror of the reference train/compute/pt emb driver CLI
   comms/pt/          mirror of the reference train/comms/pt backend plug-in, metrics and drivers
@@ -17,6 +18,6 @@ from .embedding_bag import (  # noqa: F401
     check_request,
     fill_random_,
 )
-from .quantized_bag import QuantizedBatchedEmbeddingBagMI355, QuantizedEmbeddingBagMI355  # noqa: F401
+from .quantized_bag import QuantizedBatchedEmbeddingBagMI355, QuantizedEmbeddingBagMI355, QuantizedEmbeddingMI355  # noqa: F401
 
 __version__ = "0.1.0"

@@ -90,6 +90,8 @@ EXPORTED_SYMBOLS = (
     "pm_embedding_gather_plan",
     "pm_embbag_fwd_qrows",
     "pm_embbag_qrows_plan",
+    "pm_embedding_gather_qrows",
+    "pm_embedding_gather_qrows_plan",
 )
 
 # pm_embbag_plan (include/param_amd.h): the kinds, and the members of the two plans in the order the queries fill them
@@ -309,6 +311,11 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embbag_fwd_qrows.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, i32, vp, vp]
     L.pm_embbag_qrows_plan.restype = ctypes.c_int
     L.pm_embbag_qrows_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, i32, ctypes.POINTER(i32)]
+    # ... un-pooled: (op, bits 8 | 4, PM_F32 | PM_BF16 | PM_F16, out, out_row_stride, stream) and its plan query (op, bits, int64 out[8])
+    L.pm_embedding_gather_qrows.restype = ctypes.c_int
+    L.pm_embedding_gather_qrows.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, i32, vp, i64, vp]
+    L.pm_embedding_gather_qrows_plan.restype = ctypes.c_int
+    L.pm_embedding_gather_qrows_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, ctypes.POINTER(i64)]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]
@@ -397,6 +404,13 @@ def embbag_qrows_plan(op: pm_embbag_batch, bits: int, out_dtype: int = PM_F32) -
     out = (ctypes.c_int32 * len(PLAN_FIELDS))()
     check(load().pm_embbag_qrows_plan(ctypes.byref(op), int(bits), int(out_dtype), out))
     return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
+
+
+def embedding_gather_qrows_plan(op: pm_embbag_batch, bits: int) -> dict:
+    """``pm_embedding_gather_qrows_plan``: the geometry ``pm_embedding_gather_qrows`` would use for ``op`` -- ``GATHER_PLAN_FIELDS`` by name"""
+    out = (ctypes.c_int64 * len(GATHER_PLAN_FIELDS))()
+    check(load().pm_embedding_gather_qrows_plan(ctypes.byref(op), int(bits), out))
+    return dict(zip(GATHER_PLAN_FIELDS, (int(v) for v in out)))
 
 
 def set_backward_tuning(sort_impl: int = -1, order: int = -1, xcd_affine: int = -1, max_phases: int = -1) -> None:

@@ -674,6 +674,50 @@ int pm_embedding_gather(const pm_embbag_batch* op, int32_t out_dtype, void* out,
     return PM_OK;
 }
 
+// ---- un-pooled rows of row-quantised tables (embedding_gather_qrows.hip) -----------------------------------------------------------------
+// what the lookup and its plan query refuse about the request, in one order: what pm_embbag_fwd_qrows refuses (qrows_request), then
+// what pm_embedding_gather refuses about a request
+static int qgather_request(const pm_embbag_batch* op, int32_t bits, int32_t out_dtype, const pm::PlanKnobs& knobs) {
+    pm::PlanShape shape;
+    int out_bytes = 0;
+    const int rc = qrows_request(op, bits, out_dtype, knobs, shape, out_bytes);
+    if (rc != PM_OK) return rc;
+    if (op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "un-pooled rows are unweighted: per_sample_weights must be NULL");
+    return PM_OK;
+}
+
+int pm_embedding_gather_qrows(const pm_embbag_batch* op, int32_t bits, int32_t out_dtype, void* out, int64_t out_row_stride, pm_stream_t stream) {
+    const pm::PlanKnobs knobs = current_knobs();
+    const int rc = qgather_request(op, bits, out_dtype, knobs);
+    if (rc != PM_OK) return rc;
+    if (out_row_stride < op->max_dim || out_row_stride % 4 != 0)
+        return fail(PM_ERR_INVALID, "out_row_stride must be a multiple of 4 elements and at least max_dim");
+    if (op->num_indices == 0 || op->bag_count == 0) return PM_OK;      // nothing to write, whatever `out` is
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const uintptr_t align = out_dtype == PM_F32 ? 16 : 8;
+    if (reinterpret_cast<uintptr_t>(out) % align != 0) return fail(PM_ERR_INVALID, "out must be " + std::to_string(align) + "-byte aligned");
+    const pm::GatherPlan g = pm::plan_gather_qrows(*op, bits, knobs);
+    if (g.grid > pm::kMaxGrid) return fail(PM_ERR_UNSUPPORTED, "grid too large");
+    pm::KParams p;
+    fill_params(op, pm::LaunchPlan{}, p);      // (the request; a gather has no bag tiling)
+    p.io = static_cast<float*>(out);           // (addressed in out_dtype's elements)
+    p.out_stride = out_row_stride;
+    const hipError_t h = pm::launch_embedding_gather_qrows(p, bits, out_dtype, g, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embedding_gather_qrows launch");
+    return PM_OK;
+}
+
+int pm_embedding_gather_qrows_plan(const pm_embbag_batch* op, int32_t bits, int64_t out[8]) {
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const pm::PlanKnobs knobs = current_knobs();
+    const int rc = qgather_request(op, bits, PM_F32, knobs);
+    if (rc != PM_OK) return rc;
+    const pm::GatherPlan g = pm::plan_gather_qrows(*op, bits, knobs);
+    const int64_t v[8] = {g.vec, g.group_lanes, g.tile, g.col_passes, g.unroll, g.lds_borders, g.xcd_contiguous, g.grid};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return PM_OK;
+}
+
 static int pad_guard_layout(int32_t num_tables, int32_t max_dim, int32_t table_dtype, int32_t state_kind, int64_t& row_slot, int64_t& slot) {
     if (num_tables < 1) return fail(PM_ERR_INVALID, "num_tables must be >= 1");
     if (!dtype_is_weight(table_dtype)) return fail(PM_ERR_INVALID, "weight/dst dtype must be PM_F32, PM_BF16 or PM_F16");

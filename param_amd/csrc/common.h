@@ -219,6 +219,8 @@ hipError_t launch_grad_widen(const KParams& p, int max_dim, const int64_t* pad_i
                              float* grad32, hipStream_t stream);
 // un-pooled rows (embedding_gather.hip): p.io = out of out_dtype (PM_F32 | PM_BF16 | PM_F16), p.out_stride = its row stride in elements
 hipError_t launch_embedding_gather(const KParams& p, int weight_dtype, int out_dtype, const GatherPlan& g, hipStream_t stream);
+// ... over 8- / 4-bit row-quantised tables (embedding_gather_qrows.hip): bits 8 | 4; g: plan_gather_qrows'
+hipError_t launch_embedding_gather_qrows(const KParams& p, int bits, int out_dtype, const GatherPlan& g, hipStream_t stream);
 
 // sort-based deterministic backward (embbag_bwd_sorted.hip)
 hipError_t sorted_workspace_bytes(const KParams& p, int64_t max_rows, int max_dim, size_t& bytes);

@@ -74,6 +74,37 @@ __device__ __forceinline__ int64_t row_offset(int64_t r, int64_t row_bytes) {
     return r * row_bytes;
 }
 
+// The un-pooled kernels' table of lookup position j: "the last table whose first bag starts at or before j" among the T borders
+// b[t] = offsets[t * B] -- bag_start_or_end's rule and the bounds check's --, searched in s_border (an LDS copy the workgroup fills
+// here: lds_borders, T <= kGatherLdsBorders; every thread of the workgroup calls this) or in global memory.  -1: the position is not
+// written -- past the index array (!inside), in front of every table, or in a bag outside the batch slice.
+// embedding_gather_qrows.hip calls it; embedding_gather.hip, where these lines come from, still spells them out: calling this moved
+// its measured kernels' code (a third of the assembly's lines differ), and what that costs has not been measured.
+__device__ __forceinline__ int gather_position_table(const KParams& p, int lds_borders, int64_t* s_border, int64_t j, bool inside) {
+    const int tid = static_cast<int>(threadIdx.x);
+    int lo = 0, hi = p.T;
+    if (lds_borders) {
+        if (tid < p.T) s_border[tid] = load_index(p.offsets, static_cast<int64_t>(tid) * p.B, p.idx64);
+        __syncthreads();
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (s_border[mid] <= j) lo = mid + 1; else hi = mid;
+        }
+    } else {
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (load_index(p.offsets, static_cast<int64_t>(mid) * p.B, p.idx64) <= j) lo = mid + 1; else hi = mid;
+        }
+    }
+    const int t = lo - 1;
+    bool ok = inside && t >= 0;
+    if (ok && (p.bag_begin != 0 || p.bag_count != p.B)) {
+        const int64_t g0 = static_cast<int64_t>(t) * p.B + p.bag_begin;
+        ok = j >= bag_start_or_end(p, g0) && j < bag_start_or_end(p, g0 + p.bag_count);
+    }
+    return ok ? t : -1;
+}
+
 // one lookup joins the sum: the row's 16 bytes widened to fp32, then one add -- or one fmaf when weighted -- per element
 template <typename WT, bool WEIGHTED>
 __device__ __forceinline__ void accumulate(float (&acc)[Elem<WT>::kVec], const u32x4& raw, float w) {

@@ -474,4 +474,34 @@ static inline GatherPlan plan_gather(const pm_embbag_batch& op, int elem_dtype, 
     return g;
 }
 
+// ---- gather over row-quantised tables: pm_embedding_gather_qrows (embedding_gather_qrows.hip) -------------------------------------------
+// The gather's tiles and block order; the lane group is the pooled qrows kernel's: a lane holds kQrowsLaneDwords dwords of a row's codes
+// (qrows_lane_columns: 8 columns of an 8-bit row, 16 of a 4-bit row), G = group_lanes(max_dim, that), and rows wider than G such pieces
+// take column passes (8-bit D > 512, 4-bit D > 1024; at most 8 at kQrowsMaxDim).  vec: the columns a lane holds per pass.
+// Rows in flight per lane group: pm_set_tuning's unroll rounded down to 1 / 2 / 4 / 8, as plan_gather rounds it.  The default is this
+// kernel's own, measured: its two parents disagree (kGatherUnroll = 8, kQrowsUnroll = 4).  tools/qgather_probe.py, 16 x 10 M x 128,
+// 2.6 M lookups, us per call, medians of 5 windows of one process, spread <= 0.9 % (profiles/qgather_probe.json); unroll 1 / 2 / 4 / 8:
+//   8-bit -> fp32, uniform indices 385.4 / 378.6 / 374.7 / 374.9      Zipf 376.4 / 371.2 / 360.7 / 355.4
+//   8-bit -> fp16, uniform indices 252.0 / 244.3 / 242.3 / 242.3      Zipf 187.9 / 183.0 / 179.7 / 177.0
+//   4-bit -> fp32, uniform indices 353.1 / 345.1 / 341.6 / 341.7      Zipf 335.6 / 318.3 / 327.7 / 327.2
+//   4-bit -> fp16, uniform indices 295.8 / 265.6 / 272.1 / 273.0      Zipf 317.4 / 285.2 / 298.7 / 299.0
+// (4-bit D = 128 is a group of 8 lanes: 4 and 8 are one batch of 4 / 8 rows).  Eight is the 8-bit format's optimum or within 0.1 % of it
+// everywhere; the 4-bit format would take two (up to 4.8 % faster than eight in three of its four cases, 1 % slower in the fourth).  ONE
+// default: eight -- with two the 8-bit lookups lose 1 .. 4.4 %.  D = 512 (groups of 64 / 32 lanes, 0.66 M lookups, uniform): 8-bit 359.2 /
+// 366.3 / 358.8 / 367.6, 4-bit 312.2 / 311.7 / 322.7 / 319.5 -- within 2.5 % of each other.  A default per format: not built.
+constexpr int kQgatherUnroll = 8;
+static inline GatherPlan plan_gather_qrows(const pm_embbag_batch& op, int bits, const PlanKnobs& k) {
+    GatherPlan g = {};
+    g.vec = qrows_lane_columns(bits);
+    g.group_lanes = group_lanes(op.max_dim, g.vec);
+    g.tile = kBlock;
+    g.col_passes = static_cast<int32_t>(ceil_div(op.max_dim, static_cast<int64_t>(g.group_lanes) * g.vec));
+    const int u = k.unroll != 0 ? k.unroll : kQgatherUnroll;
+    g.unroll = u >= 8 ? 8 : (u >= 4 ? 4 : (u >= 2 ? 2 : 1));
+    g.lds_borders = op.num_tables + 1 <= kGatherLdsBorders ? 1 : 0;
+    g.xcd_contiguous = (op.num_tables > 1 && k.xcd_affine != 0) ? 1 : 0;
+    g.grid = ceil_div(op.num_indices, g.tile);
+    return g;
+}
+
 }  // namespace pm

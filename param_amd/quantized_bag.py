@@ -1,20 +1,27 @@
-"""Pooled lookup over 8- and 4-bit ROW-QUANTISED embedding tables (``csrc/embbag_fwd_qrows.hip`` through ``pm_embbag_fwd_qrows``).
+"""Pooled and un-pooled lookups over 8- and 4-bit ROW-QUANTISED embedding tables (``csrc/embbag_fwd_qrows.hip`` through
+``pm_embbag_fwd_qrows``, ``csrc/embedding_gather_qrows.hip`` through ``pm_embedding_gather_qrows``).
 
 * :class:`QuantizedBatchedEmbeddingBagMI355` -- T tables stored as the bytes ``quantize_rows`` writes (torch's
   ``quantized::embedding_bag_{byte,4bit}_prepack`` layout), pooled by ONE launch that reads those bytes: no fp32 copy of a table exists.
   The serving-side sibling of :class:`BatchedEmbeddingBagMI355`; what fbgemm's ``IntNBitTableBatchedEmbeddingBagsCodegen`` is for.
+  ``lookup_sequence`` is its un-pooled lookup (``PoolingMode.NONE``): one dequantised row per lookup position, one launch.
 * :class:`QuantizedEmbeddingBagMI355` -- the single-table module with ``nn.EmbeddingBag``'s call; what
   ``torch.ao.nn.quantized.EmbeddingBag`` is for.
+* :class:`QuantizedEmbeddingMI355` -- the single-table un-pooled module with ``nn.Embedding``'s call; what
+  ``torch.ao.nn.quantized.Embedding`` is for.
 
 The arithmetic is fixed (include/param_amd.h, "ROW-QUANTISED TABLES") and equals torch's CPU operators
 ``quantized::embedding_bag_{byte,4bit}_rowwise_offsets`` bit for bit: per element and lookup, in index order from +0.0,
 ``acc = fmaf(scale * w, code, acc + bias * w)``.  It is NOT bit-identical to the fp32 forward over ``dequantized_table(t)`` (which rounds
 every dequantised element first); the two agree within summation rounding.  A bag of exactly one unweighted lookup equals
-``dequantize_rows`` of that row as a value.
+``dequantize_rows`` of that row as a value -- and that bag of one is the un-pooled rule: per lookup and column
+``out = fmaf(scale, code, +0.0 + bias)`` (the addition is part of it: the result equals ``dequantize_rows`` as a value, not on the sign
+of zeros), rounded once for a 16-bit ``output_dtype``; bit for bit ``quantized::embedding_byte`` / the two operators above over bags of one.
 
-Forward only: the tables are buffers, nothing requires grad.  There is no CPU path.  Left out, on purpose: 2-bit tables, an un-pooled
-(sequence) lookup, mean pooling, ``padding_idx``, pruned rows / index remapping, a padded row stride, per-table lane sub-groups for mixed
-dims, the operator plug-in, any backward.
+Forward only: the tables are buffers, nothing requires grad.  There is no CPU path.  Left out, on purpose: 2-bit tables, mean pooling,
+``padding_idx``, per-position weights of the un-pooled lookup, mixed dims of the un-pooled lookup from Python (the C call serves them),
+pruned rows / index remapping, a padded row stride, per-table lane sub-groups for mixed dims, a lane width per format, the operator
+plug-in, any backward.
 """
 from __future__ import annotations
 
@@ -25,8 +32,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib, quant
-from .embedding_bag import (_WDTYPE, BatchedEmbeddingBagMI355, EmbeddingBagMI355, _BoundsChecked, _TableSet, _require_device, _stream_ptr,
-                            bounds_check_mode_name)
+from .embedding_bag import (_IDTYPE, _WDTYPE, BatchedEmbeddingBagMI355, EmbeddingBagMI355, EmbeddingMI355, _BoundsChecked, _TableSet,
+                            _check_rows_out, _require_device, _stream_ptr, bounds_check_mode_name)
 
 BITWIDTHS = (8, 4)
 MAX_DIM = 4096      # kQrowsMaxDim (csrc/launch_plan.h)
@@ -104,6 +111,8 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     call -- takes the TBE request of :class:`BatchedEmbeddingBagMI355` and returns ``[B, sum D]`` (``"bd"``) or ``[T, B, D]`` (``"tbd"``) in
     ``output_dtype`` (fp32, or bf16 / fp16: the fp32 value rounded once in the kernel).  The rule is the module docstring's.
     ``plan(...)`` returns the launch geometry of the same request as a dict (``pm_embbag_qrows_plan``; nothing is launched).
+    ``lookup_sequence(indices, offsets, batch=None, out=None, bag_begin=0, bag_count=None)`` is the UN-POOLED lookup of the same request:
+    ``[N, D]``, one dequantised row per lookup position (one common embedding dim); ``sequence_plan(...)`` its launch geometry.
     ``bounds_check_mode``: see :class:`_BoundsChecked` -- the sanitiser reads rows, indices and offsets, never the tables.
 
     No gradients: the tables are a buffer (``state_dict`` round-trips the bytes), the output never requires grad.  ValueError before
@@ -216,6 +225,39 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         _, _, op = self._request(indices, offsets, per_sample_weights, bag_begin, bag_count, batch, False)
         return _lib.embbag_qrows_plan(op, self.bitwidth, _WDTYPE[self.output_dtype])
 
+    # -- un-pooled ---------------------------------------------------------------------------
+    def _sequence_request(self, indices, offsets, batch, bag_begin, bag_count, sanitize: bool, out=None):
+        if len(set(self.dims)) != 1:
+            raise ValueError("lookup_sequence needs one common embedding dim (mixed dims are served by pm_embedding_gather_qrows, the C call)")
+        if out is not None:
+            _check_rows_out(out, indices.numel(), self.dims[0], self.output_dtype, self.weights.device)
+        return self._request(indices, offsets, None, bag_begin, bag_count, batch, sanitize)
+
+    def lookup_sequence(self, indices, offsets, batch: Optional[int] = None, out=None, bag_begin=0, bag_count=None):
+        """The UN-POOLED forward over the module's T tables (int-nbit TBE's ``PoolingMode.NONE``): ``[N, D]`` in the module's
+        ``output_dtype``, ``N = indices.numel()``, row ``j`` = row ``indices[j]`` of the table that owns lookup position ``j`` (table ``t``
+        owns ``[offsets[t * B], offsets[(t + 1) * B])``), dequantised by the module docstring's rule for a bag of one -- one launch,
+        ``pm_embedding_gather_qrows``, that reads the quantised bytes.  Runs after ``bounds_check_mode``, like ``lookup``.
+        ``bag_begin/bag_count`` select a batch slice: only the rows of lookups inside it are written -- a caller's ``out`` keeps every
+        other row, a tensor allocated here holds zeros there.  Needs one common embedding dim; mixed dims and an ``out`` that is not a
+        contiguous ``[N, D]`` tensor of ``output_dtype`` on the module's device raise ValueError, floating-point indices TypeError."""
+        ts, B, op = self._sequence_request(indices, offsets, batch, bag_begin, bag_count, True, out)
+        n, D, odt = indices.numel(), self.dims[0], self.output_dtype
+        if out is None:
+            whole = bag_begin == 0 and bag_count in (None, B)
+            out = (torch.empty if whole else torch.zeros)((n, D), dtype=odt, device=ts.device)
+        if n:
+            rc = _lib.load().pm_embedding_gather_qrows(ctypes.byref(op), self.bitwidth, _WDTYPE[odt], out.data_ptr(), D, _stream_ptr())
+            if rc:
+                _lib.check(rc)
+        return out
+
+    def sequence_plan(self, indices, offsets, batch: Optional[int] = None, bag_begin=0, bag_count=None) -> dict:
+        """the launch geometry ``lookup_sequence`` would use for this request under the knobs as they stand (``_lib.GATHER_PLAN_FIELDS``
+        by name; ``pm_embedding_gather_qrows_plan``, nothing is launched)"""
+        _, _, op = self._sequence_request(indices, offsets, batch, bag_begin, bag_count, False)
+        return _lib.embedding_gather_qrows_plan(op, self.bitwidth)
+
     def sanitize_(self, indices, offsets, batch: Optional[int] = None, mode=None) -> None:
         """The sanitiser on its own (see :class:`BatchedEmbeddingBagMI355`)."""
         _require_device(self.weights, f"{type(self).__name__}.weights")
@@ -272,6 +314,76 @@ class QuantizedEmbeddingBagMI355(QuantizedBatchedEmbeddingBagMI355):
         elif offsets is None:
             raise ValueError("offsets has to be a 1D Tensor but got None")
         return self.lookup(input, offsets, per_sample_weights, batch=offsets.numel())
+
+    def extra_repr(self) -> str:
+        return f"{self.num_embeddings}, {self.embedding_dim}, bitwidth={self.bitwidth}" + (f", output_dtype={self.output_dtype}" if self._out16 is not None else "")
+
+
+class QuantizedEmbeddingMI355(QuantizedBatchedEmbeddingBagMI355):
+    """``torch.ao.nn.quantized.Embedding`` over ONE row-quantised table, on the HIP kernel: the un-pooled sibling of
+    :class:`QuantizedEmbeddingBagMI355` and the quantised sibling of :class:`EmbeddingMI355`.
+
+    ``QuantizedEmbeddingMI355(num_embeddings, embedding_dim, bitwidth=8, device="cuda", output_dtype=None, bounds_check_mode="none",
+    weight=None)``; ``forward(input)`` takes an int32 / int64 tensor of any shape and returns ``[*input.shape, D]`` in ``output_dtype``:
+    row ``input[...]`` of the table per lookup, dequantised by the module docstring's rule for a bag of one (bit for bit what
+    ``quantized::embedding_byte`` computes), moved by ONE launch (``pm_embedding_gather_qrows``: the request is :class:`EmbeddingMI355`'s
+    -- one table, one bag, ``offsets = [0]``).  An empty input returns an empty result without a launch.  ``weight``: the packed uint8
+    ``[num_embeddings, row_bytes]`` bytes of ``quantized::embedding_bag_{byte,4bit}_prepack`` (what ``torch.ao.nn.quantized.Embedding``
+    holds), copied as they are.  ``from_float(m, bitwidth=8)`` quantises a ``torch.nn.Embedding`` or an :class:`EmbeddingMI355` on the
+    GPU (``quantize_from_``: D a multiple of 8 up to 512); its ``padding_idx`` changes nothing here (a forward returns the padding row as
+    stored), ``max_norm`` raises ValueError.  ``table(0)``, ``dequantized_table(0)``, ``sanitize_(input)`` and the ``state_dict`` round
+    trip are the batched module's; no parameters, the output never requires grad.  A floating-point input raises TypeError, tensors
+    that are not on a ROCm device RuntimeError (no CPU fallback)."""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, bitwidth: int = 8, device="cuda", output_dtype=None,
+                 bounds_check_mode="none", weight: Optional[torch.Tensor] = None):
+        if weight is not None:
+            _check_spec(bitwidth, [int(embedding_dim)], "bd")
+            want = (int(num_embeddings), quant.host_row_bytes(int(embedding_dim), bitwidth))
+            if weight.dtype != torch.uint8 or tuple(weight.shape) != want:
+                raise ValueError(f"weight must be the packed uint8 rows {want}, got {weight.dtype} {tuple(weight.shape)}")
+        super().__init__([num_embeddings], [embedding_dim], bitwidth, device=device, layout="bd", output_dtype=output_dtype,
+                         bounds_check_mode=bounds_check_mode)
+        self.num_embeddings, self.embedding_dim = int(num_embeddings), int(embedding_dim)
+        self._off0: dict = {}        # the request's offsets [0], one per (dtype, device)
+        if weight is not None:
+            self.table(0).copy_(weight)
+
+    _offsets0 = EmbeddingMI355._offsets0
+
+    @classmethod
+    def from_float(cls, module, bitwidth: int = 8, **kw):
+        if not isinstance(module, (EmbeddingMI355, nn.Embedding)):
+            raise TypeError("from_float takes an EmbeddingMI355 or a torch.nn.Embedding")
+        if getattr(module, "max_norm", None) is not None:
+            raise ValueError("from_float: max_norm is not implemented (the rows would be renormalised at lookup time)")
+        w = module.weight.detach()
+        kw.setdefault("device", w.device if w.is_cuda else "cuda")
+        m = cls(int(w.shape[0]), int(w.shape[1]), bitwidth, **kw)
+        m.quantize_from_(0, w.to(device=m.weights.device, dtype=torch.float32))
+        return m
+
+    def _flat(self, input) -> torch.Tensor:
+        if not isinstance(input, torch.Tensor) or input.dtype not in _IDTYPE:
+            raise TypeError(f"QuantizedEmbeddingMI355: input must be an int32 or int64 tensor, got {getattr(input, 'dtype', type(input))}")
+        _require_device(self.weights, "QuantizedEmbeddingMI355.weights")
+        _require_device(input, "input")
+        return input.reshape(-1).contiguous()
+
+    def forward(self, input):
+        indices = self._flat(input)
+        if not indices.numel():
+            return torch.empty((*input.shape, self.embedding_dim), dtype=self.output_dtype, device=self.weights.device)
+        return self.lookup_sequence(indices, self._offsets0(indices), batch=1).view(*input.shape, self.embedding_dim)
+
+    def sanitize_(self, input, mode=None) -> None:
+        """The sanitiser on its own: repairs ``input`` in place (it must be contiguous: a copy would be repaired instead),
+        stream-ordered.  ``mode``: default the module's ``bounds_check_mode``, ``"warning"`` where that is ``"none"``."""
+        if not input.is_contiguous():
+            raise ValueError("sanitize_ needs a contiguous input (it is repaired in place)")
+        indices = self._flat(input)
+        if indices.numel():
+            super().sanitize_(indices, self._offsets0(indices), batch=1, mode=mode)
 
     def extra_repr(self) -> str:
         return f"{self.num_embeddings}, {self.embedding_dim}, bitwidth={self.bitwidth}" + (f", output_dtype={self.output_dtype}" if self._out16 is not None else "")
