@@ -390,6 +390,27 @@ def _workspace(ts: _TableSet, op, max_rows: Optional[int] = None, query=None) ->
     return ts.scratch("_ws", query(ctypes.byref(op), max(ts.rows) if max_rows is None else max_rows))
 
 
+def _sort_issued(ts: _TableSet, ws: torch.Tensor) -> None:
+    """a key sort (on its own, or inside a fused call) has been issued on the table set's workspace ``ws``"""
+    ts._ws_sorted = ws.data_ptr()
+
+
+_NOT_SORTED = {False: "pm_embbag_sort_indices has not been called for this request on this workspace (same indices / offsets pointers, "
+                      "batch, bag slice and weights as the sort's)",
+               True: "pm_embseq_sort_indices has not been called for this request on this workspace (same indices / offsets pointers, "
+                     "batch and bag slice as the sort's)"}
+
+
+def _require_sort(ts: _TableSet, ws: torch.Tensor, sequence: bool = False) -> None:
+    """``presorted=True`` on a workspace this table set has not sorted on: refused here, with the library's text.  The library keeps its
+    record of the last sort by the workspace's ADDRESS, and torch's caching allocator hands the address of a freed workspace out again:
+    to the fresh workspace of another table set, the record of a sort of the very same request tensors that a module since freed issued
+    there would pass for its own -- and the apply would read whatever the block holds now.  (A C caller owns its workspaces and the
+    order of its calls; here the workspace's lifetime is this layer's.)"""
+    if ts.__dict__.get("_ws_sorted") != ws.data_ptr():
+        raise _lib.ParamAmdError(_lib.PM_ERR_INVALID, _NOT_SORTED[sequence])
+
+
 def _check_grad(ts: _TableSet, grad, B, out16: Optional[torch.dtype] = None) -> torch.Tensor:
     """the gradient of a batch of B bags in the table set's output layout, contiguous: fp32 (always), or the module's 16-bit output
     dtype ``out16``"""
@@ -486,6 +507,7 @@ def _sort_indices(ts: _TableSet, indices, offsets, B, psw=None, bag_begin=0, bag
     ws = _workspace(ts, op)
     _lib.check(_lib.load().pm_embbag_sort_indices_ex(ctypes.byref(op), max(ts.rows), phases, ws.data_ptr(), ws.numel(),
                                                      _stream_ptr()))
+    _sort_issued(ts, ws)
 
 
 def sort_plan(ts: _TableSet, indices, offsets, B, psw=None, bag_begin=0, bag_count=None, phases: int = 1,
@@ -627,10 +649,14 @@ def _sorted_chunks_call(ts: _TableSet, op, indices, offsets, B, psw, presorted: 
             # (hybrid backward: rows looked up once skip the sort)
             sub.fixed_pooling = 0  # (the cached descriptor may carry a hint from an alternates-build run: the segmented sort takes none)
             _lib.check(fused(sub, t0, max_rows, ws))
+            _sort_issued(ts, ws)
             continue
         if not presorted:      # the alternative key sorts (sort_impl 1 / 2) read a pooling hint and may lay out two bag phases
             sub.fixed_pooling = ts.fixed_pooling(indices, offsets, B, pooling) if sub is op else 0
             _lib.check(L.pm_embbag_sort_indices_ex(ctypes.byref(sub), max_rows, phases, ws.data_ptr(), ws.numel(), s))
+            _sort_issued(ts, ws)
+        else:
+            _require_sort(ts, ws)
         _lib.check(sorted_(sub, t0, max_rows, ws))
 
 
@@ -645,6 +671,7 @@ def _seq_sort_indices(ts: _TableSet, indices, offsets, B, bag_begin=0, bag_count
     op.fixed_pooling = 0
     ws = _workspace(ts, op)
     _lib.check(_lib.load().pm_embseq_sort_indices(ctypes.byref(op), max(ts.rows), ws.data_ptr(), ws.numel(), _stream_ptr()))
+    _sort_issued(ts, ws)
 
 
 def _seq_bwd(ts: _TableSet, grad, indices, offsets, B, bag_begin, bag_count, presorted: bool, fused, sorted_, guard: _PadGuard) -> None:
@@ -659,11 +686,15 @@ def _seq_bwd(ts: _TableSet, grad, indices, offsets, B, bag_begin, bag_count, pre
     op = ts.request(indices, offsets, B, None, bag_begin, bag_count)
     op.fixed_pooling = 0
     D, base, esz = ts.dims[0], indices.data_ptr(), indices.element_size()
+    if presorted:      # (at most 1024 tables: one range, the whole request's workspace; refused before the guard launches anything)
+        _require_sort(ts, _workspace(ts, op), True)
     guard.save()
     for sub, t0, _, max_rows in _table_chunks(ts, op, indices, offsets, B):
         ws = _workspace(ts, sub, max_rows)
         n0 = ((sub.indices or 0) - base) // esz
         _lib.check((sorted_ if presorted else fused)(sub, grad.data_ptr() + n0 * D * 4, t0, max_rows, ws))
+        if not presorted:
+            _sort_issued(ts, ws)
     guard.restore()
 
 
@@ -862,6 +893,7 @@ def _sparse_grad_call(ts: _TableSet, op, grad, max_rows: int, dims: Sequence[int
     ws = _workspace(ts, op, max_rows, L.pm_embbag_sparse_grad_workspace)
     s = _stream_ptr()
     _lib.check(L.pm_embbag_sort_indices(ctypes.byref(op), max_rows, ws.data_ptr(), ws.numel(), s))
+    _sort_issued(ts, ws)
     counts = torch.empty(len(dims), dtype=torch.int64, device=ts.device)
     _lib.check(L.pm_embbag_sparse_grad_count(ctypes.byref(op), max_rows, ws.data_ptr(), ws.numel(), counts.data_ptr(), s))
     U = counts.tolist()                                   # the call's one host synchronisation

@@ -189,6 +189,13 @@ def dlrm_sparse_path(rank, world, port):
         assert kinds == ["all_to_all"] * 4 and path.commDetails[2]["out_split"] == [B * 2 * D, B * 1 * D]
     finally:
         bf.shutdown()
+        # the path, its arguments and the backend hold the process group (through reference cycles with the lookup closure): released
+        # here, inside a live interpreter.  Left to interpreter shutdown, gloo's threads were torn down while the peer rank was still
+        # working, and rank 0 aborted on a loaded machine ("terminate called without an active exception", about 3 runs in 100).
+        import gc
+
+        ca = path = bf = lookup = None
+        gc.collect()
 
 
 def dlrm_driver(rank, world, port, outdir, extra_json="[]", num_batches="4", flags_json=""):

@@ -331,6 +331,43 @@ def test_presorted_equals_fused_and_the_two_kinds_of_sort_do_not_mix():
         c.sequence_scatter_add_(g, idx, off, 1.0, batch=B, presorted=True)
 
 
+def test_presorted_is_refused_on_a_workspace_another_table_set_sorted_on():
+    """The library keeps its record of the last sort by the workspace's ADDRESS, and torch's caching allocator hands the block of a
+    freed workspace to the next one of its size.  Modelled without the allocator: module ``c`` is given the very workspace tensor on which
+    module ``a`` has sorted the same request tensors.  ``c`` has sorted nothing: ``presorted=True`` is refused for it, sequence and
+    pooled, although the library's record under that address fits the call; after a sort of its own the call goes through."""
+    from param_amd import _lib
+
+    D = 8
+    idx_h, off_h = _request()
+    idx, off, g = _dev(idx_h), _dev(off_h), _dev(_grad(idx_h.size, D))
+    pooled = torch.ones(B, T * D, device=DEV)
+    for sequence in (True, False):
+        a, c = _module(D), _module(D)
+        if sequence:
+            a.sequence_sort_indices(idx, off, batch=B)
+        else:
+            a.sort_indices(idx, off, batch=B)
+        c._tables()._ws = a._tables()._ws
+        keep = _wbits(c)
+        with pytest.raises(_lib.ParamAmdError, match="pm_embseq_sort_indices has not been called" if sequence else
+                           "pm_embbag_sort_indices has not been called"):
+            if sequence:
+                c.sequence_scatter_add_(g, idx, off, 1.0, batch=B, presorted=True)
+            else:
+                c.scatter_add_(pooled, idx, off, 1.0, batch=B, presorted=True)
+        assert c._tables()._ws.data_ptr() == a._tables()._ws.data_ptr()
+        torch.cuda.synchronize()
+        assert np.array_equal(_wbits(c), keep)
+        if sequence:
+            c.sequence_sort_indices(idx, off, batch=B)
+            c.sequence_scatter_add_(g, idx, off, 1.0, batch=B, presorted=True)
+        else:
+            c.sort_indices(idx, off, batch=B)
+            c.scatter_add_(pooled, idx, off, 1.0, batch=B, presorted=True)
+        assert not np.array_equal(_wbits(c), keep)
+
+
 # ---- 5. autograd ------------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("kind,optimizer", [("f32", "sgd"), ("f32", "rowwise_adagrad"), ("bf16", "adagrad")])
