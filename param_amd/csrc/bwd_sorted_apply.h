@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "fwd_elem.h"      // the destination types widen and round through the forward's element types
 
 namespace pm {
 

@@ -86,19 +86,13 @@ struct SDstF32 {
     // load = load_raw + widen: the main kernel's batch keeps the rows RAW until they are consumed -- arithmetic on a loaded value
     // right behind its load makes the compiler wait for the load where it stands, in the middle of the batch's load phase
     __device__ static __forceinline__ u32x4 load_raw(const char* p, int nt = 0) { return raw16_load(p, nt); }
-    __device__ static __forceinline__ void widen(const u32x4 v, float (&a)[4]) {
-        a[0] = __uint_as_float(v.x); a[1] = __uint_as_float(v.y); a[2] = __uint_as_float(v.z); a[3] = __uint_as_float(v.w);
-    }
+    __device__ static __forceinline__ void widen(const u32x4 v, float (&a)[4]) { fwd::Elem<float>::widen(v, a); }
     __device__ static __forceinline__ void load(const char* p, float (&a)[4], int nt = 0) { widen(raw16_load(p, nt), a); }
     __device__ static __forceinline__ void store(char* p, const float (&a)[4], int nt = 0) {
         raw16_store(p, u32x4{__float_as_uint(a[0]), __float_as_uint(a[1]), __float_as_uint(a[2]), __float_as_uint(a[3])}, nt);
     }
 };
-__device__ __forceinline__ uint32_t f32_to_bf16_rne(float f) {
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
+using fwd::f32_to_bf16_rne;      // (fwd_elem.h: one definition for the library)
 // fp32 -> bf16, stochastic: add 16 uniform random bits below the kept mantissa, truncate.  P(round up) equals the
 // discarded fraction, so the expectation is the fp32 value; Inf/NaN pass through the nearest-even path.
 __device__ __forceinline__ uint32_t f32_to_bf16_sr(float f, uint32_t r16) {
@@ -118,11 +112,7 @@ struct SDstBF16 {
         raw16_store(p, u32x4{w[0], w[1], w[2], w[3]}, nt);
     }
     __device__ static __forceinline__ u32x4 load_raw(const char* p, int nt = 0) { return raw16_load(p, nt); }
-    __device__ static __forceinline__ void widen(const u32x4 v, float (&a)[8]) {
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { a[2 * i] = __uint_as_float(w[i] << 16); a[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-    }
+    __device__ static __forceinline__ void widen(const u32x4 v, float (&a)[8]) { fwd::Elem<fwd::bf16_t>::widen(v, a); }
     __device__ static __forceinline__ void load(const char* p, float (&a)[8], int nt = 0) { widen(raw16_load(p, nt), a); }
     __device__ static __forceinline__ void store(char* p, const float (&a)[8], int nt = 0) {
         uint32_t w[4];
@@ -161,14 +151,7 @@ struct SDstF16 {
         raw16_store(p, u32x4{w[0], w[1], w[2], w[3]}, nt);
     }
     __device__ static __forceinline__ u32x4 load_raw(const char* p, int nt = 0) { return raw16_load(p, nt); }
-    __device__ static __forceinline__ void widen(const u32x4 v, float (&a)[8]) {
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            a[2 * i] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(w[i] & 0xffffu)));
-            a[2 * i + 1] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(w[i] >> 16)));
-        }
-    }
+    __device__ static __forceinline__ void widen(const u32x4 v, float (&a)[8]) { fwd::Elem<fwd::f16_t>::widen(v, a); }
     __device__ static __forceinline__ void load(const char* p, float (&a)[8], int nt = 0) { widen(raw16_load(p, nt), a); }
     __device__ static __forceinline__ void store(char* p, const float (&a)[8], int nt = 0) {
         uint32_t w[4];
@@ -203,27 +186,21 @@ hipError_t launch_apply_t(SortedParams sp, hipStream_t stream) {
     static const int join_env = [] { const char* e = getenv("PARAM_AMD_JOIN_TILES"); return e ? atoi(e) : 1; }();        // once per process
     const bool adagrad = sp.mom || sp.state;       // row-wise / element-wise: one column pass either way
     sp.join_tiles = (join_env != 0 && sp.exact_run < TILE && !(adagrad && sp.psw) && (adagrad || sp.max_dim % (G * DST::kVec) == 0)) ? 1 : 0;
-#define PM_LAUNCH_SORTED(W_, OPT_)                                                                                   \
-    do {                                                                                                             \
-        hipLaunchKernelGGL((bwd_sorted_main_kernel<DST, K, G, W_, OPT_, TILE>), g1, blk,                             \
-                           static_cast<size_t>(sp.T) * ((OPT_) != 0 ? 28 : 20), stream, sp);                        \
-        hipLaunchKernelGGL((bwd_sorted_fixup_kernel<DST, K, G, W_, OPT_, TILE>), g2, blk, 0, stream, sp, n_chunks); \
-    } while (0)
     // one (main, fix-up) pair per bag phase, in stream order: phase 0 has updated a row before phase 1 touches it
     for (int ph = 0; ph < sp.H; ++ph) {
         sp.phase = ph;
-        if (adagrad) {  // one column pass with all G lanes (row-wise: cross-lane reduction; element-wise keeps the rule)
-            if (sp.max_dim > G * DST::kVec || sp.H != 1 || (sp.mom && sp.state)) return hipErrorInvalidValue;
-            if (sp.state) {
-                if (sp.psw) PM_LAUNCH_SORTED(true, 2); else PM_LAUNCH_SORTED(false, 2);
-            } else {
-                if (sp.psw) PM_LAUNCH_SORTED(true, 1); else PM_LAUNCH_SORTED(false, 1);
-            }
-        } else {
-            if (sp.psw) PM_LAUNCH_SORTED(true, 0); else PM_LAUNCH_SORTED(false, 0);
-        }
+        // Adagrad: one column pass with all G lanes (row-wise: cross-lane reduction; element-wise keeps the rule)
+        if (adagrad && (sp.max_dim > G * DST::kVec || sp.H != 1 || (sp.mom && sp.state))) return hipErrorInvalidValue;
+        dispatch_opt(sp.state != nullptr, sp.mom != nullptr, [&](auto opt) {
+            dispatch_bool(sp.psw != nullptr, [&](auto w) {
+                constexpr int OPT = decltype(opt)::value;
+                constexpr bool W = decltype(w)::value;
+                hipLaunchKernelGGL((bwd_sorted_main_kernel<DST, K, G, W, OPT, TILE>), g1, blk, static_cast<size_t>(sp.T) * (OPT != 0 ? 28 : 20),
+                                   stream, sp);
+                hipLaunchKernelGGL((bwd_sorted_fixup_kernel<DST, K, G, W, OPT, TILE>), g2, blk, 0, stream, sp, n_chunks);
+            });
+        });
     }
-#undef PM_LAUNCH_SORTED
     return hipGetLastError();
 }
 
@@ -252,22 +229,12 @@ hipError_t launch_unique_g(const SortedParams& sp, const KParams& kp, const Uniq
     const size_t lds = tile_lds_bytes(kp.bags_per_block, kp.idx_cap, false);
     const int g = group_lanes(max_dim, DST::kVec);
     if ((sp.mom || sp.state) && max_dim > g * DST::kVec) return hipErrorInvalidValue;
-#define PM_LAUNCH_UNIQUE(G_)                                                                                                         \
-    do {                                                                                                                             \
-        if (sp.state) hipLaunchKernelGGL((bwd_unique_kernel<DST, G_, 2>), grid, blk, lds, stream, sp, kp, ua.hyb_tab, ua.bloom, ua.emit_keys, \
-                                         ua.emit_vals, ua.key_bytes, ua.tile_cnt, ua.tile_cnt_stride, ua.bloom_wbits);                \
-        else if (sp.mom) hipLaunchKernelGGL((bwd_unique_kernel<DST, G_, 1>), grid, blk, lds, stream, sp, kp, ua.hyb_tab, ua.bloom, ua.emit_keys,  \
-                                       ua.emit_vals, ua.key_bytes, ua.tile_cnt, ua.tile_cnt_stride, ua.bloom_wbits);                  \
-        else hipLaunchKernelGGL((bwd_unique_kernel<DST, G_, 0>), grid, blk, lds, stream, sp, kp, ua.hyb_tab, ua.bloom, ua.emit_keys,         \
-                                ua.emit_vals, ua.key_bytes, ua.tile_cnt, ua.tile_cnt_stride, ua.bloom_wbits);                         \
-    } while (0)
-    switch (g) {
-        case 8: PM_LAUNCH_UNIQUE(8); break;
-        case 16: PM_LAUNCH_UNIQUE(16); break;
-        case 32: PM_LAUNCH_UNIQUE(32); break;
-        default: PM_LAUNCH_UNIQUE(64); break;
-    }
-#undef PM_LAUNCH_UNIQUE
+    dispatch_group_lanes(g, [&](auto gl) {
+        dispatch_opt(sp.state != nullptr, sp.mom != nullptr, [&](auto opt) {
+            hipLaunchKernelGGL((bwd_unique_kernel<DST, decltype(gl)::value, decltype(opt)::value>), grid, blk, lds, stream, sp, kp, ua.hyb_tab,
+                               ua.bloom, ua.emit_keys, ua.emit_vals, ua.key_bytes, ua.tile_cnt, ua.tile_cnt_stride, ua.bloom_wbits);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -280,27 +247,15 @@ hipError_t launch_rest_g(const SortedParams& sp, const KParams& kp, const RestAr
     const size_t lds = static_cast<size_t>(2 * kRestCap + kRestAux) * sizeof(uint32_t);
     const int g = group_lanes(max_dim, DST::kVec);
     if ((sp.mom || sp.state) && max_dim > g * DST::kVec) return hipErrorInvalidValue;
-    // (the attribute is asked for once per instantiation and process)
-#define PM_LAUNCH_REST_O(G_, OPT_)                                                                                                  \
-    do {                                                                                                                            \
-        static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(hyb_rest_kernel<DST, G_, OPT_>),          \
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));     \
-        if (attr_ != hipSuccess) return attr_;                                                                                      \
-        hipLaunchKernelGGL((hyb_rest_kernel<DST, G_, OPT_>), grid, blk, lds, stream, sp, kp, ra);                                   \
-    } while (0)
-#define PM_LAUNCH_REST(G_)                                                    \
-    do {                                                                      \
-        if (sp.state) PM_LAUNCH_REST_O(G_, 2);                                \
-        else if (sp.mom) PM_LAUNCH_REST_O(G_, 1);                             \
-        else PM_LAUNCH_REST_O(G_, 0);                                         \
-    } while (0)
-    switch (g) {
-        case 8: PM_LAUNCH_REST(8); break;
-        case 16: PM_LAUNCH_REST(16); break;
-        case 32: PM_LAUNCH_REST(32); break;
-        default: PM_LAUNCH_REST(64); break;
-    }
-#undef PM_LAUNCH_REST
-#undef PM_LAUNCH_REST_O
-    return hipGetLastError();
+    return dispatch_group_lanes(g, [&](auto gl) {
+        return dispatch_opt(sp.state != nullptr, sp.mom != nullptr, [&](auto opt) {
+            constexpr auto kernel = hyb_rest_kernel<DST, decltype(gl)::value, decltype(opt)::value>;
+            // (the attribute is asked for once per instantiation and process: this lambda's body is one function per (G, OPT))
+            static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                               static_cast<int>(lds));
+            if (attr != hipSuccess) return attr;
+            hipLaunchKernelGGL(kernel, grid, blk, lds, stream, sp, kp, ra);
+            return hipGetLastError();
+        });
+    });
 }

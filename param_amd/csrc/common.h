@@ -184,6 +184,14 @@ template <typename F>
 inline auto dispatch_bool(bool flag, F&& f) {
     return flag ? f(std::true_type{}) : f(std::false_type{});
 }
+// f(std::integral_constant<int, OPT>{}) for the backward apply's optimizer: 2 element-wise Adagrad (a state array per weight),
+// 1 row-wise Adagrad (a state value per row), 0 plain update
+template <typename F>
+inline auto dispatch_opt(bool state, bool mom, F&& f) {
+    if (state) return f(std::integral_constant<int, 2>{});
+    if (mom) return f(std::integral_constant<int, 1>{});
+    return f(std::integral_constant<int, 0>{});
+}
 
 // ---- host-side launchers implemented in the kernel files ----------------------------------
 hipError_t launch_embbag_fwd(const KParams& p, int weight_dtype, int max_dim, int unroll,

@@ -144,6 +144,59 @@ __device__ __forceinline__ void state_widen(const u32x4 (&raw)[VEC / 4], float (
     }
 }
 
+// ---- building blocks of the four apply kernels (main, fix-up, bag-major, rest) --------------------------------
+// Where a kernel keeps its own text instead of calling one of these, the spot says which kernel's code the call moved
+// (profiles/bwd_refactor_isa.md).
+// The row's gradient is complete: the ONE place where OPT selects what happens to it.  `state`: the row's state value (OPT 1) or
+// the state of this lane's columns (OPT 2); OPT 1 is called by all lanes of the group, `cols` or not.
+template <typename DST, int G, int OPT>
+__device__ __forceinline__ void finish_row(char* wptr, float (&wrow)[DST::kVec], float (&acc)[DST::kVec], const float (&srow)[OPT == 2 ? DST::kVec : 1],
+                                           bool cols, float* state, float m_prev, int D, const SortedParams& p, int lig, int nt_rows,
+                                           uint64_t rowkey, int c) {
+    if constexpr (OPT == 2) {
+        if (cols) adagrad_elem_finish<DST>(wptr, wrow, acc, srow, state, p, nt_rows, rowkey, c);
+    } else
+    if (OPT == 1) adagrad_finish<DST, G>(wptr, wrow, acc, cols, state, m_prev, D, p, lig, nt_rows, rowkey, c);
+    else if (cols) DST::store(wptr, acc, nt_rows);
+}
+// a lane's VEC columns of one gradient row, 16 bytes per load; P carries the site's address space (const f32x4*: flat,
+// as_global<f32x4>: global)
+template <int VEC, typename P>
+__device__ __forceinline__ void load_grad(P g, float (&gv)[VEC]) {
+#pragma unroll
+    for (int k = 0; k < VEC; k += 4) {
+        const f32x4 x = g[k / 4];
+        gv[k] = x.x; gv[k + 1] = x.y; gv[k + 2] = x.z; gv[k + 3] = x.w;
+    }
+}
+// one lookup joins the row's sum: two roundings (the build has -ffp-contract=off), the sequential oracle's
+template <int VEC>
+__device__ __forceinline__ void add_scaled(float (&acc)[VEC], float sc, const float (&gv)[VEC]) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        const float prod = sc * gv[k];
+        acc[k] = acc[k] + prod;
+    }
+}
+// a run opens on the row just loaded: Adagrad holds the row and accumulates the gradient from zero, the plain update accumulates
+// on top of the row, in lookup order
+template <typename DST, int OPT>
+__device__ __forceinline__ void open_row(const u32x4 raw, const u32x4 (&sraw)[OPT == 2 ? DST::kVec / 4 : 1], float (&acc)[DST::kVec],
+                                         float (&wrow)[DST::kVec], float (&srow)[OPT == 2 ? DST::kVec : 1]) {
+    float wv[DST::kVec];
+    DST::widen(raw, wv);
+#pragma unroll
+    for (int k = 0; k < DST::kVec; ++k) {
+        if (OPT != 0) wrow[k] = wv[k];
+        else acc[k] = wv[k];
+    }
+    if constexpr (OPT == 2) state_widen<DST::kVec>(sraw, srow);
+}
+// A column pass: lane `lig` of a group serves columns c = lig * VEC, + G * VEC, ... < column_pass_end.  Adagrad makes exactly ONE
+// pass in which every lane of the group takes part (OPT 1: cross-lane reduction inside adagrad_finish; OPT 2 keeps the rule).
+template <int OPT, int VEC>
+__device__ __forceinline__ int column_pass_end(int lig, int width) { return OPT != 0 ? lig * VEC + 1 : width; }
+
 // ---- group-wide scans (all G lanes of a lane group call these together) ---------------------------------------
 // index of the first lane of this group whose predicate holds, G if none.  Groups of one wave may diverge: the ballot
 // only sees active lanes, and only this group's bits are looked at.
@@ -360,8 +413,7 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
     const int l1e = l1 + own_after;      // end of this group's walk (<= n_tile)
     PM_STAMP(blockIdx.x, 2);
 
-    // OPT 1: exactly one pass in which EVERY lane of the group takes part (cross-lane reduction inside); OPT 2 keeps the rule
-    const int c_end = OPT != 0 ? lig * VEC + 1 : p.max_dim;
+    const int c_end = column_pass_end<OPT, VEC>(lig, p.max_dim);
     for (int c = lig * VEC; c < c_end; c += G * VEC) {
         // mode: 0 closed, 1 leading piece (partial from zero), 2 in-chunk run, 3 trailing piece (partial from zero)
         int mode = 0;
@@ -376,6 +428,8 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
         K cur_key = 0;                  // key of the open run: row pointer, state pointer and row length are re-derived
                                         // from it when the run closes (keeping them live across the batch cost the
                                         // kernel a fifth wave per SIMD)
+        // (the zeroing is spelled out in each kernel: as a helper it moved this kernel's element-wise Adagrad instances and was in
+        // no combination of lifts that left the benchmark's kernels alone)
 #pragma unroll
         for (int k = 0; k < VEC; ++k) { acc[k] = 0.0f; wrow[k] = 0.0f; }
 #pragma unroll
@@ -386,6 +440,7 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
             const int64_t row = static_cast<int64_t>(key & row_mask);
             const int D = s_dim[t];
             char* wptr = s_dst[t] + (row * D + c) * DST::kES;
+            // (finish_row's text, kept: the call moved the benchmark's bf16 plain-update instances of this kernel)
             if constexpr (OPT == 2) {
                 if (cols) adagrad_elem_finish<DST>(wptr, w, a, srow, s_mom[t] + row * D + c, p, nt_rows, static_cast<uint64_t>(key), c);
             } else
@@ -415,6 +470,8 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
                     bool deep = kDeepMul > 1 && pos + kDeep <= l1e;
 #pragma unroll
                     for (int u = kBatch; u < kDeep; ++u) deep = deep && s_key[pos + (u < kDeep ? u : 0) + 1] == cur_key;
+                    // (written twice, for kDeep and for kBatch rows, with load_grad's and add_scaled's text: as one function of the row
+                    // count the unweighted instances of this kernel, the benchmark's fp32 plain update among them, moved)
                     if (deep) {
                         float gf[kDeep][VEC];
 #pragma unroll
@@ -503,11 +560,7 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
                 }
                 const float* g = col_ok[u] ? p.grad + s_ooff[t] + grad_bag_offset(static_cast<int64_t>(bag), p.out_stride, p.gblk_shift, p.gblk_extra) + c
                                            : reinterpret_cast<const float*>(dummy);
-#pragma unroll
-                for (int k = 0; k < VEC; k += 4) {
-                    const f32x4 x = *reinterpret_cast<const f32x4*>(g + k);
-                    gv[u][k] = x.x; gv[u][k + 1] = x.y; gv[u][k + 2] = x.z; gv[u][k + 3] = x.w;
-                }
+                load_grad<VEC>(reinterpret_cast<const f32x4*>(g), gv[u]);
                 // in-chunk runs need the destination row; the trailing open run does not
                 wraw[u] = DST::load_raw(need_row ? s_dst[t] + (row * D + c) * DST::kES : dummy, nt_rows);
                 // element-wise Adagrad: the state of the lane's columns is issued right behind the row, from the same test
@@ -547,30 +600,17 @@ __global__ void __launch_bounds__(kBlock) bwd_sorted_main_kernel(const SortedPar
                     }
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) acc[k] = 0.0f;
-                    if (mode == 2 && any_col) {
-                        float wv[VEC];
-                        DST::widen(wraw[u], wv);
-#pragma unroll
-                        for (int k = 0; k < VEC; ++k) {
-                            if (OPT != 0) wrow[k] = wv[k];   // Adagrad: gradient accumulates from zero
-                            else acc[k] = wv[k];             // SGD: accumulate on top of the row, lookup order
-                        }
-                        if constexpr (OPT == 2) state_widen<VEC>(sraw[u], srow);
-                    }
+                    if (mode == 2 && any_col) open_row<DST, OPT>(wraw[u], sraw[u], acc, wrow, srow);
                 }
-                if (mode != 0 && any_col) {
-#pragma unroll
-                    for (int k = 0; k < VEC; ++k) {
-                        const float prod = sc[u] * gv[u][k];
-                        acc[k] = acc[k] + prod;
-                    }
-                }
+                if (mode != 0 && any_col) add_scaled<VEC>(acc, sc[u], gv[u]);
             }
             // Every register a load of this batch was issued into counts as read here, whichever way the consumption above went
             // (positions past the chunk's end, columns past the table's width and runs without a row load leave theirs unread).
             // Without it such a load is still "pending" for the compiler when the next trip overwrites its register, and -- the
             // pending state of a loop merged over all those paths having no order left -- it guards EVERY position's address
             // arithmetic with `s_waitcnt vmcnt(0)`: one position's loads in flight at a time instead of kBatch.
+            // (Spelled out in the three kernels that need it: as a count_as_read(...) helper, together with the other pieces, it
+            // moved this kernel's unweighted instances and the left-over kernel's bf16 plain-update instances.)
 #pragma unroll
             for (int u = 0; u < kBatch; ++u) {
 #pragma unroll
@@ -734,7 +774,7 @@ __device__ __forceinline__ void fixup_one_run(const SortedParams& p, int64_t h, 
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 
-    const int c_end = OPT != 0 ? lig * VEC + 1 : D;
+    const int c_end = column_pass_end<OPT, VEC>(lig, D);
     for (int c = lig * VEC; c < c_end; c += G * VEC) {
         const bool any_col = c < D;
         char* wptr = reinterpret_cast<char*>(p.dst[t]) + (row * D + c) * DST::kES;
@@ -768,22 +808,12 @@ __device__ __forceinline__ void fixup_one_run(const SortedParams& p, int64_t h, 
                         const int qq = q + u < static_cast<int>(len) ? q + u : static_cast<int>(len) - 1;
                         sc[u] = WEIGHTED ? my_sc[qq] : p.alpha;
                         const float* g = gbase + grad_bag_offset(static_cast<int64_t>(my_bag[qq]), p.out_stride, p.gblk_shift, p.gblk_extra);
-#pragma unroll
-                        for (int k = 0; k < VEC; k += 4) {
-                            const f32x4 x = *reinterpret_cast<const f32x4*>(g + k);
-                            gv[u][k] = x.x; gv[u][k + 1] = x.y; gv[u][k + 2] = x.z; gv[u][k + 3] = x.w;
-                        }
+                        load_grad<VEC>(reinterpret_cast<const f32x4*>(g), gv[u]);
                     }
                 }
 #pragma unroll
                 for (int u = 0; u < kFixBatch; ++u) {
-                    if (any_col && q + u < static_cast<int>(len)) {
-#pragma unroll
-                        for (int k = 0; k < VEC; ++k) {
-                            const float prod = sc[u] * gv[u][k];
-                            acc[k] = acc[k] + prod;
-                        }
-                    }
+                    if (any_col && q + u < static_cast<int>(len)) add_scaled<VEC>(acc, sc[u], gv[u]);
                 }
             }
         } else if (any_col) {
@@ -819,11 +849,9 @@ __device__ __forceinline__ void fixup_one_run(const SortedParams& p, int64_t h, 
                 }
             }
         }
-        if constexpr (OPT == 2) {
-            if (any_col) adagrad_elem_finish<DST>(wptr, wrow, acc, srow, st_ptr, p, nt_rows, static_cast<uint64_t>(key), c);
-        } else
-        if (OPT == 1) adagrad_finish<DST, G>(wptr, wrow, acc, any_col, p.mom[t] + row, mom_prev, D, p, lig, nt_rows, static_cast<uint64_t>(key), c);
-        else DST::store(wptr, acc, nt_rows);
+        // (the plain update's passes end at D: any_col holds in every one of them)
+        finish_row<DST, G, OPT>(wptr, wrow, acc, srow, any_col, OPT == 1 ? p.mom[t] + row : st_ptr, mom_prev, D, p, lig, nt_rows,
+                                static_cast<uint64_t>(key), c);
     }
 }
 
@@ -990,19 +1018,13 @@ __global__ void __launch_bounds__(kBlock) bwd_unique_kernel(const SortedParams p
         const float* grow = grad_t + grad_bag_offset(bag0 + slot, q.out_stride, q.gblk_shift, q.gblk_extra);
         auto walk = [&](auto staged_c) {
             constexpr bool ST = decltype(staged_c)::value;
-            // OPT 1: one pass in which every lane of the group takes part (cross-lane reduction inside adagrad_finish)
-            const int c_end = OPT != 0 ? lig * VEC + 1 : D;
+            const int c_end = column_pass_end<OPT, VEC>(lig, D);
             for (int c = lig * VEC; c < c_end; c += G * VEC) {
                 const bool any_col = c < D;
-                float ga[VEC];
-                {
-                    const float* gp = any_col ? grow + c : reinterpret_cast<const float*>(dummy);
+                float ga[VEC];      // the bag's gradient, scaled once: alpha * g is every lookup's contribution
+                load_grad<VEC>(as_global<f32x4>(any_col ? grow + c : reinterpret_cast<const float*>(dummy)), ga);
 #pragma unroll
-                    for (int k = 0; k < VEC; k += 4) {
-                        const f32x4 x = *as_global<f32x4>(gp + k);
-                        ga[k] = p.alpha * x.x; ga[k + 1] = p.alpha * x.y; ga[k + 2] = p.alpha * x.z; ga[k + 3] = p.alpha * x.w;
-                    }
-                }
+                for (int k = 0; k < VEC; ++k) ga[k] = p.alpha * ga[k];
                 for (int64_t j = s; j < e; j += UB) {
                     uint32_t rr[UB];
                     u32x4 raw[UB];
@@ -1035,30 +1057,17 @@ __global__ void __launch_bounds__(kBlock) bwd_unique_kernel(const SortedParams p
                     for (int u = 0; u < UB; ++u) {
                         const bool live = j + u < e && !(rr[u] >> 31);     // uniform over the lane group
                         if (live) {
-                            float w[VEC];
-                            DST::widen(raw[u], w);
-                            if constexpr (OPT == 2) {
-                                if (any_col) {
-                                    float acc[VEC], st[VEC];
+                            // a run of one: the row and its state open it, the bag's gradient is its sum -- "from zero" under Adagrad,
+                            // as the sorted apply accumulates it (0.0f + ga: a -0.0 becomes the +0.0 it is there)
+                            float acc[VEC], w[VEC], sv[OPT == 2 ? VEC : 1];
 #pragma unroll
-                                    for (int k = 0; k < VEC; ++k) acc[k] = 0.0f + ga[k];                 // the sorted apply's "from zero"
-                                    state_widen<VEC>(sraw[u], st);
-                                    const uint32_t row = rr[u] & 0x7fffffffu;
-                                    adagrad_elem_finish<DST>(ptr[u], w, acc, st, mom_t + static_cast<uint64_t>(row) * static_cast<uint32_t>(D) + c, p, nt_rows,
-                                                             tkey | row, c);
-                                }
-                            } else
-                            if (OPT == 1) {
-                                float acc[VEC];
+                            for (int k = 0; k < VEC; ++k) acc[k] = 0.0f;
+                            open_row<DST, OPT>(raw[u], sraw[u], acc, w, sv);
 #pragma unroll
-                                for (int k = 0; k < VEC; ++k) acc[k] = any_col ? 0.0f + ga[k] : 0.0f;   // the sorted apply's "from zero"
-                                const uint32_t row = rr[u] & 0x7fffffffu;
-                                adagrad_finish<DST, G>(ptr[u], w, acc, any_col, mom_t + row, mv[u], D, p, lig, nt_rows, tkey | row, c);
-                            } else if (any_col) {
-#pragma unroll
-                                for (int k = 0; k < VEC; ++k) w[k] = w[k] + ga[k];
-                                DST::store(ptr[u], w, nt_rows);
-                            }
+                            for (int k = 0; k < VEC; ++k) acc[k] = (OPT == 0 || any_col) ? acc[k] + ga[k] : 0.0f;
+                            const uint32_t row = rr[u] & 0x7fffffffu;
+                            float* const state = OPT == 0 ? nullptr : mom_t + (OPT == 2 ? static_cast<uint64_t>(row) * static_cast<uint32_t>(D) + c : row);
+                            finish_row<DST, G, OPT>(ptr[u], w, acc, sv, any_col, state, mv[u], D, p, lig, nt_rows, tkey | row, c);
                         }
                     }
 #pragma unroll
@@ -1252,27 +1261,22 @@ __global__ void __launch_bounds__(kRestThreads) hyb_rest_kernel(const SortedPara
     const uint64_t tkey = static_cast<uint64_t>(t) << p.tshift;
     const char* const dummy = reinterpret_cast<const char*>(p.partials) + static_cast<size_t>(lig) * VEC * sizeof(float);
     PM_STAMP_DRAINED(trace_id, 4);
-    // OPT 1: one pass in which every lane of the group takes part (cross-lane reduction inside adagrad_finish)
-    const int c_end = OPT != 0 ? lig * VEC + 1 : D;
+    const int c_end = column_pass_end<OPT, VEC>(lig, D);
     for (int c = lig * VEC; c < c_end; c += G * VEC) {
         const bool any_col = c < D;
         float acc[VEC], wrow[VEC];
-        constexpr int SV = OPT == 2 ? VEC : 1;
-        float srow[SV];                     // OPT 2: the open run's state values of this lane's columns
+        float srow[OPT == 2 ? VEC : 1];     // OPT 2: the open run's state values of this lane's columns
 #pragma unroll
         for (int k = 0; k < VEC; ++k) { acc[k] = 0.0f; wrow[k] = 0.0f; }
 #pragma unroll
-        for (int k = 0; k < SV; ++k) srow[k] = 0.0f;
+        for (int k = 0; k < (OPT == 2 ? VEC : 1); ++k) srow[k] = 0.0f;
         float cur_mom = 0.0f;
         uint32_t cur_row = 0;
         bool open = false;
         auto close_run = [&]() {
             char* wptr = W + (static_cast<int64_t>(cur_row) * D + c) * DST::kES;
-            if constexpr (OPT == 2) {
-                if (any_col) adagrad_elem_finish<DST>(wptr, wrow, acc, srow, mom_t + static_cast<int64_t>(cur_row) * D + c, p, nt_rows, tkey | cur_row, c);
-            } else
-            if (OPT == 1) adagrad_finish<DST, G>(wptr, wrow, acc, any_col, mom_t + cur_row, cur_mom, D, p, lig, nt_rows, tkey | cur_row, c);
-            else if (any_col) DST::store(wptr, acc, nt_rows);
+            float* const state = OPT == 0 ? nullptr : mom_t + (OPT == 2 ? static_cast<int64_t>(cur_row) * D + c : static_cast<int64_t>(cur_row));
+            finish_row<DST, G, OPT>(wptr, wrow, acc, srow, any_col, state, cur_mom, D, p, lig, nt_rows, tkey | cur_row, c);
         };
         for (uint32_t q0 = pos; q0 < end; q0 += KB) {
             uint32_t rw[KB], bg[KB];
@@ -1293,11 +1297,9 @@ __global__ void __launch_bounds__(kRestThreads) hyb_rest_kernel(const SortedPara
             for (int u = 0; u < KB; ++u) {      // every load of the batch before the first add; positions that need none read a harmless address
                 const float* g = (valid[u] && any_col) ? grad_t + grad_bag_offset(static_cast<int64_t>(bg[u]), q.out_stride, q.gblk_shift, q.gblk_extra) + c
                                                        : reinterpret_cast<const float*>(dummy);
-#pragma unroll
-                for (int k = 0; k < VEC; k += 4) {
-                    const f32x4 x = *as_global<f32x4>(g + k);
-                    gv[u][k] = x.x; gv[u][k + 1] = x.y; gv[u][k + 2] = x.z; gv[u][k + 3] = x.w;
-                }
+                load_grad<VEC>(as_global<f32x4>(g), gv[u]);
+                // (row, state value and element-wise state: the same three lines as in the bag-major kernel; one helper for both moved
+                // every instance of this kernel)
                 wraw[u] = DST::load_raw((head[u] && any_col) ? W + (static_cast<int64_t>(rw[u]) * D + c) * DST::kES : dummy, nt_rows);
                 mv[u] = 0.0f;
                 if (OPT == 1) mv[u] = *as_global<float>(head[u] ? mom_t + rw[u] : reinterpret_cast<const float*>(dummy));
@@ -1314,24 +1316,9 @@ __global__ void __launch_bounds__(kRestThreads) hyb_rest_kernel(const SortedPara
                         cur_mom = mv[u];
 #pragma unroll
                         for (int k = 0; k < VEC; ++k) { acc[k] = 0.0f; wrow[k] = 0.0f; }
-                        if (any_col) {
-                            float wv[VEC];
-                            DST::widen(wraw[u], wv);
-#pragma unroll
-                            for (int k = 0; k < VEC; ++k) {
-                                if (OPT != 0) wrow[k] = wv[k];   // Adagrad: the gradient accumulates from zero
-                                else acc[k] = wv[k];             // SGD: on top of the row, lookup order
-                            }
-                            if constexpr (OPT == 2) state_widen<VEC>(sraw[u], srow);
-                        }
+                        if (any_col) open_row<DST, OPT>(wraw[u], sraw[u], acc, wrow, srow);
                     }
-                    if (any_col) {
-#pragma unroll
-                        for (int k = 0; k < VEC; ++k) {
-                            const float prod = p.alpha * gv[u][k];
-                            acc[k] = acc[k] + prod;
-                        }
-                    }
+                    if (any_col) add_scaled<VEC>(acc, p.alpha, gv[u]);
                 }
             }
 #pragma unroll

@@ -48,12 +48,14 @@ template <> struct Elem<f16_t> {
 // fp32 -> 16 bits, round to nearest even; overflow to +-Inf, subnormals produced, signed zeros kept, NaN -> a quiet NaN of its sign.
 // Four outputs leave as one 8-byte piece (u32x2): what the alignment rules of a request guarantee.
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+// (the one fp32 -> bf16 round-to-nearest-even of the library: the sorted apply's destination rows round through it as well)
+__device__ __forceinline__ uint32_t f32_to_bf16_rne(float f) {
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
 struct OutBF16 {
-    __device__ static __forceinline__ uint32_t round(float f) {
-        const uint32_t u = __float_as_uint(f);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;      // (the convention of the sorted apply's f32_to_bf16_rne)
-        return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-    }
+    __device__ static __forceinline__ uint32_t round(float f) { return f32_to_bf16_rne(f); }
 };
 struct OutF16 {
     __device__ static __forceinline__ uint32_t round(float f) {

@@ -200,6 +200,68 @@ def test_hybrid_rowwise_adagrad_same_bits_as_sorted_path(coracle, dtype):
         np.testing.assert_allclose(got, W, rtol=2e-5, atol=1e-6)
 
 
+# The launch ladders of the bag-major kernel (bwd_unique_kernel) and of the LDS left-over kernel (hyb_rest_kernel) pick one instance
+# per (destination dtype, lane-group width G, optimizer OPT: 0 plain update, 1 row-wise Adagrad, 2 element-wise Adagrad).  Reached by
+# other tests (G = D / 4 for fp32 tables, D / 8 for 16-bit ones, at least 8):
+#   OPT 0  fp32 G 8 / 16 / 32 / 64: test_gpu_rest.py (D 32 / 64 / 128 / 256); bf16 G 16: test_hybrid_bf16_tables_and_batch_slices
+#   OPT 1  fp32 G 32, bf16 G 16: test_hybrid_rowwise_adagrad_same_bits_as_sorted_path, test_gpu_rest.py
+#   OPT 2  fp32 G 32, bf16 G 8 (both kernels), fp32 G 8 (bag-major only): test_gpu_elem_adagrad.py
+# (the random requests below and in test_gpu_fuzz.py add whatever their seeds draw).  The cases here are every other pair.
+_LADDER = ([(torch.bfloat16, g, 0) for g in (8, 32, 64)] +
+           [(torch.float32, g, 1) for g in (8, 16, 64)] + [(torch.bfloat16, g, 1) for g in (8, 32, 64)] +
+           [(torch.float32, g, 2) for g in (8, 16, 64)] + [(torch.bfloat16, g, 2) for g in (16, 32, 64)])
+
+
+@pytest.mark.parametrize("dtype,G,opt", _LADDER, ids=[f"{'f32' if d == torch.float32 else 'bf16'}-G{g}-opt{o}" for d, g, o in _LADDER])
+def test_every_lane_group_width_and_optimizer_of_the_hybrid_kernels(coracle, dtype, G, opt):
+    """The smallest hybrid-eligible request at the row width that selects lane groups of G: two tables, 8192 lookups each (batch 1024 x
+    pooling 8) into 4 x as many rows, a few rows looked up several times on top of what uniform indices repeat, so that both the
+    bag-major kernel and the LDS left-over kernel have work.  Tables and optimizer state after two steps equal the same steps with
+    the hybrid path off, bit for bit; the plain update also equals the sequential oracle, bit for bit."""
+    import param_amd
+
+    B, L = 1024, 8
+    rows = [4 * B * L] * 2
+    D = G * (4 if dtype == torch.float32 else 8)
+    idx, off = _request(rows, B, L, 0.0, 31)
+    idx = idx.clone()
+    for t in range(2):
+        idx[t * B * L + 3:t * B * L + 40 * L:L] = 17                 # one row in 40 bags ...
+        idx[t * B * L + 5:t * B * L + 5 + 3] = 4242 + t               # ... and one three times in one bag
+    grad = torch.randn((B, len(rows) * D), device=DEV, generator=torch.Generator(device=DEV).manual_seed(5))
+    kw = {} if opt == 0 else dict(optimizer="rowwise_adagrad" if opt == 1 else "adagrad", learning_rate=0.05, eps=1e-8)
+    res = {}
+    for hyb in (2, 0):
+        param_amd.set_hybrid_tuning(hyb)
+        m = param_amd.BatchedEmbeddingBagMI355(rows, D, dtype=dtype, device=DEV, init="normal", seed=3, fused_update=False, **kw)
+        W0 = m.table(0).clone()
+        for _ in range(2):
+            if opt == 0:
+                m.scatter_add_(grad, idx, off, alpha=-0.05, batch=B)
+            else:
+                m.adagrad_step_(grad, idx, off, batch=B)
+        st = m.sort_status(idx, off, batch=B)
+        if hyb:
+            assert st["hybrid_launched"] and st["hybrid_tables"] == 2, st      # (launched: the mode it ran in, 2 = forced)
+            assert st["lds_tables"] == 2 and st["lds_pairs"] > 0 and st["pairs_sorted"] == 0, st
+        else:
+            assert st["hybrid_tables"] == 0 and st["pairs_sorted"] == idx.numel(), st
+        res[hyb] = (m.weights.data.clone(), m.momentum.clone() if opt else None)
+        del m
+    param_amd.set_hybrid_tuning()
+    assert torch.equal(res[2][0].view(torch.uint8), res[0][0].view(torch.uint8))
+    if opt:
+        assert torch.equal(res[2][1], res[0][1]) and bool(res[2][1].any())
+    else:                                                              # (bf16 tables: the only plain-update cases of the list)
+        idx_h, off_h = idx.cpu().numpy(), off.cpu().numpy()
+        g0 = np.ascontiguousarray(grad.cpu().numpy()[:, :D])
+        exp = W0.view(torch.int16).cpu().numpy().view(np.uint16).copy()
+        for _ in range(2):
+            exp = coracle.bwd_bf16(exp, idx_h[:off_h[B]], off_h[:B], g0, alpha=-0.05)
+        got = res[2][0].reshape(-1)[:rows[0] * D].reshape(rows[0], D)
+        assert np.array_equal(got.view(torch.int16).cpu().numpy().view(np.uint16), exp)
+
+
 def test_the_path_taken_depends_on_the_request_alone():
     """Which tables go hybrid is decided on the device from the request itself -- nothing is cached or carried over: uniform and
     Zipf requests alternating on ONE workspace take the same paths (and leave the same bits) as each of them on a fresh one."""

@@ -20,6 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 FORWARD = ("17embbag_fwd_kernel", "22embbag_fwd_flat_kernel", "14pad_fwd_kernel", "23embbag_fwd_split_kernel")
+# the backward's apply kernels: rows of their own in the summary table (reporting only: the pass / fail rule names no family but FORWARD)
+BACKWARD = ("22bwd_sorted_main_kernel", "23bwd_sorted_fixup_kernel", "17bwd_unique_kernel", "15hyb_rest_kernel")
 # the split forward's private element types became fwd::bf16_t / fwd::f16_t: the same kernels under another type name
 RENAMED = {"NS0_7sbf16_tE": "NS_3fwd6bf16_tE", "NS0_6sf16_tE": "NS_3fwd5f16_tE"}
 
@@ -94,7 +96,7 @@ def main():
     rows, fam = [], {}
     for n in sorted(set(old) & set(new)):
         (to, mo), (tn, mn) = old[n], new[n]
-        family = next((f[2:] for f in FORWARD if f in n), "other")
+        family = next((f[2:] for f in FORWARD + BACKWARD if f in n), "other")
         c = fam.setdefault(family, [0, 0])
         if to == tn and mo == mn:
             c[0] += 1
