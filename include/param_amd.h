@@ -563,7 +563,7 @@ int pm_embedding_gather(const pm_embbag_batch* op, int32_t out_dtype, void* out,
  * validates as the launching call does, except for `out` of that call.
  * Replaces torch's two CPU operators named above (behind torch.ao.nn.quantized.EmbeddingBag) and the forward of fbgemm's
  * IntNBitTableBatchedEmbeddingBagsCodegen for INT8 / INT4 tables.  Left out: 2-bit tables, mean, padding_idx, pruned rows / index
- * remapping, a padded row stride (the un-pooled lookup: below).
+ * remapping, a padded row stride (the un-pooled lookup: below; tables of differing format in one launch: PER-TABLE FORMATS below).
  * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these two finds out at symbol resolution.
  */
 int pm_embbag_fwd_qrows(const pm_embbag_batch* op, int32_t bits, int32_t out_dtype, void* out, pm_stream_t stream);
@@ -598,12 +598,55 @@ int pm_embbag_qrows_plan(const pm_embbag_batch* op, int32_t bits, int32_t out_dt
  * launching call does (`out` and out_row_stride of that call, and an out_dtype, are not part of it).
  * Replaces quantized::embedding_byte / embedding_4bit (behind torch.ao.nn.quantized.Embedding) and PoolingMode.NONE of fbgemm's
  * IntNBitTableBatchedEmbeddingBagsCodegen for INT8 / INT4 tables.  Left out: 2-bit tables, a padded row stride, pruned rows / index
- * remapping, padding_idx, per-position weights, a lane width per format, any backward (the tables are not trainable).
+ * remapping, padding_idx, per-position weights, a lane width per format, any backward (the tables are not trainable).  Tables of
+ * differing format in one launch: PER-TABLE FORMATS below.
  * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these two finds out at symbol resolution.
  */
 int pm_embedding_gather_qrows(const pm_embbag_batch* op, int32_t bits, int32_t out_dtype, void* out, int64_t out_row_stride,
                               pm_stream_t stream);
 int pm_embedding_gather_qrows_plan(const pm_embbag_batch* op, int32_t bits, int64_t out[8]);
+
+/*
+ * ROW-QUANTISED TABLES, PER-TABLE FORMATS -- the two lookups above in ONE launch over tables that are EACH stored in the 8-bit or the
+ * 4-bit row format (a serving model keeps its big tables at 4 bits and its small or sensitive ones at 8): table_bits is a DEVICE array
+ * of num_tables ints, table_bits[t] = 8 or 4, read by the kernels like op->dims; its contents are the caller's responsibility, as those
+ * of rows and dims are.  op->tables[t] points at uint8 [rows[t], row_bytes(dims[t], table_bits[t])], the bytes of ROW-QUANTISED TABLES:
+ * row_bytes = D + 8 (8 bits) or D / 2 + 4 (4 bits).  Everything else of the request and of `out` is the single-format call's.
+ * THE RULE: no new arithmetic.  Pooled: the output columns of table t are bit for bit what pm_embbag_fwd_qrows gives for that table alone
+ * with bits = table_bits[t] -- acc = fmaf(sc, (float)code, fl32(acc + bi)) in index order from +0.0, weighted or not, fp32 or ONE
+ * rounding to bf16 / fp16, an empty bag +0.0.  Un-pooled: row j is bit for bit what pm_embedding_gather_qrows gives with the bits of the
+ * table that owns position j -- conv(fmaf(scale, code, fl32(+0.0 + bias))).  (tests/qmixed_rules.py applies tests/qrows_rules.py /
+ * tests/qgather_rules.py table by table.)
+ * One launch each (csrc/embbag_fwd_qmixed.hip, csrc/embedding_gather_qmixed.hip): a lane holds EIGHT COLUMNS of a row whatever its
+ * format -- two dwords of an 8-bit row, one dword of a 4-bit row -- so the lane group (sized for max_dim / 8), the accumulators, the
+ * column passes and the output pieces are one for every table, and the plan needs no knowledge of the formats present: it is a function
+ * of the request struct, out_dtype and the tuning knobs alone (no further host-side argument).  Pooled: a tile's bags belong to one
+ * table, the workgroup branches once per tile into its format's row loop.  Un-pooled: the format is a row's; lane groups of one wave may
+ * differ in it and run one instruction stream.  Every read stays inside a row.  No atomics, no workspace, no allocation, stream-ordered.
+ * Column rule: dims[t] % 8 == 0 for EVERY table (the stricter of the two formats' rules), dims[t] <= 4096.
+ * Refused on the host, before any HIP call: everything the single-format calls refuse about the request, out_dtype, `out` and
+ * out_row_stride; a NULL table_bits (PM_ERR_INVALID); max_dim % 8 or min_dim % 8 non-zero (PM_ERR_UNSUPPORTED).  bag_count == 0 (and,
+ * un-pooled, num_indices == 0) is PM_OK without a launch.
+ * pm_embbag_qrows_mixed_plan / pm_embedding_gather_qrows_mixed_plan: the geometry the two calls WOULD use (plan_qmixed,
+ * plan_gather_qmixed, csrc/launch_plan.h) -- the twelve members of pm_embbag_plan / the eight of pm_embedding_gather_plan in their order
+ * (vec is 8); host only, nothing is launched, and no table_bits: the plans do not depend on the formats.
+ * Measured (tools/qmixed_probe.py, profiles/qmixed_probe.json; tables alternately 8- and 4-bit; us per call, fp32 output, uniform | Zipf
+ * 1.05 indices; (a) this call, (b) two single-format launches plus the copies that interleave their results, (c) the two launches alone):
+ *   16 x 10 M x 128, batch 8192, pooling 20   pooled     (a) 121.3 |  78.3   (b) 160.4 | 109.3   (c) 123.2 |  78.0
+ *                                             un-pooled  (a) 350.1 | 311.2   (b) 811.9 | 786.3   (c) 356.3 | 359.0
+ *   64 x 1 M x 64, batch 256, pooling 10      pooled     (a)  10.6 |  10.7   (b)  34.0 |  34.4   (c)  21.0 |  21.3
+ *                                             un-pooled  (a)  14.2 |  11.8   (b)  39.2 |  36.4   (c)  22.9 |  23.6
+ * (a) is never slower than (b) or, beyond the 0.9 % spread, than (c); fp16 output and the lane layout: README.md, "Per-table formats".
+ * Replaces the per-table weights_tys of fbgemm's IntNBitTableBatchedEmbeddingBagsCodegen for INT8 / INT4.  Left out: fp16 / bf16 / fp32
+ * rows in the same launch (the format is an int per table so that 16 can follow), 2-bit tables, mean, padding_idx, pruned rows / index
+ * remapping, a padded row stride, per-table lane sub-groups, any backward.
+ * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these four finds out at symbol resolution.
+ */
+int pm_embbag_fwd_qrows_mixed(const pm_embbag_batch* op, const int32_t* table_bits, int32_t out_dtype, void* out, pm_stream_t stream);
+int pm_embbag_qrows_mixed_plan(const pm_embbag_batch* op, int32_t out_dtype, int32_t out[12]);
+int pm_embedding_gather_qrows_mixed(const pm_embbag_batch* op, const int32_t* table_bits, int32_t out_dtype, void* out,
+                                    int64_t out_row_stride, pm_stream_t stream);
+int pm_embedding_gather_qrows_mixed_plan(const pm_embbag_batch* op, int64_t out[8]);
 
 /*
  * SEQUENCE GRADIENTS -- the batched backward of the un-pooled lookup above: the gradient of pm_embedding_gather's rows applied to all

@@ -92,6 +92,10 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_qrows_plan",
     "pm_embedding_gather_qrows",
     "pm_embedding_gather_qrows_plan",
+    "pm_embbag_fwd_qrows_mixed",
+    "pm_embbag_qrows_mixed_plan",
+    "pm_embedding_gather_qrows_mixed",
+    "pm_embedding_gather_qrows_mixed_plan",
 )
 
 # pm_embbag_plan (include/param_amd.h): the kinds, and the members of the two plans in the order the queries fill them
@@ -316,6 +320,15 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embedding_gather_qrows.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, i32, vp, i64, vp]
     L.pm_embedding_gather_qrows_plan.restype = ctypes.c_int
     L.pm_embedding_gather_qrows_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, ctypes.POINTER(i64)]
+    # ... of per-table format: table_bits (a device int32 [T], 8 | 4) in place of bits; the plan queries take no formats
+    L.pm_embbag_fwd_qrows_mixed.restype = ctypes.c_int
+    L.pm_embbag_fwd_qrows_mixed.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, vp, vp]
+    L.pm_embbag_qrows_mixed_plan.restype = ctypes.c_int
+    L.pm_embbag_qrows_mixed_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, ctypes.POINTER(i32)]
+    L.pm_embedding_gather_qrows_mixed.restype = ctypes.c_int
+    L.pm_embedding_gather_qrows_mixed.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, vp, i64, vp]
+    L.pm_embedding_gather_qrows_mixed_plan.restype = ctypes.c_int
+    L.pm_embedding_gather_qrows_mixed_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), ctypes.POINTER(i64)]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]
@@ -461,3 +474,17 @@ def set_hybrid_rest(mode: int = -1) -> None:
     """``pm_set_hybrid_rest``: 1 (default) = what the bag-major kernel leaves of a hybrid table (the flagged lookups, at most 8192 of
     them) is sorted in LDS and applied by ONE launch; 0 = the lists go through the key sort and the sorted apply (round 5)."""
     check(load().pm_set_hybrid_rest(mode))
+
+
+def embbag_qrows_mixed_plan(op: pm_embbag_batch, out_dtype: int = PM_F32) -> dict:
+    """``pm_embbag_qrows_mixed_plan``: the geometry ``pm_embbag_fwd_qrows_mixed`` would use for ``op`` -- ``PLAN_FIELDS`` by name"""
+    out = (ctypes.c_int32 * len(PLAN_FIELDS))()
+    check(load().pm_embbag_qrows_mixed_plan(ctypes.byref(op), int(out_dtype), out))
+    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
+
+
+def embedding_gather_qrows_mixed_plan(op: pm_embbag_batch) -> dict:
+    """``pm_embedding_gather_qrows_mixed_plan``: the geometry ``pm_embedding_gather_qrows_mixed`` would use -- ``GATHER_PLAN_FIELDS`` by name"""
+    out = (ctypes.c_int64 * len(GATHER_PLAN_FIELDS))()
+    check(load().pm_embedding_gather_qrows_mixed_plan(ctypes.byref(op), out))
+    return dict(zip(GATHER_PLAN_FIELDS, (int(v) for v in out)))

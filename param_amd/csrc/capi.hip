@@ -9,6 +9,8 @@
 namespace pm {
 // row-quantised tables (embbag_fwd_qrows.hip): p.io = out of out_dtype, addressed in its elements; bits 8 | 4; unroll: plan_qrows'
 hipError_t launch_embbag_fwd_qrows(const KParams& p, int bits, int out_dtype, int max_dim, int unroll, hipStream_t stream);
+// ... of per-table format (embbag_fwd_qmixed.hip): table_bits = device int32 [T], 8 | 4; unroll: plan_qmixed's
+hipError_t launch_embbag_fwd_qmixed(const KParams& p, const int32_t* table_bits, int out_dtype, int max_dim, int unroll, hipStream_t stream);
 }  // namespace pm
 
 namespace {
@@ -713,6 +715,95 @@ int pm_embedding_gather_qrows_plan(const pm_embbag_batch* op, int32_t bits, int6
     const int rc = qgather_request(op, bits, PM_F32, knobs);
     if (rc != PM_OK) return rc;
     const pm::GatherPlan g = pm::plan_gather_qrows(*op, bits, knobs);
+    const int64_t v[8] = {g.vec, g.group_lanes, g.tile, g.col_passes, g.unroll, g.lds_borders, g.xcd_contiguous, g.grid};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return PM_OK;
+}
+
+// ---- row-quantised tables of per-table format (embbag_fwd_qmixed.hip, embedding_gather_qmixed.hip) ---------------------------------------
+// what the four calls refuse on the host, in one order: op, table_bits, the eight-column rule (the stricter of the two formats' column
+// rules, for every table: a lane holds eight columns whatever the format), then what qrows_request refuses about a request of 4-bit
+// tables and the call's out_dtype.  The formats themselves are device data: not read here.
+static int qmixed_request(const pm_embbag_batch* op, const int32_t* table_bits, int32_t out_dtype, const pm::PlanKnobs& knobs, pm::PlanShape& shape,
+                          int& out_bytes) {
+    if (!op) return fail(PM_ERR_INVALID, "op is NULL");
+    if (!table_bits) return fail(PM_ERR_INVALID, "table_bits is NULL (a device array of num_tables ints, each 8 or 4)");
+    if (op->max_dim % pm::kQmixedLaneColumns != 0 || op->min_dim % pm::kQmixedLaneColumns != 0)
+        return fail(PM_ERR_UNSUPPORTED, "per-table formats: every dims[t] (max_dim and min_dim) must be a multiple of 8");
+    const int rc = qrows_request(op, 4, out_dtype, knobs, shape, out_bytes);
+    if (rc != PM_OK) return rc;
+    shape = pm::qmixed_shape(*op, knobs);          // (lanes of eight columns, as the element type qrows_request validated the grid for)
+    return PM_OK;
+}
+
+int pm_embbag_fwd_qrows_mixed(const pm_embbag_batch* op, const int32_t* table_bits, int32_t out_dtype, void* out, pm_stream_t stream) {
+    const pm::PlanKnobs knobs = current_knobs();
+    pm::PlanShape shape;
+    int out_bytes = 0;
+    const int rc = qmixed_request(op, table_bits, out_dtype, knobs, shape, out_bytes);
+    if (rc != PM_OK) return rc;
+    const pm::LaunchPlan plan = pm::plan_qmixed(*op, shape, knobs, out_bytes);
+    pm::KParams p;
+    fill_params(op, plan, p);
+    return padded_forward(p, out, out_dtype == PM_F32 ? 16 : 8, stream, [&](const pm::KParams& q, hipStream_t s) {
+        return pm::launch_embbag_fwd_qmixed(q, table_bits, out_dtype, op->max_dim, plan.unroll, s);
+    }, "pm_embbag_fwd_qrows_mixed launch");
+}
+
+int pm_embbag_qrows_mixed_plan(const pm_embbag_batch* op, int32_t out_dtype, int32_t out[12]) {
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const pm::PlanKnobs knobs = current_knobs();
+    pm::PlanShape shape;
+    int out_bytes = 0;
+    static const int32_t not_read = 0;             // (the plan is a function of the request, out_dtype and the knobs: no formats)
+    const int rc = qmixed_request(op, &not_read, out_dtype, knobs, shape, out_bytes);
+    if (rc != PM_OK) return rc;
+    const pm::LaunchPlan p = pm::plan_qmixed(*op, shape, knobs, out_bytes);
+    const int32_t v[12] = {p.tiles_per_table, p.bags_per_block, p.idx_cap, p.xcd_affine, p.nt_loads, p.ordered,
+                           p.stage_out, p.stage_bags, p.flat_bags, p.flat_target, p.flat_compact, p.unroll};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return PM_OK;
+}
+
+// ... un-pooled: qmixed_request, then what pm_embedding_gather refuses about a request
+static int qmixed_gather_request(const pm_embbag_batch* op, const int32_t* table_bits, int32_t out_dtype, const pm::PlanKnobs& knobs) {
+    pm::PlanShape shape;
+    int out_bytes = 0;
+    const int rc = qmixed_request(op, table_bits, out_dtype, knobs, shape, out_bytes);
+    if (rc != PM_OK) return rc;
+    if (op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "un-pooled rows are unweighted: per_sample_weights must be NULL");
+    return PM_OK;
+}
+
+int pm_embedding_gather_qrows_mixed(const pm_embbag_batch* op, const int32_t* table_bits, int32_t out_dtype, void* out, int64_t out_row_stride,
+                                    pm_stream_t stream) {
+    const pm::PlanKnobs knobs = current_knobs();
+    const int rc = qmixed_gather_request(op, table_bits, out_dtype, knobs);
+    if (rc != PM_OK) return rc;
+    if (out_row_stride < op->max_dim || out_row_stride % 4 != 0)
+        return fail(PM_ERR_INVALID, "out_row_stride must be a multiple of 4 elements and at least max_dim");
+    if (op->num_indices == 0 || op->bag_count == 0) return PM_OK;      // nothing to write, whatever `out` is
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const uintptr_t align = out_dtype == PM_F32 ? 16 : 8;
+    if (reinterpret_cast<uintptr_t>(out) % align != 0) return fail(PM_ERR_INVALID, "out must be " + std::to_string(align) + "-byte aligned");
+    const pm::GatherPlan g = pm::plan_gather_qmixed(*op, knobs);
+    if (g.grid > pm::kMaxGrid) return fail(PM_ERR_UNSUPPORTED, "grid too large");
+    pm::KParams p;
+    fill_params(op, pm::LaunchPlan{}, p);      // (the request; a gather has no bag tiling)
+    p.io = static_cast<float*>(out);           // (addressed in out_dtype's elements)
+    p.out_stride = out_row_stride;
+    const hipError_t h = pm::launch_embedding_gather_qmixed(p, table_bits, out_dtype, g, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embedding_gather_qrows_mixed launch");
+    return PM_OK;
+}
+
+int pm_embedding_gather_qrows_mixed_plan(const pm_embbag_batch* op, int64_t out[8]) {
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const pm::PlanKnobs knobs = current_knobs();
+    static const int32_t not_read = 0;
+    const int rc = qmixed_gather_request(op, &not_read, PM_F32, knobs);
+    if (rc != PM_OK) return rc;
+    const pm::GatherPlan g = pm::plan_gather_qmixed(*op, knobs);
     const int64_t v[8] = {g.vec, g.group_lanes, g.tile, g.col_passes, g.unroll, g.lds_borders, g.xcd_contiguous, g.grid};
     for (int i = 0; i < 8; ++i) out[i] = v[i];
     return PM_OK;

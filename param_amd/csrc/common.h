@@ -229,6 +229,8 @@ hipError_t launch_grad_widen(const KParams& p, int max_dim, const int64_t* pad_i
 hipError_t launch_embedding_gather(const KParams& p, int weight_dtype, int out_dtype, const GatherPlan& g, hipStream_t stream);
 // ... over 8- / 4-bit row-quantised tables (embedding_gather_qrows.hip): bits 8 | 4; g: plan_gather_qrows'
 hipError_t launch_embedding_gather_qrows(const KParams& p, int bits, int out_dtype, const GatherPlan& g, hipStream_t stream);
+// ... of per-table format (embedding_gather_qmixed.hip): table_bits = device int32 [T], 8 | 4; g: plan_gather_qmixed's
+hipError_t launch_embedding_gather_qmixed(const KParams& p, const int32_t* table_bits, int out_dtype, const GatherPlan& g, hipStream_t stream);
 
 // sort-based deterministic backward (embbag_bwd_sorted.hip)
 hipError_t sorted_workspace_bytes(const KParams& p, int64_t max_rows, int max_dim, size_t& bytes);

@@ -400,9 +400,9 @@ constexpr int kQrowsMaxDim = 4096;     // columns per row at most (8 column pass
 static inline int qrows_elem_dtype(int bits) { return bits == 8 ? PM_F32 : PM_BF16; }   // the element type with the format's column rule (D % 4, D % 8)
 static inline int qrows_lane_columns(int bits) { return kQrowsLaneDwords * (bits == 8 ? 4 : 8); }
 // the request's shape for this kernel's lane group (plan_shape's, with the columns a lane holds in place of an element type's)
-static inline PlanShape qrows_shape(const pm_embbag_batch& op, int bits, const PlanKnobs& k) {
+static inline PlanShape lane_columns_shape(const pm_embbag_batch& op, int lane_columns, const PlanKnobs& k) {
     PlanShape s;
-    s.vec = qrows_lane_columns(bits);
+    s.vec = lane_columns;
     s.G = group_lanes(op.max_dim, s.vec);
     s.NG = kBlock / s.G;
     s.total_bags = static_cast<int64_t>(op.num_tables) * op.batch;
@@ -412,6 +412,7 @@ static inline PlanShape qrows_shape(const pm_embbag_batch& op, int bits, const P
     s.base_tile = tile_bags(op, s, k);
     return s;
 }
+static inline PlanShape qrows_shape(const pm_embbag_batch& op, int bits, const PlanKnobs& k) { return lane_columns_shape(op, qrows_lane_columns(bits), k); }
 static inline LaunchPlan plan_qrows(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k, int out_bytes) {
     LaunchPlan p = plan_base(op, s, k);
     if (k.bags_per_block <= 0) p.bags_per_block = burst_tile(p.bags_per_block, s.NG, op.max_dim, out_bytes);
@@ -431,6 +432,24 @@ static inline LaunchPlan plan_qrows(const pm_embbag_batch& op, const PlanShape& 
 static inline LaunchPlan plan_qrows(const pm_embbag_batch& op, int bits, const PlanKnobs& k, int out_bytes) {
     return plan_qrows(op, qrows_shape(op, bits, k), k, out_bytes);
 }
+
+// ---- qmixed: pm_embbag_fwd_qrows_mixed (embbag_fwd_qmixed.hip) -- pooled lookup over tables that are EACH 8- or 4-bit ------------------
+// A lane holds kQmixedLaneColumns = EIGHT COLUMNS of a row whatever its format: two dwords of an 8-bit row (plan_qrows' product setting)
+// and ONE dword of a 4-bit row (measured above for a 4-bit-only launch: 105.6 against 103.7 us uniform, 64.1 against 60.5 us Zipf).  With
+// it the lane group G = group_lanes(max_dim, 8), the eight accumulators, the column passes and the output pieces are the same for every
+// table of the launch, and the host needs no knowledge of which formats are present: the plan is plan_qrows' for a lane of eight columns,
+// a function of the request struct, out_dtype and the knobs alone.  The alternative -- two dwords per lane for both formats, 16 columns of
+// a 4-bit row -- idles half the lanes of a 4-bit table of the widest width (G stays sized for the 8-bit rows); the pooled kernel has it as
+// the experiment build -DPM_QMIXED_4BIT_DWORDS=2 (embbag_fwd_qmixed.hip).  Measured, tools/qmixed_probe.py (16 x 10 M x 128, tables
+// alternately 8- and 4-bit, batch 8192, pooling 20; us, fp32 / fp16 output, uniform | Zipf; one process per build):
+//   eight columns per lane for both      121.3 / 117.3 |  78.3 /  72.3      profiles/qmixed_probe.json -- the product
+//   two dwords per lane for both         121.5 / 118.8 | 104.2 / 102.7      profiles/qmixed_probe_lane_dwords2.json
+// (serving shape 64 x 1 M x 64, batch 256: 10.6 against 11.0).  Two dwords lose a third under Zipf indices: half the lanes of every 4-bit
+// tile idle (why that costs so much more under Zipf than under uniform indices has not been looked into: no counters were collected).
+constexpr int kQmixedLaneColumns = 8;
+static inline PlanShape qmixed_shape(const pm_embbag_batch& op, const PlanKnobs& k) { return lane_columns_shape(op, kQmixedLaneColumns, k); }
+static inline LaunchPlan plan_qmixed(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k, int out_bytes) { return plan_qrows(op, s, k, out_bytes); }
+static inline LaunchPlan plan_qmixed(const pm_embbag_batch& op, const PlanKnobs& k, int out_bytes) { return plan_qmixed(op, qmixed_shape(op, k), k, out_bytes); }
 
 // ---- gather: pm_embedding_gather (embedding_gather.hip) -- un-pooled rows, one output row per lookup POSITION ---------------------------
 // A tile is kBlock consecutive positions of the index array, whatever tables they belong to: the output is addressed by position, so
@@ -493,6 +512,24 @@ constexpr int kQgatherUnroll = 8;
 static inline GatherPlan plan_gather_qrows(const pm_embbag_batch& op, int bits, const PlanKnobs& k) {
     GatherPlan g = {};
     g.vec = qrows_lane_columns(bits);
+    g.group_lanes = group_lanes(op.max_dim, g.vec);
+    g.tile = kBlock;
+    g.col_passes = static_cast<int32_t>(ceil_div(op.max_dim, static_cast<int64_t>(g.group_lanes) * g.vec));
+    const int u = k.unroll != 0 ? k.unroll : kQgatherUnroll;
+    g.unroll = u >= 8 ? 8 : (u >= 4 ? 4 : (u >= 2 ? 2 : 1));
+    g.lds_borders = op.num_tables + 1 <= kGatherLdsBorders ? 1 : 0;
+    g.xcd_contiguous = (op.num_tables > 1 && k.xcd_affine != 0) ? 1 : 0;
+    g.grid = ceil_div(op.num_indices, g.tile);
+    return g;
+}
+
+// ---- gather over tables that are EACH 8- or 4-bit: pm_embedding_gather_qrows_mixed (embedding_gather_qmixed.hip) -----------------------------
+// plan_gather_qrows with plan_qmixed's lane: eight columns per lane and pass for both formats, so rows wider than 512 columns take column
+// passes whatever their format (at most 8 at kQrowsMaxDim).  The format is a row's, so lane groups of one wave may differ in it; the
+// plan does not know the formats.  Rows in flight: plan_gather_qrows' rounding and default (kQgatherUnroll).
+static inline GatherPlan plan_gather_qmixed(const pm_embbag_batch& op, const PlanKnobs& k) {
+    GatherPlan g = {};
+    g.vec = kQmixedLaneColumns;
     g.group_lanes = group_lanes(op.max_dim, g.vec);
     g.tile = kBlock;
     g.col_passes = static_cast<int32_t>(ceil_div(op.max_dim, static_cast<int64_t>(g.group_lanes) * g.vec));

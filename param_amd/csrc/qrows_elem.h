@@ -1,5 +1,6 @@
 // param_amd/csrc/qrows_elem.h -- the device building blocks both kernels over 8- and 4-bit ROW-QUANTISED tables share: the pooled lookup
-// (embbag_fwd_qrows.hip) and the un-pooled one (embedding_gather_qrows.hip).  A row is uint8 [rq::row_bytes(D, BITS)]: the codes of the D
+// (embbag_fwd_qrows.hip) and the un-pooled one (embedding_gather_qrows.hip), and their siblings over tables of per-table format
+// (embbag_fwd_qmixed.hip, embedding_gather_qmixed.hip: the last block below).  A row is uint8 [rq::row_bytes(D, BITS)]: the codes of the D
 // columns (a 4-bit code of column c in byte c / 2 at bit 4 * (c % 2)), then the row's tail -- scale and bias (8 bits: two fp32; 4 bits:
 // two fp16, widened exactly).  gfx950 only.
 #pragma once
@@ -70,6 +71,34 @@ __device__ __forceinline__ QLoad<BITS> load_row(const char* row, int code_off, i
         const u32x2_a4 v = *as_global<u32x2_a4>(row + code_off);
 #pragma unroll
         for (int h = 0; h < kLaneDwords; ++h) q.raw[h] = v[h];
+    } else {
+        q.raw[0] = *as_global<uint32_t>(row + code_off);
+    }
+    q.tail = QRow<BITS>::tail(row, code_bytes);
+    return q;
+}
+
+// The kernels over tables of PER-TABLE format (embbag_fwd_qmixed.hip, embedding_gather_qmixed.hip) hold kQmixedLaneColumns = EIGHT
+// COLUMNS per lane and row whatever the row's format -- two dwords of an 8-bit row (the load above at its product setting), one dword
+// of a 4-bit row -- so that the lane group, the accumulators, the column passes and the output pieces are one for every table of a
+// launch (launch_plan.h: plan_qmixed).  Widths are multiples of 8: a lane's columns lie wholly inside the row's codes or wholly behind.
+// LD: dwords of codes per lane and row, ONE load instruction at a dword-aligned address.  The product's: kQmixedDwords<BITS> (8 bits: 2,
+// 4 bits: 1); the pooled kernel's experiment build -DPM_QMIXED_4BIT_DWORDS=2 gives a 4-bit row two (16 columns: the second dword of a
+// row's last lane may be the row's own 4-byte tail, read and never used -- never behind the row).
+template <int BITS> constexpr int kQmixedDwords = kQmixedLaneColumns / QRow<BITS>::kVec;
+template <int BITS, int LD> struct QLoadN {
+    static_assert(LD == 1 || LD == 2, "one or two dwords of codes per lane");
+    uint32_t raw[LD];
+    typename QRow<BITS>::Tail tail;
+};
+// code_off: byte offset of the lane's first dword of codes (a multiple of 4, inside the codes)
+template <int BITS, int LD>
+__device__ __forceinline__ QLoadN<BITS, LD> load_row_n(const char* row, int code_off, int code_bytes) {
+    QLoadN<BITS, LD> q;
+    if constexpr (LD == 2) {
+        const u32x2_a4 v = *as_global<u32x2_a4>(row + code_off);
+        q.raw[0] = v[0];
+        q.raw[1] = v[1];
     } else {
         q.raw[0] = *as_global<uint32_t>(row + code_off);
     }

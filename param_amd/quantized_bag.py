@@ -1,10 +1,14 @@
 """Pooled and un-pooled lookups over 8- and 4-bit ROW-QUANTISED embedding tables (``csrc/embbag_fwd_qrows.hip`` through
-``pm_embbag_fwd_qrows``, ``csrc/embedding_gather_qrows.hip`` through ``pm_embedding_gather_qrows``).
+``pm_embbag_fwd_qrows``, ``csrc/embedding_gather_qrows.hip`` through ``pm_embedding_gather_qrows``; tables of PER-TABLE format in one
+launch: ``csrc/embbag_fwd_qmixed.hip`` / ``csrc/embedding_gather_qmixed.hip`` through ``pm_embbag_fwd_qrows_mixed`` /
+``pm_embedding_gather_qrows_mixed``).
 
 * :class:`QuantizedBatchedEmbeddingBagMI355` -- T tables stored as the bytes ``quantize_rows`` writes (torch's
   ``quantized::embedding_bag_{byte,4bit}_prepack`` layout), pooled by ONE launch that reads those bytes: no fp32 copy of a table exists.
   The serving-side sibling of :class:`BatchedEmbeddingBagMI355`; what fbgemm's ``IntNBitTableBatchedEmbeddingBagsCodegen`` is for.
   ``lookup_sequence`` is its un-pooled lookup (``PoolingMode.NONE``): one dequantised row per lookup position, one launch.
+  ``bitwidth`` is one int or one int PER TABLE (that class's ``weights_tys``): tables of either format share the launch, each pooled
+  by its own format's rule -- no new arithmetic.
 * :class:`QuantizedEmbeddingBagMI355` -- the single-table module with ``nn.EmbeddingBag``'s call; what
   ``torch.ao.nn.quantized.EmbeddingBag`` is for.
 * :class:`QuantizedEmbeddingMI355` -- the single-table un-pooled module with ``nn.Embedding``'s call; what
@@ -18,8 +22,8 @@ every dequantised element first); the two agree within summation rounding.  A ba
 ``out = fmaf(scale, code, +0.0 + bias)`` (the addition is part of it: the result equals ``dequantize_rows`` as a value, not on the sign
 of zeros), rounded once for a 16-bit ``output_dtype``; bit for bit ``quantized::embedding_byte`` / the two operators above over bags of one.
 
-Forward only: the tables are buffers, nothing requires grad.  There is no CPU path.  Left out, on purpose: 2-bit tables, mean pooling,
-``padding_idx``, per-position weights of the un-pooled lookup, mixed dims of the un-pooled lookup from Python (the C call serves them),
+Forward only: the tables are buffers, nothing requires grad.  There is no CPU path.  Left out, on purpose: 2-bit tables, fp16 / bf16 /
+fp32 rows next to quantised ones, mean pooling, ``padding_idx``, per-position weights of the un-pooled lookup, mixed dims of the un-pooled lookup from Python (the C call serves them),
 pruned rows / index remapping, a padded row stride, per-table lane sub-groups for mixed dims, a lane width per format, the operator
 plug-in, any backward.
 """
@@ -56,6 +60,32 @@ def _check_spec(bitwidth, dims: Sequence[int], layout: str) -> None:
         raise ValueError('layout "tbd" needs one common embedding dim')
 
 
+def _table_bitwidths(bitwidth, dims: Sequence[int], layout: str):
+    """``(bitwidths, bitwidth)`` of a constructor's ``bitwidth`` -- an int for every table, or one int per table as any Sequence but a
+    string (a list, a tuple, a range) or an array / tensor (its ``tolist()``) -- after
+    refusing what cannot be served, before anything is allocated.  ``bitwidth`` is the int of a uniform module and ``None`` of a mixed
+    one; a sequence whose entries are all equal IS that int (today's module, today's launch)."""
+    if isinstance(bitwidth, (str, bytes)) or not (isinstance(bitwidth, Sequence) or hasattr(bitwidth, "tolist")):
+        _check_spec(bitwidth, dims, layout)
+        return [int(bitwidth)] * len(dims), int(bitwidth)
+    if hasattr(bitwidth, "tolist"):         # a numpy array or a tensor of per-table widths: its Python values
+        bitwidth = bitwidth.tolist()
+        if not isinstance(bitwidth, list):
+            bitwidth = [bitwidth]
+    bitwidth = list(bitwidth)               # (any Sequence: a list, a tuple, a range ..)
+    if len(bitwidth) != len(dims):
+        raise ValueError(f"bitwidth names {len(bitwidth)} tables, rows and dims name {len(dims)}: one entry per table (or one int)")
+    for b in bitwidth:
+        if isinstance(b, bool) or not isinstance(b, int) or b not in BITWIDTHS:
+            raise ValueError(f"bitwidth must be 8 or 4 for every table, got {b!r} (2-bit tables are not implemented; 16 bits is a table "
+                             "dtype of BatchedEmbeddingBagMI355)")
+    if len(set(bitwidth)) == 1:
+        _check_spec(bitwidth[0], dims, layout)
+        return [int(bitwidth[0])] * len(dims), int(bitwidth[0])
+    _check_spec(4, dims, layout)        # the stricter column rule (a multiple of 8), applied to every table: a lane holds eight columns
+    return [int(b) for b in bitwidth], None
+
+
 def _sum_only(mode, padding_idx, who: str) -> None:
     if str(getattr(mode, "name", mode)).lower() not in ("sum", "0"):
         raise ValueError(f"{who}: only sum pooling is implemented for row-quantised tables (got {mode!r})")
@@ -67,7 +97,7 @@ class _QTableSet(_TableSet):
     """:class:`_TableSet` over uint8 tables of quantised rows: ``dims`` are the LOGICAL column counts, ``dtype`` (what the request's
     ``weight_dtype`` says) is fp32 -- ``pm_embbag_fwd_qrows`` does not read it, the sanitiser reads rows, indices and offsets only."""
 
-    def __init__(self, tables: Sequence[torch.Tensor], dims: Sequence[int], layout: str):
+    def __init__(self, tables: Sequence[torch.Tensor], dims: Sequence[int], layout: str, bitwidths: Optional[Sequence[int]] = None):
         t0 = tables[0]
         for t in tables:
             _require_device(t, "quantised table")
@@ -86,6 +116,8 @@ class _QTableSet(_TableSet):
         self.d_ptrs = torch.tensor(self.ptrs, dtype=torch.int64, device=self.device)
         self.d_rows = torch.tensor(self.rows, dtype=torch.int64, device=self.device)
         self.d_dims = torch.tensor(self.dims, dtype=torch.int32, device=self.device)
+        # the tables' formats for the per-table-format calls (pm_embbag_fwd_qrows_mixed: table_bits), None for a uniform module
+        self.d_bits = None if bitwidths is None else torch.tensor(list(bitwidths), dtype=torch.int32, device=self.device)
         col0 = [0]
         for d in self.dims[:-1]:
             col0.append(col0[-1] + d)
@@ -102,7 +134,13 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
 
     ``QuantizedBatchedEmbeddingBagMI355(rows, dims, bitwidth, device="cuda", layout="bd", output_dtype=None, bounds_check_mode="none")``:
     ``bitwidth`` 8 (``row_bytes = D + 8``) or 4 (``D / 2 + 4``); ``dims`` multiples of 4 (8-bit) / 8 (4-bit), at most 4096, and may differ
-    per table with ``layout="bd"`` (lane groups are sized for the widest table).  The tables start as zero bytes: every row dequantises
+    per table with ``layout="bd"`` (lane groups are sized for the widest table).  ``bitwidth`` may also be a sequence of one 8 or 4 PER
+    TABLE (a serving model keeps its big tables at 4 bits and its small or sensitive ones at 8): ``bitwidths`` is always that list,
+    ``bitwidth`` the int of a uniform module and ``None`` of a mixed one; a sequence whose entries are all equal is the int (the same
+    launch, plan and bits).  A mixed module needs every dim a multiple of 8; its ``lookup`` and ``lookup_sequence`` are still ONE launch
+    (``pm_embbag_fwd_qrows_mixed`` / ``pm_embedding_gather_qrows_mixed``) and give, per table, the bits of a module of that table's
+    format alone; ``table(t)``, ``quantize_from_``, ``dequantized_table`` and the slab layout use table ``t``'s format.
+    The tables start as zero bytes: every row dequantises
     to zeros.  ``table(t)`` is the uint8 ``[rows_t, row_bytes]`` tensor -- copy prepacked bytes into it, or fill it with
     ``quantize_from_(t, fp32)`` (the ``quantize_rows`` kernel: fp32 sources, dims a multiple of 8 up to 512).  ``dequantized_table(t)`` is
     ``dequantize_rows`` of it.
@@ -120,7 +158,7 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     At call time: tensors that are not on a ROCm device raise RuntimeError (no CPU fallback), a floating-point index tensor TypeError.
     """
 
-    def __init__(self, rows: Sequence[int], dims, bitwidth: int, device="cuda", layout: str = "bd", output_dtype=None,
+    def __init__(self, rows: Sequence[int], dims, bitwidth, device="cuda", layout: str = "bd", output_dtype=None,
                  bounds_check_mode="none", pooling_mode="sum", padding_idx=None):
         super().__init__()
         self._init_shared(bounds_check_mode, output_dtype)
@@ -128,13 +166,13 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         dims = [int(dims)] * len(rows) if isinstance(dims, int) else [int(d) for d in dims]
         if len(rows) != len(dims) or not rows:
             raise ValueError("rows and dims must name the same tables, at least one")
-        _check_spec(bitwidth, dims, layout)
+        bitwidths, bitwidth = _table_bitwidths(bitwidth, dims, layout)
         _sum_only(pooling_mode, padding_idx, type(self).__name__)
         if any(r < 0 or r >= 2**31 for r in rows):
             raise ValueError("every table needs 0 <= rows < 2^31")
         self.padding_idx = None
-        self.rows, self.dims, self.bitwidth, self.layout = rows, dims, int(bitwidth), layout
-        self._row_bytes = [quant.host_row_bytes(d, self.bitwidth) for d in dims]
+        self.rows, self.dims, self.bitwidth, self.bitwidths, self.layout = rows, dims, bitwidth, bitwidths, layout
+        self._row_bytes = [quant.host_row_bytes(d, b) for d, b in zip(dims, bitwidths)]
         # table starts padded to 256 B (rows themselves are 4-byte aligned and no better)
         starts, cur = [], 0
         for r, rb in zip(rows, self._row_bytes):
@@ -160,17 +198,17 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             raise ValueError(f"quantize_from_: table {t} is {(self.rows[t], self.dims[t])}, got {tuple(source.shape)}")
         _require_device(self.weights, f"{type(self).__name__}.weights")
         if self.rows[t]:
-            quant.quantize_rows(source.detach().contiguous(), self.dims[t], self.bitwidth, out=self.table(t))
+            quant.quantize_rows(source.detach().contiguous(), self.dims[t], self.bitwidths[t], out=self.table(t))
 
     def dequantized_table(self, t: int) -> torch.Tensor:
         """fp32 ``[rows_t, D_t]``: ``dequantize_rows`` of table ``t``"""
         _require_device(self.weights, f"{type(self).__name__}.weights")
-        return quant.dequantize_rows(self.table(t), self.dims[t], self.bitwidth)
+        return quant.dequantize_rows(self.table(t), self.dims[t], self.bitwidths[t])
 
     @classmethod
-    def from_float(cls, source, bitwidth: int, **kw):
+    def from_float(cls, source, bitwidth, **kw):
         """quantise a :class:`BatchedEmbeddingBagMI355` sum module (16-bit tables are widened first) or a sequence of fp32 ``[rows, D]``
-        tensors; keywords go to the constructor (``device``, ``layout`` default to the source's)"""
+        tensors; ``bitwidth``: an int, or one per table; keywords go to the constructor (``device``, ``layout`` default to the source's)"""
         if isinstance(source, BatchedEmbeddingBagMI355):
             _sum_only(source.pooling_mode, source.padding_idx, "from_float")
             tables = [source.table(t).float() for t in range(len(source.rows))]
@@ -187,7 +225,8 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
 
     def _tables(self) -> _QTableSet:
         if self._ts is None or self._ts.ptrs[0] != self.table(0).data_ptr():
-            self._ts = _QTableSet([self.table(t) for t in range(len(self.rows))], self.dims, self.layout)
+            self._ts = _QTableSet([self.table(t) for t in range(len(self.rows))], self.dims, self.layout,
+                                  None if self.bitwidth is not None else self.bitwidths)
         return self._ts
 
     _batch_of = BatchedEmbeddingBagMI355._batch_of
@@ -212,7 +251,10 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             out = torch.empty(shape, dtype=odt, device=ts.device)
         elif out.dtype != odt or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != ts.device:
             raise ValueError(f"out must be a contiguous {str(odt).replace('torch.', '')} tensor of shape {shape} on {ts.device}")
-        rc = _lib.load().pm_embbag_fwd_qrows(ctypes.byref(op), self.bitwidth, _WDTYPE[odt], out.data_ptr(), _stream_ptr())
+        if self.bitwidth is not None:
+            rc = _lib.load().pm_embbag_fwd_qrows(ctypes.byref(op), self.bitwidth, _WDTYPE[odt], out.data_ptr(), _stream_ptr())
+        else:
+            rc = _lib.load().pm_embbag_fwd_qrows_mixed(ctypes.byref(op), ts.d_bits.data_ptr(), _WDTYPE[odt], out.data_ptr(), _stream_ptr())
         if rc:
             _lib.check(rc)
         return out
@@ -221,8 +263,11 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         return self.lookup(indices, offsets, per_sample_weights, out, bag_begin, bag_count, batch)
 
     def plan(self, indices, offsets, per_sample_weights=None, bag_begin=0, bag_count=None, batch: Optional[int] = None) -> dict:
-        """the launch geometry ``lookup`` would use for this request under the knobs as they stand (``_lib.PLAN_FIELDS`` by name)"""
+        """the launch geometry ``lookup`` would use for this request under the knobs as they stand (``_lib.PLAN_FIELDS`` by name;
+        ``pm_embbag_qrows_plan``, or ``pm_embbag_qrows_mixed_plan`` for a module of per-table formats)"""
         _, _, op = self._request(indices, offsets, per_sample_weights, bag_begin, bag_count, batch, False)
+        if self.bitwidth is None:
+            return _lib.embbag_qrows_mixed_plan(op, _WDTYPE[self.output_dtype])
         return _lib.embbag_qrows_plan(op, self.bitwidth, _WDTYPE[self.output_dtype])
 
     # -- un-pooled ---------------------------------------------------------------------------
@@ -237,7 +282,8 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         """The UN-POOLED forward over the module's T tables (int-nbit TBE's ``PoolingMode.NONE``): ``[N, D]`` in the module's
         ``output_dtype``, ``N = indices.numel()``, row ``j`` = row ``indices[j]`` of the table that owns lookup position ``j`` (table ``t``
         owns ``[offsets[t * B], offsets[(t + 1) * B])``), dequantised by the module docstring's rule for a bag of one -- one launch,
-        ``pm_embedding_gather_qrows``, that reads the quantised bytes.  Runs after ``bounds_check_mode``, like ``lookup``.
+        ``pm_embedding_gather_qrows`` (a module of per-table formats: ``pm_embedding_gather_qrows_mixed``, every row in its table's
+        format), that reads the quantised bytes.  Runs after ``bounds_check_mode``, like ``lookup``.
         ``bag_begin/bag_count`` select a batch slice: only the rows of lookups inside it are written -- a caller's ``out`` keeps every
         other row, a tensor allocated here holds zeros there.  Needs one common embedding dim; mixed dims and an ``out`` that is not a
         contiguous ``[N, D]`` tensor of ``output_dtype`` on the module's device raise ValueError, floating-point indices TypeError."""
@@ -247,15 +293,22 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             whole = bag_begin == 0 and bag_count in (None, B)
             out = (torch.empty if whole else torch.zeros)((n, D), dtype=odt, device=ts.device)
         if n:
-            rc = _lib.load().pm_embedding_gather_qrows(ctypes.byref(op), self.bitwidth, _WDTYPE[odt], out.data_ptr(), D, _stream_ptr())
+            if self.bitwidth is not None:
+                rc = _lib.load().pm_embedding_gather_qrows(ctypes.byref(op), self.bitwidth, _WDTYPE[odt], out.data_ptr(), D, _stream_ptr())
+            else:
+                rc = _lib.load().pm_embedding_gather_qrows_mixed(ctypes.byref(op), ts.d_bits.data_ptr(), _WDTYPE[odt], out.data_ptr(), D,
+                                                                 _stream_ptr())
             if rc:
                 _lib.check(rc)
         return out
 
     def sequence_plan(self, indices, offsets, batch: Optional[int] = None, bag_begin=0, bag_count=None) -> dict:
         """the launch geometry ``lookup_sequence`` would use for this request under the knobs as they stand (``_lib.GATHER_PLAN_FIELDS``
-        by name; ``pm_embedding_gather_qrows_plan``, nothing is launched)"""
+        by name; ``pm_embedding_gather_qrows_plan`` -- a module of per-table formats: ``pm_embedding_gather_qrows_mixed_plan`` --,
+        nothing is launched)"""
         _, _, op = self._sequence_request(indices, offsets, batch, bag_begin, bag_count, False)
+        if self.bitwidth is None:
+            return _lib.embedding_gather_qrows_mixed_plan(op)
         return _lib.embedding_gather_qrows_plan(op, self.bitwidth)
 
     def sanitize_(self, indices, offsets, batch: Optional[int] = None, mode=None) -> None:
@@ -266,7 +319,7 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         self._sanitize(self._tables(), indices, offsets, B, "warning" if mode == "none" else mode)
 
     def extra_repr(self) -> str:
-        return (f"rows={self.rows}, dims={self.dims}, bitwidth={self.bitwidth}, layout={self.layout}" +
+        return (f"rows={self.rows}, dims={self.dims}, bitwidth={self.bitwidth if self.bitwidth is not None else self.bitwidths}, layout={self.layout}" +
                 (f", output_dtype={self.output_dtype}" if self._out16 is not None else ""))
 
 
