@@ -43,7 +43,7 @@ int hip_fail(hipError_t rc, const char* what) {
 // path (getenv is not thread-safe against setenv, and a value that changes between two calls of one request's sequence is a hazard,
 // not a feature).
 const pm::FwdEnv& fwd_env() {
-    static const pm::FwdEnv e = [] {
+    const auto read = [] {
         auto num = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
         pm::FwdEnv r;
         const char* st = getenv("PARAM_AMD_FWD_STAGE");
@@ -54,9 +54,19 @@ const pm::FwdEnv& fwd_env() {
         r.flat_bags = num("PARAM_AMD_FLAT_BAGS", r.flat_bags);
         r.tile_major = num("PARAM_AMD_FWD_TILE_MAJOR", r.tile_major);
         r.flat_compact = num("PARAM_AMD_FLAT_COMPACT", r.flat_compact);
+        r.drain_split = num("PARAM_AMD_FWD_DRAIN_SPLIT", r.drain_split);
+        r.round_wgs = num("PARAM_AMD_FWD_ROUND_WGS", r.round_wgs);
         return r;
-    }();
+    };
+#ifdef PM_EXPERIMENTS
+    // experiment builds read the switches on every call, so that one process can measure them taking turns (tools/fwd_round_timeline.py)
+    static thread_local pm::FwdEnv again;
+    again = read();
+    return again;
+#else
+    static const pm::FwdEnv e = read();
     return e;
+#endif
 }
 
 // Every knob a plan reads, loaded once per call (apply_params alone reads one more, the sorted apply's row policy): a pm_set_* from another thread lands before or after a request's plan, never inside it.
@@ -179,6 +189,8 @@ void fill_params(const pm_embbag_batch* op, const pm::LaunchPlan& plan, pm::KPar
     p.flat_bags = plan.flat_bags;
     p.flat_target = plan.flat_target;
     p.flat_compact = plan.flat_compact;
+    p.round_wgs = plan.round_wgs;       // (what the plan asks of the launch's last round: the forward's launcher resolves it, embbag_fwd.hip)
+    p.drain_split = plan.drain_split;
 }
 
 // ---- the sorted backward's entry points: what they share ---------------------------------------------------------------
@@ -335,7 +347,7 @@ int pm_set_forward_tuning(int32_t stage_out, int32_t flat_grid, int32_t flat_tar
 int pm_embbag_plan(const pm_embbag_batch* op, int32_t kind, int32_t out[12]) {
     if (kind < PM_PLAN_BASE || kind > PM_PLAN_PADDED16) return fail(PM_ERR_INVALID, "kind must be PM_PLAN_BASE .. PM_PLAN_PADDED16");
     if (!out) return fail(PM_ERR_INVALID, "out is NULL");
-    static_assert(sizeof(pm::LaunchPlan) == 12 * sizeof(int32_t), "the query copies the twelve members in their order");
+    static_assert(offsetof(pm::LaunchPlan, unroll) == 11 * sizeof(int32_t), "the query copies the twelve reported members in their order");
     const pm::PlanKnobs knobs = current_knobs();
     pm::PlanShape shape;
     const int rc = validate_request(op, op ? op->weight_dtype : -1, knobs, &shape);

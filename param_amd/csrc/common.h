@@ -64,6 +64,9 @@ struct KParams {
     int32_t gblk_shift;          // backward kernels: blocked gradient layout (ABI v6, pm_embbag_batch::grad_block_shift): bag b of table t at
     int64_t gblk_extra;          //   io + out_offsets[t] + b * out_stride + (b >> gblk_shift) * gblk_extra ; no blocking: extra = 0
     float alpha;                 // bwd scale
+    int32_t round_wgs;           // forward, staged bag-count kernel with xcd_affine == 1: > 0 = this many workgroups are resident per XCD and
+                                 // the tiles of an XCD's last round are split (launch_plan.h: drain_block_tile); 0: every other launch
+    int32_t drain_split;         // ... workgroups that pool one tile of that last round (> 1)
 };
 
 // element offset of bag `bag`'s gradient row inside its table's slice (blocked layouts add a per-block term; extra == 0 otherwise)
@@ -118,6 +121,23 @@ __device__ __forceinline__ void block_to_tile(const KParams& p, int& t, int& til
         t = bid / p.tiles_per_table;
         tile = bid % p.tiles_per_table;
     }
+}
+
+// ... and the part of the tile the block pools: launches with round_wgs > 0 (the forward's staged bag-count kernel) take launch_plan.h's
+// drain_block_tile, whatever xcd_affine says (the launcher sets round_wgs only where that is 1: the same order, and the last round's
+// tiles in parts); every other launch keeps the order above and pools whole tiles.
+__device__ __forceinline__ void block_to_tile(const KParams& p, int& t, int& tile, int& part, int& parts, int bid = blockIdx.x) {
+    if (p.round_wgs > 0) {
+        const BlockTile b = drain_block_tile(bid, p.T, p.tiles_per_table, p.round_wgs, p.drain_split);
+        t = b.table;
+        tile = b.tile;
+        part = b.part;
+        parts = b.parts;
+        return;
+    }
+    part = 0;
+    parts = 1;
+    block_to_tile(p, t, tile, bid);
 }
 
 // LDS layout of a tile: int64 s_off[bags_per_block + 1] | int32 s_idx[idx_cap] | float s_w[idx_cap]

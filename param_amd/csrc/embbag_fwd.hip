@@ -22,10 +22,14 @@
 //   * output rows are written with non-temporal 16-byte stores (never re-read by this kernel);
 //   * blockIdx -> (table, tile) can be XCD-affine (common.h) so a table's hot rows stay in
 //     one XCD's L2 under Zipf-skewed indices.
+#include <map>
+#include <mutex>
+#include <tuple>
 #include <type_traits>
 
 #include "common.h"
 #include "fwd_elem.h"
+#include "pm_experiments.h"
 #include "rowquant.inc"
 
 namespace pm {
@@ -102,11 +106,29 @@ __global__ void __launch_bounds__(kBlock) embbag_fwd_kernel(const KParams p) {
     __shared__ int s_next;  // next unassigned bag of the tile: lane groups pull bags dynamically (ragged bag sizes)
 
     int t, tile;
-    block_to_tile(p, t, tile);
-    if (t >= p.T) return;
-    const int64_t bag0 = p.bag_begin + static_cast<int64_t>(tile) * p.bags_per_block;
+    int64_t bag0;
+    int run_bags = p.bags_per_block;   // bags this workgroup pools at most: the tile, or its part of a split tile
+    if (STAGE && !ORDERED) {
+        // (the staged bag-count launches: a tile of an XCD's last round is pooled by `parts` workgroups, launch_plan.h's
+        // drain_block_tile -- this one takes the part-th run of bags_per_block / parts bags, with the launch's LDS layout)
+        int part, parts;
+        block_to_tile(p, t, tile, part, parts);
+        if (t >= p.T) return;
+        bag0 = p.bag_begin + static_cast<int64_t>(tile) * p.bags_per_block;
+        if (parts > 1) {
+            run_bags = p.bags_per_block / parts;
+            bag0 += static_cast<int64_t>(part) * run_bags;
+            if (bag0 >= p.bag_begin + p.bag_count) return;   // the request's last tile is short: this part of it has no bags
+        }
+    } else {
+        block_to_tile(p, t, tile);
+        if (t >= p.T) return;
+        bag0 = p.bag_begin + static_cast<int64_t>(tile) * p.bags_per_block;
+    }
+    PM_STAMP(blockIdx.x, 0);                        // (experiment builds: start, end, XCD and table of every workgroup -- tools/fwd_round_timeline.py)
+    PM_STAMP_VALUE(blockIdx.x, 2, (static_cast<unsigned long long>(PM_XCC_ID()) << 32) | static_cast<unsigned>(t));
     const int64_t left_bags = p.bag_begin + p.bag_count - bag0;
-    const int nb = left_bags < p.bags_per_block ? static_cast<int>(left_bags) : p.bags_per_block;
+    const int nb = left_bags < run_bags ? static_cast<int>(left_bags) : run_bags;
     if (threadIdx.x == 0) s_next = NG;  // bags 0 .. NG-1 are taken statically; visible after stage_tile_at's barrier
 
     int64_t* s_off;
@@ -265,6 +287,7 @@ __global__ void __launch_bounds__(kBlock) embbag_fwd_kernel(const KParams p) {
             quantized_burst(p, s_out, nb, D, bag0, p.out_offsets[t]);
         }
     }
+    PM_STAMP_DRAINED(blockIdx.x, 1);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -479,8 +502,52 @@ __global__ void __launch_bounds__(kBlock) embbag_fwd_flat_kernel(const KParams p
     }
 }
 
+// Workgroups of `kernel` with `lds` bytes of dynamic LDS that are resident on ONE XCD at a time: the occupancy the runtime reports per
+// CU, times the CUs of an XCD.  Asked once per (device, instance, LDS bytes) and kept; never asked while `stream` is being captured --
+// a launch that finds no cached answer there returns 0 and keeps the plain block order (which changes no result).
+int resident_wgs_per_xcd(const void* kernel, size_t lds, hipStream_t stream) {
+    static std::mutex mu;
+    static std::map<std::tuple<int, const void*, size_t>, int> known;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    const auto key = std::make_tuple(dev, kernel, lds);
+    std::lock_guard<std::mutex> lock(mu);
+    const auto it = known.find(key);
+    if (it != known.end()) return it->second;
+    // (a query that fails must not be what the launch's hipGetLastError reports: the error is taken off)
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    if (capturing != hipStreamCaptureStatusNone) return 0;
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, lds) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    const int r = per_cu * (cus / kXcds);
+    known.emplace(key, r);
+    return r;
+}
+
+// the staged bag-count launch's split last round (launch_plan.h: resolve_drain_split): p's members and the grid, for this instance's residency
+void apply_drain_split(KParams& p, int& grid, const void* kernel, size_t lds, hipStream_t stream) {
+    const int want_split = p.drain_split, given = p.round_wgs;
+    p.round_wgs = p.drain_split = 0;
+    if (want_split <= 1 || p.xcd_affine != 1) return;
+    const int R = given > 0 ? given : resident_wgs_per_xcd(kernel, lds, stream);
+    const DrainSplit o = resolve_drain_split(p.T, p.tiles_per_table, R, want_split);
+    p.round_wgs = o.round_wgs;
+    p.drain_split = o.drain_split;
+    grid += o.extra_blocks;
+}
+
 template <typename WT, int G, int UNROLL>
-hipError_t launch_w(const KParams& p, hipStream_t stream) {
+hipError_t launch_w(const KParams& request, hipStream_t stream) {
+    KParams p = request;
+    if (p.flat_bags > 0 || !p.stage_out || p.ordered) p.round_wgs = p.drain_split = 0;   // (the staged bag-count launch alone: apply_drain_split)
     const bool weighted = p.psw != nullptr;
     int grid = p.T * p.tiles_per_table;
     size_t lds = tile_lds_bytes(p.bags_per_block, p.idx_cap, weighted);
@@ -501,12 +568,20 @@ hipError_t launch_w(const KParams& p, hipStream_t stream) {
     }
     // (spelled out in this order on purpose: the order of instantiation is the order of the kernels in the code object)
 #define PM_FWD(W_, O_, S_) hipLaunchKernelGGL((embbag_fwd_kernel<WT, G, UNROLL, W_, O_, S_>), dim3(grid), dim3(kBlock), lds, stream, p)
+#define PM_FWD_ADDR(W_, O_, S_) reinterpret_cast<const void*>(&embbag_fwd_kernel<WT, G, UNROLL, W_, O_, S_>)
     if (p.stage_out && !p.ordered) {   // fixed-pooling requests (capi.hip decides)
         lds += static_cast<size_t>(p.bags_per_block) * p.stage_out * sizeof(float);   // stage_out = widest row (elements)
-        if (weighted) PM_FWD(true, false, true); else PM_FWD(false, false, true);
+        if (weighted) {
+            apply_drain_split(p, grid, PM_FWD_ADDR(true, false, true), lds, stream);
+            PM_FWD(true, false, true);
+        } else {
+            apply_drain_split(p, grid, PM_FWD_ADDR(false, false, true), lds, stream);
+            PM_FWD(false, false, true);
+        }
     } else if (weighted) { if (p.ordered) PM_FWD(true, true, false); else PM_FWD(true, false, false); }
     else { if (p.ordered) PM_FWD(false, true, false); else PM_FWD(false, false, false); }
 #undef PM_FWD
+#undef PM_FWD_ADDR
     return hipGetLastError();
 }
 
@@ -540,3 +615,5 @@ hipError_t launch_embbag_fwd(const KParams& p, int weight_dtype, int max_dim, in
 }
 
 }  // namespace pm
+
+PM_DEFINE_TRACE_READER(pm_experiment_trace_fwd)      // experiment builds only (pm_experiments.h); nothing in the product

@@ -40,6 +40,8 @@ struct FwdEnv {
     int flat_bags = 256;   // PARAM_AMD_FLAT_BAGS (bags per flat-walk tile at most)
     int tile_major = -1;   // PARAM_AMD_FWD_TILE_MAJOR=1
     int flat_compact = 1;  // PARAM_AMD_FLAT_COMPACT=0: the flat-walk kernel's old grid (T x smallest-tile count); N > 1: exactly N workgroups
+    int drain_split = 4;   // PARAM_AMD_FWD_DRAIN_SPLIT=0 (or 1): the last round's tiles are not split; N: by N workgroups each (a power of two)
+    int round_wgs = 0;     // PARAM_AMD_FWD_ROUND_WGS=N: N resident workgroups per XCD instead of what the device reports (tests, sweeps)
 };
 // what pm_set_tuning and pm_set_forward_tuning were last given; the values here are "not set"
 struct TuningSetters {
@@ -60,6 +62,8 @@ struct PlanKnobs {
     int flat_bags;
     int flat_grid;       // 0: grid of T x smallest-tile count; 1: as many resident workgroups as the request has tiles; N > 1: exactly N
     int tile_major;
+    int drain_split;     // FwdEnv::drain_split
+    int round_wgs;       // FwdEnv::round_wgs
 };
 static inline PlanKnobs resolve_knobs(const TuningSetters& s, const FwdEnv& e) {
     PlanKnobs k;
@@ -75,15 +79,21 @@ static inline PlanKnobs resolve_knobs(const TuningSetters& s, const FwdEnv& e) {
     k.flat_bags = e.flat_bags;
     k.flat_grid = s.flat_grid >= 0 ? s.flat_grid : e.flat_compact;
     k.tile_major = e.tile_major;
+    k.drain_split = e.drain_split;
+    k.round_wgs = e.round_wgs;
     return k;
 }
 
 // ---- the plan -----------------------------------------------------------------------------------------------------------------
-// The geometry members of KParams (common.h describes each) and the forward's unroll (0 where the launch has none).
+// The geometry members of KParams (common.h describes each) and the forward's unroll (0 where the launch has none): the twelve members
+// pm_embbag_plan reports.  Behind them, unreported: what the plan asks of the launch's last round (with_drain_split); the launcher turns
+// it into KParams' members of the same names once it knows the resident workgroups (resolve_drain_split).
 struct LaunchPlan {
     int32_t tiles_per_table, bags_per_block, idx_cap, xcd_affine, nt_loads, ordered;
     int32_t stage_out, stage_bags, flat_bags, flat_target, flat_compact;
     int32_t unroll;
+    int32_t round_wgs;     // > 0: resident workgroups per XCD given by the knob; 0: the launcher asks the device
+    int32_t drain_split;   // > 1: the last round's tiles pooled by this many workgroups each
 };
 
 // what the rules below read of a request, derived once
@@ -327,10 +337,31 @@ static inline LaunchPlan forward_geometry(const pm_embbag_batch& op, const PlanS
 }
 
 // ---- forward: pm_embbag_fwd -------------------------------------------------------------------------------------------------------
+// A short final drain (drain_block_tile, further down): the tiles of an XCD's last round are pooled by S workgroups each.  Offered where
+// the order is t % 8 and the kernel is the staged bag-count one -- fixed pooling, not ordered, not the flat walk -- and left to the
+// launcher (embbag_fwd.hip), which knows how many workgroups of the launched instance are resident.  None of the reported members
+// moves.  S: a power of two, and a part keeps whole lane-group rounds of bags (S <= bags_per_block / NG).
+// Same process, the switch taking turns, medians of 7 windows, spreads <= 0.25 % (profiles/fwd_round_timeline.md; us off -> S = 4):
+//   48 x 10 M x 128 fp32 [T, B, D]   Zipf 361.3 -> 358.8 (0.7 %)   uniform 754.4 -> 751.3 (0.4 %)        S = 2: 358.5 / 752.9
+//   the same, [B, sum D]              Zipf 364.8 -> 360.7 (1.1 %)   uniform 764.7 -> 760.6 (0.5 %)
+//   64 x 10 M x 128 bf16 [T, B, D]   Zipf 277.9 -> 275.5 (0.9 %)   uniform 539.3 -> 537.8 (0.3 %)
+// The XCD's last full residency to its last workgroup's end: 44 -> 18 us of the Zipf launch; that it buys 2.6 us says the drain was not
+// idle time -- the launch is bound behind L2, and fewer workgroups still keep that path busy.
+// Built, measured and removed with it: whole-round table passes (tiles 0 .. R - 1 of each of the XCD's tables in turn, the left-overs
+// last).  One table resident 30 -> 63 % of the launch, L2 misses 17.40 M -> 17.13 M (1.5 %), the launch 0.56 % SLOWER (361.3 -> 363.3 us).
+static inline LaunchPlan with_drain_split(const PlanShape& s, const PlanKnobs& k, LaunchPlan p) {
+    if (p.xcd_affine != 1 || p.stage_out <= 0 || p.ordered || p.flat_bags > 0 || !s.even) return p;
+    int split = 1;
+    while (split * 2 <= k.drain_split && split * 2 * s.NG <= p.bags_per_block && p.bags_per_block % (split * 2) == 0) split *= 2;
+    p.drain_split = split;
+    p.round_wgs = split > 1 && k.round_wgs > 0 ? k.round_wgs : 0;
+    return p;
+}
+
 static inline LaunchPlan plan_forward(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k) {
     LaunchPlan p = forward_geometry(op, s, k);
     p.unroll = k.unroll != 0 ? k.unroll : small_request_unroll(op, s, p);
-    return p;
+    return with_drain_split(s, k, p);
 }
 static inline LaunchPlan plan_forward(const pm_embbag_batch& op, int elem_dtype, const PlanKnobs& k) {
     return plan_forward(op, plan_shape(op, elem_dtype, k), k);
@@ -478,6 +509,47 @@ struct GatherPlan {
 constexpr int64_t gather_block_tile(int64_t bid, int64_t total, bool xcd_contiguous) {
     return !xcd_contiguous ? bid : (bid % kXcds) * (total / kXcds) + ((bid % kXcds) < (total % kXcds) ? (bid % kXcds) : (total % kXcds)) + bid / kXcds;
 }
+// ---- the split last round (xcd_affine == 1 launches of the staged bag-count kernel) ----------------------------------------------------
+// XCD x = block % 8 serves the n = T / 8 tables x, x + 8, ...; its blocks, in dispatch order, are its SLOTS 0 .. n * tiles_per_table - 1,
+// the tiles of its tables in table-major order (what block_to_tile's xcd_affine == 1 branch computes).  With R workgroups resident per
+// XCD and S > 1, the XCD's last (slots mod R) slots -- its last round -- are each pooled by S workgroups, part q taking bags
+// [q, q + 1) * bags_per_block / S of the tile.  Part 0 is the slot's own block; parts 1 .. S - 1 are blocks appended behind the
+// T x tiles_per_table grid, 8 * (slots mod R) * (S - 1) of them, slot-major, on the XCD of their table (T % 8 == 0: the appended blocks
+// start at a multiple of 8).
+// A bijection of [0, T * tiles_per_table + extra) onto the (table, tile, part) triples for every (T % 8 == 0, tiles_per_table, R, S):
+// tests/test_drain_split_host.py.  Host and device (constexpr), 32-bit: resolve_drain_split keeps the grid within kMaxGrid.
+struct BlockTile {
+    int32_t table, tile;
+    int32_t part, parts;   // this block pools part `part` of the tile's `parts` equal runs of bags (1: the whole tile)
+};
+constexpr BlockTile drain_block_tile(int32_t bid, int32_t T, int32_t tiles_per_table, int32_t R, int32_t S) {
+    const int32_t main_grid = T * tiles_per_table;
+    const int32_t slots = T / kXcds * tiles_per_table;
+    const int32_t drain = S > 1 ? slots % R : 0;
+    int32_t xcd = bid % kXcds, slot = bid / kXcds, part = 0;
+    if (bid >= main_grid) {
+        const int32_t e = bid - main_grid;
+        xcd = e % kXcds;
+        slot = slots - drain + (e / kXcds) / (S - 1);
+        part = 1 + (e / kXcds) % (S - 1);
+    }
+    return BlockTile{xcd + kXcds * (slot / tiles_per_table), slot % tiles_per_table, part, slot >= slots - drain ? S : 1};
+}
+// What a launch does with the plan's wish (LaunchPlan::drain_split) once R is known: KParams' members and the blocks to append.  Only
+// where it can matter: more than one round per XCD (grid > 8 * R) and a last round that is not a whole one; all zero = the plain order,
+// the kernel's plain path.
+struct DrainSplit {
+    int32_t round_wgs, drain_split;
+    int32_t extra_blocks;
+};
+constexpr DrainSplit resolve_drain_split(int32_t T, int32_t tiles_per_table, int32_t R, int32_t want_split) {
+    if (R <= 0 || T % kXcds != 0 || tiles_per_table <= 0 || want_split <= 1) return DrainSplit{0, 0, 0};
+    const int64_t slots = static_cast<int64_t>(T / kXcds) * tiles_per_table;
+    const int64_t extra = kXcds * (slots % R) * (want_split - 1);
+    if (slots <= R || extra == 0 || static_cast<int64_t>(T) * tiles_per_table + extra > kMaxGrid) return DrainSplit{0, 0, 0};
+    return DrainSplit{R, want_split, static_cast<int32_t>(extra)};
+}
+
 static inline GatherPlan plan_gather(const pm_embbag_batch& op, int elem_dtype, const PlanKnobs& k) {
     GatherPlan g = {};
     g.vec = (elem_dtype == PM_F32) ? 4 : 8;

@@ -23,8 +23,14 @@ __device__ __forceinline__ void stamp(unsigned wg, int slot, bool drain) {
     if (drain) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     if (threadIdx.x == 0 && wg < static_cast<unsigned>(kTraceWgs)) g_trace[wg * kTraceSlots + slot] = __builtin_amdgcn_s_memrealtime();
 }
+__device__ __forceinline__ void stamp_value(unsigned wg, int slot, unsigned long long v) {
+    if (threadIdx.x == 0 && wg < static_cast<unsigned>(kTraceWgs)) g_trace[wg * kTraceSlots + slot] = v;
+}
 }  // namespace exp
 }  // namespace pm
+#define PM_STAMP_VALUE(wg, slot, v) pm::exp::stamp_value((wg), (slot), (v))
+// the XCD the wave runs on: bits 3:0 of hardware register 20 (XCC_ID, gfx940 and later): s_getreg_b32 hwreg(20, 0, 4)
+#define PM_XCC_ID() __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20)
 #define PM_STAMP(wg, slot) pm::exp::stamp((wg), (slot), false)
 #define PM_STAMP_DRAINED(wg, slot) pm::exp::stamp((wg), (slot), true)
 // the translation unit's reader: copies `words` 64-bit words of its trace buffer to `out` (device synchronised first), optionally clears it
@@ -44,5 +50,6 @@ __device__ __forceinline__ void stamp(unsigned wg, int slot, bool drain) {
 #else
 #define PM_STAMP(wg, slot) ((void)0)
 #define PM_STAMP_DRAINED(wg, slot) ((void)0)
+#define PM_STAMP_VALUE(wg, slot, v) ((void)0)
 #define PM_DEFINE_TRACE_READER(fn)
 #endif
