@@ -562,8 +562,8 @@ int pm_embedding_gather(const pm_embbag_batch* op, int32_t out_dtype, void* out,
  * bags_per_block and pm_set_forward_tuning's stage_out are honoured, nothing else of the knobs is read).  Host only, launches nothing;
  * validates as the launching call does, except for `out` of that call.
  * Replaces torch's two CPU operators named above (behind torch.ao.nn.quantized.EmbeddingBag) and the forward of fbgemm's
- * IntNBitTableBatchedEmbeddingBagsCodegen for INT8 / INT4 tables.  Left out: 2-bit tables, mean, padding_idx, pruned rows / index
- * remapping, a padded row stride (the un-pooled lookup: below; tables of differing format in one launch: PER-TABLE FORMATS below).
+ * IntNBitTableBatchedEmbeddingBagsCodegen for INT8 / INT4 tables.  Left out: 2-bit tables, mean, padding_idx, a padded row stride (the
+ * un-pooled lookup: below; tables of differing format in one launch: PER-TABLE FORMATS below; pruned rows: PRUNED TABLES below).
  * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these two finds out at symbol resolution.
  */
 int pm_embbag_fwd_qrows(const pm_embbag_batch* op, int32_t bits, int32_t out_dtype, void* out, pm_stream_t stream);
@@ -597,9 +597,9 @@ int pm_embbag_qrows_plan(const pm_embbag_batch* op, int32_t bits, int32_t out_dt
  * unroll rounded down to 1 / 2 / 4 / 8), lds_borders, xcd_contiguous, grid.  Host only, launches nothing; validates the request as the
  * launching call does (`out` and out_row_stride of that call, and an out_dtype, are not part of it).
  * Replaces quantized::embedding_byte / embedding_4bit (behind torch.ao.nn.quantized.Embedding) and PoolingMode.NONE of fbgemm's
- * IntNBitTableBatchedEmbeddingBagsCodegen for INT8 / INT4 tables.  Left out: 2-bit tables, a padded row stride, pruned rows / index
- * remapping, padding_idx, per-position weights, a lane width per format, any backward (the tables are not trainable).  Tables of
- * differing format in one launch: PER-TABLE FORMATS below.
+ * IntNBitTableBatchedEmbeddingBagsCodegen for INT8 / INT4 tables.  Left out: 2-bit tables, a padded row stride, padding_idx,
+ * per-position weights, a lane width per format, any backward (the tables are not trainable).  Tables of
+ * differing format in one launch: PER-TABLE FORMATS below; pruned rows / index remapping: PRUNED TABLES below.
  * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these two finds out at symbol resolution.
  */
 int pm_embedding_gather_qrows(const pm_embbag_batch* op, int32_t bits, int32_t out_dtype, void* out, int64_t out_row_stride,
@@ -638,8 +638,8 @@ int pm_embedding_gather_qrows_plan(const pm_embbag_batch* op, int32_t bits, int6
  *                                             un-pooled  (a)  14.2 |  11.8   (b)  39.2 |  36.4   (c)  22.9 |  23.6
  * (a) is never slower than (b) or, beyond the 0.9 % spread, than (c); fp16 output and the lane layout: README.md, "Per-table formats".
  * Replaces the per-table weights_tys of fbgemm's IntNBitTableBatchedEmbeddingBagsCodegen for INT8 / INT4.  Left out: fp16 / bf16 / fp32
- * rows in the same launch (the format is an int per table so that 16 can follow), 2-bit tables, mean, padding_idx, pruned rows / index
- * remapping, a padded row stride, per-table lane sub-groups, any backward.
+ * rows in the same launch (the format is an int per table so that 16 can follow), 2-bit tables, mean, padding_idx, a padded row stride,
+ * per-table lane sub-groups, any backward (pruned rows / index remapping: PRUNED TABLES below).
  * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these four finds out at symbol resolution.
  */
 int pm_embbag_fwd_qrows_mixed(const pm_embbag_batch* op, const int32_t* table_bits, int32_t out_dtype, void* out, pm_stream_t stream);
@@ -647,6 +647,55 @@ int pm_embbag_qrows_mixed_plan(const pm_embbag_batch* op, int32_t out_dtype, int
 int pm_embedding_gather_qrows_mixed(const pm_embbag_batch* op, const int32_t* table_bits, int32_t out_dtype, void* out,
                                     int64_t out_row_stride, pm_stream_t stream);
 int pm_embedding_gather_qrows_mixed_plan(const pm_embbag_batch* op, int64_t out[8]);
+
+/*
+ * ROW-QUANTISED TABLES, PRUNED TABLES -- the two PER-TABLE FORMATS lookups over tables whose rows were pruned: a request addresses table
+ * t's LOGICAL rows and an int32 array per table maps each logical row to a physical row or to -1, "pruned" (fbgemm's
+ * index_remappings_array / index_remappings_array_offsets; torch's pruned_weights=True / compressed_indices_mapping).  remap is a DEVICE
+ * int32 array, the tables' remaps concatenated; remap_offsets a DEVICE int64 array of num_tables + 1 entries, non-decreasing.  Table t is
+ * pruned if and only if remap_offsets[t + 1] > remap_offsets[t]; its logical row r is physical row remap[remap_offsets[t] + r], a value in
+ * [-1, physical rows of t).  A table that is not pruned is the identity.  op->rows[t] is the table's INDEX SPACE (logical rows): the
+ * sanitiser reads it, the lookup kernels do not.  op->tables[t], table_bits and everything else are the per-table-format calls'; the
+ * arrays' contents are the caller's responsibility, as those of dims and table_bits are.  The un-pooled call reads 8 bytes at
+ * op->tables[0] for a pruned position (as for a position that is not written): tables[0] points at 8 readable bytes even if every row
+ * of table 0 is pruned.
+ * THE RULE: no new arithmetic.  Pooled: within a bag the lookups whose remap value is -1 are REMOVED -- index and weight alike, whatever
+ * the weight's value (a non-finite weight of a pruned lookup does not reach the bag) --, the others take their remap value, and the
+ * result is the rule of ROW-QUANTISED TABLES: acc = fmaf(sc, (float)code, fl32(acc + bi)) in index order from +0.0; a bag that is empty
+ * or all pruned gives +0.0; a 16-bit output is one rounding.  It is bit for bit what pm_embbag_fwd_qrows_mixed gives over the physical
+ * tables for the request with the pruned lookups deleted and the rest remapped -- and what torch's
+ * quantized::embedding_bag_{byte,4bit}_rowwise_offsets give with pruned_weights=True (tests/pruned_rules.py restates it,
+ * tests/test_pruned_host.py pins it to the operators).  Un-pooled: a position of the bag slice whose remap value is -1 receives +0.0 of
+ * out_dtype in the columns [0, dims[t]) of its row (fbgemm's nobag kernel writes zeros); every other position the un-pooled rule over the
+ * remapped row; positions outside the slice are not touched.
+ * One launch each (csrc/embbag_fwd_qpruned.hip, csrc/embedding_gather_qpruned.hip), kernels of their own beside the per-table-format
+ * ones -- also for tables of one format: pass table_bits.  Pooled: the workgroup remaps a staged tile's indices in LDS in place (one
+ * pass, the tile's 4-byte loads in flight together, one barrier; a table that is not pruned skips it), a tile beyond the index tile loads
+ * its U remap values back to back; a pruned lookup issues no row load.  Un-pooled: the remap load stands with the index load, in front of
+ * the row's address.  No atomics, no workspace, no allocation, stream-ordered.  The geometry is the per-table-format calls':
+ * pm_embbag_qrows_mixed_plan / pm_embedding_gather_qrows_mixed_plan report it for the same request (there is no plan call of its own).
+ * Refused on the host, before any HIP call: everything pm_embbag_fwd_qrows_mixed / pm_embedding_gather_qrows_mixed refuse (dims[t] % 8
+ * for every table included), then a NULL remap_offsets or a NULL remap (PM_ERR_INVALID): BOTH arrays are required -- a request without a
+ * pruned table goes to the per-table-format calls.  bag_count == 0 (and, un-pooled, num_indices == 0) is PM_OK without a launch.
+ * Measured (tools/pruned_probe.py, profiles/pruned_probe.json; half of every table's rows kept, tables alternately 8- and 4-bit; us per
+ * call, fp32 output, uniform | Zipf 1.05 indices; (a) this call, (b) the route there was before: one torch gather of the request through
+ * the remap with -1 redirected to an all-zero sentinel row, then the per-table-format call, (c) the per-table-format call over the
+ * physical tables with no remapping, for context):
+ *   16 x 10 M x 128, batch 8192, pooling 20   pooled     (a) 145.2 |  97.5   (b) 155.9 | 105.9   (c) 122.8 |  75.9
+ *                                             un-pooled  (a) 344.2 | 350.4   (b) 369.9 | 298.3   (c) 354.4 | 325.8
+ *   64 x 1 M x 64, batch 256, pooling 10      pooled     (a)  11.5 |  10.2   (b)  20.1 |  18.3   (c)  10.1 |  10.2
+ *                                             un-pooled  (a)  13.6 |  11.4   (b)  19.4 |  19.3   (c)  13.4 |  11.1
+ * (a) is not slower than (b) in seven of the eight cases (0.56-0.93 of its time); THE UN-POOLED CALL UNDER ZIPF INDICES AT THE LARGE SHAPE
+ * IS 17 % SLOWER THAN (b) (350.4 against 298.3 us; spread 0.1 %): README.md, "Pruned tables".
+ * Replaces index_remappings_array of fbgemm's IntNBitTableBatchedEmbeddingBagsCodegen for INT8 / INT4.  Left out: the hash-based remap
+ * (pruned_hash_remap), pruned fp32 / bf16 training tables, single-format 8-bit dims that are multiples of 4 but not 8, 2-bit tables, mean,
+ * padding_idx, any backward.
+ * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these two finds out at symbol resolution.
+ */
+int pm_embbag_fwd_qrows_pruned(const pm_embbag_batch* op, const int32_t* table_bits, const int32_t* remap, const int64_t* remap_offsets,
+                               int32_t out_dtype, void* out, pm_stream_t stream);
+int pm_embedding_gather_qrows_pruned(const pm_embbag_batch* op, const int32_t* table_bits, const int32_t* remap, const int64_t* remap_offsets,
+                                     int32_t out_dtype, void* out, int64_t out_row_stride, pm_stream_t stream);
 
 /*
  * SEQUENCE GRADIENTS -- the batched backward of the un-pooled lookup above: the gradient of pm_embedding_gather's rows applied to all

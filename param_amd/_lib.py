@@ -96,6 +96,8 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_qrows_mixed_plan",
     "pm_embedding_gather_qrows_mixed",
     "pm_embedding_gather_qrows_mixed_plan",
+    "pm_embbag_fwd_qrows_pruned",
+    "pm_embedding_gather_qrows_pruned",
 )
 
 # pm_embbag_plan (include/param_amd.h): the kinds, and the members of the two plans in the order the queries fill them
@@ -329,6 +331,11 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embedding_gather_qrows_mixed.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, vp, i64, vp]
     L.pm_embedding_gather_qrows_mixed_plan.restype = ctypes.c_int
     L.pm_embedding_gather_qrows_mixed_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), ctypes.POINTER(i64)]
+    # ... whose rows may be pruned: remap (a device int32 array) and remap_offsets (a device int64 [T + 1]) behind table_bits
+    L.pm_embbag_fwd_qrows_pruned.restype = ctypes.c_int
+    L.pm_embbag_fwd_qrows_pruned.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp, i32, vp, vp]
+    L.pm_embedding_gather_qrows_pruned.restype = ctypes.c_int
+    L.pm_embedding_gather_qrows_pruned.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp, i32, vp, i64, vp]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]

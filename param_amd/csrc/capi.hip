@@ -11,6 +11,12 @@ namespace pm {
 hipError_t launch_embbag_fwd_qrows(const KParams& p, int bits, int out_dtype, int max_dim, int unroll, hipStream_t stream);
 // ... of per-table format (embbag_fwd_qmixed.hip): table_bits = device int32 [T], 8 | 4; unroll: plan_qmixed's
 hipError_t launch_embbag_fwd_qmixed(const KParams& p, const int32_t* table_bits, int out_dtype, int max_dim, int unroll, hipStream_t stream);
+// ... whose rows may be pruned (embbag_fwd_qpruned.hip, embedding_gather_qpruned.hip): remap = device int32, remap_offsets = device int64
+// [T + 1]; the geometry is the per-table-format calls' (plan_qmixed, plan_gather_qmixed)
+hipError_t launch_embbag_fwd_qpruned(const KParams& p, const int32_t* table_bits, const int32_t* remap, const int64_t* remap_offsets, int out_dtype,
+                                     int max_dim, int unroll, hipStream_t stream);
+hipError_t launch_embedding_gather_qpruned(const KParams& p, const int32_t* table_bits, const int32_t* remap, const int64_t* remap_offsets, int out_dtype,
+                                           const GatherPlan& g, hipStream_t stream);
 }  // namespace pm
 
 namespace {
@@ -818,6 +824,56 @@ int pm_embedding_gather_qrows_mixed_plan(const pm_embbag_batch* op, int64_t out[
     const pm::GatherPlan g = pm::plan_gather_qmixed(*op, knobs);
     const int64_t v[8] = {g.vec, g.group_lanes, g.tile, g.col_passes, g.unroll, g.lds_borders, g.xcd_contiguous, g.grid};
     for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return PM_OK;
+}
+
+// ---- ... whose rows may be pruned (embbag_fwd_qpruned.hip, embedding_gather_qpruned.hip) -------------------------------------------------
+// what the two calls refuse on the host beyond the per-table-format calls' refusals (which come first, in their order): both remap
+// arrays are required -- a request without a pruned table goes to the per-table-format calls.  Their contents are device data: not read.
+static int qpruned_arrays(const int32_t* remap, const int64_t* remap_offsets) {
+    if (!remap_offsets) return fail(PM_ERR_INVALID, "remap_offsets is NULL (a device array of num_tables + 1 int64, non-decreasing)");
+    if (!remap)
+        return fail(PM_ERR_INVALID, "remap is NULL (a device int32 array, the tables' remaps concatenated; a request without a pruned table goes to "
+                                    "pm_embbag_fwd_qrows_mixed / pm_embedding_gather_qrows_mixed)");
+    return PM_OK;
+}
+
+int pm_embbag_fwd_qrows_pruned(const pm_embbag_batch* op, const int32_t* table_bits, const int32_t* remap, const int64_t* remap_offsets,
+                               int32_t out_dtype, void* out, pm_stream_t stream) {
+    const pm::PlanKnobs knobs = current_knobs();
+    pm::PlanShape shape;
+    int out_bytes = 0;
+    int rc = qmixed_request(op, table_bits, out_dtype, knobs, shape, out_bytes);
+    if (rc != PM_OK) return rc;
+    if ((rc = qpruned_arrays(remap, remap_offsets)) != PM_OK) return rc;
+    const pm::LaunchPlan plan = pm::plan_qmixed(*op, shape, knobs, out_bytes);      // (pm_embbag_qrows_mixed_plan reports it)
+    pm::KParams p;
+    fill_params(op, plan, p);
+    return padded_forward(p, out, out_dtype == PM_F32 ? 16 : 8, stream, [&](const pm::KParams& q, hipStream_t s) {
+        return pm::launch_embbag_fwd_qpruned(q, table_bits, remap, remap_offsets, out_dtype, op->max_dim, plan.unroll, s);
+    }, "pm_embbag_fwd_qrows_pruned launch");
+}
+
+int pm_embedding_gather_qrows_pruned(const pm_embbag_batch* op, const int32_t* table_bits, const int32_t* remap, const int64_t* remap_offsets,
+                                     int32_t out_dtype, void* out, int64_t out_row_stride, pm_stream_t stream) {
+    const pm::PlanKnobs knobs = current_knobs();
+    int rc = qmixed_gather_request(op, table_bits, out_dtype, knobs);
+    if (rc != PM_OK) return rc;
+    if (out_row_stride < op->max_dim || out_row_stride % 4 != 0)
+        return fail(PM_ERR_INVALID, "out_row_stride must be a multiple of 4 elements and at least max_dim");
+    if ((rc = qpruned_arrays(remap, remap_offsets)) != PM_OK) return rc;
+    if (op->num_indices == 0 || op->bag_count == 0) return PM_OK;      // nothing to write, whatever `out` is
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const uintptr_t align = out_dtype == PM_F32 ? 16 : 8;
+    if (reinterpret_cast<uintptr_t>(out) % align != 0) return fail(PM_ERR_INVALID, "out must be " + std::to_string(align) + "-byte aligned");
+    const pm::GatherPlan g = pm::plan_gather_qmixed(*op, knobs);          // (pm_embedding_gather_qrows_mixed_plan reports it)
+    if (g.grid > pm::kMaxGrid) return fail(PM_ERR_UNSUPPORTED, "grid too large");
+    pm::KParams p;
+    fill_params(op, pm::LaunchPlan{}, p);      // (the request; a gather has no bag tiling)
+    p.io = static_cast<float*>(out);           // (addressed in out_dtype's elements)
+    p.out_stride = out_row_stride;
+    const hipError_t h = pm::launch_embedding_gather_qpruned(p, table_bits, remap, remap_offsets, out_dtype, g, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embedding_gather_qrows_pruned launch");
     return PM_OK;
 }
 

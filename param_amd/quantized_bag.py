@@ -24,8 +24,14 @@ of zeros), rounded once for a 16-bit ``output_dtype``; bit for bit ``quantized::
 
 Forward only: the tables are buffers, nothing requires grad.  There is no CPU path.  Left out, on purpose: 2-bit tables, fp16 / bf16 /
 fp32 rows next to quantised ones, mean pooling, ``padding_idx``, per-position weights of the un-pooled lookup, mixed dims of the un-pooled lookup from Python (the C call serves them),
-pruned rows / index remapping, a padded row stride, per-table lane sub-groups for mixed dims, a lane width per format, the operator
-plug-in, any backward.
+a padded row stride, per-table lane sub-groups for mixed dims, a lane width per format, the operator plug-in, any backward.
+
+PRUNED TABLES (``index_remapping=``; ``csrc/embbag_fwd_qpruned.hip`` / ``csrc/embedding_gather_qpruned.hip`` through
+``pm_embbag_fwd_qrows_pruned`` / ``pm_embedding_gather_qrows_pruned``): a request addresses a table's LOGICAL rows and an int32 array per
+table maps each to a physical row or to -1, "pruned" (fbgemm's ``index_remappings_array``, torch's ``compressed_indices_mapping``).  A
+pooled bag drops its pruned lookups -- index and weight alike -- and pools the rest from their physical rows by the rule above; an
+un-pooled pruned position is a row of +0.0.  Left out there: fbgemm's hash-based remap, pruned fp32 / bf16 training tables, 8-bit dims
+that are multiples of 4 but not 8.
 """
 from __future__ import annotations
 
@@ -93,11 +99,57 @@ def _sum_only(mode, padding_idx, who: str) -> None:
         raise ValueError(f"{who}: padding_idx is not implemented for row-quantised tables")
 
 
+def _check_remaps(index_remapping, rows: Sequence[int], dims: Sequence[int]):
+    """``index_remapping`` of a constructor as a list of one ``None`` or 1-D tensor per table, or ``None`` for a module without a pruned
+    table (``None``, or every entry ``None``) -- after refusing what cannot be served, before anything is allocated: a wrong count, an
+    entry that is no 1-D int32 / int64 tensor, an empty one, ``logical_rows_t >= 2^31``, a value outside ``[-1, rows_t)`` (ONE host read
+    for all tables), dims that are no multiples of 8 (the pruned lookups are the per-table-format kernels' siblings: eight columns per lane)."""
+    if index_remapping is None:
+        return None
+    if isinstance(index_remapping, (bool, int, float, str, bytes, torch.Tensor)) or not isinstance(index_remapping, Sequence):
+        raise TypeError(f"index_remapping must be None or a sequence of one None or 1-D int32 / int64 tensor per table, got "
+                        f"{type(index_remapping).__name__}")
+    remaps = list(index_remapping)
+    if len(remaps) != len(rows):
+        raise ValueError(f"index_remapping names {len(remaps)} tables, rows and dims name {len(rows)}: one entry per table (None: not pruned)")
+    if all(r is None for r in remaps):
+        return None
+    for t, r in enumerate(remaps):
+        if r is None:
+            continue
+        if not isinstance(r, torch.Tensor) or r.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"index_remapping[{t}] must be None or an int32 / int64 tensor, got {getattr(r, 'dtype', type(r).__name__)}")
+        if r.dim() != 1 or r.numel() == 0:
+            raise ValueError(f"index_remapping[{t}] must be 1-D with one entry per logical row, at least one (None: the table is not pruned); "
+                             f"got shape {tuple(r.shape)}")
+        if r.numel() >= 2**31:
+            raise ValueError(f"index_remapping[{t}]: a table needs logical rows < 2^31, got {r.numel()}")
+    if any(d % 8 for d in dims):
+        raise ValueError(f"a pruned module needs every embedding dim a multiple of 8 (a lane holds eight columns), got {list(dims)}")
+    pruned = [t for t, r in enumerate(remaps) if r is not None]
+    lo_hi = torch.stack([torch.stack([remaps[t].min(), remaps[t].max()]).to(torch.int64).cpu() for t in pruned]).tolist()
+    for t, (lo, hi) in zip(pruned, lo_hi):
+        if lo < -1 or hi >= rows[t]:
+            raise ValueError(f"index_remapping[{t}]: values must lie in [-1, rows[{t}]) = [-1, {rows[t]}) (-1: the row is pruned), "
+                             f"got [{lo}, {hi}]")
+    return remaps
+
+
+def _keep_remap(keep: torch.Tensor, rows: int, t: int) -> torch.Tensor:
+    """the int32 remap of a bool ``keep`` mask over a source's rows: kept rows get consecutive physical rows in order, dropped rows -1"""
+    if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or tuple(keep.shape) != (rows,):
+        raise ValueError(f"keep[{t}] must be None or a bool tensor of shape ({rows},), got {getattr(keep, 'dtype', type(keep).__name__)} "
+                         f"{tuple(getattr(keep, 'shape', ()))}")
+    phys = torch.cumsum(keep.to(torch.int32), 0, dtype=torch.int32) - 1
+    return torch.where(keep, phys, torch.full_like(phys, -1))
+
+
 class _QTableSet(_TableSet):
     """:class:`_TableSet` over uint8 tables of quantised rows: ``dims`` are the LOGICAL column counts, ``dtype`` (what the request's
     ``weight_dtype`` says) is fp32 -- ``pm_embbag_fwd_qrows`` does not read it, the sanitiser reads rows, indices and offsets only."""
 
-    def __init__(self, tables: Sequence[torch.Tensor], dims: Sequence[int], layout: str, bitwidths: Optional[Sequence[int]] = None):
+    def __init__(self, tables: Sequence[torch.Tensor], dims: Sequence[int], layout: str, bitwidths: Optional[Sequence[int]] = None,
+                 index_rows: Optional[Sequence[int]] = None, ptrs: Optional[Sequence[int]] = None):
         t0 = tables[0]
         for t in tables:
             _require_device(t, "quantised table")
@@ -112,9 +164,11 @@ class _QTableSet(_TableSet):
         self._blk_cache: dict = {}
         self.T = len(tables)
         self.max_dim, self.min_dim, self.total_dim = max(self.dims), min(self.dims), sum(self.dims)
-        self.ptrs = [t.data_ptr() for t in tables]
+        # (ptrs: where the tables begin in their slab -- a pruned module's, whose tables may have no row: torch gives an empty view no address)
+        self.ptrs = [t.data_ptr() for t in tables] if ptrs is None else [int(p) for p in ptrs]
         self.d_ptrs = torch.tensor(self.ptrs, dtype=torch.int64, device=self.device)
-        self.d_rows = torch.tensor(self.rows, dtype=torch.int64, device=self.device)
+        # the request's rows: every table's INDEX SPACE, which the sanitiser reads -- of a pruned module the logical rows (index_rows)
+        self.d_rows = torch.tensor(self.rows if index_rows is None else list(index_rows), dtype=torch.int64, device=self.device)
         self.d_dims = torch.tensor(self.dims, dtype=torch.int32, device=self.device)
         # the tables' formats for the per-table-format calls (pm_embbag_fwd_qrows_mixed: table_bits), None for a uniform module
         self.d_bits = None if bitwidths is None else torch.tensor(list(bitwidths), dtype=torch.int32, device=self.device)
@@ -153,13 +207,23 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     ``[N, D]``, one dequantised row per lookup position (one common embedding dim); ``sequence_plan(...)`` its launch geometry.
     ``bounds_check_mode``: see :class:`_BoundsChecked` -- the sanitiser reads rows, indices and offsets, never the tables.
 
+    ``index_remapping``: ``None``, or a sequence of one entry per table, each ``None`` (the table is not pruned) or a 1-D int32 / int64
+    tensor of ``logical_rows_t`` values in ``[-1, rows_t)``: the physical row of every logical row, -1 for a pruned one.  ``rows`` stays
+    the PHYSICAL row count (the storage, what ``table(t)`` holds); ``logical_rows`` is every table's index space, ``index_remapping(t)``
+    table ``t``'s remap (int32) or ``None``, ``pruned`` whether any table has one.  The remaps live in the buffers ``index_remap`` and
+    ``index_remap_offsets``, registered only for a pruned module (``state_dict`` round-trips them; loaded values are the caller's
+    responsibility).  A pruned module needs every dim a multiple of 8 and always launches ``pm_embbag_fwd_qrows_pruned`` /
+    ``pm_embedding_gather_qrows_pruned`` (one launch, tables of one format included); ``plan`` / ``sequence_plan`` report that launch's
+    geometry.  ``bounds_check_mode`` and ``sanitize_`` check indices against ``logical_rows``, before the remap: an index repaired to 0
+    is remapped like any other.  ``from_float(source, bitwidth, keep=masks)`` builds such a module from bool masks over the source's rows.
+
     No gradients: the tables are a buffer (``state_dict`` round-trips the bytes), the output never requires grad.  ValueError before
     anything is allocated: ``bitwidth`` not 8 or 4, dims breaking the column rules, ``layout="blocked"``, mean pooling, ``padding_idx``.
     At call time: tensors that are not on a ROCm device raise RuntimeError (no CPU fallback), a floating-point index tensor TypeError.
     """
 
     def __init__(self, rows: Sequence[int], dims, bitwidth, device="cuda", layout: str = "bd", output_dtype=None,
-                 bounds_check_mode="none", pooling_mode="sum", padding_idx=None):
+                 bounds_check_mode="none", pooling_mode="sum", padding_idx=None, index_remapping=None):
         super().__init__()
         self._init_shared(bounds_check_mode, output_dtype)
         rows = [int(r) for r in rows]
@@ -170,16 +234,32 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         _sum_only(pooling_mode, padding_idx, type(self).__name__)
         if any(r < 0 or r >= 2**31 for r in rows):
             raise ValueError("every table needs 0 <= rows < 2^31")
+        remaps = _check_remaps(index_remapping, rows, dims)
         self.padding_idx = None
         self.rows, self.dims, self.bitwidth, self.bitwidths, self.layout = rows, dims, bitwidth, bitwidths, layout
+        self.pruned = remaps is not None
+        self.logical_rows = list(rows) if remaps is None else [r if m is None else int(m.numel()) for r, m in zip(rows, remaps)]
         self._row_bytes = [quant.host_row_bytes(d, b) for d, b in zip(dims, bitwidths)]
         # table starts padded to 256 B (rows themselves are 4-byte aligned and no better)
         starts, cur = [], 0
         for r, rb in zip(rows, self._row_bytes):
             starts.append(cur)
             cur += (r * rb + 255) // 256 * 256
+        if self.pruned:
+            cur = max(cur, 256)     # (the un-pooled pruned lookup reads table 0's first 8 bytes for a pruned position, whatever rows[0] is)
         self._starts = starts
         self.register_buffer("weights", torch.zeros(cur, dtype=torch.uint8, device=device))
+        if self.pruned:
+            # the remaps, concatenated, and where each table's begins (pm_embbag_fwd_qrows_pruned: remap, remap_offsets): buffers of a
+            # pruned module only -- the state_dict keys of a module without a pruned table are what they were
+            ends, cat = [0], []
+            for m in remaps:
+                ends.append(ends[-1] + (0 if m is None else int(m.numel())))
+                if m is not None:
+                    cat.append(m.detach().to(device=device, dtype=torch.int32))
+            self.register_buffer("index_remap", torch.cat(cat))
+            self.register_buffer("index_remap_offsets", torch.tensor(ends, dtype=torch.int64, device=device))
+            self._remap_ends = ends
         self._ts: Optional[_QTableSet] = None
 
     _TABLES = "weights"
@@ -188,6 +268,13 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     def table(self, t: int) -> torch.Tensor:
         s, n = self._starts[t], self.rows[t] * self._row_bytes[t]
         return self.weights[s:s + n].view(self.rows[t], self._row_bytes[t])
+
+    def index_remapping(self, t: int) -> Optional[torch.Tensor]:
+        """table ``t``'s remap -- int32 ``[logical_rows[t]]``, a view of the ``index_remap`` buffer: the physical row of every logical
+        row, -1 for a pruned one -- or ``None`` for a table that is not pruned"""
+        if not self.pruned or self._remap_ends[t + 1] == self._remap_ends[t]:
+            return None
+        return self.index_remap[self._remap_ends[t]:self._remap_ends[t + 1]]
 
     def quantize_from_(self, t: int, source: torch.Tensor) -> None:
         """fill table ``t`` from the fp32 tensor ``source`` ``[rows_t, D_t]`` on the GPU with the ``quantize_rows`` kernel (its limits: fp32
@@ -206,9 +293,11 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         return quant.dequantize_rows(self.table(t), self.dims[t], self.bitwidths[t])
 
     @classmethod
-    def from_float(cls, source, bitwidth, **kw):
+    def from_float(cls, source, bitwidth, keep=None, **kw):
         """quantise a :class:`BatchedEmbeddingBagMI355` sum module (16-bit tables are widened first) or a sequence of fp32 ``[rows, D]``
-        tensors; ``bitwidth``: an int, or one per table; keywords go to the constructor (``device``, ``layout`` default to the source's)"""
+        tensors; ``bitwidth``: an int, or one per table; keywords go to the constructor (``device``, ``layout`` default to the source's).
+        ``keep``: ``None``, or per table ``None`` or a bool mask over the source's rows -- only the kept rows are quantised, into
+        consecutive physical rows in order, and the module is a pruned one whose remap sends the dropped rows to -1."""
         if isinstance(source, BatchedEmbeddingBagMI355):
             _sum_only(source.pooling_mode, source.padding_idx, "from_float")
             tables = [source.table(t).float() for t in range(len(source.rows))]
@@ -218,16 +307,35 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             if not tables or any(not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32 for x in tables):
                 raise TypeError("from_float takes a BatchedEmbeddingBagMI355 or a sequence of 2-D float32 tensors")
         kw.setdefault("device", tables[0].device)
+        if keep is not None:
+            if isinstance(keep, torch.Tensor) or not isinstance(keep, Sequence) or len(keep) != len(tables):
+                raise ValueError(f"keep must be None or a sequence of one None or bool mask per table ({len(tables)})")
+            remaps = [None if k is None else _keep_remap(k, int(x.shape[0]), t) for t, (k, x) in enumerate(zip(keep, tables))]
+            tables = [x if k is None else x[k.to(x.device)] for k, x in zip(keep, tables)]
+            kw["index_remapping"] = remaps
         m = cls([int(x.shape[0]) for x in tables], [int(x.shape[1]) for x in tables], bitwidth, **kw)
         for t, x in enumerate(tables):
             m.quantize_from_(t, x.to(m.weights.device))
         return m
 
     def _tables(self) -> _QTableSet:
+        if self.pruned:
+            # a pruned module always launches the per-table-format kernels' siblings: it carries table_bits, its index space, and the
+            # tables' addresses in the slab (the un-pooled lookup reads 8 bytes at tables[0] even if table 0 has no row)
+            base = self.weights.data_ptr()
+            if self._ts is None or self._ts.ptrs[0] != base + self._starts[0]:
+                self._ts = _QTableSet([self.table(t) for t in range(len(self.rows))], self.dims, self.layout, self.bitwidths, self.logical_rows,
+                                      [base + s for s in self._starts])
+            return self._ts
         if self._ts is None or self._ts.ptrs[0] != self.table(0).data_ptr():
             self._ts = _QTableSet([self.table(t) for t in range(len(self.rows))], self.dims, self.layout,
                                   None if self.bitwidth is not None else self.bitwidths)
         return self._ts
+
+    def _remap_ptrs(self):
+        _require_device(self.index_remap, f"{type(self).__name__}.index_remap")
+        _require_device(self.index_remap_offsets, f"{type(self).__name__}.index_remap_offsets")
+        return self.index_remap.data_ptr(), self.index_remap_offsets.data_ptr()
 
     _batch_of = BatchedEmbeddingBagMI355._batch_of
 
@@ -251,7 +359,11 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             out = torch.empty(shape, dtype=odt, device=ts.device)
         elif out.dtype != odt or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != ts.device:
             raise ValueError(f"out must be a contiguous {str(odt).replace('torch.', '')} tensor of shape {shape} on {ts.device}")
-        if self.bitwidth is not None:
+        if self.pruned:
+            remap, remap_offsets = self._remap_ptrs()
+            rc = _lib.load().pm_embbag_fwd_qrows_pruned(ctypes.byref(op), ts.d_bits.data_ptr(), remap, remap_offsets, _WDTYPE[odt],
+                                                        out.data_ptr(), _stream_ptr())
+        elif self.bitwidth is not None:
             rc = _lib.load().pm_embbag_fwd_qrows(ctypes.byref(op), self.bitwidth, _WDTYPE[odt], out.data_ptr(), _stream_ptr())
         else:
             rc = _lib.load().pm_embbag_fwd_qrows_mixed(ctypes.byref(op), ts.d_bits.data_ptr(), _WDTYPE[odt], out.data_ptr(), _stream_ptr())
@@ -264,9 +376,10 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
 
     def plan(self, indices, offsets, per_sample_weights=None, bag_begin=0, bag_count=None, batch: Optional[int] = None) -> dict:
         """the launch geometry ``lookup`` would use for this request under the knobs as they stand (``_lib.PLAN_FIELDS`` by name;
-        ``pm_embbag_qrows_plan``, or ``pm_embbag_qrows_mixed_plan`` for a module of per-table formats)"""
+        ``pm_embbag_qrows_plan``, or ``pm_embbag_qrows_mixed_plan`` for a module of per-table formats and for a pruned one, whose
+        launch has that geometry)"""
         _, _, op = self._request(indices, offsets, per_sample_weights, bag_begin, bag_count, batch, False)
-        if self.bitwidth is None:
+        if self.bitwidth is None or self.pruned:
             return _lib.embbag_qrows_mixed_plan(op, _WDTYPE[self.output_dtype])
         return _lib.embbag_qrows_plan(op, self.bitwidth, _WDTYPE[self.output_dtype])
 
@@ -293,7 +406,11 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             whole = bag_begin == 0 and bag_count in (None, B)
             out = (torch.empty if whole else torch.zeros)((n, D), dtype=odt, device=ts.device)
         if n:
-            if self.bitwidth is not None:
+            if self.pruned:
+                remap, remap_offsets = self._remap_ptrs()
+                rc = _lib.load().pm_embedding_gather_qrows_pruned(ctypes.byref(op), ts.d_bits.data_ptr(), remap, remap_offsets, _WDTYPE[odt],
+                                                                  out.data_ptr(), D, _stream_ptr())
+            elif self.bitwidth is not None:
                 rc = _lib.load().pm_embedding_gather_qrows(ctypes.byref(op), self.bitwidth, _WDTYPE[odt], out.data_ptr(), D, _stream_ptr())
             else:
                 rc = _lib.load().pm_embedding_gather_qrows_mixed(ctypes.byref(op), ts.d_bits.data_ptr(), _WDTYPE[odt], out.data_ptr(), D,
@@ -304,10 +421,10 @@ class QuantizedBatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
 
     def sequence_plan(self, indices, offsets, batch: Optional[int] = None, bag_begin=0, bag_count=None) -> dict:
         """the launch geometry ``lookup_sequence`` would use for this request under the knobs as they stand (``_lib.GATHER_PLAN_FIELDS``
-        by name; ``pm_embedding_gather_qrows_plan`` -- a module of per-table formats: ``pm_embedding_gather_qrows_mixed_plan`` --,
-        nothing is launched)"""
+        by name; ``pm_embedding_gather_qrows_plan`` -- a module of per-table formats or a pruned one:
+        ``pm_embedding_gather_qrows_mixed_plan`` --, nothing is launched)"""
         _, _, op = self._sequence_request(indices, offsets, batch, bag_begin, bag_count, False)
-        if self.bitwidth is None:
+        if self.bitwidth is None or self.pruned:
             return _lib.embedding_gather_qrows_mixed_plan(op)
         return _lib.embedding_gather_qrows_plan(op, self.bitwidth)
 
@@ -335,14 +452,15 @@ class QuantizedEmbeddingBagMI355(QuantizedBatchedEmbeddingBagMI355):
     batched module's; ``mode`` other than ``"sum"`` and ``padding_idx`` raise ValueError."""
 
     def __init__(self, num_embeddings: int, embedding_dim: int, bitwidth: int = 8, device="cuda", output_dtype=None,
-                 bounds_check_mode="none", mode="sum", padding_idx=None, weight: Optional[torch.Tensor] = None):
+                 bounds_check_mode="none", mode="sum", padding_idx=None, weight: Optional[torch.Tensor] = None, index_remapping=None):
         if weight is not None:
             _check_spec(bitwidth, [int(embedding_dim)], "bd")
             want = (int(num_embeddings), quant.host_row_bytes(int(embedding_dim), bitwidth))
             if weight.dtype != torch.uint8 or tuple(weight.shape) != want:
                 raise ValueError(f"weight must be the packed uint8 rows {want}, got {weight.dtype} {tuple(weight.shape)}")
         super().__init__([num_embeddings], [embedding_dim], bitwidth, device=device, layout="bd", output_dtype=output_dtype,
-                         bounds_check_mode=bounds_check_mode, pooling_mode=mode, padding_idx=padding_idx)
+                         bounds_check_mode=bounds_check_mode, pooling_mode=mode, padding_idx=padding_idx,
+                         index_remapping=None if index_remapping is None else [index_remapping])
         self.num_embeddings, self.embedding_dim = int(num_embeddings), int(embedding_dim)
         self._off2d: dict = {}
         if weight is not None:
@@ -351,12 +469,15 @@ class QuantizedEmbeddingBagMI355(QuantizedBatchedEmbeddingBagMI355):
     _bags_2d = EmbeddingBagMI355._bags_2d
 
     @classmethod
-    def from_float(cls, module, bitwidth: int = 8, **kw):
+    def from_float(cls, module, bitwidth: int = 8, keep=None, **kw):
         if not isinstance(module, (EmbeddingBagMI355, nn.EmbeddingBag)):
             raise TypeError("from_float takes an EmbeddingBagMI355 or a torch.nn.EmbeddingBag")
         _sum_only(module.mode, module.padding_idx, "from_float")
         w = module.weight.detach()
         kw.setdefault("device", w.device if w.is_cuda else "cuda")
+        if keep is not None:        # a bool mask over the source's rows: only the kept rows are stored, the rest is pruned
+            kw["index_remapping"] = _keep_remap(keep, int(w.shape[0]), 0)
+            w = w[keep.to(w.device)]
         m = cls(int(w.shape[0]), int(w.shape[1]), bitwidth, **kw)
         m.quantize_from_(0, w.to(device=m.weights.device, dtype=torch.float32))
         return m
@@ -389,14 +510,14 @@ class QuantizedEmbeddingMI355(QuantizedBatchedEmbeddingBagMI355):
     that are not on a ROCm device RuntimeError (no CPU fallback)."""
 
     def __init__(self, num_embeddings: int, embedding_dim: int, bitwidth: int = 8, device="cuda", output_dtype=None,
-                 bounds_check_mode="none", weight: Optional[torch.Tensor] = None):
+                 bounds_check_mode="none", weight: Optional[torch.Tensor] = None, index_remapping=None):
         if weight is not None:
             _check_spec(bitwidth, [int(embedding_dim)], "bd")
             want = (int(num_embeddings), quant.host_row_bytes(int(embedding_dim), bitwidth))
             if weight.dtype != torch.uint8 or tuple(weight.shape) != want:
                 raise ValueError(f"weight must be the packed uint8 rows {want}, got {weight.dtype} {tuple(weight.shape)}")
         super().__init__([num_embeddings], [embedding_dim], bitwidth, device=device, layout="bd", output_dtype=output_dtype,
-                         bounds_check_mode=bounds_check_mode)
+                         bounds_check_mode=bounds_check_mode, index_remapping=None if index_remapping is None else [index_remapping])
         self.num_embeddings, self.embedding_dim = int(num_embeddings), int(embedding_dim)
         self._off0: dict = {}        # the request's offsets [0], one per (dtype, device)
         if weight is not None:
@@ -405,13 +526,16 @@ class QuantizedEmbeddingMI355(QuantizedBatchedEmbeddingBagMI355):
     _offsets0 = EmbeddingMI355._offsets0
 
     @classmethod
-    def from_float(cls, module, bitwidth: int = 8, **kw):
+    def from_float(cls, module, bitwidth: int = 8, keep=None, **kw):
         if not isinstance(module, (EmbeddingMI355, nn.Embedding)):
             raise TypeError("from_float takes an EmbeddingMI355 or a torch.nn.Embedding")
         if getattr(module, "max_norm", None) is not None:
             raise ValueError("from_float: max_norm is not implemented (the rows would be renormalised at lookup time)")
         w = module.weight.detach()
         kw.setdefault("device", w.device if w.is_cuda else "cuda")
+        if keep is not None:        # a bool mask over the source's rows: only the kept rows are stored, the rest is pruned
+            kw["index_remapping"] = _keep_remap(keep, int(w.shape[0]), 0)
+            w = w[keep.to(w.device)]
         m = cls(int(w.shape[0]), int(w.shape[1]), bitwidth, **kw)
         m.quantize_from_(0, w.to(device=m.weights.device, dtype=torch.float32))
         return m
