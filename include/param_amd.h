@@ -501,6 +501,52 @@ int pm_embbag_grad_widen(const pm_embbag_batch* op, const int64_t* padding_idx, 
                          float* grad32, pm_stream_t stream);
 
 /*
+ * MAX POOLING -- torch's nn.EmbeddingBag(mode="max") rule, forward, arg-max and gradient.  padding_idx is the device array of PADDING
+ * above, or NULL when no table has a padding row.  The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client
+ * that needs the two calls finds out at symbol resolution.  tests/max_rules.py restates the rule in numpy.
+ *
+ * FORWARD   A bag's lookups that equal its table's padding index are removed first (after pm_embbag_bounds_check has repaired the
+ *           request, where the caller runs it).  Per column c, over the remaining lookups r_0, r_1, ... in index order: the first sets
+ *           cur = w[r_0, c], whatever it holds; every later one replaces it iff w[r_j, c] > cur -- an ordered, strict IEEE comparison,
+ *           a compare-and-select and never fmaxf.  So a NaN in the first kept lookup stays; a NaN anywhere later never enters; of
+ *           equal values the first wins (-0.0 followed by +0.0 stays -0.0); a bag of negative rows gives a negative maximum -- nothing
+ *           is seeded with 0.0.  A bag without kept lookups (empty, or padding only) gives +0.0.  16-bit rows are widened exactly and
+ *           compared in fp32; the widening is monotone, so the result is a stored value.  out_dtype PM_BF16 / PM_F16: ONE rounding of
+ *           that fp32 result, in registers, as for pm_embbag_fwd_out16.  On fp32, bf16 and fp16 tables this is
+ *           torch.nn.functional.embedding_bag(..., mode="max") on the CPU bit for bit (fp32 output of a 16-bit table: torch's widened).
+ * ARG-MAX   max_indices(t, b)[c] = the row index that supplied cur, int32, at the element offset of out(t, b)[c] (out_offsets[t] + b *
+ *           out_stride + c, counted in int32 elements); -1 for a bag without kept lookups (torch writes 0 there and never reads it).
+ * BACKWARD  grad(t, b)[c] goes to row max_indices(t, b)[c] of table t; a row that a bag looks up twice receives it once.  Implemented
+ *           as an expansion to a sequence gradient: g_seq[j, c] = grad(t, bag(j))[c] if j is the first position of its bag with
+ *           indices[j] == max_indices(t, bag(j))[c], else +0.0; then the sequence backward (pm_embseq_*, below) of the same request
+ *           runs unchanged on g_seq.  A table row therefore accumulates its bags' contributions in ascending bag order, which is
+ *           torch's _embedding_bag_dense_backward order for max: bit-identical to torch's CPU autograd wherever a row has at most 256
+ *           lookups in the request; above that the sequence route's ordered chunk partials apply.  A stated consequence: a looked-up
+ *           row that wins no column receives additions of alpha * 0.0 -- nothing in a zeroed dense-gradient buffer, but a scatter-add
+ *           with a positive alpha turns a stored -0.0 of such a row into +0.0.
+ *
+ * pm_embbag_fwd_max      a sibling of the padded forward's kernel (csrc/embbag_fwd_max.hip): same tiling, staging with padding
+ *                        compaction, layouts, bag slices.  out is out_dtype (PM_F32 | PM_BF16 | PM_F16), addressed in its own elements;
+ *                        max_indices NULL: not written (inference: nothing extra is stored).  Only the bags inside [bag_begin,
+ *                        bag_begin + bag_count) are written, in out and in max_indices.
+ * pm_embbag_max_grad     the expansion (csrc/embbag_max_grad.hip): grad (grad_dtype PM_F32 | PM_BF16 | PM_F16, widened exactly) and
+ *                        max_indices are addressed like out, each in its own elements; g_seq is fp32, row j at g_seq + j *
+ *                        g_seq_row_stride.  Only positions of bags inside the slice are written.  One launch, any number of tables:
+ *                        a lane group per bag, one 16-byte non-temporal store per lane and position.  Pass g_seq (advanced to a table
+ *                        range's first position for requests of more than 1024 tables) to pm_embseq_bwd_fused / pm_embseq_bwd_sorted.
+ * Both refuse, before any HIP call: what pm_embbag_fwd refuses; per_sample_weights (PM_ERR_UNSUPPORTED: max is unweighted); blocked
+ * layouts (PM_ERR_UNSUPPORTED); an unknown dtype; a NULL out / grad / max_indices (of the gradient call) / g_seq; out or grad not
+ * 16-byte aligned (8-byte for a 16-bit dtype), max_indices or g_seq not 16-byte aligned (PM_ERR_INVALID).  pm_embbag_max_grad also
+ * refuses mixed dims (min_dim given and != max_dim, PM_ERR_UNSUPPORTED: the sequence route needs one dim) and a g_seq_row_stride below
+ * max_dim or not a multiple of 4.  An empty request (bag_count == 0; for the gradient also num_indices == 0) is PM_OK without a launch.
+ * Replaces the mode="max" branches of aten::_embedding_bag and _embedding_bag_dense_backward.
+ */
+int pm_embbag_fwd_max(const pm_embbag_batch* op, const int64_t* padding_idx, int32_t out_dtype, void* out, int32_t* max_indices,
+                      pm_stream_t stream);
+int pm_embbag_max_grad(const pm_embbag_batch* op, const void* grad, int32_t grad_dtype, const int32_t* max_indices, float* g_seq,
+                       int64_t g_seq_row_stride, pm_stream_t stream);
+
+/*
  * UN-POOLED LOOKUPS -- torch's nn.Embedding rule (fbgemm TBE: PoolingMode.NONE, sequence embeddings): one output row per lookup.  For
  * every lookup position j in [0, num_indices) that belongs to a bag inside [bag_begin, bag_begin + bag_count) of its table t
  *     out[j * out_row_stride + c] = conv(table_t[indices[j], c])      for c < dims[t]

@@ -3,7 +3,8 @@
 Layout (only what the hot path needs):
   csrc/              hand-written HIP kernels + the C ABI (include/param_amd.h) -> libparam_amd.so
   _lib.py            ctypes binding (no fallback: raises if the library is missing)
-  embedding_bag.py   EmbeddingBagMI355 / BatchedEmbeddingBagMI355 (nn.EmbeddingBag / TBE surface), EmbeddingMI355 (nn.Embedding)
+  embedding_bag.py   EmbeddingBagMI355 / BatchedEmbeddingBagMI355 (nn.EmbeddingBag / TBE surface), EmbeddingMI355 (nn.Embedding),
+                     MaxEmbeddingBagMI355 / MaxBatchedEmbeddingBagMI355 (max pooling)
   quantized_bag.py   QuantizedBatchedEmbeddingBagMI355 / QuantizedEmbeddingBagMI355 / QuantizedEmbeddingMI355: pooled and un-pooled
                      lookups over 8- / 4-bit row-quantised tables
   indices.py         uniform / Zipf index generation (reference init_indices + a scalable form)
@@ -15,6 +16,8 @@ from .embedding_bag import (  # noqa: F401
     BatchedEmbeddingBagMI355,
     EmbeddingBagMI355,
     EmbeddingMI355,
+    MaxBatchedEmbeddingBagMI355,
+    MaxEmbeddingBagMI355,
     check_request,
     fill_random_,
 )

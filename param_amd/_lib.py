@@ -80,6 +80,8 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_mean_grad",
     "pm_embbag_fwd_out16",
     "pm_embbag_grad_widen",
+    "pm_embbag_fwd_max",
+    "pm_embbag_max_grad",
     "pm_embedding_gather",
     "pm_embseq_sort_indices",
     "pm_embseq_bwd_sorted",
@@ -295,6 +297,12 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embbag_fwd_out16.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, i32, vp, vp]
     L.pm_embbag_grad_widen.restype = ctypes.c_int
     L.pm_embbag_grad_widen.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, i32, vp, vp, vp]
+    # max pooling: (op, pad array or NULL, out dtype, out, max_indices or NULL, stream) and (op, grad, grad dtype, max_indices, g_seq,
+    # g_seq_row_stride, stream)
+    L.pm_embbag_fwd_max.restype = ctypes.c_int
+    L.pm_embbag_fwd_max.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, vp, vp, vp]
+    L.pm_embbag_max_grad.restype = ctypes.c_int
+    L.pm_embbag_max_grad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, vp, vp, i64, vp]
     # un-pooled rows: (op, PM_F32 | PM_BF16 | PM_F16, out, out_row_stride, stream)
     L.pm_embedding_gather.restype = ctypes.c_int
     L.pm_embedding_gather.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, vp, i64, vp]

@@ -621,6 +621,50 @@ int pm_embbag_grad_widen(const pm_embbag_batch* op, const int64_t* padding_idx, 
     return PM_OK;
 }
 
+// ---- max pooling (embbag_fwd_max.hip, embbag_max_grad.hip) -----------------------------------------------------------------------
+constexpr Subject kMaxPooling{"max pooling", "does"};
+// what the two max calls refuse of their own, behind make_params; what: the dtype argument's name
+static int max_args_ok(const pm_embbag_batch* op, int32_t dtype, const char* what) {
+    int rc = blocked_refused(op, kMaxPooling);
+    if (rc != PM_OK) return rc;
+    if (op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "max pooling is unweighted: per_sample_weights must be NULL");
+    if (dtype != PM_F32 && dtype != PM_BF16 && dtype != PM_F16) return fail(PM_ERR_INVALID, std::string(what) + " must be PM_F32, PM_BF16 or PM_F16");
+    return PM_OK;
+}
+
+int pm_embbag_fwd_max(const pm_embbag_batch* op, const int64_t* padding_idx, int32_t out_dtype, void* out, int32_t* max_indices,
+                      pm_stream_t stream) {
+    pm::KParams p;
+    int rc = make_params(op, op ? op->weight_dtype : -1, p, out_dtype == PM_F32 ? PlanKind::padded : PlanKind::padded16);
+    if (rc != PM_OK) return rc;
+    if ((rc = max_args_ok(op, out_dtype, "out_dtype")) != PM_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(max_indices) % 16 != 0) return fail(PM_ERR_INVALID, "max_indices must be 16-byte aligned");
+    return padded_forward(p, out, out_dtype == PM_F32 ? 16 : 8, stream, [&](const pm::KParams& q, hipStream_t s) {
+        return pm::launch_embbag_fwd_max(q, op->weight_dtype, op->max_dim, padding_idx, out_dtype, max_indices, s);
+    }, "pm_embbag_fwd_max launch");
+}
+
+int pm_embbag_max_grad(const pm_embbag_batch* op, const void* grad, int32_t grad_dtype, const int32_t* max_indices, float* g_seq,
+                       int64_t g_seq_row_stride, pm_stream_t stream) {
+    pm::KParams p;
+    int rc = make_params(op, op ? op->weight_dtype : -1, p);
+    if (rc != PM_OK) return rc;
+    if ((rc = max_args_ok(op, grad_dtype, "grad_dtype")) != PM_OK) return rc;
+    if (op->min_dim != 0 && op->min_dim != op->max_dim)
+        return fail(PM_ERR_UNSUPPORTED, "the max gradient needs one common embedding dim (min_dim == max_dim): the sequence backward that "
+                                        "applies g_seq takes one");
+    if (g_seq_row_stride < op->max_dim || g_seq_row_stride % 4 != 0)
+        return fail(PM_ERR_INVALID, "g_seq_row_stride must be a multiple of 4 elements and at least max_dim");
+    if (p.bag_count == 0 || p.N == 0) return PM_OK;
+    if (!grad || !max_indices || !g_seq) return fail(PM_ERR_INVALID, "grad / max_indices / g_seq is NULL");
+    if (reinterpret_cast<uintptr_t>(grad) % (grad_dtype == PM_F32 ? 16 : 8) != 0 || reinterpret_cast<uintptr_t>(max_indices) % 16 != 0 ||
+        reinterpret_cast<uintptr_t>(g_seq) % 16 != 0)
+        return fail(PM_ERR_INVALID, "grad must be 16-byte aligned (8-byte for a 16-bit grad_dtype), max_indices and g_seq 16-byte aligned");
+    const hipError_t h = pm::launch_max_grad(p, op->max_dim, grad, grad_dtype, max_indices, g_seq, g_seq_row_stride, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_max_grad launch");
+    return PM_OK;
+}
+
 // ---- row-quantised tables (embbag_fwd_qrows.hip) ---------------------------------------------------------------------------------------
 // what the lookup and its plan query refuse on the host, in one order: the request for the element type whose columns per lane the
 // format has (qrows_elem_dtype: the column rules D % 4 / D % 8), then the call's own arguments.  out_bytes: of one output element.

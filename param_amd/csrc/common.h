@@ -245,6 +245,13 @@ hipError_t launch_embbag_fwd_out16_bf16(const KParams& p, int max_dim, const int
 hipError_t launch_embbag_fwd_out16_f16(const KParams& p, int max_dim, const int64_t* pad_idx, bool mean, int out_dtype, hipStream_t stream);
 hipError_t launch_grad_widen(const KParams& p, int max_dim, const int64_t* pad_idx, bool mean, int grad_dtype, const void* grad16,
                              float* grad32, hipStream_t stream);
+// max pooling (embbag_fwd_max.hip, embbag_max_grad.hip): p = the padded plan for out_dtype's element, p.io = out of out_dtype (PM_F32 |
+// PM_BF16 | PM_F16); pad_idx may be NULL; max_indices (int32, addressed like out) NULL = not written.  The expansion: grad of
+// grad_dtype and max_indices addressed like out, g_seq fp32 [N, g_stride]
+hipError_t launch_embbag_fwd_max(const KParams& p, int weight_dtype, int max_dim, const int64_t* pad_idx, int out_dtype, int32_t* max_indices,
+                                 hipStream_t stream);
+hipError_t launch_max_grad(const KParams& p, int max_dim, const void* grad, int grad_dtype, const int32_t* max_indices, float* g_seq,
+                           int64_t g_stride, hipStream_t stream);
 // un-pooled rows (embedding_gather.hip): p.io = out of out_dtype (PM_F32 | PM_BF16 | PM_F16), p.out_stride = its row stride in elements
 hipError_t launch_embedding_gather(const KParams& p, int weight_dtype, int out_dtype, const GatherPlan& g, hipStream_t stream);
 // ... over 8- / 4-bit row-quantised tables (embedding_gather_qrows.hip): bits 8 | 4; g: plan_gather_qrows'

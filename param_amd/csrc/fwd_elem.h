@@ -1,6 +1,6 @@
 // param_amd/csrc/fwd_elem.h -- the device building blocks of the forward kernel families (embbag_fwd.hip, embbag_fwd_split.hip,
-// embbag_fwd_pad_kernel.inc), of the per_sample_weights gradient (embbag_psw_grad.hip) and of the un-pooled row gather
-// (embedding_gather.hip): element types, the 16-bit output elements, row loads, the accumulate step and the burst of a tile's rows.  embbag_fwd.hip still spells the accumulate step out and says why at the
+// embbag_fwd_pad_kernel.inc, embbag_fwd_max.hip), of the per_sample_weights gradient (embbag_psw_grad.hip) and of the un-pooled row gather
+// (embedding_gather.hip): element types, the 16-bit output elements, row loads, the accumulate step, the max step and the burst of a tile's rows.  embbag_fwd.hip still spells the accumulate step out and says why at the
 // spot: the compiler's output for these kernels moves with WHERE an expression is written, and a call that took a measured
 // kernel off its code, or an instance to another waves-per-SIMD step, was not made (profiles/fwd_refactor_isa.md).  gfx950 only.
 #pragma once
@@ -115,6 +115,23 @@ __device__ __forceinline__ void accumulate(float (&acc)[Elem<WT>::kVec], const u
     Elem<WT>::widen(raw, f);
 #pragma unroll
     for (int k = 0; k < VEC; ++k) acc[k] = WEIGHTED ? fmaf(w, f[k], acc[k]) : acc[k] + f[k];
+}
+
+// one lookup joins a MAXIMUM (embbag_fwd_max.hip; include/param_amd.h, MAX POOLING): the row's 16 bytes widened to fp32, then per
+// element a compare-and-select -- the bag's first kept lookup sets the value whatever it holds (a NaN stays), a later one replaces it
+// iff it is GREATER, an ordered strict compare (a NaN never enters, of equal values the first wins).  Not fmaxf: that drops the first
+// lookup's NaN.  WITH_ARG: the row index that supplied the value travels with it.
+template <typename WT, bool WITH_ARG>
+__device__ __forceinline__ void max_step(float (&cur)[Elem<WT>::kVec], int32_t (&arg)[Elem<WT>::kVec], const u32x4& raw, int32_t r, bool first) {
+    constexpr int VEC = Elem<WT>::kVec;
+    float f[VEC];
+    Elem<WT>::widen(raw, f);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        const bool take = first || f[k] > cur[k];
+        cur[k] = take ? f[k] : cur[k];
+        if (WITH_ARG) arg[k] = take ? r : arg[k];
+    }
 }
 
 // The tile's nb pooled fp32 rows of D floats leave the burst buffer together, 16 bytes per lane and step (call after a barrier).

@@ -328,6 +328,87 @@ def _fwd(ts: _TableSet, indices, offsets, B, psw=None, out=None, bag_begin=0, ba
     return out
 
 
+def _fwd_max(ts: _TableSet, indices, offsets, B, out=None, bag_begin=0, bag_count=None, pad: Optional[torch.Tensor] = None,
+             out16: Optional[torch.dtype] = None, max_indices=False):
+    """MAX pooling (``pm_embbag_fwd_max``: a sibling of the padded forward's kernel; rule in include/param_amd.h, MAX POOLING) ->
+    ``(out, max_indices)``.  ``pad`` / ``out16`` / ``out`` / the batch slice: as for ``_fwd``.  ``max_indices``: ``False`` -- not
+    written, ``None`` comes back (inference); ``True`` -- a fresh int32 tensor of the output's shape (-1 for the bags outside a batch
+    slice); a tensor -- the caller's (contiguous int32 of the output's shape: bags outside the slice keep their bits)."""
+    if ts.layout == "blocked":
+        raise ValueError('max pooling is not supported with layout="blocked"')
+    op = ts.request(indices, offsets, B, None, bag_begin, bag_count, forward=True)
+    _, _, shape = ts.out_desc(B)
+    odt = torch.float32 if out16 is None else out16
+    if out is None:
+        out = torch.empty(shape, dtype=odt, device=ts.device)
+    elif out.dtype != odt or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {str(odt).replace('torch.', '')} tensor of shape {shape}")
+    arg = None
+    if max_indices is True:
+        whole = bag_begin == 0 and bag_count in (None, B)
+        arg = torch.empty(shape, dtype=torch.int32, device=ts.device) if whole else torch.full(shape, -1, dtype=torch.int32, device=ts.device)
+    elif max_indices is not False and max_indices is not None:
+        arg = max_indices
+        if arg.dtype != torch.int32 or tuple(arg.shape) != tuple(shape) or not arg.is_contiguous() or arg.device != ts.device:
+            raise ValueError(f"max_indices must be a contiguous int32 tensor of shape {shape} on {ts.device}")
+    rc = _lib.load().pm_embbag_fwd_max(ctypes.byref(op), None if pad is None else pad.data_ptr(), _WDTYPE[odt], out.data_ptr(),
+                                       None if arg is None else arg.data_ptr(), _stream_ptr())
+    if rc:
+        _lib.check(rc)
+    return out, arg
+
+
+_MAX_MIXED = "the gradient of max pooling needs one common embedding dim (it is applied by the sequence backward, which takes one)"
+
+
+def _max_expand(ts: _TableSet, grad, max_indices, indices, offsets, B, bag_begin=0, bag_count=None,
+                out16: Optional[torch.dtype] = None) -> torch.Tensor:
+    """The gradient of a MAX-pooled forward as a sequence gradient (``pm_embbag_max_grad``): fp32 ``[N, D]`` from torch's allocator,
+    row ``j`` = ``grad`` of ``j``'s bag in the columns whose arg-max is ``indices[j]`` and for which ``j`` is the bag's first such
+    position, +0.0 elsewhere.  Rows of positions outside the batch slice are not written (the sequence backward of the slice reads
+    none of them).  ``grad``: fp32 or the module's 16-bit output dtype ``out16``, widened exactly in the same launch; never modified.
+    One launch for any number of tables.  ``N x D`` fp32: 1.34 GB for 16 tables x batch 8192 x pooling 20 x D = 128."""
+    if ts.layout == "blocked":
+        raise ValueError('max pooling is not supported with layout="blocked"')
+    if len(set(ts.dims)) != 1:
+        raise ValueError(_MAX_MIXED)
+    grad = _check_grad(ts, grad, B, out16)
+    if (max_indices.dtype != torch.int32 or tuple(max_indices.shape) != tuple(grad.shape) or not max_indices.is_contiguous() or
+            max_indices.device != ts.device):
+        raise ValueError(f"max_indices must be a contiguous int32 tensor of shape {tuple(grad.shape)} on {ts.device}")
+    n, D = indices.numel(), ts.dims[0]
+    op = ts.request(indices, offsets, B, None, bag_begin, bag_count)
+    g_seq = torch.empty((n, D), dtype=torch.float32, device=ts.device)
+    if n:
+        rc = _lib.load().pm_embbag_max_grad(ctypes.byref(op), grad.data_ptr(), _WDTYPE[grad.dtype], max_indices.data_ptr(), g_seq.data_ptr(),
+                                            D, _stream_ptr())
+        if rc:
+            _lib.check(rc)
+    return g_seq
+
+
+def _max_bwd(ts: _TableSet, grad, indices, offsets, B, dst_ptrs_dev, dst_dtype, alpha, pad: Optional[torch.Tensor] = None, max_indices=None,
+             bag_begin=0, bag_count=None, out16: Optional[torch.dtype] = None) -> None:
+    """The backward of a MAX-pooled forward: ``dst_t[max_indices(t, b)[c], c] += alpha * grad(t, b)[c]``, deterministic.  No apply
+    kernel of its own: the gradient is expanded to one row per lookup position (``_max_expand``) and the sequence backward of the same
+    request (``_seq_bwd``: ``pm_embseq_bwd_fused``, 1024 tables per call) applies it, so a table row accumulates its bags' contributions
+    in ascending bag order.  ``max_indices=None``: recomputed by one forward launch into a scratch.  ``pad``: the padding rows of the
+    destinations keep their bits (``_PadGuard``).  A looked-up row that wins no column receives additions of ``alpha * 0.0``."""
+    if len(set(ts.dims)) != 1:
+        raise ValueError(_MAX_MIXED)
+    if max_indices is None:
+        _check_grad(ts, grad, B, out16)      # (refused before the forward launch)
+        _, max_indices = _fwd_max(ts, indices, offsets, B, None, bag_begin, bag_count, pad, None, True)
+    g_seq = _max_expand(ts, grad, max_indices, indices, offsets, B, bag_begin, bag_count, out16)
+    L, s, dt, D = _lib.load(), _stream_ptr(), _WDTYPE[dst_dtype], ts.dims[0]
+
+    def call(fn):
+        return lambda sub, gp, t0, max_rows, ws: fn(ctypes.byref(sub), gp, D, dst_ptrs_dev.data_ptr() + 8 * t0, dt, float(alpha), max_rows,
+                                                    ws.data_ptr(), ws.numel(), s)
+    _seq_bwd(ts, g_seq, indices, offsets, B, bag_begin, bag_count, False, call(L.pm_embseq_bwd_fused), call(L.pm_embseq_bwd_sorted),
+             _PadGuard(ts, pad, dst_ptrs_dev, dst_dtype))
+
+
 def _fwd_quantized(ts: _TableSet, indices, offsets, B, bitwidth: int, psw=None, out=None, bag_begin=0, bag_count=None):
     """Forward whose output is row-wise quantised (``pm_embbag_fwd_quantized``): one quantised row per pooled vector, in
     the order of the fp32 layout.  Returns a uint8 tensor ``[*shape[:-1] as rows, row_bytes]`` -- ``(B, T, rb)`` for the
@@ -746,7 +827,8 @@ _FBGEMM_POOLING_INTS = {0: "sum", 1: "mean", 2: "none"}      # fbgemm_gpu's Pool
 def pooling_mode_name(mode) -> str:
     """``"sum" | "mean"`` from what a caller of fbgemm's TBE module passes as ``pooling_mode``: one of those names in any case, a
     ``PoolingMode`` member (read by its name) or its int (SUM 0, MEAN 1).  ``NONE`` / 2 (no pooling: one output row per lookup) and
-    anything else raise ValueError.  Needs no device."""
+    anything else raise ValueError (max pooling, which fbgemm's enum does not have, is :class:`MaxBatchedEmbeddingBagMI355`).  Needs no
+    device."""
     return _mode_name(mode, _FBGEMM_POOLING_INTS, ("sum", "mean"), "pooling_mode must be sum or mean (any case, fbgemm's "
                       "PoolingMode.SUM / MEAN or their ints 0 / 1; PoolingMode.NONE is not implemented)")
 
@@ -1027,6 +1109,29 @@ class _SparseGradFn(_DenseGradFn):
         return g, None, None, None, d_psw
 
 
+class _MaxGradFn(torch.autograd.Function):
+    """``mode="max"``: forward = the max lookup, which also writes ``max_indices`` (saved); backward = ``grad_out[b, c]`` into row
+    ``max_indices[b, c]`` of a zeroed dense fp32 ``weight.grad`` (``_max_bwd``: aten::_embedding_bag_dense_backward's max branch)."""
+
+    @staticmethod
+    def forward(ctx, weight, module, indices, offsets):
+        ts = module._tables()
+        B = offsets.numel()
+        ctx.module, ctx.B = module, B
+        out, arg = _fwd_max(ts, indices, offsets, B, pad=module._pad_dev(), out16=module._out16, max_indices=True)
+        ctx.save_for_backward(indices, offsets, arg)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        indices, offsets, arg = ctx.saved_tensors
+        m = ctx.module
+        dW = torch.zeros(m.weight.shape, dtype=torch.float32, device=grad_out.device)
+        d_ptr = torch.tensor([dW.data_ptr()], dtype=torch.int64, device=grad_out.device)
+        _max_bwd(m._tables(), grad_out.contiguous(), indices, offsets, ctx.B, d_ptr, torch.float32, 1.0, m._pad_dev(), arg, out16=m._out16)
+        return dW.to(m.weight.dtype), None, None, None
+
+
 class EmbeddingBagMI355(nn.Module, _BoundsChecked):
     """``torch.nn.EmbeddingBag(num_embeddings, embedding_dim, mode="sum" | "mean")`` on MI355X HIP kernels.
 
@@ -1050,19 +1155,25 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
     summed as the sum backward sums, dense and ``sparse=True``.  On fp32 tables that is torch's CPU module bit for bit (forward always;
     gradients where no row is looked up twice, otherwise up to the order of the additions).  16-bit tables keep this package's
     convention (rows widened, fp32 sums and output); torch's own 16-bit module rounds the sum to 16 bits before it divides.
-    ``per_sample_weights`` with ``mode="mean"`` raises ``NotImplementedError``, as torch does; ``mode="max"`` is not implemented.
+    ``per_sample_weights`` with ``mode="mean"`` raises ``NotImplementedError``, as torch does; this constructor refuses ``mode="max"``
+    as it always did: max pooling is :class:`MaxEmbeddingBagMI355`.
     ``output_dtype`` (default ``None`` = fp32; fbgemm TBE's argument): ``torch.bfloat16`` / ``torch.float16``, ``"bf16"`` / ``"fp16"`` in
     any case or an enum member of that value or name (``SparseType``): ``forward`` returns that dtype -- the fp32 result of the same
     request rounded once, to nearest even, in the lookup kernel (``pm_embbag_fwd_out16``) -- and the backward receives it: the gradient
     is widened exactly (``pm_embbag_grad_widen``, the mean scaling fused) and then treated as the fp32 gradient it stands for.
     """
 
+    _MODES = ("sum", "mean")      # what this constructor takes as ``mode`` (:class:`MaxEmbeddingBagMI355`: ``"max"``)
+
     def __init__(self, num_embeddings: int, embedding_dim: int, mode: str = "sum", sparse: bool = False,
                  dtype: torch.dtype = torch.float32, device=None, _weight: Optional[torch.Tensor] = None,
                  bounds_check_mode="none", padding_idx: Optional[int] = None, output_dtype=None):
         super().__init__()
-        if mode not in ("sum", "mean"):
-            raise NotImplementedError('only mode="sum" (the reference hot path, pytorch_emb.py:179) and mode="mean" are implemented')
+        if mode not in self._MODES:
+            raise NotImplementedError('only mode="sum" (the reference hot path, pytorch_emb.py:179) and mode="mean" are implemented'
+                                      if "sum" in self._MODES else f'{type(self).__name__} is mode="max" only')
+        if mode == "max" and sparse:
+            raise ValueError("max mode does not support sparse weights")
         self._init_shared(bounds_check_mode, output_dtype)      # (validated before anything is allocated)
         self.padding_idx = _normalize_padding_idx(padding_idx, num_embeddings if _weight is None else int(_weight.shape[0]))
         self._off2d: dict = {}
@@ -1131,6 +1242,10 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
             _require_device(w, "EmbeddingBagMI355.weight")
         if self.bounds_check_mode != "none":
             self._sanitize(self._tables(), indices, offsets, offsets.numel(), self.bounds_check_mode, per_sample_weights)
+        if self.mode == "max":
+            if w.requires_grad and torch.is_grad_enabled():
+                return _MaxGradFn.apply(w, self, indices, offsets)
+            return _fwd_max(self._tables(), indices, offsets, offsets.numel(), pad=self._pad_dev(), out16=self._out16)[0]
         if w.requires_grad and torch.is_grad_enabled():
             return (_SparseGradFn if self.sparse else _DenseGradFn).apply(w, self, indices, offsets, per_sample_weights)
         ts = self._ts
@@ -1150,6 +1265,25 @@ class EmbeddingBagMI355(nn.Module, _BoundsChecked):
         return (f"{self.num_embeddings}, {self.embedding_dim}, mode={self.mode}, dtype={self.weight.dtype}" + (", sparse=True" if self.sparse else "") +
                 (f", padding_idx={self.padding_idx}" if self.padding_idx is not None else "") +
                 (f", output_dtype={self.output_dtype}" if self._out16 is not None else ""))
+
+
+class MaxEmbeddingBagMI355(EmbeddingBagMI355):
+    """``torch.nn.EmbeddingBag(num_embeddings, embedding_dim, mode="max")`` on MI355X HIP kernels: :class:`EmbeddingBagMI355`'s surface
+    (1-D and 2-D input, ``padding_idx``, ``output_dtype``, ``bounds_check_mode``) with max pooling.  A class of its own because
+    ``EmbeddingBagMI355(mode="max")`` keeps raising ``NotImplementedError``, as it always did; ``mode``, if given, must be ``"max"``.
+
+    Per column the maximum over the bag's lookups that are not ``padding_idx``, by torch's rule -- the first kept lookup sets the value
+    whatever it holds, a later one replaces it iff it is greater (ordered, strict): a NaN in the first kept lookup stays, a later NaN
+    never enters, of equal values the first wins; an empty or all-padding bag gives +0.0.  torch's CPU module bit for bit on fp32,
+    bf16 and fp16 tables (fp32 output of a 16-bit table: torch's widened).  The backward sends ``grad[b, c]`` to the row that supplied
+    the maximum, once; ``weight.grad`` is dense and equals torch's CPU autograd bit for bit wherever a row has at most 256 lookups in
+    the request.  ``per_sample_weights`` raises ``NotImplementedError`` and ``sparse=True`` ``ValueError`` (at construction), with
+    torch's texts."""
+
+    _MODES = ("max",)
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, mode: str = "max", **kw):
+        super().__init__(num_embeddings, embedding_dim, mode=mode, **kw)
 
 
 class _EmbeddingGradFn(torch.autograd.Function):
@@ -1346,6 +1480,24 @@ class _FusedSequenceFn(torch.autograd.Function):
         return None, None, None, None, None
 
 
+_MAX_WEIGHTED = "max pooling is unweighted: per_sample_weights must be None"
+_MAX_FUSED = ("a fused optimizer would apply weight decay and state updates to looked-up rows whose gradient is zero (a row that wins no "
+              "column); use dense_grad or scatter_add_")
+
+
+class _FusedMaxRefusedFn(torch.autograd.Function):
+    """what ``forward`` of a ``pooling_mode="max"`` module with ``fused_update`` returns under autograd: the lookup's result, whose
+    ``.backward()`` is refused with the reason (there is no fused update for max pooling)"""
+
+    @staticmethod
+    def forward(ctx, anchor, out):
+        return out.view_as(out)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        raise ValueError('the fused .backward() does not take pooling_mode="max": ' + _MAX_FUSED)
+
+
 class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     """T embedding tables in one HBM slab, looked up by ONE kernel launch.
 
@@ -1379,6 +1531,9 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     fbgemm, which allows weighted mean: ``per_sample_weights`` with ``"mean"`` raises ValueError, and so do
     ``per_sample_weights_grad``, ``lookup(split_bags=True)``, ``lookup_quantized`` and ``layout="blocked"``.  ``"sum"`` adds no launch.
 
+    Max pooling (which fbgemm's enum does not have; ``pooling_mode="max"`` stays a ValueError here) is
+    :class:`MaxBatchedEmbeddingBagMI355`; sum and mean modules reach none of its code.
+
     ``output_dtype`` (default ``None`` = fp32; fbgemm TBE's argument of that name): ``torch.float32`` / ``torch.bfloat16`` /
     ``torch.float16``, ``"fp32"`` / ``"bf16"`` / ``"fp16"`` in any case, or an enum member whose value or name is one of those
     (``SparseType``); anything else raises ValueError.  With a 16-bit dtype ``forward`` / ``lookup`` (``out=`` and batch slices
@@ -1390,6 +1545,8 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     ``lookup(split_bags=True)`` and ``lookup_quantized`` do not take a 16-bit ``output_dtype`` (ValueError).  The default adds no launch.
     """
 
+    _POOLING = None      # a subclass's fixed pooling mode (:class:`MaxBatchedEmbeddingBagMI355`: ``"max"``); None: the ``pooling_mode`` argument
+
     def __init__(self, rows: Sequence[int], dims, dtype: torch.dtype = torch.float32, device="cuda",
                  layout: str = "bd", init: Optional[str] = "uniform_dlrm", seed: int = 0,
                  learning_rate: float = 0.01, fused_update: bool = True, optimizer: str = "sgd", eps: float = 1.0e-8,
@@ -1399,10 +1556,11 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         self._init_shared(bounds_check_mode, output_dtype)      # (validated, like the optimizer below, before anything is allocated)
         if self._out16 is not None and layout == "blocked":
             raise ValueError('a 16-bit output_dtype is not supported with layout="blocked"')
-        self.pooling_mode = pooling_mode_name(pooling_mode)
+        self.pooling_mode = self._POOLING or pooling_mode_name(pooling_mode)
         self._mean = self.pooling_mode == "mean"
-        if self._mean and layout == "blocked":
-            raise ValueError('pooling_mode="mean" is not supported with layout="blocked"')
+        self._max = self.pooling_mode == "max"
+        if (self._mean or self._max) and layout == "blocked":
+            raise ValueError(f'pooling_mode="{self.pooling_mode}" is not supported with layout="blocked"')
         rows = [int(r) for r in rows]
         dims = [int(dims)] * len(rows) if isinstance(dims, int) else [int(d) for d in dims]
         assert len(rows) == len(dims) and len(rows) >= 1
@@ -1501,10 +1659,31 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         return self._batch_of(offsets, indices) if batch is None else batch
 
     # -- ops ---------------------------------------------------------------------------------
+    def _max_refuses(self, what: str, why: str = "") -> None:
+        """a call that a ``pooling_mode="max"`` module does not take: ValueError naming it (and the reason, where there is one)"""
+        if self._max:
+            raise ValueError(f'{what} does not take pooling_mode="max"' + (f": {why}" if why else ""))
+
     def lookup(self, indices, offsets, per_sample_weights=None, out=None, bag_begin=0, bag_count=None,
-               batch: Optional[int] = None, split_bags: bool = False):
+               batch: Optional[int] = None, split_bags: bool = False, return_max_indices: bool = False, max_indices=None):
         """Forward without autograd glue; ``bag_begin/bag_count`` select a batch slice.  ``split_bags=True`` selects the
-        one-workgroup-per-bag kernel for few, long bags (deterministic, fp32-rounding-close to the default, not bit-equal)."""
+        one-workgroup-per-bag kernel for few, long bags (deterministic, fp32-rounding-close to the default, not bit-equal).
+        ``pooling_mode="max"`` only: ``return_max_indices=True`` returns ``(out, max_indices)`` -- int32 of the output's shape, the row
+        that supplied each maximum, -1 for a bag without kept lookups; ``max_indices=`` is a caller's tensor for it (bags outside a
+        batch slice keep their bits) and implies the pair."""
+        if self._max:
+            if split_bags or per_sample_weights is not None:
+                raise ValueError('pooling_mode="max" does not take split_bags=True' if split_bags else _MAX_WEIGHTED)
+            _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
+            B = self._batch_of(offsets, indices) if batch is None else batch
+            if self.bounds_check_mode != "none":
+                self._sanitize(self._tables(), indices, offsets, B, self.bounds_check_mode, None, bag_begin, bag_count)
+            want = return_max_indices or max_indices is not None
+            res = _fwd_max(self._tables(), indices, offsets, B, out, bag_begin, bag_count, self._pad_dev(), self._out16,
+                           (True if max_indices is None else max_indices) if want else False)
+            return res if want else res[0]
+        if return_max_indices or max_indices is not None:
+            raise ValueError('return_max_indices / max_indices need max pooling (MaxBatchedEmbeddingBagMI355)')
         if split_bags and self.padding_idx is not None:
             raise ValueError("lookup(split_bags=True) does not take padding_idx")
         if self._mean and (split_bags or per_sample_weights is not None):
@@ -1536,6 +1715,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             raise ValueError("lookup_sequence needs one common embedding dim")
         if self._mean:
             raise ValueError('lookup_sequence does not take pooling_mode="mean": a mean module has no un-pooled form')
+        self._max_refuses("lookup_sequence", "a max module has no un-pooled form")
         if out is not None:
             _check_rows_out(out, indices.numel(), self.dims[0], self.output_dtype, self.weights.device)
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
@@ -1565,13 +1745,23 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             raise ValueError("lookup_quantized does not take padding_idx")
         if self._mean:
             raise ValueError('lookup_quantized does not take pooling_mode="mean"')
+        self._max_refuses("lookup_quantized")
         if self._out16 is not None:
             raise ValueError("lookup_quantized does not take a 16-bit output_dtype (its fp16 rows are a payload format of its own)")
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
         B = self._batch_of(offsets, indices) if batch is None else batch
         return _fwd_quantized(self._tables(), indices, offsets, B, bitwidth, per_sample_weights, out, bag_begin, bag_count)
 
-    def forward(self, indices, offsets, per_sample_weights=None):
+    def forward(self, indices, offsets, per_sample_weights=None, return_max_indices: bool = False):
+        if self._max:
+            # (no fused update for max: the result carries a backward node only to refuse ``.backward()`` with the reason)
+            res = self.lookup(indices, offsets, per_sample_weights, return_max_indices=return_max_indices)
+            if not (self.fused_update and torch.is_grad_enabled()):
+                return res
+            out = _FusedMaxRefusedFn.apply(self._anchor, res[0] if return_max_indices else res)
+            return (out, res[1]) if return_max_indices else out
+        if return_max_indices:
+            raise ValueError('return_max_indices needs max pooling (MaxBatchedEmbeddingBagMI355)')
         if self.fused_update and torch.is_grad_enabled():
             return _FusedUpdateFn.apply(self._anchor, self, indices, offsets, per_sample_weights)
         return self.lookup(indices, offsets, per_sample_weights)
@@ -1585,13 +1775,34 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             for_adagrad = self.optimizer in ("rowwise_adagrad", "adagrad")
         _sort_indices(self._tables(), indices, offsets, B, per_sample_weights, phases=1 if for_adagrad else 2, pooling=pooling)
 
+    def _max_grad_args(self, what: str, per_sample_weights, method: str = "sorted", presorted: bool = False) -> None:
+        """what the two gradient calls of a max module refuse, on the host and before anything is launched"""
+        if per_sample_weights is not None:
+            raise ValueError(_MAX_WEIGHTED)
+        if method != "sorted" or presorted:
+            raise ValueError(f'{what} with pooling_mode="max" runs the sequence backward on the expanded gradient: method="atomic" and '
+                             "presorted=True are not taken")
+        if len(set(self.dims)) != 1:
+            raise ValueError(_MAX_MIXED)
+
     def scatter_add_(self, grad, indices, offsets, alpha: float, per_sample_weights=None,
                      batch: Optional[int] = None, bag_begin=0, bag_count=None, method: str = "sorted",
-                     presorted: bool = False, pooling: Optional[int] = None):
+                     presorted: bool = False, pooling: Optional[int] = None, max_indices=None):
         """In place ``W_t[idx[j]] += alpha * psw[j] * grad(t, bag(j))`` (alpha = -lr: SGD step).  ``pooling``: the
-        caller's word that every bag has exactly that many lookups (saves the one-off device check of a new request)."""
+        caller's word that every bag has exactly that many lookups (saves the one-off device check of a new request).
+        ``pooling_mode="max"``: in place ``W_t[max_indices(t, b)[c], c] += alpha * grad(t, b)[c]`` (``_max_bwd``); ``max_indices``: what
+        ``lookup(..., return_max_indices=True)`` returned for the request, or ``None`` to recompute it with one forward launch.  A
+        looked-up row that wins no column receives ``alpha * 0.0``: with a positive ``alpha`` a stored -0.0 there becomes +0.0."""
+        if self._max:
+            self._max_grad_args("scatter_add_", per_sample_weights, method, presorted)
+        elif max_indices is not None:
+            raise ValueError('max_indices needs max pooling (MaxBatchedEmbeddingBagMI355)')
         ts = self._tables()
         B = self._batch(offsets, indices, batch)
+        if self._max:
+            _max_bwd(ts, grad, indices, offsets, B, ts.d_ptrs, self.weights.dtype, alpha, self._pad_dev(), max_indices, bag_begin, bag_count,
+                     self._out16)
+            return
         _bwd(ts, grad, indices, offsets, B, ts.d_ptrs, self.weights.dtype, alpha, per_sample_weights,
              bag_begin, bag_count, method, presorted, pooling, pad=self._pad_dev(), mean=self._mean, out16=self._out16)
 
@@ -1629,6 +1840,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         ``torch.optim.Adagrad``'s arithmetic), one state value per weight: ``s[r,d] += G[r,d]^2;
         W[r,d] -= lr * G[r,d] / (sqrt(s[r,d]) + eps)``, same options (l2 adds ``wd * W`` to ``G`` first).  (Called on a module of
         any other optimizer, the step is the row-wise one, as before.)"""
+        self._max_refuses("adagrad_step_", _MAX_FUSED)
         self.momentum_table(0)
         B = self._batch(offsets, indices, batch)
         self._sr_step += 1          # a fresh stochastic-rounding stream every step, reproducible run to run
@@ -1640,6 +1852,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     def optimizer_step_(self, grad, indices, offsets, per_sample_weights=None, batch: Optional[int] = None,
                         presorted: bool = False):
         """what ``.backward()`` applies when ``fused_update`` is on"""
+        self._max_refuses("optimizer_step_", _MAX_FUSED)
         if self.optimizer in ("rowwise_adagrad", "adagrad"):
             self.adagrad_step_(grad, indices, offsets, per_sample_weights, batch, presorted)
         else:
@@ -1658,13 +1871,21 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         return outs, torch.tensor([o.data_ptr() for o in outs], dtype=torch.int64, device=ts.device)
 
     def dense_grad(self, grad, indices, offsets, per_sample_weights=None, batch: Optional[int] = None,
-                   method: str = "sorted", out: Optional[Sequence[torch.Tensor]] = None):
+                   method: str = "sorted", out: Optional[Sequence[torch.Tensor]] = None, max_indices=None):
         """fp32 dense gradients (list, one per table) -- small tables / parity tests only.  ``out``: one contiguous fp32
         ``[rows_t, dims_t]`` buffer per table to ADD the gradient to (default: fresh zeros); a padding row of such a buffer is
-        exactly what it was before the call."""
+        exactly what it was before the call.  ``pooling_mode="max"``: ``grad(t, b)[c]`` lands in row ``max_indices(t, b)[c]``
+        (``max_indices``: as for ``scatter_add_``)."""
+        if self._max:
+            self._max_grad_args("dense_grad", per_sample_weights, method)
+        elif max_indices is not None:
+            raise ValueError('max_indices needs max pooling (MaxBatchedEmbeddingBagMI355)')
         ts = self._tables()
         B = self._batch(offsets, indices, batch)
         outs, d_ptrs = self._dense_grad_buffers(ts, out)
+        if self._max:
+            _max_bwd(ts, grad, indices, offsets, B, d_ptrs, torch.float32, 1.0, self._pad_dev(), max_indices, out16=self._out16)
+            return outs
         _bwd(ts, grad, indices, offsets, B, d_ptrs, torch.float32, 1.0, per_sample_weights, method=method, pad=self._pad_dev(),
              mean=self._mean, out16=self._out16)
         return outs
@@ -1679,6 +1900,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         synchronises once (to read the U_t and allocate exactly), as torch's ``coalesce()`` does -- once per 1024 tables for larger
         requests, which are split into independent calls.  The gradient with respect to ``per_sample_weights`` is a call of its
         own: ``per_sample_weights_grad``."""
+        self._max_refuses("sparse_grad", "the max gradient is dense (torch's max mode does not support sparse weights)")
         B = self._batch(offsets, indices, batch)
         return _sparse_grad(self._tables(), grad, indices, offsets, B, per_sample_weights, bag_begin, bag_count,
                             pads=self.padding_idx, mean=self._mean, pad=self._pad_dev(), out16=self._out16)
@@ -1693,6 +1915,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         of tables (no sort, no workspace).  Call it BEFORE an in-place update of the tables."""
         if self._mean:
             raise ValueError('per_sample_weights_grad: pooling_mode="mean" is unweighted')
+        self._max_refuses("per_sample_weights_grad", "max pooling is unweighted")
         _require_device(self.weights, "BatchedEmbeddingBagMI355.weights")
         B = self._batch(offsets, indices, batch)
         return _psw_grad(self._tables(), grad, indices, offsets, B, None, out, bag_begin, bag_count, pad=self._pad_dev(), out16=self._out16)
@@ -1708,6 +1931,7 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             raise ValueError(f"{what} needs one common embedding dim")
         if self._mean:
             raise ValueError(f'{what} does not take pooling_mode="mean": a mean module has no un-pooled form')
+        self._max_refuses(what, "a max module has no un-pooled form")
         if grad is not None:
             shape = (indices.numel(), self.dims[0])
             if (grad.dtype != torch.float32 and grad.dtype != self._out16) or tuple(grad.shape) != shape:
@@ -1795,3 +2019,26 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     def check(self, indices, offsets, per_sample_weights=None, batch: Optional[int] = None) -> None:
         B = self._batch(offsets, indices, batch)
         check_request(self._tables(), indices, offsets, B, per_sample_weights)
+
+
+class MaxBatchedEmbeddingBagMI355(BatchedEmbeddingBagMI355):
+    """:class:`BatchedEmbeddingBagMI355` with MAX pooling: T tables in one slab, max-pooled by one launch.  A class of its own because
+    fbgemm's ``PoolingMode`` has no such member and ``BatchedEmbeddingBagMI355(pooling_mode="max")`` keeps raising ValueError, as it
+    always did.  The constructor's arguments are the parent's; ``pooling_mode``, if given, must be the string ``"max"`` (any case).
+    The attribute ``pooling_mode`` is ``"max"``.
+
+    ``forward`` / ``lookup`` (``out=``, batch slices, ``bd`` / ``tbd``, ``padding_idx``, ``output_dtype`` and ``bounds_check_mode``
+    included) give, per column, the maximum over the bag's kept lookups by torch's ``mode="max"`` rule (include/param_amd.h, MAX
+    POOLING); ``return_max_indices=True`` also returns the int32 rows that supplied the maxima (-1 for a bag without kept lookups).
+    ``dense_grad`` and ``scatter_add_`` take ``max_indices=`` (``None``: recomputed by one forward launch) and send ``grad(t, b)[c]`` to
+    that row, once: the gradient is expanded to an fp32 ``[N, D]`` scratch (one more launch) and applied by the sequence backward, 1024
+    tables per call; they need one common embedding dim.  ``per_sample_weights``, ``optimizer_step_``, ``adagrad_step_``, the fused
+    ``.backward()``, ``sparse_grad``, ``per_sample_weights_grad``, ``lookup_sequence`` / ``sequence_*``, ``lookup(split_bags=True)``,
+    ``lookup_quantized`` and ``layout="blocked"`` raise ValueError."""
+
+    _POOLING = "max"
+
+    def __init__(self, rows: Sequence[int], dims, *args, pooling_mode="max", **kw):
+        if not (isinstance(pooling_mode, str) and pooling_mode.lower() == "max"):
+            raise ValueError(f'MaxBatchedEmbeddingBagMI355 pools with max: pooling_mode must be the string "max", got {pooling_mode!r}')
+        super().__init__(rows, dims, *args, **kw)
