@@ -32,9 +32,10 @@ FORWARD_TUNING_DEFAULT = (-1, -1, -1)
 ENV = ("PARAM_AMD_FWD_STAGE", "PARAM_AMD_FWD_FLAT", "PARAM_AMD_FLAT_MAXL", "PARAM_AMD_FLAT_TARGET", "PARAM_AMD_FLAT_BAGS",
        "PARAM_AMD_FWD_TILE_MAJOR", "PARAM_AMD_FLAT_COMPACT")
 ENV_DEFAULT = (1, 1, 0, 256, 256, -1, 1)
-# which plan an entry point launches with (capi.hip)
+# which plan an entry point launches with (capi.hip); a pair: (fp32 output, 16-bit output) -- pm_embbag_fwd_max plans on the padded
+# family's plan for its output element, so the case decides
 ENTRY_KIND = {"fwd": "forward", "quantized": "quantized", "padded": "padded4", "mean": "padded4", "out16": "padded2", "gather": "gather",
-              "psw_grad": "base", "mean_grad": "base", "widen": "base", "atomic": "base"}
+              "psw_grad": "base", "mean_grad": "base", "widen": "base", "atomic": "base", "max": ("padded4", "padded2")}
 UNROLLS = (1, 2, 3, 4, 6, 8)
 K_BLOCK = 256
 
@@ -129,6 +130,21 @@ def request(name):
         if lens.sum() % 300 == 0:
             lens[0] += 1
         return Request(name, 3, 100, [1000, 500, 250], lens, 401)
+    if name == "pad_lumpy":
+        # even_lumpy's bag lengths with padding rows: the plan is even_lumpy's (a staged tile's index tile holds 1280 entries), the
+        # 32-bag tile of 1600 lookups reads its indices -- 40 % of them table 0's padding row -- from the request
+        T, B, rows = 3, 96, [1000, 500, 250]
+        lens = request("even_lumpy").lens
+        pads = [5, rows[1] - 1, None]
+        rng = np.random.default_rng(550)
+        idx = np.concatenate([rng.integers(0, r, int(n)) for r, n in zip(rows, np.add.reduceat(lens, np.arange(0, T * B, B)))]).astype(np.int64)
+        for t, k in enumerate(pads):
+            if k is not None:
+                lo, hi = int(lens[:t * B].sum()), int(lens[:(t + 1) * B].sum())
+                idx[lo:hi][rng.random(hi - lo) < 0.4] = k
+        r = Request(name, T, B, rows, lens, 550, pads=pads, idx=idx)
+        assert r.N == 20 * T * B and lens[32:64].sum() > 1280 and 500 < (idx[r.off[32]:r.off[64]] == 5).sum() < 800
+        return r
     if name.startswith("pad"):
         # about 40 % of the lookups of a table with a padding row are that row (padding_rules.padded_request)
         T, B, rows, kw = {"pad100": (3, 100, [1000, 500, 250], dict(max_len=9)), "pad1100": (2, 1100, [1000, 300], dict(max_len=5)),
@@ -157,6 +173,23 @@ def request(name):
     raise KeyError(name)
 
 
+def max_conditions(r, vals, args):
+    """What a padded request is there for under max pooling, read off the rule's result on some tables (``vals`` / ``args``: per table
+    ``[B, D]``, tests/max_rules.py: forward) -> three booleans: a bag all of whose lookups are padded gives +0.0 and -1; a bag's first
+    lookup is padded and a later one is kept; a bag holds the row that won a column at two positions."""
+    all_padded = first_padded = twice = False
+    for t in range(r.T):
+        k = -1 if r.pads is None or r.pads[t] is None else r.pads[t]
+        for b in range(r.B):
+            bag = r.idx[r.off[t * r.B + b]:r.off[t * r.B + b + 1]]
+            kept = bag[bag != k]
+            if bag.size and not kept.size:
+                all_padded |= bool((np.ascontiguousarray(vals[t][b]).view(np.uint32) == 0).all() and (args[t][b] == -1).all())
+            first_padded |= bool(bag.size and bag[0] == k and kept.size)
+            twice |= any((kept == a).sum() >= 2 for a in np.unique(args[t][b]))
+    return all_padded, first_padded, twice
+
+
 # ---- cases ----------------------------------------------------------------------------------------------------------------------
 class Case:
     def __init__(self, name, group, entry, request, kind="f32", dims=128, tuning=None, forward=None, env=None, weighted=False,
@@ -166,7 +199,7 @@ class Case:
         self.weighted, self.bag_slice, self.out16, self.mean, self.bits = weighted, bag_slice, out16, mean, bits
         self._dims = dims
         assert not set(self.tuning) - set(TUNING) and not set(self.forward) - set(FORWARD_TUNING) and not set(self.env) - set(ENV)
-        assert entry in ENTRY_KIND and kind in DTYPE and not (mean and weighted)
+        assert entry in ENTRY_KIND and kind in DTYPE and not (mean and weighted) and not (entry == "max" and (weighted or mean))
 
     @property
     def req(self):
@@ -178,7 +211,8 @@ class Case:
 
     @property
     def plan_kind(self):
-        return ENTRY_KIND[self.entry]
+        kind = ENTRY_KIND[self.entry]
+        return kind if isinstance(kind, str) else kind[self.out16 is not None]
 
     @property
     def bags(self):
@@ -223,6 +257,8 @@ def label(case, plan):
              f"nt{p['nt_loads']}", f"bpb{p['bags_per_block']}"}
     if family in ("tile", "pad"):
         words.add(("ordered-bitonic" if p["bags_per_block"] <= 64 else "ordered-rank") if p["ordered"] else "staged" if p["stage_out"] else "plain")
+    if case.entry == "max":
+        words.add("max")
     if p["bags_per_block"] > NG:
         words.add("tile>NG")
     if family == "flat":
@@ -251,7 +287,8 @@ def label(case, plan):
 
 
 def pad_lds_bytes(case, plan):
-    """LDS the padded family's launcher asks for before its 64 KB fallback (embbag_fwd_pad_kernel.inc: launch_pad_w)"""
+    """LDS the padded family's launcher asks for before its 64 KB fallback (embbag_fwd_pad_kernel.inc: launch_pad_w;
+    embbag_fwd_max.hip: launch_max_a, never weighted)"""
     p = dict(zip(PLAN_FIELDS, plan))
     tile = (p["bags_per_block"] + 2) // 2 * 2 * 8 + p["idx_cap"] * 4 * (2 if case.weighted else 1)
     tile = (tile + p["idx_cap"] * 2 + 15) // 16 * 16
@@ -333,6 +370,30 @@ def _cases():
     add("padded_D512_bf16_tables", "pad_D512", "padded", "pad100", "bf16", 512, tuning=dict(bags_per_block=16))
     add("out16_D512_bf16_tables", "pad_D512", "out16", "pad100", "bf16", 512, tuning=dict(bags_per_block=16), out16="bf16")
     add("out16_D512_f16_tables", "pad_D512", "out16", "pad100", "f16", 512, tuning=dict(bags_per_block=16), out16="fp16", weighted=True)
+    # -- max pooling: pm_embbag_fwd_max on the padded family's plan, fp32 and bf16 output (unweighted: max takes no weights)
+    for fam, kw in (("max", {}), ("max16bf", dict(out16="bf16"))):
+        add(f"{fam}_bpb32", f"pad_{fam}", "max", "pad100", tuning=dict(bags_per_block=32), **kw)
+        add(f"{fam}_bpb32_unstaged", f"pad_{fam}", "max", "pad100", tuning=dict(bags_per_block=32), forward=dict(stage_out=0), **kw)
+        add(f"{fam}_bpb1024", f"pad_{fam}_1024", "max", "pad1100", dims=8 if kw else 4, tuning=dict(bags_per_block=1024), **kw)
+        add(f"{fam}_xcd0", f"pad_{fam}", "max", "pad100", tuning=dict(bags_per_block=32, xcd_affine=0), **kw)
+        add(f"{fam}_xcd3", f"pad_{fam}", "max", "padfix", tuning=dict(bags_per_block=32), **kw)
+        add(f"{fam}_xcd1", f"pad_{fam}_T8", "max", "pad8", tuning=dict(bags_per_block=32), **kw)
+        add(f"{fam}_nt", f"pad_{fam}", "max", "pad100", tuning=dict(bags_per_block=32, nt_loads=1), **kw)
+        add(f"{fam}_slice", f"pad_{fam}", "max", "pad100", tuning=dict(bags_per_block=32), bag_slice=(5, 70), **kw)
+        for G in (8, 16, 64):                                      # (G = 32: every case above)
+            add(f"{fam}_G{G}", f"pad_{fam}_G", "max", "pad100", dims=G * 4, tuning=dict(bags_per_block=2 * K_BLOCK // G), **kw)
+        # fp32 rows of 512: the column loop runs twice at G = 64; 8 bags (two per lane group) fill the burst exactly
+        add(f"{fam}_D512_f32_tables", f"pad_{fam}_wide", "max", "pad100", dims=512, tuning=dict(bags_per_block=8), **kw)
+        # mixed dims: the forward takes them (only the gradient refuses); the lane group is sized for 128, the narrow tables idle lanes
+        add(f"{fam}_mixed_dims", f"pad_{fam}_wide", "max", "pad100", dims=[16, 64, 128], tuning=dict(bags_per_block=32), **kw)
+        # a 32-bag tile of 1600 lookups against an index tile of 1280: its indices, padding included, come from the request
+        add(f"{fam}_direct", f"pad_{fam}_wide", "max", "pad_lumpy", tuning=dict(bags_per_block=32), **kw)
+    add("max16h_bpb32", "pad_max16bf", "max", "pad100", tuning=dict(bags_per_block=32), out16="fp16")
+    # 16-bit tables at G = 32 and G = 64, two and four bags per lane group: at D = 512 the 4-byte burst does not fit, the 2-byte one does
+    for kind, o16 in (("bf16", "bf16"), ("f16", "fp16")):
+        for D in (256, 512):
+            add(f"max_D{D}_{kind}_tables", f"pad_max_{kind}_tables", "max", "pad100", kind, D, tuning=dict(bags_per_block=16))
+            add(f"max16_D{D}_{kind}_tables", f"pad_max_{kind}_tables", "max", "pad100", kind, D, tuning=dict(bags_per_block=16), out16=o16)
     # -- quantized forward: staged 32-bag tiles under the unrolls no other test runs
     for u, bits in ((1, 8), (3, 4), (6, 8), (6, 2), (3, 16)):
         add(f"quantized_u{u}_{bits}bit", "quantized", "quantized", "even", tuning=dict(unroll=u, bags_per_block=32), bits=bits)
@@ -377,6 +438,7 @@ def _cases():
     add(f"{e}_even_auto", e, "fwd", "even", env=env, weighted=True)
     add(f"{e}_short1", e, "fwd", "short1", env=env)
     add(f"{e}_padded", e, "padded", "pad100", tuning=dict(bags_per_block=32), env=env)
+    add(f"{e}_max", e, "max", "pad100", tuning=dict(bags_per_block=32), env=env)
     add(f"{e}_out16", e, "out16", "pad100", tuning=dict(bags_per_block=32), env=env, out16="bf16")
     assert len({c.name for c in out}) == len(out)
     for c in out:                                                  # a group shares its environment; its cases are one test

@@ -64,23 +64,25 @@ def variants(c):
 
 
 def _pads(c):
-    return c.req.pads if c.entry in ("padded", "mean", "out16", "mean_grad") or (c.entry == "widen" and c.mean) else None
+    return c.req.pads if c.entry in ("padded", "mean", "out16", "mean_grad", "max") or (c.entry == "widen" and c.mean) else None
 
 
 def module(c, layout):
     """the module of a case and its tables as fp32 values (16-bit tables widened: exact); one per distinct set of options"""
     torch = _torch()
-    from param_amd import BatchedEmbeddingBagMI355
+    from param_amd import BatchedEmbeddingBagMI355, MaxBatchedEmbeddingBagMI355
 
     td = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
     od = {None: None, "bf16": torch.bfloat16, "fp16": torch.float16}
     pads = _pads(c)
     out16 = c.out16 if c.entry != "gather" else {"f32": None, "bf16": "bf16", "f16": "fp16"}[c.kind]
-    key = ("module", c.kind, tuple(c.dims), tuple(c.req.rows), layout, None if pads is None else tuple(pads), c.mean, out16)
+    is_max = c.entry == "max"
+    key = ("module", c.kind, tuple(c.dims), tuple(c.req.rows), layout, None if pads is None else tuple(pads), c.mean, out16, is_max)
 
     def make():
-        m = BatchedEmbeddingBagMI355(c.req.rows, c.dims, dtype=td[c.kind], device=DEV, layout=layout, init="normal", seed=7, fused_update=False,
-                                     padding_idx=pads, pooling_mode="mean" if c.mean else "sum", output_dtype=od[out16])
+        cls, mode = (MaxBatchedEmbeddingBagMI355, "max") if is_max else (BatchedEmbeddingBagMI355, "mean" if c.mean else "sum")
+        m = cls(c.req.rows, c.dims, dtype=td[c.kind], device=DEV, layout=layout, init="normal", seed=7, fused_update=False,
+                padding_idx=pads, pooling_mode=mode, output_dtype=od[out16])
         return m, [m.table(t).float().cpu().numpy().copy() for t in range(c.req.T)]
     return _memo(key, make)
 
@@ -157,6 +159,65 @@ def run_forward(c, idt, layout, coracle):
     rest = np.ones(shape, dtype=bool)
     rest[sel] = False
     assert np.isnan(got[rest]).all(), "written outside the slice"
+
+
+def max_reference(c, tabs):
+    """(values, args) of tests/max_rules.py for the whole batch, per table; a Python loop over the lookups: computed once per
+    (request, table dtype, dims) and shared by the knobs, index types, layouts and output types"""
+    from tests import max_rules as MX
+
+    r = c.req
+
+    def make():
+        vals, args = MX.forward(tabs, r.idx, r.off, r.B, _pads(c))
+        held = S.max_conditions(r, vals, args)                     # what the request is there for, on the tables that are compared
+        assert held == (c.request != "pad_lumpy", True, True), f"{c.request} on these tables: all padded / first padded / winner twice = {held}"
+        return vals, args
+    return _memo(("max", c.request, c.kind, tuple(c.dims)), make)
+
+
+def run_max(c, idt, layout, coracle):
+    """pm_embbag_fwd_max: values and ``max_indices`` of the slice into a NaN canvas and a canvas of -77, both equal to the rule bit
+    for bit and untouched elsewhere; then the lookup without ``max_indices`` (the WITH_ARG = false instances): the same value bits"""
+    from tests import max_rules as MX
+
+    torch = _torch()
+    r, (b0, n) = c.req, c.bags
+    m, tabs = module(c, layout)
+    it = torch.int64 if idt == "i64" else torch.int32
+    idx_t, off_t = _t(r.idx, it), _t(r.off, it)
+    check_plan(c, m._tables().request(idx_t, off_t, r.B, None, b0, n if c.bag_slice else None, forward=True))
+    want_v, want_a = max_reference(c, tabs)
+    want_a = _assemble(want_a, layout)
+    shape = (r.B, sum(c.dims)) if layout == "bd" else (r.T, r.B, c.dims[0])
+    sel = _sel(layout, b0, n)
+    rest = np.ones(shape, dtype=bool)
+    rest[sel] = False
+    odt = torch.float32 if c.out16 is None else m.output_dtype
+    assert (c.out16 is None) == (m.output_dtype in (None, torch.float32))
+    arg_canvas = torch.full(shape, -77, dtype=torch.int32, device=DEV)
+    canvas = torch.full(shape, float("nan"), dtype=odt, device=DEV)
+    res = m.lookup(idx_t, off_t, out=canvas, batch=r.B, bag_begin=b0, bag_count=n, max_indices=arg_canvas)
+    assert res[0] is canvas and res[1] is arg_canvas
+    plain = torch.full(shape, float("nan"), dtype=odt, device=DEV)
+    assert m.lookup(idx_t, off_t, out=plain, batch=r.B, bag_begin=b0, bag_count=n) is plain
+    if c.out16 is None:
+        want = _assemble(want_v, layout)
+        for what, t in (("values", canvas), ("values without max_indices", plain)):
+            got = t.cpu().numpy()
+            assert _same_f32(got[sel], want[sel]), f"{what}: {_first_diff(got[sel].view(np.uint32), want[sel].view(np.uint32))}"
+            assert np.isnan(got[rest]).all(), f"{what}: written outside the slice"
+    else:
+        want = _assemble(MX.round_out(want_v, c.out16), layout)
+        blank = _bits16(torch.full((1,), float("nan"), dtype=odt))[0]
+        for what, t in (("values", canvas), ("values without max_indices", plain)):
+            got = _bits16(t)
+            assert O16.same_bits(got[sel], want[sel], c.out16), f"{what}: {_first_diff(got[sel], want[sel])}"
+            assert (got[rest] == blank).all(), f"{what}: written outside the slice"
+        assert np.array_equal(_bits16(canvas), _bits16(plain)), "with and without max_indices"
+    got_a = arg_canvas.cpu().numpy()
+    assert np.array_equal(got_a[sel], want_a[sel]), f"max_indices: {_first_diff(got_a[sel], want_a[sel])}"
+    assert (got_a[rest] == -77).all(), "max_indices written outside the slice"
 
 
 def run_quantized(c, idt, layout, coracle):
@@ -287,7 +348,7 @@ def run_base(c, idt, layout, coracle):
 
 
 RUN = {"fwd": run_forward, "padded": run_forward, "mean": run_forward, "out16": run_forward, "quantized": run_quantized, "gather": run_gather,
-       "psw_grad": run_base, "mean_grad": run_base, "widen": run_base, "atomic": run_base}
+       "psw_grad": run_base, "mean_grad": run_base, "widen": run_base, "atomic": run_base, "max": run_max}
 
 
 def run_group(group, coracle, log=None):

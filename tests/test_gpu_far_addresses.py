@@ -9,7 +9,8 @@ pointer reaches 2^31 and 2^32, in bytes and in elements.
   not a fault), ``far`` is zero but for its probe rows and their neighbours.  Every result is compared as BITS with the existing rule on
   the twin; updates also with the same entry point on a small twin module, and the whole slab is scanned for stray writes.
 * ``test_out_*`` / ``test_grad_*`` -- far OUTPUT and GRADIENT rows: 64-row tables, bags of one lookup, D = 1024, and an output or gradient of more than 2^32
-  elements, checked whole on the device and around the thresholds against the rule modules on the host.
+  elements, checked whole on the device and around the thresholds against the rule modules on the host.  Max pooling's
+  ``max_indices`` and expanded gradient ``g_seq`` are such tensors too (``test_out_and_grad_of_a_max_module``).
 
 Not covered here: more than 2^31 LOOKUPS through the newer paths (17 GB of indices; tests/test_gpu_parity.py has that for the original
 forward and the sorted backward)."""
@@ -24,6 +25,7 @@ import torch
 from tests import elem_adagrad_rules as A
 from tests import embedding_rules as E
 from tests import far_rows as F
+from tests import max_rules as X
 from tests import mean_rules as M
 from tests import out16_rules as O
 from tests import padding_rules as P
@@ -132,6 +134,12 @@ def _u32(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
+def _far_arg(probes, twin_arg):
+    """the rule's arg-max on the twin as rows of the full table: the probe of every row, -1 where no lookup was kept"""
+    a = np.asarray(twin_arg).astype(np.int64)
+    return np.where(a >= 0, F.expand(probes, np.maximum(a, 0)), -1)
+
+
 def test_twin_equals_full_table_for_the_float_rules(coracle):
     """rule(full table, indices) == rule(twin, compact(indices)) bit for bit, for every rule the GPU tests below put on a twin"""
     D, es = 4, 4
@@ -156,6 +164,12 @@ def test_twin_equals_full_table_for_the_float_rules(coracle):
         assert all(np.array_equal(_u32(x), _u32(y)) for x, y in zip(a, b))
         a, b = O.forward(big, idx, off, B, pads_b, "bf16", mean=True), O.forward(small, cidx, off, B, pads_s, "bf16", mean=True)
         assert all(np.array_equal(x, y) for x, y in zip(a, b))
+        # max pooling: the values, and the arg-max after mapping the twin's rows through the probes
+        for pb, ps in (([None, None], [None, None]), (pads_b, pads_s)):
+            (va, aa), (vb, ab) = X.forward(big, idx, off, B, pb), X.forward(small, cidx, off, B, ps)
+            assert all(np.array_equal(_u32(x), _u32(y)) for x, y in zip(va, vb))
+            assert (aa[0] == -1).all() and (ab[0] == -1).all() and (ab[1] >= 0).any() and (ab[1] == -1).any()
+            assert np.array_equal(aa[1], _far_arg(probes, ab[1])) and aa[1].max() >= 2 ** 7 // (D * es) and not (aa[1] == (pb[1] or -2)).any()
         # the per_sample_weights gradient
         g = np.random.default_rng(4).standard_normal((B, 2 * D)).astype(np.float32)
         gs = [g[:, :D], g[:, D:]]
@@ -282,13 +296,13 @@ def variant(m, padding_idx=None, pooling_mode=None, output_dtype=None, optimizer
     module per option would allocate and zero 18 GiB again, so the options -- plain attributes the constructor sets and the methods
     read at call time -- are set here and put back; the optimizer state a block allocates is freed with it."""
     from param_amd.embedding_bag import _output_dtype
-    names = ("padding_idx", "pooling_mode", "_mean", "output_dtype", "_out16", "optimizer")
+    names = ("padding_idx", "pooling_mode", "_mean", "_max", "output_dtype", "_out16", "optimizer")
     keep = {k: getattr(m, k) for k in names if hasattr(m, k)}      # (the quantised module has the output dtype only)
     try:
         if padding_idx is not None:
             m.padding_idx = list(padding_idx)
         if pooling_mode is not None:
-            m.pooling_mode, m._mean = pooling_mode, pooling_mode == "mean"
+            m.pooling_mode, m._mean, m._max = pooling_mode, pooling_mode == "mean", pooling_mode == "max"
         if output_dtype is not None:
             m.output_dtype = _output_dtype(output_dtype)
             m._out16 = None if m.output_dtype == torch.float32 else m.output_dtype
@@ -505,6 +519,33 @@ def test_far_lookup_mean(far, which, it):
         got = m.lookup(idx, off, batch=B)
     want = far.rule(("mean", which), lambda: cat(M.forward(far.twin_f32(), cidx, off_h, B, [None, None])))
     assert np.array_equal(_bits(got), _u32(want))
+
+
+@on_floats
+@pytest.mark.parametrize("pad", ["none", "byte32"])
+@WHICH
+@IT
+def test_far_lookup_max(far, pad, which, it):
+    """``pm_embbag_fwd_max`` on the far module (the max flag set for the block: no second slab): the staged walk's ``row_offset<true>``,
+    the unstaged walk's ``row_offset<false>``; ``max_indices`` holds the far row numbers themselves"""
+    from param_amd import _lib
+    k = None if pad == "none" else far.pad_byte32
+    idx_h, cidx, off_h, _, idx, off, _ = far.case(which, it)
+    ck = None if k is None else int(F.compact(far.probes, np.array([k]))[0])
+    assert k is None or ((idx_h == k).any() and k * far.D * far.es >= 2 ** 32)
+    with variant(far.m, pooling_mode="max", padding_idx=None if k is None else [None, k]) as m:
+        assert m._max and not m._mean
+        assert_path(float_plan(far, _lib.PM_PLAN_PADDED, idx, off, None), which, "pm_embbag_fwd_max")
+        got, arg = m.lookup(idx, off, batch=B, return_max_indices=True)
+        plain = m.lookup(idx, off, batch=B)
+    assert not far.m._max and far.m.pooling_mode == "sum"
+    want_v, want_a = far.rule(("max", ck, which), lambda: X.forward(far.twin_f32(), cidx, off_h, B, [None, ck]))
+    assert got.shape == (B, 2 * far.D) and np.array_equal(_bits(got), _u32(cat(want_v))) and np.array_equal(_bits(plain), _bits(got))
+    a = arg.cpu().numpy().astype(np.int64)
+    assert arg.dtype == torch.int32 and np.array_equal(a, cat([_far_arg(far.probes, w) for w in want_a]))
+    assert (a[:, :far.D] == -1).all() and a.max() * far.D * far.es >= 2 ** 32 and (a[LENS[which].index(0)] == -1).all()
+    if k is not None:      # (looked up, asserted above, and never the arg-max; whether it would win a column is the content's accident)
+        assert not (a == k).any()
 
 
 @on_floats
@@ -961,4 +1002,57 @@ def test_grad_dense_grad_of_a_mean_module(out):
     outs = m.dense_grad(g, idx, off, batch=N3)
     _assert_row_sums(outs, _grad_expectation(idx))
     del g
+    torch.cuda.empty_cache()
+
+
+@gpu
+def test_out_and_grad_of_a_max_module():
+    """max pooling's four new address computations beyond 2^32 elements: the bf16 values and the int32 ``max_indices`` of
+    ``pm_embbag_fwd_max`` (``arg_out + out_offsets[t] + (bag0 + bg) * out_stride + c``), then ``grad``, ``max_indices`` and ``g_seq`` of
+    ``pm_embbag_max_grad`` (``row + c4 * 4``, ``g_seq + j * g_stride``).  Bags of one lookup: a value is one rounding of the table row and
+    its arg-max the looked-up row in every column (+0.0 and -1 for the bags that look up the padding row); a gradient row lands whole in
+    that row, so the sums are the exact integers of ``_grad_expectation`` without the padded bags."""
+    import param_amd
+    from param_amd import _lib
+
+    _close_far()
+    # the values (2 bytes) next to max_indices (4); then, the values freed, max_indices (4), grad (2) and g_seq (4): 40 GiB
+    _need(N3 * D3 * (4 + 2 + 4) + 2 * N3 * 8 + 4 * GIB, "max pooling: max_indices, grad and g_seq")
+    x = _table3(11)
+    pad = 5
+    m = param_amd.MaxBatchedEmbeddingBagMI355([ROWS3], D3, device=DEV, init=None, fused_update=False, padding_idx=pad, output_dtype="bf16")
+    m.table(0).copy_(_dev(x))
+    idx = _idx3()
+    off = torch.arange(N3 + 1, dtype=torch.int64, device=DEV)
+    plan = _lib.embbag_plan(m._tables().request(idx, off, N3, None, 0, None, forward=True), _lib.PM_PLAN_PADDED16)
+    print(f"far max output: {plan}")
+    assert plan["tiles_per_table"] * plan["bags_per_block"] >= N3 and N3 * D3 > 2 ** 32
+    got, arg = m.lookup(idx, off, batch=N3, return_max_indices=True)
+    padded = idx == pad
+    n_pad = int(padded.sum())
+    assert 0 < n_pad < N3 // 32
+    x[pad] = 0.0
+    _check_far_output(got, idx, _dev(x).to(torch.bfloat16), lambda r: O.round16(x[r], "bf16"), "max pooled output bf16")
+    del got
+    torch.cuda.empty_cache()
+    # max_indices: every column of row b is idx[b], -1 for a padded bag -- whole on the device, around the thresholds on the host
+    assert tuple(arg.shape) == (N3, D3) and arg.dtype == torch.int32
+    want_arg = torch.where(padded, torch.full_like(idx, -1), idx).to(torch.int32)
+    bad = 0
+    for a in range(0, N3, CHUNK):
+        b = min(N3, a + CHUNK)
+        bad += int((arg[a:b] != want_arg[a:b, None]).any(dim=1).sum())
+    assert bad == 0, f"max_indices: {bad} of {N3} rows differ"
+    want_h = want_arg.cpu().numpy()
+    cs = _threshold_rows3(4)
+    assert {(2 ** 31) // D3, (2 ** 32) // D3} <= set(cs)
+    for c in cs:
+        assert np.array_equal(arg[c - 32:c + 32].cpu().numpy(), np.broadcast_to(want_h[c - 32:c + 32, None], (64, D3))), ("max_indices", c)
+    # the gradient: grad and max_indices read, g_seq written and read, beyond 2^32 elements each
+    g = _grad3(torch.bfloat16)
+    outs = m.dense_grad(g, idx, off, batch=N3, max_indices=arg)
+    want = _grad_expectation(idx)
+    want[pad] = 0.0
+    _assert_row_sums(outs, want)
+    del g, arg, outs
     torch.cuda.empty_cache()

@@ -4,9 +4,12 @@
 Forward (``pm_embbag_fwd_max``): values and ``max_indices`` over the widths, table dtypes, index dtypes and layouts, with the special
 values (NaN first / later, signed zeros, ties, negative rows, -Inf) and bag lengths 0, 1, 2, 3 and 5 in the request; the unstaged path
 (a bag of 5000 lookups), staging that compacts padding over several rounds, batch slices, 16-bit output, the sanitiser in front.
-Backward: the expansion kernel (``pm_embbag_max_grad``) against the rule's ``g_seq``; ``dense_grad`` / ``scatter_add_`` against the
-sequence calls fed the numpy-expanded gradient and against the rule; ``MaxEmbeddingBagMI355`` autograd against torch's recorded
-gradient; 1100 tables."""
+Backward: the expansion kernel (``pm_embbag_max_grad``) against the rule's ``g_seq`` at every lane-group width (D = 8 .. 512: 8, 16, 32
+and 64 lanes a bag, one and two rounds a lane), both index types and a bag of 5000 positions; ``dense_grad`` / ``scatter_add_`` against the
+sequence calls fed the numpy-expanded gradient and against the rule, at D = 8 and at every other width; ``MaxEmbeddingBagMI355``
+autograd against torch's recorded gradient; 1100 tables.  The forward's other plans (tiles of several bags per lane group, 1024-bag
+tiles, the bursts against row stores, the XCD mappings ...) are run by tests/test_gpu_plan_sweep.py, its far addresses by
+tests/test_gpu_far_addresses.py."""
 import ctypes
 
 import numpy as np
@@ -266,14 +269,31 @@ def test_bounds_check_ignore_repairs_the_request_first():
     assert np.array_equal(_bits(out), _bits(_join(want_v, "bd"))) and np.array_equal(arg.cpu().numpy(), _join(want_a, "bd"))
 
 
-@pytest.mark.parametrize("gdt", [torch.float32, torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("layout", ["bd", "tbd"])
-def test_the_expansion_kernel_is_the_rules_g_seq(gdt, layout):
+def _expansion_cases():
+    """(gdt, layout, D, idt) and ids.  ``launch_max_grad`` gives a bag G = group_lanes(D, 4) lanes, 4 columns a lane and round:
+    D = 8, 64, 128, 132 and 512 are G = 8, 16, 32, 64 and 64 with two rounds (256 / G = 32 .. 4 bags per workgroup).  The first six
+    are the cases this test always had, under the ids it always had; then every width with fp32 and with a 16-bit gradient, both index
+    types at D = 8 and at D = 512."""
+    f32, bf16, f16, i32, i64 = torch.float32, torch.bfloat16, torch.float16, torch.int32, torch.int64
+    cases = [(g, lay, 8, i64) for lay in ("bd", "tbd") for g in (f32, bf16, f16)]
+    ids = [f"{lay}-gdt{k}" for lay in ("bd", "tbd") for k in range(3)]
+    more = [(f32, "bd", 8, i32), (bf16, "tbd", 8, i32), (f32, "bd", 64, i64), (bf16, "tbd", 64, i32), (f32, "tbd", 128, i32), (f16, "bd", 128, i64),
+            (f32, "bd", 132, i64), (bf16, "tbd", 132, i32), (f32, "bd", 512, i64), (f32, "tbd", 512, i32), (f16, "bd", 512, i32), (bf16, "tbd", 512, i64)]
+    name = {f32: "f32", bf16: "bf16", f16: "f16", i32: "i32", i64: "i64"}
+    assert {(D, g == f32) for g, _, D, _ in cases + more} == {(D, f) for D in (8, 64, 128, 132, 512) for f in (False, True)}
+    assert {(D, i) for _, _, D, i in cases + more} >= {(D, i) for D in (8, 512) for i in (i32, i64)}
+    return cases + more, ids + [f"{lay}-{name[g]}-D{D}-{name[i]}" for g, lay, D, i in more]
+
+
+@pytest.mark.parametrize("gdt,layout,D,idt", _expansion_cases()[0], ids=_expansion_cases()[1])
+def test_the_expansion_kernel_is_the_rules_g_seq(gdt, layout, D, idt):
     from param_amd import embedding_bag as EB
+    from tests.plan_sweep import group_lanes
 
     rng = np.random.default_rng(10)
-    rows, D, B = (50, 17, 300), 8, 23
+    rows, B = (50, 17, 300), 23
     pads = (11, None, 299)
+    assert (group_lanes(D, 4), D > 256) == {8: (8, False), 64: (16, False), 128: (32, False), 132: (64, False), 512: (64, True)}[D]
     out16 = None if gdt == torch.float32 else gdt
     m, tabs = _model(rows, D, "f32", pads, layout, output_dtype=out16)
     idx_h, off_h = _request(rng, rows, B, pads)
@@ -282,11 +302,85 @@ def test_the_expansion_kernel_is_the_rules_g_seq(gdt, layout):
     g[0].fill_(-0.0)
     grads = _split(g.float(), [D] * 3, layout)
     arg = _dev(_join(want_a, layout))
-    idx, off = _dev(idx_h), _dev(off_h)
+    idx, off = _dev(idx_h, idt), _dev(off_h, idt)
+    # a bag that holds its arg-max row at two positions (table 1, bag 6: [8, 8]), inside both slices, with a gradient that is not zero
+    t2, b2 = 1, 6
+    j1 = int(off_h[t2 * B + b2])
+    assert off_h[t2 * B + b2 + 1] == j1 + 2 and idx_h[j1] == idx_h[j1 + 1] and (want_a[t2][b2] == idx_h[j1]).all() and (grads[t2][b2] != 0).all()
     for b0, nb in ((0, B), (5, 11)):
         want, written = M.expand(idx_h, off_h, B, grads, want_a, b0, nb)
         got = EB._max_expand(m._tables(), g, arg, idx, off, B, b0, nb, out16).cpu().numpy()
-        assert written.any() and np.array_equal(_bits(got[written]), _bits(want[written])), (b0, nb)
+        assert got.shape == (idx_h.size, D) and written.any() and np.array_equal(_bits(got[written]), _bits(want[written])), (b0, nb)
+        assert b0 <= b2 < b0 + nb and np.array_equal(_bits(got[j1]), _bits(grads[t2][b2])) and (_bits(got[j1 + 1]) == 0).all(), (b0, nb)
+
+
+@pytest.mark.parametrize("D", [8, 132])
+@pytest.mark.parametrize("padded", [False, True])
+def test_the_expansion_of_a_bag_of_thousands_of_positions(padded, D):
+    """one lane group walks 5000 positions (the request of ``test_a_bag_beyond_the_index_tile_takes_the_unstaged_path``); the gradient
+    with the saved ``max_indices`` and with the recomputed ones"""
+    from param_amd import embedding_bag as EB
+
+    rng = np.random.default_rng(15)
+    rows, B = (300,), 3
+    pads = (7,) if padded else (None,)
+    m, tabs = _model(rows, D, "f32", pads, seed=15)
+    long_bag = rng.integers(0, 300, size=5000)
+    if padded:
+        long_bag[rng.random(5000) < 0.3] = 7
+        long_bag[0] = 7
+    idx_h = np.concatenate([[8, 9], long_bag, [10]]).astype(np.int64)
+    off_h = np.array([0, 2, 5002], dtype=np.int64)
+    idx, off = _dev(idx_h), _dev(off_h)
+    want_v, want_a = M.forward(tabs, idx_h, off_h, B, pads)
+    out, arg = m.lookup(idx, off, batch=B, return_max_indices=True)
+    assert np.array_equal(arg.cpu().numpy(), want_a[0])
+    g = torch.randn(B, D, device=DEV)
+    want, written = M.expand(idx_h, off_h, B, [g.cpu().numpy()], want_a)
+    assert written.all() and len(np.unique(want_a[0][1])) > 1 and (np.bincount(long_bag)[want_a[0][1]] > 1).any()      # rows met again later
+    got = EB._max_expand(m._tables(), g, arg, idx, off, B)
+    assert np.array_equal(_bits(got), _bits(want))
+    assert (_bits(got[2:5002]) != 0).any(axis=1).sum() == len(np.unique(want_a[0][1]))      # one position per winning row, +0.0 elsewhere
+    saved = m.dense_grad(g, idx, off, batch=B, max_indices=arg)
+    again = m.dense_grad(g, idx, off, batch=B, max_indices=None)
+    assert np.array_equal(_bits(saved[0]), _bits(again[0])) and saved[0].any()
+    if padded:
+        assert not saved[0][7].any()
+
+
+@pytest.mark.parametrize("dname,D", [("f32", 64), ("f32", 132), ("f32", 512), ("bf16", 256)])
+def test_dense_grad_is_the_rule_at_every_width(dname, D):
+    """``dense_grad`` and ``scatter_add_`` end to end where the expansion runs 16, 32 and 64 lanes a bag and two rounds a lane"""
+    rng = np.random.default_rng(14)
+    rows, B = (50, 17, 300), 330
+    pads = (11, None, 299)
+    m, tabs = _model(rows, D, dname, pads, seed=14)
+    s, _ = _model(rows, D, dname, pads, mode="sum", seed=14)
+    same = lambda: all(np.array_equal(_bits(m.table(t)), _bits(s.table(t))) for t in range(3))      # noqa: E731
+    assert same()
+    idx_h, off_h = _hot_request(rng, rows, B, pads, 0)
+    for t in range(3):
+        assert np.bincount(idx_h[off_h[t * B]:off_h[(t + 1) * B] if t < 2 else idx_h.size]).max() <= 256      # (the sorted apply's exact-run limit)
+    idx, off = _dev(idx_h), _dev(off_h)
+    out, arg = m.lookup(idx, off, batch=B, return_max_indices=True)
+    want_v, want_a = M.forward(tabs, idx_h, off_h, B, pads)
+    assert np.array_equal(arg.cpu().numpy(), _join(want_a, "bd"))
+    g = torch.randn(B, 3 * D, device=DEV)
+    grads = _split(g, [D] * 3, "bd")
+    want = M.dense_grad(rows, [D] * 3, grads, want_a)
+    for mi in (arg, None):
+        got = m.dense_grad(g, idx, off, batch=B, max_indices=mi)
+        for t in range(3):
+            assert got[t].dtype == torch.float32 and np.array_equal(_bits(got[t]), _bits(want[t])), (t, mi is None)
+    assert all(w.any() for w in want)
+    g_seq, written = M.expand(idx_h, off_h, B, grads, want_a)
+    assert written.all()
+    m.scatter_add_(g, idx, off, alpha=-0.5, batch=B, max_indices=arg)
+    s.sequence_scatter_add_(_dev(g_seq), idx, off, alpha=-0.5, batch=B)
+    assert same() and not np.array_equal(_bits(m.table(2).float()), _bits(tabs[2]))
+    for t, p in enumerate(pads):
+        if p is not None:
+            assert np.array_equal(_bits(m.table(t)[p].float()), _bits(tabs[t][p]))
 
 
 def _hot_request(rng, rows, B, pads, hot):

@@ -1,9 +1,10 @@
 """Every forward kernel variant the launch plan can choose, run on a real MI355X (``pytest -m gpu``).
 
 The forward is several hundred template instances -- ``embbag_fwd_kernel<WT, G, UNROLL, WEIGHTED, ORDERED, STAGE>``,
-``embbag_fwd_flat_kernel<WT, G, UNROLL, WEIGHTED>``, ``pad_fwd_kernel<WT, G, WEIGHTED, MEAN, OT>`` and the row gather with an unroll of
-its own -- and param_amd/csrc/launch_plan.h picks one from a request's sizes and the tuning knobs.  Small requests under default knobs all
-land in one corner of that plan (one bag per lane group, the flat walk, unroll 2, 4 or 8).  The cases of tests/plan_sweep.py set an explicit
+``embbag_fwd_flat_kernel<WT, G, UNROLL, WEIGHTED>``, ``pad_fwd_kernel<WT, G, WEIGHTED, MEAN, OT>``, ``max_fwd_kernel<WT, G, OT, WITH_ARG>``
+and the row gather with an unroll of its own -- and param_amd/csrc/launch_plan.h picks one from a request's sizes and the tuning knobs.
+Small requests under default knobs all land in one corner of that plan (one bag per lane group, the flat walk, unroll 2, 4 or 8).
+The cases of tests/plan_sweep.py set an explicit
 tile, unroll, XCD mapping, grid or environment switch so that a few hundred bags over 1000-row tables take the variants the product
 takes at benchmark size: the longest-bag-first kernel with its bitonic and rank-counting orders, staged 32-bag tiles, unrolls 1, 3 and
 6 with their tails, 1024-bag padded tiles and their launcher's 64 KB fallback, the old flat grid, tile-major order.
@@ -11,9 +12,9 @@ takes at benchmark size: the longest-bag-first kernel with its bitonic and rank-
 For every case: the knobs are set, ``pm_embbag_plan`` must report the plan pinned in tests/plan_sweep_host.json (so the comparison is
 known to be of THAT variant, environment included), the entry point runs with int64 and int32 indices and both layouts, and the output
 must equal the rule of its operation bit for bit -- ``coracle.fwd_batched``, ``padding_rules.forward``, ``mean_rules.forward``,
-``out16_rules.forward``, ``embedding_rules.forward``, the rowquant reference and the default-knob bytes; a batch slice writes into a
-NaN canvas that must stay NaN elsewhere.  The entry points on the base plan equal their default-knob bits and their rule; the one
-non-deterministic entry, the alternates' atomic backward, is held to the fuzz test's 1e-5 bar.  No tolerance is new.
+``out16_rules.forward``, ``max_rules.forward`` (values and ``max_indices``, with and without the arg-max output), ``embedding_rules.forward``,
+the rowquant reference and the default-knob bytes; a batch slice writes into a NaN canvas that must stay NaN elsewhere.  The entry
+points on the base plan equal their default-knob bits and their rule; the one non-deterministic entry, the alternates' atomic backward, is held to the fuzz test's 1e-5 bar.  No tolerance is new.
 
 One test is one group: a few dozen launches on one small request.  The groups with an environment setting run in a fresh child each
 (``python -m tests.plan_sweep_worker GROUP``), one after another, each under its own time limit; once a child has died of a signal or

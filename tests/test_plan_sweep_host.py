@@ -137,6 +137,7 @@ def test_the_sweep_reaches_every_variant():
     rows = _pinned()
     cases = [(c, set(rows[c.name]["label"].split()), dict(zip(S.PLAN_FIELDS, rows[c.name]["plan"]))) for c in S.CASES]
     missing = []
+    from tests import plan_sweep_worker as W
 
     def need(what, cond, at_least=1):
         if sum(1 for c, w, p in cases if cond(c, w, p)) < at_least:
@@ -202,6 +203,39 @@ def test_the_sweep_reaches_every_variant():
             need(f"{fam}: G{G}", lambda c, w, p: pad(c) and {"pad", f"G{G}", "tile>NG"} <= w)
     need("D = 512 bf16 tables, 4-byte outputs: not staged", lambda c, w, p: c.entry == "padded" and {"pad", "bf16", "plain"} <= w and c.dims[0] == 512)
     need("D = 512 bf16 tables, 2-byte outputs: staged", lambda c, w, p: c.entry == "out16" and {"pad", "bf16", "staged"} <= w and c.dims[0] == 512)
+    # max pooling: pm_embbag_fwd_max on the padded family's plan, for fp32 and for bf16 output
+    for fam, o16 in (("max", None), ("max bf16", "bf16")):
+        mx = lambda c, w: c.entry == "max" and c.out16 == o16 and not c.env and c.req.pads is not None and "max" in w  # noqa: E731
+        need(f"{fam}: 32 bags staged", lambda c, w, p: mx(c, w) and {"pad", "bpb32", "staged", "partial"} <= w)
+        need(f"{fam}: 32 bags, stage_out 0", lambda c, w, p: mx(c, w) and {"pad", "bpb32", "plain"} <= w and c.forward.get("stage_out") == 0)
+        need(f"{fam}: 1024 bags staged", lambda c, w, p: mx(c, w) and {"pad", "bpb1024", "staged", "tile>NG"} <= w and c.req.B > 1024)
+        for x in (0, 1, 3):
+            need(f"{fam}: xcd_affine {x}", lambda c, w, p: mx(c, w) and {"pad", f"xcd{x}"} <= w)
+        need(f"{fam}: nt_loads", lambda c, w, p: mx(c, w) and {"pad", "nt1"} <= w)
+        need(f"{fam}: slice", lambda c, w, p: mx(c, w) and {"pad", "slice", "partial"} <= w and c.bag_slice[0] > 0)
+        for G in (8, 16, 32, 64):
+            need(f"{fam}: G{G}", lambda c, w, p: mx(c, w) and {"pad", f"G{G}", "tile>NG"} <= w)
+        need(f"{fam}: G16 on fp32 tables", lambda c, w, p: mx(c, w) and {"pad", "f32", "G16", "tile>NG"} <= w)
+        for kind16 in ("bf16", "f16"):             # (a 16-bit table's 16-bit output is its own type: fp16 tables give fp16)
+            for G in (32, 64):
+                need(f"{fam}: {kind16} tables G{G}", lambda c, w, p: c.entry == "max" and (c.out16 is None) == (o16 is None) and not c.env
+                     and {"pad", "max", kind16, f"G{G}", "tile>NG"} <= w and c.dims[0] == G * 8)
+        need(f"{fam}: fp32 rows of 512, two column passes", lambda c, w, p: mx(c, w) and {"pad", "f32", "G64", "tile>NG"} <= w and c.dims[0] == 512)
+        need(f"{fam}: direct on a 32-bag tile", lambda c, w, p: mx(c, w) and {"pad", "bpb32", "direct", "tile>NG"} <= w and p["idx_cap"] == 1280)
+        need(f"{fam}: mixed dims", lambda c, w, p: mx(c, w) and "pad" in w and c.dims == [16, 64, 128] and {lay for _, lay in W.variants(c)} == {"bd"})
+    need("max: fp16 output", lambda c, w, p: c.entry == "max" and c.out16 == "fp16" and c.kind == "f32" and {"pad", "max", "bpb32", "staged"} <= w)
+    need("max: D = 512 16-bit tables, 4-byte outputs: not staged",
+         lambda c, w, p: c.entry == "max" and c.out16 is None and {"pad", "max", "plain"} <= w and c.dims[0] == 512 and c.kind != "f32", 2)
+    need("max: D = 512 16-bit tables, 2-byte outputs: staged",
+         lambda c, w, p: c.entry == "max" and c.out16 is not None and {"pad", "max", "staged"} <= w and c.dims[0] == 512 and c.kind != "f32", 2)
+    need("max: FWD_STAGE=0", lambda c, w, p: c.entry == "max" and c.env.get("PARAM_AMD_FWD_STAGE") == 0 and {"pad", "max", "bpb32", "plain"} <= w)
+    # the launcher's 64 KB fallback (embbag_fwd_max.hip: launch_max_a) is out of reach without weights: no max case plans past it
+    for c, w, p in cases:
+        if c.entry == "max":
+            assert "max" in w and S.pad_lds_bytes(c, rows[c.name]["plan"]) <= 65536, c.name
+            assert c.plan_kind == ("padded4" if c.out16 is None else "padded2") and not c.weighted and not c.mean, c.name
+        else:
+            assert "max" not in w, c.name
     # quantized, gather, base
     for u in (1, 3, 6):
         need(f"quantized u{u}", lambda c, w, p: c.entry == "quantized" and {"tile", "staged", "bpb32", f"u{u}"} <= w)
@@ -222,13 +256,32 @@ def test_the_sweep_reaches_every_variant():
     need("FLAT_COMPACT=0", lambda c, w, p: env(c, "PARAM_AMD_FLAT_COMPACT", 0) and {"flat", "old-grid"} <= w, 4)
     need("FLAT_BAGS=48", lambda c, w, p: env(c, "PARAM_AMD_FLAT_BAGS", 48) and {"flat", "bpb48", "target64"} <= w, 2)
     need("FWD_STAGE=0: forward", lambda c, w, p: env(c, "PARAM_AMD_FWD_STAGE", 0) and {"tile", "plain"} <= w, 2)
-    need("FWD_STAGE=0: padded family", lambda c, w, p: env(c, "PARAM_AMD_FWD_STAGE", 0) and {"pad", "plain"} <= w, 2)
+    need("FWD_STAGE=0: padded family", lambda c, w, p: env(c, "PARAM_AMD_FWD_STAGE", 0) and {"pad", "plain"} <= w and "max" not in w, 2)
     assert not missing, missing
     assert len(S.ENV_GROUPS) == 6 and len({tuple(sorted(c.env.items())) for c in S.CASES if c.env}) == 6
     assert all(max(c.req.rows) <= 1000 for c in S.CASES)
     # both index types and, where the dims are equal, both layouts: every case runs them (tests/plan_sweep_worker.py: variants)
-    from tests import plan_sweep_worker as W
-
     for c in S.CASES:
         v = W.variants(c)
         assert {i for i, _ in v} == {"i64", "i32"} and (len(set(c.dims)) > 1 or c.entry == "gather" or {lay for _, lay in v} == {"bd", "tbd"}), c.name
+
+
+def test_the_padded_requests_serve_max_pooling():
+    """the requests of the max cases were drawn for sums: under the max rule each of them still holds a bag whose lookups are all
+    padded (+0.0, -1), a bag whose first lookup is padded and a bag that holds a winning row at two positions.  Checked with the rule on
+    tables of 8 normal columns; the GPU worker asserts the same on the tables it compares (tests/plan_sweep_worker.py: max_reference)."""
+    import numpy as np
+
+    from tests import max_rules as MX
+
+    names = sorted({c.request for c in S.CASES if c.entry == "max"})
+    assert set(names) == {"pad100", "pad1100", "pad8", "padfix", "pad_lumpy"}
+    for name in names:
+        r = S.request(name)
+        assert r.pads is not None and any(k is not None for k in r.pads) and r.N <= 11000
+        tabs = [np.random.default_rng(70 + t).standard_normal((rows, 8)).astype(np.float32) for t, rows in enumerate(r.rows)]
+        vals, args = MX.forward(tabs, r.idx, r.off, r.B, r.pads)
+        # (pad_lumpy's bags hold 80 and 100 lookups for the index tile's sake: none is padded throughout)
+        assert S.max_conditions(r, vals, args) == (name != "pad_lumpy", True, True), (name, S.max_conditions(r, vals, args))
+    lumpy, plain = S.request("pad_lumpy"), S.request("even_lumpy")
+    assert np.array_equal(lumpy.lens, plain.lens) and lumpy.rows == plain.rows      # (the plan is a function of the sizes)
