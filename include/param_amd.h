@@ -33,6 +33,8 @@ enum {
     PM_F32 = 0,
     PM_BF16 = 1,
     PM_F16 = 2,
+    PM_F8E4M3 = 3,           /* OCP FP8 e4m3fn: table element of pm_embbag_fwd_f8 / pm_embedding_gather_f8 only (FP8 TABLES) */
+    PM_F8E5M2 = 4,           /* OCP FP8 e5m2: likewise */
     PM_I32 = 10,
     PM_I64 = 11
 };
@@ -742,6 +744,51 @@ int pm_embbag_fwd_qrows_pruned(const pm_embbag_batch* op, const int32_t* table_b
                                int32_t out_dtype, void* out, pm_stream_t stream);
 int pm_embedding_gather_qrows_pruned(const pm_embbag_batch* op, const int32_t* table_bits, const int32_t* remap, const int64_t* remap_offsets,
                                      int32_t out_dtype, void* out, int64_t out_row_stride, pm_stream_t stream);
+
+/*
+ * FP8 TABLES -- the pooled and the un-pooled lookup over tables stored in OCP FP8: one byte per element, no scale, no bias.
+ * op->weight_dtype is PM_F8E4M3 (e4m3fn) or PM_F8E5M2 (e5m2), one format per request; op->tables[t] points at uint8 [rows[t], dims[t]],
+ * row-major, rows back to back, 16-byte aligned; dims[t] % 16 == 0, dims[t] <= 2048.  A D = 128 row is one aligned 128-byte line.
+ * dec(code), the fp32 value of a byte:
+ *   e4m3fn  1 sign, 4 exponent (bias 7), 3 mantissa bits; no infinities; 0x7f / 0xff are NaN; exponent field 0 is subnormal
+ *           (mantissa / 8 * 2^-6); the largest value is 448 (0x7e);
+ *   e5m2    1 sign, 5 exponent (bias 15), 2 mantissa bits, IEEE-like: 0x7c / 0xfc are +-Inf, 0x7d-0x7f / 0xfd-0xff are NaN; code << 8 is
+ *           the fp16 pattern of the same value.
+ * Subnormal codes decode exactly, 0x80 is -0.0, and every non-NaN code is exact in fp32, bf16 and fp16.  A NaN code gives a NaN; its
+ * sign and payload are not part of the rule.  (gfx950 converts these two formats in hardware; the fnuz formats of MI300 are others.)
+ * THE RULE, pooled (pm_embbag_fwd_f8): the padded family's rule over the decoded table.  Lookups whose index equals padding_idx[t] are
+ * removed first (padding_idx: device int64 [num_tables], -1 = the table has no padding row; NULL = no table has one).  Then per column,
+ * from acc = +0.0 in index order: acc = acc + dec(code) -- with per_sample_weights acc = fmaf(w_j, dec(code), acc).  mean == 1: one
+ * correctly rounded fp32 division by the number of kept lookups; a bag that is empty or all padding gives +0.0 (no division).
+ * out_dtype PM_F32, or PM_BF16 / PM_F16: that fp32 value rounded ONCE, in registers, as pm_embbag_fwd_out16 rounds; out is addressed
+ * like pm_embbag_fwd's in elements of out_dtype (out_offsets[t] + b * out_stride).  It is what pm_embbag_fwd_padded / _mean / _out16
+ * give over the table widened to fp32, and torch.nn.functional.embedding_bag(indices, table.to(torch.float32), ...) on the CPU, bit
+ * for bit (tests/f8_rules.py restates it, tests/test_f8_host.py pins it to torch).
+ * THE RULE, un-pooled (pm_embedding_gather_f8): the request and the addressing of UN-POOLED LOOKUPS above; for every lookup position j
+ * that belongs to a bag inside the slice, out[j * out_row_stride + c] = conv(dec(table_t[indices[j], c])), c < dims[t]; nothing else of
+ * out is touched.  The widening is exact for all three out_dtypes: -0.0, subnormals and +-Inf leave as they are stored.  No padding_idx.
+ * Kernels: csrc/embbag_fwd_f8_kernel.inc -- the padded forward's tiling (bag offsets and compacted indices in LDS, tiles beyond the
+ * index tile read from the request, the LDS output burst), sixteen columns per lane, 2 / 4 / 8 rows in flight per lane group -- and
+ * csrc/embedding_gather_f8.hip -- pm_embedding_gather's tiles with four columns per lane, so that every store instruction of a lane
+ * group writes consecutive pieces of the row.  No atomics, no workspace, no allocation, stream-ordered; 64-bit row addressing.
+ * Refused on the host, before any HIP call: what pm_embbag_fwd / pm_embedding_gather refuse about a request; a weight_dtype other than
+ * the two (PM_ERR_INVALID); max_dim or min_dim not a multiple of 16, max_dim > 2048, a non-zero table_group / grad_block_shift /
+ * grad_block_extra (PM_ERR_UNSUPPORTED); an unknown out_dtype, mean not 0 / 1 (PM_ERR_INVALID); per_sample_weights with mean == 1 or
+ * for the gather (PM_ERR_UNSUPPORTED); out_row_stride < max_dim or not a multiple of 4 (PM_ERR_INVALID).  An empty request (bag_count
+ * == 0; the gather: num_indices == 0 as well) is then PM_OK without a launch; otherwise a NULL out, or one that is not 16-byte (PM_F32)
+ * / 8-byte (16-bit) aligned, is PM_ERR_INVALID.  Every other entry point keeps refusing the two dtypes.
+ * pm_embbag_f8_plan / pm_embedding_gather_f8_plan: the geometry the two calls WOULD use (plan_f8, plan_gather_f8, csrc/launch_plan.h) --
+ * the twelve members of pm_embbag_plan (unroll 2 / 4 / 8: pm_set_tuning's unroll, below 4 -> 2, below 8 -> 4; default 2) and the eight of
+ * pm_embedding_gather_plan (vec = 4) in their order.  Host only; they validate the request as the launching calls do.
+ * Replaces the forward of fbgemm's IntNBitTableBatchedEmbeddingBagsCodegen for SparseType.FP8 tables.  Left out: a quantiser and any
+ * scaling (per-row or per-table scales), the fnuz formats, FP8 output, a format per table, FP8 next to 8- / 4-bit tables in one launch,
+ * max pooling, pruning, any backward (the tables are not trainable).
+ * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these four finds out at symbol resolution.
+ */
+int pm_embbag_fwd_f8(const pm_embbag_batch* op, const int64_t* padding_idx, int32_t mean, int32_t out_dtype, void* out, pm_stream_t stream);
+int pm_embbag_f8_plan(const pm_embbag_batch* op, int32_t out_dtype, int32_t out[12]);
+int pm_embedding_gather_f8(const pm_embbag_batch* op, int32_t out_dtype, void* out, int64_t out_row_stride, pm_stream_t stream);
+int pm_embedding_gather_f8_plan(const pm_embbag_batch* op, int64_t out[8]);
 
 /*
  * SEQUENCE GRADIENTS -- the batched backward of the un-pooled lookup above: the gradient of pm_embedding_gather's rows applied to all

@@ -7,6 +7,8 @@ Layout (only what the hot path needs):
                      MaxEmbeddingBagMI355 / MaxBatchedEmbeddingBagMI355 (max pooling)
   quantized_bag.py   QuantizedBatchedEmbeddingBagMI355 / QuantizedEmbeddingBagMI355 / QuantizedEmbeddingMI355: pooled and un-pooled
                      lookups over 8- / 4-bit row-quantised tables
+  float8_bag.py      Float8BatchedEmbeddingBagMI355 / Float8EmbeddingBagMI355 / Float8EmbeddingMI355: pooled and un-pooled lookups
+                     over OCP FP8 (e4m3fn / e5m2) tables
   indices.py         uniform / Zipf index generation (reference init_indices + a scalable form)
   compute/pt/        mirror of the reference train/compute/pt emb driver CLI
   comms/pt/          mirror of the reference train/comms/pt backend plug-in, metrics and drivers
@@ -22,5 +24,6 @@ from .embedding_bag import (  # noqa: F401
     fill_random_,
 )
 from .quantized_bag import QuantizedBatchedEmbeddingBagMI355, QuantizedEmbeddingBagMI355, QuantizedEmbeddingMI355  # noqa: F401
+from .float8_bag import Float8BatchedEmbeddingBagMI355, Float8EmbeddingBagMI355, Float8EmbeddingMI355  # noqa: F401
 
 __version__ = "0.1.0"

@@ -100,7 +100,13 @@ EXPORTED_SYMBOLS = (
     "pm_embedding_gather_qrows_mixed_plan",
     "pm_embbag_fwd_qrows_pruned",
     "pm_embedding_gather_qrows_pruned",
+    "pm_embbag_fwd_f8",
+    "pm_embbag_f8_plan",
+    "pm_embedding_gather_f8",
+    "pm_embedding_gather_f8_plan",
 )
+# table element types of the FP8 lookups alone (include/param_amd.h, FP8 TABLES): every other entry point refuses them
+PM_F8E4M3, PM_F8E5M2 = 3, 4
 
 # pm_embbag_plan (include/param_amd.h): the kinds, and the members of the two plans in the order the queries fill them
 PM_PLAN_BASE, PM_PLAN_FORWARD, PM_PLAN_QUANTIZED, PM_PLAN_PADDED, PM_PLAN_PADDED16 = 0, 1, 2, 3, 4
@@ -344,6 +350,15 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embbag_fwd_qrows_pruned.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp, i32, vp, vp]
     L.pm_embedding_gather_qrows_pruned.restype = ctypes.c_int
     L.pm_embedding_gather_qrows_pruned.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp, i32, vp, i64, vp]
+    # FP8 tables: (op, padding_idx | NULL, mean, out_dtype, out, stream) and (op, out_dtype, out, out_row_stride, stream)
+    L.pm_embbag_fwd_f8.restype = ctypes.c_int
+    L.pm_embbag_fwd_f8.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, i32, vp, vp]
+    L.pm_embbag_f8_plan.restype = ctypes.c_int
+    L.pm_embbag_f8_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, ctypes.POINTER(i32)]
+    L.pm_embedding_gather_f8.restype = ctypes.c_int
+    L.pm_embedding_gather_f8.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, vp, i64, vp]
+    L.pm_embedding_gather_f8_plan.restype = ctypes.c_int
+    L.pm_embedding_gather_f8_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), ctypes.POINTER(i64)]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]
@@ -438,6 +453,20 @@ def embedding_gather_qrows_plan(op: pm_embbag_batch, bits: int) -> dict:
     """``pm_embedding_gather_qrows_plan``: the geometry ``pm_embedding_gather_qrows`` would use for ``op`` -- ``GATHER_PLAN_FIELDS`` by name"""
     out = (ctypes.c_int64 * len(GATHER_PLAN_FIELDS))()
     check(load().pm_embedding_gather_qrows_plan(ctypes.byref(op), int(bits), out))
+    return dict(zip(GATHER_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def embbag_f8_plan(op: pm_embbag_batch, out_dtype: int = PM_F32) -> dict:
+    """``pm_embbag_f8_plan``: the geometry ``pm_embbag_fwd_f8`` would use for ``op`` -- ``PLAN_FIELDS`` by name"""
+    out = (ctypes.c_int32 * len(PLAN_FIELDS))()
+    check(load().pm_embbag_f8_plan(ctypes.byref(op), int(out_dtype), out))
+    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
+
+
+def embedding_gather_f8_plan(op: pm_embbag_batch) -> dict:
+    """``pm_embedding_gather_f8_plan``: the geometry ``pm_embedding_gather_f8`` would use for ``op`` -- ``GATHER_PLAN_FIELDS`` by name"""
+    out = (ctypes.c_int64 * len(GATHER_PLAN_FIELDS))()
+    check(load().pm_embedding_gather_f8_plan(ctypes.byref(op), out))
     return dict(zip(GATHER_PLAN_FIELDS, (int(v) for v in out)))
 
 

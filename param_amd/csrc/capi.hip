@@ -782,6 +782,87 @@ int pm_embedding_gather_qrows_plan(const pm_embbag_batch* op, int32_t bits, int6
     return PM_OK;
 }
 
+// ---- FP8 tables (embbag_fwd_f8_kernel.inc, embedding_gather_f8.hip) -----------------------------------------------------------------------
+// what the four calls refuse about a request, in one order: op and its weight_dtype, then what every entry point refuses (for the 16-bit
+// element, whose column rule D % 8 the FP8 rule D % 16 contains and whose lane groups are no narrower: no more tiles than validated),
+// then the FP8 column rules, blocked layouts and out_dtype.  gather: the un-pooled calls, which are unweighted.
+static int f8_request(const pm_embbag_batch* op, int32_t out_dtype, bool gather, const pm::PlanKnobs& knobs) {
+    if (!op) return fail(PM_ERR_INVALID, "op is NULL");
+    if (op->weight_dtype != PM_F8E4M3 && op->weight_dtype != PM_F8E5M2)
+        return fail(PM_ERR_INVALID, "weight_dtype must be PM_F8E4M3 or PM_F8E5M2 (other tables: pm_embbag_fwd and its family)");
+    const int rc = validate_request(op, PM_BF16, knobs);
+    if (rc != PM_OK) return rc;
+    if (op->max_dim % pm::kF8LaneColumns != 0 || op->min_dim % pm::kF8LaneColumns != 0)
+        return fail(PM_ERR_UNSUPPORTED, "FP8 tables: every dims[t] (max_dim, and min_dim where given) must be a multiple of 16");
+    if (op->max_dim > pm::kF8MaxDim) return fail(PM_ERR_UNSUPPORTED, "FP8 tables: dims[t] (and max_dim) must be at most " + std::to_string(pm::kF8MaxDim));
+    if (op->table_group != 0 || op->grad_block_shift != 0 || op->grad_block_extra != 0)
+        return fail(PM_ERR_UNSUPPORTED, "FP8 tables do not take blocked layouts (table_group / grad_block_shift / grad_block_extra must be 0)");
+    if (!dtype_is_weight(out_dtype)) return fail(PM_ERR_INVALID, "out_dtype must be PM_F32, PM_BF16 or PM_F16");
+    if (gather && op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "un-pooled rows are unweighted: per_sample_weights must be NULL");
+    return PM_OK;
+}
+
+int pm_embbag_fwd_f8(const pm_embbag_batch* op, const int64_t* padding_idx, int32_t mean, int32_t out_dtype, void* out, pm_stream_t stream) {
+    const pm::PlanKnobs knobs = current_knobs();
+    int rc = f8_request(op, out_dtype, false, knobs);
+    if (rc != PM_OK) return rc;
+    if (mean != 0 && mean != 1) return fail(PM_ERR_INVALID, "mean must be 0 or 1");
+    if (mean && (rc = weighted_mean_refused(op)) != PM_OK) return rc;
+    const pm::LaunchPlan plan = pm::plan_f8(*op, knobs, out_dtype == PM_F32 ? 4 : 2);
+    if (pm::ceil_div(op->bag_count, plan.bags_per_block) * op->num_tables > pm::kMaxGrid) return fail(PM_ERR_UNSUPPORTED, "grid too large");
+    pm::KParams p;
+    fill_params(op, plan, p);
+    const auto launch = op->weight_dtype == PM_F8E4M3 ? pm::launch_embbag_fwd_f8_e4m3 : pm::launch_embbag_fwd_f8_e5m2;
+    return padded_forward(p, out, out_dtype == PM_F32 ? 16 : 8, stream, [&](const pm::KParams& q, hipStream_t s) {
+        return launch(q, op->max_dim, plan.unroll, padding_idx, mean != 0, out_dtype, s);
+    }, "pm_embbag_fwd_f8 launch");
+}
+
+int pm_embbag_f8_plan(const pm_embbag_batch* op, int32_t out_dtype, int32_t out[12]) {
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const pm::PlanKnobs knobs = current_knobs();
+    const int rc = f8_request(op, out_dtype, false, knobs);
+    if (rc != PM_OK) return rc;
+    const pm::LaunchPlan p = pm::plan_f8(*op, knobs, out_dtype == PM_F32 ? 4 : 2);
+    if (pm::ceil_div(op->bag_count, p.bags_per_block) * op->num_tables > pm::kMaxGrid) return fail(PM_ERR_UNSUPPORTED, "grid too large");
+    const int32_t v[12] = {p.tiles_per_table, p.bags_per_block, p.idx_cap, p.xcd_affine, p.nt_loads, p.ordered,
+                           p.stage_out, p.stage_bags, p.flat_bags, p.flat_target, p.flat_compact, p.unroll};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return PM_OK;
+}
+
+int pm_embedding_gather_f8(const pm_embbag_batch* op, int32_t out_dtype, void* out, int64_t out_row_stride, pm_stream_t stream) {
+    const pm::PlanKnobs knobs = current_knobs();
+    const int rc = f8_request(op, out_dtype, true, knobs);
+    if (rc != PM_OK) return rc;
+    if (out_row_stride < op->max_dim || out_row_stride % 4 != 0)
+        return fail(PM_ERR_INVALID, "out_row_stride must be a multiple of 4 elements and at least max_dim");
+    if (op->num_indices == 0 || op->bag_count == 0) return PM_OK;      // nothing to write, whatever `out` is
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const uintptr_t align = out_dtype == PM_F32 ? 16 : 8;
+    if (reinterpret_cast<uintptr_t>(out) % align != 0) return fail(PM_ERR_INVALID, "out must be " + std::to_string(align) + "-byte aligned");
+    const pm::GatherPlan g = pm::plan_gather_f8(*op, knobs);
+    if (g.grid > pm::kMaxGrid) return fail(PM_ERR_UNSUPPORTED, "grid too large");
+    pm::KParams p;
+    fill_params(op, pm::LaunchPlan{}, p);      // (the request; a gather has no bag tiling)
+    p.io = static_cast<float*>(out);           // (addressed in out_dtype's elements)
+    p.out_stride = out_row_stride;
+    const hipError_t h = pm::launch_embedding_gather_f8(p, op->weight_dtype, out_dtype, g, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embedding_gather_f8 launch");
+    return PM_OK;
+}
+
+int pm_embedding_gather_f8_plan(const pm_embbag_batch* op, int64_t out[8]) {
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const pm::PlanKnobs knobs = current_knobs();
+    const int rc = f8_request(op, PM_F32, true, knobs);
+    if (rc != PM_OK) return rc;
+    const pm::GatherPlan g = pm::plan_gather_f8(*op, knobs);
+    const int64_t v[8] = {g.vec, g.group_lanes, g.tile, g.col_passes, g.unroll, g.lds_borders, g.xcd_contiguous, g.grid};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return PM_OK;
+}
+
 // ---- row-quantised tables of per-table format (embbag_fwd_qmixed.hip, embedding_gather_qmixed.hip) ---------------------------------------
 // what the four calls refuse on the host, in one order: op, table_bits, the eight-column rule (the stricter of the two formats' column
 // rules, for every table: a lane holds eight columns whatever the format), then what qrows_request refuses about a request of 4-bit

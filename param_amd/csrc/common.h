@@ -258,6 +258,12 @@ hipError_t launch_embedding_gather(const KParams& p, int weight_dtype, int out_d
 hipError_t launch_embedding_gather_qrows(const KParams& p, int bits, int out_dtype, const GatherPlan& g, hipStream_t stream);
 // ... of per-table format (embedding_gather_qmixed.hip): table_bits = device int32 [T], 8 | 4; g: plan_gather_qmixed's
 hipError_t launch_embedding_gather_qmixed(const KParams& p, const int32_t* table_bits, int out_dtype, const GatherPlan& g, hipStream_t stream);
+// FP8 tables (embbag_fwd_f8_e4m3.hip / _e5m2.hip, embedding_gather_f8.hip): p = plan_f8's geometry, p.io = out of out_dtype (PM_F32 |
+// PM_BF16 | PM_F16) addressed in its elements, unroll 2 / 4 / 8, pad_idx may be NULL; the gather: weight_dtype PM_F8E4M3 | PM_F8E5M2,
+// g: plan_gather_f8's
+hipError_t launch_embbag_fwd_f8_e4m3(const KParams& p, int max_dim, int unroll, const int64_t* pad_idx, bool mean, int out_dtype, hipStream_t stream);
+hipError_t launch_embbag_fwd_f8_e5m2(const KParams& p, int max_dim, int unroll, const int64_t* pad_idx, bool mean, int out_dtype, hipStream_t stream);
+hipError_t launch_embedding_gather_f8(const KParams& p, int weight_dtype, int out_dtype, const GatherPlan& g, hipStream_t stream);
 
 // sort-based deterministic backward (embbag_bwd_sorted.hip)
 hipError_t sorted_workspace_bytes(const KParams& p, int64_t max_rows, int max_dim, size_t& bytes);

@@ -44,6 +44,58 @@ template <> struct Elem<f16_t> {
     }
 };
 
+// OCP FP8 table elements (include/param_amd.h, FP8 TABLES; embbag_fwd_f8.hip, embedding_gather_f8.hip): 16 per 16-byte load.  The
+// widening is gfx950's own conversion -- v_cvt_pk_f32_fp8 / v_cvt_pk_f32_bf8, two bytes of a dword per instruction, OCP e4m3fn / e5m2
+// (not MI300's fnuz) -- which tests/test_gpu_f8.py pins to dec() for all 256 codes in every byte lane.  -DPM_F8_SOFT_DECODE is the
+// experiment build without those instructions: e5m2 `code << 8` IS the fp16 pattern of the value; e4m3fn `(code & 0x7f) << 7` is the
+// fp16 pattern of the value / 256 (subnormal codes included: the exponent bias differs by 8), except the NaN codes 0x7f / 0xff.
+struct f8e4m3_t { uint8_t v; };
+struct f8e5m2_t { uint8_t v; };
+
+// the four bytes of one dword, low byte first
+template <typename WT>
+__device__ __forceinline__ void widen_f8_dword(uint32_t w, float* f);
+template <>
+__device__ __forceinline__ void widen_f8_dword<f8e4m3_t>(uint32_t w, float* f) {
+#ifndef PM_F8_SOFT_DECODE
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(w), false);
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(w), true);
+    f[0] = lo[0]; f[1] = lo[1]; f[2] = hi[0]; f[3] = hi[1];
+#else
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t b = (w >> (8 * i)) & 0xffu, mag = b & 0x7fu;
+        const float v = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(mag << 7))) * 256.0f;
+        const uint32_t bits = mag == 0x7fu ? 0x7fc00000u : __float_as_uint(v);
+        f[i] = __uint_as_float(bits | ((b & 0x80u) << 24));
+    }
+#endif
+}
+template <>
+__device__ __forceinline__ void widen_f8_dword<f8e5m2_t>(uint32_t w, float* f) {
+#ifndef PM_F8_SOFT_DECODE
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_bf8(static_cast<int>(w), false);
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_bf8(static_cast<int>(w), true);
+    f[0] = lo[0]; f[1] = lo[1]; f[2] = hi[0]; f[3] = hi[1];
+#else
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        f[i] = static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(((w >> (8 * i)) & 0xffu) << 8)));
+#endif
+}
+template <typename WT>
+struct ElemF8 {
+    static constexpr int kVec = 16;
+    __device__ static __forceinline__ void widen(const u32x4& raw, float (&f)[16]) {
+        widen_f8_dword<WT>(raw.x, f);
+        widen_f8_dword<WT>(raw.y, f + 4);
+        widen_f8_dword<WT>(raw.z, f + 8);
+        widen_f8_dword<WT>(raw.w, f + 12);
+    }
+};
+template <> struct Elem<f8e4m3_t> : ElemF8<f8e4m3_t> {};
+template <> struct Elem<f8e5m2_t> : ElemF8<f8e5m2_t> {};
+
 // A 16-bit OUTPUT element (the padded forward's OT, embbag_fwd_pad_kernel.inc; the row gather's, embedding_gather.hip):
 // fp32 -> 16 bits, round to nearest even; overflow to +-Inf, subnormals produced, signed zeros kept, NaN -> a quiet NaN of its sign.
 // Four outputs leave as one 8-byte piece (u32x2): what the alignment rules of a request guarantee.

@@ -613,4 +613,51 @@ static inline GatherPlan plan_gather_qmixed(const pm_embbag_batch& op, const Pla
     return g;
 }
 
+// ---- FP8 tables: pm_embbag_fwd_f8 (embbag_fwd_f8.hip) and pm_embedding_gather_f8 (embedding_gather_f8.hip) ------------------------------
+// The 1-byte element: a 16-byte load holds 16 columns (vec = 16, elem_bytes = 1), so the pooled lane group is group_lanes(max_dim, 16) --
+// 8 lanes up to D = 128 (one aligned 128-byte line per row), 64 lanes at D = 1024, column passes above (kF8MaxDim = 2048: two).
+// The plan is plan_padded's, from the same blocks (tile_bags, burst_tile for out_bytes-elements, index_tile), plus the rows a lane group
+// keeps in flight: 2, 4 or 8 (pm_set_tuning's unroll: below 4 -> 2, below 8 -> 4, from 8 on -> 8).  At 128-byte rows two rows in flight
+// are a quarter of the fp32 kernel's bytes in flight, and the gather and the qrows kernels both measured better with deeper batches --
+// this kernel does not.  tools/f8_probe.py, 16 x 10 M x 128 e4m3, batch 8192, pooling 20, fp32 output, us per call, medians of 5 windows
+// of one process, spread <= 0.25 % (profiles/f8_probe.json); 2 / 4 / 8 rows in flight:
+//   uniform indices 78.0 / 78.5 / 88.7      Zipf 1.05  48.6 / 50.7 / 64.4
+// Two is the default, as in the fp32 forward (kDefaultUnroll): occupancy provides the memory-level parallelism, and the deeper
+// instances pay for their registers (70 to 166 VGPRs across the instances).  fp16 output (64-bag tiles, half the workgroups) is
+// another matter under Zipf indices: 50.7 us at two, 43.8 us in the earlier run of the probe whose default was four
+// (profiles/f8_probe_unroll4_default.json; two processes, not one).  A default per output type: not built.
+constexpr int kF8Unroll = 2;
+constexpr int kF8MaxDim = 2048;
+constexpr int kF8LaneColumns = 16;
+static inline PlanShape f8_shape(const pm_embbag_batch& op, const PlanKnobs& k) { return lane_columns_shape(op, kF8LaneColumns, k); }
+static inline LaunchPlan plan_f8(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k, int out_bytes) {
+    LaunchPlan p = plan_qrows(op, s, k, out_bytes);   // (the same tiling for this shape's lane group; the unroll is this kernel's own)
+    const int u = k.unroll != 0 ? k.unroll : kF8Unroll;
+    p.unroll = u >= 8 ? 8 : (u >= 4 ? 4 : 2);
+    return p;
+}
+static inline LaunchPlan plan_f8(const pm_embbag_batch& op, const PlanKnobs& k, int out_bytes) { return plan_f8(op, f8_shape(op, k), k, out_bytes); }
+
+// The un-pooled lookup: the gather's tiles and block order with FOUR columns per lane (kF8GatherLaneColumns) -- one global_load_dword per
+// lane and row, G = group_lanes(max_dim, 4) lanes (32 at D = 128, 64 from D = 256 on, column passes of 256 columns above).  Stores are the
+// point: with the pooled kernel's 16 columns per lane one store instruction of a lane group writes 16 of every 64 output bytes, the layout
+// that cost the qrows gather 643.7 against 374.9 us (profiles/qgather_probe_lane_major.json); with four, a lane's widened dword is exactly
+// one 16-byte (fp32) / 8-byte (16-bit) piece and a lane group's store instruction writes consecutive pieces of the row, while its loads
+// still cover the row contiguously.  The 16-column load with a lane exchange: not built.  Rows in flight: plan_gather's rounding.
+constexpr int kF8GatherLaneColumns = 4;
+constexpr int kF8GatherUnroll = 8;
+static inline GatherPlan plan_gather_f8(const pm_embbag_batch& op, const PlanKnobs& k) {
+    GatherPlan g = {};
+    g.vec = kF8GatherLaneColumns;
+    g.group_lanes = group_lanes(op.max_dim, g.vec);
+    g.tile = kBlock;
+    g.col_passes = static_cast<int32_t>(ceil_div(op.max_dim, static_cast<int64_t>(g.group_lanes) * g.vec));
+    const int u = k.unroll != 0 ? k.unroll : kF8GatherUnroll;
+    g.unroll = u >= 8 ? 8 : (u >= 4 ? 4 : (u >= 2 ? 2 : 1));
+    g.lds_borders = op.num_tables + 1 <= kGatherLdsBorders ? 1 : 0;
+    g.xcd_contiguous = (op.num_tables > 1 && k.xcd_affine != 0) ? 1 : 0;
+    g.grid = ceil_div(op.num_indices, g.tile);
+    return g;
+}
+
 }  // namespace pm
