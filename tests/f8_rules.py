@@ -41,6 +41,13 @@ def dec(codes, fmt):
     return out
 
 
+def finite_codes(rng, fmt, shape):
+    """uint8 codes drawn from ``rng``, all of them finite: a NaN (e5m2: or Inf) code has its top two bits cleared"""
+    c = rng.integers(0, 256, shape, dtype=np.uint8)
+    bad = (c & 0x7f) == 0x7f if fmt == "e4m3" else (c & 0x7f) >= 0x7c
+    return np.where(bad, c & 0x3f, c).astype(np.uint8)
+
+
 def is_nan_code(codes, fmt):
     c = np.asarray(codes, dtype=np.uint8)
     return (c & 0x7f) == 0x7f if fmt == "e4m3" else (c & 0x7f) > 0x7c
@@ -77,14 +84,12 @@ def sequence(tables, fmt, indices, offsets, B, bag_begin=0, bag_count=None):
     start, end = P.bag_bounds(offsets, T, B, N)
     out = np.zeros((N, tables[0].shape[1]), dtype=np.float32)
     written = np.zeros(N, dtype=bool)
-    for j in range(N):
-        t = int(owner[j])
-        if t < 0 or bag_count == 0:
-            continue
+    pos = np.arange(N)
+    for t in range(T if bag_count else 0):             # (a table at a time: its positions inside the slice, all at once)
         lo, hi = int(start[t * B + bag_begin]), int(end[t * B + bag_begin + bag_count - 1])
-        if lo <= j < hi:
-            out[j] = dec(tables[t][idx[j]], fmt)
-            written[j] = True
+        sel = (owner == t) & (pos >= lo) & (pos < hi)
+        out[sel] = dec(tables[t][idx[sel]], fmt)
+        written[sel] = True
     return out, written
 
 

@@ -21,9 +21,13 @@ PLAN_FIELDS = ("tiles_per_table", "bags_per_block", "idx_cap", "xcd_affine", "nt
                "flat_bags", "flat_target", "flat_compact", "unroll")
 GATHER_FIELDS = ("vec", "group_lanes", "tile", "col_passes", "unroll", "lds_borders", "xcd_contiguous", "grid")
 # the `kind` codes of tests/launch_plan_dump.cpp (0 .. 4: pm_embbag_plan's PM_PLAN_*; 5: the gather plan)
-KIND = {"base": 0, "forward": 1, "quantized": 2, "padded4": 3, "padded2": 4, "gather": 5}
+# (6 .. 8: plan_f8 for 4- / 2-byte output elements and plan_gather_f8, the plans of pm_embbag_f8_plan / pm_embedding_gather_f8_plan)
+KIND = {"base": 0, "forward": 1, "quantized": 2, "padded4": 3, "padded2": 4, "gather": 5, "f8_4": 6, "f8_2": 7, "f8_gather": 8}
 DTYPE = {"f32": 0, "bf16": 1, "f16": 2}
-VEC = {"f32": 4, "bf16": 8, "f16": 8}
+F8_DTYPE = {"e4m3": 3, "e5m2": 4}                                             # PM_F8E4M3 / PM_F8E5M2: the table kinds of the FP8 entries
+VEC = {"f32": 4, "bf16": 8, "f16": 8, "e4m3": 16, "e5m2": 16}                 # columns per lane of the pooled kernels
+F8_GATHER_VEC = 4                                                             # ... of the FP8 gather (one dword)
+OUT16_CODE = {None: 0, "bf16": 1, "fp16": 2}                                  # PM_F32 / PM_BF16 / PM_F16 of a case's ``out16``
 TUNING = ("unroll", "bags_per_block", "xcd_affine", "nt_loads")               # set_tuning's arguments and their "not set"
 TUNING_DEFAULT = (0, 0, -1, -1)
 FORWARD_TUNING = ("stage_out", "flat_grid", "flat_target")                    # set_forward_tuning's
@@ -35,8 +39,11 @@ ENV_DEFAULT = (1, 1, 0, 256, 256, -1, 1)
 # which plan an entry point launches with (capi.hip); a pair: (fp32 output, 16-bit output) -- pm_embbag_fwd_max plans on the padded
 # family's plan for its output element, so the case decides
 ENTRY_KIND = {"fwd": "forward", "quantized": "quantized", "padded": "padded4", "mean": "padded4", "out16": "padded2", "gather": "gather",
-              "psw_grad": "base", "mean_grad": "base", "widen": "base", "atomic": "base", "max": ("padded4", "padded2")}
+              "psw_grad": "base", "mean_grad": "base", "widen": "base", "atomic": "base", "max": ("padded4", "padded2"),
+              "f8": ("f8_4", "f8_2"), "f8_gather": "f8_gather"}
 UNROLLS = (1, 2, 3, 4, 6, 8)
+# FP8 pooled: (lane-group width, the D its unroll cases run at, the unroll its mean case runs at)
+F8_GROUP_DIMS = ((8, 64, 4), (16, 192, 8), (32, 400, 2), (64, 1024, 4))
 K_BLOCK = 256
 
 
@@ -199,7 +206,9 @@ class Case:
         self.weighted, self.bag_slice, self.out16, self.mean, self.bits = weighted, bag_slice, out16, mean, bits
         self._dims = dims
         assert not set(self.tuning) - set(TUNING) and not set(self.forward) - set(FORWARD_TUNING) and not set(self.env) - set(ENV)
-        assert entry in ENTRY_KIND and kind in DTYPE and not (mean and weighted) and not (entry == "max" and (weighted or mean))
+        assert entry in ENTRY_KIND and not (mean and weighted) and not (entry == "max" and (weighted or mean))
+        # an FP8 entry has FP8 tables (dims: multiples of 16 in [16, 2048]) and nothing else has
+        assert (kind in F8_DTYPE and all(d % 16 == 0 and 16 <= d <= 2048 for d in self.dims)) if entry.startswith("f8") else kind in DTYPE
 
     @property
     def req(self):
@@ -223,7 +232,12 @@ class Case:
     def plan_weighted(self):
         """whether the request the entry point plans for carries weights (the gather, the weights' gradient and the mean scaling
         build theirs without)"""
-        return bool(self.weighted and self.entry not in ("gather", "psw_grad", "mean_grad"))
+        return bool(self.weighted and self.entry not in ("gather", "f8_gather", "psw_grad", "mean_grad"))
+
+    @property
+    def dtype_code(self):
+        """the library's code of the table element (``weight_dtype``)"""
+        return F8_DTYPE[self.kind] if self.kind in F8_DTYPE else DTYPE[self.kind]
 
     def tuning_args(self):
         return [self.tuning.get(f, d) for f, d in zip(TUNING, TUNING_DEFAULT)]
@@ -237,7 +251,7 @@ class Case:
         weighted = int(self.plan_weighted)
         env = [int(self.env.get(f, d)) for f, d in zip(ENV, ENV_DEFAULT)]
         env[0] = 0 if str(self.env.get(ENV[0], "1")).startswith("0") else 1
-        v = [KIND[self.plan_kind], r.T, r.B, r.N, b0, n, max(self.dims), min(self.dims), DTYPE[self.kind], weighted, 0, 0, 0]
+        v = [KIND[self.plan_kind], r.T, r.B, r.N, b0, n, max(self.dims), min(self.dims), self.dtype_code, weighted, 0, 0, 0]
         return " ".join(map(str, v + self.tuning_args() + self.forward_args() + env))
 
 
@@ -246,6 +260,8 @@ def label(case, plan):
     exceed the index tile and are read from the request; ``partial``: the last tile of a table is not full) is derived from them"""
     r, (b0, n) = case.req, case.bags
     G = group_lanes(max(case.dims), VEC[case.kind])
+    if case.entry.startswith("f8"):
+        return f8_label(case, plan)
     if case.plan_kind == "gather":
         p = dict(zip(GATHER_FIELDS, plan))
         return {"gather", case.kind, f"G{p['group_lanes']}", f"u{p['unroll']}", f"passes{p['col_passes']}", f"xcd{p['xcd_contiguous']}",
@@ -283,6 +299,60 @@ def label(case, plan):
             words.add("direct")
         if n % bags:
             words.add("partial")
+    return words
+
+
+def f8_label(case, plan):
+    """the variant of an FP8 case.  Family words ``f8`` and ``pooled`` / ``unpooled`` (no word of another family: an FP8 case meets no
+    condition that is there for another kernel).  ``staged`` / ``plain`` is the output burst, as everywhere.  Read off the request's
+    offsets, indices and pads next to the plan, tile by tile as embbag_fwd_f8_kernel.inc walks them -- a tile whose lookups fit the
+    index tile compacts them in LDS, 256 entries a round, four waves a round:
+      ``rounds>1``  such a tile holds more than 256 entries before compaction;
+      ``waves>1``   in one round of such a tile at least two waves hold a kept AND a padded entry each (the prefix over the waves'
+                    counts is not the identity, and a wave behind wave 0 keeps an entry);
+      ``carry``     such a tile has a bag that is not empty and whose first entry lies in a round after the first, with a padded entry
+                    in an earlier round (the bag's bound is read from ``s_pre`` beyond the first round and the carry over rounds counts);
+      ``bounds5``   such a tile has 1024 bags (a thread's fifth bound);
+      ``direct``    a tile's lookups exceed the index tile: its indices are read from the request;  ``partial``: a last tile is not full.
+    The gather: ``partial`` is a last tile of positions that is not full."""
+    r, (b0, n) = case.req, case.bags
+    words = {"f8", case.kind, "out-" + (case.out16 or "fp32")} | ({"slice"} if case.bag_slice else set())
+    if case.entry == "f8_gather":
+        p = dict(zip(GATHER_FIELDS, plan))
+        assert p["vec"] == F8_GATHER_VEC
+        return words | {"unpooled", f"G{p['group_lanes']}", f"u{p['unroll']}", f"passes{p['col_passes']}", f"xcd{p['xcd_contiguous']}",
+                        "lds_borders" if p["lds_borders"] else "global_borders"} | ({"partial"} if r.N % p["tile"] else set())
+    p = dict(zip(PLAN_FIELDS, plan))
+    G = group_lanes(max(case.dims), VEC[case.kind])
+    bpb, cap = p["bags_per_block"], p["idx_cap"]
+    words |= {"pooled", f"G{G}", f"u{p['unroll']}", "mean" if case.mean else "weighted" if case.weighted else "unweighted", f"xcd{p['xcd_affine']}",
+              f"bpb{bpb}", "staged" if p["stage_out"] else "plain", f"passes{-(-max(case.dims) // (G * VEC[case.kind]))}"}
+    if bpb > K_BLOCK // G:
+        words.add("tile>NG")
+    for t in range(r.T):
+        pad = -1 if r.pads is None or r.pads[t] is None else r.pads[t]
+        for k in range(-(-n // bpb)):
+            g0, nb = t * r.B + b0 + k * bpb, min(bpb, n - k * bpb)
+            lo, cnt = int(r.off[g0]), int(r.off[g0 + nb] - r.off[g0])
+            if nb < bpb:
+                words.add("partial")
+            if cnt > cap:
+                words.add("direct")
+                continue
+            keep = r.idx[lo:lo + cnt] != pad
+            if nb == 1024:
+                words.add("bounds5")
+            if cnt > K_BLOCK:
+                words.add("rounds>1")
+            for i0 in range(0, cnt, K_BLOCK):
+                waves = [keep[i:min(i + 64, i0 + K_BLOCK)] for i in range(i0, min(i0 + K_BLOCK, cnt), 64)]
+                if sum(1 for w in waves if w.any() and not w.all()) >= 2:
+                    words.add("waves>1")
+            padded_before = np.concatenate([[0], np.cumsum(~keep)])
+            first = r.off[g0:g0 + nb] - lo
+            later = first[(r.lens[g0:g0 + nb] > 0) & (first >= K_BLOCK)]
+            if (padded_before[later // K_BLOCK * K_BLOCK] > 0).any():
+                words.add("carry")
     return words
 
 
@@ -415,6 +485,65 @@ def _cases():
     add("auto_bench_fp32", "auto48", "fwd", "auto48")
     add("auto_t26", "auto26", "fwd", "auto26")
     add("auto_ragged_long", "auto16r", "fwd", "auto16r")
+    # -- FP8 tables, pooled: pm_embbag_fwd_f8 on plan_f8, sixteen columns per lane (G = 8 up to D = 128, 64 from D = 528 on), every case
+    #    under an explicit tile.  With two bags per lane group a tile's fp32 rows fit the 16 KB burst at G = 8 and D <= 64 only
+    #    (bags_per_block * D * 4 = 2 * 256 / G * D * 4 <= 16384), its 16-bit rows up to G = 16.
+    def f8(name, group, rq, dims, mode="plain", fmt="e4m3", **kw):
+        add(name, group, "f8", rq, fmt, dims, weighted=mode == "weighted", mean=mode == "mean", **kw)
+
+    modes = ("plain", "weighted", "mean")
+    # the multi-tile baseline, both formats: pad100 at D = 256 (G = 16), four 32-bag tiles a table, the last of 4 bags, two bags per lane
+    # group; fp32 rows do not fit the burst (the plan says plain), 16-bit rows fill it exactly: staged, and with stage_out = 0
+    for fmt in F8_DTYPE:
+        for mode in modes:
+            f8(f"f8_base_{fmt}_{mode}", f"f8_base_{fmt}", "pad100", 256, mode, fmt, tuning=dict(bags_per_block=32))
+            f8(f"f8_base_{fmt}_{mode}_bf16", f"f8_base_{fmt}", "pad100", 256, mode, fmt, tuning=dict(bags_per_block=32), out16="bf16")
+    for mode in modes:
+        f8(f"f8_base_e4m3_{mode}_bf16_unstaged", "f8_base_e4m3", "pad100", 256, mode, tuning=dict(bags_per_block=32), forward=dict(stage_out=0), out16="bf16")
+    f8("f8_base_e4m3_plain_fp16", "f8_base_e4m3", "pad100", 256, tuning=dict(bags_per_block=32), out16="fp16")
+    # ... and with fp32 output through the burst: 64-bag tiles of D = 64 rows, 18 tiles a table (pad1100), the last of 12 bags
+    for mode in modes:
+        f8(f"f8_burst_{mode}", "f8_burst", "pad1100", 64, mode, tuning=dict(bags_per_block=64))
+        f8(f"f8_burst_{mode}_unstaged", "f8_burst", "pad1100", 64, mode, tuning=dict(bags_per_block=64), forward=dict(stage_out=0))
+    # every lane-group width x every depth, two bags per lane group, several tiles a table; mean at one depth per width.  At G = 16
+    # and 32 the row ends inside the lane group (12 of 16, 25 of 32 lanes hold columns): the full groups are the baseline and D = 512
+    for G, D, mean_u in F8_GROUP_DIMS:
+        for u in (2, 4, 8):
+            for mode in modes[:2] + (("mean",) if u == mean_u else ()):
+                f8(f"f8_G{G}_u{u}_{mode}", f"f8_G{G}", "pad100", D, mode, tuning=dict(unroll=u, bags_per_block=2 * K_BLOCK // G))
+    # block orders and a slice that begins and ends inside tiles, on the product's tile: D = 128, one bag per lane group, fp32 burst
+    f8("f8_xcd0", "f8_orders", "pad100", 128, tuning=dict(bags_per_block=32, xcd_affine=0))
+    f8("f8_xcd1", "f8_orders", "pad8", 128, tuning=dict(bags_per_block=32))
+    f8("f8_xcd3", "f8_orders", "padfix", 128, tuning=dict(bags_per_block=32))
+    f8("f8_slice", "f8_orders", "pad100", 128, tuning=dict(bags_per_block=32), bag_slice=(5, 70))
+    f8("f8_slice_mean", "f8_orders", "pad100", 128, "mean", tuning=dict(bags_per_block=32), bag_slice=(5, 70))
+    # 1024-bag tiles: about 2500 entries a tile, ten rounds of compaction, a thread's fifth bound; rows leave one by one (no burst)
+    for mode in modes:
+        f8(f"f8_bpb1024_{mode}", "f8_1024", "pad1100", 16, mode, tuning=dict(bags_per_block=1024))
+        f8(f"f8_bpb1024_{mode}_bf16", "f8_1024", "pad1100", 16, mode, tuning=dict(bags_per_block=1024), out16="bf16")
+    # a 32-bag tile of 1600 lookups, 40 % of them padded, read from the request, among compacted tiles of 640
+    for mode in modes:
+        for u in (2, 8):
+            f8(f"f8_direct_u{u}_{mode}", "f8_direct", "pad_lumpy", 128, mode, tuning=dict(unroll=u, bags_per_block=32))
+    # mixed dims (the lane group sized for 128), the 2-byte against the 4-byte burst at D = 512, two column passes at G = 64
+    f8("f8_mixed_dims", "f8_wide", "pad100", [16, 64, 128], "weighted", tuning=dict(bags_per_block=32))
+    f8("f8_D512_bf16", "f8_wide", "pad100", 512, tuning=dict(bags_per_block=16), out16="bf16")
+    f8("f8_D512_fp32", "f8_wide", "pad100", 512, tuning=dict(bags_per_block=16))
+    f8("f8_D1040_two_passes", "f8_wide", "pad100", 1040, "weighted", tuning=dict(bags_per_block=8))
+    # -- FP8 tables, un-pooled: pm_embedding_gather_f8 on plan_gather_f8, four columns per lane (G = D / 4 up to 64)
+    def f8g(name, group, rq="ragged", dims=128, fmt="e4m3", **kw):
+        add(name, group, "f8_gather", rq, fmt, dims, **kw)
+
+    for G, D in ((8, 16), (16, 64), (32, 128), (64, 256)):
+        for u in (1, 2, 4, 8):
+            f8g(f"f8_gather_G{G}_u{u}", "f8_gather_GU", dims=D, tuning=dict(unroll=u))
+    for u in (1, 2, 4, 8):
+        for o16 in ("bf16", "fp16"):
+            f8g(f"f8_gather_G32_u{u}_{o16}", "f8_gather_16", tuning=dict(unroll=u), out16=o16)
+    f8g("f8_gather_xcd0", "f8_gather_knobs", tuning=dict(unroll=2, xcd_affine=0))
+    f8g("f8_gather_D512_two_passes", "f8_gather_knobs", "mixed_ragged", 512, tuning=dict(unroll=4))
+    f8g("f8_gather_slice", "f8_gather_knobs", tuning=dict(unroll=4), bag_slice=(3, 90))
+    f8g("f8_gather_e5m2", "f8_gather_knobs", fmt="e5m2", tuning=dict(unroll=8))
     # -- the environment switches: one group per setting, each in a process of its own
     e = "env_tile_major"
     add(f"{e}_ordered", e, "fwd", "ragged", tuning=dict(bags_per_block=32), env={"PARAM_AMD_FWD_TILE_MAJOR": 1})
@@ -439,6 +568,7 @@ def _cases():
     add(f"{e}_short1", e, "fwd", "short1", env=env)
     add(f"{e}_padded", e, "padded", "pad100", tuning=dict(bags_per_block=32), env=env)
     add(f"{e}_max", e, "max", "pad100", tuning=dict(bags_per_block=32), env=env)
+    add(f"{e}_f8", e, "f8", "pad100", "e4m3", 128, tuning=dict(bags_per_block=32), env=env)
     add(f"{e}_out16", e, "out16", "pad100", tuning=dict(bags_per_block=32), env=env, out16="bf16")
     assert len({c.name for c in out}) == len(out)
     for c in out:                                                  # a group shares its environment; its cases are one test

@@ -1,6 +1,7 @@
 """Runs one group of tests/plan_sweep.py on the GPU: for every case the knobs are set, ``pm_embbag_plan`` (``pm_embedding_gather_plan``)
 must report the row pinned in tests/plan_sweep_host.json, the entry point runs -- int64 and int32 indices, layouts ``bd`` and ``tbd``
-where the dims are equal -- and its output must equal the rule of the operation bit for bit.
+where the dims are equal -- and its output must equal the rule of the operation bit for bit.  The FP8 entries (``f8``, ``f8_gather``) build ``Float8BatchedEmbeddingBagMI355``
+modules, are asked through ``pm_embbag_f8_plan`` / ``pm_embedding_gather_f8_plan`` and compare with tests/f8_rules.py.
 
 tests/test_gpu_plan_sweep.py calls ``run_group`` in its own process; for the groups with an environment setting it starts
 ``python -m tests.plan_sweep_worker GROUP`` with that setting, because the switches are read once per process.  Exit status 0: every
@@ -12,11 +13,13 @@ import sys
 import numpy as np
 
 from tests import embedding_rules as ER
+from tests import f8_rules as F8
 from tests import mean_rules as M
 from tests import out16_rules as O16
 from tests import padding_rules as P
 from tests import plan_sweep as S
 from tests import psw_grad_rules as PG
+from tests.qrows_rules import same_f32 as _same_f32_or_nan
 
 DEV = "cuda:0"
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -56,7 +59,7 @@ def _bits16(t):
 
 def variants(c):
     """(index dtype, layout) pairs a case runs"""
-    if c.entry == "gather" or len(set(c.dims)) > 1:
+    if c.entry in ("gather", "f8_gather") or len(set(c.dims)) > 1:
         return [("i64", "bd"), ("i32", "bd")]
     if c.request.startswith("auto") or c.group.startswith("base"):
         return [("i64", "bd"), ("i32", "tbd")]
@@ -123,7 +126,11 @@ def _first_diff(got, want):
 def check_plan(c, op):
     from param_amd import _lib
 
-    if c.plan_kind == "gather":
+    if c.entry == "f8":
+        got = list(_lib.embbag_f8_plan(op, S.OUT16_CODE[c.out16]).values())
+    elif c.entry == "f8_gather":
+        got = list(_lib.embedding_gather_f8_plan(op).values())
+    elif c.plan_kind == "gather":
         got = list(_lib.embedding_gather_plan(op).values())
     else:
         got = list(_lib.embbag_plan(op, S.KIND[c.plan_kind]).values())
@@ -347,8 +354,93 @@ def run_base(c, idt, layout, coracle):
             assert _same_f32(got[t], want), (t, _first_diff(got[t], want))
 
 
+def f8_tables(c):
+    """the uint8 code tables of an FP8 case, one set per (format, rows, dims): finite codes from a fixed seed (the non-finite ones are
+    tests/test_gpu_f8.py's), and in every row one of the format's zeros and subnormals, at a column that moves with the row"""
+    def make():
+        mbits = 3 if c.kind == "e4m3" else 2
+        special = np.array([s | m for s in (0, 0x80) for m in range(1 << mbits)], dtype=np.uint8)          # +-0 and the subnormals
+        tabs = []
+        for t, (rows, D) in enumerate(zip(c.req.rows, c.dims)):
+            tab = F8.finite_codes(np.random.default_rng(7000 + t), c.kind, (rows, D))
+            r = np.arange(rows)
+            tab[r, r % D] = special[r % special.size]
+            assert not F8.is_nan_code(tab, c.kind).any() and np.isfinite(F8.dec(tab, c.kind)).all() and set(special) <= set(np.unique(tab).tolist())
+            tabs.append(tab)
+        return tabs
+    return _memo(("f8 tables", c.kind, tuple(c.req.rows), tuple(c.dims)), make)
+
+
+def f8_module(c, layout):
+    """the Float8BatchedEmbeddingBagMI355 of a case, one per distinct set of options, filled through ``copy_from_``"""
+    torch = _torch()
+    from param_amd import Float8BatchedEmbeddingBagMI355
+
+    pads = None if c.entry == "f8_gather" else c.req.pads
+    key = ("f8 module", c.kind, tuple(c.dims), tuple(c.req.rows), layout, None if pads is None else tuple(pads), c.mean, c.out16)
+
+    def make():
+        m = Float8BatchedEmbeddingBagMI355(c.req.rows, c.dims, c.kind, device=DEV, layout=layout, pooling_mode="mean" if c.mean else "sum",
+                                           padding_idx=pads, output_dtype={None: None, "bf16": torch.bfloat16, "fp16": torch.float16}[c.out16])
+        for t, tab in enumerate(f8_tables(c)):
+            m.copy_from_(t, _t(tab))
+        return m
+    return _memo(key, make)
+
+
+def run_f8(c, idt, layout, coracle):
+    """pm_embbag_fwd_f8: the batch, or a slice of it, into a NaN canvas that must equal tests/f8_rules.py: forward on bits (a 16-bit
+    output: its one rounding) and stay NaN elsewhere"""
+    torch = _torch()
+    r, (b0, n) = c.req, c.bags
+    m, tabs = f8_module(c, layout), f8_tables(c)
+    it = torch.int64 if idt == "i64" else torch.int32
+    idx_t, off_t = _t(r.idx, it), _t(r.off, it)
+    psw_t = _t(r.psw) if c.weighted else None
+    check_plan(c, m._request(idx_t, off_t, psw_t, b0, n if c.bag_slice else None, r.B, False)[2])
+    outs = _memo(("f8", c.request, c.kind, tuple(c.dims), c.weighted, c.mean),
+                 lambda: F8.forward(tabs, c.kind, r.idx, r.off, r.B, r.pads, r.psw if c.weighted else None, c.mean))
+    assert all(np.isfinite(o).all() for o in outs)
+    shape = (r.B, sum(c.dims)) if layout == "bd" else (r.T, r.B, c.dims[0])
+    sel = _sel(layout, b0, n)
+    rest = np.ones(shape, dtype=bool)
+    rest[sel] = False
+    canvas = torch.full(shape, float("nan"), dtype=m.output_dtype, device=DEV)
+    assert m.lookup(idx_t, off_t, psw_t, out=canvas, batch=r.B, bag_begin=b0, bag_count=n) is canvas
+    if c.out16 is None:
+        got, want = canvas.cpu().numpy(), _assemble(outs, layout)
+        assert _same_f32_or_nan(got[sel], want[sel]), _first_diff(got[sel].view(np.uint32), want[sel].view(np.uint32))
+        assert np.isnan(got[rest]).all(), "written outside the slice"
+    else:
+        got, want = _bits16(canvas), _assemble([O16.round16(o, c.out16) for o in outs], layout)
+        assert F8.same16(got[sel], want[sel], c.out16), _first_diff(got[sel], want[sel])
+        assert (got[rest] == _bits16(torch.full((1,), float("nan"), dtype=m.output_dtype))[0]).all(), "written outside the slice"
+
+
+def run_f8_gather(c, idt, layout, coracle):
+    """pm_embedding_gather_f8 into a NaN canvas: tests/f8_rules.py: sequence on bits where the rule writes, NaN elsewhere"""
+    torch = _torch()
+    r, (b0, n) = c.req, c.bags
+    m, tabs = f8_module(c, layout), f8_tables(c)
+    it = torch.int64 if idt == "i64" else torch.int32
+    idx_t, off_t = _t(r.idx, it), _t(r.off, it)
+    check_plan(c, m._request(idx_t, off_t, None, b0, n if c.bag_slice else None, r.B, False)[2])
+    want, written = _memo(("f8 rows", c.request, c.kind, tuple(c.dims), b0, n), lambda: F8.sequence(tabs, c.kind, r.idx, r.off, r.B, b0, n))
+    assert written.any() and (written.all() != bool(c.bag_slice))
+    canvas = torch.full((r.N, c.dims[0]), float("nan"), dtype=m.output_dtype, device=DEV)
+    assert m.lookup_sequence(idx_t, off_t, batch=r.B, out=canvas, bag_begin=b0, bag_count=n) is canvas
+    if c.out16 is None:
+        got = canvas.cpu().numpy()
+        assert _same_f32_or_nan(got[written], want[written]), _first_diff(got[written].view(np.uint32), want[written].view(np.uint32))
+        assert np.isnan(got[~written]).all(), "written outside the slice"
+    else:
+        got, want16 = _bits16(canvas), F8.sequence16(want, c.out16)
+        assert F8.same16(got[written], want16[written], c.out16), _first_diff(got[written], want16[written])
+        assert (got[~written] == _bits16(torch.full((1,), float("nan"), dtype=m.output_dtype))[0]).all(), "written outside the slice"
+
+
 RUN = {"fwd": run_forward, "padded": run_forward, "mean": run_forward, "out16": run_forward, "quantized": run_quantized, "gather": run_gather,
-       "psw_grad": run_base, "mean_grad": run_base, "widen": run_base, "atomic": run_base, "max": run_max}
+       "psw_grad": run_base, "mean_grad": run_base, "widen": run_base, "atomic": run_base, "max": run_max, "f8": run_f8, "f8_gather": run_f8_gather}
 
 
 def run_group(group, coracle, log=None):
@@ -393,14 +485,19 @@ def host_plans(group):
         for c in (c for c in S.CASES if c.group == group):
             r, (b0, n) = c.req, c.bags
             op = _lib.pm_embbag_batch()
-            op.num_tables, op.weight_dtype, op.index_dtype = r.T, S.DTYPE[c.kind], _lib.PM_I64
+            op.num_tables, op.weight_dtype, op.index_dtype = r.T, c.dtype_code, _lib.PM_I64
             op.max_dim, op.min_dim, op.out_stride = max(c.dims), min(c.dims), sum(c.dims)
             op.batch, op.num_indices, op.bag_begin, op.bag_count = r.B, r.N, b0, n
             op.tables = op.rows = op.dims = op.out_offsets = op.indices = op.offsets = 8
             op.per_sample_weights = 8 if c.plan_weighted else None
             param_amd.set_tuning(*c.tuning_args())
             param_amd.set_forward_tuning(*c.forward_args())
-            plan = _lib.embedding_gather_plan(op) if c.plan_kind == "gather" else _lib.embbag_plan(op, S.KIND[c.plan_kind])
+            if c.entry == "f8":
+                plan = _lib.embbag_f8_plan(op, S.OUT16_CODE[c.out16])
+            elif c.entry == "f8_gather":
+                plan = _lib.embedding_gather_f8_plan(op)
+            else:
+                plan = _lib.embedding_gather_plan(op) if c.plan_kind == "gather" else _lib.embbag_plan(op, S.KIND[c.plan_kind])
             res[c.name] = list(plan.values())
     finally:
         param_amd.set_tuning()

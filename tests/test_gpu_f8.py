@@ -4,7 +4,13 @@ tests/f8_rules.py, on bits (``qrows_rules.same_f32`` for fp32 output; for bf16 /
 
 1. every code in every byte lane (decides that the hardware conversion is ``dec``);  2. every group width and column passes;
 3. staged and unstaged tiles, with and without padding;  4. request forms;  5. far addresses;  6. rows in flight 2 / 4 / 8;
-7. the T = 1 modules against torch's CPU functions over the widened table."""
+7. the T = 1 modules against torch's CPU functions over the widened table.
+
+The requests here are a few bags a table: a tile behind tile 0 appears only as 32 bags of one lookup (1) and as the 3-bag second tile
+of D >= 1024 (2), and the un-pooled lookups are one workgroup, but for the T = 300 case.  What a launch of many tiles adds -- full
+tiles behind tile 0 and a partial last one under every block order, compaction over several waves and rounds, 1024-bag tiles, a
+direct tile among compacted ones, every (lane group, rows in flight) pair of both kernels, PARAM_AMD_FWD_STAGE=0 -- is pinned by the
+``f8`` / ``f8_gather`` cases of the plan sweep (tests/plan_sweep.py, tests/test_gpu_plan_sweep.py), under the plan each case names."""
 import numpy as np
 import pytest
 import torch
@@ -13,6 +19,7 @@ from param_amd import _lib
 from tests import f8_rules as R
 from tests import far_rows as FR
 from tests import out16_rules as O
+from tests.f8_rules import finite_codes
 from tests.qrows_rules import same_f32
 
 pytestmark = pytest.mark.gpu
@@ -47,12 +54,6 @@ def same(got, want32, odt):
         bad = np.argwhere(g != w)[:8]
         print("first differing elements (index, got, want):", [(tuple(int(i) for i in ix), hex(int(g[tuple(ix)])), hex(int(w[tuple(ix)]))) for ix in bad])
     return ok
-
-
-def finite_codes(rng, fmt, shape):
-    c = rng.integers(0, 256, shape, dtype=np.uint8)
-    bad = (c & 0x7f) == 0x7f if fmt == "e4m3" else (c & 0x7f) >= 0x7c
-    return np.where(bad, c & 0x3f, c).astype(np.uint8)
 
 
 def module(fmt, tables, **kw):

@@ -13,7 +13,11 @@ For every case: the knobs are set, ``pm_embbag_plan`` must report the plan pinne
 known to be of THAT variant, environment included), the entry point runs with int64 and int32 indices and both layouts, and the output
 must equal the rule of its operation bit for bit -- ``coracle.fwd_batched``, ``padding_rules.forward``, ``mean_rules.forward``,
 ``out16_rules.forward``, ``max_rules.forward`` (values and ``max_indices``, with and without the arg-max output), ``embedding_rules.forward``,
-the rowquant reference and the default-knob bytes; a batch slice writes into a NaN canvas that must stay NaN elsewhere.  The entry
+the rowquant reference and the default-knob bytes; a batch slice writes into a NaN canvas that must stay NaN elsewhere.  The FP8 lookups
+(``f8_fwd_kernel<WT, G, U, WEIGHTED, MEAN, OT>``, ``embedding_gather_f8_kernel<WT, OT, G, U>``; tests/test_gpu_f8.py runs one tile a table)
+have their multi-tile paths pinned here: groups ``f8_*`` hold ``Float8BatchedEmbeddingBagMI355`` to ``f8_rules.forward`` / ``sequence``
+under ``pm_embbag_f8_plan`` / ``pm_embedding_gather_f8_plan`` -- tiles behind tile 0, the block orders, compaction over several waves and
+rounds, 1024-bag and direct tiles, every (lane group, rows in flight) pair of both kernels.  The entry
 points on the base plan equal their default-knob bits and their rule; the one non-deterministic entry, the alternates' atomic backward, is held to the fuzz test's 1e-5 bar.  No tolerance is new.
 
 One test is one group: a few dozen launches on one small request.  The groups with an environment setting run in a fresh child each

@@ -132,6 +132,92 @@ def test_auto_cases_plan_what_the_benchmark_shapes_plan():
         assert rows[case]["plan"][0] == -(-c.req.B // want[0][1])
 
 
+def _f8_conditions(cases, missing):
+    """the FP8 entries (``f8``: pm_embbag_fwd_f8, ``f8_gather``: pm_embedding_gather_f8).  Every condition reads the label
+    ``plan_sweep.f8_label`` derives from the request's offsets, indices and pads next to the pinned plan.  At the end: every FP8 case is
+    the last one left to meet some condition, so deleting any of them is noticed."""
+    f8 = [(c, w, p) for c, w, p in cases if c.entry.startswith("f8")]
+    assert all("f8" in w for c, w, p in f8) and not any("f8" in w for c, w, p in cases if not c.entry.startswith("f8"))
+    held = []                                                      # (the cases that meet a condition, how many it asks for)
+
+    def need(what, cond, at_least=1):
+        got = [c.name for c, w, p in f8 if cond(c, w, p)]
+        held.append((got, at_least))
+        if len(got) < at_least:
+            missing.append("f8: " + what)
+
+    pooled = lambda c, w: "pooled" in w and not c.env                                           # noqa: E731
+    tiles = lambda p: p["tiles_per_table"]                                                      # noqa: E731
+    modes = ("unweighted", "weighted", "mean")
+    # the multi-tile baseline: at least three tiles a table, a partial last one, two bags per lane group
+    base = lambda c, w, p: pooled(c, w) and {"G16", "bpb32", "u2", "tile>NG", "partial", "xcd0"} <= w and tiles(p) >= 3 and c.dims[0] == 256  # noqa: E731
+    for fmt in S.F8_DTYPE:
+        for mode in modes:
+            need(f"baseline {fmt} {mode}, fp32 rows leave one by one", lambda c, w, p: base(c, w, p) and {fmt, mode, "out-fp32", "plain"} <= w)
+            need(f"baseline {fmt} {mode}, bf16 burst", lambda c, w, p: base(c, w, p) and {fmt, mode, "out-bf16", "staged"} <= w)
+    for mode in modes:
+        need(f"baseline {mode}, bf16 with stage_out 0", lambda c, w, p: base(c, w, p) and {mode, "out-bf16", "plain"} <= w)
+    need("baseline fp16 burst", lambda c, w, p: base(c, w, p) and {"out-fp16", "staged"} <= w)
+    # ... and with fp32 rows through the burst (two bags per lane group: G = 8 and D <= 64 only)
+    for mode in modes:
+        for burst in ("staged", "plain"):
+            need(f"64-bag tiles of fp32 rows {mode} {burst}",
+                 lambda c, w, p: pooled(c, w) and {"G8", "bpb64", "u2", "tile>NG", "partial", "out-fp32", mode, burst} <= w and tiles(p) >= 3)
+    # every lane-group width x every depth, two bags per lane group, more than one tile a table
+    for G, D, _ in S.F8_GROUP_DIMS:
+        group = lambda c, w, p: pooled(c, w) and {f"G{G}", f"bpb{512 // G}", "tile>NG", "partial"} <= w and tiles(p) > 1 and c.dims[0] == D \
+            and c.request == "pad100"                                                          # noqa: E731
+        for u in (2, 4, 8):
+            for mode in modes[:2]:
+                need(f"G{G} u{u} {mode}", lambda c, w, p: group(c, w, p) and {f"u{u}", mode} <= w)
+        need(f"G{G} mean", lambda c, w, p: group(c, w, p) and "mean" in w)
+    # compaction: each of the three reached weighted, unweighted and under mean
+    for word in ("rounds>1", "waves>1", "carry"):
+        for mode in modes:
+            need(f"{word} {mode}", lambda c, w, p: pooled(c, w) and {word, mode} <= w)
+    # block orders, a slice, each over more than one tile a table
+    for x in (0, 1, 3):
+        need(f"xcd_affine {x}, the product's tile", lambda c, w, p: pooled(c, w) and {f"xcd{x}", "G8", "bpb32", "staged", "partial", "unweighted"} <= w
+             and tiles(p) > 1 and not {"slice", "direct"} & w and c.dims == [128] * c.req.T)
+    need("xcd_affine 1 on 8 tables", lambda c, w, p: pooled(c, w) and "xcd1" in w and c.req.T == 8 and tiles(p) > 1)
+    for mode in ("unweighted", "mean"):
+        need(f"slice inside tiles {mode}", lambda c, w, p: pooled(c, w) and {"slice", "partial", mode} <= w and tiles(p) > 1
+             and c.bag_slice[0] % p["bags_per_block"] and sum(c.bag_slice) % p["bags_per_block"])
+    # 1024-bag tiles whose indices are compacted in LDS: the fifth bound, ten rounds
+    for mode in modes:
+        for out in ("out-fp32", "out-bf16"):
+            need(f"1024 bags {mode} {out}", lambda c, w, p: pooled(c, w) and {"bounds5", "bpb1024", "rounds>1", "waves>1", "carry", mode, out} <= w
+                 and c.req.B > 1024)
+    # a direct tile with padding among compacted tiles
+    for mode in modes:
+        for u in (2, 8):
+            need(f"direct {mode} u{u}", lambda c, w, p: pooled(c, w) and {"direct", "rounds>1", "bpb32", mode, f"u{u}"} <= w and p["idx_cap"] == 1280
+                 and c.req.pads is not None and tiles(p) > 1)
+    need("mixed dims, the lane group sized for 128", lambda c, w, p: pooled(c, w) and "G8" in w and c.dims == [16, 64, 128] and tiles(p) > 1)
+    wide = lambda c, w, p: pooled(c, w) and {"G32", "bpb16", "tile>NG"} <= w and c.dims[0] == 512 and tiles(p) > 1       # noqa: E731
+    need("D = 512, 2-byte outputs: staged", lambda c, w, p: wide(c, w, p) and {"out-bf16", "staged"} <= w)
+    need("D = 512, 4-byte outputs: not staged", lambda c, w, p: wide(c, w, p) and {"out-fp32", "plain"} <= w and not c.forward)
+    need("two column passes over more than one tile", lambda c, w, p: pooled(c, w) and {"G64", "passes2", "tile>NG"} <= w and tiles(p) > 1)
+    need("FWD_STAGE=0", lambda c, w, p: c.env.get("PARAM_AMD_FWD_STAGE") == 0 and {"pooled", "plain", "bpb32"} <= w and tiles(p) > 1
+         and p["bags_per_block"] * c.dims[0] * 4 <= 16384)
+    # the gather: 16 (G, U) pairs over tens of tiles with a last one that is not full, both orders
+    gp = lambda p: dict(zip(S.GATHER_FIELDS, p.values()))                                       # noqa: E731
+    rows = lambda c, w, p: "unpooled" in w and "partial" in w and gp(p)["grid"] > 8                    # noqa: E731
+    for G in (8, 16, 32, 64):
+        for u in (1, 2, 4, 8):
+            need(f"gather G{G} u{u}", lambda c, w, p: rows(c, w, p) and {f"G{G}", f"u{u}", "out-fp32", "e4m3", "xcd1", "passes1"} <= w and "slice" not in w)
+    for u in (1, 2, 4, 8):
+        for out in ("out-bf16", "out-fp16"):
+            need(f"gather u{u} {out}", lambda c, w, p: rows(c, w, p) and {f"u{u}", out} <= w)
+    need("gather xcd0", lambda c, w, p: rows(c, w, p) and "xcd0" in w)
+    need("gather two passes", lambda c, w, p: {"unpooled", "passes2", "G64"} <= w and c.dims[0] == 512)
+    need("gather slice", lambda c, w, p: rows(c, w, p) and "slice" in w and c.bag_slice[0] > 0)
+    need("gather e5m2 next to e4m3 at one (G, U)", lambda c, w, p: rows(c, w, p) and "e5m2" in w
+         and any("e4m3" in w2 and w2 - {"e4m3"} == w - {"e5m2"} for _, w2, _ in f8))
+    spare = [c.name for c, w, p in f8 if not any(c.name in got and len(got) == n for got, n in held)]
+    assert not spare, f"FP8 cases that no condition depends on: {spare}"
+
+
 def test_the_sweep_reaches_every_variant():
     """conditions on the case list -- on the labels derived from the PLANS -- so that it cannot quietly stop covering a variant"""
     rows = _pinned()
@@ -257,13 +343,15 @@ def test_the_sweep_reaches_every_variant():
     need("FLAT_BAGS=48", lambda c, w, p: env(c, "PARAM_AMD_FLAT_BAGS", 48) and {"flat", "bpb48", "target64"} <= w, 2)
     need("FWD_STAGE=0: forward", lambda c, w, p: env(c, "PARAM_AMD_FWD_STAGE", 0) and {"tile", "plain"} <= w, 2)
     need("FWD_STAGE=0: padded family", lambda c, w, p: env(c, "PARAM_AMD_FWD_STAGE", 0) and {"pad", "plain"} <= w and "max" not in w, 2)
+    _f8_conditions(cases, missing)
     assert not missing, missing
     assert len(S.ENV_GROUPS) == 6 and len({tuple(sorted(c.env.items())) for c in S.CASES if c.env}) == 6
     assert all(max(c.req.rows) <= 1000 for c in S.CASES)
     # both index types and, where the dims are equal, both layouts: every case runs them (tests/plan_sweep_worker.py: variants)
     for c in S.CASES:
         v = W.variants(c)
-        assert {i for i, _ in v} == {"i64", "i32"} and (len(set(c.dims)) > 1 or c.entry == "gather" or {lay for _, lay in v} == {"bd", "tbd"}), c.name
+        assert {i for i, _ in v} == {"i64", "i32"} and (len(set(c.dims)) > 1 or c.entry in ("gather", "f8_gather")
+                                                        or {lay for _, lay in v} == {"bd", "tbd"}), c.name
 
 
 def test_the_padded_requests_serve_max_pooling():
