@@ -791,6 +791,55 @@ int pm_embedding_gather_f8(const pm_embbag_batch* op, int32_t out_dtype, void* o
 int pm_embedding_gather_f8_plan(const pm_embbag_batch* op, int64_t out[8]);
 
 /*
+ * SCALED FP8 TABLES -- FP8 TABLES with a power-of-two scale: a quantiser, and the pooled and the un-pooled lookup reading what it writes.
+ * A plain cast to FP8 loses a table of small values (|x| <= 3.2e-4, the uniform init of 10 M rows, is all zeros in e4m3fn); fbgemm's FP8
+ * int-nbit tables carry an exponent bias per module for the same reason.
+ * THE STORED VALUE of element (r, c) of table t is  v = dec(code[r, c]) * 2^(E_t + e_r):  dec as in FP8 TABLES; E_t an int32 per table
+ * (table_exp, a device array of num_tables values), e_r an int8 per row (row_exp, a device array of num_tables device pointers to int8
+ * [rows[t]]).  Either array may be absent (NULL), which means 0; E_t + e_r lies in [-64, 64] (the caller's contract; the kernels clamp the
+ * sum to that range before they build 2^s from it).  In that range v is exact in fp32 for every non-NaN code of both formats and always
+ * normal (the smallest magnitude is 2^-16 * 2^-64), so the rule does not depend on how a kernel forms v.
+ * THE RULE, pooled (pm_embbag_fwd_f8_scaled): pm_embbag_fwd_f8's with v in the place of dec(code) -- padding lookups removed first; per
+ * column from +0.0 in index order acc = acc + v, weighted acc = fmaf(w_j, v, acc); mean: one correctly rounded division by the kept count;
+ * an empty or all-padding bag gives +0.0; a 16-bit output is rounded once.  Un-pooled (pm_embedding_gather_f8_scaled): conv(v).  Both are
+ * torch's CPU embedding_bag / embedding over the dequantised fp32 table, bit for bit (tests/f8s_rules.py, tests/test_f8s_host.py).
+ * THE QUANTISER.  src: n_rows rows of dim columns of src_dtype (PM_F32 | PM_BF16 | PM_F16, widened exactly), src_row_stride elements
+ * apart.  fmax = 1.75 * 2^k: k = 8 for e4m3fn (448), k = 15 for e5m2 (57344).
+ *   pm_f8_row_exponents: amax = the maximum of |x_c| over the row's FINITE elements; with amax = m * 2^q, 1 <= m < 2, read from the fp32
+ *     exponent and mantissa fields with integer arithmetic, e = q - k if m <= 1.75, else q - k + 1, clamped to [-64, 64]; a row with amax == 0
+ *     or no finite element gets -64.  e is the smallest exponent at which the row does not overflow.  row_exp[r] = e.
+ *   pm_rows_quantize_f8: s = clamp(E + e_r) with E = table_exp[0] (a device int32; NULL = 0) and e_r = row_exp[r] (NULL = 0);
+ *     code = cast(x * 2^-s), cast = torch's CPU .to(float8 dtype): round to nearest even, NaN gives a NaN code, +-Inf gives +-Inf in e5m2 and
+ *     NaN in e4m3fn, and so does a finite product that rounds past fmax (e4m3fn: above 464; e5m2: from 61440 on).  The product is exact
+ *     wherever it matters (what it can lose lies below half the format's smallest subnormal), and a finite element never overflows at its
+ *     row's exponent or a larger one: E_t = max_r e_r is the per-table exponent.  The sign and payload of NaN codes are not part of the rule.
+ *     dst: uint8 [n_rows, dim], rows back to back.
+ * Kernels: csrc/f8_quantize.hip (a lane group per row, 16-byte loads, amax an integer maximum reduced by a fixed butterfly, no atomics; the
+ * hardware conversion v_cvt_pk_fp8_f32 / _bf8_f32 up to fmax, explicit selects above), csrc/embbag_fwd_f8s_kernel.inc (the FP8 kernel's
+ * tiling; v = the hardware widening times 2^s built from its bits; row exponents are loaded where the tile's indices are staged and
+ * compacted into LDS next to them) and csrc/embedding_gather_f8s.hip.  No atomics, no workspace, stream-ordered, 64-bit row addressing.
+ * Refused on the host, before any HIP call: what pm_embbag_fwd_f8 / pm_embedding_gather_f8 refuse; table_exp and row_exp both NULL (that
+ * request is the unscaled call's; PM_ERR_INVALID).  The quantiser: a src_dtype other than the three, an f8_dtype other than the two, a
+ * negative n_rows (PM_ERR_INVALID); dim not a multiple of 16 or above 2048 (PM_ERR_UNSUPPORTED); src_row_stride below dim or not a whole
+ * number of 16-byte pieces; then, unless n_rows == 0 (PM_OK without a launch), a NULL or not 16-byte aligned src or dst, a NULL row_exp
+ * output (PM_ERR_INVALID).
+ * pm_embbag_f8_scaled_plan(op, out_dtype, mean, row_exponents 0 / 1, out[12]): the geometry the pooled call WOULD use: pm_embbag_f8_plan's,
+ * except that the row exponents' LDS bytes (one per index-tile entry) drop the output burst (stage_out = 0) where the tile would pass
+ * 64 KiB with it -- explicit weighted tiles of 512 bags and more.  The un-pooled call's geometry is pm_embedding_gather_f8_plan's.
+ * Left out: scales that are not powers of two, MX block scales, FP8 output, a format per table, max pooling, pruning, any backward.
+ * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these six finds out at symbol resolution.
+ */
+int pm_f8_row_exponents(const void* src, int32_t src_dtype, int64_t n_rows, int32_t dim, int64_t src_row_stride, int32_t f8_dtype, int8_t* row_exp,
+                        pm_stream_t stream);
+int pm_rows_quantize_f8(const void* src, int32_t src_dtype, int64_t n_rows, int32_t dim, int64_t src_row_stride, int32_t f8_dtype,
+                        const int32_t* table_exp, const int8_t* row_exp, void* dst, pm_stream_t stream);
+int pm_embbag_fwd_f8_scaled(const pm_embbag_batch* op, const int64_t* padding_idx, int32_t mean, int32_t out_dtype, const int32_t* table_exp,
+                            const int8_t* const* row_exp, void* out, pm_stream_t stream);
+int pm_embbag_f8_scaled_plan(const pm_embbag_batch* op, int32_t out_dtype, int32_t mean, int32_t row_exponents, int32_t out[12]);
+int pm_embedding_gather_f8_scaled(const pm_embbag_batch* op, int32_t out_dtype, const int32_t* table_exp, const int8_t* const* row_exp, void* out,
+                                  int64_t out_row_stride, pm_stream_t stream);
+
+/*
  * SEQUENCE GRADIENTS -- the batched backward of the un-pooled lookup above: the gradient of pm_embedding_gather's rows applied to all
  * num_tables tables by one sort and one apply.  The request is the one pm_embedding_gather takes: table t owns the lookup positions
  * [offsets[t * batch], offsets[(t + 1) * batch]), the last table ends at num_indices; the bags inside a table matter only for the

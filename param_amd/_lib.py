@@ -104,6 +104,11 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_f8_plan",
     "pm_embedding_gather_f8",
     "pm_embedding_gather_f8_plan",
+    "pm_f8_row_exponents",
+    "pm_rows_quantize_f8",
+    "pm_embbag_fwd_f8_scaled",
+    "pm_embbag_f8_scaled_plan",
+    "pm_embedding_gather_f8_scaled",
 )
 # table element types of the FP8 lookups alone (include/param_amd.h, FP8 TABLES): every other entry point refuses them
 PM_F8E4M3, PM_F8E5M2 = 3, 4
@@ -359,6 +364,18 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embedding_gather_f8.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, vp, i64, vp]
     L.pm_embedding_gather_f8_plan.restype = ctypes.c_int
     L.pm_embedding_gather_f8_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), ctypes.POINTER(i64)]
+    # scaled FP8 tables: the quantiser (src, src_dtype, n_rows, dim, src_row_stride, f8_dtype, [table_exp | NULL, row_exp | NULL,] out, stream)
+    # and the lookups with (table_exp | NULL, row_exp | NULL) in front of out; the pooled plan: (op, out_dtype, mean, row_exponents, out[12])
+    L.pm_f8_row_exponents.restype = ctypes.c_int
+    L.pm_f8_row_exponents.argtypes = [vp, i32, i64, i32, i64, i32, vp, vp]
+    L.pm_rows_quantize_f8.restype = ctypes.c_int
+    L.pm_rows_quantize_f8.argtypes = [vp, i32, i64, i32, i64, i32, vp, vp, vp, vp]
+    L.pm_embbag_fwd_f8_scaled.restype = ctypes.c_int
+    L.pm_embbag_fwd_f8_scaled.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, i32, vp, vp, vp, vp]
+    L.pm_embbag_f8_scaled_plan.restype = ctypes.c_int
+    L.pm_embbag_f8_scaled_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, i32, i32, ctypes.POINTER(i32)]
+    L.pm_embedding_gather_f8_scaled.restype = ctypes.c_int
+    L.pm_embedding_gather_f8_scaled.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, vp, vp, vp, i64, vp]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]
@@ -460,6 +477,13 @@ def embbag_f8_plan(op: pm_embbag_batch, out_dtype: int = PM_F32) -> dict:
     """``pm_embbag_f8_plan``: the geometry ``pm_embbag_fwd_f8`` would use for ``op`` -- ``PLAN_FIELDS`` by name"""
     out = (ctypes.c_int32 * len(PLAN_FIELDS))()
     check(load().pm_embbag_f8_plan(ctypes.byref(op), int(out_dtype), out))
+    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
+
+
+def embbag_f8_scaled_plan(op: pm_embbag_batch, out_dtype: int = PM_F32, mean: bool = False, row_exponents: bool = False) -> dict:
+    """``pm_embbag_f8_scaled_plan``: the geometry ``pm_embbag_fwd_f8_scaled`` would use for ``op`` -- ``PLAN_FIELDS`` by name"""
+    out = (ctypes.c_int32 * len(PLAN_FIELDS))()
+    check(load().pm_embbag_f8_scaled_plan(ctypes.byref(op), int(out_dtype), int(bool(mean)), int(bool(row_exponents)), out))
     return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
 
 

@@ -863,6 +863,119 @@ int pm_embedding_gather_f8_plan(const pm_embbag_batch* op, int64_t out[8]) {
     return PM_OK;
 }
 
+// ---- scaled FP8 tables (embbag_fwd_f8s_kernel.inc, embedding_gather_f8s.hip, f8_quantize.hip) ----------------------------------------------
+// the lookups: f8_request's refusals, then the exponents -- at least one of the two arrays (none is the unscaled call's request)
+static int f8s_request(const pm_embbag_batch* op, int32_t out_dtype, bool gather, const int32_t* table_exp, const int8_t* const* row_exp,
+                       const pm::PlanKnobs& knobs) {
+    const int rc = f8_request(op, out_dtype, gather, knobs);
+    if (rc != PM_OK) return rc;
+    if (!table_exp && !row_exp)
+        return fail(PM_ERR_INVALID, "table_exp and row_exp are both NULL: an unscaled table is pm_embbag_fwd_f8's / pm_embedding_gather_f8's");
+    return PM_OK;
+}
+
+// the pooled plan: plan_f8's, with the burst dropped where the row exponents' LDS bytes push the tile past 64 KiB (f8s_stage_out)
+static pm::LaunchPlan f8s_plan(const pm_embbag_batch* op, int32_t out_dtype, bool mean, bool row, const pm::PlanKnobs& knobs) {
+    const int out_bytes = out_dtype == PM_F32 ? 4 : 2;
+    pm::LaunchPlan plan = pm::plan_f8(*op, knobs, out_bytes);
+    plan.stage_out = pm::f8s_stage_out(plan.bags_per_block, plan.idx_cap, op->per_sample_weights && !mean, row, plan.stage_out, out_bytes);
+    return plan;
+}
+
+int pm_embbag_fwd_f8_scaled(const pm_embbag_batch* op, const int64_t* padding_idx, int32_t mean, int32_t out_dtype, const int32_t* table_exp,
+                            const int8_t* const* row_exp, void* out, pm_stream_t stream) {
+    const pm::PlanKnobs knobs = current_knobs();
+    int rc = f8s_request(op, out_dtype, false, table_exp, row_exp, knobs);
+    if (rc != PM_OK) return rc;
+    if (mean != 0 && mean != 1) return fail(PM_ERR_INVALID, "mean must be 0 or 1");
+    if (mean && (rc = weighted_mean_refused(op)) != PM_OK) return rc;
+    const pm::LaunchPlan plan = f8s_plan(op, out_dtype, mean != 0, row_exp != nullptr, knobs);
+    if (pm::ceil_div(op->bag_count, plan.bags_per_block) * op->num_tables > pm::kMaxGrid) return fail(PM_ERR_UNSUPPORTED, "grid too large");
+    pm::KParams p;
+    fill_params(op, plan, p);
+    const bool e4m3 = op->weight_dtype == PM_F8E4M3;
+    const auto launch = row_exp ? (e4m3 ? pm::launch_embbag_fwd_f8s_e4m3_row : pm::launch_embbag_fwd_f8s_e5m2_row)
+                                : (e4m3 ? pm::launch_embbag_fwd_f8s_e4m3_table : pm::launch_embbag_fwd_f8s_e5m2_table);
+    const pm::F8sArgs args = {padding_idx, table_exp, row_exp};
+    return padded_forward(p, out, out_dtype == PM_F32 ? 16 : 8, stream, [&](const pm::KParams& q, hipStream_t s) {
+        return launch(q, op->max_dim, plan.unroll, args, mean != 0, out_dtype, s);
+    }, "pm_embbag_fwd_f8_scaled launch");
+}
+
+int pm_embbag_f8_scaled_plan(const pm_embbag_batch* op, int32_t out_dtype, int32_t mean, int32_t row_exponents, int32_t out[12]) {
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const pm::PlanKnobs knobs = current_knobs();
+    const int rc = f8_request(op, out_dtype, false, knobs);
+    if (rc != PM_OK) return rc;
+    if ((mean != 0 && mean != 1) || (row_exponents != 0 && row_exponents != 1)) return fail(PM_ERR_INVALID, "mean and row_exponents must be 0 or 1");
+    const pm::LaunchPlan p = f8s_plan(op, out_dtype, mean != 0, row_exponents != 0, knobs);
+    if (pm::ceil_div(op->bag_count, p.bags_per_block) * op->num_tables > pm::kMaxGrid) return fail(PM_ERR_UNSUPPORTED, "grid too large");
+    const int32_t v[12] = {p.tiles_per_table, p.bags_per_block, p.idx_cap, p.xcd_affine, p.nt_loads, p.ordered,
+                           p.stage_out, p.stage_bags, p.flat_bags, p.flat_target, p.flat_compact, p.unroll};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return PM_OK;
+}
+
+int pm_embedding_gather_f8_scaled(const pm_embbag_batch* op, int32_t out_dtype, const int32_t* table_exp, const int8_t* const* row_exp, void* out,
+                                  int64_t out_row_stride, pm_stream_t stream) {
+    const pm::PlanKnobs knobs = current_knobs();
+    const int rc = f8s_request(op, out_dtype, true, table_exp, row_exp, knobs);
+    if (rc != PM_OK) return rc;
+    if (out_row_stride < op->max_dim || out_row_stride % 4 != 0)
+        return fail(PM_ERR_INVALID, "out_row_stride must be a multiple of 4 elements and at least max_dim");
+    if (op->num_indices == 0 || op->bag_count == 0) return PM_OK;      // nothing to write, whatever `out` is
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const uintptr_t align = out_dtype == PM_F32 ? 16 : 8;
+    if (reinterpret_cast<uintptr_t>(out) % align != 0) return fail(PM_ERR_INVALID, "out must be " + std::to_string(align) + "-byte aligned");
+    const pm::GatherPlan g = pm::plan_gather_f8(*op, knobs);           // (the unscaled gather's geometry: pm_embedding_gather_f8_plan reports it)
+    if (g.grid > pm::kMaxGrid) return fail(PM_ERR_UNSUPPORTED, "grid too large");
+    pm::KParams p;
+    fill_params(op, pm::LaunchPlan{}, p);
+    p.io = static_cast<float*>(out);
+    p.out_stride = out_row_stride;
+    const hipError_t h = pm::launch_embedding_gather_f8s(p, op->weight_dtype, out_dtype, g, table_exp, row_exp, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embedding_gather_f8_scaled launch");
+    return PM_OK;
+}
+
+// the quantiser's arguments, in one order for both calls (out: row_exp / dst, whose alignment rule is the caller's)
+static int f8_quantize_args(const void* src, int32_t src_dtype, int64_t n_rows, int32_t dim, int64_t src_row_stride, int32_t f8_dtype) {
+    if (!dtype_is_weight(src_dtype)) return fail(PM_ERR_INVALID, "src_dtype must be PM_F32, PM_BF16 or PM_F16");
+    if (f8_dtype != PM_F8E4M3 && f8_dtype != PM_F8E5M2) return fail(PM_ERR_INVALID, "f8_dtype must be PM_F8E4M3 or PM_F8E5M2");
+    if (n_rows < 0) return fail(PM_ERR_INVALID, "n_rows is negative");
+    if (dim < 16 || dim % pm::kF8LaneColumns != 0) return fail(PM_ERR_UNSUPPORTED, "FP8 tables: dim must be a multiple of 16");
+    if (dim > pm::kF8MaxDim) return fail(PM_ERR_UNSUPPORTED, "FP8 tables: dim must be at most " + std::to_string(pm::kF8MaxDim));
+    const int64_t es = src_dtype == PM_F32 ? 4 : 2;
+    if (src_row_stride < dim || src_row_stride * es % 16 != 0)
+        return fail(PM_ERR_INVALID, "src_row_stride (elements) must be at least dim and a whole number of 16-byte pieces");
+    if (n_rows == 0) return PM_OK;
+    if (!src) return fail(PM_ERR_INVALID, "src is NULL");
+    if (reinterpret_cast<uintptr_t>(src) % 16 != 0) return fail(PM_ERR_INVALID, "src must be 16-byte aligned");
+    return PM_OK;
+}
+
+int pm_f8_row_exponents(const void* src, int32_t src_dtype, int64_t n_rows, int32_t dim, int64_t src_row_stride, int32_t f8_dtype, int8_t* row_exp,
+                        pm_stream_t stream) {
+    const int rc = f8_quantize_args(src, src_dtype, n_rows, dim, src_row_stride, f8_dtype);
+    if (rc != PM_OK || n_rows == 0) return rc;
+    if (!row_exp) return fail(PM_ERR_INVALID, "row_exp is NULL");
+    const hipError_t h = pm::launch_f8_row_exponents(src, src_dtype, n_rows, dim, src_row_stride, f8_dtype, row_exp, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_f8_row_exponents launch");
+    return PM_OK;
+}
+
+int pm_rows_quantize_f8(const void* src, int32_t src_dtype, int64_t n_rows, int32_t dim, int64_t src_row_stride, int32_t f8_dtype,
+                        const int32_t* table_exp, const int8_t* row_exp, void* dst, pm_stream_t stream) {
+    const int rc = f8_quantize_args(src, src_dtype, n_rows, dim, src_row_stride, f8_dtype);
+    if (rc != PM_OK || n_rows == 0) return rc;
+    if (!dst) return fail(PM_ERR_INVALID, "dst is NULL");
+    if (reinterpret_cast<uintptr_t>(dst) % 16 != 0) return fail(PM_ERR_INVALID, "dst must be 16-byte aligned");
+    const hipError_t h = pm::launch_rows_quantize_f8(src, src_dtype, n_rows, dim, src_row_stride, f8_dtype, table_exp, row_exp, dst,
+                                                     static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_rows_quantize_f8 launch");
+    return PM_OK;
+}
+
 // ---- row-quantised tables of per-table format (embbag_fwd_qmixed.hip, embedding_gather_qmixed.hip) ---------------------------------------
 // what the four calls refuse on the host, in one order: op, table_bits, the eight-column rule (the stricter of the two formats' column
 // rules, for every table: a lane holds eight columns whatever the format), then what qrows_request refuses about a request of 4-bit

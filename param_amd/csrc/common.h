@@ -264,6 +264,39 @@ hipError_t launch_embedding_gather_qmixed(const KParams& p, const int32_t* table
 hipError_t launch_embbag_fwd_f8_e4m3(const KParams& p, int max_dim, int unroll, const int64_t* pad_idx, bool mean, int out_dtype, hipStream_t stream);
 hipError_t launch_embbag_fwd_f8_e5m2(const KParams& p, int max_dim, int unroll, const int64_t* pad_idx, bool mean, int out_dtype, hipStream_t stream);
 hipError_t launch_embedding_gather_f8(const KParams& p, int weight_dtype, int out_dtype, const GatherPlan& g, hipStream_t stream);
+// SCALED FP8 tables (embbag_fwd_f8s_{e4m3,e5m2}_{table,row}.hip, embedding_gather_f8s.hip, f8_quantize.hip).  The pooled kernel's LDS is
+// the FP8 kernel's -- tile | uint16 s_pre[idx_cap] | burst -- with one exponent byte per index-tile entry behind s_pre when the request
+// has row exponents; where that pushes a tile with its burst past 64 KiB the burst is dropped (f8s_stage_out: the launcher's and
+// pm_embbag_f8_scaled_plan's one rule).
+__host__ __device__ inline size_t f8s_pre_offset(int bags_per_block, int idx_cap, bool weighted) {
+    return tile_lds_bytes(bags_per_block, idx_cap, weighted);
+}
+__host__ __device__ inline size_t f8s_out_offset(int bags_per_block, int idx_cap, bool weighted, bool row) {
+    return (f8s_pre_offset(bags_per_block, idx_cap, weighted) + static_cast<size_t>(idx_cap) * (row ? 3 : 2) + 15) / 16 * 16;
+}
+inline size_t f8s_lds_bytes(int bags_per_block, int idx_cap, bool weighted, bool row, int stage_out, int out_bytes) {
+    return f8s_out_offset(bags_per_block, idx_cap, weighted, row) + (stage_out > 0 ? static_cast<size_t>(bags_per_block) * stage_out * out_bytes : 0);
+}
+inline int f8s_stage_out(int bags_per_block, int idx_cap, bool weighted, bool row, int stage_out, int out_bytes) {
+    return f8s_lds_bytes(bags_per_block, idx_cap, weighted, row, stage_out, out_bytes) > 65536 ? 0 : stage_out;
+}
+// pad_idx, table_exp (device int32 [T]) and row_exp (device [T] pointers to int8 [rows[t]]) may each be NULL, the two exponents not both
+struct F8sArgs {
+    const int64_t* pad_idx;
+    const int32_t* table_exp;
+    const int8_t* const* row_exp;
+};
+hipError_t launch_embbag_fwd_f8s_e4m3_table(const KParams& p, int max_dim, int unroll, const F8sArgs& a, bool mean, int out_dtype, hipStream_t stream);
+hipError_t launch_embbag_fwd_f8s_e4m3_row(const KParams& p, int max_dim, int unroll, const F8sArgs& a, bool mean, int out_dtype, hipStream_t stream);
+hipError_t launch_embbag_fwd_f8s_e5m2_table(const KParams& p, int max_dim, int unroll, const F8sArgs& a, bool mean, int out_dtype, hipStream_t stream);
+hipError_t launch_embbag_fwd_f8s_e5m2_row(const KParams& p, int max_dim, int unroll, const F8sArgs& a, bool mean, int out_dtype, hipStream_t stream);
+hipError_t launch_embedding_gather_f8s(const KParams& p, int weight_dtype, int out_dtype, const GatherPlan& g, const int32_t* table_exp,
+                                       const int8_t* const* row_exp, hipStream_t stream);
+// the quantiser: src of src_dtype (PM_F32 | PM_BF16 | PM_F16) with a row stride in elements; f8_dtype PM_F8E4M3 | PM_F8E5M2
+hipError_t launch_f8_row_exponents(const void* src, int src_dtype, int64_t n_rows, int dim, int64_t stride, int f8_dtype, int8_t* row_exp,
+                                   hipStream_t stream);
+hipError_t launch_rows_quantize_f8(const void* src, int src_dtype, int64_t n_rows, int dim, int64_t stride, int f8_dtype, const int32_t* table_exp,
+                                   const int8_t* row_exp, void* dst, hipStream_t stream);
 
 // sort-based deterministic backward (embbag_bwd_sorted.hip)
 hipError_t sorted_workspace_bytes(const KParams& p, int64_t max_rows, int max_dim, size_t& bytes);

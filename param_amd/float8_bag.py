@@ -1,8 +1,10 @@
 """Pooled and un-pooled lookups over OCP FP8 embedding tables (``csrc/embbag_fwd_f8_kernel.inc`` through ``pm_embbag_fwd_f8``,
-``csrc/embedding_gather_f8.hip`` through ``pm_embedding_gather_f8``).
+``csrc/embedding_gather_f8.hip`` through ``pm_embedding_gather_f8``), plain or with power-of-two scales (``csrc/f8_quantize.hip``,
+``csrc/embbag_fwd_f8s_kernel.inc``, ``csrc/embedding_gather_f8s.hip`` through ``pm_rows_quantize_f8`` / ``pm_embbag_fwd_f8_scaled`` /
+``pm_embedding_gather_f8_scaled``).
 
 * :class:`Float8BatchedEmbeddingBagMI355` -- T tables stored as ``torch.float8_e4m3fn`` or ``torch.float8_e5m2`` bytes, one byte per
-  element, no scale and no bias, pooled (sum, weighted sum or mean, with ``padding_idx``) by ONE launch that reads those bytes;
+  element, pooled (sum, weighted sum or mean, with ``padding_idx``) by ONE launch that reads those bytes;
   ``lookup_sequence`` is its un-pooled lookup.  The serving-side sibling of :class:`BatchedEmbeddingBagMI355`; what fbgemm's
   ``IntNBitTableBatchedEmbeddingBagsCodegen`` is for with ``SparseType.FP8`` tables.
 * :class:`Float8EmbeddingBagMI355` -- the single-table module with ``nn.EmbeddingBag``'s call.
@@ -14,9 +16,17 @@ from +0.0 (one fmaf per lookup when weighted), one correctly rounded division fo
 -- so the result is ``torch.nn.functional.embedding_bag(indices, table.to(torch.float32), ...)`` on the CPU bit for bit, and the
 un-pooled rows are the stored values exactly (``-0.0``, subnormals and +-Inf included; a NaN code gives a NaN).
 
-Forward only: the tables are a buffer, nothing requires grad.  There is no CPU path.  Left out, on purpose: an FP8 quantiser kernel and
-any scaling (per-row or per-table scales: ``from_float`` casts with torch's ``.to(dtype)``), the ``fnuz`` formats, FP8 output, a format
-per table, FP8 next to 8- / 4-bit tables in one launch, max pooling, pruning, any backward, the operator plug-in.
+``scale=None`` (the default) is the plain format: no scale, no bias, ``from_float`` casts with torch's ``.to(dtype)``.  A table of small
+values does not survive that cast (the uniform init of 10 M rows, |x| <= 3.2e-4, is all zeros in e4m3fn), so the three modules take
+``scale="table"`` or ``scale="row"`` (include/param_amd.h, "SCALED FP8 TABLES"): the stored value is ``dec(code) * 2^(E_t + e_r)`` with
+one int32 exponent per table (buffer ``table_exponents``) or one int8 exponent per row (buffer ``row_exponents``), in [-64, 64];
+``quantize_from_`` / ``from_float(..., scale=...)`` run the HIP quantiser (the smallest exponent at which a row -- or the table -- does
+not overflow, then torch's cast of ``x * 2^-s``), and the lookups are the same rule over the dequantised table, bit for bit.  A module
+without a scale makes exactly the calls it made before.
+
+Forward only: the tables are a buffer, nothing requires grad.  There is no CPU path.  Left out, on purpose: scales that are not powers
+of two, MX block scales, the ``fnuz`` formats, FP8 output, a format per table, FP8 next to 8- / 4-bit tables in one launch, max pooling,
+pruning, any backward, the operator plug-in.
 """
 from __future__ import annotations
 
@@ -34,6 +44,8 @@ from .quantized_bag import _QTableSet
 
 MAX_DIM = 2048      # kF8MaxDim (csrc/launch_plan.h)
 _F8 = {torch.float8_e4m3fn: _lib.PM_F8E4M3, torch.float8_e5m2: _lib.PM_F8E5M2}
+_SRC = {torch.float32: _lib.PM_F32, torch.bfloat16: _lib.PM_BF16, torch.float16: _lib.PM_F16}      # what the quantiser reads
+EXP_MIN, EXP_MAX = -64, 64      # the range of a table's plus a row's exponent (csrc/f8s_elem.h)
 _F8_NAMES = {"e4m3": torch.float8_e4m3fn, "fp8_e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2, "fp8_e5m2": torch.float8_e5m2}
 
 
@@ -45,6 +57,17 @@ def float8_dtype(dtype) -> torch.dtype:
         raise ValueError(f"dtype must be torch.float8_e4m3fn or torch.float8_e5m2 (or \"e4m3\" / \"e5m2\" / \"fp8_e4m3\" / \"fp8_e5m2\"), got "
                          f"{dtype!r} (the fnuz formats are not implemented; other table dtypes: BatchedEmbeddingBagMI355)")
     return dt
+
+
+def _scale_kind(scale):
+    if scale is not None and scale not in ("table", "row"):
+        raise ValueError(f'scale must be None, "table" or "row", got {scale!r} (scales that are not powers of two and MX block scales are not implemented)')
+    return scale
+
+
+def _pow2(exponents: torch.Tensor) -> torch.Tensor:
+    """fp32 ``2^e`` for an integer tensor in [-64, 64], built from its bits: exact on every device"""
+    return ((exponents.to(torch.int32) + 127) << 23).view(torch.float32)
 
 
 def _pooling(mode, who: str) -> str:
@@ -97,17 +120,28 @@ class Float8BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     dim; ``padding_idx`` does not affect it); ``sequence_plan(...)`` its geometry.  ``bounds_check_mode`` and ``sanitize_``: see
     :class:`_BoundsChecked`.
 
+    ``scale=None | "table" | "row"`` (include/param_amd.h, "SCALED FP8 TABLES"): with a scale the stored value is ``dec(code) * 2^(E_t +
+    e_r)`` -- ``"table"``: an int32 ``[T]`` buffer ``table_exponents``; ``"row"``: one int8 slab ``row_exponents`` with the per-table
+    view ``row_exponents_of(t)``; every exponent in [-64, 64], all zero at first; both round-trip through ``state_dict``.
+    ``quantize_from_(t, tensor)`` fills table ``t`` from an fp32 / bf16 / fp16 tensor on the device with the HIP quantiser,
+    ``copy_from_(t, codes, exponents=...)`` takes prepacked codes and exponents, ``dequantized_table(t)`` is the fp32 table, and
+    ``from_float(source, dtype, scale=...)`` quantises instead of casting.  ``lookup``, ``forward``, ``lookup_sequence`` and ``plan`` go to
+    the scaled calls when ``scale`` is set, and only then; everything else -- ``bounds_check_mode``, ``padding_idx``, mean,
+    ``output_dtype``, batch slices, ``out=``, mixed dims -- works as without a scale.  With ``scale=None`` the module has the buffers,
+    the ``state_dict`` keys and the calls it had before scales existed.
+
     No parameters; the output never requires grad.  ValueError before anything is allocated: another dtype (``float8_e4m3fnuz``
-    included), dims that are not multiples of 16 or above 2048, ``layout="blocked"``, max / none pooling, ``rows >= 2^31``; a weighted
+    included), a ``scale`` other than the three, dims that are not multiples of 16 or above 2048, ``layout="blocked"``, max / none pooling, ``rows >= 2^31``; a weighted
     mean lookup raises ValueError at the call.  Tensors that are not on a ROCm device raise RuntimeError (no CPU fallback),
     floating-point indices TypeError.
     """
 
     def __init__(self, rows: Sequence[int], dims, dtype=torch.float8_e4m3fn, device="cuda", layout: str = "bd", output_dtype=None,
-                 bounds_check_mode="none", pooling_mode="sum", padding_idx=None):
+                 bounds_check_mode="none", pooling_mode="sum", padding_idx=None, scale=None):
         super().__init__()
         self._init_shared(bounds_check_mode, output_dtype)
         self.dtype = float8_dtype(dtype)
+        self.scale = _scale_kind(scale)
         rows = [int(r) for r in rows]
         dims = [int(dims)] * len(rows) if isinstance(dims, int) else [int(d) for d in dims]
         if len(rows) != len(dims) or not rows:
@@ -134,6 +168,14 @@ class Float8BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         self._starts = starts
         self.register_buffer("weights", torch.zeros(cur, dtype=torch.uint8, device=device))
         self._ts: Optional[_QTableSet] = None
+        # scaled tables: every exponent starts as 0 (with the zero codes: +0.0 everywhere)
+        if self.scale == "table":
+            self.register_buffer("table_exponents", torch.zeros(len(rows), dtype=torch.int32, device=device))
+        elif self.scale == "row":
+            self._row_starts = [sum(rows[:t]) for t in range(len(rows))]
+            self.register_buffer("row_exponents", torch.zeros(sum(rows), dtype=torch.int8, device=device))
+            self._row_ptrs: Optional[torch.Tensor] = None      # device int64 [T]: where each table's exponents start ...
+            self._row_ptrs_base = 0                            # ... for the slab at this address
 
     _TABLES = "weights"
 
@@ -146,16 +188,85 @@ class Float8BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         """table ``t``: the ``[rows_t, D_t]`` view of the buffer in the module's float8 dtype"""
         return self._bytes(t).view(self.dtype)
 
-    def copy_from_(self, t: int, tensor: torch.Tensor) -> None:
-        """fill table ``t`` from a ``[rows_t, D_t]`` tensor of the module's float8 dtype, or of uint8 (the same bytes): a bit copy"""
-        self._bytes(t).copy_(_weight_bytes(tensor, self.dtype, (self.rows[t], self.dims[t]), f"copy_from_: table {t}"))
+    def copy_from_(self, t: int, tensor: torch.Tensor, exponents=None) -> None:
+        """fill table ``t`` from a ``[rows_t, D_t]`` tensor of the module's float8 dtype, or of uint8 (the same bytes): a bit copy.
+        ``exponents`` (scaled modules; None keeps what the module holds): the table's exponent, an int (``scale="table"``), or an
+        integer tensor ``[rows_t]`` of row exponents (``scale="row"``), each in [-64, 64] -- checked here, once, with torch ops"""
+        codes = _weight_bytes(tensor, self.dtype, (self.rows[t], self.dims[t]), f"copy_from_: table {t}")
+        if exponents is not None:
+            if self.scale is None:
+                raise ValueError("copy_from_: exponents need a module with scale=\"table\" or scale=\"row\"")
+            e = torch.as_tensor(exponents)
+            want = () if self.scale == "table" else (self.rows[t],)
+            if e.dtype.is_floating_point or e.dtype == torch.bool or tuple(e.shape) != want:
+                raise ValueError(f"copy_from_: exponents must be {'one int' if self.scale == 'table' else f'an integer tensor of shape {want}'}, got "
+                                 f"{e.dtype} {tuple(e.shape)}")
+            if e.numel() and bool(((e < EXP_MIN) | (e > EXP_MAX)).any()):
+                raise ValueError(f"copy_from_: exponents must lie in [{EXP_MIN}, {EXP_MAX}]")
+            if self.scale == "table":
+                self.table_exponents[t] = int(e)
+            else:
+                self.row_exponents_of(t).copy_(e)
+        self._bytes(t).copy_(codes)
+
+    def row_exponents_of(self, t: int) -> torch.Tensor:
+        """``scale="row"``: the int8 ``[rows_t]`` view of table ``t``'s row exponents"""
+        if self.scale != "row":
+            raise ValueError('row_exponents_of needs a module with scale="row"')
+        return self.row_exponents[self._row_starts[t]:self._row_starts[t] + self.rows[t]]
+
+    def quantize_from_(self, t: int, tensor: torch.Tensor) -> None:
+        """fill table ``t`` of a scaled module from a ``[rows_t, D_t]`` fp32 / bf16 / fp16 tensor on the module's ROCm device with the HIP
+        quantiser: the row exponents (``pm_f8_row_exponents``), for ``scale="table"`` their maximum -- taken on the device, nothing
+        synchronises --, then the codes (``pm_rows_quantize_f8``).  Rows may be strided (``tensor[:, a:b]`` of a wider tensor)."""
+        if self.scale is None:
+            raise ValueError("quantize_from_ needs a module with scale=\"table\" or scale=\"row\" (an unscaled table is torch's cast: copy_from_)")
+        if not isinstance(tensor, torch.Tensor) or tensor.dtype not in _SRC or tuple(tensor.shape) != (self.rows[t], self.dims[t]):
+            raise ValueError(f"quantize_from_: table {t} needs a float32 / bfloat16 / float16 tensor of shape {(self.rows[t], self.dims[t])}, got "
+                             f"{getattr(tensor, 'dtype', type(tensor).__name__)} {tuple(getattr(tensor, 'shape', ()))}")
+        _require_device(self.weights, f"{type(self).__name__}.weights")
+        _require_device(tensor, "tensor")
+        src = tensor.detach()
+        if src.stride(1) != 1 or src.stride(0) < src.shape[1] or (src.stride(0) * src.element_size()) % 16 or src.data_ptr() % 16:
+            src = src.contiguous()
+        L, dst, stream = _lib.load(), self._bytes(t), _stream_ptr()
+        head = (src.data_ptr(), _SRC[src.dtype], self.rows[t], self.dims[t], src.stride(0), _F8[self.dtype])
+        rexp = self.row_exponents_of(t) if self.scale == "row" else torch.empty(self.rows[t], dtype=torch.int8, device=self.weights.device)
+        _lib.check(L.pm_f8_row_exponents(*head, rexp.data_ptr(), stream))
+        if self.scale == "row":
+            _lib.check(L.pm_rows_quantize_f8(*head, None, rexp.data_ptr(), dst.data_ptr(), stream))
+        else:
+            e_t = self.table_exponents[t:t + 1]
+            e_t.copy_(rexp.max().to(torch.int32))
+            _lib.check(L.pm_rows_quantize_f8(*head, e_t.data_ptr(), None, dst.data_ptr(), stream))
+
+    def dequantized_table(self, t: int) -> torch.Tensor:
+        """table ``t`` as fp32: ``dec(code) * 2^(E_t + e_r)``, exactly (an unscaled module: ``table(t).float()``)"""
+        w = self.table(t).to(torch.float32)
+        if self.scale == "table":
+            return w * _pow2(self.table_exponents[t])
+        if self.scale == "row":
+            return w * _pow2(self.row_exponents_of(t))[:, None]
+        return w
+
+    def _exponent_args(self):
+        """(table_exp, row_exp) of the scaled calls: a device pointer or None each"""
+        if self.scale == "table":
+            return self.table_exponents.data_ptr(), None
+        base = self.row_exponents.data_ptr()
+        if self._row_ptrs is None or self._row_ptrs_base != base:
+            self._row_ptrs = torch.tensor([base + s for s in self._row_starts], dtype=torch.int64).to(self.row_exponents.device)
+            self._row_ptrs_base = base
+        return None, self._row_ptrs.data_ptr()
 
     @classmethod
-    def from_float(cls, source, dtype=torch.float8_e4m3fn, **kw):
+    def from_float(cls, source, dtype=torch.float8_e4m3fn, scale=None, **kw):
         """cast a :class:`BatchedEmbeddingBagMI355` (sum or mean pooling; its ``layout``, ``pooling_mode`` and ``padding_idx`` carry
-        over) or a sequence of 2-D floating-point tensors with torch's ``.to(dtype)`` on the device where the source lives; keywords
-        go to the constructor (``device`` defaults to the source's)"""
+        over) or a sequence of 2-D floating-point tensors with torch's ``.to(dtype)`` on the device where the source lives -- or, with
+        ``scale="table"`` / ``"row"``, quantise it with the HIP quantiser on the module's device (``quantize_from_``); keywords go to
+        the constructor (``device`` defaults to the source's)"""
         dt = float8_dtype(dtype)
+        _scale_kind(scale)
         if isinstance(source, BatchedEmbeddingBagMI355):
             kw.setdefault("pooling_mode", _pooling(source.pooling_mode, "from_float"))
             kw.setdefault("padding_idx", source.padding_idx)
@@ -166,9 +277,15 @@ class Float8BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             if not tables or any(not isinstance(x, torch.Tensor) or x.dim() != 2 or not x.dtype.is_floating_point or x.dtype in _F8 for x in tables):
                 raise TypeError("from_float takes a BatchedEmbeddingBagMI355 or a sequence of 2-D floating-point tensors")
         kw.setdefault("device", tables[0].device)
-        m = cls([int(x.shape[0]) for x in tables], [int(x.shape[1]) for x in tables], dt, **kw)
+        if scale is None:
+            m = cls([int(x.shape[0]) for x in tables], [int(x.shape[1]) for x in tables], dt, **kw)
+            for t, x in enumerate(tables):
+                m.copy_from_(t, x.detach().to(dt))
+            return m
+        m = cls([int(x.shape[0]) for x in tables], [int(x.shape[1]) for x in tables], dt, scale=scale, **kw)
         for t, x in enumerate(tables):
-            m.copy_from_(t, x.detach().to(dt))
+            x = x.detach().to(m.weights.device)
+            m.quantize_from_(t, x if x.dtype in _SRC else x.to(torch.float32))
         return m
 
     def _tables(self) -> _QTableSet:
@@ -212,8 +329,12 @@ class Float8BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         elif out.dtype != odt or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != ts.device:
             raise ValueError(f"out must be a contiguous {str(odt).replace('torch.', '')} tensor of shape {shape} on {ts.device}")
         pad = self._pad_dev()
-        rc = _lib.load().pm_embbag_fwd_f8(ctypes.byref(op), None if pad is None else pad.data_ptr(), 1 if self._mean else 0, _WDTYPE[odt],
-                                          out.data_ptr(), _stream_ptr())
+        if self.scale is None:
+            rc = _lib.load().pm_embbag_fwd_f8(ctypes.byref(op), None if pad is None else pad.data_ptr(), 1 if self._mean else 0, _WDTYPE[odt],
+                                              out.data_ptr(), _stream_ptr())
+        else:
+            rc = _lib.load().pm_embbag_fwd_f8_scaled(ctypes.byref(op), None if pad is None else pad.data_ptr(), 1 if self._mean else 0, _WDTYPE[odt],
+                                                     *self._exponent_args(), out.data_ptr(), _stream_ptr())
         if rc:
             _lib.check(rc)
         return out
@@ -225,7 +346,9 @@ class Float8BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         """the launch geometry ``lookup`` would use for this request under the knobs as they stand (``_lib.PLAN_FIELDS`` by name;
         ``pm_embbag_f8_plan``, nothing is launched)"""
         _, _, op = self._request(indices, offsets, per_sample_weights, bag_begin, bag_count, batch, False)
-        return _lib.embbag_f8_plan(op, _WDTYPE[self.output_dtype])
+        if self.scale is None:
+            return _lib.embbag_f8_plan(op, _WDTYPE[self.output_dtype])
+        return _lib.embbag_f8_scaled_plan(op, _WDTYPE[self.output_dtype], self._mean, self.scale == "row")
 
     # -- un-pooled ---------------------------------------------------------------------------
     def _sequence_request(self, indices, offsets, batch, bag_begin, bag_count, sanitize: bool, out=None):
@@ -246,14 +369,19 @@ class Float8BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         if out is None:
             whole = bag_begin == 0 and bag_count in (None, B)
             out = (torch.empty if whole else torch.zeros)((n, D), dtype=odt, device=ts.device)
-        if n:
+        if n and self.scale is not None:
+            rc = _lib.load().pm_embedding_gather_f8_scaled(ctypes.byref(op), _WDTYPE[odt], *self._exponent_args(), out.data_ptr(), D, _stream_ptr())
+            if rc:
+                _lib.check(rc)
+        elif n:
             rc = _lib.load().pm_embedding_gather_f8(ctypes.byref(op), _WDTYPE[odt], out.data_ptr(), D, _stream_ptr())
             if rc:
                 _lib.check(rc)
         return out
 
     def sequence_plan(self, indices, offsets, batch: Optional[int] = None, bag_begin=0, bag_count=None) -> dict:
-        """the launch geometry ``lookup_sequence`` would use (``_lib.GATHER_PLAN_FIELDS`` by name; ``pm_embedding_gather_f8_plan``)"""
+        """the launch geometry ``lookup_sequence`` would use (``_lib.GATHER_PLAN_FIELDS`` by name; ``pm_embedding_gather_f8_plan``: the
+        scaled un-pooled lookup has the unscaled one's geometry)"""
         _, _, op = self._sequence_request(indices, offsets, batch, bag_begin, bag_count, False)
         return _lib.embedding_gather_f8_plan(op)
 
@@ -267,7 +395,8 @@ class Float8BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
     def extra_repr(self) -> str:
         return (f"rows={self.rows}, dims={self.dims}, dtype={self.dtype}, layout={self.layout}, pooling_mode={self.pooling_mode}" +
                 (f", padding_idx={self.padding_idx}" if self.padding_idx is not None else "") +
-                (f", output_dtype={self.output_dtype}" if self._out16 is not None else ""))
+                (f", output_dtype={self.output_dtype}" if self._out16 is not None else "") +
+                (f", scale={self.scale}" if self.scale is not None else ""))
 
 
 def _torch_weight(module, kinds, what: str) -> torch.Tensor:
@@ -276,6 +405,13 @@ def _torch_weight(module, kinds, what: str) -> torch.Tensor:
     if getattr(module, "max_norm", None) is not None:
         raise ValueError("from_float: max_norm is not implemented (the rows would be renormalised at lookup time)")
     return module.weight.detach()
+
+
+def _quantized(m, w: torch.Tensor):
+    """the single-table modules' ``from_float(..., scale=...)``: the source's weight through the quantiser on the module's device"""
+    w = w.to(m.weights.device)
+    m.quantize_from_(0, w if w.dtype in _SRC else w.to(torch.float32))
+    return m
 
 
 class Float8EmbeddingBagMI355(Float8BatchedEmbeddingBagMI355):
@@ -289,12 +425,13 @@ class Float8EmbeddingBagMI355(Float8BatchedEmbeddingBagMI355):
     ``.to(dtype)``.  Refusals as the batched module's; ``mode="max"`` raises ValueError."""
 
     def __init__(self, num_embeddings: int, embedding_dim: int, dtype=torch.float8_e4m3fn, mode="sum", padding_idx=None, device="cuda",
-                 output_dtype=None, bounds_check_mode="none", weight: Optional[torch.Tensor] = None):
+                 output_dtype=None, bounds_check_mode="none", weight: Optional[torch.Tensor] = None, scale=None):
         dt = float8_dtype(dtype)
+        _scale_kind(scale)
         if weight is not None:
             weight = _weight_bytes(weight, dt, (int(num_embeddings), int(embedding_dim)), "weight")
         super().__init__([num_embeddings], [embedding_dim], dt, device=device, layout="bd", output_dtype=output_dtype,
-                         bounds_check_mode=bounds_check_mode, pooling_mode=mode, padding_idx=padding_idx)
+                         bounds_check_mode=bounds_check_mode, pooling_mode=mode, padding_idx=padding_idx, scale=scale)
         self.num_embeddings, self.embedding_dim, self.mode = int(num_embeddings), int(embedding_dim), self.pooling_mode
         self._off2d: dict = {}
         if weight is not None:
@@ -303,13 +440,15 @@ class Float8EmbeddingBagMI355(Float8BatchedEmbeddingBagMI355):
     _bags_2d = EmbeddingBagMI355._bags_2d
 
     @classmethod
-    def from_float(cls, module, dtype=torch.float8_e4m3fn, **kw):
+    def from_float(cls, module, dtype=torch.float8_e4m3fn, scale=None, **kw):
         w = _torch_weight(module, (EmbeddingBagMI355, nn.EmbeddingBag), "an EmbeddingBagMI355 or a torch.nn.EmbeddingBag")
         dt = float8_dtype(dtype)
         kw.setdefault("mode", _pooling(module.mode, "from_float"))
         kw.setdefault("padding_idx", module.padding_idx)
         kw.setdefault("device", w.device if w.is_cuda else "cuda")
-        return cls(int(w.shape[0]), int(w.shape[1]), dt, weight=w.to(dt), **kw)
+        if _scale_kind(scale) is None:
+            return cls(int(w.shape[0]), int(w.shape[1]), dt, weight=w.to(dt), **kw)
+        return _quantized(cls(int(w.shape[0]), int(w.shape[1]), dt, scale=scale, **kw), w)
 
     def forward(self, input, offsets=None, per_sample_weights=None):
         if input.dim() == 2:
@@ -335,12 +474,13 @@ class Float8EmbeddingMI355(Float8BatchedEmbeddingBagMI355):
     ``padding_idx`` changes nothing here (a forward returns the padding row as stored), ``max_norm`` raises ValueError."""
 
     def __init__(self, num_embeddings: int, embedding_dim: int, dtype=torch.float8_e4m3fn, device="cuda", output_dtype=None,
-                 bounds_check_mode="none", weight: Optional[torch.Tensor] = None):
+                 bounds_check_mode="none", weight: Optional[torch.Tensor] = None, scale=None):
         dt = float8_dtype(dtype)
+        _scale_kind(scale)
         if weight is not None:
             weight = _weight_bytes(weight, dt, (int(num_embeddings), int(embedding_dim)), "weight")
         super().__init__([num_embeddings], [embedding_dim], dt, device=device, layout="bd", output_dtype=output_dtype,
-                         bounds_check_mode=bounds_check_mode)
+                         bounds_check_mode=bounds_check_mode, scale=scale)
         self.num_embeddings, self.embedding_dim = int(num_embeddings), int(embedding_dim)
         self._off0: dict = {}        # the request's offsets [0], one per (dtype, device)
         if weight is not None:
@@ -349,11 +489,13 @@ class Float8EmbeddingMI355(Float8BatchedEmbeddingBagMI355):
     _offsets0 = EmbeddingMI355._offsets0
 
     @classmethod
-    def from_float(cls, module, dtype=torch.float8_e4m3fn, **kw):
+    def from_float(cls, module, dtype=torch.float8_e4m3fn, scale=None, **kw):
         w = _torch_weight(module, (EmbeddingMI355, nn.Embedding), "an EmbeddingMI355 or a torch.nn.Embedding")
         dt = float8_dtype(dtype)
         kw.setdefault("device", w.device if w.is_cuda else "cuda")
-        return cls(int(w.shape[0]), int(w.shape[1]), dt, weight=w.to(dt), **kw)
+        if _scale_kind(scale) is None:
+            return cls(int(w.shape[0]), int(w.shape[1]), dt, weight=w.to(dt), **kw)
+        return _quantized(cls(int(w.shape[0]), int(w.shape[1]), dt, scale=scale, **kw), w)
 
     def _flat(self, input) -> torch.Tensor:
         if not isinstance(input, torch.Tensor) or input.dtype not in _IDTYPE:
