@@ -35,6 +35,8 @@ enum {
     PM_F16 = 2,
     PM_F8E4M3 = 3,           /* OCP FP8 e4m3fn: table element of pm_embbag_fwd_f8 / pm_embedding_gather_f8 only (FP8 TABLES) */
     PM_F8E5M2 = 4,           /* OCP FP8 e5m2: likewise */
+    PM_Q8 = 5,               /* 8-bit quantised rows: a table FORMAT code of pm_embbag_fwd_anyfmt / pm_embedding_gather_anyfmt only (MIXED-FORMAT TABLES) */
+    PM_Q4 = 6,               /* 4-bit quantised rows: likewise */
     PM_I32 = 10,
     PM_I64 = 11
 };
@@ -838,6 +840,46 @@ int pm_embbag_fwd_f8_scaled(const pm_embbag_batch* op, const int64_t* padding_id
 int pm_embbag_f8_scaled_plan(const pm_embbag_batch* op, int32_t out_dtype, int32_t mean, int32_t row_exponents, int32_t out[12]);
 int pm_embedding_gather_f8_scaled(const pm_embbag_batch* op, int32_t out_dtype, const int32_t* table_exp, const int8_t* const* row_exp, void* out,
                                   int64_t out_row_stride, pm_stream_t stream);
+
+/*
+ * MIXED-FORMAT TABLES -- every table of ONE launch in its own stored format: what a serving model holds (the huge tables at 4 bits or
+ * FP8, the mid-size ones at 8 bits, the small or sensitive ones at fp16 or fp32; fbgemm's IntNBitTableBatchedEmbeddingBagsCodegen takes one
+ * SparseType per table).  table_formats: a DEVICE array of num_tables format codes --
+ *   PM_F32, PM_BF16, PM_F16   [rows[t], dims[t]] elements of that type, rows back to back, tables[t] 16-byte aligned
+ *   PM_F8E4M3, PM_F8E5M2      uint8 [rows[t], dims[t]] codes (FP8 TABLES), tables[t] 8-byte aligned
+ *   PM_Q8, PM_Q4              uint8 [rows[t], row_bytes(dims[t], 8 | 4)] quantised rows (ROW-QUANTISED TABLES), tables[t] 4-byte aligned
+ * -- and op->tables[t] points at that format's bytes exactly as the format's own call takes them.  table_exp: a DEVICE int32 array of
+ * num_tables power-of-two table exponents E_t in [-64, 64] (SCALED FP8 TABLES), or NULL meaning all zero; read for FP8 tables only.
+ * op->weight_dtype is not read.  The kernels read the formats like dims; the host never does.
+ * THE RULE: NO NEW ARITHMETIC.  The columns of table t are bit for bit what that format's own call gives for the table alone:
+ *   pooled (pm_embbag_fwd_anyfmt), per column from +0.0 in index order: fp32 / bf16 / fp16 acc = acc + f, weighted fmaf(w_j, f, acc)
+ *     (pm_embbag_fwd_padded without padding, pm_embbag_fwd_out16); FP8 the same with f = dec(code) * 2^E_t (pm_embbag_fwd_f8 /
+ *     pm_embbag_fwd_f8_scaled); PM_Q8 / PM_Q4 acc = fmaf(scale_r * w_j, code, acc + bias_r * w_j) (pm_embbag_fwd_qrows).  Sum pooling only.
+ *   un-pooled (pm_embedding_gather_anyfmt), per position and column: conv(element) (pm_embedding_gather: same type in and out is a bit
+ *     copy), conv(dec(code) * 2^E_t) (pm_embedding_gather_f8_scaled), conv(fmaf(scale_r, code, +0.0 + bias_r)) (pm_embedding_gather_qrows).
+ *   out_dtype PM_F32, or PM_BF16 / PM_F16: the fp32 value rounded ONCE, in registers.  out is addressed in its own elements, like the
+ *   per-table-format calls' (out_offsets / out_stride; the un-pooled call: row j at out + j * out_row_stride).
+ *   A format code that is none of the seven is a defined result, not a fault: that table's output rows are +0.0 and none of its bytes is read.
+ * Kernels: csrc/embbag_fwd_anyfmt_kernel.inc (the per-table-format kernel's tiles; the workgroup branches once per tile into its table's
+ * format; a lane holds eight columns of a row whatever the format) and csrc/embedding_gather_anyfmt.hip (tiles of 256 positions; a lane
+ * group branches on its row's format).  No atomics, no workspace, stream-ordered, 64-bit row addressing.
+ * Refused on the host, before any HIP call: everything pm_embbag_fwd_qrows_mixed / pm_embedding_gather_qrows_mixed refuse (with a NULL
+ * table_formats in a NULL table_bits' place: PM_ERR_INVALID; max_dim or min_dim not a multiple of 8, blocked layouts: PM_ERR_UNSUPPORTED;
+ * an out_dtype other than the three: PM_ERR_INVALID); max_dim above 2048 (PM_ERR_UNSUPPORTED); a NULL or misaligned out (16 bytes fp32,
+ * 8 bytes 16-bit), an out_row_stride below max_dim or not a multiple of 4 (PM_ERR_INVALID).  An empty request returns PM_OK without a launch.
+ * pm_embbag_anyfmt_plan / pm_embedding_gather_anyfmt_plan: the geometry the two calls WOULD use (plan_anyfmt, plan_gather_anyfmt:
+ * csrc/launch_plan.h), in pm_embbag_qrows_plan's / pm_embedding_gather_plan's order.  They need no device and no formats: the geometry is
+ * a function of the request, out_dtype and the knobs.  The pooled kernel's rows in flight are a compile-time value per format (unroll is
+ * reported as 0); the un-pooled kernel's are 4.
+ * Left out: FP8 row exponents, pruning, mean and max pooling, padding rows, 2-bit rows, a lane-group width per format, any backward.
+ * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these four finds out at symbol resolution.
+ */
+int pm_embbag_fwd_anyfmt(const pm_embbag_batch* op, const int32_t* table_formats, const int32_t* table_exp, int32_t out_dtype, void* out,
+                         pm_stream_t stream);
+int pm_embbag_anyfmt_plan(const pm_embbag_batch* op, int32_t out_dtype, int32_t out[12]);
+int pm_embedding_gather_anyfmt(const pm_embbag_batch* op, const int32_t* table_formats, const int32_t* table_exp, int32_t out_dtype, void* out,
+                               int64_t out_row_stride, pm_stream_t stream);
+int pm_embedding_gather_anyfmt_plan(const pm_embbag_batch* op, int64_t out[8]);
 
 /*
  * SEQUENCE GRADIENTS -- the batched backward of the un-pooled lookup above: the gradient of pm_embedding_gather's rows applied to all

@@ -9,6 +9,8 @@ Layout (only what the hot path needs):
                      lookups over 8- / 4-bit row-quantised tables
   float8_bag.py      Float8BatchedEmbeddingBagMI355 / Float8EmbeddingBagMI355 / Float8EmbeddingMI355: pooled and un-pooled lookups
                      over OCP FP8 (e4m3fn / e5m2) tables
+  mixed_bag.py       MixedBatchedEmbeddingBagMI355: pooled and un-pooled lookups over tables that are EACH in their own format
+                     (fp32 / bf16 / fp16 / FP8 / 8- / 4-bit rows), one launch
   indices.py         uniform / Zipf index generation (reference init_indices + a scalable form)
   compute/pt/        mirror of the reference train/compute/pt emb driver CLI
   comms/pt/          mirror of the reference train/comms/pt backend plug-in, metrics and drivers
@@ -25,5 +27,6 @@ from .embedding_bag import (  # noqa: F401
 )
 from .quantized_bag import QuantizedBatchedEmbeddingBagMI355, QuantizedEmbeddingBagMI355, QuantizedEmbeddingMI355  # noqa: F401
 from .float8_bag import Float8BatchedEmbeddingBagMI355, Float8EmbeddingBagMI355, Float8EmbeddingMI355  # noqa: F401
+from .mixed_bag import MixedBatchedEmbeddingBagMI355  # noqa: F401
 
 __version__ = "0.1.0"

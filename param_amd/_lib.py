@@ -109,9 +109,15 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_fwd_f8_scaled",
     "pm_embbag_f8_scaled_plan",
     "pm_embedding_gather_f8_scaled",
+    "pm_embbag_fwd_anyfmt",
+    "pm_embbag_anyfmt_plan",
+    "pm_embedding_gather_anyfmt",
+    "pm_embedding_gather_anyfmt_plan",
 )
 # table element types of the FP8 lookups alone (include/param_amd.h, FP8 TABLES): every other entry point refuses them
 PM_F8E4M3, PM_F8E5M2 = 3, 4
+# table FORMAT codes of the mixed-format lookups alone (include/param_amd.h, MIXED-FORMAT TABLES): 8- and 4-bit quantised rows
+PM_Q8, PM_Q4 = 5, 6
 
 # pm_embbag_plan (include/param_amd.h): the kinds, and the members of the two plans in the order the queries fill them
 PM_PLAN_BASE, PM_PLAN_FORWARD, PM_PLAN_QUANTIZED, PM_PLAN_PADDED, PM_PLAN_PADDED16 = 0, 1, 2, 3, 4
@@ -350,6 +356,15 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embedding_gather_qrows_mixed.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, vp, i64, vp]
     L.pm_embedding_gather_qrows_mixed_plan.restype = ctypes.c_int
     L.pm_embedding_gather_qrows_mixed_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), ctypes.POINTER(i64)]
+    # mixed-format tables: table_formats and table_exp (device int32 [T]; table_exp may be NULL) behind the request
+    L.pm_embbag_fwd_anyfmt.restype = ctypes.c_int
+    L.pm_embbag_fwd_anyfmt.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, vp, vp]
+    L.pm_embbag_anyfmt_plan.restype = ctypes.c_int
+    L.pm_embbag_anyfmt_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, ctypes.POINTER(i32)]
+    L.pm_embedding_gather_anyfmt.restype = ctypes.c_int
+    L.pm_embedding_gather_anyfmt.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, vp, i64, vp]
+    L.pm_embedding_gather_anyfmt_plan.restype = ctypes.c_int
+    L.pm_embedding_gather_anyfmt_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), ctypes.POINTER(i64)]
     # ... whose rows may be pruned: remap (a device int32 array) and remap_offsets (a device int64 [T + 1]) behind table_bits
     L.pm_embbag_fwd_qrows_pruned.restype = ctypes.c_int
     L.pm_embbag_fwd_qrows_pruned.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp, i32, vp, vp]
@@ -555,4 +570,18 @@ def embedding_gather_qrows_mixed_plan(op: pm_embbag_batch) -> dict:
     """``pm_embedding_gather_qrows_mixed_plan``: the geometry ``pm_embedding_gather_qrows_mixed`` would use -- ``GATHER_PLAN_FIELDS`` by name"""
     out = (ctypes.c_int64 * len(GATHER_PLAN_FIELDS))()
     check(load().pm_embedding_gather_qrows_mixed_plan(ctypes.byref(op), out))
+    return dict(zip(GATHER_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def embbag_anyfmt_plan(op: pm_embbag_batch, out_dtype: int = PM_F32) -> dict:
+    """``pm_embbag_anyfmt_plan``: the geometry ``pm_embbag_fwd_anyfmt`` would use for ``op`` -- ``PLAN_FIELDS`` by name"""
+    out = (ctypes.c_int32 * len(PLAN_FIELDS))()
+    check(load().pm_embbag_anyfmt_plan(ctypes.byref(op), int(out_dtype), out))
+    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
+
+
+def embedding_gather_anyfmt_plan(op: pm_embbag_batch) -> dict:
+    """``pm_embedding_gather_anyfmt_plan``: the geometry ``pm_embedding_gather_anyfmt`` would use -- ``GATHER_PLAN_FIELDS`` by name"""
+    out = (ctypes.c_int64 * len(GATHER_PLAN_FIELDS))()
+    check(load().pm_embedding_gather_anyfmt_plan(ctypes.byref(op), out))
     return dict(zip(GATHER_PLAN_FIELDS, (int(v) for v in out)))

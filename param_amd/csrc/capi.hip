@@ -17,6 +17,13 @@ hipError_t launch_embbag_fwd_qpruned(const KParams& p, const int32_t* table_bits
                                      int max_dim, int unroll, hipStream_t stream);
 hipError_t launch_embedding_gather_qpruned(const KParams& p, const int32_t* table_bits, const int32_t* remap, const int64_t* remap_offsets, int out_dtype,
                                            const GatherPlan& g, hipStream_t stream);
+// mixed-format tables (embbag_fwd_anyfmt_{f32,bf16,f16}.hip: one translation unit per output type; embedding_gather_anyfmt.hip):
+// table_formats = device int32 [T] of format codes, table_exp = device int32 [T] or NULL; the geometry is plan_anyfmt's / plan_gather_anyfmt's
+hipError_t launch_embbag_fwd_anyfmt_f32(const KParams& p, const int32_t* table_formats, const int32_t* table_exp, int max_dim, hipStream_t stream);
+hipError_t launch_embbag_fwd_anyfmt_bf16(const KParams& p, const int32_t* table_formats, const int32_t* table_exp, int max_dim, hipStream_t stream);
+hipError_t launch_embbag_fwd_anyfmt_f16(const KParams& p, const int32_t* table_formats, const int32_t* table_exp, int max_dim, hipStream_t stream);
+hipError_t launch_embedding_gather_anyfmt(const KParams& p, const int32_t* table_formats, const int32_t* table_exp, int out_dtype, const GatherPlan& g,
+                                          hipStream_t stream);
 }  // namespace pm
 
 namespace {
@@ -1060,6 +1067,100 @@ int pm_embedding_gather_qrows_mixed_plan(const pm_embbag_batch* op, int64_t out[
     const int rc = qmixed_gather_request(op, &not_read, PM_F32, knobs);
     if (rc != PM_OK) return rc;
     const pm::GatherPlan g = pm::plan_gather_qmixed(*op, knobs);
+    const int64_t v[8] = {g.vec, g.group_lanes, g.tile, g.col_passes, g.unroll, g.lds_borders, g.xcd_contiguous, g.grid};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return PM_OK;
+}
+
+// ---- mixed-format tables (embbag_fwd_anyfmt_kernel.inc, embedding_gather_anyfmt.hip) ------------------------------------------------------
+// what the four calls refuse on the host, in one order: everything the per-table-format calls refuse (op, the eight-column rule, the
+// request, out_dtype, blocked layouts), with table_formats in table_bits' place, then this family's width limit.  The formats and
+// exponents are device data: not read here.
+static int anyfmt_request(const pm_embbag_batch* op, const int32_t* table_formats, int32_t out_dtype, const pm::PlanKnobs& knobs, pm::PlanShape& shape,
+                          int& out_bytes) {
+    if (!op) return fail(PM_ERR_INVALID, "op is NULL");
+    if (!table_formats)
+        return fail(PM_ERR_INVALID, "table_formats is NULL (a device array of num_tables format codes: PM_F32, PM_BF16, PM_F16, PM_F8E4M3, "
+                                    "PM_F8E5M2, PM_Q8 or PM_Q4)");
+    const int rc = qmixed_request(op, table_formats, out_dtype, knobs, shape, out_bytes);
+    if (rc != PM_OK) return rc;
+    if (op->max_dim > pm::kAnyfmtMaxDim)
+        return fail(PM_ERR_UNSUPPORTED, "mixed-format tables: dims[t] (and max_dim) must be at most " + std::to_string(pm::kAnyfmtMaxDim));
+    shape = pm::anyfmt_shape(*op, knobs);
+    return PM_OK;
+}
+
+int pm_embbag_fwd_anyfmt(const pm_embbag_batch* op, const int32_t* table_formats, const int32_t* table_exp, int32_t out_dtype, void* out,
+                         pm_stream_t stream) {
+    const pm::PlanKnobs knobs = current_knobs();
+    pm::PlanShape shape;
+    int out_bytes = 0;
+    const int rc = anyfmt_request(op, table_formats, out_dtype, knobs, shape, out_bytes);
+    if (rc != PM_OK) return rc;
+    const pm::LaunchPlan plan = pm::plan_anyfmt(*op, shape, knobs, out_bytes);
+    pm::KParams p;
+    fill_params(op, plan, p);
+    const auto launch = out_dtype == PM_BF16 ? pm::launch_embbag_fwd_anyfmt_bf16
+                                             : (out_dtype == PM_F16 ? pm::launch_embbag_fwd_anyfmt_f16 : pm::launch_embbag_fwd_anyfmt_f32);
+    return padded_forward(p, out, out_dtype == PM_F32 ? 16 : 8, stream, [&](const pm::KParams& q, hipStream_t s) {
+        return launch(q, table_formats, table_exp, op->max_dim, s);
+    }, "pm_embbag_fwd_anyfmt launch");
+}
+
+int pm_embbag_anyfmt_plan(const pm_embbag_batch* op, int32_t out_dtype, int32_t out[12]) {
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const pm::PlanKnobs knobs = current_knobs();
+    pm::PlanShape shape;
+    int out_bytes = 0;
+    static const int32_t not_read = 0;             // (the plan is a function of the request, out_dtype and the knobs: no formats)
+    const int rc = anyfmt_request(op, &not_read, out_dtype, knobs, shape, out_bytes);
+    if (rc != PM_OK) return rc;
+    const pm::LaunchPlan p = pm::plan_anyfmt(*op, shape, knobs, out_bytes);
+    const int32_t v[12] = {p.tiles_per_table, p.bags_per_block, p.idx_cap, p.xcd_affine, p.nt_loads, p.ordered,
+                           p.stage_out, p.stage_bags, p.flat_bags, p.flat_target, p.flat_compact, p.unroll};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return PM_OK;
+}
+
+// ... un-pooled: anyfmt_request, then what pm_embedding_gather refuses about a request
+static int anyfmt_gather_request(const pm_embbag_batch* op, const int32_t* table_formats, int32_t out_dtype, const pm::PlanKnobs& knobs) {
+    pm::PlanShape shape;
+    int out_bytes = 0;
+    const int rc = anyfmt_request(op, table_formats, out_dtype, knobs, shape, out_bytes);
+    if (rc != PM_OK) return rc;
+    if (op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "un-pooled rows are unweighted: per_sample_weights must be NULL");
+    return PM_OK;
+}
+
+int pm_embedding_gather_anyfmt(const pm_embbag_batch* op, const int32_t* table_formats, const int32_t* table_exp, int32_t out_dtype, void* out,
+                               int64_t out_row_stride, pm_stream_t stream) {
+    const pm::PlanKnobs knobs = current_knobs();
+    const int rc = anyfmt_gather_request(op, table_formats, out_dtype, knobs);
+    if (rc != PM_OK) return rc;
+    if (out_row_stride < op->max_dim || out_row_stride % 4 != 0)
+        return fail(PM_ERR_INVALID, "out_row_stride must be a multiple of 4 elements and at least max_dim");
+    if (op->num_indices == 0 || op->bag_count == 0) return PM_OK;      // nothing to write, whatever `out` is
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const uintptr_t align = out_dtype == PM_F32 ? 16 : 8;
+    if (reinterpret_cast<uintptr_t>(out) % align != 0) return fail(PM_ERR_INVALID, "out must be " + std::to_string(align) + "-byte aligned");
+    const pm::GatherPlan g = pm::plan_gather_anyfmt(*op, knobs);
+    if (g.grid > pm::kMaxGrid) return fail(PM_ERR_UNSUPPORTED, "grid too large");
+    pm::KParams p;
+    fill_params(op, pm::LaunchPlan{}, p);      // (the request; a gather has no bag tiling)
+    p.io = static_cast<float*>(out);           // (addressed in out_dtype's elements)
+    p.out_stride = out_row_stride;
+    const hipError_t h = pm::launch_embedding_gather_anyfmt(p, table_formats, table_exp, out_dtype, g, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embedding_gather_anyfmt launch");
+    return PM_OK;
+}
+
+int pm_embedding_gather_anyfmt_plan(const pm_embbag_batch* op, int64_t out[8]) {
+    if (!out) return fail(PM_ERR_INVALID, "out is NULL");
+    const pm::PlanKnobs knobs = current_knobs();
+    static const int32_t not_read = 0;
+    const int rc = anyfmt_gather_request(op, &not_read, PM_F32, knobs);
+    if (rc != PM_OK) return rc;
+    const pm::GatherPlan g = pm::plan_gather_anyfmt(*op, knobs);
     const int64_t v[8] = {g.vec, g.group_lanes, g.tile, g.col_passes, g.unroll, g.lds_borders, g.xcd_contiguous, g.grid};
     for (int i = 0; i < 8; ++i) out[i] = v[i];
     return PM_OK;

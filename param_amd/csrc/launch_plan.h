@@ -613,6 +613,36 @@ static inline GatherPlan plan_gather_qmixed(const pm_embbag_batch& op, const Pla
     return g;
 }
 
+// ---- MIXED-FORMAT tables: pm_embbag_fwd_anyfmt (embbag_fwd_anyfmt_kernel.inc) and pm_embedding_gather_anyfmt (embedding_gather_anyfmt.hip) --
+// Every table of a launch in its own format (fp32, bf16, fp16, FP8 e4m3fn / e5m2, 8- / 4-bit rows).  plan_qmixed's argument, extended: a
+// lane holds kAnyfmtLaneColumns = EIGHT COLUMNS of a row whatever its format, so the lane group G = group_lanes(max_dim, 8), the column
+// passes (more than one above 512 columns; kAnyfmtMaxDim = 2048: four) and the output pieces are one for every table, and the plan is
+// a function of the request struct, out_dtype and the knobs alone -- the host never learns which formats are present.  The pooled plan
+// is plan_qmixed's but for the rows in flight: those are a compile-time value per format in the kernel (the format's own product
+// default), so `unroll` is reported as 0 and pm_set_tuning's unroll is not read.  The un-pooled kernel branches per lane group and keeps
+// kAnyfmtGatherUnroll rows in flight (a compile-time value as well; it divides every group width).
+constexpr int kAnyfmtLaneColumns = 8;
+constexpr int kAnyfmtMaxDim = 2048;
+constexpr int kAnyfmtGatherUnroll = 4;
+static inline PlanShape anyfmt_shape(const pm_embbag_batch& op, const PlanKnobs& k) { return lane_columns_shape(op, kAnyfmtLaneColumns, k); }
+static inline LaunchPlan plan_anyfmt(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k, int out_bytes) {
+    LaunchPlan p = plan_qrows(op, s, k, out_bytes);
+    p.unroll = 0;
+    return p;
+}
+static inline GatherPlan plan_gather_anyfmt(const pm_embbag_batch& op, const PlanKnobs& k) {
+    GatherPlan g = {};
+    g.vec = kAnyfmtLaneColumns;
+    g.group_lanes = group_lanes(op.max_dim, g.vec);
+    g.tile = kBlock;
+    g.col_passes = static_cast<int32_t>(ceil_div(op.max_dim, static_cast<int64_t>(g.group_lanes) * g.vec));
+    g.unroll = kAnyfmtGatherUnroll;
+    g.lds_borders = op.num_tables + 1 <= kGatherLdsBorders ? 1 : 0;
+    g.xcd_contiguous = (op.num_tables > 1 && k.xcd_affine != 0) ? 1 : 0;
+    g.grid = ceil_div(op.num_indices, g.tile);
+    return g;
+}
+
 // ---- FP8 tables: pm_embbag_fwd_f8 (embbag_fwd_f8.hip) and pm_embedding_gather_f8 (embedding_gather_f8.hip) ------------------------------
 // The 1-byte element: a 16-byte load holds 16 columns (vec = 16, elem_bytes = 1), so the pooled lane group is group_lanes(max_dim, 16) --
 // 8 lanes up to D = 128 (one aligned 128-byte line per row), 64 lanes at D = 1024, column passes above (kF8MaxDim = 2048: two).
