@@ -2,7 +2,9 @@
 // stdin: one case per line, 27 integers --
 //   kind (0 base, 1 forward, 2 quantized, 3 padded with 4-byte output elements, 4 padded with 2-byte ones; 5 the row gather,
 //         which prints the eight members of pm::GatherPlan instead; 6 / 7 the FP8 pooled lookup with 4- / 2-byte output elements;
-//         8 the FP8 row gather, eight members as 5 -- for 6 .. 8 dtype is PM_F8E4M3 / PM_F8E5M2)
+//         8 the FP8 row gather, eight members as 5 -- for 6 .. 8 dtype is PM_F8E4M3 / PM_F8E5M2; the scaled FP8 lookups plan on 6 .. 8
+//         too, their pooled plan being plan_f8 followed by f8s_stage_out, which tests/plan_sweep.py restates;
+//         9 / 10 the mixed-format pooled lookup with 4- / 2-byte output elements; 11 the mixed-format row gather, eight members as 5)
 //   the request: num_tables batch num_indices bag_begin bag_count max_dim min_dim dtype weighted table_group grad_block_shift grad_block_extra
 //   what the setters were given: unroll bags_per_block xcd_affine nt_loads | stage_out flat_grid flat_target
 //   the environment's values: stage flat flat_maxl flat_target flat_bags tile_major flat_compact
@@ -66,6 +68,14 @@ int main() {
             case 7: p = pm::plan_f8(op, k, 2); break;
             case 8: {
                 const pm::GatherPlan g = pm::plan_gather_f8(op, k);
+                printf("%d %d %d %d %d %d %d %lld\n", g.vec, g.group_lanes, g.tile, g.col_passes, g.unroll, g.lds_borders, g.xcd_contiguous,
+                       static_cast<long long>(g.grid));
+                continue;
+            }
+            case 9: p = pm::plan_anyfmt(op, pm::anyfmt_shape(op, k), k, 4); break;
+            case 10: p = pm::plan_anyfmt(op, pm::anyfmt_shape(op, k), k, 2); break;
+            case 11: {
+                const pm::GatherPlan g = pm::plan_gather_anyfmt(op, k);
                 printf("%d %d %d %d %d %d %d %lld\n", g.vec, g.group_lanes, g.tile, g.col_passes, g.unroll, g.lds_borders, g.xcd_contiguous,
                        static_cast<long long>(g.grid));
                 continue;

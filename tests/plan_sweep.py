@@ -10,7 +10,14 @@ what 8192 bags over 10 M-row tables reach.
 A case names its entry point, table dtype / dims / rows, request, the arguments of ``set_tuning`` and ``set_forward_tuning``, at most
 one environment setting (its group then runs in a child process: the switches are read once per process) and, optionally, a batch
 slice.  ``label()`` derives the variant from the PLAN, never from the case's intent; ``test_the_sweep_reaches_every_variant`` holds the
-list to conditions on those labels."""
+list to conditions on those labels.
+
+The scaled FP8 entries (``f8s``, ``f8s_gather``) add ``scale`` (``"table"`` / ``"row"``) to a case and plan on the FP8 plans; the pooled
+one's plan is ``plan_f8`` followed by the launcher's LDS rule, which ``f8s_out_offset`` / ``f8s_lds_bytes`` / ``f8s_stage_out`` restate
+here and ``pinned_plan`` applies to the dumped row -- group ``f8s_edge`` sits on both sides of the one corner where the row exponents'
+bytes cost a tile its burst.  The mixed-format entries (``anyfmt``, ``anyfmt_gather``) add ``formats``, one stored format per table; they
+take no padding row and read the padded requests' indices as plain indices, and ``anyfmt_label`` derives, per format, which tiles it
+owns, which of them read their indices from the request and which reach the tail loop behind that format's rows in flight."""
 import functools
 
 import numpy as np
@@ -22,7 +29,9 @@ PLAN_FIELDS = ("tiles_per_table", "bags_per_block", "idx_cap", "xcd_affine", "nt
 GATHER_FIELDS = ("vec", "group_lanes", "tile", "col_passes", "unroll", "lds_borders", "xcd_contiguous", "grid")
 # the `kind` codes of tests/launch_plan_dump.cpp (0 .. 4: pm_embbag_plan's PM_PLAN_*; 5: the gather plan)
 # (6 .. 8: plan_f8 for 4- / 2-byte output elements and plan_gather_f8, the plans of pm_embbag_f8_plan / pm_embedding_gather_f8_plan)
-KIND = {"base": 0, "forward": 1, "quantized": 2, "padded4": 3, "padded2": 4, "gather": 5, "f8_4": 6, "f8_2": 7, "f8_gather": 8}
+# (9 .. 11: plan_anyfmt for 4- / 2-byte output elements and plan_gather_anyfmt, the plans of pm_embbag_anyfmt_plan / pm_embedding_gather_anyfmt_plan)
+KIND = {"base": 0, "forward": 1, "quantized": 2, "padded4": 3, "padded2": 4, "gather": 5, "f8_4": 6, "f8_2": 7, "f8_gather": 8,
+        "anyfmt_4": 9, "anyfmt_2": 10, "anyfmt_gather": 11}
 DTYPE = {"f32": 0, "bf16": 1, "f16": 2}
 F8_DTYPE = {"e4m3": 3, "e5m2": 4}                                             # PM_F8E4M3 / PM_F8E5M2: the table kinds of the FP8 entries
 VEC = {"f32": 4, "bf16": 8, "f16": 8, "e4m3": 16, "e5m2": 16}                 # columns per lane of the pooled kernels
@@ -40,11 +49,18 @@ ENV_DEFAULT = (1, 1, 0, 256, 256, -1, 1)
 # family's plan for its output element, so the case decides
 ENTRY_KIND = {"fwd": "forward", "quantized": "quantized", "padded": "padded4", "mean": "padded4", "out16": "padded2", "gather": "gather",
               "psw_grad": "base", "mean_grad": "base", "widen": "base", "atomic": "base", "max": ("padded4", "padded2"),
-              "f8": ("f8_4", "f8_2"), "f8_gather": "f8_gather"}
+              "f8": ("f8_4", "f8_2"), "f8_gather": "f8_gather",
+              # the scaled FP8 lookups plan on the FP8 plans: the pooled one on plan_f8 followed by f8s_stage_out (``pinned_plan`` below)
+              "f8s": ("f8_4", "f8_2"), "f8s_gather": "f8_gather", "anyfmt": ("anyfmt_4", "anyfmt_2"), "anyfmt_gather": "anyfmt_gather"}
+GATHER_ENTRIES = ("gather", "f8_gather", "f8s_gather", "anyfmt_gather")
 UNROLLS = (1, 2, 3, 4, 6, 8)
 # FP8 pooled: (lane-group width, the D its unroll cases run at, the unroll its mean case runs at)
 F8_GROUP_DIMS = ((8, 64, 4), (16, 192, 8), (32, 400, 2), (64, 1024, 4))
 K_BLOCK = 256
+ANY_VEC = 8                                                                   # columns per lane of both mixed-format kernels
+# the mixed-format pooled kernel's compile-time rows in flight per format (embbag_fwd_anyfmt_kernel.inc: kUnroll -- the float formats'
+# 2, kF8Unroll, kQrowsUnroll)
+ANY_UNROLL = {"fp32": 2, "bf16": 2, "fp16": 2, "fp8_e4m3": 2, "fp8_e5m2": 2, "int8": 4, "int4": 4}
 
 
 def group_lanes(max_dim, vec):
@@ -156,12 +172,31 @@ def request(name):
         # about 40 % of the lookups of a table with a padding row are that row (padding_rules.padded_request)
         T, B, rows, kw = {"pad100": (3, 100, [1000, 500, 250], dict(max_len=9)), "pad1100": (2, 1100, [1000, 300], dict(max_len=5)),
                           "pad8": (8, 40, [1000, 500, 250, 125, 1000, 500, 250, 125], dict(max_len=9)),
-                          "padfix": (3, 100, [1000, 500, 250], dict(fixed=4))}[name]
+                          "padfix": (3, 100, [1000, 500, 250], dict(fixed=4)),
+                          # 600 bags of 4.5 lookups on average: an explicit 512-bag tile gets the whole index tile (4096 entries)
+                          "pad600": (2, 600, [1000, 300], dict(max_len=9))}[name]
         pads = [5, rows[1] - 1] + [None if t % 2 == 0 else 0 for t in range(2, T)]
         idx, off = P.padded_request(np.random.default_rng(500 + B + T), rows, B, pads, **kw)
         r = Request(name, T, B, rows, np.diff(off), 500 + B + T, pads=pads, idx=idx)
         share = P.padded_mask(idx, off, T, B, pads).mean()
         assert 0.2 < share < 0.45, share
+        return r
+    if name == "ragged8":
+        # the gathers' eight tables: seven of them end inside the first 256-position tile (one tile holds seven formats, a wave several),
+        # the eighth reaches into a second tile that is not full; empty bags, an empty first bag of table 3
+        T, B = 8, 14
+        lens = np.random.default_rng(802).integers(0, 6, T * B)
+        lens[3 * B] = 0
+        r = Request(name, T, B, [1000, 500, 250, 125, 1000, 500, 250, 125], lens, 810)
+        assert r.off[7 * B] <= K_BLOCK < r.N < 2 * K_BLOCK and all(r.off[(t + 1) * B] > r.off[t * B] for t in range(T))
+        return r
+    if name == "many260":
+        # more tables than the gathers stage borders for in LDS (T + 1 > 256): a few rows and two bags each
+        T, B = 260, 2
+        lens = np.random.default_rng(803).integers(0, 4, T * B)
+        lens[0] = lens[7] = 0
+        r = Request(name, T, B, [3 + t % 5 for t in range(T)], lens, 803)
+        assert r.N > 2 * K_BLOCK and r.N % K_BLOCK
         return r
     if name.startswith("auto"):
         # product scale, no knob set: about 1.3 M lookups over 1000-row tables
@@ -200,15 +235,25 @@ def max_conditions(r, vals, args):
 # ---- cases ----------------------------------------------------------------------------------------------------------------------
 class Case:
     def __init__(self, name, group, entry, request, kind="f32", dims=128, tuning=None, forward=None, env=None, weighted=False,
-                 bag_slice=None, out16=None, mean=False, bits=None):
+                 bag_slice=None, out16=None, mean=False, bits=None, scale=None, formats=None):
         self.name, self.group, self.entry, self.request, self.kind = name, group, entry, request, kind
         self.tuning, self.forward, self.env = dict(tuning or {}), dict(forward or {}), dict(env or {})
         self.weighted, self.bag_slice, self.out16, self.mean, self.bits = weighted, bag_slice, out16, mean, bits
+        self.scale, self.formats = scale, None if formats is None else list(formats)
         self._dims = dims
         assert not set(self.tuning) - set(TUNING) and not set(self.forward) - set(FORWARD_TUNING) and not set(self.env) - set(ENV)
         assert entry in ENTRY_KIND and not (mean and weighted) and not (entry == "max" and (weighted or mean))
         # an FP8 entry has FP8 tables (dims: multiples of 16 in [16, 2048]) and nothing else has
         assert (kind in F8_DTYPE and all(d % 16 == 0 and 16 <= d <= 2048 for d in self.dims)) if entry.startswith("f8") else kind in DTYPE
+        # a scaled FP8 entry says which exponents its tables carry, and nothing else does
+        assert (scale in ("table", "row")) if entry.startswith("f8s") else scale is None
+        # a mixed-format entry names one stored format per table (the request struct says fp32, which no kernel reads), dims in
+        # multiples of 8 -- of 16 for an FP8 table -- up to 2048, no mean pooling; nothing else names formats
+        if entry.startswith("anyfmt"):
+            assert kind == "f32" and not mean and len(self.formats) == self.req.T and set(self.formats) <= set(ANY_UNROLL)
+            assert all(d % (16 if f.startswith("fp8") else 8) == 0 and 8 <= d <= 2048 for f, d in zip(self.formats, self.dims))
+        else:
+            assert formats is None
 
     @property
     def req(self):
@@ -232,7 +277,7 @@ class Case:
     def plan_weighted(self):
         """whether the request the entry point plans for carries weights (the gather, the weights' gradient and the mean scaling
         build theirs without)"""
-        return bool(self.weighted and self.entry not in ("gather", "f8_gather", "psw_grad", "mean_grad"))
+        return bool(self.weighted and self.entry not in GATHER_ENTRIES + ("psw_grad", "mean_grad"))
 
     @property
     def dtype_code(self):
@@ -255,11 +300,22 @@ class Case:
         return " ".join(map(str, v + self.tuning_args() + self.forward_args() + env))
 
 
-def label(case, plan):
+def label(case, plan, dumped=None):
     """the variant a plan selects, as a set of words; what depends on the request's own offsets (``direct``: some tile's lookups
-    exceed the index tile and are read from the request; ``partial``: the last tile of a table is not full) is derived from them"""
+    exceed the index tile and are read from the request; ``partial``: the last tile of a table is not full) is derived from them.
+    ``plan`` is the pinned row (``pinned_plan``), ``dumped`` what launch_plan_dump printed for the case where the two can differ"""
     r, (b0, n) = case.req, case.bags
+    if case.entry.startswith("anyfmt"):
+        return anyfmt_label(case, plan)
     G = group_lanes(max(case.dims), VEC[case.kind])
+    if case.entry.startswith("f8s"):
+        # f8_label's words, the kind of exponent, and whether the restated LDS rule took a burst that plan_f8 had granted
+        words = f8_label(case, plan) | {case.scale}
+        if case.entry == "f8s":
+            assert dumped is not None and pinned_plan(case, dumped) == list(plan), "a scaled pooled case is labelled next to its dumped plan_f8 row"
+            if dict(zip(PLAN_FIELDS, dumped))["stage_out"] > 0 and not dict(zip(PLAN_FIELDS, plan))["stage_out"]:
+                words.add("burst-dropped")
+        return words
     if case.entry.startswith("f8"):
         return f8_label(case, plan)
     if case.plan_kind == "gather":
@@ -317,7 +373,7 @@ def f8_label(case, plan):
     The gather: ``partial`` is a last tile of positions that is not full."""
     r, (b0, n) = case.req, case.bags
     words = {"f8", case.kind, "out-" + (case.out16 or "fp32")} | ({"slice"} if case.bag_slice else set())
-    if case.entry == "f8_gather":
+    if case.entry in ("f8_gather", "f8s_gather"):
         p = dict(zip(GATHER_FIELDS, plan))
         assert p["vec"] == F8_GATHER_VEC
         return words | {"unpooled", f"G{p['group_lanes']}", f"u{p['unroll']}", f"passes{p['col_passes']}", f"xcd{p['xcd_contiguous']}",
@@ -354,6 +410,89 @@ def f8_label(case, plan):
             if (padded_before[later // K_BLOCK * K_BLOCK] > 0).any():
                 words.add("carry")
     return words
+
+
+def anyfmt_label(case, plan):
+    """the variant of a mixed-format case.  Family words ``any`` and ``pooled`` / ``unpooled``; the output type; per format and tile, from
+    the request's offsets next to the plan (a tile's bags belong to one table, so to one format):
+      ``fmt:<name>``     the format owns at least one tile (the gather: at least one written position);
+      ``direct:<name>``  ... a tile whose lookups exceed the index tile: its indices are read from the request;
+      ``tail:<name>``    ... a tile with a bag whose length is no multiple of that format's rows in flight (``ANY_UNROLL``): its tail loop runs.
+    The gather: ``partial`` is a last tile of positions that is not full, ``tile-formats<k>`` the most formats one 256-position tile
+    holds, ``wave-formats<k>`` the most formats the 64 positions of one wave hold."""
+    r, (b0, n) = case.req, case.bags
+    words = {"any", "out-" + (case.out16 or "fp32")} | ({"slice"} if case.bag_slice else set())
+    if case.entry == "anyfmt_gather":
+        p = dict(zip(GATHER_FIELDS, plan))
+        assert p["vec"] == ANY_VEC
+        words |= {"unpooled", f"G{p['group_lanes']}", f"u{p['unroll']}", f"passes{p['col_passes']}", f"xcd{p['xcd_contiguous']}",
+                  "lds_borders" if p["lds_borders"] else "global_borders"} | ({"partial"} if r.N % p["tile"] else set())
+        if max(case.dims) % (p["group_lanes"] * ANY_VEC):
+            words.add("row-ends-in-pass")                          # the last pass has pieces at or behind the row's width
+        owner = np.full(r.N, -1)
+        for t in range(r.T):
+            owner[r.off[t * r.B + b0]:r.off[t * r.B + b0 + n]] = t
+        fmt_of = np.array([list(ANY_UNROLL).index(f) for f in case.formats] + [-1])[owner]          # -1: the position is not written
+        words |= {f"fmt:{list(ANY_UNROLL)[k]}" for k in set(fmt_of.tolist()) - {-1}}
+        per = lambda width: max(len(set(fmt_of[i:i + width].tolist()) - {-1}) for i in range(0, r.N, width))  # noqa: E731
+        return words | {f"tile-formats{per(p['tile'])}", f"wave-formats{per(64)}"}
+    p = dict(zip(PLAN_FIELDS, plan))
+    G = group_lanes(max(case.dims), ANY_VEC)
+    bpb, cap = p["bags_per_block"], p["idx_cap"]
+    assert p["unroll"] == 0                                        # (the rows in flight are the formats' own)
+    words |= {"pooled", f"G{G}", "weighted" if case.weighted else "unweighted", f"xcd{p['xcd_affine']}", f"bpb{bpb}",
+              "staged" if p["stage_out"] else "plain", f"passes{-(-max(case.dims) // (G * ANY_VEC))}"}
+    if max(case.dims) % (G * ANY_VEC):
+        words.add("row-ends-in-pass")
+    if bpb > K_BLOCK // G:
+        words.add("tile>NG")
+    for t, fmt in enumerate(case.formats):
+        for k in range(-(-n // bpb)):
+            g0, nb = t * r.B + b0 + k * bpb, min(bpb, n - k * bpb)
+            words.add(f"fmt:{fmt}")
+            if nb < bpb:
+                words.add("partial")
+            if r.off[g0 + nb] - r.off[g0] > cap:
+                words.add(f"direct:{fmt}")
+            if (r.lens[g0:g0 + nb] % ANY_UNROLL[fmt]).any():
+                words.add(f"tail:{fmt}")
+    return words
+
+
+# ---- the scaled FP8 pooled launcher's LDS rule, restated (param_amd/csrc/common.h: f8s_out_offset / f8s_lds_bytes / f8s_stage_out) -----
+def f8s_out_offset(bpb, idx_cap, weighted, row):
+    """where the burst begins: int64 offsets[bpb + 1, rounded up to even] | int32 indices[idx_cap] | fp32 weights[idx_cap] (weighted) |
+    uint16 compacted positions[idx_cap] | int8 row exponents[idx_cap] (``row``), rounded up to 16 bytes"""
+    tile = (bpb + 2) // 2 * 2 * 8 + idx_cap * 4 * (2 if weighted else 1)
+    return (tile + idx_cap * (3 if row else 2) + 15) // 16 * 16
+
+
+def f8s_lds_bytes(bpb, idx_cap, weighted, row, stage_out, out_bytes):
+    return f8s_out_offset(bpb, idx_cap, weighted, row) + (bpb * stage_out * out_bytes if stage_out > 0 else 0)
+
+
+def f8s_stage_out(bpb, idx_cap, weighted, row, stage_out, out_bytes):
+    """the burst leaves where it pushes the tile's LDS past 64 KiB"""
+    return 0 if f8s_lds_bytes(bpb, idx_cap, weighted, row, stage_out, out_bytes) > 65536 else stage_out
+
+
+def f8s_case_lds(case, dumped):
+    """(bytes with the burst plan_f8 granted, bytes the launcher asks for) of a scaled pooled case"""
+    p = dict(zip(PLAN_FIELDS, dumped))
+    a = (p["bags_per_block"], p["idx_cap"], case.plan_weighted and not case.mean, case.scale == "row")
+    ob = 2 if case.out16 else 4
+    return f8s_lds_bytes(*a, p["stage_out"], ob), f8s_lds_bytes(*a, f8s_stage_out(*a, p["stage_out"], ob), ob)
+
+
+def pinned_plan(case, dumped):
+    """the row tests/plan_sweep_host.json pins for a case: what launch_plan_dump printed, but for the scaled FP8 pooled lookup, whose
+    plan is plan_f8's with ``stage_out`` as f8s_stage_out leaves it -- what ``pm_embbag_f8_scaled_plan`` must report"""
+    if case.entry != "f8s":
+        return list(dumped)
+    p = dict(zip(PLAN_FIELDS, dumped))
+    p["stage_out"] = f8s_stage_out(p["bags_per_block"], p["idx_cap"], case.plan_weighted and not case.mean, case.scale == "row", p["stage_out"],
+                                   2 if case.out16 else 4)
+    return [p[f] for f in PLAN_FIELDS]
 
 
 def pad_lds_bytes(case, plan):
@@ -544,6 +683,124 @@ def _cases():
     f8g("f8_gather_D512_two_passes", "f8_gather_knobs", "mixed_ragged", 512, tuning=dict(unroll=4))
     f8g("f8_gather_slice", "f8_gather_knobs", tuning=dict(unroll=4), bag_slice=(3, 90))
     f8g("f8_gather_e5m2", "f8_gather_knobs", fmt="e5m2", tuning=dict(unroll=8))
+    # -- scaled FP8 tables, pooled: pm_embbag_fwd_f8_scaled on plan_f8 followed by f8s_stage_out; the FP8 cases' shapes with row exponents
+    #    (one byte per index-tile entry in LDS, behind the compacted positions and in front of the burst) or a table exponent
+    def f8s(name, group, rq, dims, scale, mode="plain", fmt="e4m3", **kw):
+        add(name, group, "f8s", rq, fmt, dims, weighted=mode == "weighted", mean=mode == "mean", scale=scale, **kw)
+
+    scales = ("row", "table")
+    # the multi-tile baseline (see f8_base_*): both formats x both kinds of exponent x the three modes, fp32 rows one by one and bf16 burst
+    for fmt in F8_DTYPE:
+        for sc in scales:
+            for mode in modes:
+                f8s(f"f8s_base_{fmt}_{sc}_{mode}", f"f8s_base_{fmt}_{sc}", "pad100", 256, sc, mode, fmt, tuning=dict(bags_per_block=32))
+                f8s(f"f8s_base_{fmt}_{sc}_{mode}_bf16", f"f8s_base_{fmt}_{sc}", "pad100", 256, sc, mode, fmt, tuning=dict(bags_per_block=32), out16="bf16")
+    f8s("f8s_base_e4m3_row_weighted_bf16_unstaged", "f8s_base_e4m3_row", "pad100", 256, "row", "weighted", tuning=dict(bags_per_block=32),
+        forward=dict(stage_out=0), out16="bf16")
+    # fp32 rows through the burst, which lies behind the exponent bytes: 64-bag tiles of D = 64 rows, 18 tiles a table
+    for sc, ms in (("row", modes), ("table", modes[:1])):
+        for mode in ms:
+            f8s(f"f8s_burst_{sc}_{mode}", "f8s_burst", "pad1100", 64, sc, mode, tuning=dict(bags_per_block=64))
+            f8s(f"f8s_burst_{sc}_{mode}_unstaged", "f8s_burst", "pad1100", 64, sc, mode, tuning=dict(bags_per_block=64), forward=dict(stage_out=0))
+    # every lane-group width x every depth with row exponents, two bags per lane group; mean and a table exponent at one depth per width
+    for G, D, mean_u in F8_GROUP_DIMS:
+        for u in (2, 4, 8):
+            for mode in modes[:2] + (("mean",) if u == mean_u else ()):
+                f8s(f"f8s_G{G}_u{u}_{mode}", f"f8s_G{G}", "pad100", D, "row", mode, tuning=dict(unroll=u, bags_per_block=2 * K_BLOCK // G))
+        f8s(f"f8s_G{G}_u{mean_u}_table", f"f8s_G{G}", "pad100", D, "table", "weighted", tuning=dict(unroll=mean_u, bags_per_block=2 * K_BLOCK // G))
+    # block orders (block_to_tile picks the table's exponent pointer) and a slice that begins and ends inside tiles
+    f8s("f8s_xcd0", "f8s_orders", "pad100", 128, "row", tuning=dict(bags_per_block=32, xcd_affine=0))
+    f8s("f8s_xcd1", "f8s_orders", "pad8", 128, "row", tuning=dict(bags_per_block=32))
+    f8s("f8s_xcd3", "f8s_orders", "padfix", 128, "row", tuning=dict(bags_per_block=32))
+    f8s("f8s_slice", "f8s_orders", "pad100", 128, "row", tuning=dict(bags_per_block=32), bag_slice=(5, 70))
+    f8s("f8s_slice_mean", "f8s_orders", "pad100", 128, "row", "mean", tuning=dict(bags_per_block=32), bag_slice=(5, 70))
+    # 1024-bag tiles: ten rounds of compaction with the exponent bytes travelling next to the indices, a thread's fifth bound
+    for mode in modes:
+        f8s(f"f8s_bpb1024_{mode}", "f8s_1024", "pad1100", 16, "row", mode, tuning=dict(bags_per_block=1024))
+        f8s(f"f8s_bpb1024_{mode}_bf16", "f8s_1024", "pad1100", 16, "row", mode, tuning=dict(bags_per_block=1024), out16="bf16")
+    # the direct tile loads a row's exponent next to the index it reads from the request
+    for mode in modes:
+        for u in (2, 8):
+            f8s(f"f8s_direct_u{u}_{mode}", "f8s_direct", "pad_lumpy", 128, "row", mode, tuning=dict(unroll=u, bags_per_block=32))
+    # the LDS edge: 512-bag tiles of D = 16 bf16 rows fill the 16 KiB burst; with 4096 index-tile entries, weights and row exponents the
+    # tile is 49168 + 16384 = 65552 bytes, sixteen over, and the burst leaves; with a table exponent (61456) or without weights it stays
+    f8s("f8s_edge_row_weighted", "f8s_edge", "pad600", 16, "row", "weighted", tuning=dict(bags_per_block=512), out16="bf16")
+    f8s("f8s_edge_table_weighted", "f8s_edge", "pad600", 16, "table", "weighted", tuning=dict(bags_per_block=512), out16="bf16")
+    f8s("f8s_edge_row_plain", "f8s_edge", "pad600", 16, "row", tuning=dict(bags_per_block=512), out16="bf16")
+    f8s("f8s_mixed_dims", "f8s_wide", "pad100", [16, 64, 128], "row", "weighted", tuning=dict(bags_per_block=32))
+    f8s("f8s_D512_bf16", "f8s_wide", "pad100", 512, "row", tuning=dict(bags_per_block=16), out16="bf16")
+    f8s("f8s_D512_fp32", "f8s_wide", "pad100", 512, "row", tuning=dict(bags_per_block=16))
+    f8s("f8s_D1040_two_passes", "f8s_wide", "pad100", 1040, "row", "weighted", tuning=dict(bags_per_block=8))
+    # -- scaled FP8 tables, un-pooled: pm_embedding_gather_f8_scaled on plan_gather_f8; three tables, each with exponents of its own
+    def f8sg(name, group, scale="row", rq="ragged", dims=128, fmt="e4m3", **kw):
+        add(name, group, "f8s_gather", rq, fmt, dims, scale=scale, **kw)
+
+    for (G, D), table_u in zip(((8, 16), (16, 64), (32, 128), (64, 256)), (2, 8, 1, 4)):
+        for u in (1, 2, 4, 8):
+            f8sg(f"f8s_gather_G{G}_u{u}", "f8s_gather_GU", dims=D, tuning=dict(unroll=u))
+        f8sg(f"f8s_gather_G{G}_u{table_u}_table", "f8s_gather_GU", "table", dims=D, tuning=dict(unroll=table_u))
+    f8sg("f8s_gather_bf16", "f8s_gather_knobs", tuning=dict(unroll=8), out16="bf16")
+    f8sg("f8s_gather_fp16", "f8s_gather_knobs", tuning=dict(unroll=2), out16="fp16")
+    f8sg("f8s_gather_xcd0", "f8s_gather_knobs", tuning=dict(unroll=2, xcd_affine=0))
+    f8sg("f8s_gather_D512_two_passes", "f8s_gather_knobs", rq="mixed_ragged", dims=512, tuning=dict(unroll=4))
+    f8sg("f8s_gather_slice", "f8s_gather_knobs", tuning=dict(unroll=4), bag_slice=(3, 90))
+    f8sg("f8s_gather_e5m2", "f8s_gather_knobs", fmt="e5m2", tuning=dict(unroll=8))
+    # -- mixed-format tables, pooled: pm_embbag_fwd_anyfmt on plan_anyfmt, eight columns per lane whatever the format (G = 8 up to D = 64,
+    #    64 from D = 264 on); a tile's table decides which of the seven row loops the workgroup runs, each with its own rows in flight
+    def anyf(name, group, rq, dims, formats, **kw):
+        add(name, group, "anyfmt", rq, "f32", dims, formats=formats, **kw)
+
+    seven = list(ANY_UNROLL)
+    rot = [[seven[(3 * k + t) % 7] for t in range(3)] for k in range(3)]    # three tables, three rotations: every format, neighbours differ
+    eight = seven + ["int8"]
+    # every format x every lane-group width x weighted, two bags per lane group (the fp32 burst filled exactly), several tiles a table
+    for G in (8, 16, 32, 64):
+        for k in range(3):
+            for w in (False, True):
+                anyf(f"any_G{G}_rot{k}_{wname[w]}", f"any_G{G}", "pad100", G * ANY_VEC, rot[k], tuning=dict(bags_per_block=2 * K_BLOCK // G), weighted=w)
+    # four bags per lane group: the 2-byte burst fits, the 4-byte one does not; all seven formats
+    anyf("any_out_bf16", "any_out16", "pad8", 256, eight, tuning=dict(bags_per_block=32), out16="bf16")
+    anyf("any_out_fp16_weighted", "any_out16", "pad8", 256, eight, tuning=dict(bags_per_block=32), out16="fp16", weighted=True)
+    anyf("any_out_fp32", "any_out16", "pad8", 256, eight, tuning=dict(bags_per_block=32))
+    # the fp32 burst over 18 tiles a table, and the same rows one by one
+    for w in (False, True):
+        anyf(f"any_burst_{wname[w]}", "any_burst", "pad1100", 64, ["fp8_e4m3", "int4"], tuning=dict(bags_per_block=64), weighted=w)
+        anyf(f"any_burst_{wname[w]}_unstaged", "any_burst", "pad1100", 64, ["fp8_e4m3", "int4"], tuning=dict(bags_per_block=64), forward=dict(stage_out=0),
+             weighted=w)
+    # block orders (block_to_tile picks the table, hence the format; the plain order on three tables: any_G16_*) and slices that begin
+    # and end inside tiles
+    anyf("any_xcd0_seven", "any_orders", "pad8", 128, eight, tuning=dict(bags_per_block=32, xcd_affine=0), weighted=True)
+    anyf("any_xcd1_seven", "any_orders", "pad8", 128, eight, tuning=dict(bags_per_block=32))
+    anyf("any_xcd3", "any_orders", "padfix", 128, rot[2], tuning=dict(bags_per_block=32))
+    anyf("any_slice", "any_orders", "pad100", 128, rot[1], tuning=dict(bags_per_block=32), bag_slice=(5, 70))
+    anyf("any_slice_weighted", "any_orders", "pad100", 128, rot[2], tuning=dict(bags_per_block=32), bag_slice=(5, 70), weighted=True)
+    # 1024-bag tiles
+    anyf("any_bpb1024_plain", "any_1024", "pad1100", 16, ["fp8_e5m2", "int4"], tuning=dict(bags_per_block=1024))
+    anyf("any_bpb1024_weighted", "any_1024", "pad1100", 16, ["bf16", "int8"], tuning=dict(bags_per_block=1024), weighted=True)
+    # the 32-bag tile of 1600 lookups (table 0's) reads its indices from the request: owned by an FP8, a 4-bit and an fp32 table
+    for first, rest in (("fp8_e4m3", ["bf16", "int8"]), ("int4", ["fp16", "fp8_e5m2"]), ("fp32", ["int8", "bf16"])):
+        for w in (False, True):
+            anyf(f"any_direct_{first}_{wname[w]}", "any_direct", "pad_lumpy", 256, [first] + rest, tuning=dict(bags_per_block=32), weighted=w)
+    # a second pass that ends inside the lane group (D = 520: one lane of 64 holds columns; no FP8 table has that width), four
+    # passes, mixed dims with the lane group sized for 128
+    anyf("any_D520_weighted", "any_wide", "pad100", 520, ["int4", "fp32", "int8"], tuning=dict(bags_per_block=8), weighted=True)
+    anyf("any_D520", "any_wide", "pad100", 520, ["bf16", "int4", "fp16"], tuning=dict(bags_per_block=8))
+    anyf("any_D2048_four_passes", "any_wide", "pad100", 2048, ["fp8_e4m3", "int4", "fp16"], tuning=dict(bags_per_block=8))
+    anyf("any_D2048_four_passes_weighted", "any_wide", "pad100", 2048, ["int8", "fp8_e5m2", "fp32"], tuning=dict(bags_per_block=8), weighted=True)
+    anyf("any_mixed_dims", "any_wide", "pad100", [16, 64, 128], ["fp8_e5m2", "int8", "fp32"], tuning=dict(bags_per_block=32), weighted=True)
+    # -- mixed-format tables, un-pooled: pm_embedding_gather_anyfmt on plan_gather_anyfmt; a lane group branches on its row's format
+    def anyg(name, group, rq="ragged8", dims=128, formats=None, **kw):
+        add(name, group, "anyfmt_gather", rq, "f32", dims, formats=formats or seven + ["fp16"], **kw)
+
+    plain5 = ["fp32", "int8", "bf16", "int4", "fp16", "int8", "fp32", "int4"]          # (D = 520 is no FP8 width)
+    for G in (8, 16, 32, 64):
+        for o16 in (None, "bf16", "fp16"):
+            anyg(f"any_gather_G{G}_{o16 or 'fp32'}", "any_gather_G", dims=G * ANY_VEC, out16=o16)
+    anyg("any_gather_xcd0", "any_gather_knobs", tuning=dict(xcd_affine=0))
+    anyg("any_gather_slice", "any_gather_knobs", bag_slice=(3, 8), out16="fp16")
+    anyg("any_gather_D520", "any_gather_knobs", dims=520, formats=plain5, out16="bf16")
+    anyg("any_gather_D2048_four_passes", "any_gather_knobs", dims=2048)
+    anyg("any_gather_260_tables", "any_gather_knobs", rq="many260", dims=64, formats=[seven[t % 7] for t in range(260)])
     # -- the environment switches: one group per setting, each in a process of its own
     e = "env_tile_major"
     add(f"{e}_ordered", e, "fwd", "ragged", tuning=dict(bags_per_block=32), env={"PARAM_AMD_FWD_TILE_MAJOR": 1})
@@ -569,6 +826,8 @@ def _cases():
     add(f"{e}_padded", e, "padded", "pad100", tuning=dict(bags_per_block=32), env=env)
     add(f"{e}_max", e, "max", "pad100", tuning=dict(bags_per_block=32), env=env)
     add(f"{e}_f8", e, "f8", "pad100", "e4m3", 128, tuning=dict(bags_per_block=32), env=env)
+    add(f"{e}_f8s", e, "f8s", "pad100", "e4m3", 128, tuning=dict(bags_per_block=32), env=env, scale="row")
+    add(f"{e}_anyfmt", e, "anyfmt", "pad100", "f32", 128, tuning=dict(bags_per_block=32), env=env, formats=rot[1])
     add(f"{e}_out16", e, "out16", "pad100", tuning=dict(bags_per_block=32), env=env, out16="bf16")
     assert len({c.name for c in out}) == len(out)
     for c in out:                                                  # a group shares its environment; its cases are one test

@@ -1,7 +1,11 @@
 """Runs one group of tests/plan_sweep.py on the GPU: for every case the knobs are set, ``pm_embbag_plan`` (``pm_embedding_gather_plan``)
 must report the row pinned in tests/plan_sweep_host.json, the entry point runs -- int64 and int32 indices, layouts ``bd`` and ``tbd``
 where the dims are equal -- and its output must equal the rule of the operation bit for bit.  The FP8 entries (``f8``, ``f8_gather``) build ``Float8BatchedEmbeddingBagMI355``
-modules, are asked through ``pm_embbag_f8_plan`` / ``pm_embedding_gather_f8_plan`` and compare with tests/f8_rules.py.
+modules, are asked through ``pm_embbag_f8_plan`` / ``pm_embedding_gather_f8_plan`` and compare with tests/f8_rules.py; the scaled ones
+(``f8s``, ``f8s_gather``) build the same class with ``scale=``, exponents as tests/test_gpu_f8s.py draws them, are asked through
+``pm_embbag_f8_scaled_plan`` / ``pm_embedding_gather_f8_plan`` and compare with tests/f8s_rules.py; the mixed-format ones (``anyfmt``,
+``anyfmt_gather``) build ``MixedBatchedEmbeddingBagMI355`` over the tables of tests/anyfmt_cases.py, are asked through
+``pm_embbag_anyfmt_plan`` / ``pm_embedding_gather_anyfmt_plan`` and compare with tests/anyfmt_rules.py.
 
 tests/test_gpu_plan_sweep.py calls ``run_group`` in its own process; for the groups with an environment setting it starts
 ``python -m tests.plan_sweep_worker GROUP`` with that setting, because the switches are read once per process.  Exit status 0: every
@@ -12,8 +16,11 @@ import sys
 
 import numpy as np
 
+from tests import anyfmt_cases as AC
+from tests import anyfmt_rules as AR
 from tests import embedding_rules as ER
 from tests import f8_rules as F8
+from tests import f8s_rules as F8S
 from tests import mean_rules as M
 from tests import out16_rules as O16
 from tests import padding_rules as P
@@ -59,7 +66,7 @@ def _bits16(t):
 
 def variants(c):
     """(index dtype, layout) pairs a case runs"""
-    if c.entry in ("gather", "f8_gather") or len(set(c.dims)) > 1:
+    if c.entry in S.GATHER_ENTRIES or len(set(c.dims)) > 1:
         return [("i64", "bd"), ("i32", "bd")]
     if c.request.startswith("auto") or c.group.startswith("base"):
         return [("i64", "bd"), ("i32", "tbd")]
@@ -128,8 +135,14 @@ def check_plan(c, op):
 
     if c.entry == "f8":
         got = list(_lib.embbag_f8_plan(op, S.OUT16_CODE[c.out16]).values())
-    elif c.entry == "f8_gather":
+    elif c.entry == "f8s":
+        got = list(_lib.embbag_f8_scaled_plan(op, S.OUT16_CODE[c.out16], c.mean, c.scale == "row").values())
+    elif c.entry in ("f8_gather", "f8s_gather"):
         got = list(_lib.embedding_gather_f8_plan(op).values())
+    elif c.entry == "anyfmt":
+        got = list(_lib.embbag_anyfmt_plan(op, S.OUT16_CODE[c.out16]).values())
+    elif c.entry == "anyfmt_gather":
+        got = list(_lib.embedding_gather_anyfmt_plan(op).values())
     elif c.plan_kind == "gather":
         got = list(_lib.embedding_gather_plan(op).values())
     else:
@@ -376,14 +389,19 @@ def f8_module(c, layout):
     torch = _torch()
     from param_amd import Float8BatchedEmbeddingBagMI355
 
-    pads = None if c.entry == "f8_gather" else c.req.pads
-    key = ("f8 module", c.kind, tuple(c.dims), tuple(c.req.rows), layout, None if pads is None else tuple(pads), c.mean, c.out16)
+    pads = None if c.entry in S.GATHER_ENTRIES else c.req.pads
+    key = ("f8 module", c.kind, tuple(c.dims), tuple(c.req.rows), layout, None if pads is None else tuple(pads), c.mean, c.out16, c.scale)
 
     def make():
         m = Float8BatchedEmbeddingBagMI355(c.req.rows, c.dims, c.kind, device=DEV, layout=layout, pooling_mode="mean" if c.mean else "sum",
-                                           padding_idx=pads, output_dtype={None: None, "bf16": torch.bfloat16, "fp16": torch.float16}[c.out16])
+                                           padding_idx=pads, output_dtype={None: None, "bf16": torch.bfloat16, "fp16": torch.float16}[c.out16],
+                                           scale=c.scale)
         for t, tab in enumerate(f8_tables(c)):
-            m.copy_from_(t, _t(tab))
+            if c.scale is None:
+                m.copy_from_(t, _t(tab))
+            else:
+                E, er = f8s_exps(c)[t]
+                m.copy_from_(t, _t(tab), exponents=E if c.scale == "table" else _t(er))
         return m
     return _memo(key, make)
 
@@ -439,8 +457,171 @@ def run_f8_gather(c, idt, layout, coracle):
         assert (got[~written] == _bits16(torch.full((1,), float("nan"), dtype=m.output_dtype))[0]).all(), "written outside the slice"
 
 
+def f8s_exps(c):
+    """the exponents of a scaled case's tables, ``[(E_t | None, e_rows | None)]`` as tests/f8s_rules.py takes them, drawn as
+    tests/test_gpu_f8s.py: make_exps draws them -- row mode: one per row in [-30, 10], no two neighbours equal; table mode: one value;
+    a different set per table"""
+    def make():
+        if c.scale == "table":
+            return [((13 * t + 5) % 41 - 30, None) for t in range(c.req.T)]
+        return [(None, ((np.arange(rows) * 7 + (11 * t + 3) % 41) % 41 - 30).astype(np.int64)) for t, rows in enumerate(c.req.rows)]
+    exps = _memo(("f8s exps", c.scale, tuple(c.req.rows)), make)
+    if c.scale == "row":
+        assert all((np.diff(er) != 0).all() for _, er in exps) and (c.req.T == 1 or not np.array_equal(exps[0][1][:100], exps[1][1][:100]))
+    else:
+        assert len({E for E, _ in exps}) == c.req.T and all(E for E, _ in exps)
+    return exps
+
+
+def run_f8s(c, idt, layout, coracle):
+    """pm_embbag_fwd_f8_scaled: run_f8 with exponents -- ``pm_embbag_f8_scaled_plan`` must report the pinned row (plan_f8's with the
+    restated f8s_stage_out), the NaN canvas must equal tests/f8s_rules.py: forward on bits and stay NaN elsewhere"""
+    torch = _torch()
+    r, (b0, n) = c.req, c.bags
+    m, tabs, exps = f8_module(c, layout), f8_tables(c), f8s_exps(c)
+    assert m.scale == c.scale
+    it = torch.int64 if idt == "i64" else torch.int32
+    idx_t, off_t = _t(r.idx, it), _t(r.off, it)
+    psw_t = _t(r.psw) if c.weighted else None
+    check_plan(c, m._request(idx_t, off_t, psw_t, b0, n if c.bag_slice else None, r.B, False)[2])
+    outs = _memo(("f8s", c.request, c.kind, tuple(c.dims), c.weighted, c.mean, c.scale),
+                 lambda: F8S.forward(tabs, c.kind, exps, r.idx, r.off, r.B, r.pads, r.psw if c.weighted else None, c.mean))
+    assert all(np.isfinite(o).all() for o in outs)
+    shape = (r.B, sum(c.dims)) if layout == "bd" else (r.T, r.B, c.dims[0])
+    sel = _sel(layout, b0, n)
+    rest = np.ones(shape, dtype=bool)
+    rest[sel] = False
+    canvas = torch.full(shape, float("nan"), dtype=m.output_dtype, device=DEV)
+    assert m.lookup(idx_t, off_t, psw_t, out=canvas, batch=r.B, bag_begin=b0, bag_count=n) is canvas
+    if c.out16 is None:
+        got, want = canvas.cpu().numpy(), _assemble(outs, layout)
+        assert _same_f32_or_nan(got[sel], want[sel]), _first_diff(got[sel].view(np.uint32), want[sel].view(np.uint32))
+        assert np.isnan(got[rest]).all(), "written outside the slice"
+    else:
+        got, want = _bits16(canvas), _assemble([F8S.round16(o, c.out16) for o in outs], layout)
+        assert F8S.same16(got[sel], want[sel], c.out16), _first_diff(got[sel], want[sel])
+        assert (got[rest] == _bits16(torch.full((1,), float("nan"), dtype=m.output_dtype))[0]).all(), "written outside the slice"
+
+
+def run_f8s_gather(c, idt, layout, coracle):
+    """pm_embedding_gather_f8_scaled into a NaN canvas: tests/f8s_rules.py: sequence on bits where the rule writes, NaN elsewhere"""
+    torch = _torch()
+    r, (b0, n) = c.req, c.bags
+    m, tabs, exps = f8_module(c, layout), f8_tables(c), f8s_exps(c)
+    assert m.scale == c.scale
+    it = torch.int64 if idt == "i64" else torch.int32
+    idx_t, off_t = _t(r.idx, it), _t(r.off, it)
+    check_plan(c, m._request(idx_t, off_t, None, b0, n if c.bag_slice else None, r.B, False)[2])
+    if _memo(("f8 unscaled twin asked", c.group), lambda: [c.name, idt])[:] == [c.name, idt]:
+        # once per group: pm_embedding_gather_f8_scaled launches on plan_gather_f8, a scaled module's ``sequence_plan`` is an unscaled one's
+        from param_amd import Float8BatchedEmbeddingBagMI355
+
+        plain = _memo(("f8 unscaled twin", c.kind, tuple(c.dims), tuple(r.rows), layout),
+                      lambda: Float8BatchedEmbeddingBagMI355(r.rows, c.dims, c.kind, device=DEV, layout=layout))
+        assert plain.scale is None
+        args = dict(batch=r.B, bag_begin=b0, bag_count=n if c.bag_slice else None)
+        assert m.sequence_plan(idx_t, off_t, **args) == plain.sequence_plan(idx_t, off_t, **args) and list(m.sequence_plan(idx_t, off_t, **args).values()) == pinned(c.name)
+    want, written = _memo(("f8s rows", c.request, c.kind, tuple(c.dims), c.scale, b0, n),
+                          lambda: F8S.sequence(tabs, c.kind, exps, r.idx, r.off, r.B, b0, n))
+    assert written.any() and (written.all() != bool(c.bag_slice)) and np.isfinite(want).all()
+    canvas = torch.full((r.N, c.dims[0]), float("nan"), dtype=m.output_dtype, device=DEV)
+    assert m.lookup_sequence(idx_t, off_t, batch=r.B, out=canvas, bag_begin=b0, bag_count=n) is canvas
+    if c.out16 is None:
+        got = canvas.cpu().numpy()
+        assert _same_f32_or_nan(got[written], want[written]), _first_diff(got[written].view(np.uint32), want[written].view(np.uint32))
+        assert np.isnan(got[~written]).all(), "written outside the slice"
+    else:
+        got, want16 = _bits16(canvas), F8S.round16(want, c.out16)
+        assert F8S.same16(got[written], want16[written], c.out16), _first_diff(got[written], want16[written])
+        assert (got[~written] == _bits16(torch.full((1,), float("nan"), dtype=m.output_dtype))[0]).all(), "written outside the slice"
+
+
+_ANY_KIND = {None: "f32", "bf16": "bf16", "fp16": "f16"}           # a case's ``out16`` as tests/anyfmt_rules.py spells the output kind
+
+
+def anyfmt_tables(c):
+    """the tables of a mixed-format case as tests/anyfmt_rules.py: Table (the bytes the module stores), from tests/anyfmt_cases.py: one
+    set per (formats, rows, dims); every FP8 table carries a table exponent that is not 0, neighbours' differ"""
+    def make():
+        tabs = AC.tables(c.formats, c.req.rows, c.dims, 7100, exps=[(-2, 3, -5, 1)[t % 4] for t in range(c.req.T)])
+        assert all(tab.exp != 0 for tab in tabs if tab.fmt.startswith("fp8"))
+        return tabs
+    return _memo(("anyfmt tables", tuple(c.formats), tuple(c.req.rows), tuple(c.dims)), make)
+
+
+def anyfmt_module(c, layout):
+    """the MixedBatchedEmbeddingBagMI355 of a case, one per distinct set of options; float and FP8 tables go in through ``copy_from_``
+    (FP8: uint8 codes and the exponent), quantised rows through the table view"""
+    torch = _torch()
+    from param_amd import MixedBatchedEmbeddingBagMI355
+
+    key = ("anyfmt module", tuple(c.formats), tuple(c.dims), tuple(c.req.rows), layout, c.out16)
+    view = {"fp32": np.float32, "bf16": np.int16, "fp16": np.int16}
+    tdt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+
+    def make():
+        m = MixedBatchedEmbeddingBagMI355(c.req.rows, c.dims, c.formats, device=DEV, layout=layout,
+                                          output_dtype={None: None, "bf16": torch.bfloat16, "fp16": torch.float16}[c.out16])
+        for t, tab in enumerate(anyfmt_tables(c)):
+            if tab.fmt in view:
+                m.copy_from_(t, _t(tab.data.view(view[tab.fmt]).reshape(-1, tab.dim)).view(tdt[tab.fmt]))
+            elif tab.fmt.startswith("fp8"):
+                m.copy_from_(t, _t(tab.data), exponent=tab.exp)
+            else:
+                m.table(t).copy_(_t(tab.data))
+        assert m.formats == c.formats and m.table_exponents.tolist() == [tab.exp for tab in anyfmt_tables(c)]
+        return m
+    return _memo(key, make)
+
+
+def run_anyfmt(c, idt, layout, coracle):
+    """pm_embbag_fwd_anyfmt: the batch, or a slice of it, into a NaN canvas that must equal tests/anyfmt_rules.py: forward_bits (every
+    table by its own format's rule; a 16-bit output: the one rounding) and stay NaN elsewhere.  The padded requests' indices are plain
+    indices here: the module has no padding row."""
+    torch = _torch()
+    r, (b0, n) = c.req, c.bags
+    m, tabs, kind = anyfmt_module(c, layout), anyfmt_tables(c), _ANY_KIND[c.out16]
+    it = torch.int64 if idt == "i64" else torch.int32
+    idx_t, off_t = _t(r.idx, it), _t(r.off, it)
+    psw_t = _t(r.psw) if c.weighted else None
+    check_plan(c, m._request(idx_t, off_t, psw_t, b0, n if c.bag_slice else None, r.B, False)[2])
+    outs = _memo(("anyfmt", c.request, tuple(c.formats), tuple(c.dims), c.weighted),
+                 lambda: AR.forward(tabs, r.idx, r.off, r.B, r.psw if c.weighted else None))
+    assert all(np.isfinite(o).all() for o in outs)
+    want = _assemble([AR.to_kind(o, kind) for o in outs], layout)
+    shape = (r.B, sum(c.dims)) if layout == "bd" else (r.T, r.B, c.dims[0])
+    sel = _sel(layout, b0, n)
+    rest = np.ones(shape, dtype=bool)
+    rest[sel] = False
+    canvas = torch.full(shape, float("nan"), dtype=m.output_dtype, device=DEV)
+    assert m.lookup(idx_t, off_t, psw_t, out=canvas, batch=r.B, bag_begin=b0, bag_count=n) is canvas
+    got = canvas.cpu().numpy().view(np.uint32) if c.out16 is None else _bits16(canvas)
+    assert AR.same(got[sel], want[sel], kind), _first_diff(got[sel], want[sel])
+    assert AR.is_nan(got[rest], kind).all(), "written outside the slice"
+
+
+def run_anyfmt_gather(c, idt, layout, coracle):
+    """pm_embedding_gather_anyfmt into a NaN canvas: tests/anyfmt_rules.py: sequence on bits where the rule writes (a 16-bit row to
+    its own type: a bit copy), NaN elsewhere"""
+    torch = _torch()
+    r, (b0, n) = c.req, c.bags
+    m, tabs, kind = anyfmt_module(c, layout), anyfmt_tables(c), _ANY_KIND[c.out16]
+    it = torch.int64 if idt == "i64" else torch.int32
+    idx_t, off_t = _t(r.idx, it), _t(r.off, it)
+    check_plan(c, m._request(idx_t, off_t, None, b0, n if c.bag_slice else None, r.B, False)[2])
+    want, written, copied = _memo(("anyfmt rows", c.request, tuple(c.formats), tuple(c.dims), kind, b0, n),
+                                  lambda: AR.sequence(tabs, r.idx, r.off, r.B, kind, b0, n))
+    assert written.any() and (written.all() != bool(c.bag_slice)) and (copied.any() or kind == "f32" and "fp32" not in c.formats)
+    canvas = torch.full((r.N, c.dims[0]), float("nan"), dtype=m.output_dtype, device=DEV)
+    assert m.lookup_sequence(idx_t, off_t, batch=r.B, out=canvas, bag_begin=b0, bag_count=n) is canvas
+    got = canvas.cpu().numpy().view(np.uint32) if c.out16 is None else _bits16(canvas)
+    assert AR.same(got[written], want[written], kind, copied[written]), _first_diff(got[written], want[written])
+    assert AR.is_nan(got[~written], kind).all(), "written outside the slice"
+
+
 RUN = {"fwd": run_forward, "padded": run_forward, "mean": run_forward, "out16": run_forward, "quantized": run_quantized, "gather": run_gather,
-       "psw_grad": run_base, "mean_grad": run_base, "widen": run_base, "atomic": run_base, "max": run_max, "f8": run_f8, "f8_gather": run_f8_gather}
+       "psw_grad": run_base, "mean_grad": run_base, "widen": run_base, "atomic": run_base, "max": run_max, "f8": run_f8, "f8_gather": run_f8_gather,
+       "f8s": run_f8s, "f8s_gather": run_f8s_gather, "anyfmt": run_anyfmt, "anyfmt_gather": run_anyfmt_gather}
 
 
 def run_group(group, coracle, log=None):
@@ -494,8 +675,14 @@ def host_plans(group):
             param_amd.set_forward_tuning(*c.forward_args())
             if c.entry == "f8":
                 plan = _lib.embbag_f8_plan(op, S.OUT16_CODE[c.out16])
-            elif c.entry == "f8_gather":
+            elif c.entry == "f8s":
+                plan = _lib.embbag_f8_scaled_plan(op, S.OUT16_CODE[c.out16], c.mean, c.scale == "row")
+            elif c.entry in ("f8_gather", "f8s_gather"):
                 plan = _lib.embedding_gather_f8_plan(op)
+            elif c.entry == "anyfmt":
+                plan = _lib.embbag_anyfmt_plan(op, S.OUT16_CODE[c.out16])
+            elif c.entry == "anyfmt_gather":
+                plan = _lib.embedding_gather_anyfmt_plan(op)
             else:
                 plan = _lib.embedding_gather_plan(op) if c.plan_kind == "gather" else _lib.embbag_plan(op, S.KIND[c.plan_kind])
             res[c.name] = list(plan.values())

@@ -17,7 +17,16 @@ the rowquant reference and the default-knob bytes; a batch slice writes into a N
 (``f8_fwd_kernel<WT, G, U, WEIGHTED, MEAN, OT>``, ``embedding_gather_f8_kernel<WT, OT, G, U>``; tests/test_gpu_f8.py runs one tile a table)
 have their multi-tile paths pinned here: groups ``f8_*`` hold ``Float8BatchedEmbeddingBagMI355`` to ``f8_rules.forward`` / ``sequence``
 under ``pm_embbag_f8_plan`` / ``pm_embedding_gather_f8_plan`` -- tiles behind tile 0, the block orders, compaction over several waves and
-rounds, 1024-bag and direct tiles, every (lane group, rows in flight) pair of both kernels.  The entry
+rounds, 1024-bag and direct tiles, every (lane group, rows in flight) pair of both kernels.  The scaled FP8 lookups
+(``f8s_fwd_kernel<WT, G, U, WEIGHTED, MEAN, ROW, OT>``, ``embedding_gather_f8s_kernel``; tests/test_gpu_f8s.py runs one table and one tile)
+are pinned in groups ``f8s_*``: the same shapes with row exponents -- the exponent byte compacted next to its index over ten rounds, loaded
+next to the index of a direct tile, picked per table under every block order, the burst behind the exponent bytes -- and with a table
+exponent, under ``pm_embbag_f8_scaled_plan``, whose ``stage_out`` must be 0 on the one side of the 64 KiB edge (``f8s_edge``) and the
+row's width on the other; the un-pooled lookup's ``sequence_plan`` must equal an unscaled module's.  The mixed-format lookups
+(``anyfmt_fwd_kernel<G, WEIGHTED, OT>``, ``anyfmt_gather_kernel<OT, G>``; tests/test_gpu_anyfmt.py runs G = 8, 32 and 64 with one tile a
+table) are pinned in groups ``any_*``: every format at every lane-group width, weighted and not, over several tiles a table whose
+neighbours differ in format, each format's tail loop, direct tiles of an FP8, a 4-bit and an fp32 table, D = 520 and 2048, 1024-bag
+tiles, block orders and slices; the gather with seven formats in one tile of positions and with more tables than it stages borders for.  The entry
 points on the base plan equal their default-knob bits and their rule; the one non-deterministic entry, the alternates' atomic backward, is held to the fuzz test's 1e-5 bar.  No tolerance is new.
 
 One test is one group: a few dozen launches on one small request.  The groups with an environment setting run in a fresh child each

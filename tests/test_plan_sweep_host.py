@@ -37,7 +37,11 @@ def planned(tmp_path_factory):
 
 
 def _rows(planned):
-    return {c.name: {"plan": planned[c.name], "label": " ".join(sorted(S.label(c, planned[c.name])))} for c in S.CASES}
+    rows = {}
+    for c in S.CASES:                                              # (the scaled FP8 pooled plan: plan_f8's row after the restated LDS rule)
+        plan = S.pinned_plan(c, planned[c.name])
+        rows[c.name] = {"plan": plan, "label": " ".join(sorted(S.label(c, plan, planned[c.name])))}
+    return rows
 
 
 def _pinned():
@@ -136,8 +140,9 @@ def _f8_conditions(cases, missing):
     """the FP8 entries (``f8``: pm_embbag_fwd_f8, ``f8_gather``: pm_embedding_gather_f8).  Every condition reads the label
     ``plan_sweep.f8_label`` derives from the request's offsets, indices and pads next to the pinned plan.  At the end: every FP8 case is
     the last one left to meet some condition, so deleting any of them is noticed."""
-    f8 = [(c, w, p) for c, w, p in cases if c.entry.startswith("f8")]
-    assert all("f8" in w for c, w, p in f8) and not any("f8" in w for c, w, p in cases if not c.entry.startswith("f8"))
+    f8 = [(c, w, p) for c, w, p in cases if c.entry in ("f8", "f8_gather")]
+    assert all("f8" in w for c, w, p in cases if c.entry.startswith("f8")) and not any("f8" in w for c, w, p in cases if not c.entry.startswith("f8"))
+    assert not any({"row", "table"} & w for c, w, p in f8)          # (the scaled entries' words: _f8s_conditions)
     held = []                                                      # (the cases that meet a condition, how many it asks for)
 
     def need(what, cond, at_least=1):
@@ -216,6 +221,172 @@ def _f8_conditions(cases, missing):
          and any("e4m3" in w2 and w2 - {"e4m3"} == w - {"e5m2"} for _, w2, _ in f8))
     spare = [c.name for c, w, p in f8 if not any(c.name in got and len(got) == n for got, n in held)]
     assert not spare, f"FP8 cases that no condition depends on: {spare}"
+
+
+def _needs(family, missing, prefix):
+    """(need, spare): ``need(what, cond, at_least=1)`` notes ``what`` as missing unless ``at_least`` cases of ``family`` meet ``cond``;
+    ``spare()`` names the cases that are never the last ones left to meet a condition -- deleting one of those would go unnoticed"""
+    held = []
+
+    def need(what, cond, at_least=1):
+        got = [c.name for c, w, p in family if cond(c, w, p)]
+        held.append((got, at_least))
+        if len(got) < at_least:
+            missing.append(f"{prefix}: {what}")
+
+    return need, lambda: [c.name for c, w, p in family if not any(c.name in got and len(got) == n for got, n in held)]
+
+
+def _f8s_conditions(cases, missing):
+    """the scaled FP8 entries (``f8s``: pm_embbag_fwd_f8_scaled, ``f8s_gather``: pm_embedding_gather_f8_scaled): the FP8 entries'
+    conditions on ``f8_label``'s words plus the kind of exponent, and the LDS edge where the row exponents' bytes cost a tile its burst.
+    At the end: every scaled case is the last one left to meet some condition."""
+    fam = [(c, w, p) for c, w, p in cases if c.entry.startswith("f8s")]
+    assert all(len({"row", "table"} & w) == 1 for c, w, p in fam)
+    need, spare = _needs(fam, missing, "f8s")
+    pooled = lambda c, w: "pooled" in w and not c.env                                           # noqa: E731
+    tiles = lambda p: p["tiles_per_table"]                                                      # noqa: E731
+    modes = ("unweighted", "weighted", "mean")
+    base = lambda c, w, p: pooled(c, w) and {"G16", "bpb32", "u2", "tile>NG", "partial", "xcd0"} <= w and tiles(p) >= 3 and c.dims[0] == 256  # noqa: E731
+    for fmt in S.F8_DTYPE:
+        for sc in ("row", "table"):
+            for mode in modes:
+                need(f"baseline {fmt} {sc} {mode}, fp32 rows leave one by one", lambda c, w, p: base(c, w, p) and {fmt, sc, mode, "out-fp32", "plain"} <= w)
+                need(f"baseline {fmt} {sc} {mode}, bf16 burst", lambda c, w, p: base(c, w, p) and {fmt, sc, mode, "out-bf16", "staged"} <= w)
+    need("baseline bf16 with stage_out 0", lambda c, w, p: base(c, w, p) and {"row", "out-bf16", "plain"} <= w and c.forward.get("stage_out") == 0)
+    for sc, ms in (("row", modes), ("table", modes[:1])):
+        for mode in ms:
+            for burst in ("staged", "plain"):
+                need(f"64-bag tiles of fp32 rows {sc} {mode} {burst}",
+                     lambda c, w, p: pooled(c, w) and {"G8", "bpb64", "u2", "tile>NG", "partial", "out-fp32", sc, mode, burst} <= w and tiles(p) >= 3)
+    for G, D, _ in S.F8_GROUP_DIMS:
+        group = lambda c, w, p: pooled(c, w) and {f"G{G}", f"bpb{512 // G}", "tile>NG", "partial"} <= w and tiles(p) > 1 and c.dims[0] == D \
+            and c.request == "pad100"                                                          # noqa: E731
+        for u in (2, 4, 8):
+            for mode in modes[:2]:
+                need(f"G{G} u{u} {mode} row", lambda c, w, p: group(c, w, p) and {f"u{u}", mode, "row"} <= w)
+        need(f"G{G} mean row", lambda c, w, p: group(c, w, p) and {"mean", "row"} <= w)
+        need(f"G{G} table", lambda c, w, p: group(c, w, p) and "table" in w)
+    for x in (0, 1, 3):
+        need(f"xcd_affine {x}, row exponents", lambda c, w, p: pooled(c, w) and {f"xcd{x}", "G8", "bpb32", "staged", "partial", "unweighted", "row"} <= w
+             and tiles(p) > 1 and not {"slice", "direct"} & w and c.dims == [128] * c.req.T)
+    need("xcd_affine 1 on 8 tables", lambda c, w, p: pooled(c, w) and {"xcd1", "row"} <= w and c.req.T == 8 and tiles(p) > 1)
+    for mode in ("unweighted", "mean"):
+        need(f"slice inside tiles {mode}", lambda c, w, p: pooled(c, w) and {"slice", "partial", mode, "row"} <= w and tiles(p) > 1
+             and c.bag_slice[0] % p["bags_per_block"] and sum(c.bag_slice) % p["bags_per_block"])
+    for mode in modes:
+        for out in ("out-fp32", "out-bf16"):
+            need(f"1024 bags {mode} {out}", lambda c, w, p: pooled(c, w) and {"bounds5", "bpb1024", "rounds>1", "waves>1", "carry", mode, out, "row"} <= w
+                 and c.req.B > 1024)
+    for mode in modes:
+        for u in (2, 8):
+            need(f"direct {mode} u{u}", lambda c, w, p: pooled(c, w) and {"direct", "rounds>1", "bpb32", mode, f"u{u}", "row"} <= w
+                 and p["idx_cap"] == 1280 and c.req.pads is not None and tiles(p) > 1)
+    # the LDS edge (common.h: f8s_stage_out), byte for byte from the restated rule: (with the burst plan_f8 granted, as launched)
+    # (the reach test sees the pinned rows only: the stage_out plan_f8 granted is put back from the label word here, so these conditions
+    # hold the label, the pinned stage_out and the byte counts to one another; that the pinned row IS the dump's row after the rule is
+    # test_every_case_plans_its_pinned_row's, which recomputes row and label from launch_plan_dump)
+    def lds(c, w, p):
+        dumped = dict(p, stage_out=max(c.dims) if "burst-dropped" in w else p["stage_out"])
+        return S.f8s_case_lds(c, [dumped[f] for f in S.PLAN_FIELDS])
+    edge = lambda c, w, p: pooled(c, w) and {"bpb512", "out-bf16", "G8"} <= w and p["idx_cap"] == 4096 and c.dims[0] == 16          # noqa: E731
+    need("edge: row exponents and weights drop the burst", lambda c, w, p: edge(c, w, p) and {"row", "weighted", "burst-dropped", "plain"} <= w
+         and p["stage_out"] == 0 and lds(c, w, p) == (65552, 49168))
+    need("edge: a table exponent keeps it", lambda c, w, p: edge(c, w, p) and {"table", "weighted", "staged"} <= w and lds(c, w, p) == (61456, 61456))
+    need("edge: row exponents without weights keep it", lambda c, w, p: edge(c, w, p) and {"row", "unweighted", "staged"} <= w and lds(c, w, p) == (49168, 49168))
+    for c, w, p in fam:                                            # ... and nothing else plans past it
+        if c.entry == "f8s":
+            assert ("burst-dropped" in w) == (lds(c, w, p)[0] > 65536) and lds(c, w, p)[1] <= 65536, c.name
+    need("mixed dims, the lane group sized for 128", lambda c, w, p: pooled(c, w) and {"G8", "row"} <= w and c.dims == [16, 64, 128] and tiles(p) > 1)
+    wide = lambda c, w, p: pooled(c, w) and {"G32", "bpb16", "tile>NG", "row"} <= w and c.dims[0] == 512 and tiles(p) > 1       # noqa: E731
+    need("D = 512, 2-byte outputs: staged", lambda c, w, p: wide(c, w, p) and {"out-bf16", "staged"} <= w)
+    need("D = 512, 4-byte outputs: not staged", lambda c, w, p: wide(c, w, p) and {"out-fp32", "plain"} <= w and not c.forward)
+    need("two column passes over more than one tile", lambda c, w, p: pooled(c, w) and {"G64", "passes2", "tile>NG", "row"} <= w and tiles(p) > 1)
+    need("FWD_STAGE=0", lambda c, w, p: c.env.get("PARAM_AMD_FWD_STAGE") == 0 and {"pooled", "plain", "bpb32", "row"} <= w and tiles(p) > 1
+         and p["bags_per_block"] * c.dims[0] * 4 <= 16384)
+    gp = lambda p: dict(zip(S.GATHER_FIELDS, p.values()))                                       # noqa: E731
+    rows = lambda c, w, p: "unpooled" in w and "partial" in w and gp(p)["grid"] > 8 and c.req.T > 1    # noqa: E731
+    for G in (8, 16, 32, 64):
+        for u in (1, 2, 4, 8):
+            need(f"gather G{G} u{u} row", lambda c, w, p: rows(c, w, p) and {f"G{G}", f"u{u}", "out-fp32", "e4m3", "xcd1", "passes1", "row"} <= w
+                 and "slice" not in w)
+        need(f"gather G{G} table", lambda c, w, p: rows(c, w, p) and {f"G{G}", "table"} <= w)
+    for out in ("out-bf16", "out-fp16"):
+        need(f"gather {out}", lambda c, w, p: rows(c, w, p) and {out, "row"} <= w)
+    need("gather xcd0", lambda c, w, p: rows(c, w, p) and "xcd0" in w)
+    need("gather two passes", lambda c, w, p: {"unpooled", "passes2", "G64", "row"} <= w and c.dims[0] == 512)
+    need("gather slice", lambda c, w, p: rows(c, w, p) and "slice" in w and c.bag_slice[0] > 0)
+    need("gather e5m2", lambda c, w, p: rows(c, w, p) and {"e5m2", "row"} <= w)
+    assert not spare(), f"scaled FP8 cases that no condition depends on: {spare()}"
+
+
+def _anyfmt_conditions(cases, missing):
+    """the mixed-format entries (``anyfmt``: pm_embbag_fwd_anyfmt, ``anyfmt_gather``: pm_embedding_gather_anyfmt) on the words of
+    ``plan_sweep.anyfmt_label``.  At the end: every mixed-format case is the last one left to meet some condition."""
+    fam = [(c, w, p) for c, w, p in cases if c.entry.startswith("anyfmt")]
+    assert all("any" in w for c, w, p in fam) and not any("any" in w for c, w, p in cases if not c.entry.startswith("anyfmt"))
+    need, spare = _needs(fam, missing, "anyfmt")
+    seven = list(S.ANY_UNROLL)
+    pooled = lambda c, w: "pooled" in w and not c.env                                           # noqa: E731
+    tiles = lambda p: p["tiles_per_table"]                                                      # noqa: E731
+    wt = ("unweighted", "weighted")
+    differ = lambda c: all(a != b for a, b in zip(c.formats, c.formats[1:]))                    # noqa: E731
+    all7 = lambda w: {f"fmt:{f}" for f in seven} <= w                                           # noqa: E731
+    assert all(differ(c) for c, w, p in fam), "tables next to each other differ in format: so do consecutive tiles of different tables"
+    # every (format, lane-group width, weighted) in a multi-tile case with two bags per lane group
+    for G in (8, 16, 32, 64):
+        for f in seven:
+            for mode in wt:
+                need(f"{f} G{G} {mode}", lambda c, w, p: pooled(c, w) and {f"fmt:{f}", f"G{G}", f"bpb{512 // G}", "tile>NG", "partial", "staged", mode,
+                                                                          "out-fp32", "passes1"} <= w
+                     and tiles(p) > 1 and c.request == "pad100" and c.dims == [G * 8] * 3 and not c.bag_slice)
+    for f in seven:
+        need(f"{f}: a bag that ends in the tail loop of its {S.ANY_UNROLL[f]} rows in flight", lambda c, w, p: pooled(c, w) and f"tail:{f}" in w)
+    # four bags per lane group: the 16-bit burst fits, the 4-byte one does not; all seven formats
+    four = lambda c, w, p: pooled(c, w) and {"G32", "bpb32", "tile>NG", "partial"} <= w and all7(w) and tiles(p) > 1       # noqa: E731
+    need("bf16 burst", lambda c, w, p: four(c, w, p) and {"out-bf16", "staged"} <= w)
+    need("fp16 burst", lambda c, w, p: four(c, w, p) and {"out-fp16", "staged"} <= w)
+    need("fp32 rows of the same tile leave one by one", lambda c, w, p: four(c, w, p) and {"out-fp32", "plain"} <= w and not c.forward)
+    for mode in wt:
+        for burst in ("staged", "plain"):
+            need(f"64-bag tiles of fp32 rows {mode} {burst}",
+                 lambda c, w, p: pooled(c, w) and {"G8", "bpb64", "tile>NG", "partial", "out-fp32", mode, burst} <= w and tiles(p) >= 3 and c.req.B > 1024)
+    need("xcd_affine 0, all seven formats", lambda c, w, p: pooled(c, w) and {"xcd0", "G16", "bpb32"} <= w and all7(w) and tiles(p) > 1)
+    need("xcd_affine 1, all seven formats", lambda c, w, p: pooled(c, w) and {"xcd1", "G16", "bpb32"} <= w and all7(w) and tiles(p) > 1 and c.req.T == 8)
+    need("xcd_affine 3", lambda c, w, p: pooled(c, w) and {"xcd3", "G16", "bpb32", "partial"} <= w and tiles(p) > 1)
+    for mode in wt:
+        need(f"slice inside tiles {mode}", lambda c, w, p: pooled(c, w) and {"slice", "partial", mode} <= w and tiles(p) > 1
+             and c.bag_slice[0] % p["bags_per_block"] and sum(c.bag_slice) % p["bags_per_block"])
+        need(f"1024 bags {mode}", lambda c, w, p: pooled(c, w) and {"bpb1024", "tile>NG", "partial", mode} <= w and c.req.B > 1024)
+        for f in ("fp8_e4m3", "int4", "fp32"):
+            need(f"direct tile of a {f} table {mode}", lambda c, w, p: pooled(c, w) and {f"direct:{f}", "G32", "bpb32", "tile>NG", mode} <= w
+                 and p["idx_cap"] == 1280 and tiles(p) > 1)
+        need(f"D = 520 {mode}", lambda c, w, p: pooled(c, w) and {"G64", "passes2", "row-ends-in-pass", "tile>NG", mode} <= w and tiles(p) > 1)
+        need(f"four passes {mode}", lambda c, w, p: pooled(c, w) and {"G64", "passes4", "tile>NG", mode} <= w and c.dims[0] == 2048 and tiles(p) > 1)
+    need("mixed dims, the lane group sized for 128", lambda c, w, p: pooled(c, w) and "G16" in w and c.dims == [16, 64, 128] and tiles(p) > 1)
+    need("FWD_STAGE=0", lambda c, w, p: c.env.get("PARAM_AMD_FWD_STAGE") == 0 and {"any", "pooled", "plain", "bpb32"} <= w and tiles(p) > 1
+         and p["bags_per_block"] * c.dims[0] * 4 <= 16384)
+    # the launcher's 64 KiB fallback (embbag_fwd_anyfmt_kernel.inc: launch_any_w) is out of reach: the largest tile any plan can ask for
+    # -- 1024 bags, 4096 index-tile entries, weights -- is 40976 bytes, the burst at most 16384
+    any_lds = lambda bpb, cap, weighted, burst: ((bpb + 2) // 2 * 2 * 8 + cap * 4 * (2 if weighted else 1) + 15) // 16 * 16 + burst  # noqa: E731
+    assert any_lds(1024, 4096, True, 16384) == 40976 + 16384 <= 65536
+    for c, w, p in fam:
+        if c.entry == "anyfmt":
+            burst = p["bags_per_block"] * p["stage_out"] * (2 if c.out16 else 4)
+            assert burst <= 16384 and p["idx_cap"] <= 4096 and any_lds(p["bags_per_block"], p["idx_cap"], c.weighted, burst) <= 57360, c.name
+    # the gather: a tile of positions holds all seven formats, a wave several
+    gp = lambda p: dict(zip(S.GATHER_FIELDS, p.values()))                                       # noqa: E731
+    rows = lambda c, w, p: {"unpooled", "partial", "u4"} <= w and gp(p)["grid"] > 1                    # noqa: E731
+    for G in (8, 16, 32, 64):
+        for out in ("out-fp32", "out-bf16", "out-fp16"):
+            need(f"gather G{G} {out}", lambda c, w, p: rows(c, w, p) and {f"G{G}", out, "tile-formats7", "lds_borders", "xcd1", "passes1"} <= w
+                 and not {"wave-formats1", "slice"} & w and c.dims[0] == G * 8)
+    need("gather xcd0", lambda c, w, p: rows(c, w, p) and {"xcd0", "tile-formats7"} <= w)
+    need("gather slice", lambda c, w, p: rows(c, w, p) and "slice" in w and c.bag_slice[0] > 0)
+    need("gather D = 520", lambda c, w, p: rows(c, w, p) and {"G64", "passes2", "row-ends-in-pass"} <= w)
+    need("gather four passes", lambda c, w, p: rows(c, w, p) and {"G64", "passes4"} <= w and c.dims[0] == 2048)
+    need("gather beyond 255 tables", lambda c, w, p: rows(c, w, p) and {"global_borders", "tile-formats7"} <= w and c.req.T > 255)
+    assert not spare(), f"mixed-format cases that no condition depends on: {spare()}"
 
 
 def test_the_sweep_reaches_every_variant():
@@ -344,13 +515,17 @@ def test_the_sweep_reaches_every_variant():
     need("FWD_STAGE=0: forward", lambda c, w, p: env(c, "PARAM_AMD_FWD_STAGE", 0) and {"tile", "plain"} <= w, 2)
     need("FWD_STAGE=0: padded family", lambda c, w, p: env(c, "PARAM_AMD_FWD_STAGE", 0) and {"pad", "plain"} <= w and "max" not in w, 2)
     _f8_conditions(cases, missing)
+    _f8s_conditions(cases, missing)
+    _anyfmt_conditions(cases, missing)
+    assert {c.request for c in S.CASES if c.entry.startswith(("f8s", "anyfmt"))} - {c.request for c in S.CASES if not c.entry.startswith(("f8s", "anyfmt"))} \
+        == {"pad600", "ragged8", "many260"}
     assert not missing, missing
     assert len(S.ENV_GROUPS) == 6 and len({tuple(sorted(c.env.items())) for c in S.CASES if c.env}) == 6
     assert all(max(c.req.rows) <= 1000 for c in S.CASES)
     # both index types and, where the dims are equal, both layouts: every case runs them (tests/plan_sweep_worker.py: variants)
     for c in S.CASES:
         v = W.variants(c)
-        assert {i for i, _ in v} == {"i64", "i32"} and (len(set(c.dims)) > 1 or c.entry in ("gather", "f8_gather")
+        assert {i for i, _ in v} == {"i64", "i32"} and (len(set(c.dims)) > 1 or c.entry in S.GATHER_ENTRIES
                                                         or {lay for _, lay in v} == {"bd", "tbd"}), c.name
 
 
