@@ -37,6 +37,7 @@ enum {
     PM_F8E5M2 = 4,           /* OCP FP8 e5m2: likewise */
     PM_Q8 = 5,               /* 8-bit quantised rows: a table FORMAT code of pm_embbag_fwd_anyfmt / pm_embedding_gather_anyfmt only (MIXED-FORMAT TABLES) */
     PM_Q4 = 6,               /* 4-bit quantised rows: likewise */
+    PM_MX4 = 7,              /* OCP MXFP4 rows: table element of pm_embbag_fwd_mx4 / pm_embedding_gather_mx4 only (MXFP4 TABLES) */
     PM_I32 = 10,
     PM_I64 = 11
 };
@@ -828,7 +829,7 @@ int pm_embedding_gather_f8_plan(const pm_embbag_batch* op, int64_t out[8]);
  * pm_embbag_f8_scaled_plan(op, out_dtype, mean, row_exponents 0 / 1, out[12]): the geometry the pooled call WOULD use: pm_embbag_f8_plan's,
  * except that the row exponents' LDS bytes (one per index-tile entry) drop the output burst (stage_out = 0) where the tile would pass
  * 64 KiB with it -- explicit weighted tiles of 512 bags and more.  The un-pooled call's geometry is pm_embedding_gather_f8_plan's.
- * Left out: scales that are not powers of two, MX block scales, FP8 output, a format per table, max pooling, pruning, any backward.
+ * Left out: scales that are not powers of two, MX block scales (MXFP4 TABLES has its own), FP8 output, a format per table, max pooling, pruning, any backward.
  * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these six finds out at symbol resolution.
  */
 int pm_f8_row_exponents(const void* src, int32_t src_dtype, int64_t n_rows, int32_t dim, int64_t src_row_stride, int32_t f8_dtype, int8_t* row_exp,
@@ -880,6 +881,72 @@ int pm_embbag_anyfmt_plan(const pm_embbag_batch* op, int32_t out_dtype, int32_t 
 int pm_embedding_gather_anyfmt(const pm_embbag_batch* op, const int32_t* table_formats, const int32_t* table_exp, int32_t out_dtype, void* out,
                                int64_t out_row_stride, pm_stream_t stream);
 int pm_embedding_gather_anyfmt_plan(const pm_embbag_batch* op, int64_t out[8]);
+
+/*
+ * MXFP4 TABLES -- the pooled and the un-pooled lookup over tables stored in OCP Microscaling FP4, and the quantiser that writes them:
+ * e2m1 elements that share a power-of-two E8M0 scale in blocks of 32 columns.  The scales sit INSIDE the row (one fetch per row where
+ * SCALED FP8 TABLES with row exponents take two), there is no bias, and a row with one outlier loses one block, not the row.  gfx950
+ * decodes the format in hardware.  op->weight_dtype is PM_MX4.
+ * DIMENSIONS: dims[t] % 32 == 0, dims[t] <= 2048.
+ * ELEMENT CODE: 4 bits s e e m -- 1 sign bit, 2 exponent bits (bias 1), 1 mantissa bit.  The magnitudes of codes 0 .. 7 are 0, 0.5, 1, 1.5,
+ * 2, 3, 4, 6; code 8 is -0.0; there is no NaN and no Inf among the codes.  The code of column c sits in byte c / 2 at bit 4 * (c % 2): the
+ * nibble order of ROW-QUANTISED TABLES' 4-bit rows and of torch.float4_e2m1fn_x2.
+ * BLOCK SCALE: one byte x per 32 consecutive columns, value 2^(x - 127); x == 255: every element of the block is NaN
+ * (torch.float8_e8m0fnu).
+ * ROW LAYOUT: D / 2 code bytes, then D / 32 scale bytes -- the scale of columns [32 k, 32 k + 32) at byte D / 2 + k --, zero-padded to
+ * row_bytes(D) = round_up(D / 2 + D / 32, 8): 72 bytes at D = 128, 24 at D = 32.  Rows lie back to back and tables[t] is 8-byte aligned, so
+ * every row, and every lane's 8-byte piece of codes, is naturally aligned.  A caller-chosen stride is left out.
+ * THE STORED VALUE: v = e2m1(code) * 2^(x - 127) with x in [2, 252], or NaN for x == 255.  In that range v is exact and normal in fp32 for
+ * all 16 codes (the smallest non-zero magnitude is 2^-126, the largest 6 * 2^125), so the rule depends neither on how a kernel forms v
+ * nor on the denormal mode; -0.0 is kept.  x in {0, 1, 253, 254} is outside the contract: the quantiser never writes it, the kernels need
+ * not define it (the Python module's copy_from_ refuses it).  A NaN's sign and payload are not part of the rule.
+ * THE RULE, pooled (pm_embbag_fwd_mx4): pm_embbag_fwd_f8's with v in the place of dec(code) and no padding_idx.  Per column, from acc = +0.0
+ * in index order, acc = acc + v -- with per_sample_weights acc = fmaf(w_j, v, acc).  mean == 1 (unweighted only): one correctly rounded
+ * fp32 division by the bag's length, none for an empty bag, which stays +0.0.  out_dtype PM_F32, or PM_BF16 / PM_F16: that fp32 value
+ * rounded ONCE, in registers; out is addressed like pm_embbag_fwd's in elements of out_dtype.  int32 / int64 indices, "bd" / "tbd"
+ * addressing, batch slices and mixed dims in one launch, as pm_embbag_fwd_f8.
+ * THE RULE, un-pooled (pm_embedding_gather_mx4): for every lookup position j that belongs to a bag inside the slice,
+ * out[j * out_row_stride + c] = conv(v), c < dims[t]; nothing else of out is touched.  fp32 output is exact; a 16-bit output is rounded
+ * once (fp16 may overflow or underflow).
+ * THE QUANTISER (pm_rows_quantize_mx4).  src: n_rows rows of dim columns of src_dtype (PM_F32 | PM_BF16 | PM_F16, widened exactly),
+ * src_row_stride elements apart; dst: n_rows rows of row_bytes(dim) bytes, 8-byte aligned.  Per block of 32 columns, on real numbers:
+ *   if any element is NaN or +-Inf, x = 255 (the block's code bytes are then not part of the rule);
+ *   otherwise, with amax the largest magnitude of the block: amax == 0 gives x = 2; else q = floor(log2(amax)), read from the fp32 exponent
+ *   field with integer arithmetic (an fp32-subnormal amax counts as q = -127), and x = clamp(q - 2 + 127, 2, 252) -- the upper clamp never
+ *   binds for fp32 input, the lower one does;
+ *   the code of element y = x_c * 2^(127 - x) is its sign and the e2m1 magnitude nearest to |y|; a tie goes to the magnitude whose code is
+ *   even (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4); |y| > 6 gives 6 (|y| < 8 always holds above the lower
+ *   clamp); -0.0 and negative values that round to zero keep their sign bit.  Pad bytes are written as zeros.
+ * This is the OCP MX v1.0 conversion (shared exponent = floor(log2 amax) - emax_elem, round to nearest even, saturating) with the scale
+ * clamped into the normal range.
+ * Kernels: csrc/mx4_quantize.hip (the source is read once: 8 lanes -- 4 for a 16-bit source -- own a block with one 16-byte load each,
+ * amax is an integer maximum over a fixed butterfly and carries the non-finite flag, the codes are exchanged inside the block so that
+ * they leave as 8-byte stores of consecutive bytes), csrc/embbag_fwd_mx4.hip (the FP8 kernel's tiling; a lane owns 16 columns = one
+ * 8-byte load, a lane pair shares a scale byte that is loaded with the codes, 2 / 4 rows in flight) and csrc/embedding_gather_mx4.hip
+ * (pm_embedding_gather's tiles with four columns per lane).  Decode and encode are gfx950's v_cvt_scalef32_pk_f32_fp4 /
+ * v_cvt_scalef32_pk_fp4_f32 (csrc/mx4_elem.h; -DPM_MX4_SOFT_DECODE / -DPM_MX4_SOFT_ENCODE build the integer paths).  No atomics, no
+ * workspace, no allocation, stream-ordered; 64-bit row addressing.
+ * Refused on the host, before any HIP call: what pm_embbag_fwd / pm_embedding_gather refuse about a request; a weight_dtype other than
+ * PM_MX4 (PM_ERR_INVALID); max_dim or min_dim not a multiple of 32, max_dim > 2048, a non-zero table_group / grad_block_shift /
+ * grad_block_extra (PM_ERR_UNSUPPORTED); an unknown out_dtype, mean not 0 / 1 (PM_ERR_INVALID); per_sample_weights with mean == 1 or for
+ * the gather (PM_ERR_UNSUPPORTED); out_row_stride < max_dim or not a multiple of 4 (PM_ERR_INVALID).  An empty request (bag_count == 0;
+ * the gather: num_indices == 0 as well) is then PM_OK without a launch; otherwise a NULL out, or one that is not 16-byte (PM_F32) / 8-byte
+ * (16-bit) aligned, is PM_ERR_INVALID.  The quantiser: a src_dtype other than the three, a negative n_rows (PM_ERR_INVALID); dim not a
+ * multiple of 32 or above 2048 (PM_ERR_UNSUPPORTED); src_row_stride below dim or not a whole number of 16-byte pieces; then, unless
+ * n_rows == 0 (PM_OK without a launch), a NULL or not 16-byte aligned src, a NULL or not 8-byte aligned dst (PM_ERR_INVALID).  Every
+ * other entry point keeps refusing PM_MX4.
+ * pm_embbag_mx4_plan / pm_embedding_gather_mx4_plan: the geometry the two calls WOULD use (plan_mx4, plan_gather_mx4, csrc/launch_plan.h)
+ * -- the twelve members of pm_embbag_plan (unroll 2 / 4: pm_set_tuning's unroll, below 4 -> 2; default 2) and the eight of
+ * pm_embedding_gather_plan (vec = 4) in their order.  Host only; they validate the request as the launching calls do.
+ * Left out: padding_idx, max pooling, pruning, membership in the mixed-format launch, MXFP6 / MXFP8, NVFP4-style fp8 scales, a
+ * caller-chosen row stride, MX4 in the quantised all-to-all, any backward.
+ * The request struct is unchanged (sizeof 144) and the ABI version stays 8: a client that needs these five finds out at symbol resolution.
+ */
+int pm_rows_quantize_mx4(const void* src, int32_t src_dtype, int64_t n_rows, int32_t dim, int64_t src_row_stride, void* dst, pm_stream_t stream);
+int pm_embbag_fwd_mx4(const pm_embbag_batch* op, int32_t mean, int32_t out_dtype, void* out, pm_stream_t stream);
+int pm_embbag_mx4_plan(const pm_embbag_batch* op, int32_t out_dtype, int32_t out[12]);
+int pm_embedding_gather_mx4(const pm_embbag_batch* op, int32_t out_dtype, void* out, int64_t out_row_stride, pm_stream_t stream);
+int pm_embedding_gather_mx4_plan(const pm_embbag_batch* op, int64_t out[8]);
 
 /*
  * SEQUENCE GRADIENTS -- the batched backward of the un-pooled lookup above: the gradient of pm_embedding_gather's rows applied to all

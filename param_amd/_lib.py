@@ -113,11 +113,18 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_anyfmt_plan",
     "pm_embedding_gather_anyfmt",
     "pm_embedding_gather_anyfmt_plan",
+    "pm_rows_quantize_mx4",
+    "pm_embbag_fwd_mx4",
+    "pm_embbag_mx4_plan",
+    "pm_embedding_gather_mx4",
+    "pm_embedding_gather_mx4_plan",
 )
 # table element types of the FP8 lookups alone (include/param_amd.h, FP8 TABLES): every other entry point refuses them
 PM_F8E4M3, PM_F8E5M2 = 3, 4
 # table FORMAT codes of the mixed-format lookups alone (include/param_amd.h, MIXED-FORMAT TABLES): 8- and 4-bit quantised rows
 PM_Q8, PM_Q4 = 5, 6
+# table element type of the MXFP4 lookups alone (include/param_amd.h, MXFP4 TABLES): every other entry point refuses it
+PM_MX4 = 7
 
 # pm_embbag_plan (include/param_amd.h): the kinds, and the members of the two plans in the order the queries fill them
 PM_PLAN_BASE, PM_PLAN_FORWARD, PM_PLAN_QUANTIZED, PM_PLAN_PADDED, PM_PLAN_PADDED16 = 0, 1, 2, 3, 4
@@ -391,6 +398,17 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embbag_f8_scaled_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, i32, i32, ctypes.POINTER(i32)]
     L.pm_embedding_gather_f8_scaled.restype = ctypes.c_int
     L.pm_embedding_gather_f8_scaled.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, vp, vp, vp, i64, vp]
+    # MXFP4 tables: the quantiser (src, src_dtype, n_rows, dim, src_row_stride, dst, stream), then the lookups and their plans
+    L.pm_rows_quantize_mx4.restype = ctypes.c_int
+    L.pm_rows_quantize_mx4.argtypes = [vp, i32, i64, i32, i64, vp, vp]
+    L.pm_embbag_fwd_mx4.restype = ctypes.c_int
+    L.pm_embbag_fwd_mx4.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, i32, vp, vp]
+    L.pm_embbag_mx4_plan.restype = ctypes.c_int
+    L.pm_embbag_mx4_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, ctypes.POINTER(i32)]
+    L.pm_embedding_gather_mx4.restype = ctypes.c_int
+    L.pm_embedding_gather_mx4.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, vp, i64, vp]
+    L.pm_embedding_gather_mx4_plan.restype = ctypes.c_int
+    L.pm_embedding_gather_mx4_plan.argtypes = [ctypes.POINTER(pm_embbag_batch), ctypes.POINTER(i64)]
     if alternates:
         L.pm_embbag_bwd.restype = ctypes.c_int
         L.pm_embbag_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, i32, ctypes.c_float, vp]
@@ -507,6 +525,20 @@ def embedding_gather_f8_plan(op: pm_embbag_batch) -> dict:
     out = (ctypes.c_int64 * len(GATHER_PLAN_FIELDS))()
     check(load().pm_embedding_gather_f8_plan(ctypes.byref(op), out))
     return dict(zip(GATHER_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def embbag_mx4_plan(op: pm_embbag_batch, out_dtype: int = PM_F32) -> dict:
+    """``pm_embbag_mx4_plan``: the geometry ``pm_embbag_fwd_mx4`` would use for ``op`` -- ``PLAN_FIELDS`` by name"""
+    out = (ctypes.c_int32 * 12)()
+    check(load().pm_embbag_mx4_plan(ctypes.byref(op), int(out_dtype), out))
+    return dict(zip(PLAN_FIELDS, out))
+
+
+def embedding_gather_mx4_plan(op: pm_embbag_batch) -> dict:
+    """``pm_embedding_gather_mx4_plan``: the geometry ``pm_embedding_gather_mx4`` would use for ``op`` -- ``GATHER_PLAN_FIELDS`` by name"""
+    out = (ctypes.c_int64 * 8)()
+    check(load().pm_embedding_gather_mx4_plan(ctypes.byref(op), out))
+    return dict(zip(GATHER_PLAN_FIELDS, out))
 
 
 def set_backward_tuning(sort_impl: int = -1, order: int = -1, xcd_affine: int = -1, max_phases: int = -1) -> None:

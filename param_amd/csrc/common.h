@@ -297,6 +297,12 @@ hipError_t launch_f8_row_exponents(const void* src, int src_dtype, int64_t n_row
                                    hipStream_t stream);
 hipError_t launch_rows_quantize_f8(const void* src, int src_dtype, int64_t n_rows, int dim, int64_t stride, int f8_dtype, const int32_t* table_exp,
                                    const int8_t* row_exp, void* dst, hipStream_t stream);
+// MXFP4 tables (embbag_fwd_mx4.hip, embedding_gather_mx4.hip, mx4_quantize.hip): p = plan_mx4's geometry, p.io = out of out_dtype
+// addressed in its elements, unroll 2 / 4; g: plan_gather_mx4's; the quantiser: src of src_dtype with a row stride in elements, dst the
+// table's rows (mx4_elem.h: row_bytes(dim) each)
+hipError_t launch_embbag_fwd_mx4(const KParams& p, int max_dim, int unroll, bool mean, int out_dtype, hipStream_t stream);
+hipError_t launch_embedding_gather_mx4(const KParams& p, int out_dtype, const GatherPlan& g, hipStream_t stream);
+hipError_t launch_rows_quantize_mx4(const void* src, int src_dtype, int64_t n_rows, int dim, int64_t stride, void* dst, hipStream_t stream);
 
 // sort-based deterministic backward (embbag_bwd_sorted.hip)
 hipError_t sorted_workspace_bytes(const KParams& p, int64_t max_rows, int max_dim, size_t& bytes);

@@ -690,4 +690,44 @@ static inline GatherPlan plan_gather_f8(const pm_embbag_batch& op, const PlanKno
     return g;
 }
 
+// ---- MXFP4 tables: pm_embbag_fwd_mx4 (embbag_fwd_mx4.hip) and pm_embedding_gather_mx4 (embedding_gather_mx4.hip) -------------------------
+// Half a byte per column and one scale byte per 32: a lane of the pooled kernel holds SIXTEEN columns = one 8-byte load of codes (and its
+// block's scale byte), so the lane group is the FP8 kernel's, group_lanes(max_dim, 16) -- 8 lanes up to D = 128, 64 lanes at D = 1024, two
+// column passes at kMx4MaxDim = 2048 -- and the plan is plan_f8's tiling (plan_qrows for that lane) with this kernel's own rows in
+// flight: 2 or 4 (pm_set_tuning's unroll: below 4 -> 2, from 4 on -> 4).  tools/mx4_probe.py, 16 x 10 M x 128, batch 8192, pooling 20,
+// fp32 output, us per call, medians of 5 windows of one process, spread <= 0.2 % (profiles/mx4_probe.json); 2 / 4 rows in flight:
+//   uniform indices 108.2 / 107.8      Zipf 1.05  55.4 / 58.0
+// (the run whose default was four, profiles/mx4_probe_unroll4_default.json: 107.9 / 107.8 and 55.3 / 58.1)
+// Two is the default, as in the FP8 kernel (kF8Unroll): the 4-bit row-quantised kernel's four (kQrowsUnroll) does not carry over.
+constexpr int kMx4Unroll = 2;
+constexpr int kMx4MaxDim = 2048;
+constexpr int kMx4LaneColumns = 16;
+static inline PlanShape mx4_shape(const pm_embbag_batch& op, const PlanKnobs& k) { return lane_columns_shape(op, kMx4LaneColumns, k); }
+static inline LaunchPlan plan_mx4(const pm_embbag_batch& op, const PlanShape& s, const PlanKnobs& k, int out_bytes) {
+    LaunchPlan p = plan_qrows(op, s, k, out_bytes);
+    const int u = k.unroll != 0 ? k.unroll : kMx4Unroll;
+    p.unroll = u >= 4 ? 4 : 2;
+    return p;
+}
+static inline LaunchPlan plan_mx4(const pm_embbag_batch& op, const PlanKnobs& k, int out_bytes) { return plan_mx4(op, mx4_shape(op, k), k, out_bytes); }
+
+// The un-pooled lookup: plan_gather_f8's argument and geometry -- FOUR columns per lane (two bytes of codes), so that a lane's decoded
+// columns are exactly one 16-byte (fp32) / 8-byte (16-bit) piece and every store instruction of a lane group writes consecutive pieces of
+// the output row; G = group_lanes(max_dim, 4), column passes of 256 columns above.  Rows in flight: plan_gather's rounding and default.
+constexpr int kMx4GatherLaneColumns = 4;
+constexpr int kMx4GatherUnroll = 8;
+static inline GatherPlan plan_gather_mx4(const pm_embbag_batch& op, const PlanKnobs& k) {
+    GatherPlan g = {};
+    g.vec = kMx4GatherLaneColumns;
+    g.group_lanes = group_lanes(op.max_dim, g.vec);
+    g.tile = kBlock;
+    g.col_passes = static_cast<int32_t>(ceil_div(op.max_dim, static_cast<int64_t>(g.group_lanes) * g.vec));
+    const int u = k.unroll != 0 ? k.unroll : kMx4GatherUnroll;
+    g.unroll = u >= 8 ? 8 : (u >= 4 ? 4 : (u >= 2 ? 2 : 1));
+    g.lds_borders = op.num_tables + 1 <= kGatherLdsBorders ? 1 : 0;
+    g.xcd_contiguous = (op.num_tables > 1 && k.xcd_affine != 0) ? 1 : 0;
+    g.grid = ceil_div(op.num_indices, g.tile);
+    return g;
+}
+
 }  // namespace pm
