@@ -552,6 +552,46 @@ int pm_embbag_max_grad(const pm_embbag_batch* op, const void* grad, int32_t grad
                        int64_t g_seq_row_stride, pm_stream_t stream);
 
 /*
+ * MAX POOLING, DIRECT BACKWARD -- the same gradient applied from the [B, sum D]-sized grad through max_indices, without the [N, D]
+ * expansion (csrc/embbag_max_bwd.hip).  Mixed dims are taken.  ABI version and request struct unchanged.  tests/max_direct_rules.py
+ * restates the rule in numpy.
+ *
+ * RULE      For table t, row r, column c: W(t, r, c) = the bags b of the slice with max_indices(t, b)[c] == r, ascending.  A bag counts
+ *           once however often it holds r; -1 matches nothing; a padding row is never an arg-max, so nothing lands on one and no guard
+ *           is needed.  G = the sum of grad(t, b)[c] over W in fp32, one addition after the other in ascending bag order, starting
+ *           from the first term (not from 0.0).  W empty: dst[r, c] is not read, not written and keeps its bits -- a -0.0, a NaN
+ *           payload or a subnormal of a looked-up row that wins no column stays; THE STATED DIFFERENCE to the expansion route, which adds
+ *           alpha * 0.0 there.  Otherwise dst[r, c] = round_dst(fl32(widen(dst[r, c]) + fl32(alpha * G))): one multiplication, one
+ *           addition, no FMA, one rounding for a 16-bit destination (a 16-bit destination is stored four columns at a time: columns of
+ *           the four that did not win are stored back as read).  A 16-bit grad is widened exactly, in registers.
+ * EXACTNESS A row's RUN is its lookups in the slice, in lookup order (its pairs in the request's key sort).  A run of at most 256
+ *           lookups (kExactRun) is summed in exactly the sequential order above: torch's CPU _embedding_bag_dense_backward for max, bit
+ *           for bit.  A longer run is cut into PIECES of 256 lookups counted from the run's first lookup -- piece k holds the run's
+ *           lookups [256 k, 256 k + 256), repeats of a bag included in the count; a bag whose repeats straddle a cut belongs to the
+ *           piece of its first lookup.  Per column, every piece is summed sequentially starting from its own first term, and the pieces
+ *           that have a term are added in ascending k starting from the first such piece.  The association is a function of the request
+ *           alone -- not of the grid, a tunable or timing -- so two calls give the same bits.
+ *
+ * pm_embbag_max_bwd_workspace  bytes of caller-owned device scratch: pm_embbag_bwd_sorted_workspace of the request, then a list of hot
+ *                              runs and two fp32 partial rows (with their won masks) per 256 lookups: about num_indices * max_dim / 25
+ *                              bytes beyond the sort's, against num_indices * max_dim * 4 for the expansion.
+ * pm_embbag_max_bwd            sort + apply in one call: pm_embbag_sort_indices (one phase; it never defers) on the workspace, then at
+ *                              most two launches for up to 1024 tables -- the main kernel over tiles of the sorted pairs, which finishes
+ *                              every run of at most 256 lookups (one row, one owner, no atomics on a destination), and a small kernel
+ *                              that adds the pieces of the longer runs in order.  grad (grad_dtype PM_F32 | PM_BF16 | PM_F16) and
+ *                              max_indices are addressed like the forward's out; dst_tables: device array [T] of destinations of
+ *                              dst_dtype (PM_F32 | PM_BF16 | PM_F16) with the tables' shapes.  Only bags inside the slice contribute.
+ * Refused before any launch: what pm_embbag_max_grad refuses of the request (per_sample_weights and blocked layouts PM_ERR_UNSUPPORTED,
+ * an unknown dtype PM_ERR_INVALID); num_indices or batch >= 2^32, more than 1024 tables (PM_ERR_UNSUPPORTED); a NULL grad / max_indices
+ * / dst_tables, grad not 16-byte (8-byte for 16 bits) or max_indices not 16-byte aligned, a NULL, misaligned or too small workspace
+ * (PM_ERR_INVALID).  num_indices == 0 or bag_count == 0 is PM_OK without a launch.
+ * Left out: per_sample_weights, blocked layouts, the fused optimizers.
+ */
+int64_t pm_embbag_max_bwd_workspace(const pm_embbag_batch* op, int64_t max_rows);
+int pm_embbag_max_bwd(const pm_embbag_batch* op, const void* grad, int32_t grad_dtype, const int32_t* max_indices, void* const* dst_tables,
+                      int32_t dst_dtype, float alpha, int64_t max_rows, void* workspace, int64_t workspace_bytes, pm_stream_t stream);
+
+/*
  * UN-POOLED LOOKUPS -- torch's nn.Embedding rule (fbgemm TBE: PoolingMode.NONE, sequence embeddings): one output row per lookup.  For
  * every lookup position j in [0, num_indices) that belongs to a bag inside [bag_begin, bag_begin + bag_count) of its table t
  *     out[j * out_row_stride + c] = conv(table_t[indices[j], c])      for c < dims[t]

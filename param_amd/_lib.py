@@ -82,6 +82,8 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_grad_widen",
     "pm_embbag_fwd_max",
     "pm_embbag_max_grad",
+    "pm_embbag_max_bwd_workspace",
+    "pm_embbag_max_bwd",
     "pm_embedding_gather",
     "pm_embseq_sort_indices",
     "pm_embseq_bwd_sorted",
@@ -327,6 +329,12 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embbag_fwd_max.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, vp, vp, vp]
     L.pm_embbag_max_grad.restype = ctypes.c_int
     L.pm_embbag_max_grad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, vp, vp, i64, vp]
+    # ... its direct backward: (op, max_rows) and (op, grad, grad dtype, max_indices, dst_tables, dst dtype, alpha, max_rows, workspace,
+    # workspace_bytes, stream)
+    L.pm_embbag_max_bwd_workspace.restype = ctypes.c_int64
+    L.pm_embbag_max_bwd_workspace.argtypes = [ctypes.POINTER(pm_embbag_batch), i64]
+    L.pm_embbag_max_bwd.restype = ctypes.c_int
+    L.pm_embbag_max_bwd.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, vp, vp, i32, ctypes.c_float, i64, vp, i64, vp]
     # un-pooled rows: (op, PM_F32 | PM_BF16 | PM_F16, out, out_row_stride, stream)
     L.pm_embedding_gather.restype = ctypes.c_int
     L.pm_embedding_gather.argtypes = [ctypes.POINTER(pm_embbag_batch), i32, vp, i64, vp]

@@ -1762,6 +1762,56 @@ int pm_embbag_sparse_grad(const pm_embbag_batch* op, const float* grad, int64_t 
     return PM_OK;
 }
 
+// ---- direct backward of max pooling (embbag_max_bwd.hip) ------------------------------------------------------------------------------
+// The workspace is the sorted backward's followed by the hot-run list and the piece partials.
+// what both calls refuse of the request; dst_dtype: the element type the rows are updated as
+static int max_bwd_request(const pm_embbag_batch* op, int32_t dst_dtype, int32_t grad_dtype, int64_t max_rows, pm::KParams& p) {
+    int rc = make_params(op, dst_dtype, p);
+    if (rc != PM_OK) return rc;
+    if ((rc = max_args_ok(op, grad_dtype, "grad_dtype")) != PM_OK) return rc;
+    return sorted_args_ok(op, max_rows);
+}
+
+static int max_bwd_bytes(const pm_embbag_batch* op, int64_t max_rows, const pm::KParams& p, size_t& sorted, size_t& total) {
+    const int rc = sorted_bytes("pm_embbag_max_bwd_workspace", op, max_rows, false, p, sorted, total);
+    if (rc != PM_OK) return rc;
+    sorted = (sorted + 255) / 256 * 256;
+    total = sorted + pm::max_bwd_extra_bytes(p.N, op->max_dim);
+    return PM_OK;
+}
+
+int64_t pm_embbag_max_bwd_workspace(const pm_embbag_batch* op, int64_t max_rows) {
+    pm::KParams p;
+    size_t sorted = 0, total = 0;
+    int rc = max_bwd_request(op, op ? op->weight_dtype : -1, PM_F32, max_rows, p);
+    if (rc != PM_OK || (rc = max_bwd_bytes(op, max_rows, p, sorted, total)) != PM_OK) return rc;
+    return static_cast<int64_t>(total);
+}
+
+int pm_embbag_max_bwd(const pm_embbag_batch* op, const void* grad, int32_t grad_dtype, const int32_t* max_indices, void* const* dst_tables,
+                      int32_t dst_dtype, float alpha, int64_t max_rows, void* workspace, int64_t workspace_bytes, pm_stream_t stream) {
+    pm::KParams p;
+    int rc = max_bwd_request(op, dst_dtype, grad_dtype, max_rows, p);
+    if (rc != PM_OK) return rc;
+    if (p.N == 0 || p.bag_count == 0) return PM_OK;
+    if (!grad || !max_indices || !dst_tables) return fail(PM_ERR_INVALID, "grad / max_indices / dst_tables is NULL");
+    if (reinterpret_cast<uintptr_t>(grad) % (grad_dtype == PM_F32 ? 16 : 8) != 0 || reinterpret_cast<uintptr_t>(max_indices) % 16 != 0)
+        return fail(PM_ERR_INVALID, "grad must be 16-byte aligned (8-byte for a 16-bit grad_dtype), max_indices 16-byte aligned");
+    size_t sorted = 0, need = 0;
+    if ((rc = max_bwd_bytes(op, max_rows, p, sorted, need)) != PM_OK) return rc;
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 16 != 0 || workspace_bytes < static_cast<int64_t>(need))
+        return fail(PM_ERR_INVALID, "workspace must be 16-byte aligned and hold " + std::to_string(need) + " bytes (pm_embbag_max_bwd_workspace)");
+    // the complete one-phase key sort of the request: issued on its own, it never defers
+    if ((rc = sort_request(op, max_rows, 1, workspace, workspace_bytes, stream, false)) != PM_OK) return rc;
+    pm::MaxBwdPairs mp;
+    if ((rc = plan_fail(pm::max_bwd_pairs(p, max_rows, op->max_dim, workspace, mp), "")) != PM_OK) return rc;
+    p.tables = static_cast<const void* const*>(static_cast<const void*>(dst_tables));
+    const hipError_t h = pm::launch_max_bwd(p, op->max_dim, mp, static_cast<char*>(workspace) + sorted, grad, grad_dtype, max_indices, dst_dtype,
+                                            alpha, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_max_bwd launch");
+    return PM_OK;
+}
+
 int pm_dlrm_regroup(const int64_t* lengths, const int64_t* indices, int32_t world_size, int32_t num_tables,
                     int64_t batch, int64_t* out_indices, int64_t* out_offsets, int64_t* scratch, pm_stream_t stream) {
     if (world_size < 1 || num_tables < 1 || batch < 0) return fail(PM_ERR_INVALID, "world_size / num_tables / batch");

@@ -527,6 +527,20 @@ hipError_t sparse_grad_count(const SparsePairs& sp, int T, int64_t n, void* extr
 hipError_t sparse_grad_rows(const SparsePairs& sp, int T, int64_t n, const void* extra, const int32_t* dims, int64_t* const* row_ids,
                             float* const* values, hipStream_t stream);
 
+// direct backward of max pooling (embbag_max_bwd.hip): the pairs of the complete pooled, unweighted key sort last issued on a workspace,
+// and the sorted apply's four control words, which that sort's first kernel zeroes (ctl[0] counts the hot runs the main kernel lists)
+struct MaxBwdPairs {
+    const void* keys;
+    const uint32_t* vals;
+    const uint32_t* d_count;
+    uint32_t* ctl;
+    int key_bytes, tshift;
+};
+PlanStatus max_bwd_pairs(const KParams& p, int64_t max_rows, int max_dim, const void* workspace, MaxBwdPairs& out);
+size_t max_bwd_extra_bytes(int64_t n, int max_dim);   // behind the sorted backward's workspace: hot-run list, piece partials
+hipError_t launch_max_bwd(const KParams& p, int max_dim, const MaxBwdPairs& mp, void* extra, const void* grad, int grad_dtype,
+                          const int32_t* max_indices, int dst_dtype, float alpha, hipStream_t stream);
+
 // DLRM input redistribution (dlrm_regroup.hip)
 hipError_t launch_dlrm_regroup(const int64_t* lengths, const int64_t* indices, int W, int F, int64_t B,
                                int64_t* out_indices, int64_t* out_offsets, int64_t* scratch, hipStream_t stream);

@@ -472,6 +472,26 @@ PlanStatus sparse_grad_pairs(const KParams& p, int64_t max_rows, int max_dim, co
     return PlanStatus::ok;
 }
 
+PlanStatus max_bwd_pairs(const KParams& p, int64_t max_rows, int max_dim, const void* workspace, MaxBwdPairs& out) {
+    SortPlan g;
+    const PlanStatus st = find_plan(workspace, p, max_rows, true, g, [&](SortPlan& r) {
+        if (r.sequence) return PlanStatus::sequence_sort;
+        if (r.relabelled) return PlanStatus::relabelled;
+        if (!r.v2 || r.hyb || r.H != 1 || r.weighted) return PlanStatus::not_complete_segmented;
+        return PlanStatus::ok;
+    });
+    if (st != PlanStatus::ok) return st;
+    const SortWs ws = ws_layout(p, max_rows, max_dim, g.weighted, const_cast<void*>(workspace));
+    if (ws.rc != hipSuccess) return PlanStatus::none;
+    out.keys = g.in_b ? ws.keys_b : ws.keys_a;
+    out.vals = g.in_b ? ws.vals_b : ws.vals_a;
+    out.d_count = seg_sort_view(ws.temp, static_cast<size_t>(p.N), p.T).n_total;
+    out.ctl = ws.fix_ctl;
+    out.key_bytes = g.key_bytes;
+    out.tshift = g.tshift;
+    return PlanStatus::ok;
+}
+
 PlanStatus sorted_pairs_info(const KParams& p, int64_t max_rows, int max_dim, const void* workspace, SortedPairsInfo& out) {
     SortPlan g;
     if (find_plan(workspace, p, max_rows, false, g, [](SortPlan&) { return PlanStatus::ok; }) != PlanStatus::ok) return PlanStatus::none;

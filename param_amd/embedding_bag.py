@@ -358,7 +358,9 @@ def _fwd_max(ts: _TableSet, indices, offsets, B, out=None, bag_begin=0, bag_coun
     return out, arg
 
 
-_MAX_MIXED = "the gradient of max pooling needs one common embedding dim (it is applied by the sequence backward, which takes one)"
+_MAX_MIXED = ('the gradient of max pooling needs one common embedding dim (it is applied by the sequence backward, which takes one); '
+              'method="direct" takes mixed dims')
+_DIRECT_NEEDS_MAX = 'method="direct" is the direct backward of max pooling (MaxBatchedEmbeddingBagMI355)'
 
 
 def _max_expand(ts: _TableSet, grad, max_indices, indices, offsets, B, bag_begin=0, bag_count=None,
@@ -407,6 +409,34 @@ def _max_bwd(ts: _TableSet, grad, indices, offsets, B, dst_ptrs_dev, dst_dtype, 
                                                     ws.data_ptr(), ws.numel(), s)
     _seq_bwd(ts, g_seq, indices, offsets, B, bag_begin, bag_count, False, call(L.pm_embseq_bwd_fused), call(L.pm_embseq_bwd_sorted),
              _PadGuard(ts, pad, dst_ptrs_dev, dst_dtype))
+
+
+def _max_bwd_direct(ts: _TableSet, grad, indices, offsets, B, dst_ptrs_dev, dst_dtype, alpha, pad: Optional[torch.Tensor] = None,
+                    max_indices=None, bag_begin=0, bag_count=None, out16: Optional[torch.dtype] = None) -> None:
+    """The backward of a MAX-pooled forward on its own apply kernel (``pm_embbag_max_bwd``; rule in include/param_amd.h, MAX POOLING,
+    DIRECT BACKWARD): the pooled key sort of the request, then ``grad`` -- fp32 or the module's 16-bit ``out16`` -- is applied through
+    ``max_indices`` from its own ``[B, sum D]``-sized buffer.  Nothing of ``N x D`` is allocated, mixed dims are taken, and a looked-up row
+    that wins no column is neither read nor written.  No pad guard: a padding row is never an arg-max, so no contribution can land on
+    one (``pad`` only feeds the forward that recomputes ``max_indices`` when it is ``None``).  One call per range of at most 1024 tables,
+    sharing the cached workspace."""
+    if ts.layout == "blocked":
+        raise ValueError('max pooling is not supported with layout="blocked"')
+    grad = _check_grad(ts, grad, B, out16)
+    if max_indices is None:
+        _, max_indices = _fwd_max(ts, indices, offsets, B, None, bag_begin, bag_count, pad, None, True)
+    elif (max_indices.dtype != torch.int32 or tuple(max_indices.shape) != tuple(grad.shape) or not max_indices.is_contiguous() or
+          max_indices.device != ts.device):
+        raise ValueError(f"max_indices must be a contiguous int32 tensor of shape {tuple(grad.shape)} on {ts.device}")
+    if not indices.numel():
+        return
+    op = ts.request(indices, offsets, B, None, bag_begin, bag_count)
+    op.fixed_pooling = 0
+    L, s = _lib.load(), _stream_ptr()
+    for sub, t0, _, max_rows in _table_chunks(ts, op, indices, offsets, B):
+        ws = _workspace(ts, sub, max_rows, L.pm_embbag_max_bwd_workspace)
+        _lib.check(L.pm_embbag_max_bwd(ctypes.byref(sub), grad.data_ptr(), _WDTYPE[grad.dtype], max_indices.data_ptr(),
+                                       dst_ptrs_dev.data_ptr() + 8 * t0, _WDTYPE[dst_dtype], float(alpha), max_rows, ws.data_ptr(), ws.numel(), s))
+        _sort_issued(ts, ws)
 
 
 def _fwd_quantized(ts: _TableSet, indices, offsets, B, bitwidth: int, psw=None, out=None, bag_begin=0, bag_count=None):
@@ -1779,10 +1809,10 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
         """what the two gradient calls of a max module refuse, on the host and before anything is launched"""
         if per_sample_weights is not None:
             raise ValueError(_MAX_WEIGHTED)
-        if method != "sorted" or presorted:
-            raise ValueError(f'{what} with pooling_mode="max" runs the sequence backward on the expanded gradient: method="atomic" and '
-                             "presorted=True are not taken")
-        if len(set(self.dims)) != 1:
+        if method not in ("sorted", "direct") or presorted:
+            raise ValueError(f'{what} with pooling_mode="max" runs the sequence backward on the expanded gradient (method="sorted") or the '
+                             'direct apply (method="direct"): method="atomic" and presorted=True are not taken')
+        if method == "sorted" and len(set(self.dims)) != 1:
             raise ValueError(_MAX_MIXED)
 
     def scatter_add_(self, grad, indices, offsets, alpha: float, per_sample_weights=None,
@@ -1797,11 +1827,13 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             self._max_grad_args("scatter_add_", per_sample_weights, method, presorted)
         elif max_indices is not None:
             raise ValueError('max_indices needs max pooling (MaxBatchedEmbeddingBagMI355)')
+        elif method == "direct":
+            raise ValueError(_DIRECT_NEEDS_MAX)
         ts = self._tables()
         B = self._batch(offsets, indices, batch)
         if self._max:
-            _max_bwd(ts, grad, indices, offsets, B, ts.d_ptrs, self.weights.dtype, alpha, self._pad_dev(), max_indices, bag_begin, bag_count,
-                     self._out16)
+            (_max_bwd_direct if method == "direct" else _max_bwd)(ts, grad, indices, offsets, B, ts.d_ptrs, self.weights.dtype, alpha,
+                                                                  self._pad_dev(), max_indices, bag_begin, bag_count, self._out16)
             return
         _bwd(ts, grad, indices, offsets, B, ts.d_ptrs, self.weights.dtype, alpha, per_sample_weights,
              bag_begin, bag_count, method, presorted, pooling, pad=self._pad_dev(), mean=self._mean, out16=self._out16)
@@ -1880,11 +1912,14 @@ class BatchedEmbeddingBagMI355(nn.Module, _BoundsChecked):
             self._max_grad_args("dense_grad", per_sample_weights, method)
         elif max_indices is not None:
             raise ValueError('max_indices needs max pooling (MaxBatchedEmbeddingBagMI355)')
+        elif method == "direct":
+            raise ValueError(_DIRECT_NEEDS_MAX)
         ts = self._tables()
         B = self._batch(offsets, indices, batch)
         outs, d_ptrs = self._dense_grad_buffers(ts, out)
         if self._max:
-            _max_bwd(ts, grad, indices, offsets, B, d_ptrs, torch.float32, 1.0, self._pad_dev(), max_indices, out16=self._out16)
+            (_max_bwd_direct if method == "direct" else _max_bwd)(ts, grad, indices, offsets, B, d_ptrs, torch.float32, 1.0, self._pad_dev(),
+                                                                  max_indices, out16=self._out16)
             return outs
         _bwd(ts, grad, indices, offsets, B, d_ptrs, torch.float32, 1.0, per_sample_weights, method=method, pad=self._pad_dev(),
              mean=self._mean, out16=self._out16)
