@@ -4,7 +4,8 @@
 //         which prints the eight members of pm::GatherPlan instead; 6 / 7 the FP8 pooled lookup with 4- / 2-byte output elements;
 //         8 the FP8 row gather, eight members as 5 -- for 6 .. 8 dtype is PM_F8E4M3 / PM_F8E5M2; the scaled FP8 lookups plan on 6 .. 8
 //         too, their pooled plan being plan_f8 followed by f8s_stage_out, which tests/plan_sweep.py restates;
-//         9 / 10 the mixed-format pooled lookup with 4- / 2-byte output elements; 11 the mixed-format row gather, eight members as 5)
+//         9 / 10 the mixed-format pooled lookup with 4- / 2-byte output elements; 11 the mixed-format row gather, eight members as 5;
+//         12 / 13 the MXFP4 pooled lookup with 4- / 2-byte output elements; 14 the MXFP4 row gather, eight members as 5 -- dtype is PM_MX4)
 //   the request: num_tables batch num_indices bag_begin bag_count max_dim min_dim dtype weighted table_group grad_block_shift grad_block_extra
 //   what the setters were given: unroll bags_per_block xcd_affine nt_loads | stage_out flat_grid flat_target
 //   the environment's values: stage flat flat_maxl flat_target flat_bags tile_major flat_compact
@@ -76,6 +77,14 @@ int main() {
             case 10: p = pm::plan_anyfmt(op, pm::anyfmt_shape(op, k), k, 2); break;
             case 11: {
                 const pm::GatherPlan g = pm::plan_gather_anyfmt(op, k);
+                printf("%d %d %d %d %d %d %d %lld\n", g.vec, g.group_lanes, g.tile, g.col_passes, g.unroll, g.lds_borders, g.xcd_contiguous,
+                       static_cast<long long>(g.grid));
+                continue;
+            }
+            case 12: p = pm::plan_mx4(op, k, 4); break;
+            case 13: p = pm::plan_mx4(op, k, 2); break;
+            case 14: {
+                const pm::GatherPlan g = pm::plan_gather_mx4(op, k);
                 printf("%d %d %d %d %d %d %d %lld\n", g.vec, g.group_lanes, g.tile, g.col_passes, g.unroll, g.lds_borders, g.xcd_contiguous,
                        static_cast<long long>(g.grid));
                 continue;

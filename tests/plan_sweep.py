@@ -17,7 +17,9 @@ one's plan is ``plan_f8`` followed by the launcher's LDS rule, which ``f8s_out_o
 here and ``pinned_plan`` applies to the dumped row -- group ``f8s_edge`` sits on both sides of the one corner where the row exponents'
 bytes cost a tile its burst.  The mixed-format entries (``anyfmt``, ``anyfmt_gather``) add ``formats``, one stored format per table; they
 take no padding row and read the padded requests' indices as plain indices, and ``anyfmt_label`` derives, per format, which tiles it
-owns, which of them read their indices from the request and which reach the tail loop behind that format's rows in flight."""
+owns, which of them read their indices from the request and which reach the tail loop behind that format's rows in flight.  The MXFP4
+entries (``mx4``, ``mx4_gather``) plan on ``plan_mx4`` / ``plan_gather_mx4``, take no padding row either and are labelled by
+``f8_label`` under the family word ``mx4``; ``mx4_lds_bytes`` restates the launcher's LDS rule and why its 64 KiB fallback is out of reach."""
 import functools
 
 import numpy as np
@@ -30,12 +32,15 @@ GATHER_FIELDS = ("vec", "group_lanes", "tile", "col_passes", "unroll", "lds_bord
 # the `kind` codes of tests/launch_plan_dump.cpp (0 .. 4: pm_embbag_plan's PM_PLAN_*; 5: the gather plan)
 # (6 .. 8: plan_f8 for 4- / 2-byte output elements and plan_gather_f8, the plans of pm_embbag_f8_plan / pm_embedding_gather_f8_plan)
 # (9 .. 11: plan_anyfmt for 4- / 2-byte output elements and plan_gather_anyfmt, the plans of pm_embbag_anyfmt_plan / pm_embedding_gather_anyfmt_plan)
+# (12 .. 14: plan_mx4 for 4- / 2-byte output elements and plan_gather_mx4, the plans of pm_embbag_mx4_plan / pm_embedding_gather_mx4_plan)
 KIND = {"base": 0, "forward": 1, "quantized": 2, "padded4": 3, "padded2": 4, "gather": 5, "f8_4": 6, "f8_2": 7, "f8_gather": 8,
-        "anyfmt_4": 9, "anyfmt_2": 10, "anyfmt_gather": 11}
+        "anyfmt_4": 9, "anyfmt_2": 10, "anyfmt_gather": 11, "mx4_4": 12, "mx4_2": 13, "mx4_gather": 14}
 DTYPE = {"f32": 0, "bf16": 1, "f16": 2}
 F8_DTYPE = {"e4m3": 3, "e5m2": 4}                                             # PM_F8E4M3 / PM_F8E5M2: the table kinds of the FP8 entries
-VEC = {"f32": 4, "bf16": 8, "f16": 8, "e4m3": 16, "e5m2": 16}                 # columns per lane of the pooled kernels
+MX4_DTYPE = {"mx4": 7}                                                        # PM_MX4: the table kind of the MXFP4 entries
+VEC = {"f32": 4, "bf16": 8, "f16": 8, "e4m3": 16, "e5m2": 16, "mx4": 16}      # columns per lane of the pooled kernels
 F8_GATHER_VEC = 4                                                             # ... of the FP8 gather (one dword)
+MX4_GATHER_VEC = 4                                                            # ... of the MXFP4 gather (two bytes of codes)
 OUT16_CODE = {None: 0, "bf16": 1, "fp16": 2}                                  # PM_F32 / PM_BF16 / PM_F16 of a case's ``out16``
 TUNING = ("unroll", "bags_per_block", "xcd_affine", "nt_loads")               # set_tuning's arguments and their "not set"
 TUNING_DEFAULT = (0, 0, -1, -1)
@@ -51,11 +56,14 @@ ENTRY_KIND = {"fwd": "forward", "quantized": "quantized", "padded": "padded4", "
               "psw_grad": "base", "mean_grad": "base", "widen": "base", "atomic": "base", "max": ("padded4", "padded2"),
               "f8": ("f8_4", "f8_2"), "f8_gather": "f8_gather",
               # the scaled FP8 lookups plan on the FP8 plans: the pooled one on plan_f8 followed by f8s_stage_out (``pinned_plan`` below)
-              "f8s": ("f8_4", "f8_2"), "f8s_gather": "f8_gather", "anyfmt": ("anyfmt_4", "anyfmt_2"), "anyfmt_gather": "anyfmt_gather"}
-GATHER_ENTRIES = ("gather", "f8_gather", "f8s_gather", "anyfmt_gather")
+              "f8s": ("f8_4", "f8_2"), "f8s_gather": "f8_gather", "anyfmt": ("anyfmt_4", "anyfmt_2"), "anyfmt_gather": "anyfmt_gather",
+              "mx4": ("mx4_4", "mx4_2"), "mx4_gather": "mx4_gather"}
+GATHER_ENTRIES = ("gather", "f8_gather", "f8s_gather", "anyfmt_gather", "mx4_gather")
 UNROLLS = (1, 2, 3, 4, 6, 8)
 # FP8 pooled: (lane-group width, the D its unroll cases run at, the unroll its mean case runs at)
 F8_GROUP_DIMS = ((8, 64, 4), (16, 192, 8), (32, 400, 2), (64, 1024, 4))
+# MXFP4 pooled: (lane-group width, a D that fills the group, a D whose row ends inside it, the unroll its mean cases run at)
+MX4_GROUP_DIMS = ((8, 128, 96, 2), (16, 256, 160, 4), (32, 512, 416, 2), (64, 1024, 736, 4))
 K_BLOCK = 256
 ANY_VEC = 8                                                                   # columns per lane of both mixed-format kernels
 # the mixed-format pooled kernel's compile-time rows in flight per format (embbag_fwd_anyfmt_kernel.inc: kUnroll -- the float formats'
@@ -244,7 +252,9 @@ class Case:
         assert not set(self.tuning) - set(TUNING) and not set(self.forward) - set(FORWARD_TUNING) and not set(self.env) - set(ENV)
         assert entry in ENTRY_KIND and not (mean and weighted) and not (entry == "max" and (weighted or mean))
         # an FP8 entry has FP8 tables (dims: multiples of 16 in [16, 2048]) and nothing else has
-        assert (kind in F8_DTYPE and all(d % 16 == 0 and 16 <= d <= 2048 for d in self.dims)) if entry.startswith("f8") else kind in DTYPE
+        # ... an MXFP4 entry has MXFP4 tables (dims: multiples of 32 in [32, 2048])
+        assert (kind in F8_DTYPE and all(d % 16 == 0 and 16 <= d <= 2048 for d in self.dims)) if entry.startswith("f8") else \
+            (kind in MX4_DTYPE and all(d % 32 == 0 and 32 <= d <= 2048 for d in self.dims)) if entry.startswith("mx4") else kind in DTYPE
         # a scaled FP8 entry says which exponents its tables carry, and nothing else does
         assert (scale in ("table", "row")) if entry.startswith("f8s") else scale is None
         # a mixed-format entry names one stored format per table (the request struct says fp32, which no kernel reads), dims in
@@ -282,7 +292,7 @@ class Case:
     @property
     def dtype_code(self):
         """the library's code of the table element (``weight_dtype``)"""
-        return F8_DTYPE[self.kind] if self.kind in F8_DTYPE else DTYPE[self.kind]
+        return F8_DTYPE[self.kind] if self.kind in F8_DTYPE else MX4_DTYPE[self.kind] if self.kind in MX4_DTYPE else DTYPE[self.kind]
 
     def tuning_args(self):
         return [self.tuning.get(f, d) for f, d in zip(TUNING, TUNING_DEFAULT)]
@@ -316,7 +326,7 @@ def label(case, plan, dumped=None):
             if dict(zip(PLAN_FIELDS, dumped))["stage_out"] > 0 and not dict(zip(PLAN_FIELDS, plan))["stage_out"]:
                 words.add("burst-dropped")
         return words
-    if case.entry.startswith("f8"):
+    if case.entry.startswith(("f8", "mx4")):
         return f8_label(case, plan)
     if case.plan_kind == "gather":
         p = dict(zip(GATHER_FIELDS, plan))
@@ -370,23 +380,36 @@ def f8_label(case, plan):
                     in an earlier round (the bag's bound is read from ``s_pre`` beyond the first round and the carry over rounds counts);
       ``bounds5``   such a tile has 1024 bags (a thread's fifth bound);
       ``direct``    a tile's lookups exceed the index tile: its indices are read from the request;  ``partial``: a last tile is not full.
-    The gather: ``partial`` is a last tile of positions that is not full."""
+    The gather: ``partial`` is a last tile of positions that is not full.
+    An MXFP4 case (``mx4``, ``mx4_gather``) takes the same words under the family word ``mx4``: it has no padding row, so a request's pads
+    are ordinary lookups and none of the compaction words applies; ``row-ends-in-pass``: the last column pass has lanes at or behind the
+    widest row's end; the gather's ``NB<k>``: batches of U rows a lane group ping-pongs through (embedding_gather_mx4.hip: NB = G / U)."""
     r, (b0, n) = case.req, case.bags
-    words = {"f8", case.kind, "out-" + (case.out16 or "fp32")} | ({"slice"} if case.bag_slice else set())
-    if case.entry in ("f8_gather", "f8s_gather"):
+    mx4 = case.entry.startswith("mx4")
+    words = {"mx4" if mx4 else "f8", case.kind, "out-" + (case.out16 or "fp32")} | ({"slice"} if case.bag_slice else set())
+    if case.entry in GATHER_ENTRIES:
         p = dict(zip(GATHER_FIELDS, plan))
-        assert p["vec"] == F8_GATHER_VEC
+        assert p["vec"] == (MX4_GATHER_VEC if mx4 else F8_GATHER_VEC)
+        if mx4:
+            words |= {f"NB{p['group_lanes'] // p['unroll']}"} | ({"row-ends-in-pass"} if max(case.dims) % (p["group_lanes"] * p["vec"]) else set())
+            width = np.zeros(r.N, dtype=np.int64)                  # of the table that owns a written position
+            for t in range(r.T):
+                width[r.off[t * r.B + b0]:r.off[t * r.B + b0 + n]] = case.dims[t]
+            if any(len(set(width[i:i + p["tile"]].tolist()) - {0}) > 1 for i in range(0, r.N, p["tile"])):
+                words.add("mixed-tile")                            # one tile of positions holds rows of different widths
         return words | {"unpooled", f"G{p['group_lanes']}", f"u{p['unroll']}", f"passes{p['col_passes']}", f"xcd{p['xcd_contiguous']}",
                         "lds_borders" if p["lds_borders"] else "global_borders"} | ({"partial"} if r.N % p["tile"] else set())
     p = dict(zip(PLAN_FIELDS, plan))
     G = group_lanes(max(case.dims), VEC[case.kind])
+    if mx4 and max(case.dims) % (G * VEC[case.kind]):
+        words.add("row-ends-in-pass")
     bpb, cap = p["bags_per_block"], p["idx_cap"]
     words |= {"pooled", f"G{G}", f"u{p['unroll']}", "mean" if case.mean else "weighted" if case.weighted else "unweighted", f"xcd{p['xcd_affine']}",
               f"bpb{bpb}", "staged" if p["stage_out"] else "plain", f"passes{-(-max(case.dims) // (G * VEC[case.kind]))}"}
     if bpb > K_BLOCK // G:
         words.add("tile>NG")
     for t in range(r.T):
-        pad = -1 if r.pads is None or r.pads[t] is None else r.pads[t]
+        pad = -1 if mx4 or r.pads is None or r.pads[t] is None else r.pads[t]
         for k in range(-(-n // bpb)):
             g0, nb = t * r.B + b0 + k * bpb, min(bpb, n - k * bpb)
             lo, cnt = int(r.off[g0]), int(r.off[g0 + nb] - r.off[g0])
@@ -394,6 +417,9 @@ def f8_label(case, plan):
                 words.add("partial")
             if cnt > cap:
                 words.add("direct")
+                continue
+            if mx4:                                                # (nothing is compacted; ``indexed``: a tile that reads its indices from LDS)
+                words.add("indexed")
                 continue
             keep = r.idx[lo:lo + cnt] != pad
             if nb == 1024:
@@ -493,6 +519,21 @@ def pinned_plan(case, dumped):
     p["stage_out"] = f8s_stage_out(p["bags_per_block"], p["idx_cap"], case.plan_weighted and not case.mean, case.scale == "row", p["stage_out"],
                                    2 if case.out16 else 4)
     return [p[f] for f in PLAN_FIELDS]
+
+
+# ---- the MXFP4 pooled launcher's LDS rule, restated (param_amd/csrc/embbag_fwd_mx4.hip: launch_mx4_w; common.h: tile_lds_bytes) --------
+def mx4_lds_bytes(bpb, idx_cap, weighted, stage_out, out_bytes):
+    """int64 offsets[bpb + 1, rounded up to even] | int32 indices[idx_cap] | fp32 weights[idx_cap] (weighted), rounded up to 16 bytes,
+    then the burst.  Past 65536 the launcher would drop the burst and ``pm_embbag_mx4_plan`` would still report it -- but no plan gets
+    there: the largest tile (1024 bags, 4096 entries, weights) is 40976 bytes, the burst at most kBurstBytes = 16384, 57360 in all.
+    tests/test_plan_sweep_host.py asserts the bound for every MXFP4 case; group ``mx4_edge`` runs the largest request that keeps a burst."""
+    tile = ((bpb + 2) // 2 * 2 * 8 + idx_cap * 4 * (2 if weighted else 1) + 15) // 16 * 16
+    return tile + (bpb * stage_out * out_bytes if stage_out > 0 else 0)
+
+
+def mx4_case_lds(case, plan):
+    p = dict(zip(PLAN_FIELDS, plan))
+    return mx4_lds_bytes(p["bags_per_block"], p["idx_cap"], case.plan_weighted and not case.mean, p["stage_out"], 2 if case.out16 else 4)
 
 
 def pad_lds_bytes(case, plan):
@@ -801,6 +842,76 @@ def _cases():
     anyg("any_gather_D520", "any_gather_knobs", dims=520, formats=plain5, out16="bf16")
     anyg("any_gather_D2048_four_passes", "any_gather_knobs", dims=2048)
     anyg("any_gather_260_tables", "any_gather_knobs", rq="many260", dims=64, formats=[seven[t % 7] for t in range(260)])
+    # -- MXFP4 tables, pooled: pm_embbag_fwd_mx4 on plan_mx4 -- plan_f8's tiling, sixteen columns per lane (G = 8 up to D = 128, 64 from
+    #    D = 544 on, two passes above 1024), 2 or 4 rows in flight.  No padding row: the padded requests' pads are ordinary lookups.
+    def mx4(name, group, rq, dims, mode="plain", **kw):
+        add(name, group, "mx4", rq, "mx4", dims, weighted=mode == "weighted", mean=mode == "mean", **kw)
+
+    # the multi-tile baseline (see f8_base_*): four 32-bag tiles a table, the last of 4 bags, two bags per lane group; fp32 rows leave
+    # one by one with non-temporal stores, 16-bit rows fill the burst exactly
+    for mode in modes:
+        mx4(f"mx4_base_{mode}", "mx4_base", "pad100", 256, mode, tuning=dict(bags_per_block=32))
+        mx4(f"mx4_base_{mode}_bf16", "mx4_base", "pad100", 256, mode, tuning=dict(bags_per_block=32), out16="bf16")
+    mx4("mx4_base_plain_fp16", "mx4_base", "pad100", 256, tuning=dict(bags_per_block=32), out16="fp16")
+    mx4("mx4_base_plain_bf16_unstaged", "mx4_base", "pad100", 256, tuning=dict(bags_per_block=32), forward=dict(stage_out=0), out16="bf16")
+    # fp32 rows through the burst: 64-bag tiles of D = 64 rows (four of the group's eight lanes hold columns), 18 tiles a table
+    for mode in modes:
+        mx4(f"mx4_burst_{mode}", "mx4_burst", "pad1100", 64, mode, tuning=dict(bags_per_block=64))
+        mx4(f"mx4_burst_{mode}_unstaged", "mx4_burst", "pad1100", 64, mode, tuning=dict(bags_per_block=64), forward=dict(stage_out=0))
+    # every lane-group width x both depths, two bags per lane group (the loop over a group's bags runs twice), at a width that fills the
+    # group and at one whose row ends inside it; mean at one depth per width, the other depth at the other width
+    for G, full, part, mean_u in MX4_GROUP_DIMS:
+        for D in (full, part):
+            for u in (2, 4):
+                for mode in modes[:2] + (("mean",) if (u == mean_u) == (D == full) else ()):
+                    mx4(f"mx4_G{G}_D{D}_u{u}_{mode}", f"mx4_G{G}", "pad100", D, mode, tuning=dict(unroll=u, bags_per_block=2 * K_BLOCK // G))
+    # pm_set_tuning's unroll 1, 2, 3, 4, 6, 8 plans 2, 2, 2, 4, 4, 4 rows in flight
+    for u in UNROLLS:
+        mx4(f"mx4_unroll_map_u{u}", "mx4_unroll_map", "pad100", 128, "weighted", tuning=dict(unroll=u, bags_per_block=32))
+    # block orders and a slice that begins and ends inside tiles, on the product's tile: D = 128, one bag per lane group, fp32 burst
+    mx4("mx4_xcd0", "mx4_orders", "pad100", 128, tuning=dict(bags_per_block=32, xcd_affine=0))
+    mx4("mx4_xcd1", "mx4_orders", "pad8", 128, tuning=dict(bags_per_block=32))
+    mx4("mx4_xcd3", "mx4_orders", "padfix", 128, tuning=dict(bags_per_block=32))
+    mx4("mx4_slice", "mx4_orders", "pad100", 128, tuning=dict(bags_per_block=32), bag_slice=(5, 70))
+    mx4("mx4_slice_mean", "mx4_orders", "pad100", 128, "mean", tuning=dict(bags_per_block=32), bag_slice=(5, 70))
+    # 1024-bag tiles: four bags per lane at G = 8, a last tile of 76; rows leave one by one (no burst)
+    for mode in modes:
+        mx4(f"mx4_bpb1024_{mode}", "mx4_1024", "pad1100", 32, mode, tuning=dict(bags_per_block=1024))
+        mx4(f"mx4_bpb1024_{mode}_bf16", "mx4_1024", "pad1100", 32, mode, tuning=dict(bags_per_block=1024), out16="bf16")
+    # a 32-bag tile of 1600 lookups reads its indices (and weights) from the request, among tiles of 640 that stage theirs
+    for mode in modes:
+        for u in (2, 4):
+            mx4(f"mx4_direct_u{u}_{mode}", "mx4_direct", "pad_lumpy", 128, mode, tuning=dict(unroll=u, bags_per_block=32))
+    # the launcher's LDS edge: 256-bag tiles of D = 32 bf16 rows fill the 16 KiB burst behind the index tile -- with weights (2560
+    # entries) 22544 + 16384 = 38928 bytes, without (4096 entries) 18448 + 16384 = 34832: the sweep's two largest tiles with a burst, and
+    # both keep it (mx4_lds_bytes says why the launcher's 64 KiB fallback is out of every plan's reach)
+    mx4("mx4_edge_weighted", "mx4_edge", "pad600", 32, "weighted", tuning=dict(bags_per_block=256), out16="bf16")
+    mx4("mx4_edge_plain", "mx4_edge", "pad600", 32, tuning=dict(bags_per_block=256), out16="bf16")
+    # mixed dims (the lane group sized for 128), the 2-byte against the 4-byte burst at D = 512, a second column pass that ends inside
+    # the lane group (D = 1056: two of 64 lanes hold columns), two full passes
+    mx4("mx4_mixed_dims", "mx4_wide", "pad100", [32, 64, 128], "weighted", tuning=dict(bags_per_block=32))
+    mx4("mx4_D512_bf16", "mx4_wide", "pad100", 512, tuning=dict(bags_per_block=16), out16="bf16")
+    mx4("mx4_D512_fp32", "mx4_wide", "pad100", 512, tuning=dict(bags_per_block=16))
+    mx4("mx4_D1056_weighted", "mx4_wide", "pad100", 1056, "weighted", tuning=dict(bags_per_block=8))
+    mx4("mx4_D2048", "mx4_wide", "pad100", 2048, tuning=dict(bags_per_block=8))
+    # -- MXFP4 tables, un-pooled: pm_embedding_gather_mx4 on plan_gather_mx4, four columns per lane (G = D / 4 up to 64); G = U = 8 is the
+    #    kernel's NB == 1 branch, every other pair ping-pongs through 2 .. 64 batches
+    def mx4g(name, group, rq="ragged", dims=128, **kw):
+        add(name, group, "mx4_gather", rq, "mx4", dims, **kw)
+
+    for G, D in ((8, 32), (16, 64), (32, 128), (64, 256)):
+        for u in (1, 2, 4, 8):
+            mx4g(f"mx4_gather_G{G}_u{u}", "mx4_gather_GU", dims=D, tuning=dict(unroll=u))
+    for u in (1, 2, 4, 8):
+        for o16 in ("bf16", "fp16"):
+            mx4g(f"mx4_gather_G32_u{u}_{o16}", "mx4_gather_16", tuning=dict(unroll=u), out16=o16)
+    mx4g("mx4_gather_xcd0", "mx4_gather_knobs", tuning=dict(unroll=2, xcd_affine=0))
+    mx4g("mx4_gather_D512_two_passes", "mx4_gather_knobs", "mixed_ragged", 512, tuning=dict(unroll=4))
+    mx4g("mx4_gather_D2048_bf16", "mx4_gather_knobs", "mixed_ragged", 2048, out16="bf16")
+    mx4g("mx4_gather_slice", "mx4_gather_knobs", tuning=dict(unroll=4), bag_slice=(3, 90))
+    # rows of three widths in one tile of positions: a lane past its row's width reads offset 0 and stores nothing
+    mx4g("mx4_gather_mixed_dims", "mx4_gather_knobs", "ragged8", [32, 128, 64, 32, 128, 64, 32, 128])
+    mx4g("mx4_gather_260_tables", "mx4_gather_knobs", "many260", 32)
     # -- the environment switches: one group per setting, each in a process of its own
     e = "env_tile_major"
     add(f"{e}_ordered", e, "fwd", "ragged", tuning=dict(bags_per_block=32), env={"PARAM_AMD_FWD_TILE_MAJOR": 1})
@@ -828,6 +939,7 @@ def _cases():
     add(f"{e}_f8", e, "f8", "pad100", "e4m3", 128, tuning=dict(bags_per_block=32), env=env)
     add(f"{e}_f8s", e, "f8s", "pad100", "e4m3", 128, tuning=dict(bags_per_block=32), env=env, scale="row")
     add(f"{e}_anyfmt", e, "anyfmt", "pad100", "f32", 128, tuning=dict(bags_per_block=32), env=env, formats=rot[1])
+    add(f"{e}_mx4", e, "mx4", "pad100", "mx4", 128, tuning=dict(bags_per_block=32), env=env)
     add(f"{e}_out16", e, "out16", "pad100", tuning=dict(bags_per_block=32), env=env, out16="bf16")
     assert len({c.name for c in out}) == len(out)
     for c in out:                                                  # a group shares its environment; its cases are one test

@@ -5,7 +5,9 @@ modules, are asked through ``pm_embbag_f8_plan`` / ``pm_embedding_gather_f8_plan
 (``f8s``, ``f8s_gather``) build the same class with ``scale=``, exponents as tests/test_gpu_f8s.py draws them, are asked through
 ``pm_embbag_f8_scaled_plan`` / ``pm_embedding_gather_f8_plan`` and compare with tests/f8s_rules.py; the mixed-format ones (``anyfmt``,
 ``anyfmt_gather``) build ``MixedBatchedEmbeddingBagMI355`` over the tables of tests/anyfmt_cases.py, are asked through
-``pm_embbag_anyfmt_plan`` / ``pm_embedding_gather_anyfmt_plan`` and compare with tests/anyfmt_rules.py.
+``pm_embbag_anyfmt_plan`` / ``pm_embedding_gather_anyfmt_plan`` and compare with tests/anyfmt_rules.py; the MXFP4 ones (``mx4``,
+``mx4_gather``) build ``MX4BatchedEmbeddingBagMI355`` over tables drawn as tests/test_gpu_mx4.py draws them, are asked through
+``pm_embbag_mx4_plan`` / ``pm_embedding_gather_mx4_plan`` and compare with tests/mx4_rules.py under that file's sequential fp32 ``pool``.
 
 tests/test_gpu_plan_sweep.py calls ``run_group`` in its own process; for the groups with an environment setting it starts
 ``python -m tests.plan_sweep_worker GROUP`` with that setting, because the switches are read once per process.  Exit status 0: every
@@ -22,6 +24,7 @@ from tests import embedding_rules as ER
 from tests import f8_rules as F8
 from tests import f8s_rules as F8S
 from tests import mean_rules as M
+from tests import mx4_rules as MX
 from tests import out16_rules as O16
 from tests import padding_rules as P
 from tests import plan_sweep as S
@@ -143,6 +146,10 @@ def check_plan(c, op):
         got = list(_lib.embbag_anyfmt_plan(op, S.OUT16_CODE[c.out16]).values())
     elif c.entry == "anyfmt_gather":
         got = list(_lib.embedding_gather_anyfmt_plan(op).values())
+    elif c.entry == "mx4":
+        got = list(_lib.embbag_mx4_plan(op, S.OUT16_CODE[c.out16]).values())
+    elif c.entry == "mx4_gather":
+        got = list(_lib.embedding_gather_mx4_plan(op).values())
     elif c.plan_kind == "gather":
         got = list(_lib.embedding_gather_plan(op).values())
     else:
@@ -619,9 +626,121 @@ def run_anyfmt_gather(c, idt, layout, coracle):
     assert AR.is_nan(got[~written], kind).all(), "written outside the slice"
 
 
+def mx4_tables(c):
+    """the uint8 tables of an MXFP4 case as tests/test_gpu_mx4.py: random_table draws them, one set per (request, dims): all 256 code
+    bytes under scale bytes near 127 (sums stay finite), and in every table one NaN block (x = 255), block 0 of the row the table's middle
+    lookup names -- over the request some bags (positions) look a NaN block up and others do not.  -> (tables, their fp32 values)"""
+    def make():
+        r, rng = c.req, np.random.default_rng(7200)
+        tabs = []
+        for t, (rows, D) in enumerate(zip(r.rows, c.dims)):
+            tab = np.zeros((rows, MX.row_bytes(D)), dtype=np.uint8)
+            tab[:, :D // 2] = rng.integers(0, 256, (rows, D // 2))
+            tab[:, D // 2:D // 2 + D // 32] = rng.integers(120, 135, (rows, D // 32))
+            lo, hi = int(r.off[t * r.B]), int(r.off[(t + 1) * r.B])
+            tab[int(r.idx[(lo + hi) // 2]) if hi > lo else 0, D // 2] = 255
+            tabs.append(tab)
+        assert len(set(np.concatenate([tab[:, :D // 2].reshape(-1) for tab, D in zip(tabs, c.dims)]).tolist())) == 256
+        return tabs, [MX.dequant(tab, D) for tab, D in zip(tabs, c.dims)]
+    return _memo(("mx4 tables", c.request, tuple(c.dims)), make)
+
+
+def mx4_module(c, layout):
+    """the MX4BatchedEmbeddingBagMI355 of a case, one per distinct set of options, filled through ``copy_from_``"""
+    torch = _torch()
+    from param_amd import MX4BatchedEmbeddingBagMI355
+
+    def make():
+        m = MX4BatchedEmbeddingBagMI355(c.req.rows, c.dims, device=DEV, layout=layout, pooling_mode="mean" if c.mean else "sum",
+                                        output_dtype={None: None, "bf16": torch.bfloat16, "fp16": torch.float16}[c.out16])
+        for t, (tab, D) in enumerate(zip(mx4_tables(c)[0], c.dims)):
+            m.copy_from_(t, _t(tab[:, :D // 2]), _t(tab[:, D // 2:D // 2 + D // 32]))
+        return m
+    return _memo(("mx4 module", c.request, tuple(c.dims), layout, c.mean, c.out16), make)
+
+
+def run_mx4(c, idt, layout, coracle):
+    """pm_embbag_fwd_mx4: ``pm_embbag_mx4_plan`` must report the pinned row; the batch, or a slice of it, into a NaN canvas that must equal
+    the sequential fp32 rule of tests/test_gpu_mx4.py: pool over tests/mx4_rules.py: dequant (weighted: the exact fmaf of
+    tests/qrows_rules.py; a 16-bit output: its one rounding) on bits -- NaN by class -- and stay NaN elsewhere.  The padded requests'
+    pads are ordinary lookups: the module has no padding row."""
+    from tests.test_gpu_mx4 import pool
+
+    torch = _torch()
+    r, (b0, n) = c.req, c.bags
+    m, (_, W) = mx4_module(c, layout), mx4_tables(c)
+    it = torch.int64 if idt == "i64" else torch.int32
+    idx_t, off_t = _t(r.idx, it), _t(r.off, it)
+    psw_t = _t(r.psw) if c.weighted else None
+    check_plan(c, m._request(idx_t, off_t, psw_t, b0, n if c.bag_slice else None, r.B, False)[2])
+    outs = _memo(("mx4", c.request, tuple(c.dims), c.weighted, c.mean),
+                 lambda: [pool(W[t], r.idx, r.off, r.B, t, r.psw if c.weighted else None, c.mean) for t in range(r.T)])
+    nan_bags = np.concatenate([np.isnan(o).any(axis=1) for o in outs])
+    assert nan_bags.any() and not nan_bags.all() and all(np.isfinite(o[~np.isnan(o)]).all() for o in outs)
+    shape = (r.B, sum(c.dims)) if layout == "bd" else (r.T, r.B, c.dims[0])
+    sel = _sel(layout, b0, n)
+    rest = np.ones(shape, dtype=bool)
+    rest[sel] = False
+    canvas = torch.full(shape, float("nan"), dtype=m.output_dtype, device=DEV)
+    assert m.lookup(idx_t, off_t, psw_t, out=canvas, batch=r.B, bag_begin=b0, bag_count=n) is canvas
+    if c.out16 is None:
+        got, want = canvas.cpu().numpy(), _assemble(outs, layout)
+        assert _same_f32_or_nan(got[sel], want[sel]), _first_diff(got[sel].view(np.uint32), want[sel].view(np.uint32))
+        assert np.isnan(got[rest]).all(), "written outside the slice"
+    else:
+        got, want = _bits16(canvas), _assemble([O16.round16(o, c.out16) for o in outs], layout)
+        assert F8.same16(got[sel], want[sel], c.out16), _first_diff(got[sel], want[sel])
+        assert (got[rest] == _bits16(torch.full((1,), float("nan"), dtype=m.output_dtype))[0]).all(), "written outside the slice"
+
+
+def run_mx4_gather(c, idt, layout, coracle):
+    """pm_embedding_gather_mx4 into a NaN canvas ``[N, max D]``: ``pm_embedding_gather_mx4_plan`` must report the pinned row; position j of
+    the slice holds tests/mx4_rules.py: dequant of its row (a 16-bit output: the one rounding) in its table's first D_t columns on bits --
+    NaN by class --, everything else stays NaN.  One common dim goes through ``lookup_sequence``; tables of different widths, which the
+    module refuses, through the C call on the module's own request."""
+    import ctypes
+
+    from param_amd import _lib
+
+    torch = _torch()
+    r, (b0, n) = c.req, c.bags
+    m, (_, W) = mx4_module(c, layout), mx4_tables(c)
+    it = torch.int64 if idt == "i64" else torch.int32
+    idx_t, off_t = _t(r.idx, it), _t(r.off, it)
+    op = m._request(idx_t, off_t, None, b0, n if c.bag_slice else None, r.B, False)[2]
+    check_plan(c, op)
+    D = max(c.dims)
+
+    def make():
+        want, written = np.full((r.N, D), np.nan, dtype=np.float32), np.zeros((r.N, D), dtype=bool)
+        for t in range(r.T):
+            lo, hi = int(r.off[t * r.B + b0]), int(r.off[t * r.B + b0 + n])
+            want[lo:hi, :c.dims[t]] = W[t][r.idx[lo:hi]]
+            written[lo:hi, :c.dims[t]] = True
+        return want, written
+    want, written = _memo(("mx4 rows", c.request, tuple(c.dims), b0, n), make)
+    nan_rows = np.isnan(want[:, 0]) & written[:, 0]
+    assert nan_rows.any() and not nan_rows[written[:, 0]].all() and (written.all() != bool(c.bag_slice or len(set(c.dims)) > 1))
+    canvas = torch.full((r.N, D), float("nan"), dtype=m.output_dtype, device=DEV)
+    if len(set(c.dims)) == 1:
+        assert m.lookup_sequence(idx_t, off_t, batch=r.B, out=canvas, bag_begin=b0, bag_count=n) is canvas
+    else:
+        _lib.check(_lib.load().pm_embedding_gather_mx4(ctypes.byref(op), S.OUT16_CODE[c.out16], canvas.data_ptr(), D, None))
+        torch.cuda.synchronize()
+    if c.out16 is None:
+        got = canvas.cpu().numpy()
+        assert _same_f32_or_nan(got[written], want[written]), _first_diff(got.view(np.uint32) * written, want.view(np.uint32) * written)
+        assert np.isnan(got[~written]).all(), "written outside the slice or behind a row's width"
+    else:
+        got, want16 = _bits16(canvas), O16.round16(want, c.out16)
+        assert F8.same16(got[written], want16[written], c.out16), _first_diff(got * written, want16 * written)
+        assert (got[~written] == _bits16(torch.full((1,), float("nan"), dtype=m.output_dtype))[0]).all(), "written outside the slice or behind a row's width"
+
+
 RUN = {"fwd": run_forward, "padded": run_forward, "mean": run_forward, "out16": run_forward, "quantized": run_quantized, "gather": run_gather,
        "psw_grad": run_base, "mean_grad": run_base, "widen": run_base, "atomic": run_base, "max": run_max, "f8": run_f8, "f8_gather": run_f8_gather,
-       "f8s": run_f8s, "f8s_gather": run_f8s_gather, "anyfmt": run_anyfmt, "anyfmt_gather": run_anyfmt_gather}
+       "f8s": run_f8s, "f8s_gather": run_f8s_gather, "anyfmt": run_anyfmt, "anyfmt_gather": run_anyfmt_gather, "mx4": run_mx4,
+       "mx4_gather": run_mx4_gather}
 
 
 def run_group(group, coracle, log=None):
@@ -683,6 +802,10 @@ def host_plans(group):
                 plan = _lib.embbag_anyfmt_plan(op, S.OUT16_CODE[c.out16])
             elif c.entry == "anyfmt_gather":
                 plan = _lib.embedding_gather_anyfmt_plan(op)
+            elif c.entry == "mx4":
+                plan = _lib.embbag_mx4_plan(op, S.OUT16_CODE[c.out16])
+            elif c.entry == "mx4_gather":
+                plan = _lib.embedding_gather_mx4_plan(op)
             else:
                 plan = _lib.embedding_gather_plan(op) if c.plan_kind == "gather" else _lib.embbag_plan(op, S.KIND[c.plan_kind])
             res[c.name] = list(plan.values())

@@ -1,6 +1,10 @@
 """The direct backward of max pooling on the GPU (``pytest -m gpu``): ``dense_grad`` / ``scatter_add_`` with ``method="direct"``
 (``pm_embbag_max_bwd``) against the numpy restatement of its rule (tests/max_direct_rules.py), on bits.  Three small tables, ragged
-bags with empty ones, a bag that holds its arg-max row twice, a tie between two rows, a bag whose later rows win no column."""
+bags with empty ones, a bag that holds its arg-max row twice, a tie between two rows, a bag whose later rows win no column.  Then the
+constructed requests of tests/max_direct_cases.py under hand-written ``max_indices``: a bag's repeat across a piece cut and across a
+tile border, pieces and a run that win nothing, a run start four tiles back, a run from sorted position 0, hot runs in every table and
+gradient type, under ``tbd``, a slice and a padding row, with mixed dims up to D = 2048, and 8-byte sort keys through the C call.  Hot
+rows need no tolerance either: the rule restates the piece cuts."""
 import ctypes
 import functools
 
@@ -8,8 +12,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests import max_direct_cases as C
 from tests import max_direct_rules as R
 from tests import max_rules as M
+from tests import out16_rules as O
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -189,3 +195,138 @@ def test_c_refusals():
     torch.cuda.synchronize()
     assert all(np.array_equal(_bits(m.table(t)), before[t]) for t in range(3))
     assert call() == _lib.PM_OK
+
+
+# ---- hot runs against the piece cuts, the tile borders and the key width (tests/max_direct_cases.py builds and checks the requests) ------
+
+def _hot_case(name):
+    return {"repeat100": lambda: C.repeat(263), "repeat768": lambda: C.repeat(85), "nothing": C.nothing, "far": C.far, "zero": C.zero,
+            "sliced": C.sliced, "mixed": C.mixed}[name]()
+
+
+def _hot_module(c, tdt="f32", layout="bd", out16=None):
+    import param_amd
+
+    pads = list(c.pads) if any(p is not None for p in c.pads) else None
+    m = param_amd.MaxBatchedEmbeddingBagMI355(list(C.ROWS), list(c.dims), dtype=TDT[tdt], device=DEV, init=None, layout=layout, padding_idx=pads,
+                                              output_dtype=out16, fused_update=False)
+    rng = np.random.default_rng(77)
+    for t, (r, d) in enumerate(zip(C.ROWS, c.dims)):
+        w = (rng.integers(-80, 81, size=(r, d)) / 8.0).astype(np.float32)      # exact in 16 bits
+        w[7, 0] = -0.0
+        m.table(t).copy_(_dev(w).to(TDT[tdt]))
+    return m
+
+
+def _hot_grads(c, gdt):
+    return c.grads if gdt == "f32" else [O.widen(O.round16(g, gdt), gdt) for g in c.grads]
+
+
+def _hot_dense(c, gdt="f32", layout="bd", idt=torch.int64):
+    """dense_grad(method="direct") under the case's hand-written max_indices == the rule on bits, twice"""
+    grads = _hot_grads(c, gdt)
+    m = _hot_module(c, layout=layout, out16=None if gdt == "f32" else TDT[gdt])
+    idx, off = _dev(c.idx, idt), _dev(c.off, idt)
+    g, arg = _join(grads, layout, TDT[gdt]), _join(c.args, layout, torch.int32)
+    res = R.sums(C.ROWS, c.dims, c.idx, c.off, c.B, grads, c.args)
+    want = [R.apply(np.zeros(G.shape, np.uint32), "f32", G, won, 1.0) for G, won, _, _, _ in res]
+    for call in range(2):
+        got = m.dense_grad(g, idx, off, batch=c.B, method="direct", max_indices=arg)
+        for t in range(3):
+            assert np.array_equal(_bits(got[t]), want[t]), (t, call, np.argwhere(_bits(got[t]) != want[t])[:4].tolist())
+    return res
+
+
+@pytest.mark.parametrize("name", ["repeat100", "repeat768", "nothing", "far", "zero", "mixed"])
+def test_hot_runs_against_the_cuts_on_bits(name):
+    """repeat100 / repeat768: a bag's repeat across a piece cut, inside a tile and where the cut is a tile border; nothing: pieces, the
+    first one included, and a whole run that win no column; far: a run start four tiles back; zero: a run from sorted position 0;
+    mixed: dims (8, 2048, 32) with hot runs in the narrow and the wide table"""
+    c = _hot_case(name)
+    res = _hot_dense(c)
+    for (t, row), n in c.hot().items():
+        assert res[t][4][row].max() <= n and n > R.EXACT_RUN
+    if name == "nothing":
+        assert not res[2][1][3].any() and not res[1][1][7, 7] and M.bits(res[1][0][7])[0] == 0x80000000
+
+
+@pytest.mark.parametrize("kind,dt", [("table", "f32"), ("table", "bf16"), ("table", "fp16"), ("grad", "f32"), ("grad", "bf16"), ("grad", "fp16")])
+def test_hot_runs_in_every_element_type(kind, dt):
+    """the request whose pieces 0 and 2 win nothing: 16-bit gradients through ``output_dtype`` and ``dense_grad``; fp32, bf16 and fp16
+    tables through ``scatter_add_`` with alpha = -0.5, where the run that wins nothing and the column that nobody wins keep their bits
+    and the -0.0 sum of column 0 meets a stored -0.0"""
+    c = C.nothing()
+    if kind == "grad":
+        _hot_dense(c, gdt=dt)
+        return
+    m = _hot_module(c, tdt=dt)
+    before = [_bits(m.table(t)).copy() for t in range(3)]
+    idx, off, g, arg = _dev(c.idx), _dev(c.off), _join(c.grads, "bd", torch.float32), _join(c.args, "bd", torch.int32)
+    res = R.sums(C.ROWS, c.dims, c.idx, c.off, c.B, c.grads, c.args)
+    zero16 = 0x80000000 if dt == "f32" else 0x8000
+    assert before[1][7, 0] == zero16
+    for call in range(2):
+        m.scatter_add_(g, idx, off, alpha=-0.5, batch=c.B, method="direct", max_indices=arg)
+        for t, (G, won, _, _, _) in enumerate(res):
+            after = _bits(m.table(t))
+            assert np.array_equal(after, R.apply(before[t], dt, G, won, -0.5)), (t, call)
+        assert np.array_equal(_bits(m.table(2))[3], before[2][3]) and _bits(m.table(1))[7, 7] == before[1][7, 7] and _bits(m.table(1))[7, 0] == 0
+        for t in range(3):
+            m.table(t).copy_(_dev(before[t].view(np.int32 if dt == "f32" else np.int16)).view(TDT[dt]))
+
+
+def test_hot_runs_under_tbd_a_slice_and_a_padding_row():
+    """layout tbd with int32 indices; the slice cuts one hot run to 257 pairs and another to 256; 300 padded lookups in the slice leave
+    the device fewer pairs than the request has lookups"""
+    c = C.sliced()
+    b0, nb = c.slice
+    m = _hot_module(c, layout="tbd")
+    before = [_bits(m.table(t)).copy() for t in range(3)]
+    idx, off = _dev(c.idx, torch.int32), _dev(c.off, torch.int32)
+    g, arg = _join(c.grads, "tbd", torch.float32), _join(c.args, "tbd", torch.int32)
+    res = R.sums(C.ROWS, c.dims, c.idx, c.off, c.B, c.grads, c.args, b0, nb)
+    assert (res[1][4][7] == 257).all() and (res[2][4][3] == 256).all() and (res[0][4][9] == 300).all() and not res[0][1][5].any()
+    for call in range(2):
+        m.scatter_add_(g, idx, off, alpha=-0.5, batch=c.B, bag_begin=b0, bag_count=nb, method="direct", max_indices=arg)
+        for t, (G, won, _, _, _) in enumerate(res):
+            assert np.array_equal(_bits(m.table(t)), R.apply(before[t], "f32", G, won, -0.5)), (t, call)
+        for t in range(3):
+            m.table(t).copy_(_dev(before[t].view(np.int32)).view(torch.float32))
+
+
+@pytest.mark.parametrize("name", ["case", "repeat100"])
+def test_eight_byte_keys(name):
+    """``pm_embbag_max_bwd`` with a ``max_rows`` of 2^30: three tables take 2 + 30 key bits and one spare, so the sort plan says 8-byte
+    keys and the kernels load ``uint64`` keys (``key64``).  The bits equal the rule's and the 4-byte-key run's."""
+    from param_amd import _lib
+
+    if name == "case":
+        dims = (8, 8, 8)
+        tabs, idx_h, off_h, grads, args = _case(dims)
+        m, nb = _module(dims, tabs), B
+    else:
+        c = C.repeat(263)
+        dims, idx_h, off_h, grads, args, nb = c.dims, c.idx, c.off, c.grads, c.args, c.B
+        m = _hot_module(c)
+    idx, off, g, arg = _dev(idx_h), _dev(off_h), _join(grads, "bd", torch.float32), _join(args, "bd", torch.int32)
+    ts, L = m._tables(), _lib.load()
+    op = _lib.pm_embbag_batch.from_buffer_copy(ts.request(idx, off, nb, None, 0, None))
+    op.fixed_pooling = 0
+    want = [R.apply(np.zeros(G.shape, np.uint32), "f32", G, won, 1.0) for G, won, _, _, _ in R.sums(ROWS, dims, idx_h, off_h, nb, grads, args)]
+    small = m.dense_grad(g, idx, off, batch=nb, method="direct", max_indices=arg)
+    for max_rows, key_bytes in ((max(ROWS), "4"), (1 << 30, "8")):
+        buf = ctypes.create_string_buffer(512)
+        assert L.pm_embbag_sort_plan(ctypes.byref(op), max_rows, 1, buf, 512) == _lib.PM_OK, L.pm_last_error()
+        assert dict(kv.split("=") for kv in buf.value.decode().split())["key_bytes"] == key_bytes
+        need = L.pm_embbag_max_bwd_workspace(ctypes.byref(op), max_rows)
+        assert 0 < need < 1 << 30, need
+        ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+        for call in range(2):
+            outs = [torch.zeros(r, d, device=DEV) for r, d in zip(ROWS, dims)]
+            ptrs = torch.tensor([o.data_ptr() for o in outs], dtype=torch.int64, device=DEV)
+            assert L.pm_embbag_max_bwd(ctypes.byref(op), g.data_ptr(), _lib.PM_F32, arg.data_ptr(), ptrs.data_ptr(), _lib.PM_F32, 1.0, max_rows,
+                                       ws.data_ptr(), need, None) == _lib.PM_OK, L.pm_last_error()
+            torch.cuda.synchronize()
+            for t in range(3):
+                assert np.array_equal(_bits(outs[t]), want[t]), (key_bytes, t, call)
+                assert np.array_equal(_bits(outs[t]), _bits(small[t])), (key_bytes, t, "the module's 4-byte-key run")

@@ -26,7 +26,16 @@ row's width on the other; the un-pooled lookup's ``sequence_plan`` must equal an
 (``anyfmt_fwd_kernel<G, WEIGHTED, OT>``, ``anyfmt_gather_kernel<OT, G>``; tests/test_gpu_anyfmt.py runs G = 8, 32 and 64 with one tile a
 table) are pinned in groups ``any_*``: every format at every lane-group width, weighted and not, over several tiles a table whose
 neighbours differ in format, each format's tail loop, direct tiles of an FP8, a 4-bit and an fp32 table, D = 520 and 2048, 1024-bag
-tiles, block orders and slices; the gather with seven formats in one tile of positions and with more tables than it stages borders for.  The entry
+tiles, block orders and slices; the gather with seven formats in one tile of positions and with more tables than it stages borders for.
+The MXFP4 lookups (``mx4_fwd_kernel<G, U, WEIGHTED, MEAN, OT>``, ``embedding_gather_mx4_kernel<OT, G, U>``; tests/test_gpu_mx4.py runs
+one tile a table under the default block order and the gather's default unroll) are pinned in groups ``mx4_base``, ``mx4_burst``,
+``mx4_G8`` .. ``mx4_G64``, ``mx4_unroll_map``, ``mx4_orders``, ``mx4_1024``, ``mx4_direct``, ``mx4_edge``, ``mx4_wide`` and
+``mx4_gather_GU``, ``mx4_gather_16``, ``mx4_gather_knobs``: ``MX4BatchedEmbeddingBagMI355`` against ``mx4_rules.dequant`` under the
+sequential fp32 ``pool`` of tests/test_gpu_mx4.py, NaN blocks by class, under ``pm_embbag_mx4_plan`` / ``pm_embedding_gather_mx4_plan`` --
+tiles behind tile 0 with a short last one, the three block orders, several bags per lane group, the fp32, the 2-byte and no burst, 1024-bag
+tiles, a direct tile among staged ones, slices inside tiles, rows that end inside the lane group at every width and in a second column pass;
+the gather's sixteen (lane group, rows in flight) pairs with ``NB == 1``, eight 16-bit passes, mixed dims in one tile of positions (through
+the C call: the module refuses them) and more tables than it stages borders for.  The entry
 points on the base plan equal their default-knob bits and their rule; the one non-deterministic entry, the alternates' atomic backward, is held to the fuzz test's 1e-5 bar.  No tolerance is new.
 
 One test is one group: a few dozen launches on one small request.  The groups with an environment setting run in a fresh child each

@@ -389,6 +389,102 @@ def _anyfmt_conditions(cases, missing):
     assert not spare(), f"mixed-format cases that no condition depends on: {spare()}"
 
 
+def _mx4_conditions(cases, missing):
+    """the MXFP4 entries (``mx4``: pm_embbag_fwd_mx4, ``mx4_gather``: pm_embedding_gather_mx4) on ``f8_label``'s words under the family
+    word ``mx4``.  At the end: every MXFP4 case is the last one left to meet some condition."""
+    fam = [(c, w, p) for c, w, p in cases if c.entry.startswith("mx4")]
+    assert all("mx4" in w for c, w, p in fam) and not any("mx4" in w for c, w, p in cases if not c.entry.startswith("mx4"))
+    assert not any({"rounds>1", "waves>1", "carry", "bounds5"} & w for c, w, p in fam)      # (no padding row: nothing is compacted)
+    need, spare = _needs(fam, missing, "mx4")
+    pooled = lambda c, w: "pooled" in w and not c.env                                           # noqa: E731
+    tiles = lambda p: p["tiles_per_table"]                                                      # noqa: E731
+    modes = ("unweighted", "weighted", "mean")
+    # the multi-tile baseline: tiles behind tile 0 and a short last tile, two bags per lane group
+    base = lambda c, w, p: pooled(c, w) and {"G16", "bpb32", "u2", "tile>NG", "partial", "xcd0", "indexed"} <= w and tiles(p) >= 3 \
+        and c.dims[0] == 256 and c.req.B % 32                                                  # noqa: E731
+    for mode in modes:
+        need(f"baseline {mode}, fp32 rows leave one by one", lambda c, w, p: base(c, w, p) and {mode, "out-fp32", "plain"} <= w and not c.tuning.get("unroll"))
+        need(f"baseline {mode}, bf16 burst", lambda c, w, p: base(c, w, p) and {mode, "out-bf16", "staged"} <= w)
+    need("baseline bf16 with stage_out 0", lambda c, w, p: base(c, w, p) and {"out-bf16", "plain"} <= w and c.forward.get("stage_out") == 0)
+    need("baseline fp16 burst", lambda c, w, p: base(c, w, p) and {"out-fp16", "staged"} <= w)
+    for mode in modes:
+        for burst in ("staged", "plain"):
+            need(f"64-bag tiles of fp32 rows {mode} {burst}",
+                 lambda c, w, p: pooled(c, w) and {"G8", "bpb64", "u2", "tile>NG", "partial", "out-fp32", mode, burst} <= w and tiles(p) >= 18)
+    # every lane-group width x both depths x {a full group, a row that ends inside it}; mean at both depths of every width
+    for G, full, part, _ in S.MX4_GROUP_DIMS:
+        for D, ends in ((full, False), (part, True)):
+            group = lambda c, w, p: pooled(c, w) and {f"G{G}", f"bpb{512 // G}", "tile>NG", "partial", "passes1"} <= w and tiles(p) > 1 \
+                and c.dims[0] == D and c.request == "pad100" and ("row-ends-in-pass" in w) == ends and c.tuning.get("unroll")     # noqa: E731
+            for u in (2, 4):
+                for mode in modes[:2]:
+                    need(f"G{G} D{D} u{u} {mode}", lambda c, w, p: group(c, w, p) and {f"u{u}", mode} <= w)
+            need(f"G{G} D{D} mean", lambda c, w, p: group(c, w, p) and "mean" in w)
+        for u in (2, 4):
+            need(f"G{G} u{u} mean", lambda c, w, p: pooled(c, w) and {f"G{G}", f"bpb{512 // G}", f"u{u}", "mean"} <= w and c.dims[0] in (full, part))
+    # pm_set_tuning's unroll -> rows in flight
+    for u, planned in zip(S.UNROLLS, (2, 2, 2, 4, 4, 4)):
+        need(f"unroll {u} plans {planned}", lambda c, w, p: pooled(c, w) and c.tuning.get("unroll") == u and p["unroll"] == planned
+             and {"G8", "bpb32", "weighted", "staged"} <= w and c.dims[0] == 128 and c.request == "pad100")
+    for x in (0, 1, 3):
+        need(f"xcd_affine {x}, the product's tile", lambda c, w, p: pooled(c, w) and {f"xcd{x}", "G8", "bpb32", "staged", "partial", "unweighted"} <= w
+             and tiles(p) > 1 and not {"slice", "direct"} & w and c.dims == [128] * c.req.T)
+    need("xcd_affine 1 on 8 tables", lambda c, w, p: pooled(c, w) and "xcd1" in w and c.req.T == 8 and tiles(p) > 1)
+    for mode in ("unweighted", "mean"):
+        need(f"slice inside tiles {mode}", lambda c, w, p: pooled(c, w) and {"slice", "partial", mode} <= w and tiles(p) > 1
+             and c.bag_slice[0] % p["bags_per_block"] and sum(c.bag_slice) % p["bags_per_block"])
+    for mode in modes:
+        for out in ("out-fp32", "out-bf16"):
+            need(f"1024 bags {mode} {out}", lambda c, w, p: pooled(c, w) and {"bpb1024", "tile>NG", "partial", "plain", "indexed", mode, out} <= w
+                 and c.req.B > 1024)
+    # exactly the lumpy tile exceeds the index tile, the others stage their indices
+    lumpy = S.request("pad_lumpy")
+    over = [int(lumpy.off[g + 32] - lumpy.off[g]) > 1280 for g in range(0, lumpy.T * lumpy.B, 32)]
+    assert lumpy.B % 32 == 0 and sum(over) == 1 and over[1]
+    for mode in modes:
+        for u in (2, 4):
+            need(f"direct {mode} u{u}", lambda c, w, p: pooled(c, w) and {"direct", "indexed", "bpb32", mode, f"u{u}"} <= w and p["idx_cap"] == 1280
+                 and c.request == "pad_lumpy" and tiles(p) > 1)
+    # the LDS edge (embbag_fwd_mx4.hip: launch_mx4_w), byte for byte from the restated rule: both sides keep the burst ...
+    edge = lambda c, w, p: pooled(c, w) and {"bpb256", "out-bf16", "G8", "staged"} <= w and c.dims[0] == 32 and p["stage_out"] == 32           # noqa: E731
+    need("edge: weighted", lambda c, w, p: edge(c, w, p) and "weighted" in w and S.mx4_case_lds(c, list(p.values())) == 22544 + 16384)
+    need("edge: unweighted", lambda c, w, p: edge(c, w, p) and "unweighted" in w and S.mx4_case_lds(c, list(p.values())) == 18448 + 16384)
+    # ... and the launcher's 64 KiB fallback is out of reach: the largest tile any plan can ask for -- 1024 bags, 4096 index-tile entries,
+    # weights -- is 40976 bytes, the burst at most 16384.  So pm_embbag_mx4_plan's stage_out IS what runs; no case plans past the bound
+    assert S.mx4_lds_bytes(1024, 4096, True, 0, 4) == 40976 and 40976 + 16384 <= 65536
+    for c, w, p in fam:
+        if c.entry == "mx4":
+            burst = p["bags_per_block"] * p["stage_out"] * (2 if c.out16 else 4)
+            assert burst <= 16384 and p["idx_cap"] <= 4096 and p["bags_per_block"] <= 1024 and S.mx4_case_lds(c, list(p.values())) <= 57360, c.name
+            assert ("staged" in w) == (burst > 0), c.name
+    need("mixed dims, the lane group sized for 128", lambda c, w, p: pooled(c, w) and {"G8", "weighted"} <= w and c.dims == [32, 64, 128] and tiles(p) > 1)
+    wide = lambda c, w, p: pooled(c, w) and {"G32", "bpb16", "tile>NG"} <= w and c.dims[0] == 512 and tiles(p) > 1 and not c.tuning.get("unroll")  # noqa: E731
+    need("D = 512, 2-byte outputs: staged", lambda c, w, p: wide(c, w, p) and {"out-bf16", "staged"} <= w)
+    need("D = 512, 4-byte outputs: not staged", lambda c, w, p: wide(c, w, p) and {"out-fp32", "plain"} <= w and not c.forward)
+    need("a second pass that ends inside the group", lambda c, w, p: pooled(c, w) and {"G64", "passes2", "row-ends-in-pass", "weighted"} <= w and tiles(p) > 1)
+    need("two full passes", lambda c, w, p: pooled(c, w) and {"G64", "passes2"} <= w and c.dims[0] == 2048 and tiles(p) > 1)
+    need("FWD_STAGE=0", lambda c, w, p: c.env.get("PARAM_AMD_FWD_STAGE") == 0 and {"pooled", "plain", "bpb32"} <= w and tiles(p) > 1
+         and p["bags_per_block"] * c.dims[0] * 4 <= 16384)
+    # the gather: 16 (G, U) pairs over tens of tiles with a last one that is not full; NB == 1 and every larger batch count
+    gp = lambda p: dict(zip(S.GATHER_FIELDS, p.values()))                                       # noqa: E731
+    rows = lambda c, w, p: "unpooled" in w and "partial" in w and gp(p)["grid"] > 1                    # noqa: E731
+    for G in (8, 16, 32, 64):
+        for u in (1, 2, 4, 8):
+            need(f"gather G{G} u{u}", lambda c, w, p: rows(c, w, p) and {f"G{G}", f"u{u}", f"NB{G // u}", "out-fp32", "xcd1", "passes1", "lds_borders"} <= w
+                 and not {"slice", "mixed-tile"} & w and gp(p)["grid"] > 8)
+    need("gather NB == 1", lambda c, w, p: rows(c, w, p) and {"G8", "u8", "NB1"} <= w, 2)
+    for u in (1, 2, 4, 8):
+        for out in ("out-bf16", "out-fp16"):
+            need(f"gather u{u} {out}", lambda c, w, p: rows(c, w, p) and {f"u{u}", out, "passes1"} <= w)
+    need("gather xcd0", lambda c, w, p: rows(c, w, p) and "xcd0" in w)
+    need("gather two passes", lambda c, w, p: rows(c, w, p) and {"passes2", "G64", "out-fp32"} <= w and c.dims[0] == 512)
+    need("gather eight passes, 16-bit output", lambda c, w, p: rows(c, w, p) and {"passes8", "G64", "out-bf16"} <= w and c.dims[0] == 2048)
+    need("gather slice", lambda c, w, p: rows(c, w, p) and "slice" in w and c.bag_slice[0] > 0)
+    need("gather mixed dims in one tile", lambda c, w, p: rows(c, w, p) and "mixed-tile" in w and len(set(c.dims)) == 3)
+    need("gather beyond 255 tables", lambda c, w, p: rows(c, w, p) and "global_borders" in w and c.req.T > 255)
+    assert not spare(), f"MXFP4 cases that no condition depends on: {spare()}"
+
+
 def test_the_sweep_reaches_every_variant():
     """conditions on the case list -- on the labels derived from the PLANS -- so that it cannot quietly stop covering a variant"""
     rows = _pinned()
@@ -517,7 +613,9 @@ def test_the_sweep_reaches_every_variant():
     _f8_conditions(cases, missing)
     _f8s_conditions(cases, missing)
     _anyfmt_conditions(cases, missing)
-    assert {c.request for c in S.CASES if c.entry.startswith(("f8s", "anyfmt"))} - {c.request for c in S.CASES if not c.entry.startswith(("f8s", "anyfmt"))} \
+    _mx4_conditions(cases, missing)
+    newer = ("f8s", "anyfmt", "mx4")
+    assert {c.request for c in S.CASES if c.entry.startswith(newer)} - {c.request for c in S.CASES if not c.entry.startswith(newer)} \
         == {"pad600", "ragged8", "many260"}
     assert not missing, missing
     assert len(S.ENV_GROUPS) == 6 and len({tuple(sorted(c.env.items())) for c in S.CASES if c.env}) == 6
