@@ -78,7 +78,11 @@ __device__ __forceinline__ void store_pruned(char* row_out, const PrunedLoad& q,
         float f[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float v = fmaf(scale, static_cast<float>((w >> (k * width)) & mask), t);
+            float v = fmaf(scale, static_cast<float>((w >> (k * width)) & mask), t);
+            // a 16-bit output is the ONE rounding of this fp32 value.  Behind the select the compiler folded the fmaf and OT::round into
+            // v_fma_mixlo_f16, which rounds the unrounded product-sum once: another bit where the fp32 value is a 16-bit tie.  The empty
+            // statement keeps the fp32 value a value of its own (no instruction).
+            if constexpr (!std::is_same<OT, float>::value) asm volatile("" : "+v"(v));
             f[k] = pruned ? 0.0f : v;
         }
         const int c = c0 + (s * G + lig) * 4;

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.fuzz_cases import hot_row_bound
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 EXACT_RUN = 256
@@ -119,7 +121,7 @@ def test_random_request_vs_oracle(seed, coracle):
         # (atomics; also the sequential CPU oracle), and ~ (chunk + n/chunk) * 2^-24 with the sorted path's
         # ordered chunk partials: the bound widens accordingly for the 1-row / 3-row tables of this sweep.
         cnt = np.bincount(c["idx"][s:e], minlength=rows[t]).astype(np.float64)[:, None]
-        tol_sorted = np.maximum(1e-5, (256 + cnt / 32) * 2.0 ** -24) * mag + 1e-30
+        tol_sorted = hot_row_bound(cnt, mag)
         tol_atomic = np.maximum(1e-5, cnt * 2.0 ** -23) * mag + 1e-30
         got = dws[t].cpu().numpy()
         cold = cnt[:, 0] <= EXACT_RUN

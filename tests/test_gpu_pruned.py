@@ -392,3 +392,26 @@ def test_from_float_keep_quantises_the_kept_rows():
     bag = torch.nn.EmbeddingBag.from_pretrained(torch.from_numpy(xs[0]), mode="sum")
     e = QuantizedEmbeddingBagMI355.from_float(bag, bitwidth=8, keep=torch.from_numpy(masks[0]))
     assert e.pruned and np.array_equal(e.table(0).cpu().numpy(), rowquant.quantize_rows(xs[0][masks[0]], 8))
+
+
+# ---- a regression case of the family fuzz (tests/test_gpu_fuzz_families.py, a one-off soak: pruned seeds 70, 93, 141, 200) -------------
+
+def test_sequence_fp16_output_is_the_one_rounding_of_the_fp32_row():
+    """One 8-bit row, D = 8, identity remap: scale 0x3b6061b2, bias 0xbebef8f6, code 148.  The fp32 row value is
+    fmaf(scale, 148, bias) = 0x3e08f000 = 0.13372803, which lies exactly halfway between the fp16 values 0x3047 and 0x3048; the
+    unrounded product-sum is 0.133728021755.. just below it.  The rule (one rounding of the fp32 value, to nearest even) gives 0x3048;
+    the pruned un-pooled kernel gave 0x3047 -- the compiler had folded the multiply-add and the fp16 conversion into one v_fma_mixlo_f16,
+    which rounds the unrounded value once -- while its fp32 output was the rule's.  The same held at 0xbe9e3000 / 0xb4f2 (seed 70)."""
+    D = 8
+    row = np.zeros((1, R.row_bytes(D, 8)), dtype=np.uint8)
+    row[0, :D] = 148
+    row[0, D:D + 8] = np.array([0x3b6061b2, 0xbebef8f6], dtype=np.uint32).view(np.uint8)
+    remap = np.zeros(1, dtype=np.int32)
+    idx, off = np.zeros(3, dtype=np.int64), np.array([0, 1, 3], dtype=np.int64)
+    want32, written = P.gather([row], D, [8], [remap], idx, off, 2)
+    assert written.all() and (want32.view(np.uint32) == 0x3e08f000).all()
+    m = pmodule([1], [D], [8], [row], [remap])
+    assert (bits_of(m.lookup_sequence(dev(idx), dev(off), batch=2)).view(np.uint32) == 0x3e08f000).all()
+    m = pmodule([1], [D], [8], [row], [remap], output_dtype="fp16")
+    got = bits_of(m.lookup_sequence(dev(idx), dev(off), batch=2))
+    assert (O.round16(want32, "fp16") == 0x3048).all() and np.array_equal(got, O.round16(want32, "fp16")), hex(int(got[0, 0]))
