@@ -296,6 +296,47 @@ int pm_embbag_sparse_grad(const pm_embbag_batch* op, const float* grad, int64_t 
                           int64_t* const* row_ids, float* const* values, pm_stream_t stream);
 
 /*
+ * SPARSE-ROW ADAM.  Lazy Adam / AdamW over coalesced sparse gradients (csrc/sparse_rows_adam.hip): ONE launch applies the rule to
+ * num_tables tables, to the rows the gradient lists and to no other -- what torch.optim.SparseAdam does to a parameter with a coalesced
+ * sparse .grad (bias-corrected, no amsgrad), plus decoupled weight decay on the touched rows.  The gradient is what pm_embbag_sparse_grad
+ * writes: row_ids[t] = int64[U_t], DISTINCT within a table (any order) and below the table's row count -- the caller's contract, nothing
+ * on the device checks it --, values[t] = float[U_t * dims[t]], 16-byte aligned.  exp_avg[t] / exp_avg_sq[t]: fp32 [rows_t, dims_t], the
+ * state, always fp32; tables[t]: [rows_t, dims_t] of table_dtype (PM_F32 | PM_BF16 | PM_F16), 16-byte aligned.  row_prefix: device
+ * int64 [num_tables + 1], row_prefix[t] = U_0 + .. + U_{t-1}; num_rows = row_prefix[num_tables] (host).  tables, row_ids, values,
+ * exp_avg, exp_avg_sq and dims are device arrays [num_tables]; entries of a table with U_t = 0 are never read.
+ * The caller computes the step's scalars in double precision and rounds each ONCE to fp32 (pm_sparse_adam):
+ *     c1 = 1 - beta1,   c2 = 1 - beta2,   eps,   step_size s = lr * sqrt(1 - beta2^step) / (1 - beta1^step),   decay d = 1 - lr * weight_decay
+ * Per listed row and column, g = the gradient value (-g with maximize), w = the stored weight widened exactly to fp32:
+ *     w0 = w * d   (d != 1; otherwise w)
+ *     m' = m + (g - m) * c1
+ *     v' = v + (g * g - v) * c2
+ *     w' = conv(w0 - s * (m' / (sqrt(v') + eps)))
+ * Every operation is rounded to fp32 on its own, in this order, nothing is contracted into a fused multiply-add, sqrt and the division
+ * are correctly rounded; conv is the identity for PM_F32 and ONE round-to-nearest-even for PM_BF16 / PM_F16.  numpy restates the rule
+ * exactly (tests/sparse_adam_rules.py) and the kernel is held to it bit for bit; with d = 1 it is torch.optim.SparseAdam's rule.
+ * nontemporal (0 / 1): non-temporal accesses for values, exp_avg and exp_avg_sq, which a step touches once -- a cache policy, the
+ * result does not depend on it.
+ * Refused before any HIP call: a NULL opt, an unknown table_dtype, negative num_tables / num_rows, a non-finite scalar, maximize /
+ * nontemporal not 0 or 1 (PM_ERR_INVALID); max_dim (the largest dims[t]) not a positive multiple of 4 or above 4096, num_rows of 2^39
+ * or more (PM_ERR_UNSUPPORTED).  num_tables == 0 or num_rows == 0 is then PM_OK without a launch or a device; otherwise a NULL array
+ * is PM_ERR_INVALID.  Stream-ordered; never synchronises.  The ABI version is unchanged (8): a client that needs the call finds out at
+ * symbol resolution.
+ */
+typedef struct pm_sparse_adam {
+    float c1;
+    float c2;
+    float eps;
+    float step_size;
+    float decay;
+    int32_t maximize;
+    int32_t nontemporal;
+    int32_t reserved;
+} pm_sparse_adam;
+int pm_sparse_rows_adam(int32_t num_tables, int64_t num_rows, int32_t max_dim, void* const* tables, int32_t table_dtype,
+                        const int64_t* const* row_ids, const float* const* values, float* const* exp_avg, float* const* exp_avg_sq,
+                        const int32_t* dims, const int64_t* row_prefix, const pm_sparse_adam* opt, pm_stream_t stream);
+
+/*
  * Fused backward + exact row-wise Adagrad (the optimizer the reference configures for its TBE ops,
  * train/comms/pt/comms_utils.py:2014 and split_table_batched_embeddings_ops.py:289; algorithm as
  * published by fbgemm_gpu): per touched row r of table t,

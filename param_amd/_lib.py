@@ -120,6 +120,7 @@ EXPORTED_SYMBOLS = (
     "pm_embbag_mx4_plan",
     "pm_embedding_gather_mx4",
     "pm_embedding_gather_mx4_plan",
+    "pm_sparse_rows_adam",
 )
 # table element types of the FP8 lookups alone (include/param_amd.h, FP8 TABLES): every other entry point refuses them
 PM_F8E4M3, PM_F8E5M2 = 3, 4
@@ -146,6 +147,21 @@ class pm_rowwise_adagrad(ctypes.Structure):
         ("stochastic_rounding", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
         ("seed", ctypes.c_uint64),
+    ]
+
+
+class pm_sparse_adam(ctypes.Structure):
+    """Mirror of ``struct pm_sparse_adam`` (include/param_amd.h): one step's scalars, each rounded once to fp32 by the caller."""
+
+    _fields_ = [
+        ("c1", ctypes.c_float),
+        ("c2", ctypes.c_float),
+        ("eps", ctypes.c_float),
+        ("step_size", ctypes.c_float),
+        ("decay", ctypes.c_float),
+        ("maximize", ctypes.c_int32),
+        ("nontemporal", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
     ]
 
 
@@ -298,6 +314,8 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embbag_sparse_grad_count.argtypes = [ctypes.POINTER(pm_embbag_batch), i64, vp, i64, vp, vp]
     L.pm_embbag_sparse_grad.restype = ctypes.c_int
     L.pm_embbag_sparse_grad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i64, vp, i64, vp, vp, vp]
+    L.pm_sparse_rows_adam.restype = ctypes.c_int
+    L.pm_sparse_rows_adam.argtypes = [i32, i64, i32, vp, i32, vp, vp, vp, vp, vp, vp, ctypes.POINTER(pm_sparse_adam), vp]
     L.pm_embbag_psw_grad.restype = ctypes.c_int
     L.pm_embbag_psw_grad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp]
     L.pm_embbag_bounds_check_scratch.restype = ctypes.c_int64

@@ -1,5 +1,6 @@
 // param_amd/csrc/capi.hip -- extern "C" entry points of libparam_amd.so (include/param_amd.h).
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -1809,6 +1810,28 @@ int pm_embbag_max_bwd(const pm_embbag_batch* op, const void* grad, int32_t grad_
     const hipError_t h = pm::launch_max_bwd(p, op->max_dim, mp, static_cast<char*>(workspace) + sorted, grad, grad_dtype, max_indices, dst_dtype,
                                             alpha, static_cast<hipStream_t>(stream));
     if (h != hipSuccess) return hip_fail(h, "pm_embbag_max_bwd launch");
+    return PM_OK;
+}
+
+// ---- lazy Adam over coalesced sparse gradients (sparse_rows_adam.hip) -------------------------------------------------------------------
+int pm_sparse_rows_adam(int32_t num_tables, int64_t num_rows, int32_t max_dim, void* const* tables, int32_t table_dtype,
+                        const int64_t* const* row_ids, const float* const* values, float* const* exp_avg, float* const* exp_avg_sq,
+                        const int32_t* dims, const int64_t* row_prefix, const pm_sparse_adam* opt, pm_stream_t stream) {
+    if (!opt) return fail(PM_ERR_INVALID, "pm_sparse_rows_adam: opt is NULL");
+    if (!dtype_is_weight(table_dtype)) return fail(PM_ERR_INVALID, "pm_sparse_rows_adam: table_dtype must be PM_F32, PM_BF16 or PM_F16");
+    if (num_tables < 0 || num_rows < 0) return fail(PM_ERR_INVALID, "pm_sparse_rows_adam: negative num_tables / num_rows");
+    for (const float x : {opt->c1, opt->c2, opt->eps, opt->step_size, opt->decay})
+        if (!std::isfinite(x)) return fail(PM_ERR_INVALID, "pm_sparse_rows_adam: c1, c2, eps, step_size and decay must be finite");
+    if ((opt->maximize | opt->nontemporal) & ~1) return fail(PM_ERR_INVALID, "pm_sparse_rows_adam: maximize / nontemporal must be 0 or 1");
+    if (max_dim < 4 || max_dim % 4 != 0 || max_dim > 4096)
+        return fail(PM_ERR_UNSUPPORTED, "pm_sparse_rows_adam: every dims[t] (and max_dim) must be a multiple of 4 in [4, 4096]");
+    if (num_rows >= (1LL << 39)) return fail(PM_ERR_UNSUPPORTED, "pm_sparse_rows_adam: num_rows must be below 2^39 (grid too large)");
+    if (num_tables == 0 || num_rows == 0) return PM_OK;
+    if (!tables || !row_ids || !values || !exp_avg || !exp_avg_sq || !dims || !row_prefix)
+        return fail(PM_ERR_INVALID, "pm_sparse_rows_adam: tables / row_ids / values / exp_avg / exp_avg_sq / dims / row_prefix is NULL");
+    const hipError_t h = pm::launch_sparse_rows_adam(num_tables, num_rows, tables, table_dtype, row_ids, values, exp_avg, exp_avg_sq, dims,
+                                                     row_prefix, opt, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_sparse_rows_adam launch");
     return PM_OK;
 }
 

@@ -527,6 +527,11 @@ hipError_t sparse_grad_count(const SparsePairs& sp, int T, int64_t n, void* extr
 hipError_t sparse_grad_rows(const SparsePairs& sp, int T, int64_t n, const void* extra, const int32_t* dims, int64_t* const* row_ids,
                             float* const* values, hipStream_t stream);
 
+// lazy Adam over coalesced sparse gradients (sparse_rows_adam.hip): every array a device array of T entries (prefix: T + 1), U >= 1 rows
+hipError_t launch_sparse_rows_adam(int T, int64_t U, void* const* tables, int table_dtype, const int64_t* const* row_ids,
+                                   const float* const* values, float* const* m, float* const* v, const int32_t* dims,
+                                   const int64_t* prefix, const pm_sparse_adam* opt, hipStream_t stream);
+
 // direct backward of max pooling (embbag_max_bwd.hip): the pairs of the complete pooled, unweighted key sort last issued on a workspace,
 // and the sorted apply's four control words, which that sort's first kernel zeroes (ctl[0] counts the hot runs the main kernel lists)
 struct MaxBwdPairs {
