@@ -337,6 +337,48 @@ int pm_sparse_rows_adam(int32_t num_tables, int64_t num_rows, int32_t max_dim, v
                         const int32_t* dims, const int64_t* row_prefix, const pm_sparse_adam* opt, pm_stream_t stream);
 
 /*
+ * SPARSE-ROW ADAGRAD AND SGD.  torch.optim.Adagrad (element-wise), row-wise Adagrad and torch.optim.SGD (no momentum, no weight decay)
+ * over coalesced sparse gradients (csrc/sparse_rows_step.hip): ONE launch applies the rule to num_tables tables, to the rows the
+ * gradient lists and to no other.  tables, table_dtype, row_ids, values, dims, row_prefix, num_rows and max_dim are
+ * pm_sparse_rows_adam's (SPARSE-ROW ADAM above), with the same contract on the row ids.  state_sum[t] (Adagrad): fp32, always;
+ * [rows_t, dims_t] for the element-wise rule, [rows_t] -- one value per row -- for the row-wise one.
+ * The caller computes in double precision and rounds ONCE to fp32:
+ *     alpha = -(lr / (1 + (step - 1) * lr_decay))   (Adagrad; step counts from 1)        alpha = -lr   (SGD)        eps
+ * Per listed row and column, g = the gradient value (-g with maximize, exact), w = the stored weight widened exactly to fp32:
+ *     SGD          w' = conv(fmaf(alpha, g, w))
+ *     element-wise s' = s + g * g ;   q = g / (sqrt(s') + eps) ;   w' = conv(fmaf(alpha, q, w))
+ *     row-wise     s' = s + S / (float)D ;   mult = alpha / (sqrt(s') + eps) ;   w'[c] = conv(fmaf(mult, g[c], w[c]))
+ * Every operation is rounded to fp32 on its own; fmaf is a true fused multiply-add (one rounding) and nothing else is contracted; sqrt
+ * and the division are correctly rounded; conv is the identity for PM_F32 and ONE round-to-nearest-even for PM_BF16 / PM_F16.
+ * S, the row's sum of squares (fbgemm's EXACT_ROWWISE_ADAGRAD keeps the mean square per row), has a fixed order: a row of D columns
+ * takes G = next_pow2(D / 4) lanes, at most 64; lane l owns columns 4 (pass * G + l) + k, k = 0..3; its partial starts at +0.0 and adds
+ * fl(g * g) with pass ascending, then k ascending, columns past D adding nothing; the G partials are combined by an xor butterfly with
+ * masks 1, 2, 4, .., G / 2, low mask first.  S is a function of the row alone.
+ * With fp32 tables the SGD and element-wise rules give torch.optim.SGD's and torch.optim.Adagrad's bits on a coalesced sparse gradient.
+ * numpy restates the three rules exactly (tests/sparse_step_rules.py) and the kernel is held to that bit for bit.
+ * nontemporal (0 / 1): non-temporal accesses for values and for an element-wise state_sum -- a cache policy, the result does not
+ * depend on it.
+ * Refusals are pm_sparse_rows_adam's, before any HIP call: a NULL opt (Adagrad), an unknown table_dtype, negative num_tables /
+ * num_rows, a non-finite scalar, a flag not 0 or 1 (PM_ERR_INVALID); max_dim not a positive multiple of 4 or above 4096, num_rows of
+ * 2^39 or more (PM_ERR_UNSUPPORTED).  num_tables == 0 or num_rows == 0 is then PM_OK without a launch or a device; otherwise a NULL
+ * array is PM_ERR_INVALID.  Stream-ordered; never synchronises.  The ABI version is unchanged (8).
+ */
+typedef struct pm_sparse_adagrad {
+    float alpha;
+    float eps;
+    int32_t rowwise;
+    int32_t maximize;
+    int32_t nontemporal;
+    int32_t reserved;
+} pm_sparse_adagrad;
+int pm_sparse_rows_adagrad(int32_t num_tables, int64_t num_rows, int32_t max_dim, void* const* tables, int32_t table_dtype,
+                           const int64_t* const* row_ids, const float* const* values, float* const* state_sum, const int32_t* dims,
+                           const int64_t* row_prefix, const pm_sparse_adagrad* opt, pm_stream_t stream);
+int pm_sparse_rows_sgd(int32_t num_tables, int64_t num_rows, int32_t max_dim, void* const* tables, int32_t table_dtype,
+                       const int64_t* const* row_ids, const float* const* values, const int32_t* dims, const int64_t* row_prefix,
+                       float alpha, int32_t maximize, int32_t nontemporal, pm_stream_t stream);
+
+/*
  * Fused backward + exact row-wise Adagrad (the optimizer the reference configures for its TBE ops,
  * train/comms/pt/comms_utils.py:2014 and split_table_batched_embeddings_ops.py:289; algorithm as
  * published by fbgemm_gpu): per touched row r of table t,

@@ -13,7 +13,8 @@ Layout (only what the hot path needs):
                      (fp32 / bf16 / fp16 / FP8 / 8- / 4-bit rows), one launch
   mx4_bag.py         MX4BatchedEmbeddingBagMI355: pooled and un-pooled lookups over OCP MXFP4 tables (block-scaled 4-bit) and the HIP
                      quantiser that writes them
-  optim.py           SparseAdamMI355 / sparse_adam_rows_: lazy Adam / AdamW over the coalesced sparse gradients of the sparse=True modules
+  optim.py           SparseAdamMI355 / sparse_adam_rows_: lazy Adam / AdamW over the coalesced sparse gradients of the sparse=True modules;
+                     SparseAdagradMI355 (element-wise or row-wise) / SparseSGDMI355 and their *_rows_ functions over the same gradients
   indices.py         uniform / Zipf index generation (reference init_indices + a scalable form)
   compute/pt/        mirror of the reference train/compute/pt emb driver CLI
   comms/pt/          mirror of the reference train/comms/pt backend plug-in, metrics and drivers
@@ -32,6 +33,7 @@ from .quantized_bag import QuantizedBatchedEmbeddingBagMI355, QuantizedEmbedding
 from .float8_bag import Float8BatchedEmbeddingBagMI355, Float8EmbeddingBagMI355, Float8EmbeddingMI355  # noqa: F401
 from .mixed_bag import MixedBatchedEmbeddingBagMI355  # noqa: F401
 from .mx4_bag import MX4BatchedEmbeddingBagMI355  # noqa: F401
-from .optim import SparseAdamMI355, sparse_adam_rows_  # noqa: F401
+from .optim import (SparseAdagradMI355, SparseAdamMI355, SparseSGDMI355, sparse_adagrad_rows_, sparse_adam_rows_,  # noqa: F401
+                    sparse_sgd_rows_)
 
 __version__ = "0.1.0"

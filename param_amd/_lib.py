@@ -121,6 +121,8 @@ EXPORTED_SYMBOLS = (
     "pm_embedding_gather_mx4",
     "pm_embedding_gather_mx4_plan",
     "pm_sparse_rows_adam",
+    "pm_sparse_rows_adagrad",
+    "pm_sparse_rows_sgd",
 )
 # table element types of the FP8 lookups alone (include/param_amd.h, FP8 TABLES): every other entry point refuses them
 PM_F8E4M3, PM_F8E5M2 = 3, 4
@@ -159,6 +161,19 @@ class pm_sparse_adam(ctypes.Structure):
         ("eps", ctypes.c_float),
         ("step_size", ctypes.c_float),
         ("decay", ctypes.c_float),
+        ("maximize", ctypes.c_int32),
+        ("nontemporal", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class pm_sparse_adagrad(ctypes.Structure):
+    """Mirror of ``struct pm_sparse_adagrad`` (include/param_amd.h): ``alpha`` and ``eps`` rounded once to fp32 by the caller."""
+
+    _fields_ = [
+        ("alpha", ctypes.c_float),
+        ("eps", ctypes.c_float),
+        ("rowwise", ctypes.c_int32),
         ("maximize", ctypes.c_int32),
         ("nontemporal", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
@@ -316,6 +331,10 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embbag_sparse_grad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i64, vp, i64, vp, vp, vp]
     L.pm_sparse_rows_adam.restype = ctypes.c_int
     L.pm_sparse_rows_adam.argtypes = [i32, i64, i32, vp, i32, vp, vp, vp, vp, vp, vp, ctypes.POINTER(pm_sparse_adam), vp]
+    L.pm_sparse_rows_adagrad.restype = ctypes.c_int
+    L.pm_sparse_rows_adagrad.argtypes = [i32, i64, i32, vp, i32, vp, vp, vp, vp, vp, ctypes.POINTER(pm_sparse_adagrad), vp]
+    L.pm_sparse_rows_sgd.restype = ctypes.c_int
+    L.pm_sparse_rows_sgd.argtypes = [i32, i64, i32, vp, i32, vp, vp, vp, vp, ctypes.c_float, i32, i32, vp]
     L.pm_embbag_psw_grad.restype = ctypes.c_int
     L.pm_embbag_psw_grad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, vp, vp]
     L.pm_embbag_bounds_check_scratch.restype = ctypes.c_int64

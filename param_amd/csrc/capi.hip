@@ -3,6 +3,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 #include <string>
 
 #include "common.h"
@@ -1832,6 +1833,57 @@ int pm_sparse_rows_adam(int32_t num_tables, int64_t num_rows, int32_t max_dim, v
     const hipError_t h = pm::launch_sparse_rows_adam(num_tables, num_rows, tables, table_dtype, row_ids, values, exp_avg, exp_avg_sq, dims,
                                                      row_prefix, opt, static_cast<hipStream_t>(stream));
     if (h != hipSuccess) return hip_fail(h, "pm_sparse_rows_adam launch");
+    return PM_OK;
+}
+
+// ---- SGD and Adagrad over coalesced sparse gradients (sparse_rows_step.hip) ---------------------------------------------------------------
+// the refusals the two entry points share with pm_sparse_rows_adam, before any HIP call; `done`: PM_OK without a launch.
+// scalar_names / flag_names / array_names: the entry point's own arguments, for the messages
+static int sparse_step_checks(const std::string& who, int32_t num_tables, int64_t num_rows, int32_t max_dim, int32_t table_dtype,
+                              std::initializer_list<float> scalars, const char* scalar_names, int32_t flags, const char* flag_names,
+                              bool arrays, const char* array_names, bool& done) {
+    done = false;
+    if (!dtype_is_weight(table_dtype)) return fail(PM_ERR_INVALID, who + ": table_dtype must be PM_F32, PM_BF16 or PM_F16");
+    if (num_tables < 0 || num_rows < 0) return fail(PM_ERR_INVALID, who + ": negative num_tables / num_rows");
+    for (const float x : scalars)
+        if (!std::isfinite(x)) return fail(PM_ERR_INVALID, who + ": " + scalar_names + " must be finite");
+    if (flags & ~1) return fail(PM_ERR_INVALID, who + ": " + flag_names + " must be 0 or 1");
+    if (max_dim < 4 || max_dim % 4 != 0 || max_dim > 4096)
+        return fail(PM_ERR_UNSUPPORTED, who + ": every dims[t] (and max_dim) must be a multiple of 4 in [4, 4096]");
+    if (num_rows >= (1LL << 39)) return fail(PM_ERR_UNSUPPORTED, who + ": num_rows must be below 2^39 (grid too large)");
+    done = num_tables == 0 || num_rows == 0;
+    if (!done && !arrays) return fail(PM_ERR_INVALID, who + ": " + array_names + " is NULL");
+    return PM_OK;
+}
+
+int pm_sparse_rows_adagrad(int32_t num_tables, int64_t num_rows, int32_t max_dim, void* const* tables, int32_t table_dtype,
+                           const int64_t* const* row_ids, const float* const* values, float* const* state_sum, const int32_t* dims,
+                           const int64_t* row_prefix, const pm_sparse_adagrad* opt, pm_stream_t stream) {
+    if (!opt) return fail(PM_ERR_INVALID, "pm_sparse_rows_adagrad: opt is NULL");
+    bool done;
+    const int rc = sparse_step_checks("pm_sparse_rows_adagrad", num_tables, num_rows, max_dim, table_dtype, {opt->alpha, opt->eps},
+                                      "alpha and eps", opt->rowwise | opt->maximize | opt->nontemporal, "rowwise / maximize / nontemporal",
+                                      tables && row_ids && values && state_sum && dims && row_prefix,
+                                      "tables / row_ids / values / state_sum / dims / row_prefix", done);
+    if (rc != PM_OK || done) return rc;
+    const hipError_t h = pm::launch_sparse_rows_step(num_tables, num_rows, tables, table_dtype, row_ids, values, state_sum, dims, row_prefix,
+                                                     opt->alpha, opt->eps, opt->rowwise != 0, opt->maximize != 0, opt->nontemporal != 0,
+                                                     static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_sparse_rows_adagrad launch");
+    return PM_OK;
+}
+
+int pm_sparse_rows_sgd(int32_t num_tables, int64_t num_rows, int32_t max_dim, void* const* tables, int32_t table_dtype,
+                       const int64_t* const* row_ids, const float* const* values, const int32_t* dims, const int64_t* row_prefix,
+                       float alpha, int32_t maximize, int32_t nontemporal, pm_stream_t stream) {
+    bool done;
+    const int rc = sparse_step_checks("pm_sparse_rows_sgd", num_tables, num_rows, max_dim, table_dtype, {alpha}, "alpha",
+                                      maximize | nontemporal, "maximize / nontemporal", tables && row_ids && values && dims && row_prefix,
+                                      "tables / row_ids / values / dims / row_prefix", done);
+    if (rc != PM_OK || done) return rc;
+    const hipError_t h = pm::launch_sparse_rows_step(num_tables, num_rows, tables, table_dtype, row_ids, values, nullptr, dims, row_prefix,
+                                                     alpha, 0.0f, false, maximize != 0, nontemporal != 0, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_sparse_rows_sgd launch");
     return PM_OK;
 }
 

@@ -532,6 +532,11 @@ hipError_t launch_sparse_rows_adam(int T, int64_t U, void* const* tables, int ta
                                    const float* const* values, float* const* m, float* const* v, const int32_t* dims,
                                    const int64_t* prefix, const pm_sparse_adam* opt, hipStream_t stream);
 
+// SGD / Adagrad / row-wise Adagrad over the same gradients (sparse_rows_step.hip).  state == nullptr: SGD; else Adagrad (`rowwise`: one value per row)
+hipError_t launch_sparse_rows_step(int T, int64_t U, void* const* tables, int table_dtype, const int64_t* const* row_ids,
+                                   const float* const* values, float* const* state, const int32_t* dims, const int64_t* prefix,
+                                   float alpha, float eps, bool rowwise, bool maximize, bool nontemporal, hipStream_t stream);
+
 // direct backward of max pooling (embbag_max_bwd.hip): the pairs of the complete pooled, unweighted key sort last issued on a workspace,
 // and the sorted apply's four control words, which that sort's first kernel zeroes (ctl[0] counts the hot runs the main kernel lists)
 struct MaxBwdPairs {

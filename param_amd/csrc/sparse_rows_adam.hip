@@ -20,15 +20,13 @@
 //      nothing -- so the batch is straight-line code.  g, m and v are touched once per step: non-temporal when NT (the entry point's
 //      cache-policy switch, a speed matter only); w takes plain accesses, the next forward reads it.
 // No atomics, no inline assembly, no scratch, no cross-lane operation.
-#include "common.h"
-#include "fwd_elem.h"
+#include "sparse_rows_walk.h"
 
 namespace pm {
 namespace {
 
-using namespace fwd;
+using namespace rows;
 
-constexpr int kAdamLdsPrefix = 256;   // prefix entries the LDS copy holds: T + 1 <= 256, i.e. up to 255 tables
 constexpr int kAdamRows = 4;          // rows in flight per lane group (fp32: 4 x 16 VGPRs of row data; no kernel spills)
 
 struct AdamArgs {
@@ -47,50 +45,6 @@ struct AdamArgs {
     float c1, c2, eps, s, d;
 };
 
-// log2 of the lanes a row of D columns takes: next_pow2(D / 4), capped at 64
-__device__ __forceinline__ int adam_group_log2(int D) {
-    int lg = 0;
-    while (lg < 6 && (4 << lg) < D) ++lg;
-    return lg;
-}
-
-template <bool NT>
-__device__ __forceinline__ f32x4 adam_load4(int64_t base, int c) {
-    const PM_GLOBAL f32x4* q = reinterpret_cast<const PM_GLOBAL f32x4*>(base) + (c >> 2);
-    return NT ? __builtin_nontemporal_load(q) : *q;
-}
-template <bool NT>
-__device__ __forceinline__ void adam_store4(int64_t base, int c, const f32x4& x) {
-    PM_GLOBAL f32x4* q = reinterpret_cast<PM_GLOBAL f32x4*>(base) + (c >> 2);
-    if (NT) __builtin_nontemporal_store(x, q); else *q = x;
-}
-
-// four columns of a weight row, widened exactly, and back with the table type's one rounding (fp32: the identity)
-template <typename WT> struct AdamW;
-template <> struct AdamW<float> {
-    typedef f32x4 raw_t;
-    __device__ static __forceinline__ float widen(const raw_t& r, int k) { return r[k]; }
-    __device__ static __forceinline__ raw_t pack(const float (&f)[4]) { return raw_t{f[0], f[1], f[2], f[3]}; }
-};
-template <> struct AdamW<bf16_t> {
-    typedef u32x2 raw_t;
-    __device__ static __forceinline__ float widen(const raw_t& r, int k) {
-        return __uint_as_float((k & 1) ? (r[k >> 1] & 0xffff0000u) : (r[k >> 1] << 16));
-    }
-    __device__ static __forceinline__ raw_t pack(const float (&f)[4]) {
-        return raw_t{f32_to_bf16_rne(f[0]) | (f32_to_bf16_rne(f[1]) << 16), f32_to_bf16_rne(f[2]) | (f32_to_bf16_rne(f[3]) << 16)};
-    }
-};
-template <> struct AdamW<f16_t> {
-    typedef u32x2 raw_t;
-    __device__ static __forceinline__ float widen(const raw_t& r, int k) {
-        return static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>((k & 1) ? (r[k >> 1] >> 16) : (r[k >> 1] & 0xffffu))));
-    }
-    __device__ static __forceinline__ raw_t pack(const float (&f)[4]) {
-        return raw_t{OutF16::round(f[0]) | (OutF16::round(f[1]) << 16), OutF16::round(f[2]) | (OutF16::round(f[3]) << 16)};
-    }
-};
-
 template <typename WT, bool NT>
 __global__ void __launch_bounds__(kBlock) sparse_rows_adam_kernel(const AdamArgs a) {
     typedef typename AdamW<WT>::raw_t wraw_t;
@@ -105,20 +59,14 @@ __global__ void __launch_bounds__(kBlock) sparse_rows_adam_kernel(const AdamArgs
     const int n = a.U - j0 < kBlock ? static_cast<int>(a.U - j0) : kBlock;   // slots of this tile (>= 1: the grid is ceil(U / kBlock))
     const int64_t j = j0 + tid;
 
-    // 1. the slot's table: the first t with prefix[t + 1] > j (tables without rows are passed over: equal neighbouring entries)
-    int lo = 0, hi = a.T - 1;
+    // 1. the slot's table (sparse_rows_walk.h), from the LDS copy of the prefix or from global memory
+    int lo;
     if (a.lds_prefix) {
         if (tid <= a.T) s_prefix[tid] = a.prefix[tid];
         __syncthreads();
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (s_prefix[mid + 1] <= j) lo = mid + 1; else hi = mid;
-        }
+        lo = slot_table(s_prefix, a.T, j);
     } else {
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (a.prefix[mid + 1] <= j) lo = mid + 1; else hi = mid;
-        }
+        lo = slot_table(a.prefix, a.T, j);
     }
     if (tid < n) {
         const int t = lo;
@@ -144,14 +92,8 @@ __global__ void __launch_bounds__(kBlock) sparse_rows_adam_kernel(const AdamArgs
         const int lg = adam_group_log2(s_dim[b]);
         int d_max = 0;
         const int run0 = b;
-        for (; t <= t_last; ++t) {                                           // tables [t, ..) of this width: the run ends where the last ends
-            const int64_t end = (a.lds_prefix ? s_prefix[t + 1] : a.prefix[t + 1]) - j0;
-            if (end <= b) continue;                                          // a table without rows: no slot, whatever its width
-            const int D = a.dims[t];
-            if (adam_group_log2(D) != lg) break;                             // (never the table of slot b: the run grows by at least that one)
-            b = end < n ? static_cast<int>(end) : n;
-            d_max = D > d_max ? D : d_max;
-        }
+        b = a.lds_prefix ? run_end(s_prefix, a.dims, j0, n, t_last, lg, b, t, d_max)   // tables [t, ..) of this width
+                         : run_end(a.prefix, a.dims, j0, n, t_last, lg, b, t, d_max);
         const int G = 1 << lg, NG = kBlock >> lg;
         const int gid = tid >> lg, lig = tid & (G - 1);
         const int passes = (d_max + 4 * G - 1) / (4 * G);                    // > 1 only for G = 64 and rows wider than 256 columns
