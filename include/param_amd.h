@@ -337,6 +337,46 @@ int pm_sparse_rows_adam(int32_t num_tables, int64_t num_rows, int32_t max_dim, v
                         const int32_t* dims, const int64_t* row_prefix, const pm_sparse_adam* opt, pm_stream_t stream);
 
 /*
+ * FUSED LAZY ADAM.  The SPARSE-ROW ADAM rule above applied inside the deterministic backward of a sum-pooled forward
+ * (csrc/embbag_bwd_adam.hip): a row's summed gradient is formed in registers from the [B, sum D]-sized grad and the row is updated at
+ * once; no coalesced gradient is written or read back.  tests/adam_bag_rules.py restates the rule in numpy.
+ *
+ * RULE      For table t and row r, take the lookups of r in bags inside the slice: bags ascending, in index order inside a bag (r's RUN
+ *           in the request's key sort).  A bag that holds r twice counts TWICE (unlike max pooling).  A run of at most 256 lookups
+ *           (kExactRun): G[c] = the fp32 sum of grad(t, bag)[c] in that order, one addition after the other starting from +0.0 -- the
+ *           pooled sorted apply's summation, the value pm_embbag_sparse_grad returns for the row, bit for bit.  A longer run is cut
+ *           into PIECES of 256 lookups counted from its first lookup; every piece is summed that way from +0.0 and the pieces are added
+ *           in ascending order starting from the first piece.  G is a function of the request alone -- not of the grid, a tunable or
+ *           timing.  A 16-bit grad is widened exactly in the kernel's loads.  (w, m, v)[r] is then updated from G by the rule of
+ *           SPARSE-ROW ADAM, unchanged: the same pm_sparse_adam scalars, the same operations in the same order.
+ * LAZY      A row with no lookup in the slice is neither read nor written: w, exp_avg and exp_avg_sq keep their bits.  pad_rows
+ *           (device int64 [T], -1: none; may be NULL): the run of a table's padding row is skipped whole, state included.
+ *
+ * pm_embbag_bwd_adam_workspace  bytes of caller-owned device scratch: pm_embbag_bwd_sorted_workspace of the request, then a list of hot
+ *                               run counter of the call's own, a list of hot runs and two fp32 partial rows per 256 lookups.
+ * pm_embbag_bwd_adam            sort + update in one call: pm_embbag_sort_indices (one phase; it never defers) on the workspace, then at
+ *                               most three launches -- one that zeroes the hot-run counter, the main kernel over tiles of 1024 sorted pairs, which finishes every run of at
+ *                               most 256 lookups (one row, one owner, no atomics on tables or state), and a small kernel that adds the
+ *                               pieces of the longer runs in order and updates those rows.  grad (grad_dtype PM_F32 | PM_BF16 | PM_F16)
+ *                               is addressed like the forward's out; tables: device array [T] of table_dtype (PM_F32 | PM_BF16 |
+ *                               PM_F16), rows 16-byte aligned; exp_avg / exp_avg_sq: device arrays [T] of fp32 [rows_t, dims_t].
+ * Refused before any HIP call: what pm_embbag_max_bwd refuses of the request (per_sample_weights and blocked layouts PM_ERR_UNSUPPORTED,
+ * an unknown dtype PM_ERR_INVALID; num_indices or batch >= 2^32, more than 1024 tables PM_ERR_UNSUPPORTED); a NULL opt, a non-finite
+ * scalar, maximize / nontemporal not 0 or 1 (PM_ERR_INVALID).  num_indices == 0 or bag_count == 0 is then PM_OK without a launch or a
+ * device; otherwise a NULL grad / tables / exp_avg / exp_avg_sq, a misaligned grad, a NULL, misaligned or too small workspace are
+ * PM_ERR_INVALID.  Stream-ordered; never synchronises.  The ABI version is unchanged (8).
+ * AFTER THE CALL the workspace holds the request's complete one-phase key sort, exactly as pm_embbag_sort_indices leaves it: the call
+ * writes only behind the sorted backward's part of the workspace and touches none of the sorted apply's control words, so a
+ * pm_embbag_bwd_sorted of the same request on the same workspace may consume the sort.  (pm_embbag_max_bwd differs: it counts its hot
+ * runs in the sorted apply's control word 0 and leaves the count there; sort again before a sorted apply on that workspace.)
+ * Left out: amsgrad, coupled L2, stochastic rounding, 16-bit state, per_sample_weights, sequence requests, blocked layouts.
+ */
+int64_t pm_embbag_bwd_adam_workspace(const pm_embbag_batch* op, int64_t max_rows);
+int pm_embbag_bwd_adam(const pm_embbag_batch* op, const void* grad, int32_t grad_dtype, void* const* tables, int32_t table_dtype,
+                       float* const* exp_avg, float* const* exp_avg_sq, const int64_t* pad_rows /* device [T], -1: none; may be NULL */,
+                       const pm_sparse_adam* opt, int64_t max_rows, void* workspace, int64_t workspace_bytes, pm_stream_t stream);
+
+/*
  * SPARSE-ROW ADAGRAD AND SGD.  torch.optim.Adagrad (element-wise), row-wise Adagrad and torch.optim.SGD (no momentum, no weight decay)
  * over coalesced sparse gradients (csrc/sparse_rows_step.hip): ONE launch applies the rule to num_tables tables, to the rows the
  * gradient lists and to no other.  tables, table_dtype, row_ids, values, dims, row_prefix, num_rows and max_dim are

@@ -4,7 +4,8 @@ Layout (only what the hot path needs):
   csrc/              hand-written HIP kernels + the C ABI (include/param_amd.h) -> libparam_amd.so
   _lib.py            ctypes binding (no fallback: raises if the library is missing)
   embedding_bag.py   EmbeddingBagMI355 / BatchedEmbeddingBagMI355 (nn.EmbeddingBag / TBE surface), EmbeddingMI355 (nn.Embedding),
-                     MaxEmbeddingBagMI355 / MaxBatchedEmbeddingBagMI355 (max pooling)
+                     MaxEmbeddingBagMI355 / MaxBatchedEmbeddingBagMI355 (max pooling), AdamBatchedEmbeddingBagMI355 (lazy Adam
+                     fused into the backward)
   quantized_bag.py   QuantizedBatchedEmbeddingBagMI355 / QuantizedEmbeddingBagMI355 / QuantizedEmbeddingMI355: pooled and un-pooled
                      lookups over 8- / 4-bit row-quantised tables
   float8_bag.py      Float8BatchedEmbeddingBagMI355 / Float8EmbeddingBagMI355 / Float8EmbeddingMI355: pooled and un-pooled lookups
@@ -21,6 +22,7 @@ Layout (only what the hot path needs):
 """
 from ._lib import LIB_PATH, ParamAmdError, load as load_library, set_backward_tuning, set_forward_tuning, set_hybrid_min_tiles, set_hybrid_rest, set_hybrid_tuning, set_sort_tuning, set_tuning  # noqa: F401
 from .embedding_bag import (  # noqa: F401
+    AdamBatchedEmbeddingBagMI355,
     BatchedEmbeddingBagMI355,
     EmbeddingBagMI355,
     EmbeddingMI355,

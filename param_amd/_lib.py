@@ -123,6 +123,8 @@ EXPORTED_SYMBOLS = (
     "pm_sparse_rows_adam",
     "pm_sparse_rows_adagrad",
     "pm_sparse_rows_sgd",
+    "pm_embbag_bwd_adam_workspace",
+    "pm_embbag_bwd_adam",
 )
 # table element types of the FP8 lookups alone (include/param_amd.h, FP8 TABLES): every other entry point refuses them
 PM_F8E4M3, PM_F8E5M2 = 3, 4
@@ -368,6 +370,10 @@ def _open(path: str, alternates: bool) -> ctypes.CDLL:
     L.pm_embbag_max_grad.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, vp, vp, i64, vp]
     # ... its direct backward: (op, max_rows) and (op, grad, grad dtype, max_indices, dst_tables, dst dtype, alpha, max_rows, workspace,
     # workspace_bytes, stream)
+    L.pm_embbag_bwd_adam_workspace.restype = ctypes.c_int64
+    L.pm_embbag_bwd_adam_workspace.argtypes = [ctypes.POINTER(pm_embbag_batch), i64]
+    L.pm_embbag_bwd_adam.restype = ctypes.c_int
+    L.pm_embbag_bwd_adam.argtypes = [ctypes.POINTER(pm_embbag_batch), vp, i32, vp, i32, vp, vp, vp, ctypes.POINTER(pm_sparse_adam), i64, vp, i64, vp]
     L.pm_embbag_max_bwd_workspace.restype = ctypes.c_int64
     L.pm_embbag_max_bwd_workspace.argtypes = [ctypes.POINTER(pm_embbag_batch), i64]
     L.pm_embbag_max_bwd.restype = ctypes.c_int

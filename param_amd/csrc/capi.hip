@@ -1814,6 +1814,64 @@ int pm_embbag_max_bwd(const pm_embbag_batch* op, const void* grad, int32_t grad_
     return PM_OK;
 }
 
+// ---- lazy Adam fused into the backward (embbag_bwd_adam.hip) ----------------------------------------------------------------------------
+// The workspace is the sorted backward's followed by the hot-run list and the piece partials.
+// what both calls refuse of the request: pm_embbag_max_bwd's refusals, and more than 1024 tables in either library
+static int adam_bwd_request(const pm_embbag_batch* op, int32_t table_dtype, int32_t grad_dtype, int64_t max_rows, pm::KParams& p) {
+    int rc = make_params(op, table_dtype, p);
+    if (rc != PM_OK) return rc;
+    if ((rc = blocked_refused(op, Subject{"pm_embbag_bwd_adam", "does"})) != PM_OK) return rc;
+    if (op->per_sample_weights) return fail(PM_ERR_UNSUPPORTED, "pm_embbag_bwd_adam is unweighted: per_sample_weights must be NULL");
+    if (!dtype_is_weight(grad_dtype)) return fail(PM_ERR_INVALID, "grad_dtype must be PM_F32, PM_BF16 or PM_F16");
+    if ((rc = sorted_args_ok(op, max_rows)) != PM_OK) return rc;
+    if (op->num_tables > pm::kSegSortMaxTables) return fail(PM_ERR_UNSUPPORTED, "pm_embbag_bwd_adam: at most 1024 tables per request");
+    return PM_OK;
+}
+
+static int adam_bwd_bytes(const pm_embbag_batch* op, int64_t max_rows, const pm::KParams& p, size_t& sorted, size_t& total) {
+    const int rc = sorted_bytes("pm_embbag_bwd_adam_workspace", op, max_rows, false, p, sorted, total);
+    if (rc != PM_OK) return rc;
+    sorted = (sorted + 255) / 256 * 256;
+    total = sorted + pm::adam_bwd_extra_bytes(p.N, op->max_dim);
+    return PM_OK;
+}
+
+int64_t pm_embbag_bwd_adam_workspace(const pm_embbag_batch* op, int64_t max_rows) {
+    pm::KParams p;
+    size_t sorted = 0, total = 0;
+    int rc = adam_bwd_request(op, op ? op->weight_dtype : -1, PM_F32, max_rows, p);
+    if (rc != PM_OK || (rc = adam_bwd_bytes(op, max_rows, p, sorted, total)) != PM_OK) return rc;
+    return static_cast<int64_t>(total);
+}
+
+int pm_embbag_bwd_adam(const pm_embbag_batch* op, const void* grad, int32_t grad_dtype, void* const* tables, int32_t table_dtype,
+                       float* const* exp_avg, float* const* exp_avg_sq, const int64_t* pad_rows, const pm_sparse_adam* opt,
+                       int64_t max_rows, void* workspace, int64_t workspace_bytes, pm_stream_t stream) {
+    pm::KParams p;
+    int rc = adam_bwd_request(op, table_dtype, grad_dtype, max_rows, p);
+    if (rc != PM_OK) return rc;
+    if (!opt) return fail(PM_ERR_INVALID, "pm_embbag_bwd_adam: opt is NULL");
+    for (const float x : {opt->c1, opt->c2, opt->eps, opt->step_size, opt->decay})
+        if (!std::isfinite(x)) return fail(PM_ERR_INVALID, "pm_embbag_bwd_adam: c1, c2, eps, step_size and decay must be finite");
+    if ((opt->maximize | opt->nontemporal) & ~1) return fail(PM_ERR_INVALID, "pm_embbag_bwd_adam: maximize / nontemporal must be 0 or 1");
+    if (p.N == 0 || p.bag_count == 0) return PM_OK;
+    if (!grad || !tables || !exp_avg || !exp_avg_sq) return fail(PM_ERR_INVALID, "grad / tables / exp_avg / exp_avg_sq is NULL");
+    if (reinterpret_cast<uintptr_t>(grad) % (grad_dtype == PM_F32 ? 16 : 8) != 0)
+        return fail(PM_ERR_INVALID, "grad must be 16-byte aligned (8-byte for a 16-bit grad_dtype)");
+    size_t sorted = 0, need = 0;
+    if ((rc = adam_bwd_bytes(op, max_rows, p, sorted, need)) != PM_OK) return rc;
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 16 != 0 || workspace_bytes < static_cast<int64_t>(need))
+        return fail(PM_ERR_INVALID, "workspace must be 16-byte aligned and hold " + std::to_string(need) + " bytes (pm_embbag_bwd_adam_workspace)");
+    // the complete one-phase key sort of the request: issued on its own, it never defers
+    if ((rc = sort_request(op, max_rows, 1, workspace, workspace_bytes, stream, false)) != PM_OK) return rc;
+    pm::MaxBwdPairs mp;
+    if ((rc = plan_fail(pm::max_bwd_pairs(p, max_rows, op->max_dim, workspace, mp), "")) != PM_OK) return rc;
+    const hipError_t h = pm::launch_adam_bwd(p, op->max_dim, mp, static_cast<char*>(workspace) + sorted, grad, grad_dtype, tables, table_dtype,
+                                             exp_avg, exp_avg_sq, pad_rows, opt, static_cast<hipStream_t>(stream));
+    if (h != hipSuccess) return hip_fail(h, "pm_embbag_bwd_adam launch");
+    return PM_OK;
+}
+
 // ---- lazy Adam over coalesced sparse gradients (sparse_rows_adam.hip) -------------------------------------------------------------------
 int pm_sparse_rows_adam(int32_t num_tables, int64_t num_rows, int32_t max_dim, void* const* tables, int32_t table_dtype,
                         const int64_t* const* row_ids, const float* const* values, float* const* exp_avg, float* const* exp_avg_sq,

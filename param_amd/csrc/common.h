@@ -551,6 +551,13 @@ size_t max_bwd_extra_bytes(int64_t n, int max_dim);   // behind the sorted backw
 hipError_t launch_max_bwd(const KParams& p, int max_dim, const MaxBwdPairs& mp, void* extra, const void* grad, int grad_dtype,
                           const int32_t* max_indices, int dst_dtype, float alpha, hipStream_t stream);
 
+// lazy Adam fused into the backward (embbag_bwd_adam.hip): the same pairs (max_bwd_pairs); tables / m / v: device arrays [T]; pad_rows:
+// device [T] (-1: none) or NULL; extra: adam_bwd_extra_bytes behind the sorted backward's workspace (hot-run list, piece partials)
+size_t adam_bwd_extra_bytes(int64_t n, int max_dim);
+hipError_t launch_adam_bwd(const KParams& p, int max_dim, const MaxBwdPairs& mp, void* extra, const void* grad, int grad_dtype,
+                           void* const* tables, int table_dtype, float* const* m, float* const* v, const int64_t* pad_rows,
+                           const pm_sparse_adam* opt, hipStream_t stream);
+
 // DLRM input redistribution (dlrm_regroup.hip)
 hipError_t launch_dlrm_regroup(const int64_t* lengths, const int64_t* indices, int W, int F, int64_t B,
                                int64_t* out_indices, int64_t* out_offsets, int64_t* scratch, hipStream_t stream);

@@ -21,7 +21,7 @@ from __future__ import annotations
 import ctypes
 import math
 import operator
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -2077,3 +2077,158 @@ class MaxBatchedEmbeddingBagMI355(BatchedEmbeddingBagMI355):
         if not (isinstance(pooling_mode, str) and pooling_mode.lower() == "max"):
             raise ValueError(f'MaxBatchedEmbeddingBagMI355 pools with max: pooling_mode must be the string "max", got {pooling_mode!r}')
         super().__init__(rows, dims, *args, **kw)
+
+
+_ADAM_REFUSED = ("AdamBatchedEmbeddingBagMI355 has one fused step, lazy Adam over unweighted pooled requests (optimizer_step_ and the "
+                 "fused .backward()): ")
+
+
+class AdamBatchedEmbeddingBagMI355(BatchedEmbeddingBagMI355):
+    """:class:`BatchedEmbeddingBagMI355` whose fused update is lazy Adam / AdamW (fbgemm ``OptimType.ADAM``): T tables in one slab,
+    the deterministic backward and the optimizer step in one call (``pm_embbag_bwd_adam``, csrc/embbag_bwd_adam.hip; rule in
+    include/param_amd.h, FUSED LAZY ADAM).  A class of its own because ``BatchedEmbeddingBagMI355(optimizer="adam")`` keeps raising
+    ValueError, as it always did.  The constructor's arguments are the parent's (``pooling_mode`` ``"sum"`` / ``"mean"``,
+    ``padding_idx``, ``output_dtype``, ``bounds_check_mode``, layouts ``"bd"`` / ``"tbd"``, fp32 / bf16 / fp16 tables) with Adam's
+    ``learning_rate``, ``betas``, ``eps`` and a DECOUPLED ``weight_decay`` (AdamW's, on the touched rows); ``optimizer``, if given, must
+    be the string ``"adam"``.
+
+    State: two flat fp32 buffers ``exp_avg`` / ``exp_avg_sq`` (``exp_avg_table(t)`` / ``exp_avg_sq_table(t)``: ``[rows_t, dims_t]``
+    views), always fp32, and an int64 buffer ``step``: ONE count for all tables (fbgemm's ``iter``), incremented once per
+    issued ``optimizer_step_`` (the scalars are computed from ``step + 1``; a refused call does not count) (in double precision, each rounded once to fp32, as optim.py does).
+
+    ``optimizer_step_(grad, indices, offsets, batch=None, bag_begin=0, bag_count=None)``: ``grad`` is ``[B, sum D]`` or ``[T, B, D]``,
+    fp32 or the module's 16-bit ``output_dtype``.  Every row looked up in the slice gets the summed gradient of its lookups (the pooled
+    sorted apply's summation: ``sparse_grad``'s value bit for bit for a row of at most 256 lookups) and one step of the sparse-row Adam
+    rule; a row without a lookup, and a table's ``padding_idx`` row, keep the bits of ``w``, ``exp_avg`` and ``exp_avg_sq``.  With
+    mean pooling the gradient is scaled first through the parent's scratch route; a 16-bit gradient under sum pooling is widened in the
+    kernel's loads.  ``forward(...).backward(g)`` with ``fused_update`` applies it.  No host synchronisation, no allocation that depends
+    on the request's contents.
+
+    ValueError, before anything is allocated or launched: ``per_sample_weights`` (``forward`` with grad enabled, ``optimizer_step_``),
+    ``adagrad_step_``, ``sequence_optimizer_step_`` and ``forward_sequence`` under autograd, ``layout="blocked"``,
+    ``stochastic_rounding=True``, a ``weight_decay_mode``, more than 1024 tables, dims that are not multiples of 4 (fp32) / 8 (16-bit)."""
+
+    def __init__(self, rows: Sequence[int], dims, *args, optimizer="adam", learning_rate: float = 1e-3,
+                 betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, **kw):
+        if optimizer != "adam":
+            raise ValueError(f'AdamBatchedEmbeddingBagMI355 steps with Adam: optimizer must be the string "adam", got {optimizer!r}')
+        if len(args) > 5:
+            raise TypeError("AdamBatchedEmbeddingBagMI355: pass the arguments after seed by keyword")
+        names = ("dtype", "device", "layout", "init", "seed")
+        given = dict(zip(names, args), **kw)
+        if given.get("layout", "bd") == "blocked":
+            raise ValueError(_ADAM_REFUSED + 'layout="blocked" is not taken')
+        if given.get("stochastic_rounding", False):
+            raise ValueError(_ADAM_REFUSED + "stochastic_rounding is not taken")
+        if given.get("weight_decay_mode") is not None:
+            raise ValueError(_ADAM_REFUSED + "weight_decay is decoupled (AdamW's); weight_decay_mode is not taken")
+        n_tables = len(list(rows))
+        if n_tables > _SORTED_MAX_TABLES:
+            raise ValueError(_ADAM_REFUSED + f"at most {_SORTED_MAX_TABLES} tables (got {n_tables})")
+        vec = 4 if given.get("dtype", torch.float32) == torch.float32 else 8
+        if any(int(d) < vec or int(d) % vec for d in ([dims] if isinstance(dims, int) else dims)):
+            raise ValueError(_ADAM_REFUSED + f"every dim must be a positive multiple of {vec} for this table dtype")
+        if not 0.0 < learning_rate:
+            raise ValueError(f"Invalid learning rate: {learning_rate}")
+        if not 0.0 < eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"Invalid beta parameters: {betas}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        super().__init__(rows, dims, *args, optimizer="sgd", learning_rate=learning_rate, eps=eps, weight_decay=weight_decay, **kw)
+        self.optimizer, self.betas = "adam", (float(betas[0]), float(betas[1]))
+        dev = self.weights.device
+        n = sum(self._sizes)
+        self.register_buffer("exp_avg", torch.zeros(n, dtype=torch.float32, device=dev))
+        self.register_buffer("exp_avg_sq", torch.zeros(n, dtype=torch.float32, device=dev))
+        self.register_buffer("step", torch.zeros((), dtype=torch.int64))      # on the host: reading it never synchronises
+        starts = [0]
+        for s in self._sizes[:-1]:
+            starts.append(starts[-1] + s)      # (a multiple of 4 floats: every row of the state stays 16-byte aligned)
+        self._adam_starts = starts
+        self._adam_base = None
+        self._adam_ptrs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+        self._step_seen = None
+
+    def _state_table(self, buf: torch.Tensor, t: int) -> torch.Tensor:
+        s = self._adam_starts[t]
+        return buf[s:s + self._sizes[t]].view(self.rows[t], self.dims[t])
+
+    def exp_avg_table(self, t: int) -> torch.Tensor:
+        """first-moment state of table t, fp32 ``[rows_t, dims_t]`` (a view)"""
+        return self._state_table(self.exp_avg, t)
+
+    def exp_avg_sq_table(self, t: int) -> torch.Tensor:
+        """second-moment state of table t, fp32 ``[rows_t, dims_t]`` (a view)"""
+        return self._state_table(self.exp_avg_sq, t)
+
+    def _state_ptrs(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """device pointer arrays [T] of the two state buffers (rebuilt when ``.to()`` or ``load_state_dict`` moved them)"""
+        base = (self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.exp_avg.device)
+        if self._adam_base != base:
+            dev = self.exp_avg.device
+            self._adam_ptrs = tuple(torch.tensor([b.data_ptr() + 4 * s for s in self._adam_starts], dtype=torch.int64, device=dev)
+                                    for b in (self.exp_avg, self.exp_avg_sq))
+            self._adam_base = base
+        return self._adam_ptrs
+
+    def _steps_done(self) -> int:
+        """the value of ``step``; the buffer is read only when something else wrote it (``load_state_dict``, ``.to()``)"""
+        key = (self.step.data_ptr(), self.step._version)
+        if self._step_seen is None or self._step_seen[0] != key:
+            self._step_seen = (key, int(self.step))
+        return self._step_seen[1]
+
+    def _count_step(self) -> None:
+        """``step += 1``, once the step has been issued: a call that is refused does not count"""
+        n = self._steps_done() + 1
+        self.step += 1
+        self._step_seen = ((self.step.data_ptr(), self.step._version), n)
+
+    def forward(self, indices, offsets, per_sample_weights=None, return_max_indices: bool = False):
+        if per_sample_weights is not None and self.fused_update and torch.is_grad_enabled():
+            raise ValueError(_ADAM_REFUSED + "per_sample_weights must be None")
+        return super().forward(indices, offsets, per_sample_weights, return_max_indices)
+
+    def adagrad_step_(self, *args, **kw):
+        raise ValueError(_ADAM_REFUSED + "adagrad_step_ is not taken")
+
+    def sequence_optimizer_step_(self, *args, **kw):
+        raise ValueError(_ADAM_REFUSED + "sequence_optimizer_step_ is not taken (sequence requests are left out)")
+
+    def forward_sequence(self, indices, offsets, batch: Optional[int] = None):
+        if self.fused_update and torch.is_grad_enabled():      # (its .backward() would be sequence_optimizer_step_: refused before the lookup)
+            raise ValueError(_ADAM_REFUSED + "forward_sequence under autograd is not taken; use lookup_sequence, or torch.no_grad()")
+        return super().forward_sequence(indices, offsets, batch)
+
+    def optimizer_step_(self, grad, indices, offsets, batch: Optional[int] = None, bag_begin=0, bag_count=None,
+                        per_sample_weights=None, presorted: bool = False):
+        """one fused backward + lazy Adam step over the bag slice (see the class); what ``.backward()`` applies when ``fused_update`` is on"""
+        if per_sample_weights is not None:
+            raise ValueError(_ADAM_REFUSED + "per_sample_weights must be None")
+        if presorted:
+            raise ValueError(_ADAM_REFUSED + "the key sort runs inside the call, presorted=True is not taken")
+        ts = self._tables()
+        B = self._batch(offsets, indices, batch)
+        grad = _check_grad(ts, grad, B, self._out16)
+        pad = self._pad_dev()
+        if self._mean:      # the parent's scratch route: the gradient of the sum forward, in fp32
+            grad = _grad_as_sum(ts, grad, indices, offsets, B, None, pad, True, bag_begin, bag_count, self._out16)
+        op = ts.request(indices, offsets, B, None, bag_begin, bag_count)
+        from .optim import _NONTEMPORAL, _step_scalars      # (optim.py imports this module)
+        opt = _step_scalars(self._steps_done() + 1, self.learning_rate, self.betas, self.eps, self.weight_decay, False, _NONTEMPORAL)
+        if not indices.numel():
+            self._count_step()      # an empty request is a step that touches no row
+            return
+        op.fixed_pooling = 0
+        m_ptrs, v_ptrs = self._state_ptrs()
+        L, max_rows = _lib.load(), max(ts.rows)
+        ws = _workspace(ts, op, max_rows, L.pm_embbag_bwd_adam_workspace)
+        _lib.check(L.pm_embbag_bwd_adam(ctypes.byref(op), grad.data_ptr(), _WDTYPE[grad.dtype], ts.d_ptrs.data_ptr(), _WDTYPE[ts.dtype],
+                                        m_ptrs.data_ptr(), v_ptrs.data_ptr(), None if pad is None else pad.data_ptr(), ctypes.byref(opt),
+                                        max_rows, ws.data_ptr(), ws.numel(), _stream_ptr()))
+        self._count_step()
+        # the call leaves the request's complete one-phase sort on the workspace and touches none of the sorted apply's control words:
+        # an inherited presorted=True apply of the same request may consume it
+        _sort_issued(ts, ws)
